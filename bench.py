@@ -2,6 +2,7 @@
 """Headline benchmark: (window x band) LTS solves/s.
 
     python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg2|cfg4|cfg5] [--shard bands|traces]
+                    [--full] [--dump-outputs DIR]
 
 A step is ONE WHOLE drop-in call — ``narrow_band_least_squares(...)`` exactly as example.py makes it
 (reference narrow_band_least_squares.py:8-127; SURVEY.md §8(d): "wall time of the whole call including
@@ -25,10 +26,21 @@ weak-scaling number under the same metric.  --shard traces (launcher only) gives
 trace and whole call (weak scaling, no collective).  torch.distributed (gloo) is used by THIS SCRIPT only for
 the barrier around the timed region and the max-over-ranks — the product path has no PyTorch in it.
 
-The JSON line carries ``roofline`` (dominant kernel = the int8-MFMA screening correlator; duration measured
-live with HIP events on the library's stream), ``roofline_hbm`` (the mandated HBM figure: algorithmic bytes /
-wall time), ``noise`` (the same call on an incoherent-noise trace: the screening work is data dependent),
-``cpu_baseline`` (the CPU oracle timed on this box's host cores: 1 core and all cores) and ``env``.
+A plain run sets up, warms up, times the K steps and prints the JSON line: ``value``, ``ms_per_step`` (one timed
+step), the spread of the timed steps, ``config`` and ``env``.  Everything that takes runs of its own is behind
+``--full``: ``ms_per_step_results_replaced``, ``kernel_only_ms`` / ``stage_ms`` / ``stage_ms_in_call``, ``roofline``
+(dominant kernel = the int8-MFMA screening correlator; duration measured live with HIP events on the library's
+stream), ``roofline_solve``, ``roofline_hbm`` (the mandated HBM figure: algorithmic bytes / wall time),
+``upload_ms`` / ``value_trace_resident``, ``noise`` (the same call on an incoherent-noise trace: the screening work
+is data dependent), ``independent_calls`` (launcher runs) and ``cpu_baseline`` (the CPU oracle timed on the host
+cores: 1 core and all cores).
+
+``--dump-outputs DIR`` writes what the last timed call returned as ``DIR/<name>.npy`` (float64; element numbers
+float32): the grids, ``t``, ``sig_tau``, ``num_compute``, the filter responses ``w`` / ``h`` with a trailing
+(real, imag) axis, and the dropped-element dictionary as ``stdict_keys`` (band number, window time),
+``stdict_elements`` (zero-padded element numbers), ``stdict_rows`` (entry indices) and ``stdict_size``.  At most
+64 MB in all: a larger dictionary is written as a fixed, seeded sample of its entries.  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -59,6 +71,54 @@ LABELS = {
     'cfg1': 'cfg-1: 6-element synthetic plane wave, 10 linear bands 0.5-5 Hz, OLS, 20 min @ 20 Hz',
     'cfg1b': 'cfg-1b: example.py parameters, 8-element synthetic, 8 log bands, cheby1, adaptive windows, OLS',
 }
+
+# names of the returned tuples' members, as --dump-outputs writes them
+NBLS_RETURNS = ('vel', 'baz', 'mdccm', 't', 'stdict', 'sig_tau', 'num_compute', 'w', 'h')
+LTSVA_RETURNS = ('vel', 'baz', 't', 'mdccm', 'stdict', 'sigma_tau', 'conf_int_vel', 'conf_int_baz')
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def stdict_arrays(stdict):
+    """A dropped-element dictionary as arrays, entries in insertion order ('size' apart): keys (n, 2) float64 =
+    (band number of the key's 'NN_' prefix, 0 without one; window time), elements (n, longest entry) float32 = the
+    1-based element numbers of the entry, zero-padded."""
+    items = [(k, v) for k, v in stdict.items() if k != 'size']
+    keys = np.zeros((len(items), 2))
+    elements = np.zeros((len(items), max([len(v) for _, v in items], default=0)), dtype=np.float32)
+    for i, (k, v) in enumerate(items):
+        band, _, tm = k.rpartition('_')
+        keys[i] = (int(band) if band else 0, float(tm))
+        elements[i, :len(v)] = v
+    return keys, elements
+
+
+def dump_outputs(path, names, out, budget=DUMP_BUDGET_BYTES):
+    """Write the members of a returned tuple as ``path/<name>.npy`` (see the module docstring), at most ``budget`` bytes
+    of array data: a dictionary that does not fit is cut to a sample of its entries (seed 0, kept in entry order)."""
+    arrays, dicts = {}, {}
+    for name, v in zip(names, out):
+        if v is None:
+            continue
+        if isinstance(v, dict):
+            dicts[name] = v
+            continue
+        a = np.asarray(v)
+        arrays[name] = np.stack([a.real, a.imag], axis=-1) if np.iscomplexobj(a) else a.astype(np.float64)
+    room = budget - sum(a.nbytes for a in arrays.values())
+    if room < 0:
+        raise ValueError('--dump-outputs: the arrays alone are %d bytes, more than %d' % (budget - room, budget))
+    for name, d in dicts.items():
+        keys, elements = stdict_arrays(d)
+        rows = np.arange(len(keys))
+        keep = max(0, (room - 8) // (keys.itemsize * 3 + elements.itemsize * elements.shape[1]))
+        if keep < len(rows):
+            rows = np.sort(np.random.default_rng(0).choice(len(rows), size=keep, replace=False))
+        arrays.update({name + '_keys': keys[rows], name + '_elements': elements[rows], name + '_rows': rows.astype(np.float64),
+                       name + '_size': np.array([float(d.get('size', 0))])})
+        room -= sum(arrays[name + s].nbytes for s in ('_keys', '_elements', '_rows', '_size'))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def cpu_model():
@@ -149,6 +209,8 @@ def ltsva_entry(args):
         held.append(out)
     h.sync()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, LTSVA_RETURNS, out)
     n = len(out[0])
     line = {'metric': '(window x band) LTS solves/sec, 8-element synthetic', 'entry': 'ltsva (broadband filter_data -> ltsva, example.py:108-109)',
             'value': n * args.steps / el, 'unit': 'solves/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
@@ -179,8 +241,8 @@ def main():
                     help='"k/n": run only the k-th of n band shares of the config (default 0/8 for cfg4, all bands otherwise)')
     ap.add_argument('--scale', type=float, default=1.0, help='shorten the trace (debug only; invalidates the metric)')
     ap.add_argument('--independent-calls', choices=['auto', 'on', 'off'], default='auto',
-                    help='after the main measurement, time one whole single-GPU call per rank on the rank\'s own trace '
-                         '(no collective; extra field `independent_calls`).  auto: in band-sharded runs under a launcher')
+                    help='--full: after the main measurement, time one whole single-GPU call per rank on the rank\'s own trace '
+                         '(no collective; extra field `independent_calls`).  auto: in band-sharded --full runs under a launcher')
     ap.add_argument('--entry', default='nbls', choices=['nbls', 'ltsva'],
                     help='nbls (default): the narrow-band call of the metric.  ltsva: the broadband route of example.py:108-109 — '
                          'filter_data(st, ...) then ltsva(stf, ...) over the configuration\'s trace (one band, WINLEN = 50 s), '
@@ -188,8 +250,14 @@ def main():
     ap.add_argument('--transport-lib', default=None,
                     help='REHEARSAL ONLY (one-GPU box): a library with RCCL\'s ten entry points to use instead of RCCL, several '
                          'ranks on one device (tests/c_caller/loopback_rccl.cpp); the numbers of such a run mean nothing')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-noise', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out the CPU baseline')
+    ap.add_argument('--no-noise', action='store_true', help='--full: leave out the incoherent-noise leg')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also measure what takes runs of its own: kernel-only and in-call stage '
+                         'times, rooflines, the resident-trace and results-replaced calls, the noise leg, independent calls '
+                         '(launcher runs) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed call returned to DIR/<name>.npy (float32/float64, at most 64 MB)')
     args = ap.parse_args()
 
     if args.transport_lib:
@@ -400,6 +468,50 @@ def main():
         give_up(failure + '; not measured (no fallback to --shard traces: that is a different, weak-scaling measurement)')
     elapsed, out = timed(st, args.steps)
     steps_ms = sorted(step_times)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, NBLS_RETURNS, out)
+    nwin_list = out[6]
+    units_call = int(sum(nwin_list))
+    total_units = units_call * (ngpu if shard_traces else 1)
+    value = total_units * args.steps / elapsed
+    ms_step = elapsed / args.steps * 1e3
+    P = nchans * (nchans - 1) // 2
+    Wb = np.array([int(wl * fs) for wl in winlens], dtype=np.float64)
+
+    line = None
+    if rank == 0:
+        line = {
+            'metric': '(window x band) LTS solves/sec, 8-element synthetic', 'value': value, 'unit': 'solves/s',
+            'n_gpus': ngpu, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_step,
+            'ms_per_step_min_median_max': [steps_ms[0], float(np.median(steps_ms)), steps_ms[-1]],
+            'value_median_step': total_units / (float(np.median(steps_ms)) * 1e-3),
+            'higher_is_better': True, 'scaling': 'weak' if (shard_traces or not multi) else 'strong',
+            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': LABELS.get(args.config, args.config) + ', %s s windows %d%% overlap, %s order %d%s'
+                                   % ('/'.join(sorted({str(w) for w in winlens}, key=float)), int(round(c['overlap'] * 100)), c['ftype'], c['order'],
+                                      ' zero-phase' if c['ftype'] == 'butter' else '')
+                                   + ('; band share %s (%d of %d bands)' % (share, nb, nb_all) if share else ''),
+                       'step': 'one whole narrow_band_least_squares%s() call: trace upload, filter design + plan, device pass, '
+                               'one D2H of grids + packed LTS weights, filter responses, stdict (%d entries)'
+                               % ('_parallel' if multi and not shard_traces else '', 0 if out[4] is None else len(out[4])),
+                       'units_per_call': units_call, 'bands': nb, 'elements': nchans, 'pairs': P,
+                       'window_samples': sorted({int(w) for w in Wb}),
+                       'parallelism': ('1 GPU' if not multi else
+                                       ('%d GPUs (%s), bands of one call sharded by cost, one RCCL gather in the library'
+                                        % (ngpu, 'one process drives all of them' if one_process else 'one process per GPU')
+                                        if not shard_traces else '%d GPUs, one independent trace and whole call per rank, no collective' % ngpu)),
+                       'scale': args.scale},
+            'env': {k: v for k, v in sorted(os.environ.items()) if k.startswith('NBLS_')},
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if td is not None:
+            td.barrier()
+            td.destroy_process_group()
+    if not args.full:
+        return finish()
 
     def replaced_ms(stream, steps):
         """The same calls in the loop form `out = narrow_band_least_squares(...)`: every call's result replaces the previous
@@ -440,16 +552,8 @@ def main():
         return {k: float(np.median([a_.get(k, 0.0) for a_ in acc])) for k in acc[0]} if acc else {}
     in_call = in_call_stage_ms(st) if (not multi and call_args is not None) else {}
     kern, stages = measure_kernels(st, max(3, args.steps // 2))
-    nwin_list = out[6]
-    units_call = int(sum(nwin_list))
-    total_units = units_call * (ngpu if shard_traces else 1)
-    value = total_units * args.steps / elapsed
-    ms_step = elapsed / args.steps * 1e3
 
-    line = None
     if rank == 0:
-        P = nchans * (nchans - 1) // 2
-        Wb = np.array([int(wl * fs) for wl in winlens], dtype=np.float64)
         incb = np.array([int(np.round((1 - c['overlap']) * w)) for w in Wb], dtype=np.float64)
         nw = np.array(nwin_list, dtype=np.float64)
         units_gpu = units_call if (not multi or shard_traces) else units_call / ngpu
@@ -477,28 +581,8 @@ def main():
             except Exception:
                 traffic = None
         launches = int(stages[-1]['xcorr_launches'])
-        line = {
-            'metric': '(window x band) LTS solves/sec, 8-element synthetic', 'value': value, 'unit': 'solves/s',
-            'n_gpus': ngpu, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_step,
-            'ms_per_step_min_median_max': [steps_ms[0], float(np.median(steps_ms)), steps_ms[-1]],
+        line.update({
             'ms_per_step_results_replaced': ms_replaced,      # each call's result replaces the previous one INSIDE the timed loop (its teardown counted)
-            'value_median_step': total_units / (float(np.median(steps_ms)) * 1e-3),
-            'higher_is_better': True, 'scaling': 'weak' if (shard_traces or not multi) else 'strong',
-            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': LABELS.get(args.config, args.config) + ', %s s windows %d%% overlap, %s order %d%s'
-                                   % ('/'.join(sorted({str(w) for w in winlens}, key=float)), int(round(c['overlap'] * 100)), c['ftype'], c['order'],
-                                      ' zero-phase' if c['ftype'] == 'butter' else '')
-                                   + ('; band share %s (%d of %d bands)' % (share, nb, nb_all) if share else ''),
-                       'step': 'one whole narrow_band_least_squares%s() call: trace upload, filter design + plan, device pass, '
-                               'one D2H of grids + packed LTS weights, filter responses, stdict (%d entries)'
-                               % ('_parallel' if multi and not shard_traces else '', 0 if out[4] is None else len(out[4])),
-                       'units_per_call': units_call, 'bands': nb, 'elements': nchans, 'pairs': P,
-                       'window_samples': sorted({int(w) for w in Wb}),
-                       'parallelism': ('1 GPU' if not multi else
-                                       ('%d GPUs (%s), bands of one call sharded by cost, one RCCL gather in the library'
-                                        % (ngpu, 'one process drives all of them' if one_process else 'one process per GPU')
-                                        if not shard_traces else '%d GPUs, one independent trace and whole call per rank, no collective' % ngpu)),
-                       'scale': args.scale},
             'kernel_only_ms': kernel_only,
             'kernel_only_value': units_gpu / (kernel_only * 1e-3) * (ngpu if multi else 1),
             'stage_ms_in_call': {k.replace('_ms', ''): v for k, v in in_call.items()} or None,
@@ -530,8 +614,7 @@ def main():
                              'frac_kernel_only': bytes_total * share_f / (kernel_only * 1e-3) / 1e9 / HBM_PEAK_GBS,
                              'bytes_per_call': bytes_total,
                              'note': 'SURVEY 8(d): algorithmic bytes (8*N*inc + 40 + ceil(P/8) per unit) / wall time of the whole call'},
-            'env': {k: v for k, v in sorted(os.environ.items()) if k.startswith('NBLS_')},
-        }
+        })
     # what the upload of the trace costs inside a call (host-blocking copy from the stream's buffers)
     rows_up = engine.stream_rows(st)[0]
     t_up = time.perf_counter()
@@ -609,13 +692,9 @@ def main():
                     'n_gpus': ngpu, 'steps': args.steps, 'scaling': 'weak',
                     'what': 'one whole narrow_band_least_squares() call per rank on the rank\'s own synthetic trace of the same '
                             'configuration, barrier + max over ranks around the %d calls, no collective in the timed region' % args.steps}
-    if rank == 0:
-        if not args.no_cpu_baseline and ngpu == 1:
-            line['cpu_baseline'] = cpu_baseline(c, edges, winlens)
-        print(json.dumps(line), flush=True)
-    if td is not None:
-        td.barrier()
-        td.destroy_process_group()
+    if rank == 0 and not args.no_cpu_baseline and ngpu == 1:
+        line['cpu_baseline'] = cpu_baseline(c, edges, winlens)
+    finish()
 
 
 if __name__ == '__main__':

@@ -876,7 +876,7 @@ def test_bench_drives_two_ranks_without_a_launcher_over_the_loopback_transport()
     root, env = _loopback_env()
     env['NBLS_DEVICES'] = '0,0'
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--config', 'cfg2', '--steps', '2', '--warmup', '1',
-           '--no-cpu-baseline', '--no-noise', '--transport-lib', env['NBLS_TEST_TRANSPORT']]
+           '--full', '--no-cpu-baseline', '--no-noise', '--transport-lib', env['NBLS_TEST_TRANSPORT']]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -924,7 +924,7 @@ def test_bench_under_the_launcher_with_two_ranks_over_the_loopback_transport():
     root, env = _loopback_env()
     env['NBLS_DEVICE'] = '0'
     r = _launch_two_ranks([os.path.join(root, 'bench.py'), '--gpus', '2', '--config', 'cfg2', '--steps', '2', '--warmup', '1',
-                           '--no-noise', '--transport-lib', env['NBLS_TEST_TRANSPORT']], env, 29743)
+                           '--full', '--no-noise', '--transport-lib', env['NBLS_TEST_TRANSPORT']], env, 29743)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -933,6 +933,47 @@ def test_bench_under_the_launcher_with_two_ranks_over_the_loopback_transport():
     assert 'one process per GPU' in line['config']['parallelism']
     ind = line['independent_calls']
     assert ind['scaling'] == 'weak' and ind['n_gpus'] == 2 and ind['value'] > 0
+
+
+def test_plain_bench_run_is_lean_and_dumps_what_its_last_call_returned(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: ONE JSON line with the headline fields and none of
+    the measurements that take runs of their own; `--dump-outputs DIR` holds what the last timed call returned — the
+    same as that call made here on the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / 'out'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--config', 'cfg2', '--steps', '3',
+                        '--warmup', '1', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0 and line['n_gpus'] == 1
+    assert line['unit'] == 'solves/s' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+    assert not {'kernel_only_ms', 'stage_ms', 'roofline', 'roofline_hbm', 'noise', 'cpu_baseline', 'value_trace_resident',
+                'ms_per_step_results_replaced'} & set(line)
+
+    c = synthetic.build_config('cfg2', trace_seed=synthetic.SEED + 1)
+    nb = c['NBANDS']
+    fr = np.logspace(np.log10(0.01), np.log10(c['fs'] / 2), 1000)
+    wd = np.zeros(len(fr))
+    exp = narrow_band_least_squares(c['WINLEN_list'], c['overlap'], c['alpha'], c['st'], None, None, nb, wd, wd,
+                                    c['freqlist'][:nb + 1], c['band_type'], fr, c['ftype'], c['order'], c['ripple'], rij=c['rij'])
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for i, name in enumerate(('vel', 'baz', 'mdccm', 't')):
+        np.testing.assert_allclose(got[name], exp[i], rtol=RTOL)
+    np.testing.assert_array_equal(got['num_compute'], exp[6])
+    np.testing.assert_array_equal(got['w'][..., 0] + 1j * got['w'][..., 1], exp[7])
+    assert len(got['stdict_keys']) == len(exp[4]) - 1 and got['stdict_size'][0] == exp[4]['size']
+    for (band, tm), el, (key, v) in zip(got['stdict_keys'], got['stdict_elements'], [kv for kv in exp[4].items() if kv[0] != 'size']):
+        assert key == str(int(band)).zfill(2) + '_' + repr(float(tm))
+        np.testing.assert_array_equal(el[:len(v)], v)
+        assert not el[len(v):].any()
 
 
 @pytest.mark.parametrize('alpha', [0.75, 1.0])

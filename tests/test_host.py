@@ -488,6 +488,68 @@ def test_bench_refuses_what_it_cannot_measure():
         assert line['value'] is None and line['status'] == 'failed' and line['n_gpus'] == int(extra[1]) and line['note']
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('nbls_bench', os.path.join(ROOT, 'bench.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """`bench.py --dump-outputs DIR`: every member of the returned tuple as DIR/<name>.npy in float64 (element numbers
+    float32) — complex responses with a trailing (real, imag) axis, the dropped-element dictionary as key / element / row
+    arrays in entry order — and a dictionary that does not fit the budget as the same seeded sample of its entries."""
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    stdict, want_keys = {}, []
+    for i in range(40):
+        band, tm = 98 + i // 10, 17884.0 + i / 7.0          # prefixes '98_' ... '101_' (three characters past 99 bands)
+        stdict[str(band).zfill(2) + '_' + repr(tm)] = np.arange(1, 2 + i % 5)
+        want_keys.append((band, tm))
+        if i == 9:
+            stdict['size'] = 8                                # 'size' sits after the first band's entries
+    grid = rng.standard_normal((4, 10))
+    resp = rng.standard_normal((4, 6)) + 1j * rng.standard_normal((4, 6))
+    out = (grid, grid + 1, grid + 2, grid + 3, stdict, np.zeros((4, 10)), [10, 9, 8, 7], resp, resp.conj())
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    bench.dump_outputs(str(tmp_path / 'whole'), bench.NBLS_RETURNS, out)
+    whole = load(str(tmp_path / 'whole'))
+    assert set(whole) == {'vel', 'baz', 'mdccm', 't', 'sig_tau', 'num_compute', 'w', 'h',
+                          'stdict_keys', 'stdict_elements', 'stdict_rows', 'stdict_size'}
+    assert all(a.dtype in (np.float32, np.float64) for a in whole.values())
+    np.testing.assert_array_equal(whole['vel'], grid)
+    np.testing.assert_array_equal(whole['t'], grid + 3)
+    np.testing.assert_array_equal(whole['num_compute'], [10, 9, 8, 7])
+    np.testing.assert_array_equal(whole['w'][..., 0] + 1j * whole['w'][..., 1], resp)
+    np.testing.assert_array_equal(whole['h'][..., 0] + 1j * whole['h'][..., 1], resp.conj())
+    np.testing.assert_array_equal(whole['stdict_keys'], np.array(want_keys))
+    np.testing.assert_array_equal(whole['stdict_rows'], np.arange(40))
+    assert whole['stdict_size'].tolist() == [8.0]
+    for i in range(40):
+        np.testing.assert_array_equal(whole['stdict_elements'][i], np.r_[np.arange(1, 2 + i % 5), np.zeros(4 - i % 5)])
+
+    # a budget that leaves room for 10 of the 40 entries: the same sorted, seeded sample on every run
+    fixed = sum(whole[k].nbytes for k in ('vel', 'baz', 'mdccm', 't', 'sig_tau', 'num_compute', 'w', 'h'))
+    budget = fixed + 8 + 10 * (3 * 8 + 5 * 4)
+    parts = []
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), bench.NBLS_RETURNS, out, budget=budget)
+        parts.append(load(str(tmp_path / run)))
+        assert sum(a.nbytes for a in parts[-1].values()) <= budget
+    rows = parts[0]['stdict_rows'].astype(int)
+    assert len(rows) == 10 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(parts[1]['stdict_rows'], parts[0]['stdict_rows'])
+    np.testing.assert_array_equal(parts[0]['stdict_keys'], whole['stdict_keys'][rows])
+    np.testing.assert_array_equal(parts[0]['stdict_elements'], whole['stdict_elements'][rows])
+
+    # an OLS call returns no dictionary: nothing is written for it
+    bench.dump_outputs(str(tmp_path / 'ols'), bench.NBLS_RETURNS, out[:4] + (None,) + out[5:])
+    assert not any(f.startswith('stdict') for f in os.listdir(tmp_path / 'ols'))
+
+
 def test_generated_screen_kloop_is_current():
     """csrc/screen_kloop.inc (the hand-scheduled K loop of the screening kernel) is what its generator prints, and
     its schedule keeps the invariants the kernel relies on: every accumulator is written by exactly the products of

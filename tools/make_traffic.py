@@ -49,7 +49,7 @@ def main():
           'all_kernels_hbm_bytes_per_pass': sum(2.0 * fetch.get(k, 0.0) + write.get(k, 0.0) for k in per_kernel) / passes,
           'xcorr_hbm_bytes_per_launch': (2.0 * fetch.get(dom, 0.0) + write.get(dom, 0.0)) / max(1, nf.get(dom, 1)),
           'all_kernels_hbm_bytes_total': sum(2.0 * fetch.get(k, 0.0) + write.get(k, 0.0) for k in per_kernel),
-          'method': 'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python bench.py --steps 4 --warmup 1 '
+          'method': 'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python bench.py --full --steps 4 --warmup 1 '
                     '--no-cpu-baseline --no-noise` (with --kernel-trace only); counter values are KiB; FETCH_SIZE doubled per '
                     'MI355X_MICROARCH.md (gfx950 reports half of a wide 16-B/lane coalesced stream); per PASS = the sum over all '
                     'launches of the kernel / the number of device passes in the run (one forward filter-state kernel per pass); '

@@ -6,15 +6,15 @@ TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT
-BENCH="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-noise"
+BENCH="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-noise"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- $BENCH > $OUT/fetch.log 2>&1 || exit 3
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- $BENCH > $OUT/write.log 2>&1 || exit 4
 python tools/make_traffic.py $TAG $OUT --traffic-only || exit 5
 python bench.py --entry ltsva --steps 10 --warmup 3 > $OUT/${TAG}_bench_ltsva_cfg3.json 2> $OUT/bench_ltsva.err || exit 6
-python bench.py --config cfg1b --steps 20 --warmup 3 --no-noise > $OUT/${TAG}_bench_cfg1b.json 2> $OUT/bench_cfg1b.err || exit 7
+python bench.py --full --config cfg1b --steps 20 --warmup 3 --no-noise > $OUT/${TAG}_bench_cfg1b.json 2> $OUT/bench_cfg1b.err || exit 7
 for CFG in cfg3 cfg2 cfg5 cfg4; do
-  python bench.py --config $CFG --steps 6 --warmup 2 > $OUT/${TAG}_bench_$CFG.json 2> $OUT/bench_$CFG.err || exit 1
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$CFG -- python bench.py --config $CFG --steps 4 --warmup 1 --no-cpu-baseline --no-noise > $OUT/stats_$CFG.log 2>&1 || exit 2
+  python bench.py --full --config $CFG --steps 6 --warmup 2 > $OUT/${TAG}_bench_$CFG.json 2> $OUT/bench_$CFG.err || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$CFG -- python bench.py --full --config $CFG --steps 4 --warmup 1 --no-cpu-baseline --no-noise > $OUT/stats_$CFG.log 2>&1 || exit 2
   cp $OUT/stats_$CFG/*/*kernel_stats.csv $OUT/${TAG}_bench_${CFG}_kernel_stats.csv
   echo "$CFG done: $(tail -c 300 $OUT/${TAG}_bench_$CFG.json | head -c 10)"
 done
