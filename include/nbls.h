@@ -146,6 +146,17 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
               int32_t taper_len, const int32_t* winlen, const int32_t* wininc,
               int32_t vector_len, const nbls_lts_params* lts, int32_t xcorr_impl);
 
+/* Several recordings of ONE array in one pass: the trace's nchans rows are nseg consecutive blocks of
+ * E = nchans / nseg rows, block s = recording s (same element order, npts and fs for all).  The geometry
+ * describes one array of E elements.  The next nbls_plan with B bands gives B*nseg result rows, row
+ * r = b*nseg + s (band-major): nbls_fetch, nbls_fetch_packed, nbls_result_layout, nbls_fetch_uncertainty and the
+ * streamed result batches all describe B*nseg rows; nbls_fetch_filtered still takes a band b < B and returns all
+ * nchans trace rows.  nseg = 1 (the default) is the one-recording behaviour.  At plan time: NBLS_ERR_ARG if
+ * nchans % nseg != 0, NBLS_ERR_GEOMETRY if E is outside 3..32 (or below 4 under LTS), NBLS_ERR_UNSUPPORTED
+ * together with nbls_set_window_ranges or an RCCL communicator (nbls_comm_*).  No kernel changes: the filter
+ * writes [B][nseg*E][npts] = [B*nseg][E][npts], which is what the correlators read for B*nseg rows of E elements. */
+int nbls_set_segments(nbls_handle* h, int32_t nseg);
+
 /* Window sharding (fewer bands than GPUs, or traces too long for one GPU's time
  * budget): restrict the NEXT plans to windows [first[b], first[b] + count[b]) of band b (count < 0 =
  * to the end).  The filter still runs over the whole trace (zero-phase filtering is not local in time),

@@ -22,6 +22,7 @@ EXPORTS = [
     'nbls_developer_build', 'nbls_set_trace_from', 'nbls_debug_lts_coop_breakdown', 'nbls_filter_segment',
     'nbls_set_filtered', 'nbls_load_result_block', 'nbls_stream_results', 'nbls_result_batches', 'nbls_wait_result_batch',
     'nbls_comm_set_library', 'nbls_set_uncertainty', 'nbls_fetch_uncertainty', 'nbls_expect_upload', 'nbls_abort_upload',
+    'nbls_set_segments',
 ]
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -117,6 +118,7 @@ def load_library(path=None):
     lib.nbls_probe_mfma_i8.argtypes = [vp, ip, ip, ip]
     lib.nbls_debug_screen_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.nbls_set_window_ranges.argtypes = [vp, C.c_int32, ip, ip]
+    lib.nbls_set_segments.argtypes = [vp, C.c_int32]
     lib.nbls_debug_screen_stamps.argtypes = [vp, dp]
     lib.nbls_debug_lts_stamps.argtypes = [vp, dp]
     lib.nbls_debug_lts_coop_breakdown.argtypes = [vp, dp]
@@ -157,6 +159,7 @@ class Handle:
         self.device_id = int(device_id)
         self.nchans = self.npts = self.npairs = 0
         self.nbands = self.vector_len = 0
+        self.nseg = 1
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -291,7 +294,8 @@ class Handle:
         self._chk(self.lib.nbls_plan(self._h, nb, sos_p, nsec, int(bool(zero_phase)), _dptr(tl), _dptr(tr),
                                      len(tl), _iptr(winlen), _iptr(wininc), int(vector_len), lp,
                                      int(xcorr_impl)))
-        self.nbands, self.vector_len = nb, int(vector_len)
+        self.nbands, self.vector_len = nb * self.nseg, int(vector_len)     # result rows: band-major, nseg per band
+        self.fbands = nb
         self._nsec = nsec
 
     def set_option(self, key, value):
@@ -308,6 +312,12 @@ class Handle:
         sends from.  ``block``: contiguous uint8 array in the layout of ``nbls_result_layout`` for all of the rank's bands."""
         block = np.ascontiguousarray(block, dtype=np.uint8)
         self._chk(self.lib.nbls_load_result_block(self._h, block.ctypes.data, block.nbytes))
+
+    def set_segments(self, nseg):
+        """The next plans treat the trace's rows as ``nseg`` recordings of one array (``nbls_set_segments``): nseg
+        consecutive blocks of nchans / nseg rows; a plan of B bands then gives B * nseg result rows, row b * nseg + s."""
+        self._chk(self.lib.nbls_set_segments(self._h, int(nseg)))
+        self.nseg = int(nseg)
 
     def set_window_ranges(self, first=None, count=None):
         """Per-band window slices for the next plan(s); None resets to "all windows"."""
@@ -405,7 +415,7 @@ class Handle:
         """One causal filter pass over the resident segment continuing from ``state_in`` (nbands, nchans, 2*nsections)
         -> the state leaving the segment (or None).  See ``nbls_filter_segment``."""
         si = None if state_in is None else _f64(state_in)
-        so = np.empty((self.nbands, self.nchans, 2 * self._nsec)) if want_state else None
+        so = np.empty((self.fbands, self.nchans, 2 * self._nsec)) if want_state else None
         self._chk(self.lib.nbls_filter_segment(self._h, int(bool(reverse)), _dptr(si), _dptr(so)))
         return so
 

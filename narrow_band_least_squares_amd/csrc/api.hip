@@ -371,6 +371,18 @@ void nbls_destroy(nbls_handle* h) {
     delete h;
 }
 
+// Array elements of a trace of `nchans` rows under the handle's segment count (nbls_set_segments; rows that do not
+// divide into the segments: nbls_plan refuses them).  A geometry of another array size is stale.
+static void set_elements(nbls_handle* h, int32_t nchans) {
+    const int E = h->nseg > 1 && nchans % h->nseg == 0 ? nchans / h->nseg : nchans;
+    if (h->nelem != E && h->d_xij) {
+        (void)hipFree(h->d_xij); h->d_xij = nullptr;
+        h->caps.erase((const void*)&h->d_xij);
+        h->npairs = 0;
+    }
+    h->nelem = E;
+}
+
 // Declare the trace: allocation and shape, no samples yet (h->trace_loaded = false).
 static int trace_shape_impl(nbls_handle* h, int32_t nchans, int64_t npts, double fs) {
     HIPCHK(h, hipSetDevice(h->device));
@@ -381,11 +393,7 @@ static int trace_shape_impl(nbls_handle* h, int32_t nchans, int64_t npts, double
         HIPCHK(h, hipMalloc((void**)&h->d_trace, need));
         h->cap_trace = need;
     }
-    if (h->nchans != nchans && h->d_xij) {      // a geometry of another array size is stale
-        (void)hipFree(h->d_xij); h->d_xij = nullptr;
-        h->caps.erase((const void*)&h->d_xij);
-        h->npairs = 0;
-    }
+    set_elements(h, nchans);
     h->nchans = nchans;
     h->npts = npts;
     h->npts_pad = pad;
@@ -527,11 +535,7 @@ int nbls_set_trace_from(nbls_handle* h, const nbls_handle* src) {
         if (!src->uev.empty() && (int)src->uev.size() >= src->nchans) HIPCHK(h, hipStreamWaitEvent(h->stream, src->uev[src->nchans - 1], 0));
     }
     HIPCHK(h, hipMemcpyAsync(h->d_trace, src->d_trace, need, hipMemcpyDeviceToDevice, h->stream));
-    if (h->nchans != src->nchans && h->d_xij) {
-        (void)hipFree(h->d_xij); h->d_xij = nullptr;
-        h->caps.erase((const void*)&h->d_xij);
-        h->npairs = 0;
-    }
+    set_elements(h, src->nchans);
     h->nchans = src->nchans;
     h->npts = src->npts;
     h->npts_pad = src->npts_pad;
@@ -586,6 +590,15 @@ int nbls_set_geometry(nbls_handle* h, const double* xij, const int32_t* pair_idx
     return NBLS_OK;
 }
 
+int nbls_set_segments(nbls_handle* h, int32_t nseg) {
+    if (!h) return NBLS_ERR_ARG;
+    if (nseg < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_segments: nseg must be at least 1");
+    h->nseg = nseg;
+    if (h->d_trace) set_elements(h, h->nchans);
+    h->planned = false;                      // (consumed by the next nbls_plan)
+    return NBLS_OK;
+}
+
 int nbls_set_window_ranges(nbls_handle* h, int32_t nbands, const int32_t* first, const int32_t* count) {
     if (!h) return NBLS_ERR_ARG;
     // consumed by the NEXT nbls_plan; an existing plan keeps the ranges it was made with
@@ -614,13 +627,27 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: 0..8 second-order sections supported");
     if (taper_len < 0 || 2 * (int64_t)taper_len > h->npts || (taper_len > 0 && (!taper_left || !taper_right)))
         return fail(h, NBLS_ERR_ARG, "nbls_plan: bad taper");
+    // several recordings of one array (nbls_set_segments): nseg blocks of E rows, result row r = b * nseg + s
+    const int NS = h->nseg;
+    if (NS > 1) {
+        if (h->nchans % NS != 0)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->nchans) + " trace rows do not divide into " + std::to_string(NS) + " segments");
+        if (!h->win_first.empty())
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: window ranges (nbls_set_window_ranges) are not supported with several segments");
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the RCCL gather (nbls_comm_*) is not supported with several segments");
+    }
+    h->nelem = h->nchans / NS;
+    const int E = h->nelem;
+    if (NS > 1 && (E < 3 || E > 32))
+        return fail(h, NBLS_ERR_GEOMETRY, "nbls_plan: " + std::to_string(E) + " elements per segment (3..32 supported)");
     // geometry is optional for a filter-only plan (filter_data()); execute checks it
     const int P = h->d_xij ? h->npairs : 1;
-    if (h->d_xij && (int64_t)h->nchans * (h->nchans - 1) / 2 != P)
-        return fail(h, NBLS_ERR_ARG, "nbls_plan: geometry pair count does not match the trace channel count");
+    if (h->d_xij && (int64_t)E * (E - 1) / 2 != P)
+        return fail(h, NBLS_ERR_ARG, "nbls_plan: geometry pair count does not match the array's element count");
     if (lts) {
         if (!h->d_xij) return fail(h, NBLS_ERR_STATE, "nbls_plan: LTS needs the geometry");
-        if (h->nchans < 4) return fail(h, NBLS_ERR_GEOMETRY, "LTS needs at least 4 array elements");
+        if (E < 4) return fail(h, NBLS_ERR_GEOMETRY, "LTS needs at least 4 array elements");
         if (lts->nstarts < 1 || lts->nstarts > NBLS_MAX_STARTS || !lts->starts || !lts->rew_table)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: bad LTS starts");
         if (lts->h < 2 || lts->h > P) return fail(h, NBLS_ERR_ARG, "nbls_plan: LTS h out of range");
@@ -664,15 +691,18 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
     h->res_loaded = false;
     h->arena_mode = true;                                // alloc_copy: places in the arena, ONE upload at the end
 
-    h->W.assign(winlen, winlen + nbands);
-    h->inc.assign(wininc, wininc + nbands);
-    h->nwin.resize(nbands);
-    h->unit_off.resize(nbands + 1);
-    std::vector<int32_t> woff(nbands, 0);
+    // per result row (R = nbands * nseg, rows of one band consecutive): the filter tables above stay per band
+    const int R = nbands * NS;
+    h->W.resize(R);
+    h->inc.resize(R);
+    for (int r = 0; r < R; ++r) { h->W[r] = winlen[r / NS]; h->inc[r] = wininc[r / NS]; }
+    h->nwin.resize(R);
+    h->unit_off.resize(R + 1);
+    std::vector<int32_t> woff(R, 0);
     int64_t U = 0;
     int maxW = 0, uniW = nbands > 0 ? winlen[0] : 0;
-    for (int b = 0; b < nbands; ++b) {
-        const int W = winlen[b], inc = wininc[b];
+    for (int b = 0; b < R; ++b) {
+        const int W = h->W[b], inc = h->inc[b];
         if (W != uniW) uniW = 0;
         if (W < 2 || inc < 1)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: window length must be at least 2 samples, the hop at least 1");
@@ -681,7 +711,7 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         int64_t n = span > 0 ? (span + inc - 1) / inc : 0;
         if (n > vector_len) return fail(h, NBLS_ERR_ARG, "nbls_plan: vector_len smaller than a band's window count");
         int64_t first = 0;
-        if ((int)h->win_first.size() == nbands) {          // window sharding: this handle's slice of the band
+        if ((int)h->win_first.size() == R) {               // window sharding: this handle's slice of the band
             first = h->win_first[b] < n ? h->win_first[b] : n;
             int64_t cnt = h->win_count[b] < 0 ? n - first : h->win_count[b];
             if (cnt > n - first) cnt = n - first;
@@ -693,13 +723,14 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         U += n;
         if (W > maxW) maxW = W;
     }
-    h->unit_off[nbands] = (int32_t)U;
+    h->unit_off[R] = (int32_t)U;
     h->woff = woff;
     if (U > 0x7fffffffLL / (P > 0 ? P : 1)) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: too many (unit, pair) items for one launch");
     h->nunits = U;
     h->maxW = maxW;
     h->uniW = uniW;
-    h->nbands = nbands;
+    h->fbands = nbands;
+    h->nbands = R;
     h->nsections = nsections;
     h->zero_phase = zero_phase ? 1 : 0;
     h->taper_len = taper_len;
@@ -729,26 +760,26 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
             if (tn) { h->h_tl.assign(taper_left, taper_left + tn); h->h_tr.assign(taper_right, taper_right + tn); }
         }
     }
-    if ((rc = alloc_copy(h, &h->d_W, h->W.data(), (size_t)nbands))) return rc;
-    if ((rc = alloc_copy(h, &h->d_inc, h->inc.data(), (size_t)nbands))) return rc;
-    if ((rc = alloc_copy(h, &h->d_nwin, h->nwin.data(), (size_t)nbands))) return rc;
-    if ((rc = alloc_copy(h, &h->d_unit_off, h->unit_off.data(), (size_t)nbands + 1))) return rc;
-    if ((rc = alloc_copy(h, &h->d_win_off, woff.data(), (size_t)nbands))) return rc;
+    if ((rc = alloc_copy(h, &h->d_W, h->W.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, &h->d_inc, h->inc.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, &h->d_nwin, h->nwin.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, &h->d_unit_off, h->unit_off.data(), (size_t)R + 1))) return rc;
+    if ((rc = alloc_copy(h, &h->d_win_off, woff.data(), (size_t)R))) return rc;
     std::vector<int32_t>& ub = h->hp_ub;
     ub.resize((size_t)U);
-    for (int b = 0; b < nbands; ++b)
+    for (int b = 0; b < R; ++b)
         for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) ub[(size_t)u] = b;
     if ((rc = alloc_copy(h, &h->d_unit_band, ub.data(), (size_t)U))) return rc;
     {
         std::vector<int32_t>& uw = h->hp_uw;
         uw.resize((size_t)(U > 0 ? U : 1));
-        for (int b = 0; b < nbands; ++b)
+        for (int b = 0; b < R; ++b)
             for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) uw[(size_t)u] = (int32_t)(u - h->unit_off[b]) + woff[b];
         if ((rc = alloc_copy(h, &h->d_unit_win, uw.data(), (size_t)U))) return rc;
     }
 
     const auto tp2 = std::chrono::steady_clock::now();
-    const size_t nseries = (size_t)nbands * h->nchans;
+    const size_t nseries = (size_t)nbands * h->nchans;      // (= R * E)
     // + 64 bytes: the verifier's 16-byte copies of a window that starts on an odd sample read one sample past its end
     if ((rc = ensure(h, &h->d_filt, &h->cap_filt, nseries * h->npts_pad * sizeof(double) + 64))) return rc;
     if ((rc = ensure(h, &h->d_cstate, &h->cap_cstate, nseries * h->nchunks * D * sizeof(double)))) return rc;
@@ -772,7 +803,7 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
     if ((rc = ensure(h, &h->d_gin, &h->cap_gin, nseries * ngroups * D * sizeof(double)))) return rc;
     // results: every buffer has its own capacity; the views into the result block are recomputed by
     // every plan (a smaller plan after a bigger one keeps the allocation but must move the grid offsets)
-    const size_t cells = (size_t)nbands * vector_len;
+    const size_t cells = (size_t)R * vector_len;
     h->mask_bytes = (P + 7) / 8;
     h->res_bytes = cells * (4 * sizeof(double) + (size_t)h->mask_bytes);
     h->d_vel = h->d_baz = h->d_mdccm = h->d_sig = nullptr;
@@ -794,9 +825,9 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         h->wgroups.clear();
         int maxWP = 0;
         bool all_ok = true, any_ok = false;
-        for (int b = 0; b < nbands; ) {
+        for (int b = 0; b < R; ) {
             int e = b + 1;
-            while (e < nbands && h->W[e] == h->W[b]) ++e;
+            while (e < R && h->W[e] == h->W[b]) ++e;
             nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
             int S_, PFB_, CSB_, CSA_, WP_, nsl_, G_, NC_;
             size_t lds_;
@@ -818,7 +849,7 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         // unit batches small enough for the quantised windows to stay in the 256 MiB Infinity Cache (192 MB: measured
         // against 96 — the value of rounds 1-2 — and 384 at every BASELINE shape: 0.2-1.2 % of the pass, fewer launch tails)
         const int64_t batch_mb = h->opt.screen_batch_mb > 0 ? h->opt.screen_batch_mb : 192;
-        int64_t batch = (int64_t)(batch_mb << 20) / ((int64_t)h->nchans * 2 * WP_);
+        int64_t batch = (int64_t)(batch_mb << 20) / ((int64_t)E * 2 * WP_);
         if (batch < 64) batch = 64;
         if (batch > U) batch = U > 0 ? U : 1;
         // equal batches (a multiple of 8 units, the XCD grouping of the screening grid) instead of full ones plus a
@@ -829,12 +860,12 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
             if (eq < batch) batch = eq;
         }
         h->screen_batch = batch;
-        if ((rc = ensure(h, &h->d_qbuf, &h->cap_qbuf, (size_t)batch * h->nchans * 2 * WP_))) return rc;
-        if ((rc = ensure(h, &h->d_qmeta, &h->cap_qmeta, (size_t)batch * h->nchans * (10 + WP_ / 32) * sizeof(double)))) return rc;
+        if ((rc = ensure(h, &h->d_qbuf, &h->cap_qbuf, (size_t)batch * E * 2 * WP_))) return rc;
+        if ((rc = ensure(h, &h->d_qmeta, &h->cap_qmeta, (size_t)batch * E * (10 + WP_ / 32) * sizeof(double)))) return rc;
         if (h->opt.screen_stamps || h->opt.lts_stamps) {
-            if ((rc = ensure(h, &h->d_stamps, &h->cap_stamps, (size_t)(batch + 8) * h->nchans * ((h->nchans + 1) / 2) * 8 * sizeof(unsigned long long)))) return rc;   // one record per screening workgroup: (unit, sliding channel, partner group)
+            if ((rc = ensure(h, &h->d_stamps, &h->cap_stamps, (size_t)(batch + 8) * E * ((E + 1) / 2) * 8 * sizeof(unsigned long long)))) return rc;   // one record per screening workgroup: (unit, sliding channel, partner group)
         }
-        if ((rc = ensure(h, &h->d_cand, &h->cap_cand, (size_t)batch * h->nchans * h->nchans * 32 * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(h, &h->d_cand, &h->cap_cand, (size_t)batch * E * E * 32 * sizeof(int32_t)))) return rc;
     }
     h->lts = lts != nullptr;
     if (lts) {
@@ -1150,7 +1181,7 @@ int nbls_fetch_uncertainty(nbls_handle* h, double* vel_uncert, double* baz_uncer
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out) {
     if (!h || !out) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_filtered: no plan");
-    if (band < 0 || band >= h->nbands) return fail(h, NBLS_ERR_ARG, "nbls_fetch_filtered: band out of range");
+    if (band < 0 || band >= h->fbands) return fail(h, NBLS_ERR_ARG, "nbls_fetch_filtered: band out of range");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy2DAsync(out, h->npts * sizeof(double),
@@ -1163,7 +1194,7 @@ int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out) {
 int nbls_set_filtered(nbls_handle* h, int32_t band, const double* data) {
     if (!h || !data) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_set_filtered: no plan");
-    if (band < 0 || band >= h->nbands) return fail(h, NBLS_ERR_ARG, "nbls_set_filtered: band out of range");
+    if (band < 0 || band >= h->fbands) return fail(h, NBLS_ERR_ARG, "nbls_set_filtered: band out of range");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpy2DAsync(h->d_filt + (size_t)band * h->nchans * h->npts_pad, h->npts_pad * sizeof(double), data,
                                h->npts * sizeof(double), h->npts * sizeof(double), h->nchans, hipMemcpyHostToDevice, h->stream));
@@ -1182,7 +1213,7 @@ int nbls_filter_segment(nbls_handle* h, int32_t reverse, const double* state_in,
     HIPCHK(h, hipSetDevice(h->device));
     wait_uploads(h);
     h->work_queued = true;
-    const size_t n = (size_t)h->nbands * h->nchans * 2 * h->nsections;
+    const size_t n = (size_t)h->fbands * h->nchans * 2 * h->nsections;
     int rc;
     if ((rc = ensure(h, &h->d_seg_state, &h->cap_seg_state, 2 * n * sizeof(double)))) return rc;
     double* d_init = nullptr;
@@ -1365,7 +1396,7 @@ int nbls_debug_screen_stats(nbls_handle* h, int64_t* out4) {
     if (!h->d_cand || h->screen_batch <= 0) return fail(h, NBLS_ERR_STATE, "no screening run yet");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int N = h->nchans;
+    const int N = h->nelem;
     const int64_t last = h->last_batch > 0 ? h->last_batch : h->nunits - ((h->nunits - 1) / h->screen_batch) * h->screen_batch;
     std::vector<int32_t> c((size_t)last * N * N * 32);
     HIPCHK(h, copy_sync(h, c.data(), h->d_cand, c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1404,7 +1435,7 @@ int nbls_debug_screen_stamps(nbls_handle* h, double* out6) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int64_t last = h->last_batch > 0 ? h->last_batch : h->nunits - ((h->nunits - 1) / h->screen_batch) * h->screen_batch;
-    const int64_t nwg = ((last + 7) / 8) * 8 * h->nchans;   // upper bound (one or two channels per workgroup)
+    const int64_t nwg = ((last + 7) / 8) * 8 * h->nelem;   // upper bound (one or two channels per workgroup)
     std::vector<unsigned long long> st((size_t)nwg * 8);
     HIPCHK(h, copy_sync(h, st.data(), h->d_stamps, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int i = 0; i < 10; ++i) out6[i] = 0.0;

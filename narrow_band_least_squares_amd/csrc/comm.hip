@@ -211,6 +211,7 @@ int nbls_comm_gather(nbls_handle* const* hs, int32_t n, int32_t root, int64_t bl
     for (int i = 0; i < n; ++i) {
         nbls_handle* h = hs[i];
         if (!h->comm || h->comm_world != world) return cfail(h0, NBLS_ERR_STATE, "nbls_comm_gather: no communicator (nbls_comm_init_*)");
+        if (h->nseg > 1) return cfail(h0, NBLS_ERR_UNSUPPORTED, "nbls_comm_gather: not supported with several segments (nbls_set_segments)");
         if (root < 0 ? i == 0 : h->comm_rank == root) deliver = h;
     }
     int first_rc = NBLS_OK;                       // the first local failure: returned AFTER the collective

@@ -464,11 +464,11 @@ hipError_t run_pass(nbls_handle* h, const FilterArgs& a, bool states_ready) {
 template <int S>
 hipError_t run_filter(nbls_handle* h, int ch0, int nch) {
     FilterArgs a;
-    a.nchans = h->nchans;
-    a.nseries = h->nbands * h->nchans;
+    a.nchans = h->nchans;                  // trace rows (all segments): the filter's series are (band, row)
+    a.nseries = h->fbands * h->nchans;
     a.ch0 = ch0;
     a.nch = nch;
-    a.nsub = h->nbands * nch;
+    a.nsub = h->fbands * nch;
     a.npts = h->npts;
     a.nchunks = h->nchunks;
     a.ngroups = (int)((h->nchunks + G - 1) / G);
@@ -529,7 +529,7 @@ template <int S>
 hipError_t run_filter_segment(nbls_handle* h, int reverse, const double* d_init, double* d_fin) {
     FilterArgs a;
     a.nchans = h->nchans;
-    a.nseries = h->nbands * h->nchans;
+    a.nseries = h->fbands * h->nchans;
     a.ch0 = 0;
     a.nch = h->nchans;
     a.nsub = a.nseries;

@@ -97,7 +97,9 @@ struct nbls_handle {
     // ---- trace (HBM resident) ----
     double* d_trace = nullptr;     // [nchans][npts_pad]
     size_t cap_trace = 0;
-    int nchans = 0;
+    int nchans = 0;                // trace rows
+    int nseg = 1;                  // recordings in the trace (nbls_set_segments): nseg blocks of nelem consecutive rows
+    int nelem = 0;                 // array elements = nchans / nseg: what the correlators, the screening buffers and the geometry see
     int64_t npts = 0, npts_pad = 0;
     double fs = 0.0;
 
@@ -113,7 +115,11 @@ struct nbls_handle {
 
     // ---- plan ----
     bool planned = false;
+    int fbands = 0;                // filter bands of the plan (d_sos, d_M, d_fw; series of d_filt = fbands x nchans)
     int nbands = 0, nsections = 0, zero_phase = 0, taper_len = 0, vector_len = 0, xcorr_impl = 0;
+    // nbands = result rows = fbands * nseg, row r = band r / nseg of recording r % nseg: the window / unit tables, the
+    // result block and everything the correlators and solvers index are per row.  d_filt [fbands][nchans][npts_pad] is
+    // the layout [nbands][nelem][npts_pad]
     std::vector<int32_t> W, inc, nwin, unit_off;
     int64_t nunits = 0;
     int maxW = 0;

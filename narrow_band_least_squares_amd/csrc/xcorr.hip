@@ -280,7 +280,7 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
     XArgs a{};
     a.filt = h->d_filt;
     a.npts_pad = h->npts_pad;
-    a.nchans = h->nchans;
+    a.nchans = h->nelem;                   // array elements (several recordings: d_filt rows of result row r = band r)
     a.npairs = h->npairs;
     a.pair = h->d_pair;
     a.Wb = h->d_W;
@@ -295,7 +295,7 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
     const int64_t nu = ue - ub;
     if (nu <= 0) return hipSuccess;
     // f64-MFMA kernel: needs one wave per channel (N <= 16) and the N-channel window in LDS
-    const int N = h->nchans;
+    const int N = h->nelem;
     bool mfma_ok = N >= 3 && N <= 16 && h->npairs <= 64 * N;
     size_t shm_m = 0;
     if (mfma_ok) {

@@ -1463,7 +1463,7 @@ static bool boff_dfs(int* o, int j, int N, int S, long* budget) {
 // two groups of four; 16 elements x 4500 samples: two groups of eight.  Beyond ~7900 samples even two partners
 // do not fit (the copies alone take 16 bytes per sample): the caller falls back to the general correlator.
 bool nbls_screen_geometry(const nbls_handle* h, int maxW, int* S, int* PFB, int* CSB, int* CSA, int* WP, size_t* lds, int* nsl, int* G, int* ncopy) {
-    const int N = h->nchans;
+    const int N = h->nelem;
     if (N < 3 || N > 33 || maxW < 64) return false;
     const int NPc = (N - 1) < 16 ? (N - 1) : 16;     // partners per workgroup when everything fits (more than 16: partner groups)
     *WP = round_up(maxW, 16);
@@ -1510,7 +1510,7 @@ hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue
     QArgs a{};
     size_t lds = 0;
     if (!nbls_screen_geometry(h, gW, &a.S, &a.PFB, &a.CSB, &a.CSA, &a.WP, &lds, &a.nsl, &a.pgsz, &a.ncopy)) return hipErrorInvalidValue;
-    const int N = h->nchans;
+    const int N = h->nelem;
     a.npg = (N - 1 + a.pgsz - 1) / a.pgsz;
     a.Wuni = gW;
     {   // energy tables in LDS when they do not cost occupancy (two workgroups per CU, or still one)
@@ -1584,7 +1584,10 @@ hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue
     }
     // persistent double-buffered verifier (verify_dma_kernel): up to 8 elements, the unit's windows twice in LDS
     const int vwp = (gW + 3) & ~1;                                       // LDS row stride: even, >= W + 2
-    const size_t dlds = ((size_t)2 * N * vwp + 2) * sizeof(double) + (size_t)2 * h->nbands * sizeof(int);
+    // (the kernel's W / inc tables in LDS cover rows [0, vrows): several recordings make B * nseg rows, of which a launch
+    //  reads those up to the row of its last unit — the LDS a batch adds to a launch stays 8 bytes per row before it)
+    const int vrows = h->nseg > 1 && ue > ub ? h->hp_ub[(size_t)(ue - 1)] + 1 : h->nbands;
+    const size_t dlds = ((size_t)2 * N * vwp + 2) * sizeof(double) + (size_t)2 * vrows * sizeof(int);
     const bool vdma = N <= 8 && h->npairs <= 32 && dlds <= 160 * 1024 &&
                       (h->npts_pad & 1) == 0;
     if (vdma) {
@@ -1664,7 +1667,7 @@ hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue
         if (vdma) {
             const int share = (a.nu + 7) >> 3;
             const int per_xcd = h->num_cus > 0 ? (h->num_cus + 7) / 8 : 32;      // one workgroup per CU
-            hipLaunchKernelGGL(verify_dma_kernel, dim3(8 * (share < per_xcd ? share : per_xcd)), dim3(1024), dlds, h->stream, a, vwp, h->nbands);
+            hipLaunchKernelGGL(verify_dma_kernel, dim3(8 * (share < per_xcd ? share : per_xcd)), dim3(1024), dlds, h->stream, a, vwp, vrows);
         } else if (vlds <= 158 * 1024)
             // (many pairs per unit: sixteen waves share them — the workgroup has the CU to itself when its windows fill the LDS)
             hipLaunchKernelGGL(verify_lds_kernel, dim3(xcd_grid(1, a.nu)), dim3(h->npairs > 128 && vlds > 80 * 1024 ? 1024 : 512), vlds, h->stream, a);

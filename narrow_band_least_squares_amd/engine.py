@@ -760,6 +760,100 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     return res
 
 
+def batch_rows(streams):
+    """Several recordings of one array -> (per recording the ``stream_rows`` list of rows, fs, per recording the start
+    date number).  Every recording must have the same element count, sample count and sampling rate: ``ValueError``
+    naming the mismatch otherwise (host-side only, before any GPU work)."""
+    rows, t0s = [], []
+    fs = npts = nchans = None
+    for i, st in enumerate(streams):
+        r, f, t0 = stream_rows(st)
+        if nchans is None:
+            nchans, npts, fs = len(r), len(r[0]), f
+        elif len(r) != nchans:
+            raise ValueError('recording %d has %d elements, recording 0 has %d' % (i, len(r), nchans))
+        elif len(r[0]) != npts:
+            raise ValueError('recording %d has %d samples per trace, recording 0 has %d' % (i, len(r[0]), npts))
+        elif f != fs:
+            raise ValueError('recording %d is sampled at %r Hz, recording 0 at %r Hz' % (i, f, fs))
+        rows.append(r)
+        t0s.append(t0)
+    return rows, fs, t0s
+
+
+def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
+                  filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False):
+    """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
+    rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
+    recording s alone (bit for bit: the kernels see the same per-row work).
+
+    The S*N rows go up as one trace of S segments (``nbls_set_segments``); a plan of B bands then holds B*S result rows,
+    row b*S + s.  The bands of a batch whose filtered traces do not fit the HBM budget (``max_bands_per_pass`` of S*N rows)
+    run in consecutive rounds; if not even one band of the whole batch fits, the batch is cut into sub-batches of as many
+    recordings as fit.  A batch never takes the time-segmented path.  The passes are fetched in one piece, or streamed
+    batch by batch where ``stream_pays`` (per-row windows) says so; either way every recording's rows are complete before
+    its dictionary is built (the caller's side: rows of one recording are spread over all bands)."""
+    S = len(recordings)
+    nchans, npts = len(recordings[0]), len(recordings[0][0])
+    nb = len(band_edges)
+    prep = prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type, filter_order, filter_ripple,
+                   vector_len, prefiltered)
+    VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
+    per_sub = S if max_bands_per_pass(S * nchans, npts) >= 1 else max_bands_per_pass(nchans, npts)
+    if per_sub < 1:
+        raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
+                         'process it on its own' % (nchans, npts))
+    grids = [np.zeros((4, nb, VL)) for _ in range(S)]
+    masks = [np.zeros((nb, VL, MB), dtype=np.uint8) for _ in range(S)]
+    uncs = [np.zeros((2, nb, VL)) for _ in range(S)] if want_uncert else None
+    h = get_handle(device, 0)
+    try:
+        for s0 in range(0, S, per_sub):
+            k = min(per_sub, S - s0)
+            h.set_segments(k)
+            h.set_trace_rows([r for rec in recordings[s0:s0 + k] for r in rec], fs)
+            cap = max(1, max_bands_per_pass(k * nchans, npts))
+            streamed = stream_pays(alpha, np.tile(prep.nwin, k), P)
+            for b0 in range(0, nb, cap):
+                b1 = min(nb, b0 + cap)
+                R = (b1 - b0) * k
+                launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert)
+                if streamed:
+                    g = np.zeros((4, R * VL))
+                    m = np.zeros((R * VL, MB), dtype=np.uint8)
+                    for q in range(h.result_batches()):
+                        _, _, c0, c1, gsrc, msrc = h.wait_result_batch(q)
+                        g[:, c0:c1] = gsrc[:, c0:c1]
+                        m[c0:c1] = msrc[c0:c1]
+                    if getattr(h, 'profiling', False):
+                        h.sync()                       # (turns the pass's events into ``timings()``)
+                else:
+                    out = h.fetch_packed()
+                    g = np.stack((out['vel'], out['baz'], out['mdccm'], out['sigma_tau']))
+                    m = out['mask']
+                g = g.reshape(4, b1 - b0, k, VL)
+                m = m.reshape(b1 - b0, k, VL, MB)
+                unc = np.stack(h.fetch_uncertainty()).reshape(2, b1 - b0, k, VL) if want_uncert else None
+                for j in range(k):
+                    grids[s0 + j][:, b0:b1] = g[:, :, j]
+                    masks[s0 + j][b0:b1] = m[:, j]
+                    if want_uncert:
+                        uncs[s0 + j][:, b0:b1] = unc[:, :, j]
+    finally:
+        h.set_segments(1)
+    out = []
+    for s in range(S):
+        tt = np.zeros((nb, VL))
+        for b in range(nb):
+            tt[b, :prep.nwin[b]] = window_times(t0s[s], fs, int(prep.W[b]), int(prep.inc[b]), int(prep.nwin[b]))
+        g = grids[s]
+        out.append(BandBatch(vel=g[0], baz=g[1], mdccm=g[2], sigma_tau=g[3], nwin=prep.nwin.astype(int), t=tt, mask=masks[s],
+                             lag=None, cmax=None, z=None, sos=list(prep.sos_ret), W=prep.W, inc=prep.inc, pair_idx=prep.pair_idx,
+                             xij=prep.xij, nchans=nchans, alpha=alpha, handle=h, lts=alpha < 1.0, fs=fs,
+                             vel_uncert=None if uncs is None else uncs[s][0], baz_uncert=None if uncs is None else uncs[s][1]))
+    return out
+
+
 def time_keys(t, nwin, prefixes=None):
     """The ``stdict`` key text of every (band, window): prefix + ``str(numpy.float64 time)`` — repr of a
     Python float is the same shortest round-trip text.  -> ONE flat list of strings, bands in order,

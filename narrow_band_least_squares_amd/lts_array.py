@@ -50,3 +50,34 @@ def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
     conf_int_vel = res.vel_uncert[0, :n].copy()
     conf_int_baz = res.baz_uncert[0, :n].copy()
     return vel, baz, t, mdccm, stdict, sigma_tau, conf_int_vel, conf_int_baz
+
+
+def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None):
+    """``ltsva`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of 8-tuples,
+    element i equal to ``ltsva(streams[i], ...)``.  Every stream must have the same element count, trace length and
+    sampling rate, and all share the geometry; ``ValueError`` names a mismatch before any GPU work.  The "ALPHA is
+    1.0" message prints once per batch.  An empty sequence gives ``[]``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva(streams[0], lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)]
+    nchans = len(recs[0])
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
+                                   prefiltered=True, want_uncert=True)
+    out = []
+    for res in results:
+        n = int(res.nwin[0])
+        if alpha == 1.0:
+            stdict = {}
+        else:
+            stdict = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, nchans, engine.time_keys(res.t, res.nwin))
+        out.append((res.vel[0, :n].copy(), res.baz[0, :n].copy(), res.t[0, :n].copy(), res.mdccm[0, :n].copy(), stdict,
+                    res.sigma_tau[0, :n].copy(), res.vel_uncert[0, :n].copy(), res.baz_uncert[0, :n].copy()))
+    return out

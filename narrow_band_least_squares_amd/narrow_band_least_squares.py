@@ -150,6 +150,63 @@ def narrow_band_least_squares(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_lis
             w_array, h_array)
 
 
+def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                    FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None):
+    """``narrow_band_least_squares`` over several recordings of ONE array in one GPU pass -> a list of 9-tuples,
+    element i equal to ``narrow_band_least_squares(..., streams[i], ...)``.
+
+    Every stream must have the same element count, trace length and sampling rate, and all share the geometry
+    (``lat_list`` / ``lon_list`` or ``rij``); ``ValueError`` names a mismatch before any GPU work.  The S*N rows go up
+    from the streams' own buffers.  Window times come from each stream's own start time, the dictionary is per
+    recording; ``w_array`` / ``h_array`` are equal for all recordings (separate copies).  The BT caution prints once
+    per batch.  An empty sequence gives ``[]``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    if len(streams) == 1:          # a batch of one IS the single call (which overlaps its upload with the plan)
+        return [narrow_band_least_squares(WINLEN_list, WINOVER, ALPHA, streams[0], lat_list, lon_list, NBANDS, w, h,
+                                          freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                          FILTER_RIPPLE, rij=rij)]
+    vector_len = _vector_len(WINLEN_list, WINOVER, streams[0])
+    if len(w) != len(freq_resp_list) or len(h) != len(freq_resp_list):
+        raise ValueError('could not broadcast filter response of length %d into rows of length %d'
+                         % (len(freq_resp_list), len(w)))
+    nchans = len(recs[0])
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    bands = list(range(NBANDS))
+    edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
+    results = engine.process_batch(recs, fs, t0s, rij, edges, [WINLEN_list[ii] for ii in bands], WINOVER, ALPHA,
+                                   FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len=vector_len)
+    sos = results[0].sos
+    w_rows = np.zeros((len(bands), len(freq_resp_list)), dtype=complex)
+    h_rows = np.zeros((len(bands), len(freq_resp_list)), dtype=complex)
+    fast = planner.sosfreqz_bands(sos, freq_resp_list, fs)
+    for n, ii in enumerate(bands):
+        if fast is None:
+            ww, hh = signal.sosfreqz(sos[n], freq_resp_list, fs=fs)
+        else:
+            ww, hh = fast[0], fast[1][n]
+        w_rows[n, :] = ww
+        h_rows[n, :] = hh
+        _bt_caution(WINLEN_list[ii], edges[n][0], edges[n][1])
+    prefixes = [_band_prefix(ii + 1) for ii in bands]
+    out = []
+    for res in results:
+        num_compute_list = [int(n) for n in res.nwin]
+        if ALPHA == 1.0:
+            stdict_all = None
+            sig_tau_array = res.sigma_tau
+        else:
+            keys = engine.time_key_text(res.t, res.nwin, prefixes)
+            stdict_all = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, res.nchans, keys)
+            sig_tau_array = np.zeros(res.sigma_tau.shape)
+        out.append((res.vel, res.baz, res.mdccm, res.t, stdict_all, sig_tau_array, num_compute_list,
+                    w_rows.copy(), h_rows.copy()))
+    return out
+
+
 def narrow_band_loop(ii, freqlist, FREQ_BAND_TYPE, freq_resp_list, st, FILTER_TYPE, FILTER_ORDER,
                      FILTER_RIPPLE, lat_list, lon_list, WINLEN_list, WINOVER, ALPHA, vector_len, rij=None):
     """One band (the reference's joblib task body, narrow_band_least_squares.py:134-218) ->
