@@ -322,6 +322,44 @@ int nbls_comm_destroy(nbls_handle* h);
 int nbls_set_option(nbls_handle* h, const char* key, int64_t value);
 int nbls_developer_build(void);
 
+/* The correlator route of one window group: which kernels the correlation stage launches for windows of W samples of an
+ * array of `nelem` elements, with what tiling and how much LDS.  A pure host function (no handle, no device): nbls_plan
+ * and the launchers take every window-length decision from it, tests scan it.  `npairs` pairs per unit, `vrows` result
+ * rows the launch covers (several recordings: nbls_set_segments), `npts_pad` the padded trace length (its parity
+ * matters), `xcorr_impl` as in nbls_plan, `flags` the NBLS_ROUTE_OPT_* bits of the handle options that change the
+ * route.  Returns NBLS_ERR_ARG for arguments out of range, else 0 — also when a forced xcorr_impl does not apply
+ * (correlator == NBLS_ROUTE_REJECTED). */
+enum {
+    NBLS_ROUTE_REJECTED = 0,      /* the forced xcorr_impl (2: f64 MFMA, 3: int8 screening) does not take this window  */
+    NBLS_ROUTE_SCREEN = 1,        /* quantiser + int8 screening kernel + FP64 verifier                                 */
+    NBLS_ROUTE_MFMA = 2,          /* xcorr_mfma_kernel                                                                 */
+    NBLS_ROUTE_VALU_LDS = 3,      /* xcorr_simple_kernel, both windows in LDS                                          */
+    NBLS_ROUTE_VALU_GLOBAL = 4    /* xcorr_simple_kernel, windows read from global memory                              */
+};
+enum { NBLS_ROUTE_QUANTIZE = 0, NBLS_ROUTE_SCREEN_STAGE = 1, NBLS_ROUTE_VERIFY = 2, NBLS_ROUTE_GENERAL = 3 };   /* lds_* index */
+enum { NBLS_ROUTE_OPT_NC4 = 1, NBLS_ROUTE_OPT_NSL1 = 2, NBLS_ROUTE_OPT_TB8 = 4, NBLS_ROUTE_OPT_TB4 = 8 };   /* options screen_nc4 ... */
+typedef struct {
+    int32_t correlator;       /* NBLS_ROUTE_*                                                                       */
+    int32_t impl;             /* what nbls_get_timings reports as xcorr_impl: 3 screening, 2 f64 MFMA, 1 VALU, 0 none */
+    int32_t ncopy, G, S, nsl; /* screening: byte-shifted copies (8 / 4), partners per workgroup, lag blocks per tile,
+                                 sliding channels per workgroup; f64 MFMA: S lag blocks per tile                      */
+    int32_t PFB, CSB, CSA, WP;/* screening: lag-block prefix, partner image / copy stride (bytes), padded window;
+                                 f64 MFMA: PFB = zero prefix, CSB = channel stride (doubles)                          */
+    int32_t screen_inst;      /* 0 none, 1 screen_kernel<4,8>, 2 <4,4>, 3 <8,8>                                    */
+    int32_t tab_lds;          /* the screening kernel's energy tables in LDS                                        */
+    int32_t quant_inst;       /* 0 none, 2/3/4/6/8 quantize_reg_kernel<G>, 1 quantize_kernel                       */
+    int32_t quant_waves;      /* waves per quantiser workgroup                                                      */
+    int32_t verifier;         /* 0 none, 1 verify_dma_kernel, 2 verify_lds_kernel, 3 verify_kernel                  */
+    int32_t verify_threads;   /* workgroup size of the verifier                                                     */
+    int64_t lds_dyn[4];       /* dynamic LDS bytes per workgroup of each kernel launched (NBLS_ROUTE_QUANTIZE ...)  */
+    int64_t lds_static[4];    /* static LDS bytes of the same kernels                                               */
+} nbls_route;
+int nbls_route_xcorr(int32_t nelem, int32_t W, int32_t npairs, int32_t vrows, int64_t npts_pad, int32_t xcorr_impl,
+                     int32_t flags, nbls_route* out);
+/* The routes of every window length W0..W1 (out[W - W0]): one call for a scan. */
+int nbls_route_table(int32_t nelem, int32_t W0, int32_t W1, int32_t npairs, int32_t vrows, int64_t npts_pad,
+                     int32_t xcorr_impl, int32_t flags, nbls_route* out);
+
 /* Enable (1) / disable (0) HIP-event timing of the stages; read the last run's timings. */
 int nbls_set_profiling(nbls_handle* h, int32_t on);
 int nbls_get_timings(nbls_handle* h, nbls_timings* out);

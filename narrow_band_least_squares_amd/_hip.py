@@ -22,7 +22,7 @@ EXPORTS = [
     'nbls_developer_build', 'nbls_set_trace_from', 'nbls_debug_lts_coop_breakdown', 'nbls_filter_segment',
     'nbls_set_filtered', 'nbls_load_result_block', 'nbls_stream_results', 'nbls_result_batches', 'nbls_wait_result_batch',
     'nbls_comm_set_library', 'nbls_set_uncertainty', 'nbls_fetch_uncertainty', 'nbls_expect_upload', 'nbls_abort_upload',
-    'nbls_set_segments',
+    'nbls_set_segments', 'nbls_route_xcorr', 'nbls_route_table',
 ]
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -49,6 +49,23 @@ class Timings(C.Structure):
                 ('total_ms', C.c_double), ('xcorr_launches', C.c_int64), ('quantize_ms', C.c_double),
                 ('screen_ms', C.c_double), ('verify_ms', C.c_double), ('xcorr_impl', C.c_int32),
                 ('xcorr_fallback_bands', C.c_int32)]
+
+
+# nbls_route (include/nbls.h): the correlator route of one window group
+ROUTE_REJECTED, ROUTE_SCREEN, ROUTE_MFMA, ROUTE_VALU_LDS, ROUTE_VALU_GLOBAL = 0, 1, 2, 3, 4
+ROUTE_QUANTIZE, ROUTE_SCREEN_STAGE, ROUTE_VERIFY, ROUTE_GENERAL = 0, 1, 2, 3
+ROUTE_OPT_NC4, ROUTE_OPT_NSL1, ROUTE_OPT_TB8, ROUTE_OPT_TB4 = 1, 2, 4, 8
+ROUTE_DTYPE = np.dtype([(k, np.int32) for k in ('correlator', 'impl', 'ncopy', 'G', 'S', 'nsl', 'PFB', 'CSB', 'CSA', 'WP',
+                                                 'screen_inst', 'tab_lds', 'quant_inst', 'quant_waves', 'verifier',
+                                                 'verify_threads')] +
+                       [('lds_dyn', np.int64, (4,)), ('lds_static', np.int64, (4,))])
+# the fields that name the kernels a route launches and their tiling (the LDS sizes follow from them)
+ROUTE_KEYS = ('correlator', 'ncopy', 'G', 'S', 'nsl', 'screen_inst', 'tab_lds', 'quant_inst', 'quant_waves', 'verifier',
+              'verify_threads')
+
+
+class Route(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ROUTE_DTYPE.names[:16]] + [('lds_dyn', C.c_int64 * 4), ('lds_static', C.c_int64 * 4)]
 
 
 _lib = None
@@ -122,6 +139,10 @@ def load_library(path=None):
     lib.nbls_debug_screen_stamps.argtypes = [vp, dp]
     lib.nbls_debug_lts_stamps.argtypes = [vp, dp]
     lib.nbls_debug_lts_coop_breakdown.argtypes = [vp, dp]
+    lib.nbls_route_xcorr.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                     C.POINTER(Route)]
+    lib.nbls_route_table.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                     C.c_void_p]
     for name in EXPORTS:
         if name not in ('nbls_destroy', 'nbls_last_error'):
             getattr(lib, name).restype = C.c_int
@@ -478,3 +499,41 @@ class Handle:
         out = np.empty(256)
         self._chk(self.lib.nbls_probe_mfma_f64(self._h, _dptr(a), _dptr(b), _dptr(out)))
         return out.reshape(64, 4)
+
+
+def _route_args(nelem, npairs):
+    return int(nelem), int(nelem * (nelem - 1) // 2 if npairs is None else npairs)
+
+
+def route(nelem, W, npairs=None, vrows=1, npts_pad=64, xcorr_impl=0, flags=0):
+    """The correlator route of windows of W samples (nbls_route_xcorr; host only, no device) -> dict of the
+    nbls_route fields.  npairs None: every pair of the array."""
+    nelem, npairs = _route_args(nelem, npairs)
+    r = Route()
+    rc = load_library().nbls_route_xcorr(nelem, int(W), npairs, int(vrows), int(npts_pad), int(xcorr_impl), int(flags),
+                                         C.byref(r))
+    if rc != 0:
+        raise ValueError('nbls_route_xcorr: arguments out of range')
+    return {k: (list(getattr(r, k)) if k.startswith('lds') else getattr(r, k)) for k in ROUTE_DTYPE.names}
+
+
+def route_table(nelem, W0, W1, npairs=None, vrows=1, npts_pad=64, xcorr_impl=0, flags=0):
+    """The routes of W = W0..W1 (nbls_route_table: the scan runs in the library) -> structured array, row W - W0."""
+    nelem, npairs = _route_args(nelem, npairs)
+    out = np.zeros(int(W1) - int(W0) + 1, dtype=ROUTE_DTYPE)
+    rc = load_library().nbls_route_table(nelem, int(W0), int(W1), npairs, int(vrows), int(npts_pad), int(xcorr_impl),
+                                         int(flags), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError('nbls_route_table: arguments out of range')
+    return out
+
+
+def route_boundaries(nelem, W0=2, W1=16384, npairs=None, vrows=1, npts_pad=64, xcorr_impl=0, flags=0):
+    """Every pair (W_last, W_first) of adjacent window lengths in W0..W1 where any field of the route (kernels,
+    tiling, LDS) changes: the window lengths where a correlator can go wrong without its neighbours noticing."""
+    t = route_table(nelem, W0, W1, npairs, vrows, npts_pad, xcorr_impl, flags)
+    same = np.ones(len(t) - 1, dtype=bool)
+    for k in ROUTE_KEYS:
+        same &= t[k][1:] == t[k][:-1]
+    w = np.flatnonzero(~same) + int(W0)
+    return [(int(a), int(a) + 1) for a in w]

@@ -829,10 +829,10 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
             int e = b + 1;
             while (e < R && h->W[e] == h->W[b]) ++e;
             nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
-            int S_, PFB_, CSB_, CSA_, WP_, nsl_, G_, NC_;
-            size_t lds_;
-            g.screen = h->d_xij && nbls_screen_geometry(h, g.W, &S_, &PFB_, &CSB_, &CSA_, &WP_, &lds_, &nsl_, &G_, &NC_);
-            if (g.screen) { any_ok = true; if (WP_ > maxWP) maxWP = WP_; }
+            nbls_route r;                               // (xcorr_route.hip: the launchers take the same route)
+            nbls_route_compute(nbls_route_query_of(h, g.W, R, 3, false), &r);
+            g.screen = h->d_xij && r.correlator == NBLS_ROUTE_SCREEN;
+            if (g.screen) { any_ok = true; if (r.WP > maxWP) maxWP = r.WP; }
             else if (g.u1 > g.u0) all_ok = false;
             h->wgroups.push_back(g);
             b = e;

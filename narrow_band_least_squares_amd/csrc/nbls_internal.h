@@ -15,9 +15,14 @@
 #define NBLS_FILTER_TILE 16        // samples per LDS tile row
 #define NBLS_FILTER_GROUP 64       // chunks per carry group
 #define NBLS_MAX_PAIRS 512
-#define NBLS_LDS_WINDOW 10000     // samples: beyond, the two windows of xcorr_simple_kernel (2 * W * 8 B) do not fit a CU's 160 KB of LDS and are read from global memory
 #define NBLS_MAX_STARTS 1024
 #define NBLS_MAX_CAND 16
+// Static LDS of the correlation-stage kernels (bytes, = .amdhsa_group_segment_fixed_size of each; the kernels
+// static_assert their __shared__ arrays against these): nbls_route_compute adds them to the dynamic part.  The kernels
+// not named here have none.
+#define NBLS_SLDS_XCORR_SIMPLE 80     // xcorr_simple_kernel: red_v[8] doubles + red_k[4] ints
+#define NBLS_SLDS_VERIFY 16640        // verify_kernel: vscr[4][VRUN_SCR] doubles
+#define NBLS_SCREEN_TB 4              // tile steps of the four-tile screening instances (the copy stride is sized for them)
 
 // Per-handle switches (nbls_set_option).  The first group selects between implementations that give
 // IDENTICAL results (A/B timing, tests that compare kernels with each other).  The second group exists only
@@ -249,7 +254,17 @@ hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipS
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);
 hipError_t nbls_launch_probe_mfma(nbls_handle* h, const double* da, const double* db, double* dout);
-bool nbls_screen_geometry(const nbls_handle* h, int maxW, int* S, int* PFB, int* CSB, int* CSA, int* WP, size_t* lds, int* nsl, int* G, int* ncopy);
+// The correlator route of a window group (xcorr_route.hip; nbls_route_xcorr is its C ABI form).  no_screen: the general
+// correlators only (a group that does not take the screening path); pad_kb: developer option screen_pad_kb.
+struct nbls_route_query {
+    int N, W, npairs, vrows;
+    int64_t npts_pad;
+    int impl, flags, pad_kb;
+    bool no_screen;
+};
+void nbls_route_compute(const nbls_route_query& q, nbls_route* r);
+// the query of a launch of handle h: its array, pair count, padded trace length and route options
+nbls_route_query nbls_route_query_of(const nbls_handle* h, int W, int vrows, int impl, bool no_screen);
 hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue, int gW, int64_t* launches_io);
 hipError_t nbls_xcorr_screen_finish(nbls_handle* h, int64_t launches);
 hipError_t nbls_launch_probe_mfma_i8(nbls_handle* h, const int* da, const int* db, int* dout);

@@ -36,8 +36,8 @@ struct XArgs {
     int CS;                   // LDS elements per channel buffer, == 2 (mod 32)
     int PF;                   // zero padding in front of each channel window
     int u0;                   // first unit of this launch (window groups of a plan: nbls_launch_xcorr)
-    int from_global;          // xcorr_simple_kernel: the two windows do not fit a CU's LDS (> 10 000 samples) and are read
-                              // from global memory (L2) instead — no window length is refused
+    int from_global;          // xcorr_simple_kernel: the two windows do not fit a CU's LDS beside the kernel's static LDS
+                              // (> 10 235 samples: nbls_route_compute) and are read from global memory (L2) instead
 };
 
 // ------------------------------------------------------------------------------------
@@ -64,6 +64,7 @@ __global__ __launch_bounds__(256) void xcorr_simple_kernel(XArgs a) {
     const double* sb = a.from_global ? xb : sm + W;
     __shared__ double red_v[8];
     __shared__ int red_k[4];
+    static_assert(sizeof(red_v) + sizeof(red_k) == NBLS_SLDS_XCORR_SIMPLE, "static LDS of xcorr_simple_kernel: nbls_internal.h");
 
     double qa = 0.0, qb = 0.0;
     for (int n = tid; n < W; n += 256) {
@@ -294,32 +295,24 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
     a.u0 = (int)ub;
     const int64_t nu = ue - ub;
     if (nu <= 0) return hipSuccess;
-    // f64-MFMA kernel: needs one wave per channel (N <= 16) and the N-channel window in LDS
-    const int N = h->nelem;
-    bool mfma_ok = N >= 3 && N <= 16 && h->npairs <= 64 * N;
-    size_t shm_m = 0;
-    if (mfma_ok) {
-        a.S = 16 / (N - 1);
-        a.PF = 16 * (a.S - 1);
-        int cs = a.PF + gW + 32;
-        cs += ((2 - cs) % 32 + 32) % 32;            // CS == 2 (mod 32)
-        a.CS = cs;
-        shm_m = ((size_t)N * cs + N + N * 16) * sizeof(double) + (size_t)N * 16 * sizeof(int);
-        if (shm_m > 160 * 1024) mfma_ok = false;
-    }
-    if (impl == 2 && !mfma_ok) return hipErrorInvalidValue;
-    if (mfma_ok && impl != 1) {
-        hipError_t e = hipFuncSetAttribute((const void*)xcorr_mfma_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_m);
+    // the correlator and its LDS: nbls_route_compute (xcorr_route.hip), the general correlators only
+    nbls_route r;
+    nbls_route_compute(nbls_route_query_of(h, gW, h->nbands, impl, true), &r);
+    if (r.correlator == NBLS_ROUTE_REJECTED) return hipErrorInvalidValue;
+    const size_t shm = (size_t)r.lds_dyn[NBLS_ROUTE_GENERAL];
+    if (r.correlator == NBLS_ROUTE_MFMA) {
+        a.S = r.S;
+        a.PF = r.PFB;
+        a.CS = r.CSB;
+        hipError_t e = hipFuncSetAttribute((const void*)xcorr_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
         if (e != hipSuccess) return e;
         *used = 2;
-        hipLaunchKernelGGL(xcorr_mfma_kernel, dim3((unsigned)nu), dim3(64 * N), shm_m, h->stream, a);
+        hipLaunchKernelGGL(xcorr_mfma_kernel, dim3((unsigned)nu), dim3(64 * h->nelem), shm, h->stream, a);
         return hipGetLastError();
     }
     const int64_t nblocks = nu * h->npairs;
-    a.from_global = (size_t)2 * gW * sizeof(double) > 160 * 1024 ? 1 : 0;
-    const size_t shm = a.from_global ? 0 : (size_t)2 * gW * sizeof(double);
-    if (shm > 48 * 1024) {      // long windows (W up to 10000): opt in to more than the default dynamic LDS
+    a.from_global = r.correlator == NBLS_ROUTE_VALU_GLOBAL ? 1 : 0;
+    if (shm > 48 * 1024) {      // long windows: opt in to more than the default dynamic LDS
         hipError_t e = hipFuncSetAttribute((const void*)xcorr_simple_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
         if (e != hipSuccess) return e;
     }

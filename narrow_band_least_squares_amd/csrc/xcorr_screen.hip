@@ -386,8 +386,6 @@ __device__ inline void stamp(unsigned long long*, int) {}
 #define NBLS_ABL(bits) 0
 #endif
 
-constexpr int TB = 4;            // tile steps processed together (they share the B fragments)
-
 // Fragment of the FOUR-copy layout (long windows, QArgs.ncopy == 4): 16 bytes at a 4-byte aligned LDS address.
 __device__ inline __attribute__((ext_vector_type(4))) int ld_frag32(const unsigned char* p) {
     typedef const int __attribute__((address_space(3))) * lds_i;     // (not volatile: pairs may become ds_read2_b32)
@@ -1371,6 +1369,7 @@ __global__ __launch_bounds__(1024) void verify_dma_kernel(QArgs a, int wp, int n
 
 __global__ __launch_bounds__(256) void verify_kernel(QArgs a) {
     __shared__ double vscr[4][VRUN_SCR];            // per wave: a chunk of the sliding window (wave_dot_run)
+    static_assert(sizeof(vscr) == NBLS_SLDS_VERIFY, "static LDS of verify_kernel: nbls_internal.h");
     const int lane = threadIdx.x & 63;
     const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int P = a.npairs, N = a.nchans;
@@ -1409,8 +1408,6 @@ __global__ void probe_mfma_i8_kernel(const int* a, const int* b, int* out) {
     out[lane * 4 + 2] = acc[2];
     out[lane * 4 + 3] = acc[3];
 }
-
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 }  // namespace
 
@@ -1456,69 +1453,30 @@ static bool boff_dfs(int* o, int j, int N, int S, long* budget) {
     return false;
 }
 
-// Eligibility + LDS size of the screening path for windows of up to maxW samples.
-// *G = partners per workgroup.  All N-1 (at most 16) when their images fit; else the largest group size whose
-// images fit next to the sliding channel's eight shifted copies in a CU's 160 KB — the workgroups of a sliding
-// channel then split its partners (the mechanism that serves 18..32 elements), e.g. 8 elements x 6000 samples:
-// two groups of four; 16 elements x 4500 samples: two groups of eight.  Beyond ~7900 samples even two partners
-// do not fit (the copies alone take 16 bytes per sample): the caller falls back to the general correlator.
-bool nbls_screen_geometry(const nbls_handle* h, int maxW, int* S, int* PFB, int* CSB, int* CSA, int* WP, size_t* lds, int* nsl, int* G, int* ncopy) {
-    const int N = h->nelem;
-    if (N < 3 || N > 33 || maxW < 64) return false;
-    const int NPc = (N - 1) < 16 ? (N - 1) : 16;     // partners per workgroup when everything fits (more than 16: partner groups)
-    *WP = round_up(maxW, 16);
-    // first the layout of eight byte-shifted copies per sliding channel (16 bytes of LDS per sample, two aligned 8-byte
-    // reads per fragment, hand-scheduled K loops); where not even two partners fit beside them (~7900 samples) FOUR copies
-    // with dword-granular addressing on top (8 bytes per sample, four 4-byte reads per fragment, the C++ K loop): ~13 000
-    // samples — example.py's WINLEN_1 = 60 s at 200 Hz
-    for (int nc = h->opt.screen_nc4 ? 4 : 8; nc >= 4; nc -= 4) {        // (option screen_nc4: the four-copy layout also where eight fit — experiment)
-        *ncopy = nc;
-        for (int g = NPc; g >= 2; --g) {
-            if (nc == 4 && g == 16) continue;            // (S == 1 selects the eight-tile instance, built for eight copies)
-            *G = g;
-            *S = 16 / g;
-            if (*S > 8) break;                           // (the column decode handles up to 8 lag blocks per tile)
-            *PFB = 16 * (*S - 1);
-            // partner image: PFB + window + read-ahead padding, a whole number of 256-B bank rows, plus one
-            // row of room for the per-partner skew
-            *CSB = round_up(*PFB + *WP + 192, 256) + 256;
-            // K round-up + read-ahead of the last tile of a group (sized for the eight-tile groups of the one-block instance
-            // where it may be chosen: S == 1)
-            int csa = *WP + 144 + ((*S == 1 ? 8 : TB) - 1) * 16 * (*S);
-            csa = round_up(csa, 32);
-            while (csa % 64 != 32) csa += 32;                // copy stride == 32 B (mod 64): the 8 copies start 8 banks apart (mod 64), conflict-free ds_read_b64
-            *CSA = csa;
-            // two sliding channels per workgroup (8 waves, all N images) when two such workgroups fit a CU's
-            // LDS, else one sliding channel (4 waves, N-1 images)
-            // + running maxima and merge scalars (6 x 32 ints) + the per-channel records (4 doubles each); the f32 energy tables of the pruning test are added by
-            // the caller when they still fit (nbls_screen_tables)
-            // (partner groups: a workgroup with two sliding channels stages the group's g + 1 channels, not all N)
-            const size_t lds2 = (size_t)2 * (N - 1 <= 16 ? N : g + 1) * (*CSB) + (size_t)4 * nc * csa + 6 * 128 + 16 + 32 * N + 64;
-            const size_t lds1 = (size_t)2 * g * (*CSB) + (size_t)2 * nc * csa + 6 * 128 + 16 + 32 * N + 64;
-            const bool force1 = h->opt.screen_nsl1 != 0;                         // option: one sliding channel per workgroup
-            if (nc == 8 && g == NPc && lds2 + (size_t)(2 + N) * (*WP / 32 + 2) * 4 <= 80 * 1024 && !force1) { *nsl = 2; *lds = lds2; }
-            else { *nsl = 1; *lds = lds1; }
-            if (*lds <= 160 * 1024 && *lds >= 1024) return true;
-        }
-    }
-    return false;
-}
-
 // The units [ub, ue) — consecutive bands of ONE window length W (nbls_plan: h->wgroups) — through the screening path.
 // *launches counts the unit batches (profiling events are taken from h->bev at 4 * *launches).
 hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue, int gW, int64_t* launches_io) {
     QArgs a{};
-    size_t lds = 0;
-    if (!nbls_screen_geometry(h, gW, &a.S, &a.PFB, &a.CSB, &a.CSA, &a.WP, &lds, &a.nsl, &a.pgsz, &a.ncopy)) return hipErrorInvalidValue;
     const int N = h->nelem;
+    // the geometry, the kernel instances and their LDS: nbls_route_compute (xcorr_route.hip).  (The verifier's W / inc
+    // tables in LDS cover rows [0, vrows): several recordings make B * nseg rows, of which a launch reads those up to the
+    // row of its last unit — the LDS a batch adds to a launch stays 8 bytes per row before it)
+    const int vrows = h->nseg > 1 && ue > ub ? h->hp_ub[(size_t)(ue - 1)] + 1 : h->nbands;
+    nbls_route r;
+    nbls_route_compute(nbls_route_query_of(h, gW, vrows, 3, false), &r);
+    if (r.correlator != NBLS_ROUTE_SCREEN) return hipErrorInvalidValue;
+    a.S = r.S;
+    a.PFB = r.PFB;
+    a.CSB = r.CSB;
+    a.CSA = r.CSA;
+    a.WP = r.WP;
+    a.nsl = r.nsl;
+    a.pgsz = r.G;
+    a.ncopy = r.ncopy;
     a.npg = (N - 1 + a.pgsz - 1) / a.pgsz;
     a.Wuni = gW;
-    {   // energy tables in LDS when they do not cost occupancy (two workgroups per CU, or still one)
-        const size_t tab = (size_t)(a.nsl + N) * (a.WP / 32 + 2) * 4;
-        const size_t cap = lds <= 80 * 1024 ? 80 * 1024 : 160 * 1024;
-        a.tab_lds = lds + tab <= cap ? 1 : 0;
-        if (a.tab_lds) lds += tab;
-    }
+    a.tab_lds = r.tab_lds;
+    const size_t lds = (size_t)r.lds_dyn[NBLS_ROUTE_SCREEN_STAGE];
     a.filt = h->d_filt;
     a.npts_pad = h->npts_pad;
     a.nchans = N;
@@ -1570,28 +1528,16 @@ hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue
         for (int q = 0; q < 16; ++q) a.boffp0 |= (unsigned long long)(h->skew_o[q] & 15) << (4 * q);
         for (int q = 16; q < 32; ++q) a.boffp1 |= (unsigned long long)(h->skew_o[q] & 15) << (4 * (q - 16));
     }
-    lds += (size_t)h->opt.screen_pad_kb * 1024;                                                      // developer: occupancy experiment
-    // eight-tile instance: one lag block per tile step and a CU per workgroup (two waves per SIMD: 256 VGPRs)
-    // (option screen_tb8: the eight-tile instance wherever S == 1, also for workgroups that would fit a CU twice)
-    const bool tb8 = a.S == 1 && (lds > 80 * 1024 || h->opt.screen_tb8) && !h->opt.screen_tb4 && a.ncopy == 8;
-    const void* skern = tb8 ? (const void*)screen_kernel<8, 8> : (a.ncopy == 4 ? (const void*)screen_kernel<4, 4> : (const void*)screen_kernel<4, 8>);
+    const int sinst = r.screen_inst;
+    const void* skern = sinst == 3 ? (const void*)screen_kernel<8, 8> : (sinst == 2 ? (const void*)screen_kernel<4, 4> : (const void*)screen_kernel<4, 8>);
     hipError_t e = hipFuncSetAttribute(skern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    size_t vlds = ((size_t)N * gW + 2) * sizeof(double);   // + the zero slot
-    if (vlds <= 158 * 1024) {
-        e = hipFuncSetAttribute((const void*)verify_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds);
-        if (e != hipSuccess) return e;
-    }
     // persistent double-buffered verifier (verify_dma_kernel): up to 8 elements, the unit's windows twice in LDS
     const int vwp = (gW + 3) & ~1;                                       // LDS row stride: even, >= W + 2
-    // (the kernel's W / inc tables in LDS cover rows [0, vrows): several recordings make B * nseg rows, of which a launch
-    //  reads those up to the row of its last unit — the LDS a batch adds to a launch stays 8 bytes per row before it)
-    const int vrows = h->nseg > 1 && ue > ub ? h->hp_ub[(size_t)(ue - 1)] + 1 : h->nbands;
-    const size_t dlds = ((size_t)2 * N * vwp + 2) * sizeof(double) + (size_t)2 * vrows * sizeof(int);
-    const bool vdma = N <= 8 && h->npairs <= 32 && dlds <= 160 * 1024 &&
-                      (h->npts_pad & 1) == 0;
-    if (vdma) {
-        e = hipFuncSetAttribute((const void*)verify_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds);
+    const size_t vlds = (size_t)r.lds_dyn[NBLS_ROUTE_VERIFY];
+    if (r.verifier == 1 || r.verifier == 2) {
+        e = hipFuncSetAttribute(r.verifier == 1 ? (const void*)verify_dma_kernel : (const void*)verify_lds_kernel,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds);
         if (e != hipSuccess) return e;
     }
     int64_t launches = *launches_io;
@@ -1629,48 +1575,39 @@ hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue
         hipEvent_t* ev = h->prof ? &h->bev[5 * launches] : nullptr;
         if (ev) (void)hipEventRecord(ev[0], h->stream);
         {
-            const int gpl = (a.WP / 8 + 63) / 64;          // 8-sample groups per lane
-            const size_t qlds = (size_t)4 * (a.WP / 8 + 8) * sizeof(double);
             // (one instance per group count: a lane holds 8 G samples in registers, and the registers set how many
-            //  waves hide the HBM latency of this streaming kernel)
-            if (gpl <= 2)
-                hipLaunchKernelGGL((quantize_reg_kernel<2>), dim3(xcd_grid(4, a.nu * N)), dim3(256), qlds, h->stream, a);
-            else if (gpl == 3)
-                hipLaunchKernelGGL((quantize_reg_kernel<3>), dim3(xcd_grid(4, a.nu * N)), dim3(256), qlds, h->stream, a);
-            else if (gpl <= 4)
-                hipLaunchKernelGGL((quantize_reg_kernel<4>), dim3(xcd_grid(4, a.nu * N)), dim3(256), qlds, h->stream, a);
-            else if (gpl <= 6)
-                hipLaunchKernelGGL((quantize_reg_kernel<6>), dim3(xcd_grid(4, a.nu * N)), dim3(256), qlds, h->stream, a);
-            else if (gpl <= 8)
-                hipLaunchKernelGGL((quantize_reg_kernel<8>), dim3(xcd_grid(4, a.nu * N)), dim3(256), qlds, h->stream, a);
-            else {
-                // one LDS slab per wave: as many waves per workgroup (<= 4) as fit a CU's 160 KB
-                const size_t slab = (size_t)(a.WP + a.WP / 4 + 8) * sizeof(double);
-                int nwq = (int)((160 * 1024) / slab);
-                nwq = nwq > 4 ? 4 : nwq;
-                if (nwq < 1) return hipErrorInvalidValue;
-                if (slab * nwq > 48 * 1024) {
-                    hipError_t qe = hipFuncSetAttribute((const void*)quantize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(slab * nwq));
-                    if (qe != hipSuccess) return qe;
+            //  waves hide the HBM latency of this streaming kernel; beyond, one LDS slab per wave)
+            const size_t qlds = (size_t)r.lds_dyn[NBLS_ROUTE_QUANTIZE];
+            const dim3 qgrid(xcd_grid(r.quant_waves, a.nu * N));
+            switch (r.quant_inst) {
+                case 2: hipLaunchKernelGGL((quantize_reg_kernel<2>), qgrid, dim3(256), qlds, h->stream, a); break;
+                case 3: hipLaunchKernelGGL((quantize_reg_kernel<3>), qgrid, dim3(256), qlds, h->stream, a); break;
+                case 4: hipLaunchKernelGGL((quantize_reg_kernel<4>), qgrid, dim3(256), qlds, h->stream, a); break;
+                case 6: hipLaunchKernelGGL((quantize_reg_kernel<6>), qgrid, dim3(256), qlds, h->stream, a); break;
+                case 8: hipLaunchKernelGGL((quantize_reg_kernel<8>), qgrid, dim3(256), qlds, h->stream, a); break;
+                default: {
+                    if (qlds > 48 * 1024) {
+                        hipError_t qe = hipFuncSetAttribute((const void*)quantize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qlds);
+                        if (qe != hipSuccess) return qe;
+                    }
+                    hipLaunchKernelGGL(quantize_kernel, qgrid, dim3(64 * r.quant_waves), qlds, h->stream, a);
                 }
-                hipLaunchKernelGGL(quantize_kernel, dim3(xcd_grid(nwq, a.nu * N)), dim3(64 * nwq), slab * nwq, h->stream, a);
             }
         }
         if (ev) (void)hipEventRecord(ev[1], h->stream);
         const int ngrp = (a.nu + 7) / 8;
         // 8 waves: two sliding channels x 4, or one channel x 8
         const dim3 sgrid(8 * ((N + a.nsl - 1) / a.nsl) * a.npg, ngrp);
-        if (tb8) hipLaunchKernelGGL((screen_kernel<8, 8>), sgrid, dim3(512), lds, h->stream, a);
-        else if (a.ncopy == 4) hipLaunchKernelGGL((screen_kernel<4, 4>), sgrid, dim3(512), lds, h->stream, a);
+        if (sinst == 3) hipLaunchKernelGGL((screen_kernel<8, 8>), sgrid, dim3(512), lds, h->stream, a);
+        else if (sinst == 2) hipLaunchKernelGGL((screen_kernel<4, 4>), sgrid, dim3(512), lds, h->stream, a);
         else hipLaunchKernelGGL((screen_kernel<4, 8>), sgrid, dim3(512), lds, h->stream, a);
         if (ev) (void)hipEventRecord(ev[2], h->stream);
-        if (vdma) {
+        if (r.verifier == 1) {
             const int share = (a.nu + 7) >> 3;
             const int per_xcd = h->num_cus > 0 ? (h->num_cus + 7) / 8 : 32;      // one workgroup per CU
-            hipLaunchKernelGGL(verify_dma_kernel, dim3(8 * (share < per_xcd ? share : per_xcd)), dim3(1024), dlds, h->stream, a, vwp, vrows);
-        } else if (vlds <= 158 * 1024)
-            // (many pairs per unit: sixteen waves share them — the workgroup has the CU to itself when its windows fill the LDS)
-            hipLaunchKernelGGL(verify_lds_kernel, dim3(xcd_grid(1, a.nu)), dim3(h->npairs > 128 && vlds > 80 * 1024 ? 1024 : 512), vlds, h->stream, a);
+            hipLaunchKernelGGL(verify_dma_kernel, dim3(8 * (share < per_xcd ? share : per_xcd)), dim3(1024), vlds, h->stream, a, vwp, vrows);
+        } else if (r.verifier == 2)
+            hipLaunchKernelGGL(verify_lds_kernel, dim3(xcd_grid(1, a.nu)), dim3(r.verify_threads), vlds, h->stream, a);
         else
             hipLaunchKernelGGL(verify_kernel, dim3((a.nu * h->npairs + 3) / 4), dim3(256), 0, h->stream, a);
         if (ev) (void)hipEventRecord(ev[3], h->stream);
