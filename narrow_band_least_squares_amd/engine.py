@@ -2,6 +2,7 @@
 (filter -> xcorr/lag pick -> MdCCM + OLS|LTS for every band x window) and unpacks the result
 grids.  Used by ``ltsva``, ``filter_data``, ``narrow_band_least_squares*`` and ``bench.py``.
 """
+import functools
 import itertools
 import operator
 import os
@@ -201,6 +202,45 @@ def row_pipeline_for(nchans, npts):
     return bool(ROW_PIPELINE) and 8 * int(nchans) * int(npts) >= ROW_PIPELINE_MIN_BYTES
 
 
+class TraceUpload:
+    """The rows of a trace going up to handle ``h`` on a helper thread (a blocking copy from pageable memory inside the
+    library, GIL released) while the caller designs filters and plans the pass: the handle knows the trace's shape
+    (``set_trace_shape``), only ``nbls_execute`` needs the samples.  ``landed()`` joins the copy and re-raises ITS exception
+    on the caller's thread; a second call does nothing.  ``close()`` only joins: every way out of a call goes through
+    it, so that no copy is left running behind the caller.  ``row_pipeline``: the handle has been told to expect the rows
+    (``row_pipeline_for``), the pass may be queued before ``landed()``.  ``worker``: an ``_UploadWorker`` (``process``: one
+    thread kept between calls, starting one costs 0.1 ms of the 1.3 ms the copy takes); None starts a thread of its own
+    (the sharded call: one per GPU at the same time)."""
+
+    def __init__(self, h, rows, fs, worker=None):
+        self.h, self.rows, self.error = h, rows, None
+        h.set_trace_shape(len(rows), len(rows[0]), fs)
+        self.row_pipeline = row_pipeline_for(len(rows), len(rows[0])) and hasattr(h, 'expect_upload')
+        if self.row_pipeline:
+            h.expect_upload()
+        if worker is not None:
+            self.job = worker.submit(self._run)
+        else:
+            self.job = threading.Thread(target=self._run, name='nbls-upload')
+            self.job.start()
+
+    def _run(self):
+        try:
+            self.h.upload_rows(self.rows)
+        except BaseException as e:                # handed to the calling thread by landed()
+            self.error = e
+
+    def close(self):
+        job, self.job = self.job, None
+        if job is not None:
+            job.join()
+        return job is not None
+
+    def landed(self):
+        if self.close() and self.error is not None:
+            raise self.error
+
+
 def _trace_key(data, fs):
     """Identity of a trace as the caller holds it: where its samples lie (address, length of every row) and the
     sampling rate.  None for anything that is not float64 C-contiguous (such rows are converted per call: no identity)."""
@@ -270,6 +310,37 @@ def window_times(t0_datenum, fs, W, inc, nwin):
     return t0_datenum + (idx / fs) / 86400.0
 
 
+def time_grid(t0_datenum, fs, W, inc, nwin, vector_len):
+    """Window-centre times of every band -> (nbands, vector_len), zero behind a band's last window."""
+    tt = np.zeros((len(nwin), vector_len))
+    rows = {}                                    # (one row of window times per distinct window plan)
+    for b in range(len(nwin)):
+        key = (int(W[b]), int(inc[b]), int(nwin[b]))
+        if key not in rows:
+            rows[key] = window_times(t0_datenum, fs, *key)
+        tt[b, :key[2]] = rows[key]
+    return tt
+
+
+def plan_windows(npts, fs, winlens, winover, vector_len=None):
+    """Per-band window plan -> (W samples int32, inc samples int32, nwin int64, vector_len): the result row length
+    defaults to the longest band's window count and must hold it."""
+    nb = len(winlens)
+    W, inc, nwin = [np.empty(nb, dtype=t) for t in (np.int32, np.int32, np.int64)]
+    plans = {}                                   # (bands usually share a few window lengths: one plan per length)
+    for b in range(nb):
+        wl = float(winlens[b])
+        if wl not in plans:
+            plans[wl] = planner.window_plan(npts, fs, winlens[b], winover)
+        W[b], inc[b], nwin[b] = plans[wl]
+    if vector_len is None:
+        vector_len = max(1, int(nwin.max()))
+    if nwin.max() > vector_len:
+        raise ValueError('could not broadcast %d windows into result rows of length %d '
+                         '(vector_len too small for this band)' % (int(nwin.max()), vector_len))
+    return W, inc, nwin, int(vector_len)
+
+
 class BandBatch:
     """Results of one device pass over ``nbands`` bands (arrays are (nbands, vector_len)).
     ``mask`` (nbands, vector_len, ceil(P/8)) is the packed LTS weight mask as the GPU returns it;
@@ -285,6 +356,54 @@ class BandBatch:
             P = len(self.pair_idx)
             self._weights = np.unpackbits(self.mask, axis=-1, bitorder='little')[..., :P]
         return self._weights
+
+
+GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``BandBatch.grids``, in result-block order
+
+
+def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
+               want_uncert=False):
+    """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
+    vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
+    ``handle`` are the driver's to set."""
+    nb, P = len(nwin), nchans * (nchans - 1) // 2
+    grids = np.zeros((4, nb, vector_len))
+    unc = np.zeros((2, nb, vector_len)) if want_uncert else (None, None)
+    return BandBatch(grids=grids, vel=grids[0], baz=grids[1], mdccm=grids[2], sigma_tau=grids[3], nwin=nwin.astype(int), t=None,
+                     mask=np.zeros((nb, vector_len, (P + 7) // 8), dtype=np.uint8),
+                     lag=np.zeros((nb, vector_len, P), dtype=np.int32) if want_lag else None,
+                     cmax=np.zeros((nb, vector_len, P)) if want_cmax else None,
+                     z=np.zeros((nb, vector_len, 2)) if want_z else None, vel_uncert=unc[0], baz_uncert=unc[1],
+                     sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
+                     lts=alpha < 1.0, fs=fs)
+
+
+def drain(h, streamed, grids, mask, b0, b1, batch_done=None):
+    """Bring the result of the pass that handle ``h`` has just run into rows [b0, b1) of ``grids`` (4, B, VL; None: the
+    mask only) and ``mask`` (B, VL, MB), both C-contiguous.  Not streamed: waits for the pass, ONE D2H copy (grids + weight
+    mask).  Streamed: the rows arrive batch by batch in a pinned mirror of the result block; each batch is waited for once,
+    in order, its cells [c0, c1) are copied out (the mirror is undefined outside them) and ``batch_done(u0, u1)`` is told
+    the batch's units — relative to the pass — while the GPU is busy with the next batch."""
+    if not streamed:
+        out = h.fetch_packed()
+        if grids is not None:
+            for g, name in enumerate(GRID_NAMES):
+                grids[g, b0:b1] = out[name]
+        mask[b0:b1] = out['mask']
+        return
+    gdst = None if grids is None else [grids[g, b0:b1].reshape(-1) for g in range(4)]
+    mdst = mask[b0:b1].reshape(-1, mask.shape[-1])
+    for k in range(h.result_batches()):
+        u0, u1, c0, c1, gsrc, msrc = h.wait_result_batch(k)
+        if c1 > c0:
+            if gdst is not None:
+                for g in range(4):
+                    gdst[g][c0:c1] = gsrc[g, c0:c1]
+            mdst[c0:c1] = msrc[c0:c1]
+        if batch_done is not None:
+            batch_done(u0, u1)
+    if getattr(h, 'profiling', False):
+        h.sync()                                   # (turns the pass's events into ``timings()``)
 
 
 def _filtered_budget_bytes():
@@ -346,24 +465,11 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     h = get_handle(device)
     budget = _filtered_budget_bytes()
     seg_len = max(512, int(budget // (16.0 * nchans)))               # raw + filtered copy of a segment
-    W, inc, nwin = [np.empty(nb, dtype=t) for t in (np.int32, np.int32, np.int64)]
-    for b in range(nb):
-        W[b], inc[b], nwin[b] = planner.window_plan(npts, fs, winlens[b], winover)
-    xij, pair_idx, _ = planner.co_array(rij)
-    P = xij.shape[0]
-    MB = (P + 7) // 8
-    grids = np.zeros((4, nb, vector_len))
-    mask = np.zeros((nb, vector_len, MB), dtype=np.uint8)
-    lag = np.zeros((nb, vector_len, P), dtype=np.int32) if want_lag else None
-    cmax = np.zeros((nb, vector_len, P)) if want_cmax else None
-    z = np.zeros((nb, vector_len, 2)) if want_z else None
-    tt = np.zeros((nb, vector_len))
-    for b in range(nb):
-        tt[b, :nwin[b]] = window_times(t0_datenum, fs, int(W[b]), int(inc[b]), int(nwin[b]))
+    W, inc, nwin, vector_len = plan_windows(npts, fs, winlens, winover, vector_len)
     designs = planner.design_bandpass_many(filter_type, band_edges, filter_order, filter_ripple, fs)
-    res = BandBatch(vel=grids[0], baz=grids[1], mdccm=grids[2], sigma_tau=grids[3], nwin=nwin.astype(int), t=tt,
-                    mask=mask, lag=lag, cmax=cmax, z=z, sos=[d[2] for d in designs], W=W, inc=inc, pair_idx=pair_idx,
-                    xij=xij, nchans=nchans, alpha=alpha, handle=h, lts=alpha < 1.0, fs=fs)
+    res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z)
+    res.xij, res.pair_idx, _ = planner.co_array(rij)
+    res.t, res.sos, res.handle = time_grid(t0_datenum, fs, W, inc, nwin, vector_len), [d[2] for d in designs], h
     if host_overlap is not None:
         host_overlap(res)
     tl, tr = planner.taper_ramps(npts)
@@ -384,11 +490,11 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
                            prefiltered=True, handle=h, xcorr_impl=xcorr_impl, want_lag=want_lag, want_cmax=want_cmax,
                            want_z=want_z, vector_len=w1 - w0)
             assert int(part.nwin[0]) == w1 - w0
-            grids[:, b, w0:w1] = np.stack((part.vel[0], part.baz[0], part.mdccm[0], part.sigma_tau[0]))
-            mask[b, w0:w1] = part.mask[0]
-            for name, arr in (('lag', lag), ('cmax', cmax), ('z', z)):
-                if arr is not None:
-                    arr[b, w0:w1] = getattr(part, name)[0]
+            res.grids[:, b, w0:w1] = part.grids[:, 0]
+            res.mask[b, w0:w1] = part.mask[0]
+            for name in ('lag', 'cmax', 'z'):
+                if getattr(res, name) is not None:
+                    getattr(res, name)[b, w0:w1] = getattr(part, name)[0]
         if group_done is not None:
             group_done(res, b, b + 1)
     return res
@@ -404,29 +510,17 @@ class Prep:
 
 
 def prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
-            filter_ripple=None, vector_len=None, prefiltered=False, common=None):
+            filter_ripple=None, vector_len=None, prefiltered=False, common=None, windows=None):
     """``common``: the Prep of another band group of the same call — its co-array, taper ramps and FAST-LTS plan
-    do not depend on the bands and are reused instead of being recomputed per group."""
+    do not depend on the bands and are reused instead of being recomputed per group.  ``windows``: these bands'
+    ``plan_windows`` result, where the caller has planned the windows of the whole call already."""
     check_elements(nchans, alpha)
     nb = len(band_edges)
     if common is not None:
         xij, pair_idx, xpinv = common.xij, common.pair_idx, common.xpinv
     else:
         xij, pair_idx, xpinv = planner.co_array(rij)
-    W = np.empty(nb, dtype=np.int32)
-    inc = np.empty(nb, dtype=np.int32)
-    nwin = np.empty(nb, dtype=np.int64)
-    plans = {}                                   # (bands usually share a few window lengths: one plan per length)
-    for b in range(nb):
-        wl = float(winlens[b])
-        if wl not in plans:
-            plans[wl] = planner.window_plan(npts, fs, winlens[b], winover)
-        W[b], inc[b], nwin[b] = plans[wl]
-    if vector_len is None:
-        vector_len = max(1, int(nwin.max()))
-    if nwin.max() > vector_len:
-        raise ValueError('could not broadcast %d windows into result rows of length %d '
-                         '(vector_len too small for this band)' % (int(nwin.max()), vector_len))
+    W, inc, nwin, vector_len = windows or plan_windows(npts, fs, winlens, winover, vector_len)
     sos_ret = []
     if prefiltered:
         if nb != 1:
@@ -496,10 +590,7 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
 
 
 def all_window_times(prep, t0_datenum):
-    t = np.zeros((prep.nbands, prep.vector_len))
-    for b in range(prep.nbands):
-        t[b, :prep.nwin[b]] = window_times(t0_datenum, prep.fs, int(prep.W[b]), int(prep.inc[b]), int(prep.nwin[b]))
-    return t
+    return time_grid(t0_datenum, prep.fs, prep.W, prep.inc, prep.nwin, prep.vector_len)
 
 
 def split_block(block, nbands, vector_len, mask_bytes):
@@ -511,252 +602,213 @@ def split_block(block, nbands, vector_len, mask_bytes):
     return grids, mask
 
 
+def group_bounds(nwin, ngroups, cap, split=None):
+    """Contiguous band groups by unit count -> (bounds [(b0, b1), ...], sequential).  ``split`` (``PIPELINE_SPLIT``, e.g.
+    (0.15, 0.5, 0.35)): explicit shares, which also set the group count (a small first group gets the GPU started sooner,
+    a small last group leaves less dictionary work after the GPU has finished).  The groups' filtered traces are in HBM
+    side by side: if ``ngroups`` times the largest group exceeds ``cap`` bands, the call runs in consecutive rounds of
+    <= ``cap`` bands on one handle instead (``sequential``)."""
+    nb = len(nwin)
+    if split and ngroups > 1:
+        shares = [max(0.0, float(x)) for x in split]
+        ngroups = max(1, min(len(shares), nb))
+        shares = np.cumsum(shares[:ngroups]) / max(1e-30, float(np.sum(shares[:ngroups])))
+    else:
+        # mildly decreasing shares (0.41 / 0.33 / 0.26 for three groups): what is left to do on the host after the
+        # GPU has finished is the dictionary of the LAST group (measured: 23.1 -> 22.6 ms per cfg-3 call)
+        wts = 1.0 + 0.3 * np.arange(ngroups - 1, -1, -1)
+        shares = np.cumsum(wts) / float(np.sum(wts))
+    cum = np.concatenate(([0], np.cumsum(nwin)))
+    cuts = [0]
+    for g in range(1, ngroups):
+        b = int(np.searchsorted(cum, cum[-1] * shares[g - 1]))
+        cuts.append(min(max(b, cuts[-1] + 1), nb - (ngroups - g)))
+    cuts.append(nb)
+    bounds = [(cuts[g], cuts[g + 1]) for g in range(ngroups)]
+    if max(b1 - b0 for b0, b1 in bounds) * ngroups > cap:           # HBM budget: consecutive rounds of <= cap bands
+        return [(b0, min(b0 + cap, nb)) for b0 in range(0, nb, cap)], True
+    return bounds, False
+
+
+def choose_form(alpha, nwin, nchans, cap, groups=None, window_slice=None, single=False):
+    """How ``process`` runs a call -> (streamed, bounds, sequential): ONE streamed pass where ``stream_pays``; else
+    ``groups`` / ``pipeline_groups`` band groups side by side (one group for ``single`` calls — pre-filtered, on a given
+    handle, without upload — and for OLS: nothing for the host to do per group); either way in rounds where HBM is short."""
+    nb, npairs = len(nwin), nchans * (nchans - 1) // 2
+    streamed = groups is None and window_slice is None and stream_pays(alpha, nwin, npairs)
+    one_pass = (single or (alpha >= 1.0 and not os.environ.get('NBLS_PIPELINE_GROUPS'))) and groups is None
+    ngroups = 1 if one_pass or streamed else (groups or pipeline_groups(nwin, npairs))
+    bounds, sequential = group_bounds(nwin, max(1, min(ngroups, nb)), cap, PIPELINE_SPLIT if groups is None else None)
+    return streamed, bounds, sequential
+
+
+class _Notifier:
+    """Tells the caller of ``process`` which rows are in ``res``: ``units_done(res, u0, u1)`` if given (flat unit index over
+    all bands of the call, band-major), else ``group_done(res, b0, b1)`` for the bands a unit range completes, else
+    nothing.  What lands before ``host_overlap`` has run (``ready``) is kept and replayed behind it, in band order."""
+
+    def __init__(self, res, units_done, group_done):
+        self.res, self.units_done, self.group_done = res, units_done, group_done
+        self.cum = np.concatenate(([0], np.cumsum(res.nwin))).astype(np.int64)
+        self.done_band = 0                            # bands [0, done_band) have been reported through group_done
+        self.ready, self.deferred = False, []
+
+    def units(self, b0, b1, u0, u1):
+        """Units [u0, u1) of the pass over bands [b0, b1) have landed (a batch of a streamed pass)."""
+        cum = self.cum
+        g0, g1 = int(cum[b0]) + u0, int(cum[b0]) + u1
+        if self.units_done is not None:
+            if g1 > g0:
+                self.units_done(self.res, g0, g1)
+        elif self.group_done is not None:
+            bd = int(np.searchsorted(cum, g1, side='right')) - 1       # bands complete up to unit g1
+            bd = b1 if g1 >= cum[b1] else min(max(bd, self.done_band), b1)
+            if bd > self.done_band:
+                self.group_done(self.res, self.done_band, bd)
+                self.done_band = bd
+
+    def bands(self, b0, b1):
+        """All rows of bands [b0, b1) have landed."""
+        if not self.ready:
+            self.deferred.append((b0, b1))
+        elif self.units_done is not None:
+            self.units(b0, b1, 0, int(self.cum[b1] - self.cum[b0]))
+        elif self.group_done is not None:
+            self.group_done(self.res, b0, b1)
+            self.done_band = b1
+
+    def replay(self):
+        self.ready = True
+        for b0, b1 in self.deferred:
+            self.bands(b0, b1)
+
+
+def collect(res, h, b0, b1, streamed, note):
+    """The rows of bands [b0, b1), whose pass handle ``h`` has just run, into ``res``; then (streamed and past
+    ``host_overlap``: batch by batch) ``note`` is told."""
+    live = streamed and note.ready
+    drain(h, streamed, res.grids, res.mask, b0, b1, functools.partial(note.units, b0, b1) if live else None)
+    extras = [name for name in ('lag', 'cmax', 'z') if getattr(res, name) is not None]
+    if extras:
+        ext = h.fetch(grids=False, **{'want_' + name: True for name in extras})
+        for name in extras:
+            getattr(res, name)[b0:b1] = ext[name]
+    if res.vel_uncert is not None:
+        res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty()
+    if not live:
+        note.bands(b0, b1)
+
+
+def start_upload(data, fs, device):
+    """``process``: unless these very buffers are in HBM already (``resident_trace``) or ``UPLOAD_OVERLAP`` is off, start
+    the trace's upload to the call's first handle -> (``TraceUpload`` or None, resident)."""
+    h0 = get_handle(device, 0)
+    rk = getattr(h0, 'resident_key', None)
+    if rk is not None and rk == _trace_key(data, fs):
+        return None, True
+    if not UPLOAD_OVERLAP:
+        return None, False
+    rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
+    return TraceUpload(h0, rows, fs, _upload_worker()), False
+
+
+def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequential, streamed, up, resident, note,
+                  handle=None, device=None, **launch_kw):
+    """Design, plan and queue the pass of every band group (``prepare`` of its bands — ``prep_tail``: the arguments behind
+    ``winlens`` — then ``launch``), group 0 while the trace is still going up (``up``).  Sequential rounds share one
+    handle: each is collected before the next is planned.  -> the (handle, b0, b1) still to collect."""
+    launched, prep = [], None
+    nchans, npts = _shape_of(data)
+    for g, (b0, b1) in enumerate(bounds):
+        prep = prepare(nchans, npts, res.fs, rij, band_edges[b0:b1], winlens[b0:b1], *prep_tail, common=prep,
+                       windows=(res.W[b0:b1], res.inc[b0:b1], res.nwin[b0:b1], res.grids.shape[2]))
+        res.sos.extend(prep.sos_ret)
+        res.pair_idx, res.xij = prep.pair_idx, prep.xij
+        h = handle if handle is not None else get_handle(device, 0 if sequential else g)
+        if sequential and launched:               # one handle, one plan at a time: finish the previous round first
+            collect(res, *launched.pop(), streamed, note)
+        joins = up is not None and g == 0                 # this launch rides on the upload thread's rows
+        early = joins or (resident and (g == 0 or sequential))
+        # the groups finish in the order they were queued (GPU-side ordering of their correlation stages): the
+        # dictionary of group k is built while groups k+1.. are still running.  Left to itself the GPU shares
+        # itself between the passes and all of them land together at the end (stream priorities alone did the
+        # job on some boxes and not on others)
+        ordered = launched and not sequential and GROUP_ORDER
+        try:
+            launch(h, data, prep, trace_from=launched[0][0] if (launched and not sequential) else None, trace_ready=early,
+                   after=launched[-1][0] if ordered else None, stream=streamed,
+                   before_execute=up.landed if (joins and not up.row_pipeline) else None, **launch_kw)
+        except BaseException:
+            if joins:
+                up.landed()                       # the pass could not be queued: the upload's own error is the cause, if it has one
+            raise
+        if joins:
+            up.landed()                           # (row_pipeline: the pass is queued, the library filters the rows as they land)
+        launched.append((h, b0, b1))
+        res.handle = h
+    return launched
+
+
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
             want_uncert=False):
-    """Run the hot path for a list of bands on one GPU.
-
-    window_slice=(k, n): process only the k-th of n contiguous window slices of every band (window
-    sharding across GPUs); rows outside the slice stay zero, ``nwin``/``t`` describe the whole band.
+    """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
     band_edges [(fmin, fmax), ...]; winlens [seconds per band].
     prefiltered=True: ``data`` is already filtered/tapered (``ltsva`` entry), one band.
+    window_slice=(k, n): process only the k-th of n contiguous window slices of every band (window
+    sharding across GPUs); rows outside the slice stay zero, ``nwin``/``t`` describe the whole band.
     want_uncert=True: also ``res.vel_uncert`` / ``res.baz_uncert`` (nbands, vector_len), the confidence intervals of
     the slowness estimate, computed on the GPU behind each unit's solve (``nbls_set_uncertainty``).
 
-    Host/GPU overlap: the bands are cut into ``groups`` contiguous groups (``pipeline_groups``), each an
-    asynchronous pass on its own handle of the same GPU, queued as soon as its filters are designed.
-    ``host_overlap(res)`` runs once everything is queued (filter responses, key strings: host work that needs
-    no GPU result); ``group_done(res, b0, b1)`` runs as soon as the rows of bands [b0, b1) have landed, while
-    later groups are still being computed (the caller builds its dictionary there).
-    More bands than fit in HBM at once are processed in consecutive rounds.
-
-    Round 4, where it pays (``stream_pays``: LTS calls of 16 000 units and more; ``groups`` given or ``NBLS_PIPELINE_GROUPS`` > 1
-    select the band groups above, smaller and OLS calls are one pass fetched in one piece): ONE pass on one handle whose unit batches — consecutive (band, window) units, each a complete
-    correlate -> solve -> pack chain on the GPU — copy their rows into a pinned host mirror as they finish
-    (``nbls_stream_results``).  ``units_done(res, u0, u1)`` runs as soon as the rows of the units [u0, u1) (flat index
-    over all bands of the call, band-major) are in ``res``, while the GPU works on the next batch; without it
-    ``group_done`` is called for the bands a batch completes."""
+    In this order:
+    1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
+       or a resident trace); every way out from here on joins that copy;
+    2. the windows of all bands are planned once; a trace of which not even one filtered band fits the HBM budget goes to
+       ``process_segmented``;
+    3. the form is chosen (``choose_form``): ONE pass whose unit batches — consecutive (band, window) units, each a complete
+       correlate -> solve -> pack chain on the GPU — stream their rows to the host (``stream_pays``), or contiguous band
+       groups, each an asynchronous pass on its own handle of the same GPU (small and OLS calls: one group, fetched in
+       one piece); more bands than fit in HBM at once run in consecutive rounds on one handle;
+    4. every group's filters are designed and its pass is queued (``launch_groups``), group 0 while the rows still go up;
+    5. with everything queued, the host work that needs no GPU result: ``release_deferred``, the window times,
+       ``host_overlap(res)`` (filter responses, key strings);
+    6. the passes are collected in band order (``collect``).  ``units_done(res, u0, u1)`` runs as soon as the rows of the
+       units [u0, u1) (flat index over all bands of the call, band-major) are in ``res`` — per batch of a streamed pass,
+       while the GPU works on the next one —; without it ``group_done(res, b0, b1)`` runs for the bands a batch or a
+       group completes (the caller builds its dictionary there).  Rounds collected in step 4 are reported after step 5."""
     nchans, npts = _shape_of(data)
-    nb = len(band_edges)
     cap = max_bands_per_pass(nchans, npts)
-    # the trace goes up (a blocking copy from pageable memory, inside the library: the GIL is released) on a helper
-    # thread while this thread designs the first group's filters AND plans its pass: the handle knows the trace's
-    # shape (set_trace_shape), only nbls_execute needs the samples
-    uploader = None
-    upload_error = []
-    resident = False
-    row_pipeline = False
-    if upload and handle is None and (cap >= 1 or prefiltered):
-        rk = getattr(get_handle(device, 0), 'resident_key', None)           # engine.resident_trace: these very buffers are in HBM already
-        resident = rk is not None and rk == _trace_key(data, fs)
-    if upload and handle is None and (cap >= 1 or prefiltered) and UPLOAD_OVERLAP and not resident:
-        h0 = get_handle(device, 0)
-        up_rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
-        h0.set_trace_shape(nchans, npts, fs)
-        row_pipeline = row_pipeline_for(nchans, npts) and hasattr(h0, 'expect_upload')
-        if row_pipeline:
-            h0.expect_upload()                    # the pass will be queued while the rows are still going up
-
-        def _upload():
-            try:
-                h0.upload_rows(up_rows)
-            except BaseException as e:            # re-raised on the calling thread below
-                upload_error.append(e)
-        uploader = _upload_worker().submit(_upload)      # (a thread kept between calls: starting one costs 0.1 ms of the 1.3 ms the copy takes)
-
-    # (started before anything else of the call: from here on every way out joins it)
+    single = prefiltered or handle is not None or not upload
+    up, resident = start_upload(data, fs, device) if upload and handle is None and (cap >= 1 or prefiltered) else (None, False)
     try:
-        W, inc, nwin = [np.empty(nb, dtype=t) for t in (np.int32, np.int32, np.int64)]
-        plans = {}                                   # (bands usually share a few window lengths: one plan per length)
-        for b in range(nb):
-            wl = float(winlens[b])
-            if wl not in plans:
-                plans[wl] = planner.window_plan(npts, fs, winlens[b], winover)
-            W[b], inc[b], nwin[b] = plans[wl]
-        if vector_len is None:
-            vector_len = max(1, int(nwin.max()))
-        if nwin.max() > vector_len:
-            raise ValueError('could not broadcast %d windows into result rows of length %d '
-                             '(vector_len too small for this band)' % (int(nwin.max()), vector_len))
+        W, inc, nwin, vector_len = plan_windows(npts, fs, winlens, winover, vector_len)
         check_elements(nchans, alpha)
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
                                      group_done)
-        cap = max(1, cap)
-        streamed = groups is None and window_slice is None and stream_pays(alpha, nwin, nchans * (nchans - 1) // 2)
-        one_pass = (prefiltered or handle is not None or not upload or (alpha >= 1.0 and not os.environ.get('NBLS_PIPELINE_GROUPS'))) and groups is None
-        ngroups = 1 if one_pass or streamed else (groups or pipeline_groups(nwin, nchans * (nchans - 1) // 2))     # (OLS: nothing for the host to do per group)
-        ngroups = max(1, min(ngroups, nb))
-        # contiguous band groups by unit count.  engine.PIPELINE_SPLIT = (0.15, 0.5, 0.35): explicit shares (a small first
-        # group gets the GPU started sooner, a small last group leaves less dictionary work after the GPU has finished)
-        split = PIPELINE_SPLIT
-        if split and groups is None and ngroups > 1:
-            shares = [max(0.0, float(x)) for x in split]
-            ngroups = max(1, min(len(shares), nb))
-            shares = np.cumsum(shares[:ngroups]) / max(1e-30, float(np.sum(shares[:ngroups])))
-        else:
-            # mildly decreasing shares (0.41 / 0.33 / 0.26 for three groups): what is left to do on the host after the
-            # GPU has finished is the dictionary of the LAST group (measured: 23.1 -> 22.6 ms per cfg-3 call)
-            wts = 1.0 + 0.3 * np.arange(ngroups - 1, -1, -1)
-            shares = np.cumsum(wts) / float(np.sum(wts))
-        cum = np.concatenate(([0], np.cumsum(nwin)))
-        cuts = [0]
-        for g in range(1, ngroups):
-            b = int(np.searchsorted(cum, cum[-1] * shares[g - 1]))
-            cuts.append(min(max(b, cuts[-1] + 1), nb - (ngroups - g)))
-        cuts.append(nb)
-        bounds = [(cuts[g], cuts[g + 1]) for g in range(ngroups)]
-        if max(b1 - b0 for b0, b1 in bounds) * ngroups > cap:           # HBM budget: consecutive rounds of <= cap bands
-            bounds = [(b0, min(b0 + cap, nb)) for b0 in range(0, nb, cap)]
-            sequential = True
-        else:
-            sequential = False
-
-        def upload_done():
-            nonlocal uploader
-            if uploader is not None:
-                uploader.join()
-                uploader = None
-                if upload_error:
-                    raise upload_error[0]
-        P = nchans * (nchans - 1) // 2
-        MB = (P + 7) // 8
-        grids = np.zeros((4, nb, vector_len))
-        mask = np.zeros((nb, vector_len, MB), dtype=np.uint8)
-        lag = np.zeros((nb, vector_len, P), dtype=np.int32) if want_lag else None
-        cmax = np.zeros((nb, vector_len, P)) if want_cmax else None
-        z = np.zeros((nb, vector_len, 2)) if want_z else None
-        unc = np.zeros((2, nb, vector_len)) if want_uncert else None
-        res = BandBatch(vel=grids[0], baz=grids[1], mdccm=grids[2], sigma_tau=grids[3], nwin=nwin.astype(int), t=None,
-                        mask=mask, lag=lag, cmax=cmax, z=z, sos=[], W=W, inc=inc, pair_idx=None, xij=None,
-                        nchans=nchans, alpha=alpha, handle=None, lts=alpha < 1.0, fs=fs,
-                        vel_uncert=None if unc is None else unc[0], baz_uncert=None if unc is None else unc[1])
-
-        deferred = []                                 # rounds collected before host_overlap has run (sequential rounds)
-
-        cum_units = np.concatenate(([0], np.cumsum(nwin))).astype(np.int64)
-        done_band = [0]                               # bands [0, done_band) have been reported through group_done
-
-        def collect_streamed(h, b0, b1, notify):
-            # the rows arrive batch by batch (pinned mirror of the result block): copy each batch's cells out and tell
-            # the caller, while the GPU is busy with the next batch
-            for k in range(h.result_batches()):
-                u0, u1, c0, c1, gsrc, msrc = h.wait_result_batch(k)
-                if c1 > c0:
-                    for g in range(4):
-                        grids[g, b0:b1].reshape(-1)[c0:c1] = gsrc[g, c0:c1]
-                    mask[b0:b1].reshape(-1, MB)[c0:c1] = msrc[c0:c1]
-                if not notify:
-                    continue
-                g0, g1 = int(cum_units[b0]) + u0, int(cum_units[b0]) + u1
-                if units_done is not None:
-                    if g1 > g0:
-                        units_done(res, g0, g1)
-                elif group_done is not None:
-                    bd = int(np.searchsorted(cum_units, g1, side='right')) - 1     # bands complete up to unit g1
-                    bd = min(max(bd, done_band[0]), b1)
-                    if g1 >= cum_units[b1]:
-                        bd = b1
-                    if bd > done_band[0]:
-                        group_done(res, done_band[0], bd)
-                        done_band[0] = bd
-            if getattr(h, 'profiling', False):
-                h.sync()                               # (turns the pass's events into ``timings()``)
-
-        def collect(h, b0, b1, notify=True):
-            if streamed:
-                collect_streamed(h, b0, b1, notify)
-            else:
-                out = h.fetch_packed()                    # waits for that pass; ONE D2H copy (grids + weight mask)
-                grids[:, b0:b1] = np.stack((out['vel'], out['baz'], out['mdccm'], out['sigma_tau']))
-                mask[b0:b1] = out['mask']
-            if want_lag or want_cmax or want_z:
-                ext = h.fetch(want_lag=want_lag, want_cmax=want_cmax, want_z=want_z, grids=False)
-                for name, arr in (('lag', lag), ('cmax', cmax), ('z', z)):
-                    if arr is not None:
-                        arr[b0:b1] = ext[name]
-            if want_uncert:
-                unc[0, b0:b1], unc[1, b0:b1] = h.fetch_uncertainty()
-            if not notify:
-                deferred.append((b0, b1))
-            elif streamed:
-                pass                                   # (told batch by batch above)
-            elif units_done is not None:
-                if cum_units[b1] > cum_units[b0]:
-                    units_done(res, int(cum_units[b0]), int(cum_units[b1]))
-            elif group_done is not None:
-                group_done(res, b0, b1)
-
-        def finish_skeleton(prep):
-            res.pair_idx, res.xij = prep.pair_idx, prep.xij
-            tt = np.zeros((nb, vector_len))
-            rows_t = {}                              # (one row of window times per distinct window plan)
-            for b in range(nb):
-                key = (int(W[b]), int(inc[b]), int(nwin[b]))
-                if key not in rows_t:
-                    rows_t[key] = window_times(t0_datenum, fs, *key)
-                tt[b, :nwin[b]] = rows_t[key]
-            res.t = tt
-
-    except BaseException:
-        if uploader is not None:
-            uploader.join()
-        raise
-    launched = []
-    prep = None
-    try:
-        for g, (b0, b1) in enumerate(bounds):
-            prep = prepare(nchans, npts, fs, rij, band_edges[b0:b1], winlens[b0:b1], winover, alpha, filter_type,
-                           filter_order, filter_ripple, vector_len, prefiltered, common=prep)
-            res.sos.extend(prep.sos_ret)
-            h = handle if handle is not None else get_handle(device, 0 if sequential else g)
-            if sequential and launched:           # one handle, one plan at a time: finish the previous round first
-                collect(*launched.pop(), notify=False)     # (group_done waits for host_overlap: replayed below)
-            early = (uploader is not None and g == 0) or (resident and (g == 0 or sequential))
-            # the groups finish in the order they were queued (GPU-side ordering of their correlation stages): the
-            # dictionary of group k is built while groups k+1.. are still running.  Left to itself the GPU shares
-            # itself between the passes and all of them land together at the end (stream priorities alone did the
-            # job on some boxes and not on others)
-            ordered = launched and not sequential and GROUP_ORDER
-            joins = early and not resident               # this launch rides on the upload thread's rows
-            try:
-                launch(h, data, prep, upload=upload, window_slice=window_slice, uncert=want_uncert,
-                       xcorr_impl=xcorr_impl, trace_from=launched[0][0] if (launched and not sequential) else None,
-                       trace_ready=early, after=launched[-1][0] if ordered else None,
-                       before_execute=upload_done if (joins and not row_pipeline) else None, stream=streamed)
-            except BaseException:
-                if joins and uploader is not None:       # the pass could not be queued: the upload's own error is the cause, if it has one
-                    uploader.join()
-                    uploader = None
-                    if upload_error:
-                        raise upload_error[0]
-                raise
-            if joins:
-                upload_done()                            # (row_pipeline: the pass is queued, the library filters the rows as they land)
-            launched.append((h, b0, b1))
-            res.handle = h
+        streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
+        res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert)
+        note = _Notifier(res, units_done, group_done)
+        launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
+                                                                  vector_len, prefiltered),
+                                 res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
+                                 window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl)
     finally:
-        if uploader is not None:                  # prepare() / plan raised: do not leave the copy running behind the caller
-            uploader.join()
+        if up is not None:
+            up.close()
     # everything is queued: host work that needs no GPU result hides behind the passes
     release_deferred()
-    finish_skeleton(prep)
+    res.t = time_grid(t0_datenum, fs, W, inc, nwin, vector_len)
     if host_overlap is not None:
         host_overlap(res)
-    for b0, b1 in deferred:                       # rounds that landed before the skeleton existed, in band order
-        if units_done is not None:
-            if cum_units[b1] > cum_units[b0]:
-                units_done(res, int(cum_units[b0]), int(cum_units[b1]))
-        elif group_done is not None:
-            group_done(res, b0, b1)
-            done_band[0] = b1
-    for item in launched:
-        collect(*item)
+    note.replay()
+    for h, b0, b1 in launched:
+        collect(res, h, b0, b1, streamed, note)
     return res
 
 
@@ -803,9 +855,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     if per_sub < 1:
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
                          'process it on its own' % (nchans, npts))
-    grids = [np.zeros((4, nb, VL)) for _ in range(S)]
-    masks = [np.zeros((nb, VL, MB), dtype=np.uint8) for _ in range(S)]
-    uncs = [np.zeros((2, nb, VL)) for _ in range(S)] if want_uncert else None
+    out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert) for _ in range(S)]
     h = get_handle(device, 0)
     try:
         for s0 in range(0, S, per_sub):
@@ -818,40 +868,24 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 b1 = min(nb, b0 + cap)
                 R = (b1 - b0) * k
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert)
-                if streamed:
-                    g = np.zeros((4, R * VL))
-                    m = np.zeros((R * VL, MB), dtype=np.uint8)
-                    for q in range(h.result_batches()):
-                        _, _, c0, c1, gsrc, msrc = h.wait_result_batch(q)
-                        g[:, c0:c1] = gsrc[:, c0:c1]
-                        m[c0:c1] = msrc[c0:c1]
-                    if getattr(h, 'profiling', False):
-                        h.sync()                       # (turns the pass's events into ``timings()``)
-                else:
-                    out = h.fetch_packed()
-                    g = np.stack((out['vel'], out['baz'], out['mdccm'], out['sigma_tau']))
-                    m = out['mask']
+                g = np.zeros((4, R, VL))
+                m = np.zeros((R, VL, MB), dtype=np.uint8)
+                drain(h, streamed, g, m, 0, R)
                 g = g.reshape(4, b1 - b0, k, VL)
                 m = m.reshape(b1 - b0, k, VL, MB)
                 unc = np.stack(h.fetch_uncertainty()).reshape(2, b1 - b0, k, VL) if want_uncert else None
-                for j in range(k):
-                    grids[s0 + j][:, b0:b1] = g[:, :, j]
-                    masks[s0 + j][b0:b1] = m[:, j]
+                for j, res in enumerate(out[s0:s0 + k]):
+                    res.grids[:, b0:b1] = g[:, :, j]
+                    res.mask[b0:b1] = m[:, j]
                     if want_uncert:
-                        uncs[s0 + j][:, b0:b1] = unc[:, :, j]
+                        res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = unc[:, :, j]
     finally:
         h.set_segments(1)
-    out = []
-    for s in range(S):
-        tt = np.zeros((nb, VL))
-        for b in range(nb):
-            tt[b, :prep.nwin[b]] = window_times(t0s[s], fs, int(prep.W[b]), int(prep.inc[b]), int(prep.nwin[b]))
-        g = grids[s]
-        out.append(BandBatch(vel=g[0], baz=g[1], mdccm=g[2], sigma_tau=g[3], nwin=prep.nwin.astype(int), t=tt, mask=masks[s],
-                             lag=None, cmax=None, z=None, sos=list(prep.sos_ret), W=prep.W, inc=prep.inc, pair_idx=prep.pair_idx,
-                             xij=prep.xij, nchans=nchans, alpha=alpha, handle=h, lts=alpha < 1.0, fs=fs,
-                             vel_uncert=None if uncs is None else uncs[s][0], baz_uncert=None if uncs is None else uncs[s][1]))
+    for res, t0 in zip(out, t0s):
+        res.t = time_grid(t0, fs, prep.W, prep.inc, prep.nwin, VL)
+        res.sos, res.pair_idx, res.xij, res.handle = list(prep.sos_ret), prep.pair_idx, prep.xij, h
     return out
+
 
 
 def time_keys(t, nwin, prefixes=None):

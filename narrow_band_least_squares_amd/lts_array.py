@@ -9,6 +9,19 @@ from . import engine
 from .helpers import get_rij
 
 
+def _returns(res, nchans, alpha, keys=None):
+    """One band's ``BandBatch`` -> ltsva's 8-tuple (copies of the band's first ``nwin`` cells).  The confidence intervals
+    (Szuberla & Olson) are per-unit scalar math on the GPU behind the solve, csrc/solve.hip: uncertainty_kernel."""
+    n = int(res.nwin[0])
+    stdict = {}
+    if alpha != 1.0:
+        stdict = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, nchans,
+                                         engine.time_keys(res.t, res.nwin) if keys is None else keys)
+    vel, baz, t, mdccm, sigma_tau, conf_int_vel, conf_int_baz = [
+        a[0, :n].copy() for a in (res.vel, res.baz, res.t, res.mdccm, res.sigma_tau, res.vel_uncert, res.baz_uncert)]
+    return vel, baz, t, mdccm, stdict, sigma_tau, conf_int_vel, conf_int_baz
+
+
 def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
           plot_array_coordinates=False, rij=None):
     """Window the (already filtered) stream, pick pairwise cross-correlation lags and solve for
@@ -35,21 +48,7 @@ def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
 
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
                          prefiltered=True, host_overlap=host_side, want_uncert=True)
-    n = int(res.nwin[0])
-    vel = res.vel[0, :n].copy()
-    baz = res.baz[0, :n].copy()
-    t = res.t[0, :n].copy()
-    mdccm = res.mdccm[0, :n].copy()
-    sigma_tau = res.sigma_tau[0, :n].copy()
-    if alpha == 1.0:
-        stdict = {}
-    else:
-        stdict = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, nchans, res.keys)
-    # (Szuberla & Olson confidence intervals: per-unit scalar math on the GPU behind the solve, csrc/solve.hip:
-    #  uncertainty_kernel — no host loop over windows)
-    conf_int_vel = res.vel_uncert[0, :n].copy()
-    conf_int_baz = res.baz_uncert[0, :n].copy()
-    return vel, baz, t, mdccm, stdict, sigma_tau, conf_int_vel, conf_int_baz
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None))
 
 
 def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None):
@@ -71,13 +70,4 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
                                    prefiltered=True, want_uncert=True)
-    out = []
-    for res in results:
-        n = int(res.nwin[0])
-        if alpha == 1.0:
-            stdict = {}
-        else:
-            stdict = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, nchans, engine.time_keys(res.t, res.nwin))
-        out.append((res.vel[0, :n].copy(), res.baz[0, :n].copy(), res.t[0, :n].copy(), res.mdccm[0, :n].copy(), stdict,
-                    res.sigma_tau[0, :n].copy(), res.vel_uncert[0, :n].copy(), res.baz_uncert[0, :n].copy()))
-    return out
+    return [_returns(res, nchans, alpha) for res in results]

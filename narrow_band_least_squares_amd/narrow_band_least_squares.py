@@ -7,8 +7,8 @@ Reference: narrow_band_least_squares.py:8-127 (serial), :134-218 (``narrow_band_
 the GPUs of a node and collects the result blocks with one RCCL gather inside the library
 (``dist.py``); with one GPU it equals the serial call.
 """
+import functools
 import os
-import threading
 
 import numpy as np
 from scipy import signal
@@ -40,6 +40,36 @@ def _bt_caution(winlen, fmin, fmax):
     temp_BT = winlen * (fmax - fmin)
     if temp_BT < 5.0:
         print('CAUTION: BT < 5! Band between ' + str(fmin) + ' Hz and ' + str(fmax) + ' Hz has BT = ' + str(temp_BT))
+
+
+def _bt_cautions(winlens, edges):
+    for winlen, (fmin, fmax) in zip(winlens, edges):
+        _bt_caution(winlen, fmin, fmax)
+
+
+def filter_responses(sos_list, freq_resp_list, fs):
+    """``sosfreqz`` of every band (narrow_band_least_squares.py:78-80) -> (w rows, h rows), each (nbands, F) complex."""
+    w_rows = np.zeros((len(sos_list), len(freq_resp_list)), dtype=complex)
+    h_rows = np.zeros((len(sos_list), len(freq_resp_list)), dtype=complex)
+    fast = planner.sosfreqz_bands(sos_list, freq_resp_list, fs)         # SciPy's values (bit for bit), all bands at once
+    for n, sos in enumerate(sos_list):
+        w_rows[n, :], h_rows[n, :] = signal.sosfreqz(sos, freq_resp_list, fs=fs) if fast is None else (fast[0], fast[1][n])
+    return w_rows, h_rows
+
+
+def _check_response_rows(w, h, freq_resp_list):
+    if len(w) != len(freq_resp_list) or len(h) != len(freq_resp_list):
+        raise ValueError('could not broadcast filter response of length %d into rows of length %d'
+                         % (len(freq_resp_list), len(w)))
+
+
+def _returns(ALPHA, vel, baz, mdccm, sigma_tau, t, stdict, nwin, w_array, h_array):
+    """The reference's 9-tuple: OLS has no dictionary, LTS leaves ``sig_tau_array`` zero (calloc: no pages touched)."""
+    if ALPHA == 1.0:
+        stdict, sig_tau_array = None, sigma_tau
+    else:
+        sig_tau_array = np.zeros(sigma_tau.shape)
+    return (vel, baz, mdccm, t, stdict, sig_tau_array, [int(n) for n in nwin], w_array, h_array)
 
 
 def _band_prefix(band_number):
@@ -77,17 +107,8 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
     def host_side(res):
         # (the two response arrays are made here, while the GPU works: 1.5 MB of fresh pages before the first launch
         #  were a tenth of a millisecond on the call's critical path)
-        w_rows = out_rows['w'] = np.zeros((len(bands), len(freq_resp_list)), dtype=complex)
-        h_rows = out_rows['h'] = np.zeros((len(bands), len(freq_resp_list)), dtype=complex)
-        fast = planner.sosfreqz_bands(res.sos, freq_resp_list, fs)      # SciPy's values (bit for bit), all bands at once
-        for n, ii in enumerate(bands):
-            if fast is None:
-                ww, hh = signal.sosfreqz(res.sos[n], freq_resp_list, fs=fs)
-            else:
-                ww, hh = fast[0], fast[1][n]
-            w_rows[n, :] = ww
-            h_rows[n, :] = hh
-            _bt_caution(WINLEN_list[ii], edges[n][0], edges[n][1])
+        out_rows['w'], out_rows['h'] = filter_responses(res.sos, freq_resp_list, fs)
+        _bt_cautions(winlens, edges)
         if ALPHA < 1.0 and want_keys:
             res.keys = engine.time_key_text(res.t, res.nwin, key_prefixes)
             res.stdict = engine.new_stdict(engine.n_keys(res.keys))
@@ -131,23 +152,15 @@ def narrow_band_least_squares(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_lis
     merged dropped-element dictionary and leaves ``sig_tau_array`` zero, as the reference does.
     ``rij`` (2, N) km is an extension: it overrides the lat/lon geometry."""
     vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    if len(w) != len(freq_resp_list) or len(h) != len(freq_resp_list):
-        raise ValueError('could not broadcast filter response of length %d into rows of length %d'
-                         % (len(freq_resp_list), len(w)))
+    _check_response_rows(w, h, freq_resp_list)
     bands = list(range(NBANDS))
     res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
                                        FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
                                        FILTER_RIPPLE, vector_len, rij=rij,
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands])
-    num_compute_list = [int(n) for n in res.nwin]
-    if ALPHA == 1.0:
-        stdict_all = None
-        sig_tau_array = res.sigma_tau
-    else:
-        stdict_all = res.stdict                  # built group by group while the GPU was still working
-        sig_tau_array = np.zeros(res.sigma_tau.shape)          # (calloc: no pages touched)
-    return (res.vel, res.baz, res.mdccm, res.t, stdict_all, sig_tau_array, num_compute_list,
-            w_array, h_array)
+    # (the dictionary was built group by group while the GPU was still working)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array)
 
 
 def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -169,41 +182,26 @@ def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_li
                                           freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
                                           FILTER_RIPPLE, rij=rij)]
     vector_len = _vector_len(WINLEN_list, WINOVER, streams[0])
-    if len(w) != len(freq_resp_list) or len(h) != len(freq_resp_list):
-        raise ValueError('could not broadcast filter response of length %d into rows of length %d'
-                         % (len(freq_resp_list), len(w)))
+    _check_response_rows(w, h, freq_resp_list)
     nchans = len(recs[0])
     if rij is None:
         rij = get_rij(lat_list, lon_list, nchans)
     bands = list(range(NBANDS))
     edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
-    results = engine.process_batch(recs, fs, t0s, rij, edges, [WINLEN_list[ii] for ii in bands], WINOVER, ALPHA,
-                                   FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len=vector_len)
-    sos = results[0].sos
-    w_rows = np.zeros((len(bands), len(freq_resp_list)), dtype=complex)
-    h_rows = np.zeros((len(bands), len(freq_resp_list)), dtype=complex)
-    fast = planner.sosfreqz_bands(sos, freq_resp_list, fs)
-    for n, ii in enumerate(bands):
-        if fast is None:
-            ww, hh = signal.sosfreqz(sos[n], freq_resp_list, fs=fs)
-        else:
-            ww, hh = fast[0], fast[1][n]
-        w_rows[n, :] = ww
-        h_rows[n, :] = hh
-        _bt_caution(WINLEN_list[ii], edges[n][0], edges[n][1])
+    winlens = [WINLEN_list[ii] for ii in bands]
+    results = engine.process_batch(recs, fs, t0s, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
+                                   FILTER_RIPPLE, vector_len=vector_len)
+    w_rows, h_rows = filter_responses(results[0].sos, freq_resp_list, fs)
+    _bt_cautions(winlens, edges)
     prefixes = [_band_prefix(ii + 1) for ii in bands]
     out = []
     for res in results:
-        num_compute_list = [int(n) for n in res.nwin]
-        if ALPHA == 1.0:
-            stdict_all = None
-            sig_tau_array = res.sigma_tau
-        else:
+        stdict_all = None
+        if ALPHA != 1.0:
             keys = engine.time_key_text(res.t, res.nwin, prefixes)
             stdict_all = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, res.nchans, keys)
-            sig_tau_array = np.zeros(res.sigma_tau.shape)
-        out.append((res.vel, res.baz, res.mdccm, res.t, stdict_all, sig_tau_array, num_compute_list,
-                    w_rows.copy(), h_rows.copy()))
+        out.append(_returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, stdict_all, res.nwin,
+                            w_rows.copy(), h_rows.copy()))
     return out
 
 
@@ -226,6 +224,97 @@ def narrow_band_loop(ii, freqlist, FREQ_BAND_TYPE, freq_resp_list, st, FILTER_TY
         stdict_elements = temp_array[:, 1]
     return (res.vel[0], res.baz[0], res.mdccm[0], res.t[0], stdict_times, stdict_elements,
             res.sigma_tau[0], num_compute, w_rows[0], h_rows[0])
+
+
+def _launch_share(hd, up, rows, prep, mine, wsl, cap, block_bytes, use_stream):
+    """Queue rank's share ``mine`` (band indices; ``wsl``: its window slice of all bands instead) on its handle ``hd``,
+    whose trace ``up`` is bringing up."""
+    if len(mine) <= cap:
+        # (queued while the rows may still be going up: the library filters the channels as they land)
+        try:
+            engine.launch(hd, rows, prep, bands=None if wsl else mine, window_slice=wsl, reserve_bytes=block_bytes,
+                          trace_ready=True, before_execute=None if up.row_pipeline else up.landed, stream=use_stream)
+        except BaseException:
+            up.landed()                     # the upload's own error is the cause, if it has one
+            raise
+        up.landed()
+        return
+    # the rank's share does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): consecutive passes of
+    # <= cap bands, each fetched to the host; the assembled block goes back to the GPU for the ONE gather
+    grids = np.zeros((4, len(mine), prep.vector_len))
+    mask = np.zeros((len(mine), prep.vector_len, prep.mask_bytes), dtype=np.uint8)
+    for k0 in range(0, len(mine), cap):
+        sub = mine[k0:k0 + cap]
+        engine.launch(hd, rows, prep, bands=sub, window_slice=wsl, reserve_bytes=block_bytes, trace_ready=True,
+                      before_execute=up.landed)
+        engine.drain(hd, False, grids, mask, k0, k0 + len(sub))
+    hd.load_result_block(np.frombuffer(grids.tobytes() + mask.tobytes(), dtype=np.uint8))
+
+
+def _stream_local_dictionaries(group, shards, prep, keys):
+    """Where the shares are contiguous band ranges, every LOCAL pass also STREAMS its rows to the host
+    (nbls_stream_results), and the dropped-element dictionary — one entry per window, ~130 ns each under the GIL: 6.5 ms
+    at the benchmark's shape, more than an eighth of a GPU pass — is built for the local ranks while the GPUs are still
+    working: all of it when one process drives every GPU, this rank's 1/world of it under a launcher (the other ranks'
+    entries are made after the gather, from the gathered masks; so do the grids arrive).  -> (head, parts, pattern cache).
+    Rank order = band order: the lowest local rank's batches first (the later ranks' rows wait in their pinned mirrors
+    meanwhile).  Local ranks 0, 1, … (a prefix of the rank order) write straight into the final dictionary ``head``; a
+    local rank r behind a remote one fills ``parts[r]``, merged in rank order after the gather (None: r's are in ``head``)."""
+    cum = np.concatenate(([0], np.cumsum(prep.nwin))).astype(np.int64)
+    smask = np.zeros((prep.nbands, prep.vector_len, prep.mask_bytes), dtype=np.uint8)
+    head, parts, cache = engine.new_stdict(engine.n_keys(keys)), {}, engine.new_pattern_cache()
+    order = sorted(range(len(group.handles)), key=lambda i: group.ranks[i])
+    for n, i in enumerate(order):
+        r, sh = group.ranks[i], shards[group.ranks[i]]
+        target = head
+        if r != n:
+            target = parts[r] = engine.new_stdict(int(cum[sh[-1] + 1] - cum[sh[0]]) if sh else 0)
+        parts.setdefault(r, None)
+        if sh:
+            engine.drain(group.handles[i], True, None, smask, sh[0], sh[-1] + 1, functools.partial(
+                _units_into, target, cache, smask, prep, keys, int(cum[sh[0]])))
+    return head, parts, cache
+
+
+def _units_into(target, cache, mask, prep, keys, base, u0, u1):
+    if u1 > u0:
+        engine.stdict_from_mask(mask, prep.nwin, prep.pair_idx, prep.nchans, keys, into=target, cache=cache,
+                                units=(base + u0, base + u1))
+
+
+def _merge_dictionaries(head, parts, cache, shards, mask, prep, keys):
+    """Rank order = band order = the order of the reference's dictionary: what a local rank streamed is there already
+    (``_stream_local_dictionaries``), the rest comes from the gathered masks."""
+    cum = np.concatenate(([0], np.cumsum(prep.nwin))).astype(np.int64)
+    for r, sh in enumerate(shards):
+        if r not in parts:
+            if sh:
+                engine.stdict_from_mask(mask, prep.nwin, prep.pair_idx, prep.nchans, keys, into=head, cache=cache,
+                                        units=(int(cum[sh[0]]), int(cum[sh[-1] + 1])))
+        elif parts[r] is not None:
+            head.update(parts[r])
+    if 'size' not in head:
+        head['size'] = prep.nchans
+    engine.release_later(cache)
+    return head
+
+
+def _assemble(blocks, shards, prep):
+    """The ranks' gathered result blocks -> (grids (4, NBANDS, VL), mask).  ``shards`` None: window slices, which are
+    disjoint, and rows outside a slice are zero: grids add, masks OR."""
+    NB, VL, MB = prep.nbands, prep.vector_len, prep.mask_bytes
+    grids = np.zeros((4, NB, VL))
+    mask = np.zeros((NB, VL, MB), dtype=np.uint8)
+    for r in range(len(blocks)):
+        if shards is None:
+            g, m = engine.split_block(blocks[r], NB, VL, MB)
+            grids += g
+            mask |= m
+        else:
+            g, m = engine.split_block(blocks[r], len(shards[r]), VL, MB)
+            grids[:, shards[r], :] = g
+            mask[shards[r]] = m
+    return grids, mask
 
 
 def narrow_band_least_squares_parallel(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h,
@@ -251,61 +340,34 @@ def narrow_band_least_squares_parallel(WINLEN_list, WINOVER, ALPHA, st, lat_list
     rows, fs, t0 = engine.stream_rows(st)
     nchans, npts = len(rows), len(rows[0])
     bands = list(range(NBANDS))
-    status, failure, prep = 0, None, None
+    winlens = [WINLEN_list[ii] for ii in bands]
+    status, failure, prep, shards = 0, None, None, None
     by_windows = NBANDS < world or os.environ.get('NBLS_SHARD') == 'windows'
-    shards = None
     # the trace goes up to every local GPU on helper threads (the copy runs inside the library, GIL released) while
     # this thread designs the filters of all bands; a pass is planned as soon as the design is there and queued when
-    # its GPU's copy has landed
-    uploads = []                    # (thread, error list) per local handle
-    row_pipeline = engine.row_pipeline_for(nchans, npts)      # long traces: the passes are queued while the rows still go up
+    # its GPU's copy has landed (long traces: while the rows still go up)
+    uploads = []                    # one engine.TraceUpload per local handle
     try:
         for hd in group.handles:
-            hd.set_trace_shape(nchans, npts, fs)
-            if row_pipeline and hasattr(hd, 'expect_upload'):
-                hd.expect_upload()
-            err = []
-
-            def _up(hd=hd, err=err):
-                try:
-                    hd.upload_rows(rows)
-                except BaseException as e:      # noqa: BLE001 - re-raised where the pass is queued
-                    err.append(e)
-            th = threading.Thread(target=_up, name='nbls-upload')
-            th.start()
-            uploads.append((th, err))
+            uploads.append(engine.TraceUpload(hd, rows, fs))
     except Exception as e:
         status, failure = 1, e
     try:
         if rij is None:
             rij = get_rij(lat_list, lon_list, nchans)
         edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
-        prep = engine.prepare(nchans, npts, fs, rij, edges, [WINLEN_list[ii] for ii in bands], WINOVER, ALPHA,
-                              FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len)
+        prep = engine.prepare(nchans, npts, fs, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
+                              FILTER_RIPPLE, vector_len)
     except Exception as e:          # a rank that cannot even plan still takes part in the gather (status word)
         status, failure = 1, failure or e
     npairs = nchans * (nchans - 1) // 2
-    unit_bytes = 32 + (npairs + 7) // 8
-    if by_windows:
-        nb_block = NBANDS
-    else:
-        costs = dist.band_costs(npts, fs, [WINLEN_list[b] for b in bands], WINOVER, npairs)
-        shards, contiguous = dist.plan_shards(costs, world)
+    nb_block = NBANDS
+    if not by_windows:
+        shards, contiguous = dist.plan_shards(dist.band_costs(npts, fs, winlens, WINOVER, npairs), world)
         nb_block = max(1, max(len(sh) for sh in shards))
-    block_bytes = (nb_block * vector_len * unit_bytes + 7) // 8 * 8 + 8       # + the status word
+    block_bytes = (nb_block * vector_len * (32 + (npairs + 7) // 8) + 7) // 8 * 8 + 8       # + the status word
 
-    def landed(i):
-        th, err = uploads[i]
-        th.join()
-        if err:
-            raise err[0]
-
-    # The shares are contiguous band ranges: every LOCAL pass also STREAMS its rows to the host (nbls_stream_results), and
-    # the dropped-element dictionary — one entry per window, ~130 ns each under the GIL: 6.5 ms at the benchmark's shape,
-    # more than an eighth of a GPU pass — is built for the local ranks (= band ranges) while the GPUs are still working:
-    # all of it when one process drives every GPU, this rank's 1/world of it under a launcher (the other ranks' entries
-    # are made after the gather, from the gathered masks).  The grids still arrive through the ONE RCCL gather below.
-    use_stream = False
+    use_stream = False              # contiguous band shares under LTS: see _stream_local_dictionaries
     if status == 0:
         cap = max(1, engine.max_bands_per_pass(nchans, npts))      # filtered bands one pass may keep in HBM
         use_stream = (not by_windows and ALPHA < 1.0 and contiguous
@@ -314,88 +376,28 @@ def narrow_band_least_squares_parallel(WINLEN_list, WINOVER, ALPHA, st, lat_list
 
         def start(i, hd):
             r = group.ranks[i]
-            mine = list(range(NBANDS)) if by_windows else shards[r]
-            wsl = (r, world) if by_windows else None
-            if len(mine) <= cap:
-                # (queued while the rows may still be going up: the library filters the channels as they land)
-                try:
-                    engine.launch(hd, rows, prep, bands=None if by_windows else mine, window_slice=wsl, reserve_bytes=block_bytes,
-                                  trace_ready=True, before_execute=None if row_pipeline else (lambda: landed(i)), stream=use_stream)
-                except BaseException:
-                    landed(i)                   # the upload's own error is the cause, if it has one
-                    raise
-                landed(i)
-                return
-            # the rank's share does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): consecutive passes of
-            # <= cap bands, each fetched to the host; the assembled block goes back to the GPU for the ONE gather
-            MBr = prep.mask_bytes
-            grids = np.zeros((4, len(mine), vector_len))
-            mask = np.zeros((len(mine), vector_len, MBr), dtype=np.uint8)
-            for k0 in range(0, len(mine), cap):
-                sub = mine[k0:k0 + cap]
-                engine.launch(hd, rows, prep, bands=sub, window_slice=wsl, reserve_bytes=block_bytes, trace_ready=True,
-                              before_execute=(lambda: landed(i)) if k0 == 0 else None)
-                out = hd.fetch_packed()
-                grids[:, k0:k0 + len(sub)] = np.stack((out['vel'], out['baz'], out['mdccm'], out['sigma_tau']))
-                mask[k0:k0 + len(sub)] = out['mask']
-            hd.load_result_block(np.frombuffer(grids.tobytes() + mask.tobytes(), dtype=np.uint8))
+            _launch_share(hd, uploads[i], rows, prep, bands if by_windows else shards[r], (r, world) if by_windows else None,
+                          cap, block_bytes, use_stream)
         errs = [e for e in dist.run_on_handles(start, group.handles) if e is not None]
         if errs:
             status, failure = 1, errs[0]
-    for th, _ in uploads:           # (a failed rank never reached its join)
-        th.join()
+    for up in uploads:              # (a failed rank never reached its join)
+        up.close()
 
-    # host work that needs no GPU result, while the passes run
-    F = len(freq_resp_list)
-    w_array = np.zeros((NBANDS, F), dtype=complex)
-    h_array = np.zeros((NBANDS, F), dtype=complex)
-    t_array = keys = None
+    # host work that needs no GPU result, while the passes run; then the local shares' dictionary, batch by batch
+    w_array = h_array = t_array = keys = stdict_head = None
     if status == 0:
         try:
-            fast = planner.sosfreqz_bands(prep.sos_ret, freq_resp_list, fs)
-            for n, ii in enumerate(bands):
-                ww, hh = signal.sosfreqz(prep.sos_ret[n], freq_resp_list, fs=fs) if fast is None else (fast[0], fast[1][n])
-                w_array[n, :], h_array[n, :] = ww, hh
-                if 0 in group.ranks:
-                    _bt_caution(WINLEN_list[ii], edges[n][0], edges[n][1])
-            t_array = engine.all_window_times(prep, t0)
+            w_array, h_array = filter_responses(prep.sos_ret, freq_resp_list, fs)
+            if 0 in group.ranks:
+                _bt_cautions(winlens, edges)
+            t_array = engine.time_grid(t0, fs, prep.W, prep.inc, prep.nwin, vector_len)
             if ALPHA < 1.0:
                 keys = engine.time_key_text(t_array, prep.nwin, [_band_prefix(ii + 1) for ii in bands])
-        except Exception as e:
-            status, failure = 1, e
-
-    stdict_head, stdict_parts, cum, cache = None, {}, None, None
-    if use_stream and status == 0:
-        # rank order = band order: the lowest local rank's batches first (the later ranks' rows wait in their pinned mirrors
-        # meanwhile).  Local ranks 0, 1, … (a prefix of the rank order) write straight into the final dictionary; a local rank
-        # behind a remote one fills a dictionary of its own, merged in rank order after the gather
-        try:
-            MBs = prep.mask_bytes
-            cum = np.concatenate(([0], np.cumsum(prep.nwin))).astype(np.int64)
-            smask = np.zeros((NBANDS, vector_len, MBs), dtype=np.uint8)
-            stdict_head = engine.new_stdict(engine.n_keys(keys))
-            cache = engine.new_pattern_cache()
-            order = sorted(range(len(group.handles)), key=lambda i: group.ranks[i])
-            for n, i in enumerate(order):
-                r, hd = group.ranks[i], group.handles[i]
-                if r == n:
-                    target = stdict_head
-                else:
-                    target = stdict_parts[r] = engine.new_stdict(int(cum[shards[r][-1] + 1] - cum[shards[r][0]]) if shards[r] else 0)
-                stdict_parts.setdefault(r, None)
-                sh = shards[r]
-                if not sh:
-                    continue
-                b0, b1 = sh[0], sh[-1] + 1
-                for k in range(hd.result_batches()):
-                    u0, u1, c0, c1, _, msrc = hd.wait_result_batch(k)
-                    if c1 > c0:
-                        smask[b0:b1].reshape(-1, MBs)[c0:c1] = msrc[c0:c1]
-                    if u1 > u0:
-                        engine.stdict_from_mask(smask, prep.nwin, prep.pair_idx, nchans, keys, into=target, cache=cache,
-                                                units=(int(cum[b0]) + u0, int(cum[b0]) + u1))
+            if use_stream:
+                stdict_head, stdict_parts, cache = _stream_local_dictionaries(group, shards, prep, keys)
         except Exception as e:      # noqa: BLE001 - reported through the gather's status word like every other local failure
-            status, failure, stdict_head, stdict_parts = 1, e, None, {}
+            status, failure, stdict_head = 1, e, None
 
     blocks = group.gather(block_bytes, status)          # the ONE collective
     if failure is not None:
@@ -406,42 +408,10 @@ def narrow_band_least_squares_parallel(WINLEN_list, WINOVER, ALPHA, st, lat_list
     if np.any(stat != 0):
         raise RuntimeError('narrow_band_least_squares_parallel: rank(s) %s failed' % np.nonzero(stat)[0].tolist())
 
-    MB = prep.mask_bytes
-    if by_windows:
-        # slices are disjoint and rows outside a slice are zero: grids add, masks OR
-        grids = np.zeros((4, NBANDS, vector_len))
-        mask = np.zeros((NBANDS, vector_len, MB), dtype=np.uint8)
-        for r in range(world):
-            g, m = engine.split_block(blocks[r], NBANDS, vector_len, MB)
-            grids += g
-            mask |= m
-    else:
-        grids = np.zeros((4, NBANDS, vector_len))
-        mask = np.zeros((NBANDS, vector_len, MB), dtype=np.uint8)
-        for r in range(world):
-            g, m = engine.split_block(blocks[r], len(shards[r]), vector_len, MB)
-            grids[:, shards[r], :] = g
-            mask[shards[r]] = m
-    num_compute_list = [int(n) for n in prep.nwin]
-    if ALPHA == 1.0:
-        stdict_all = None
-        sig_tau_array = grids[3]
-    else:
-        if stdict_head is None:
-            stdict_all = engine.stdict_from_mask(mask, prep.nwin, prep.pair_idx, nchans, keys)
-        else:
-            # rank order = band order = the order of the reference's dictionary: what a local rank streamed is there already,
-            # the rest comes from the gathered masks
-            stdict_all = stdict_head
-            for r in range(world):
-                if r not in stdict_parts:
-                    if shards[r]:
-                        engine.stdict_from_mask(mask, prep.nwin, prep.pair_idx, nchans, keys, into=stdict_all, cache=cache,
-                                                units=(int(cum[shards[r][0]]), int(cum[shards[r][-1] + 1])))
-                elif stdict_parts[r] is not None:
-                    stdict_all.update(stdict_parts[r])
-            if 'size' not in stdict_all:
-                stdict_all['size'] = nchans
-            engine.release_later(cache)
-        sig_tau_array = np.zeros((NBANDS, vector_len))
-    return (grids[0], grids[1], grids[2], t_array, stdict_all, sig_tau_array, num_compute_list, w_array, h_array)
+    grids, mask = _assemble(blocks, shards, prep)
+    stdict_all = None
+    if ALPHA != 1.0 and stdict_head is None:
+        stdict_all = engine.stdict_from_mask(mask, prep.nwin, prep.pair_idx, nchans, keys)
+    elif ALPHA != 1.0:
+        stdict_all = _merge_dictionaries(stdict_head, stdict_parts, cache, shards, mask, prep, keys)
+    return _returns(ALPHA, grids[0], grids[1], grids[2], grids[3], t_array, stdict_all, prep.nwin, w_array, h_array)

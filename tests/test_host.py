@@ -1020,3 +1020,164 @@ def test_plan_constants_are_kept_read_only_and_equal_a_fresh_computation():
     p1['rew_table'][0] = 123.0                            # the caller's copy is its own
     assert planner.lts_plan(a[0], 0.5)['rew_table'][0] == 1.0
     assert planner.lts_plan(a[0], 0.75)['h'] != p1['h']
+
+
+def test_group_bounds_against_the_table_of_the_previous_driver():
+    """engine.group_bounds(nwin, ngroups, cap, split) -> (bounds, sequential).  The expected values were recorded by running
+    the band-group lines of the previous ``engine.process`` (the commit before the drivers shared their parts) on these
+    inputs and pasting what they gave; nothing here comes from the function under test."""
+    from narrow_band_least_squares_amd import engine
+    EQ = [100] * 12
+    UNEQ = [4000, 2000, 1000, 500, 250, 120, 60, 30, 15, 8, 4, 2]
+    RISE = UNEQ[::-1]
+    SPLIT = (0.15, 0.5, 0.35)
+    each = [(b, b + 1) for b in range(12)]
+    table = [
+        (EQ, 1, 1000, None, [(0, 12)], False),                                       # one group
+        (EQ, 2, 1000, None, [(0, 7), (7, 12)], False),                               # 2, 3, 4 groups, equal bands
+        (EQ, 3, 1000, None, [(0, 5), (5, 9), (9, 12)], False),
+        (EQ, 4, 1000, None, [(0, 4), (4, 8), (8, 10), (10, 12)], False),
+        (UNEQ, 2, 1000, None, [(0, 2), (2, 12)], False),                             # ... strongly unequal, falling
+        (UNEQ, 3, 1000, None, [(0, 1), (1, 2), (2, 12)], False),
+        (UNEQ, 4, 1000, None, [(0, 1), (1, 2), (2, 3), (3, 12)], False),
+        (RISE, 2, 1000, None, [(0, 11), (11, 12)], False),                           # ... and rising
+        (RISE, 3, 1000, None, [(0, 10), (10, 11), (11, 12)], False),
+        (RISE, 4, 1000, None, [(0, 9), (9, 10), (10, 11), (11, 12)], False),
+        ([7, 7, 7, 7, 7], 5, 1000, None, [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5)], False),   # as many groups as bands
+        (UNEQ, 12, 1000, None, each, False),
+        (EQ, 3, 1000, SPLIT, [(0, 2), (2, 8), (8, 12)], False),                      # explicit shares
+        (UNEQ, 3, 1000, SPLIT, [(0, 1), (1, 2), (2, 12)], False),
+        (RISE, 2, 1000, SPLIT, [(0, 10), (10, 11), (11, 12)], False),                # (the shares set the group count)
+        (EQ, 1, 1000, SPLIT, [(0, 12)], False),                                      # (... not for a single group)
+        ([5, 5], 3, 1000, SPLIT, [(0, 1), (1, 2)], False),
+        (EQ, 3, 11, None, [(0, 11), (11, 12)], True),                                # cap < largest group x groups: rounds
+        (EQ, 3, 12, None, [(0, 12)], True),
+        (EQ, 3, 15, None, [(0, 5), (5, 9), (9, 12)], False),
+        (UNEQ, 4, 8, None, [(0, 8), (8, 12)], True),
+        (EQ, 1, 5, None, [(0, 5), (5, 10), (10, 12)], True),
+        (EQ, 1, 12, None, [(0, 12)], False),
+        (EQ, 2, 1, None, each, True),                                                # cap = 1
+        (EQ, 1, 1, None, each, True),
+        ([9], 1, 1, None, [(0, 1)], False),
+    ]
+    for nwin, ngroups, cap, split, bounds, sequential in table:
+        got = engine.group_bounds(np.array(nwin, dtype=np.int64), ngroups, cap, split)
+        assert got == (bounds, sequential), (nwin, ngroups, cap, split, got)
+
+
+def test_trace_upload_hands_its_exception_to_the_caller_once_and_is_always_joined():
+    """engine.TraceUpload: ``landed()`` re-raises the upload's own exception on the calling thread, once; a second call
+    does nothing; whatever happens on the caller's side between the start and ``landed()``, ``close()`` leaves no copy
+    running.  With a thread of its own and on the per-process worker of ``engine.process``."""
+    import threading
+    import time
+    from narrow_band_least_squares_amd import engine
+
+    class Slow:
+        def __init__(self, fail=False):
+            self.fail, self.done, self.thread, self.shape = fail, False, None, None
+
+        def set_trace_shape(self, *a):
+            self.shape = a
+
+        def upload_rows(self, rows):
+            self.thread = threading.current_thread()
+            time.sleep(0.02)
+            self.done = True
+            if self.fail:
+                raise OSError('injected upload failure')
+
+    rows = [np.zeros(8), np.zeros(8), np.zeros(8)]
+    for worker in (None, engine._upload_worker()):
+        h = Slow(fail=True)
+        up = engine.TraceUpload(h, rows, 20.0, worker)
+        assert h.shape == (3, 8, 20.0) and not up.row_pipeline
+        with pytest.raises(OSError, match='injected upload failure'):
+            up.landed()
+        assert h.done and h.thread is not threading.current_thread()
+        up.landed()                                   # the second call does nothing
+        up.close()
+        # the caller fails between start and landed(): the copy is joined on the way out, its own error stays put
+        h = Slow(fail=True)
+        with pytest.raises(KeyError):
+            up = engine.TraceUpload(h, rows, 20.0, worker)
+            try:
+                assert not h.done
+                raise KeyError('the caller fails')
+            finally:
+                up.close()
+        assert h.done
+        up.landed()                                   # (already joined by close(): nothing happens, nothing is raised)
+        h = Slow()
+        up = engine.TraceUpload(h, rows, 20.0, worker)
+        up.landed()
+        assert h.done
+
+
+def test_drain_streamed_equals_one_piece_and_mask_only_leaves_the_grids():
+    """engine.drain on a streamed stand-in (batches that cut through bands; every batch's source is NaN / 0x55 outside its
+    own cells [c0, c1)): the rows equal those of the one-piece drain of the same stand-in, every batch is waited for
+    once and in order, the callback sees every batch's units; the mask-only form has no grid destination and touches no
+    grid source (here: None)."""
+    from narrow_band_least_squares_amd import engine
+    rng = np.random.default_rng(5)
+    B, VL, MB = 4, 9, 2
+    nwin = [9, 5, 0, 7]
+    g = rng.random((4, B, VL))
+    m = rng.integers(0, 256, (B, VL, MB), dtype=np.uint8)
+    for b in range(B):
+        g[:, b, nwin[b]:] = 0.0
+        m[b, nwin[b]:] = 0
+    cuts = [0, 3, 10, 10, 15, 21]
+    waited, told = [], []
+
+    def cell(u):
+        off = 0
+        for b, n in enumerate(nwin):
+            if u < off + n:
+                return b * VL + (u - off)
+            off += n
+        raise AssertionError(u)
+
+    class Stub:
+        def fetch_packed(self):
+            return dict(vel=g[0], baz=g[1], mdccm=g[2], sigma_tau=g[3], mask=m)
+
+        def result_batches(self):
+            return len(cuts) - 1
+
+        def wait_result_batch(self, k):
+            waited.append(k)
+            u0, u1 = cuts[k], cuts[k + 1]
+            c0, c1 = (cell(u0), cell(u1 - 1) + 1) if u1 > u0 else (0, 0)
+            gsrc = np.full((4, B * VL), np.nan)
+            msrc = np.full((B * VL, MB), 0x55, dtype=np.uint8)
+            gsrc[:, c0:c1] = g.reshape(4, -1)[:, c0:c1]
+            msrc[c0:c1] = m.reshape(-1, MB)[c0:c1]
+            return u0, u1, c0, c1, gsrc, msrc
+
+    def dest():            # two more bands in front of and one behind the pass's bands [2, 6)
+        return np.full((4, B + 3, VL), 7.0), np.full((B + 3, VL, MB), 9, dtype=np.uint8)
+    g1, m1 = dest()
+    engine.drain(Stub(), False, g1, m1, 2, 2 + B)
+    assert not waited
+    np.testing.assert_array_equal(g1[:, 2:2 + B], g)
+    np.testing.assert_array_equal(m1[2:2 + B], m)
+    assert np.all(g1[:, :2] == 7.0) and np.all(g1[:, 2 + B:] == 7.0) and np.all(m1[:2] == 9) and np.all(m1[2 + B:] == 9)
+    g2, m2 = dest()
+    g2[:, 2:2 + B], m2[2:2 + B] = 0.0, 0               # (what no batch delivers stays as the skeleton has it: zero)
+    engine.drain(Stub(), True, g2, m2, 2, 2 + B, lambda u0, u1: told.append((u0, u1)))
+    assert waited == list(range(len(cuts) - 1)) and told == list(zip(cuts[:-1], cuts[1:]))
+    assert g1.tobytes() == g2.tobytes() and m1.tobytes() == m2.tobytes()
+    # mask only (the sharded call's dictionary): the form takes NO grid destination, so no grid cell is read or copied
+    class MaskOnly(Stub):
+        def wait_result_batch(self, k):
+            return Stub.wait_result_batch(self, k)[:4] + (None,) + Stub.wait_result_batch(self, k)[5:]
+    _, m3 = dest()
+    m3[2:2 + B] = 0
+    del waited[:]
+    engine.drain(MaskOnly(), True, None, m3, 2, 2 + B)
+    assert waited[::2] == list(range(len(cuts) - 1)) and m3.tobytes() == m1.tobytes()
+    _, m4 = dest()
+    engine.drain(Stub(), False, None, m4, 2, 2 + B)
+    assert m4.tobytes() == m1.tobytes()
