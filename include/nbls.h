@@ -260,6 +260,43 @@ int nbls_stream_results(nbls_handle* h, int32_t on);
 int nbls_result_batches(nbls_handle* h, int32_t* nbatches);
 int nbls_wait_result_batch(nbls_handle* h, int32_t k, int64_t* out4, const void** host_block);
 
+/* ---- several estimators on one pass's lags ---------------------------------------------------------------------
+ * Replaces "one whole call per ALPHA and per sub-array" (narrow_band_least_squares.py:110-124 returns sig_tau_array
+ * only for ALPHA == 1.0 and the dictionary only for ALPHA < 1.0; re-processing an array without the element LTS named
+ * is a third call): filter, screening and verification depend on neither ALPHA nor on which other elements are
+ * present, so one pass correlates the full array once and then solves every unit once per estimator.
+ * Estimator 0 is what nbls_set_geometry / nbls_plan / nbls_set_uncertainty describe.  nbls_set_estimators names up to
+ * 8 FURTHER ones, before nbls_plan; each is an array of `nkept` of the trace's elements (kept[]: 0-based, ascending, no
+ * repeats; all of them = the full array) with the tables of THAT array exactly as a pass over it alone would get them:
+ *   lts       FAST-LTS parameters (as for nbls_plan; starts index the sub-array's pairs), NULL for OLS
+ *   xij       [P'][2], pair_idx [P'][2] (element numbers 0..nkept-1, lexicographic), xpinv [2][P'], P' = nkept (nkept-1)/2
+ *   eig6      as nbls_set_uncertainty, NULL: no confidence intervals for this estimator
+ * The arrays are copied.  Everything is checked before the handle changes: NBLS_ERR_GEOMETRY for fewer than 3 kept
+ * elements (4 under LTS) or a collinear sub-array, NBLS_ERR_ARG for a bad index or table, NBLS_ERR_UNSUPPORTED for more
+ * than 8 estimators and together with several segments, window ranges or an RCCL communicator (a plan refuses those
+ * combinations too, whichever was set first).  n == 0 resets: the next plan is the plain pass again, launch for launch.
+ * A sub-array's solve reads compact copies [B][VL][P'] of its pairs' lags and maxima, gathered per unit batch behind the
+ * verifier; the solve kernels themselves are the ones of a plain pass.
+ * The results of estimator e (0 = the existing calls) come from the nbls_est_* forms of the result calls: the layout and
+ * block hold ceil(P'/8) mask bytes per cell, nbls_est_fetch gives lag / cmax / weights as [B][VL][P'].  A streamed pass
+ * delivers batch k of EVERY estimator before batch k+1 of any; each estimator has a pinned mirror of its own. */
+typedef struct {
+    const nbls_lts_params* lts;
+    int32_t nkept;
+    const int32_t* kept;
+    const double* xij;
+    const int32_t* pair_idx;
+    const double* xpinv;
+    const double* eig6;
+} nbls_estimator_desc;
+int nbls_set_estimators(nbls_handle* h, int32_t n, const nbls_estimator_desc* desc);
+int nbls_est_result_layout(nbls_handle* h, int32_t e, int64_t* out4);
+int nbls_est_fetch_packed(nbls_handle* h, int32_t e, void* out, int64_t nbytes);
+int nbls_est_fetch(nbls_handle* h, int32_t e, double* vel, double* baz, double* mdccm, double* sigma_tau, int32_t* nwin,
+                   int32_t* lag, double* cmax, uint8_t* weights, double* z);
+int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t e, double* vel_uncert, double* baz_uncert);
+int nbls_est_wait_result_batch(nbls_handle* h, int32_t e, int32_t k, int64_t* out4, const void** host_block);
+
 /* ---- multi-GPU: ONE grouped RCCL operation collects every GPU's result block ----------------------
  * Replaces the joblib fan-out / collection of narrow_band_least_squares_parallel()
  * (narrow_band_least_squares.py:285 and :291-320).  Bands (or window slices) are sharded by the host;

@@ -7,8 +7,9 @@ Same Python call surface as amiezzi/narrow_band_least_squares (+ ``lts_array.lts
 import sys as _sys
 
 from .narrow_band_least_squares import (narrow_band_least_squares, narrow_band_loop,
-                                        narrow_band_least_squares_parallel, narrow_band_least_squares_batch)
-from .lts_array import ltsva, ltsva_batch
+                                        narrow_band_least_squares_parallel, narrow_band_least_squares_batch,
+                                        narrow_band_least_squares_multi)
+from .lts_array import ltsva, ltsva_batch, ltsva_multi
 from .helpers import (get_freqlist, get_winlenlist, filter_data, make_float, get_rij,
                       write_txtfile, read_txtfile)
 from .stream import Stream, Trace, Stats
@@ -17,7 +18,7 @@ from .engine import resident_trace
 __all__ = ['narrow_band_least_squares', 'narrow_band_loop', 'narrow_band_least_squares_parallel',
            'ltsva', 'get_freqlist', 'get_winlenlist', 'filter_data', 'make_float', 'get_rij',
            'write_txtfile', 'read_txtfile', 'Stream', 'Trace', 'Stats', 'install_as_reference_modules', 'resident_trace',
-           'narrow_band_least_squares_batch', 'ltsva_batch']
+           'narrow_band_least_squares_batch', 'ltsva_batch', 'narrow_band_least_squares_multi', 'ltsva_multi']
 
 
 def install_as_reference_modules():

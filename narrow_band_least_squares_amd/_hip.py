@@ -22,8 +22,10 @@ EXPORTS = [
     'nbls_developer_build', 'nbls_set_trace_from', 'nbls_debug_lts_coop_breakdown', 'nbls_filter_segment',
     'nbls_set_filtered', 'nbls_load_result_block', 'nbls_stream_results', 'nbls_result_batches', 'nbls_wait_result_batch',
     'nbls_comm_set_library', 'nbls_set_uncertainty', 'nbls_fetch_uncertainty', 'nbls_expect_upload', 'nbls_abort_upload',
-    'nbls_set_segments', 'nbls_route_xcorr', 'nbls_route_table',
+    'nbls_set_segments', 'nbls_route_xcorr', 'nbls_route_table', 'nbls_set_estimators', 'nbls_est_result_layout',
+    'nbls_est_fetch_packed', 'nbls_est_fetch', 'nbls_est_fetch_uncertainty', 'nbls_est_wait_result_batch',
 ]
+MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
 NBLS_ERR_HIP, NBLS_ERR_NOMEM, NBLS_ERR_UNSUPPORTED, NBLS_ERR_COMM = -4, -5, -6, -7
@@ -42,6 +44,12 @@ class LtsParams(C.Structure):
         ('ncand', C.c_int32), ('xij_mad', C.c_double * 2), ('raw_factor', C.c_double),
         ('rew_table', C.POINTER(C.c_double)), ('quantile', C.c_double), ('zero_scale', C.c_double),
     ]
+
+
+class EstimatorDesc(C.Structure):
+    _fields_ = [('lts', C.POINTER(LtsParams)), ('nkept', C.c_int32), ('kept', C.POINTER(C.c_int32)),
+                ('xij', C.POINTER(C.c_double)), ('pair_idx', C.POINTER(C.c_int32)), ('xpinv', C.POINTER(C.c_double)),
+                ('eig6', C.POINTER(C.c_double))]
 
 
 class Timings(C.Structure):
@@ -126,6 +134,12 @@ def load_library(path=None):
     lib.nbls_sync.argtypes = [vp]
     fetch_args = [dp, dp, dp, dp, ip, ip, dp, u8p, dp]
     lib.nbls_fetch.argtypes = [vp] + fetch_args
+    lib.nbls_set_estimators.argtypes = [vp, C.c_int32, C.POINTER(EstimatorDesc)]
+    lib.nbls_est_result_layout.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+    lib.nbls_est_fetch_packed.argtypes = [vp, C.c_int32, C.c_void_p, C.c_int64]
+    lib.nbls_est_fetch.argtypes = [vp, C.c_int32] + fetch_args
+    lib.nbls_est_fetch_uncertainty.argtypes = [vp, C.c_int32, dp, dp]
+    lib.nbls_est_wait_result_batch.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -149,6 +163,52 @@ def load_library(path=None):
     if path is None:
         _lib = lib
     return lib
+
+
+def _lts_params(lts):
+    """dict from planner.lts_plan() -> (LtsParams, the arrays it points into)."""
+    starts = np.ascontiguousarray(lts['starts'], dtype=np.int32)
+    rew = _f64(lts['rew_table'])
+    p = LtsParams()
+    p.alpha = float(lts['alpha'])
+    p.h = int(lts['h'])
+    p.nstarts = int(starts.shape[0])
+    p.starts = _iptr(starts)
+    p.csteps = int(lts['csteps'])
+    p.csteps2 = int(lts['csteps2'])
+    p.ncand = int(lts['ncand'])
+    p.xij_mad[0] = float(lts['xij_mad'][0])
+    p.xij_mad[1] = float(lts['xij_mad'][1])
+    p.raw_factor = float(lts['raw_factor'])
+    p.rew_table = _dptr(rew)
+    p.quantile = float(lts['quantile'])
+    p.zero_scale = float(lts['zero_scale'])
+    return p, [starts, rew, p]
+
+
+def estimator_descs(ests):
+    """Dicts as ``Handle.set_estimators`` takes them -> (EstimatorDesc array, the arrays it points into, pair counts)."""
+    descs = (EstimatorDesc * max(1, len(ests)))()
+    keep, npairs = [], []
+    for d, e in zip(descs, ests):
+        kept = np.ascontiguousarray(e['kept'], dtype=np.int32)
+        xij, xpinv = _f64(e['xij']), _f64(e['xpinv'])
+        pair_idx = np.ascontiguousarray(e['pair_idx'], dtype=np.int32)
+        nk = len(kept)
+        if xij.shape != (nk * (nk - 1) // 2, 2) or xpinv.shape != (2, xij.shape[0]) or pair_idx.shape != xij.shape:
+            raise ValueError('set_estimators: the tables do not have the pair count of the kept elements')
+        d.nkept, d.kept, d.xij, d.pair_idx, d.xpinv = nk, _iptr(kept), _dptr(xij), _iptr(pair_idx), _dptr(xpinv)
+        keep += [kept, xij, xpinv, pair_idx]
+        if e.get('lts') is not None:
+            p, held = _lts_params(e['lts'])
+            d.lts = C.pointer(p)
+            keep += held
+        if e.get('eig6') is not None:
+            eig = _f64(e['eig6'])
+            d.eig6 = _dptr(eig)
+            keep.append(eig)
+        npairs.append(xij.shape[0])
+    return descs, keep, npairs
 
 
 def _dptr(a):
@@ -181,6 +241,7 @@ class Handle:
         self.nchans = self.npts = self.npairs = 0
         self.nbands = self.vector_len = 0
         self.nseg = 1
+        self.est_npairs = []            # pair counts of the further estimators (set_estimators)
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -294,24 +355,9 @@ class Handle:
         lp = None
         keep = [sos, tl, tr, winlen, wininc]
         if lts is not None:
-            starts = np.ascontiguousarray(lts['starts'], dtype=np.int32)
-            rew = _f64(lts['rew_table'])
-            p = LtsParams()
-            p.alpha = float(lts['alpha'])
-            p.h = int(lts['h'])
-            p.nstarts = int(starts.shape[0])
-            p.starts = _iptr(starts)
-            p.csteps = int(lts['csteps'])
-            p.csteps2 = int(lts['csteps2'])
-            p.ncand = int(lts['ncand'])
-            p.xij_mad[0] = float(lts['xij_mad'][0])
-            p.xij_mad[1] = float(lts['xij_mad'][1])
-            p.raw_factor = float(lts['raw_factor'])
-            p.rew_table = _dptr(rew)
-            p.quantile = float(lts['quantile'])
-            p.zero_scale = float(lts['zero_scale'])
+            p, held = _lts_params(lts)
             lp = C.byref(p)
-            keep += [starts, rew, p]
+            keep += held
         self._chk(self.lib.nbls_plan(self._h, nb, sos_p, nsec, int(bool(zero_phase)), _dptr(tl), _dptr(tr),
                                      len(tl), _iptr(winlen), _iptr(wininc), int(vector_len), lp,
                                      int(xcorr_impl)))
@@ -340,6 +386,16 @@ class Handle:
         self._chk(self.lib.nbls_set_segments(self._h, int(nseg)))
         self.nseg = int(nseg)
 
+    def set_estimators(self, estimators=()):
+        """Further estimators of the next plans (``nbls_set_estimators``), beside estimator 0 = what ``set_geometry`` /
+        ``plan`` describe: a sequence of dicts with ``kept`` (0-based element indices, ascending), ``xij``, ``pair_idx``,
+        ``xpinv`` of THAT array, ``lts`` (``planner.lts_plan`` dict, None for OLS) and ``eig6`` (``planner.uncertainty_frame``,
+        None: no confidence intervals).  Empty: reset to the plain pass."""
+        ests = list(estimators)
+        descs, keep, npairs = estimator_descs(ests)
+        self._chk(self.lib.nbls_set_estimators(self._h, len(ests), descs if ests else None))
+        self.est_npairs = npairs
+
     def set_window_ranges(self, first=None, count=None):
         """Per-band window slices for the next plan(s); None resets to "all windows"."""
         if first is None:
@@ -360,8 +416,12 @@ class Handle:
     def sync(self):
         self._chk(self.lib.nbls_sync(self._h))
 
-    def fetch(self, want_lag=False, want_cmax=False, want_weights=False, want_z=False, grids=True):
-        B, VL, P = self.nbands, self.vector_len, self.npairs
+    def _est_pairs(self, est):
+        return self.npairs if est == 0 else self.est_npairs[est - 1]
+
+    def fetch(self, want_lag=False, want_cmax=False, want_weights=False, want_z=False, grids=True, est=0):
+        """``est``: the estimator whose results are fetched (0: the plan's own; its lag / cmax / weights are (B, VL, P'))."""
+        B, VL, P = self.nbands, self.vector_len, self._est_pairs(est)
         if grids:
             g = np.empty((4, B, VL))               # one block: nbls_fetch moves the four grids in one copy
             out = dict(vel=g[0], baz=g[1], mdccm=g[2], sigma_tau=g[3], nwin=np.empty(B, dtype=np.int32))
@@ -371,20 +431,29 @@ class Handle:
         cmax = np.empty((B, VL, P)) if want_cmax else None
         wts = np.empty((B, VL, P), dtype=np.uint8) if want_weights else None
         z = np.empty((B, VL, 2)) if want_z else None
-        self._chk(self.lib.nbls_fetch(self._h, _dptr(out['vel']), _dptr(out['baz']), _dptr(out['mdccm']),
-                                      _dptr(out['sigma_tau']), _iptr(out['nwin']), _iptr(lag), _dptr(cmax),
-                                      _u8ptr(wts), _dptr(z)))
+        args = (_dptr(out['vel']), _dptr(out['baz']), _dptr(out['mdccm']), _dptr(out['sigma_tau']), _iptr(out['nwin']),
+                _iptr(lag), _dptr(cmax), _u8ptr(wts), _dptr(z))
+        if est == 0:
+            self._chk(self.lib.nbls_fetch(self._h, *args))
+        else:
+            self._chk(self.lib.nbls_est_fetch(self._h, int(est), *args))
         out.update(lag=lag, cmax=cmax, weights=wts, z=z)
         return out
 
-    def fetch_packed(self):
-        """One D2H copy of the result block -> dict(vel, baz, mdccm, sigma_tau (B, VL) float64 views of one
-        buffer, mask (B, VL, ceil(P/8)) uint8: bit k & 7 of byte k >> 3 = LTS weight of pair k)."""
+    def fetch_packed(self, est=0):
+        """One D2H copy of the result block (of estimator ``est``) -> dict(vel, baz, mdccm, sigma_tau (B, VL) float64 views
+        of one buffer, mask (B, VL, ceil(P/8)) uint8: bit k & 7 of byte k >> 3 = LTS weight of pair k)."""
         lay = (C.c_int64 * 4)()
-        self._chk(self.lib.nbls_result_layout(self._h, lay))
+        if est == 0:
+            self._chk(self.lib.nbls_result_layout(self._h, lay))
+        else:
+            self._chk(self.lib.nbls_est_result_layout(self._h, int(est), lay))
         cells, mb, total, moff = lay[0], lay[1], lay[2], lay[3]
         buf = np.empty(total // 8 + 1, dtype=np.float64)       # 8-byte aligned
-        self._chk(self.lib.nbls_fetch_packed(self._h, buf.ctypes.data, total))
+        if est == 0:
+            self._chk(self.lib.nbls_fetch_packed(self._h, buf.ctypes.data, total))
+        else:
+            self._chk(self.lib.nbls_est_fetch_packed(self._h, int(est), buf.ctypes.data, total))
         B, VL = self.nbands, self.vector_len
         grids = buf[:4 * cells].reshape(4, B, VL)
         mask = buf.view(np.uint8)[moff:moff + cells * mb].reshape(B, VL, mb)
@@ -396,10 +465,13 @@ class Handle:
         e = None if eig6 is None else _f64(eig6)
         self._chk(self.lib.nbls_set_uncertainty(self._h, _dptr(e)))
 
-    def fetch_uncertainty(self):
+    def fetch_uncertainty(self, est=0):
         """-> (vel_uncert, baz_uncert), each (nbands, vector_len)."""
         out = np.empty((2, self.nbands, self.vector_len))
-        self._chk(self.lib.nbls_fetch_uncertainty(self._h, _dptr(out[0]), _dptr(out[1])))
+        if est == 0:
+            self._chk(self.lib.nbls_fetch_uncertainty(self._h, _dptr(out[0]), _dptr(out[1])))
+        else:
+            self._chk(self.lib.nbls_est_fetch_uncertainty(self._h, int(est), _dptr(out[0]), _dptr(out[1])))
         return out[0], out[1]
 
     def stream_results(self, on=True):
@@ -412,15 +484,18 @@ class Handle:
         self._chk(self.lib.nbls_result_batches(self._h, C.byref(n)))
         return n.value
 
-    def wait_result_batch(self, k):
+    def wait_result_batch(self, k, est=0):
         """Wait for batch ``k`` of the queued pass -> (u0, u1, c0, c1, grids (4, B*VL) float64, mask (B*VL, MB) uint8):
         the batch's units [u0, u1) own the cells [c0, c1) of the two VIEWS of the library's pinned mirror (valid until
         the handle's next pass; cells of batches not yet waited for are undefined)."""
         out = (C.c_int64 * 4)()
         blk = C.c_void_p()
-        self._chk(self.lib.nbls_wait_result_batch(self._h, int(k), out, C.byref(blk)))
+        if est == 0:
+            self._chk(self.lib.nbls_wait_result_batch(self._h, int(k), out, C.byref(blk)))
+        else:
+            self._chk(self.lib.nbls_est_wait_result_batch(self._h, int(est), int(k), out, C.byref(blk)))
         cells = self.nbands * self.vector_len
-        mb = (self.npairs + 7) // 8
+        mb = (self._est_pairs(est) + 7) // 8
         raw = (C.c_uint8 * (cells * (32 + mb))).from_address(blk.value)
         buf = np.frombuffer(raw, dtype=np.uint8)
         grids = buf[:32 * cells].view(np.float64).reshape(4, cells)

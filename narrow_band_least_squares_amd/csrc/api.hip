@@ -350,6 +350,12 @@ void nbls_destroy(nbls_handle* h) {
         std::unordered_set<const void*> in_arena;       // members that point into d_parena
         for (const void* m : h->arena_owned) in_arena.insert(*(void* const*)m);
         for (void* b : bufs) if (b && !in_arena.count(b)) (void)hipFree(b);
+        for (nbls_estimator& x : h->est) {
+            void* eb[] = {x.d_xij, x.d_xpinv, x.d_xs, x.d_xc, x.d_xss, x.d_rew, x.d_starts, x.d_kept_pair,
+                          x.d_lag, x.d_cmax, x.d_z, x.d_unc, x.d_wts, x.d_res};
+            for (void* b : eb) if (b && !in_arena.count(b)) (void)hipFree(b);
+            if (x.h_res) (void)hipHostFree(x.h_res);
+        }
         if (h->d_parena) (void)hipFree(h->d_parena);
     }
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
@@ -614,6 +620,84 @@ int nbls_set_window_ranges(nbls_handle* h, int32_t nbands, const int32_t* first,
     return NBLS_OK;
 }
 
+int nbls_set_estimators(nbls_handle* h, int32_t n, const nbls_estimator_desc* desc) {
+    if (!h) return NBLS_ERR_ARG;
+    if (n <= 0) {                                // reset: the next plan is the plain pass (the buffers stay for a later use)
+        h->nest = 0;
+        h->planned = false;
+        return NBLS_OK;
+    }
+    // everything is checked, and the new estimators are built beside the handle's, before the handle changes
+    if (!desc) return fail(h, NBLS_ERR_ARG, "nbls_set_estimators: NULL pointer");
+    if (n > NBLS_MAX_ESTIMATORS) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_set_estimators: at most 8 further estimators");
+    if (h->nseg > 1) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_set_estimators: not supported with several segments (nbls_set_segments)");
+    if (!h->win_first.empty()) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_set_estimators: not supported with window ranges (nbls_set_window_ranges)");
+    if (h->comm) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_set_estimators: not supported with an RCCL communicator (nbls_comm_*)");
+    if (!h->d_trace) return fail(h, NBLS_ERR_STATE, "nbls_set_estimators: no trace set (the element count is not known)");
+    const int E = h->nelem;
+    struct Built { std::vector<int32_t> kept, kept_pair, starts; std::vector<double> xij, xpinv, rew; };
+    std::vector<Built> built((size_t)n);
+    for (int e = 0; e < n; ++e) {
+        const nbls_estimator_desc& d = desc[e];
+        const std::string who = "nbls_set_estimators: estimator " + std::to_string(e + 1) + ": ";
+        if (!d.kept || !d.xij || !d.pair_idx || !d.xpinv) return fail(h, NBLS_ERR_ARG, who + "NULL pointer");
+        if (d.nkept < 0 || d.nkept > E) return fail(h, NBLS_ERR_ARG, who + "more kept elements than the trace has");
+        for (int i = 0; i < d.nkept; ++i) {
+            if (d.kept[i] < 0 || d.kept[i] >= E) return fail(h, NBLS_ERR_ARG, who + "element index out of range");
+            if (i > 0 && d.kept[i] <= d.kept[i - 1]) return fail(h, NBLS_ERR_ARG, who + "element indices must ascend without repeats");
+        }
+        if (d.nkept < 3) return fail(h, NBLS_ERR_GEOMETRY, who + "need at least 3 array elements");
+        if (d.lts && d.nkept < 4) return fail(h, NBLS_ERR_GEOMETRY, who + "LTS needs at least 4 array elements");
+        const int K = d.nkept, P = K * (K - 1) / 2;
+        for (int i = 0, k = 0; i < K - 1; ++i)
+            for (int j = i + 1; j < K; ++j, ++k)
+                if (d.pair_idx[2 * k] != i || d.pair_idx[2 * k + 1] != j)
+                    return fail(h, NBLS_ERR_ARG, who + "pair_idx is not the lexicographic pair list of the kept elements");
+        double sxx = 0, sxy = 0, syy = 0;
+        for (int k = 0; k < P; ++k) { sxx += d.xij[2*k]*d.xij[2*k]; sxy += d.xij[2*k]*d.xij[2*k+1]; syy += d.xij[2*k+1]*d.xij[2*k+1]; }
+        const double det = sxx * syy - sxy * sxy;
+        if (!(det > 1e-12 * (sxx + syy) * (sxx + syy))) return fail(h, NBLS_ERR_GEOMETRY, who + "co-array is rank deficient (collinear array)");
+        if (d.lts) {
+            const nbls_lts_params* l = d.lts;
+            if (l->nstarts < 1 || l->nstarts > NBLS_MAX_STARTS || !l->starts || !l->rew_table) return fail(h, NBLS_ERR_ARG, who + "bad LTS starts");
+            if (l->h < 2 || l->h > P) return fail(h, NBLS_ERR_ARG, who + "LTS h out of range");
+            if (l->ncand < 1 || l->ncand > NBLS_MAX_CAND) return fail(h, NBLS_ERR_ARG, who + "ncand out of range");
+            for (int i = 0; i < l->nstarts * 4; ++i)
+                if (l->starts[i] >= P) return fail(h, NBLS_ERR_ARG, who + "start index out of range");
+        }
+        if (d.eig6 && (!(d.eig6[0] > 0.0) || !(d.eig6[1] > 0.0))) return fail(h, NBLS_ERR_ARG, who + "the eigenvalues of X^T X must be positive");
+        Built& b = built[(size_t)e];
+        b.kept.assign(d.kept, d.kept + K);
+        if (K < E) {                             // pair (i, j) of the sub-array = pair (kept[i], kept[j]) of the full one
+            for (int i = 0; i < K - 1; ++i)
+                for (int j = i + 1; j < K; ++j) {
+                    const int a = d.kept[i], c = d.kept[j];
+                    b.kept_pair.push_back(a * (2 * E - a - 1) / 2 + (c - a - 1));
+                }
+        }
+        b.xij.assign(d.xij, d.xij + 2 * (size_t)P);
+        b.xpinv.assign(d.xpinv, d.xpinv + 2 * (size_t)P);
+        if (d.lts) {
+            b.starts.assign(d.lts->starts, d.lts->starts + (size_t)d.lts->nstarts * 4);
+            b.rew.assign(d.lts->rew_table, d.lts->rew_table + (size_t)P + 1);
+        }
+    }
+    for (int e = 0; e < n; ++e) {
+        nbls_estimator& x = h->est[e];
+        Built& b = built[(size_t)e];
+        x.kept.swap(b.kept); x.kept_pair.swap(b.kept_pair);
+        x.h_xij.swap(b.xij); x.h_xpinv.swap(b.xpinv); x.h_starts.swap(b.starts); x.h_rew.swap(b.rew);
+        x.lts = desc[e].lts != nullptr;
+        x.ltsp = nbls_lts_params{};
+        if (x.lts) { x.ltsp = *desc[e].lts; x.ltsp.starts = nullptr; x.ltsp.rew_table = nullptr; }
+        x.want_unc = desc[e].eig6 != nullptr;
+        for (int i = 0; i < 6; ++i) x.unc_par[i] = x.want_unc ? desc[e].eig6[i] : 0.0;
+    }
+    h->nest = n;
+    h->planned = false;
+    return NBLS_OK;
+}
+
 int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsections, int32_t zero_phase,
               const double* taper_left, const double* taper_right, int32_t taper_len,
               const int32_t* winlen, const int32_t* wininc, int32_t vector_len,
@@ -637,8 +721,13 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the RCCL gather (nbls_comm_*) is not supported with several segments");
     }
+    if (h->nest > 0 && (NS > 1 || !h->win_first.empty() || h->comm))
+        return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
+    for (int e = 0; e < h->nest; ++e)
+        if (!h->d_xij || h->est[e].kept.empty() || h->est[e].kept.back() >= E || ((int)h->est[e].kept.size() == E) != h->est[e].kept_pair.empty())
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: the further estimators (nbls_set_estimators) do not fit this trace's elements and geometry");
     if (NS > 1 && (E < 3 || E > 32))
         return fail(h, NBLS_ERR_GEOMETRY, "nbls_plan: " + std::to_string(E) + " elements per segment (3..32 supported)");
     // geometry is optional for a filter-only plan (filter_data()); execute checks it
@@ -888,6 +977,40 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         for (int i = 0; i < NS; ++i) { xss[2 * i] = xs[2 * (4 * i)]; xss[2 * i + 1] = xs[2 * (4 * i) + 1]; }
         if ((rc = alloc_copy(h, &h->d_xss, xss.data(), xss.size()))) return rc;
     }
+    for (int e = 0; e < h->nest; ++e) {         // the further estimators: their arrays' tables and their own result buffers
+        nbls_estimator& x = h->est[e];
+        const int Pe = (int)(x.h_xij.size() / 2);
+        if ((rc = alloc_copy(h, &x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
+        if ((rc = alloc_copy(h, &x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
+        if (!x.kept_pair.empty() && (rc = alloc_copy(h, &x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
+        if (x.lts) {                             // (as for estimator 0 above)
+            if ((rc = alloc_copy(h, &x.d_starts, x.h_starts.data(), x.h_starts.size()))) return rc;
+            if ((rc = alloc_copy(h, &x.d_rew, x.h_rew.data(), x.h_rew.size()))) return rc;
+            const int PP = Pe + 16;
+            std::vector<double> xs((size_t)PP * 2, 0.0), xc((size_t)PP, 0.0);
+            for (int k = 0; k < Pe; ++k) {
+                xs[2 * k] = x.h_xij[2 * k] / x.ltsp.xij_mad[0];
+                xs[2 * k + 1] = x.h_xij[2 * k + 1] / x.ltsp.xij_mad[1];
+                xc[k] = xs[2 * k] * xs[2 * k + 1];
+            }
+            if ((rc = alloc_copy(h, &x.d_xs, xs.data(), xs.size()))) return rc;
+            if ((rc = alloc_copy(h, &x.d_xc, xc.data(), xc.size()))) return rc;
+            const int NS4 = (Pe + 3) / 4;
+            std::vector<double> xss((size_t)(NS4 + 16) * 2, 0.0);
+            for (int i = 0; i < NS4; ++i) { xss[2 * i] = xs[2 * (4 * i)]; xss[2 * i + 1] = xs[2 * (4 * i) + 1]; }
+            if ((rc = alloc_copy(h, &x.d_xss, xss.data(), xss.size()))) return rc;
+        }
+        x.mask_bytes = (Pe + 7) / 8;
+        x.res_bytes = cells * (4 * sizeof(double) + (size_t)x.mask_bytes);
+        if ((rc = ensure(h, &x.d_res, &x.cap_res, x.res_bytes))) return rc;
+        if (!x.kept_pair.empty()) {
+            if ((rc = ensure(h, &x.d_lag, &x.cap_lag, cells * Pe * sizeof(int32_t)))) return rc;
+            if ((rc = ensure(h, &x.d_cmax, &x.cap_cmax, cells * Pe * sizeof(double)))) return rc;
+        }
+        if ((rc = ensure(h, &x.d_z, &x.cap_z, 2 * cells * sizeof(double)))) return rc;
+        if ((rc = ensure(h, &x.d_wts, &x.cap_wts, cells * Pe))) return rc;
+        if (x.want_unc && (rc = ensure(h, &x.d_unc, &x.cap_unc, 2 * cells * sizeof(double)))) return rc;
+    }
     // the arena's tables in one piece (copies queued before it on the same stream came from other parts of the staging arena)
     h->arena_mode = false;
     if (h->stage && h->d_parena && h->stage_used)
@@ -936,6 +1059,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (!h->rbatches.empty() && h->cstream) HIPCHK(h, hipStreamWaitEvent(h->stream, h->rev[2 * (h->rbatches.size() - 1) + 1], 0));
     h->rbatches.clear();
     HIPCHK(h, hipMemsetAsync(h->d_res, 0, h->res_bytes, h->stream));
+    for (int e = 0; e < h->nest; ++e) HIPCHK(h, hipMemsetAsync(h->est[e].d_res, 0, h->est[e].res_bytes, h->stream));
     if (h->prof) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (stage_mask & 1) {
         // every (band, channel) series is filtered on its own: the channels that have landed so far, then the next ones
@@ -974,6 +1098,14 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
             if (h->h_res) { (void)hipHostFree(h->h_res); h->h_res = nullptr; h->cap_hres = 0; }
             HIPCHK(h, hipHostMalloc((void**)&h->h_res, h->res_bytes ? h->res_bytes : 8, hipHostMallocDefault));
             h->cap_hres = h->res_bytes ? h->res_bytes : 8;
+        }
+        for (int e = 0; e < h->nest; ++e) {
+            nbls_estimator& x = h->est[e];
+            if (x.cap_hres >= x.res_bytes) continue;
+            HIPCHK(h, hipStreamSynchronize(h->cstream));
+            if (x.h_res) { (void)hipHostFree(x.h_res); x.h_res = nullptr; x.cap_hres = 0; }
+            HIPCHK(h, hipHostMalloc((void**)&x.h_res, x.res_bytes ? x.res_bytes : 8, hipHostMallocDefault));
+            x.cap_hres = x.res_bytes ? x.res_bytes : 8;
         }
     }
     // nbls_execute_after: this pass's filter may run beside the other handle's correlation stage (memory-bound next to
@@ -1017,14 +1149,19 @@ hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipSt
     hipError_t e = hipEventRecord(h->rev[2 * k], producer);
     if (e != hipSuccess) return e;
     if ((e = hipStreamWaitEvent(h->cstream, h->rev[2 * k], 0)) != hipSuccess) return e;
-    if (rb.c1 > rb.c0) {
+    // (estimator 0, then the further ones: the event behind them marks the batch of EVERY estimator)
+    for (int q = 0; q <= h->nest && rb.c1 > rb.c0; ++q) {
         const size_t cells = (size_t)h->nbands * h->vector_len;
+        unsigned char* const hres = q ? h->est[q - 1].h_res : h->h_res;
+        const unsigned char* const dres = q ? h->est[q - 1].d_res : h->d_res;
+        const size_t mbytes = (size_t)(q ? h->est[q - 1].mask_bytes : h->mask_bytes);
+        if (!hres) return hipErrorInvalidValue;
         for (int g = 0; g < 4; ++g) {
             const size_t off = ((size_t)g * cells + (size_t)rb.c0) * sizeof(double);
-            if ((e = hipMemcpyAsync(h->h_res + off, h->d_res + off, (size_t)(rb.c1 - rb.c0) * sizeof(double), hipMemcpyDeviceToHost, h->cstream)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(hres + off, dres + off, (size_t)(rb.c1 - rb.c0) * sizeof(double), hipMemcpyDeviceToHost, h->cstream)) != hipSuccess) return e;
         }
-        const size_t moff = 4 * cells * sizeof(double) + (size_t)rb.c0 * h->mask_bytes;
-        if ((e = hipMemcpyAsync(h->h_res + moff, h->d_res + moff, (size_t)(rb.c1 - rb.c0) * h->mask_bytes, hipMemcpyDeviceToHost, h->cstream)) != hipSuccess) return e;
+        const size_t moff = 4 * cells * sizeof(double) + (size_t)rb.c0 * mbytes;
+        if ((e = hipMemcpyAsync(hres + moff, dres + moff, (size_t)(rb.c1 - rb.c0) * mbytes, hipMemcpyDeviceToHost, h->cstream)) != hipSuccess) return e;
     }
     if ((e = hipEventRecord(h->rev[2 * k + 1], h->cstream)) != hipSuccess) return e;
     h->rbatches.push_back(rb);
@@ -1046,14 +1183,19 @@ int nbls_result_batches(nbls_handle* h, int32_t* nbatches) {
 }
 
 int nbls_wait_result_batch(nbls_handle* h, int32_t k, int64_t* out4, const void** host_block) {
+    return nbls_est_wait_result_batch(h, 0, k, out4, host_block);
+}
+
+int nbls_est_wait_result_batch(nbls_handle* h, int32_t est, int32_t k, int64_t* out4, const void** host_block) {
     if (!h) return NBLS_ERR_ARG;
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_wait_result_batch: no such estimator");
     if (!h->stream_results || k < 0 || (size_t)k >= h->rbatches.size())
         return fail(h, NBLS_ERR_STATE, "nbls_wait_result_batch: no such batch (nbls_stream_results + nbls_execute first)");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipEventSynchronize(h->rev[2 * (size_t)k + 1]));
     const nbls_handle::result_batch& rb = h->rbatches[(size_t)k];
     if (out4) { out4[0] = rb.u0; out4[1] = rb.u1; out4[2] = rb.c0; out4[3] = rb.c1; }
-    if (host_block) *host_block = h->h_res;
+    if (host_block) *host_block = est ? h->est[est - 1].h_res : h->h_res;
     return NBLS_OK;
 }
 
@@ -1100,14 +1242,22 @@ int nbls_sync(nbls_handle* h) {
 
 int nbls_fetch(nbls_handle* h, double* vel, double* baz, double* mdccm, double* sigma_tau, int32_t* nwin,
                int32_t* lag, double* cmax, uint8_t* weights, double* z) {
+    return nbls_est_fetch(h, 0, vel, baz, mdccm, sigma_tau, nwin, lag, cmax, weights, z);
+}
+
+int nbls_est_fetch(nbls_handle* h, int32_t est, double* vel, double* baz, double* mdccm, double* sigma_tau, int32_t* nwin,
+                   int32_t* lag, double* cmax, uint8_t* weights, double* z) {
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch: no plan");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch: no such estimator");
     { const int rc = finish_pass(h); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    const double* dg[4] = {h->d_vel, h->d_baz, h->d_mdccm, h->d_sig};
+    const nbls_solve_set s = nbls_solve_set_of(h, est);
+    const size_t P = (size_t)s.npairs;
+    const double* dg[4] = {s.d_vel, s.d_baz, s.d_mdccm, s.d_sig};
     double* hg[4] = {vel, baz, mdccm, sigma_tau};
     if (vel && baz == vel + cells && mdccm == baz + cells && sigma_tau == mdccm + cells) {
-        HIPCHK(h, copy_sync(h, vel, h->d_vel, 4 * cells * sizeof(double), hipMemcpyDeviceToHost));   // caller's grids are one block too
+        HIPCHK(h, copy_sync(h, vel, s.d_vel, 4 * cells * sizeof(double), hipMemcpyDeviceToHost));   // caller's grids are one block too
     } else {
         for (int g = 0; g < 4; ++g)
             if (hg[g]) HIPCHK(h, copy_sync(h, hg[g], dg[g], cells * sizeof(double), hipMemcpyDeviceToHost));
@@ -1127,19 +1277,22 @@ int nbls_fetch(nbls_handle* h, double* vel, double* baz, double* mdccm, double* 
     // would have written is zeros here, not the previous pass's values
     const bool ran_x = (h->last_stage_mask & 2) != 0, ran_s = (h->last_stage_mask & 4) != 0;
     if (lag) {
-        if (ran_x) { HIPCHK(h, copy_sync(h, lag, h->d_lag, cells * h->npairs * sizeof(int32_t), hipMemcpyDeviceToHost)); zero_uncomputed(lag, h->npairs * sizeof(int32_t)); }
-        else memset(lag, 0, cells * h->npairs * sizeof(int32_t));
+        // (a sub-array's compact rows are gathered behind the verifier as part of its solve)
+        const bool have = ran_x && (!s.d_kept_pair || ran_s);
+        if (have) { HIPCHK(h, copy_sync(h, lag, s.d_lag, cells * P * sizeof(int32_t), hipMemcpyDeviceToHost)); zero_uncomputed(lag, P * sizeof(int32_t)); }
+        else memset(lag, 0, cells * P * sizeof(int32_t));
     }
     if (cmax) {
-        if (ran_x) { HIPCHK(h, copy_sync(h, cmax, h->d_cmax, cells * h->npairs * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(cmax, h->npairs * sizeof(double)); }
-        else memset(cmax, 0, cells * h->npairs * sizeof(double));
+        const bool have = ran_x && (!s.d_kept_pair || ran_s);
+        if (have) { HIPCHK(h, copy_sync(h, cmax, s.d_cmax, cells * P * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(cmax, P * sizeof(double)); }
+        else memset(cmax, 0, cells * P * sizeof(double));
     }
     if (weights) {
-        if (ran_s) { HIPCHK(h, copy_sync(h, weights, h->d_wts, cells * h->npairs, hipMemcpyDeviceToHost)); zero_uncomputed(weights, (size_t)h->npairs); }
-        else memset(weights, 0, cells * h->npairs);
+        if (ran_s) { HIPCHK(h, copy_sync(h, weights, s.d_wts, cells * P, hipMemcpyDeviceToHost)); zero_uncomputed(weights, P); }
+        else memset(weights, 0, cells * P);
     }
     if (z) {
-        if (ran_s) { HIPCHK(h, copy_sync(h, z, h->d_z, 2 * cells * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(z, 2 * sizeof(double)); }
+        if (ran_s) { HIPCHK(h, copy_sync(h, z, s.d_z, 2 * cells * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(z, 2 * sizeof(double)); }
         else memset(z, 0, 2 * cells * sizeof(double));
     }
     return NBLS_OK;
@@ -1157,16 +1310,22 @@ int nbls_set_uncertainty(nbls_handle* h, const double* eig6) {
 }
 
 int nbls_fetch_uncertainty(nbls_handle* h, double* vel_uncert, double* baz_uncert) {
+    return nbls_est_fetch_uncertainty(h, 0, vel_uncert, baz_uncert);
+}
+
+int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t est, double* vel_uncert, double* baz_uncert) {
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_uncertainty: no plan");
-    if (!h->want_unc || !h->d_unc) return fail(h, NBLS_ERR_STATE, "nbls_fetch_uncertainty: nbls_set_uncertainty before nbls_plan");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_uncertainty: no such estimator");
+    const nbls_solve_set s = nbls_solve_set_of(h, est);
+    if (!s.want_unc || !s.d_unc) return fail(h, NBLS_ERR_STATE, "nbls_fetch_uncertainty: nbls_set_uncertainty (or the estimator's eig6) before nbls_plan");
     { const int rc = finish_pass(h); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len;
     double* outs[2] = {vel_uncert, baz_uncert};
     for (int g = 0; g < 2; ++g) {
         if (!outs[g]) continue;
         if (!(h->last_stage_mask & 4)) { memset(outs[g], 0, cells * sizeof(double)); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], h->d_unc + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(h, copy_sync(h, outs[g], s.d_unc + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
         // rows of windows this plan did not compute are zeros, like the grids
         for (int b = 0; b < h->nbands; ++b) {
             const int64_t first = (int)h->woff.size() == h->nbands ? h->woff[b] : 0, n = h->nwin[b];
@@ -1236,22 +1395,30 @@ int nbls_device_results(nbls_handle* h, void** ptrs, int64_t* bytes_per_grid) {
     return NBLS_OK;
 }
 
-int nbls_result_layout(nbls_handle* h, int64_t* out4) {
+int nbls_result_layout(nbls_handle* h, int64_t* out4) { return nbls_est_result_layout(h, 0, out4); }
+
+int nbls_est_result_layout(nbls_handle* h, int32_t est, int64_t* out4) {
     if (!h || !out4) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_result_layout: no plan");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_result_layout: no such estimator");
     out4[0] = (int64_t)h->nbands * h->vector_len;
-    out4[1] = h->mask_bytes;
-    out4[2] = (int64_t)h->res_bytes;
+    out4[1] = est ? h->est[est - 1].mask_bytes : h->mask_bytes;
+    out4[2] = (int64_t)(est ? h->est[est - 1].res_bytes : h->res_bytes);
     out4[3] = (int64_t)(4 * sizeof(double)) * out4[0];      // byte offset of the mask
     return NBLS_OK;
 }
 
-int nbls_fetch_packed(nbls_handle* h, void* out, int64_t nbytes) {
+int nbls_fetch_packed(nbls_handle* h, void* out, int64_t nbytes) { return nbls_est_fetch_packed(h, 0, out, nbytes); }
+
+int nbls_est_fetch_packed(nbls_handle* h, int32_t est, void* out, int64_t nbytes) {
     if (!h || !out) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_packed: no plan");
-    if (nbytes != (int64_t)h->res_bytes) return fail(h, NBLS_ERR_ARG, "nbls_fetch_packed: size does not match nbls_result_layout");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_packed: no such estimator");
+    const unsigned char* dres = est ? h->est[est - 1].d_res : h->d_res;
+    const size_t rbytes = est ? h->est[est - 1].res_bytes : h->res_bytes;
+    if (nbytes != (int64_t)rbytes) return fail(h, NBLS_ERR_ARG, "nbls_fetch_packed: size does not match nbls_result_layout");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(out, h->d_res, h->res_bytes, hipMemcpyDeviceToHost, h->stream));   // ordered after the pass
+    HIPCHK(h, hipMemcpyAsync(out, dres, rbytes, hipMemcpyDeviceToHost, h->stream));   // ordered after the pass
     return finish_pass(h);
 }
 

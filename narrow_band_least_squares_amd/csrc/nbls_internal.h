@@ -60,6 +60,66 @@ struct nbls_options {
 // Consecutive bands of one window length: the unit of the correlator choice (nbls_plan / nbls_launch_xcorr).
 struct nbls_wgroup { int b0, b1, W; int64_t u0, u1; bool screen; };
 
+// What one solve of a pass reads and writes: the geometry and LTS tables of ONE array (the full one or a sub-array),
+// the lag / cmax rows it takes them from and the result block it fills.  Estimator 0 is what nbls_set_geometry and
+// nbls_plan describe (nbls_solve_set_of copies the handle's members); further estimators (nbls_set_estimators) own theirs.
+struct nbls_solve_set {
+    int npairs = 0;
+    const double* d_xij = nullptr;     // [P'][2]
+    const double* d_xpinv = nullptr;   // [2][P']
+    bool lts = false;
+    nbls_lts_params ltsp{};
+    const double* d_xs = nullptr;
+    const double* d_xc = nullptr;
+    const double* d_xss = nullptr;
+    const int32_t* d_starts = nullptr;
+    const double* d_rew = nullptr;
+    bool want_unc = false;
+    double unc_par[6] = {0, 0, 0, 0, 0, 0};
+    double* d_unc = nullptr;           // [2][B][VL]
+    // a sub-array's solve reads compact copies of its pairs' rows (gather_pairs_kernel): d_lag / d_cmax are then the
+    // estimator's own [B][VL][P'] buffers, filled per unit batch from the handle's through d_kept_pair [P']
+    const int32_t* d_kept_pair = nullptr;
+    int32_t* d_lag = nullptr;          // [B][VL][P']
+    double* d_cmax = nullptr;
+    double* d_vel = nullptr;           // [B][VL] (views into d_res)
+    double* d_baz = nullptr;
+    double* d_mdccm = nullptr;
+    double* d_sig = nullptr;
+    uint8_t* d_mask = nullptr;
+    double* d_z = nullptr;
+    uint8_t* d_wts = nullptr;
+    int mask_bytes = 0;
+    unsigned char* d_res = nullptr;    // result block, layout as nbls_handle::d_res
+    size_t res_bytes = 0;
+    unsigned char* h_res = nullptr;    // its pinned mirror (streamed passes)
+};
+
+// A further estimator of the pass (nbls_set_estimators): host copies of what the caller described, the device tables
+// nbls_plan makes of them, and the buffers of its own results.
+struct nbls_estimator {
+    std::vector<int32_t> kept;         // element indices, ascending
+    std::vector<int32_t> kept_pair;    // [P']: index of pair k of the sub-array in the full array's pair list (empty: all elements kept)
+    std::vector<double> h_xij, h_xpinv;
+    bool lts = false;
+    nbls_lts_params ltsp{};            // starts / rew_table point into the two vectors below
+    std::vector<int32_t> h_starts;
+    std::vector<double> h_rew;
+    bool want_unc = false;
+    double unc_par[6] = {0, 0, 0, 0, 0, 0};
+    // device side
+    double *d_xij = nullptr, *d_xpinv = nullptr, *d_xs = nullptr, *d_xc = nullptr, *d_xss = nullptr, *d_rew = nullptr;
+    int32_t *d_starts = nullptr, *d_kept_pair = nullptr;
+    int32_t* d_lag = nullptr;
+    double *d_cmax = nullptr, *d_z = nullptr, *d_unc = nullptr;
+    uint8_t* d_wts = nullptr;
+    unsigned char *d_res = nullptr, *h_res = nullptr;
+    size_t cap_lag = 0, cap_cmax = 0, cap_z = 0, cap_unc = 0, cap_wts = 0, cap_res = 0, cap_hres = 0, res_bytes = 0;
+    int mask_bytes = 0;
+};
+
+#define NBLS_MAX_ESTIMATORS 8      // further estimators of one pass, beside estimator 0
+
 struct nbls_handle {
     int device = 0;
     nbls_options opt;
@@ -233,6 +293,10 @@ struct nbls_handle {
     double* d_xc = nullptr;        // [P] c0*c1 of the standardised co-array; d_xs and d_xc are padded by 16 pairs (solve_bucket.inc reads one block ahead)
     size_t cap_starts = 0;
 
+    // ---- further estimators of the pass (nbls_set_estimators); nest == 0: the plain pass ----
+    int nest = 0;
+    nbls_estimator est[NBLS_MAX_ESTIMATORS];
+
     // ---- profiling ----
     bool prof = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -251,6 +315,10 @@ hipError_t nbls_launch_xcorr(nbls_handle* h);
 hipError_t nbls_launch_solve(nbls_handle* h);
 hipError_t nbls_launch_solve_range(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// the solve set of estimator e of the handle's plan (0: the handle's own geometry, LTS plan and result block)
+nbls_solve_set nbls_solve_set_of(const nbls_handle* h, int e);
+// [gather ->] solve -> [uncertainty ->] pack of units [u0, u0 + nu) for one solve set
+hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);
 hipError_t nbls_launch_probe_mfma(nbls_handle* h, const double* da, const double* db, double* dout);

@@ -1343,74 +1343,176 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const uint8_t* wts, u
     mask[o * MB + mb] = (uint8_t)m;
 }
 
-static hipError_t solve_range_impl(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// The rows of a sub-array's pairs, compact: lag_c / cmax_c [cell][Pc] = lag / cmax [cell][kept_pair[k]] for the units
+// [u0, u0 + nunits) (an estimator that leaves elements out, nbls_set_estimators; the solve kernels then run on the compact
+// rows with npairs = Pc).  A pure copy: one wave per unit and trip, the unit's P lags and maxima read coalesced into the
+// wave's LDS rows, the map held in LDS for the workgroup's life, the Pc kept values written with plain vector stores.
+// Every wave of a workgroup makes the same number of trips (the barriers are uniform).  Dynamic LDS:
+// GATHER_WAVES * P * 12 + Pc * 4 bytes (26 KB at 32 elements).
+constexpr int GATHER_WAVES = 4;
+__global__ __launch_bounds__(GATHER_WAVES * 64) void gather_pairs_kernel(const int32_t* __restrict__ lag, const double* __restrict__ cmax,
+                                                                         int32_t* __restrict__ lag_c, double* __restrict__ cmax_c,
+                                                                         const int32_t* __restrict__ kept_pair,
+                                                                         const int32_t* __restrict__ unit_band,
+                                                                         const int32_t* __restrict__ unit_win, int vector_len, int P,
+                                                                         int Pc, int u0, int nunits) {
+    extern __shared__ double gather_lds[];
+    double* row_c = gather_lds;                                          // [GATHER_WAVES][P]
+    int32_t* row_l = (int32_t*)(gather_lds + GATHER_WAVES * P);          // [GATHER_WAVES][P]
+    int32_t* map = row_l + GATHER_WAVES * P;                             // [Pc]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = threadIdx.x; k < Pc; k += GATHER_WAVES * 64) map[k] = kept_pair[k];
+    double* rc = row_c + wave * P;
+    int32_t* rl = row_l + wave * P;
+    for (int base = blockIdx.x * GATHER_WAVES; base < nunits; base += gridDim.x * GATHER_WAVES) {
+        const int ul = base + wave;
+        const bool live = ul < nunits;
+        int64_t o = 0;
+        if (live) {
+            const int u = u0 + ul;
+            o = (int64_t)unit_band[u] * vector_len + unit_win[u];
+            for (int k = lane; k < P; k += 64) { rl[k] = lag[o * P + k]; rc[k] = cmax[o * P + k]; }
+        }
+        __syncthreads();
+        if (live)
+            for (int k = lane; k < Pc; k += 64) {
+                const int src = map[k];
+                lag_c[o * Pc + k] = rl[src];
+                cmax_c[o * Pc + k] = rc[src];
+            }
+        __syncthreads();
+    }
+}
 
-hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
+static hipError_t solve_range_impl(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st);
+
+static hipError_t pack_weights_of(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
-    const int MB = h->mask_bytes;
+    const int MB = s.mask_bytes;
     const int64_t items = nu * MB;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, h->d_wts, h->d_mask,
-                       h->d_unit_band, h->d_unit_win, h->vector_len, h->npairs, MB, (int)u0, (int)nu);
+    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s.d_wts, s.d_mask,
+                       h->d_unit_band, h->d_unit_win, h->vector_len, s.npairs, MB, (int)u0, (int)nu);
     return hipGetLastError();
 }
 
-hipError_t nbls_launch_solve_range(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
-    hipError_t e = solve_range_impl(h, u0, nu, st);
-    if (e != hipSuccess) return e;
-    if (h->want_unc && h->d_unc && nu > 0) {
+hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
+    return pack_weights_of(h, nbls_solve_set_of(h, 0), u0, nu, st);
+}
+
+nbls_solve_set nbls_solve_set_of(const nbls_handle* h, int e) {
+    nbls_solve_set s;
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    if (e <= 0) {
+        s.npairs = h->npairs;
+        s.d_xij = h->d_xij; s.d_xpinv = h->d_xpinv;
+        s.lts = h->lts; s.ltsp = h->ltsp;
+        s.d_xs = h->d_xs; s.d_xc = h->d_xc; s.d_xss = h->d_xss; s.d_starts = h->d_starts; s.d_rew = h->d_rew;
+        s.want_unc = h->want_unc;
+        for (int i = 0; i < 6; ++i) s.unc_par[i] = h->unc_par[i];
+        s.d_unc = h->d_unc;
+        s.d_lag = h->d_lag; s.d_cmax = h->d_cmax;
+        s.d_vel = h->d_vel; s.d_baz = h->d_baz; s.d_mdccm = h->d_mdccm; s.d_sig = h->d_sig; s.d_mask = h->d_mask;
+        s.d_z = h->d_z; s.d_wts = h->d_wts;
+        s.mask_bytes = h->mask_bytes;
+        s.d_res = h->d_res; s.res_bytes = h->res_bytes; s.h_res = h->h_res;
+        return s;
+    }
+    const nbls_estimator& x = h->est[e - 1];
+    s.npairs = (int)(x.h_xij.size() / 2);
+    s.d_xij = x.d_xij; s.d_xpinv = x.d_xpinv;
+    s.lts = x.lts; s.ltsp = x.ltsp;
+    s.d_xs = x.d_xs; s.d_xc = x.d_xc; s.d_xss = x.d_xss; s.d_starts = x.d_starts; s.d_rew = x.d_rew;
+    s.want_unc = x.want_unc;
+    for (int i = 0; i < 6; ++i) s.unc_par[i] = x.unc_par[i];
+    s.d_unc = x.d_unc;
+    if (x.kept_pair.empty()) { s.d_lag = h->d_lag; s.d_cmax = h->d_cmax; }          // the full array: the pass's own rows
+    else { s.d_kept_pair = x.d_kept_pair; s.d_lag = x.d_lag; s.d_cmax = x.d_cmax; }
+    s.d_vel = (double*)x.d_res;
+    s.d_baz = s.d_vel + cells; s.d_mdccm = s.d_baz + cells; s.d_sig = s.d_mdccm + cells;
+    s.d_mask = x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr;
+    s.d_z = x.d_z; s.d_wts = x.d_wts;
+    s.mask_bytes = x.mask_bytes;
+    s.d_res = x.d_res; s.res_bytes = x.res_bytes; s.h_res = x.h_res;
+    return s;
+}
+
+hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st) {
+    hipError_t e;
+    if (s.d_kept_pair && nu > 0) {
+        const int P = h->npairs, Pc = s.npairs;
+        const size_t shm = (size_t)GATHER_WAVES * P * (sizeof(double) + sizeof(int32_t)) + (size_t)Pc * sizeof(int32_t);
+        int64_t grid = (nu + GATHER_WAVES - 1) / GATHER_WAVES;
+        const int64_t cap = (int64_t)(h->num_cus > 0 ? h->num_cus : 256) * 8;       // a few trips per wave: the map is loaded once
+        if (grid > cap) grid = cap;
+        hipLaunchKernelGGL(gather_pairs_kernel, dim3((unsigned)grid), dim3(GATHER_WAVES * 64), shm, st, (const int32_t*)h->d_lag,
+                           (const double*)h->d_cmax, s.d_lag, s.d_cmax, s.d_kept_pair, (const int32_t*)h->d_unit_band,
+                           (const int32_t*)h->d_unit_win, h->vector_len, P, Pc, (int)u0, (int)nu);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if ((e = solve_range_impl(h, s, u0, nu, st)) != hipSuccess) return e;
+    if (s.want_unc && s.d_unc && nu > 0) {
         UArgs a{};
         const size_t cells = (size_t)h->nbands * h->vector_len;
-        a.z = h->d_z; a.sig = h->d_sig; a.vunc = h->d_unc; a.bunc = h->d_unc + cells;
+        a.z = s.d_z; a.sig = s.d_sig; a.vunc = s.d_unc; a.bunc = s.d_unc + cells;
         a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
         a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
-        a.ev0 = h->unc_par[0]; a.ev1 = h->unc_par[1];
-        a.r00 = h->unc_par[2]; a.r01 = h->unc_par[3]; a.r10 = h->unc_par[4]; a.r11 = h->unc_par[5];
+        a.ev0 = s.unc_par[0]; a.ev1 = s.unc_par[1];
+        a.r00 = s.unc_par[2]; a.r01 = s.unc_par[3]; a.r10 = s.unc_par[4]; a.r11 = s.unc_par[5];
         hipLaunchKernelGGL(uncertainty_kernel, dim3((unsigned)((nu + 63) / 64)), dim3(64), 0, st, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    return nbls_launch_pack_weights(h, u0, nu, st);
+    return pack_weights_of(h, s, u0, nu, st);
 }
 
-static hipError_t solve_range_impl(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
+// Every estimator of the pass, one after the other on `st`: estimator 0, then the further ones (nbls_set_estimators).
+hipError_t nbls_launch_solve_range(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
+    for (int e = 0; e <= h->nest; ++e) {
+        const hipError_t err = nbls_launch_solve_set(h, nbls_solve_set_of(h, e), u0, nu, st);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+static hipError_t solve_range_impl(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
     SArgs a{};
     a.u0 = (int)u0;
-    a.lag = h->d_lag;
-    a.cmax = h->d_cmax;
-    a.npairs = h->npairs;
+    a.lag = s.d_lag;
+    a.cmax = s.d_cmax;
+    a.npairs = s.npairs;
     a.vector_len = h->vector_len;
     a.unit_off = h->d_unit_off;
     a.win_off = h->d_win_off;
     a.unit_band = h->d_unit_band;
     a.unit_win = h->d_unit_win;
     a.fs = h->fs;
-    a.xij = h->d_xij;
-    a.xpinv = h->d_xpinv;
-    a.vel = h->d_vel;
-    a.baz = h->d_baz;
-    a.mdccm = h->d_mdccm;
-    a.sig = h->d_sig;
-    a.z = h->d_z;
-    a.wts = h->d_wts;
+    a.xij = s.d_xij;
+    a.xpinv = s.d_xpinv;
+    a.vel = s.d_vel;
+    a.baz = s.d_baz;
+    a.mdccm = s.d_mdccm;
+    a.sig = s.d_sig;
+    a.z = s.d_z;
+    a.wts = s.d_wts;
     const int nunits = (int)nu;
-    if (!h->lts) {
-        const int sp = h->npairs <= 64 ? h->npairs : 0;          // the lanes' MdCCM columns in LDS (<= 32 KB)
+    if (!s.lts) {
+        const int sp = s.npairs <= 64 ? s.npairs : 0;          // the lanes' MdCCM columns in LDS (<= 32 KB)
         hipLaunchKernelGGL(solve_ols_kernel, dim3((nunits + 63) / 64), dim3(64), (size_t)sp * 64 * sizeof(double), st, a, nunits, sp);
         return hipGetLastError();
     }
-    a.xs = h->d_xs;
-    a.starts = h->d_starts;
-    a.nstarts = h->ltsp.nstarts;
-    a.h = h->ltsp.h;
-    a.csteps = h->ltsp.csteps;
-    a.csteps2 = h->ltsp.csteps2;
-    a.ncand = h->ltsp.ncand;
-    a.xmad0 = h->ltsp.xij_mad[0];
-    a.xmad1 = h->ltsp.xij_mad[1];
-    a.raw_factor = h->ltsp.raw_factor;
-    a.rew = h->d_rew;
-    a.quantile = h->ltsp.quantile;
-    a.zero_scale = h->ltsp.zero_scale;
+    a.xs = s.d_xs;
+    a.starts = s.d_starts;
+    a.nstarts = s.ltsp.nstarts;
+    a.h = s.ltsp.h;
+    a.csteps = s.ltsp.csteps;
+    a.csteps2 = s.ltsp.csteps2;
+    a.ncand = s.ltsp.ncand;
+    a.xmad0 = s.ltsp.xij_mad[0];
+    a.xmad1 = s.ltsp.xij_mad[1];
+    a.raw_factor = s.ltsp.raw_factor;
+    a.rew = s.d_rew;
+    a.quantile = s.ltsp.quantile;
+    a.zero_scale = s.ltsp.zero_scale;
     a.nsample = h->opt.lts_sample_its > 0 ? h->opt.lts_sample_its : (h->opt.lts_sample_its < 0 ? 0 : 1000);
     a.stamps = nullptr;
     a.stamp_waves = 0;
@@ -1424,7 +1526,7 @@ static hipError_t solve_range_impl(nbls_handle* h, int64_t u0, int64_t nu, hipSt
         }
     }
     if (h->opt.lts_impl != 1) {
-        switch (h->npairs) {     // register-resident kernel for 4..8 elements (larger P spills registers)
+        switch (s.npairs) {     // register-resident kernel for 4..8 elements (larger P spills registers)
             case 6: return launch_fast<6, 4>(h, a, nunits, st);
             case 10: return launch_fast<10, 6>(h, a, nunits, st);
             case 15: return launch_fast<15, 9>(h, a, nunits, st);
@@ -1433,31 +1535,31 @@ static hipError_t solve_range_impl(nbls_handle* h, int64_t u0, int64_t nu, hipSt
             default: break;
         }
     }
-    if (h->opt.lts_impl == 0 && h->npairs <= NBLS_MAX_PAIRS && a.nstarts <= NBLS_MAX_STARTS && h->d_xc) {
+    if (h->opt.lts_impl == 0 && s.npairs <= NBLS_MAX_PAIRS && a.nstarts <= NBLS_MAX_STARTS && s.d_xc) {
         // one start per lane, bucket selection (solve_bucket.inc): every other pair count (9..32 elements).
         // Up to 255 pairs: u8 histogram counters and merging of identical subsets (three 4-wave workgroups per CU at
         // 120 pairs); beyond: u16 counters and no merging (it removes a tenth of the starts at 496 pairs and its masks
         // are what would keep a CU at ONE workgroup: two per CU let one unit's refinement run beside the next one's
         // C-steps).
-        const bool small = h->npairs <= 255;
+        const bool small = s.npairs <= 255;
         int threads = 256;
         if (h->opt.lts_coop_threads >= 64 && h->opt.lts_coop_threads <= 512) threads = h->opt.lts_coop_threads & ~63;
-        const size_t bshm = lts_bucket_lds_bytes(h->npairs, a.nstarts, threads / 64, small ? 4 : 2, small);
+        const size_t bshm = lts_bucket_lds_bytes(s.npairs, a.nstarts, threads / 64, small ? 4 : 2, small);
         if (bshm <= 160 * 1024) {
             const void* fn = small ? (const void*)solve_lts_bucket_kernel<4, true> : (const void*)solve_lts_bucket_kernel<2, false>;
             hipError_t be = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bshm);
             if (be != hipSuccess) return be;
             if (small)
-                hipLaunchKernelGGL((solve_lts_bucket_kernel<4, true>), dim3(nunits), dim3(threads), bshm, st, a, (const double*)h->d_xs, (const double*)h->d_xc, (const double*)h->d_xss, nunits);
+                hipLaunchKernelGGL((solve_lts_bucket_kernel<4, true>), dim3(nunits), dim3(threads), bshm, st, a, (const double*)s.d_xs, (const double*)s.d_xc, (const double*)s.d_xss, nunits);
             else
-                hipLaunchKernelGGL((solve_lts_bucket_kernel<2, false>), dim3(nunits), dim3(threads), bshm, st, a, (const double*)h->d_xs, (const double*)h->d_xc, (const double*)h->d_xss, nunits);
+                hipLaunchKernelGGL((solve_lts_bucket_kernel<2, false>), dim3(nunits), dim3(threads), bshm, st, a, (const double*)s.d_xs, (const double*)s.d_xc, (const double*)s.d_xss, nunits);
             return hipGetLastError();
         }
     }
     // cache |r_k| per lane in LDS when a workgroup's slab fits in half a CU's LDS
-    const bool absr = lts_lds_bytes(h->npairs, a.nstarts, true) <= 80 * 1024;
+    const bool absr = lts_lds_bytes(s.npairs, a.nstarts, true) <= 80 * 1024;
     a.use_absr = absr;
-    const size_t shm = lts_lds_bytes(h->npairs, a.nstarts, absr);
+    const size_t shm = lts_lds_bytes(s.npairs, a.nstarts, absr);
     if (shm > 160 * 1024) return hipErrorInvalidValue;
     hipError_t e;
     if (absr) {

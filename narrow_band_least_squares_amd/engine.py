@@ -553,13 +553,14 @@ def upload_trace(h, data, fs):
 
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
-           trace_ready=False, after=None, before_execute=None, stream=False, uncert=False):
+           trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
     ``trace_ready``: the caller has already uploaded the trace to ``h`` (``upload_trace``).  ``after``: the handle
     of the band group queued before this one (``Handle.execute``).  ``before_execute()``: called between plan and
-    execute (the caller joins its upload thread there)."""
+    execute (the caller joins its upload thread there).  ``estimators``: the further estimators of the pass
+    (``Handle.set_estimators``); a handle that still carries some from an earlier call is reset."""
     if upload:
         if trace_ready:
             pass
@@ -568,6 +569,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         else:
             upload_trace(h, data, prep.fs)
         h.set_geometry(prep.xij, prep.pair_idx, prep.xpinv)
+    if estimators or getattr(h, 'est_npairs', None):       # (behind the trace: the library checks the indices against its elements)
+        h.set_estimators(estimators or ())
     idx = np.arange(prep.nbands) if bands is None else np.asarray(bands, dtype=np.int64)
     sos = None if prep.sos is None else prep.sos[idx]
     if window_slice is not None:
@@ -810,6 +813,180 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     for h, b0, b1 in launched:
         collect(res, h, b0, b1, streamed, note)
     return res
+
+
+MAX_ESTIMATORS = 8        # estimators of one multi-estimator call
+
+
+def normalize_estimators(estimators, nchans):
+    """``ESTIMATORS`` of the multi-estimator calls -> list of ``(alpha float, remove tuple of ascending ints)``; a bare
+    number means ``(alpha, ())``.  ``ValueError`` (host-side, before any GPU work) for an empty list, more than
+    ``MAX_ESTIMATORS``, an ALPHA outside [0.5, 1], a ``remove`` index that is out of range, given twice or not ascending,
+    and fewer than 3 kept elements (4 under LTS)."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError('ESTIMATORS is empty: at least one (ALPHA, remove) estimator is needed')
+    if len(ests) > MAX_ESTIMATORS:
+        raise ValueError('%d estimators: at most %d in one call' % (len(ests), MAX_ESTIMATORS))
+    out = []
+    for i, e in enumerate(ests):
+        if isinstance(e, (tuple, list)):
+            if len(e) != 2:
+                raise ValueError('estimator %d: expected ALPHA or (ALPHA, remove)' % i)
+            alpha, remove = float(e[0]), tuple(e[1])
+        else:
+            alpha, remove = float(e), ()
+        if not (0.5 <= alpha <= 1.0):
+            raise ValueError('estimator %d: ALPHA must be in [0.5, 1.0].' % i)
+        idx = []
+        for r in remove:
+            if isinstance(r, bool) or int(r) != r:
+                raise ValueError('estimator %d: remove holds %r, not a trace index' % (i, r))
+            r = int(r)
+            if not (0 <= r < nchans):
+                raise ValueError('estimator %d: remove index %d is out of range for %d traces' % (i, r, nchans))
+            if idx and r <= idx[-1]:
+                raise ValueError('estimator %d: remove indices must ascend without repeats' % i)
+            idx.append(r)
+        kept = nchans - len(idx)
+        if kept < 3:
+            raise ValueError('estimator %d: %d elements kept, at least 3 are needed for the least squares estimate' % (i, kept))
+        if alpha < 1.0 and kept < 4:
+            raise ValueError('estimator %d: %d elements kept, at least 4 are needed for least trimmed squares' % (i, kept))
+        out.append((alpha, tuple(idx)))
+    return out
+
+
+def kept_elements(nchans, remove):
+    """The 0-based trace indices an estimator keeps, ascending."""
+    gone = set(remove)
+    return [i for i in range(nchans) if i not in gone]
+
+
+def kept_pair_map(nchans, remove):
+    """For every pair of the reduced array, in its own (lexicographic) order, the index of the same pair in the full
+    array's pair list (what ``gather_pairs_kernel`` follows; the library builds its own from the kept elements)."""
+    kept = kept_elements(nchans, remove)
+    return np.array([a * (2 * nchans - a - 1) // 2 + (c - a - 1) for n, a in enumerate(kept) for c in kept[n + 1:]],
+                    dtype=np.int32)
+
+
+class _EstimatorResults:
+    """What ``drain`` needs of a handle, for the results of estimator ``est`` of its pass."""
+
+    def __init__(self, h, est):
+        self.h, self.est = h, est
+        self.profiling = False            # (the events of the pass are read once, through estimator 0)
+
+    def fetch_packed(self):
+        return self.h.fetch_packed(est=self.est)
+
+    def result_batches(self):
+        return self.h.result_batches()
+
+    def wait_result_batch(self, k):
+        return self.h.wait_result_batch(k, est=self.est)
+
+
+def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators, filter_type=None, filter_order=None,
+                  filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_lag=False,
+                  want_cmax=False, host_overlap=None, units_done=None):
+    """``process`` for several estimators ``(alpha, remove)`` of ONE trace in one device pass -> a list of ``BandBatch``,
+    element e what ``process`` gives for ``alpha_e`` on the rows that ``remove_e`` leaves (``estimators`` as
+    ``normalize_estimators`` returns them; ``rijs[e]``: the (2, kept) geometry of estimator e, ``t0s[e]`` its start date).
+
+    The full array is filtered and correlated once; every unit is then solved once per estimator, a sub-array's on compact
+    copies of its pairs' lags (``nbls_set_estimators``).  Estimator 0 of the pass is the first estimator that removes
+    nothing — or, when every one removes something, an OLS solve of the full array whose rows are not returned.  Every
+    estimator's geometry goes through the host functions of a single call on its rows (``planner.co_array``, ``lts_plan``,
+    ``uncertainty_frame``).  The bands run in rounds where HBM is short (``max_bands_per_pass``); the rows come back in one
+    piece or, where ``stream_pays`` for the most demanding estimator, batch by batch — estimator by estimator, each through
+    ``drain``.  ``host_overlap(results)`` runs once the first pass is queued; ``units_done(e, res, u0, u1)`` when the
+    units [u0, u1) (flat over all bands) of estimator e are in ``results[e]``."""
+    rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
+    nchans, npts = _shape_of(rows)
+    nb = len(band_edges)
+    cap = max_bands_per_pass(nchans, npts)
+    if cap < 1 and not prefiltered:
+        raise ValueError('not even one filtered band of %d x %d samples fits the HBM budget of one pass' % (nchans, npts))
+    cap = max(1, cap)
+    full = next((i for i, (_, rm) in enumerate(estimators) if not rm), None)
+    order = ([full] if full is not None else []) + [i for i in range(len(estimators)) if i != full]
+    alpha0 = estimators[full][0] if full is not None else 1.0
+    rij0 = rijs[full] if full is not None else rijs[-1]        # (no full-array estimator: ``rijs`` ends with the full geometry)
+    first_est = 0 if full is not None else 1                   # device index of order[0]
+    extras = []
+    for i in (order[1:] if full is not None else order):
+        alpha, remove = estimators[i]
+        xij, pair_idx, xpinv = planner.co_array(rijs[i])
+        extras.append(dict(kept=kept_elements(nchans, remove), xij=xij, pair_idx=pair_idx, xpinv=xpinv,
+                           lts=planner.lts_plan(xij, alpha) if alpha < 1.0 else None,
+                           eig6=planner.uncertainty_frame(xij) if want_uncert else None))
+    W, inc, nwin, vector_len = plan_windows(npts, fs, winlens, winover, vector_len)
+    check_elements(nchans, alpha0)
+    results = [None] * len(estimators)
+    for i, (alpha, remove) in enumerate(estimators):
+        res = new_result(nchans - len(remove), alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax,
+                         want_uncert=want_uncert)
+        res.xij, res.pair_idx, _ = planner.co_array(rijs[i])
+        results[i] = res
+    streamed = stream_pays(min(a for a, _ in estimators), nwin, nchans * (nchans - 1) // 2)
+    cum = np.concatenate(([0], np.cumsum(nwin))).astype(np.int64)
+    h = get_handle(device, 0)
+    up, resident = start_upload(rows, fs, device)
+    prep, told = None, False
+    try:
+        for b0 in range(0, nb, cap):
+            b1 = min(nb, b0 + cap)
+            prep = prepare(nchans, npts, fs, rij0, band_edges[b0:b1], winlens[b0:b1], winover, alpha0, filter_type,
+                           filter_order, filter_ripple, vector_len, prefiltered, common=prep,
+                           windows=(W[b0:b1], inc[b0:b1], nwin[b0:b1], vector_len))
+            joins = up is not None and b0 == 0
+            try:
+                launch(h, rows, prep, trace_ready=joins or resident or b0 > 0, stream=streamed, uncert=want_uncert,
+                       before_execute=up.landed if (joins and not up.row_pipeline) else None, estimators=extras)
+            finally:
+                if joins:
+                    up.landed()
+            for res in results:
+                res.sos.extend(prep.sos_ret)
+                res.handle = h
+            if not told:                   # the pass is queued: host work that needs no GPU result
+                told = True
+                release_deferred()
+                grids = {}
+                for res, t0 in zip(results, t0s):
+                    if t0 not in grids:
+                        grids[t0] = time_grid(t0, fs, W, inc, nwin, vector_len)
+                    res.t = grids[t0]
+                if host_overlap is not None:
+                    host_overlap(results)
+            for n, i in enumerate(order):
+                res, est = results[i], n + first_est
+                view = h if est == 0 else _EstimatorResults(h, est)
+                done = None
+                if units_done is not None and streamed:
+                    done = functools.partial(_multi_units, units_done, i, res, int(cum[b0]))
+                drain(view, streamed, res.grids, res.mask, b0, b1, done)
+                if units_done is not None and not streamed:
+                    units_done(i, res, int(cum[b0]), int(cum[b1]))
+                extras_wanted = [name for name in ('lag', 'cmax') if getattr(res, name) is not None]
+                if extras_wanted:
+                    ext = h.fetch(grids=False, est=est, **{'want_' + name: True for name in extras_wanted})
+                    for name in extras_wanted:
+                        getattr(res, name)[b0:b1] = ext[name]
+                if want_uncert:
+                    res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty(est=est)
+    finally:
+        if up is not None:
+            up.close()
+        h.set_estimators(())              # the handle is shared with the plain calls: back to the plain pass
+    return results
+
+
+def _multi_units(units_done, e, res, base, u0, u1):
+    if u1 > u0:
+        units_done(e, res, base + u0, base + u1)
 
 
 def batch_rows(streams):

@@ -71,3 +71,37 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
                                    prefiltered=True, want_uncert=True)
     return [_returns(res, nchans, alpha) for res in results]
+
+
+def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None):
+    """``ltsva`` of one (already filtered) stream for several estimators ``(alpha, remove)`` in one GPU pass -> a list of
+    ``ltsva``'s 8-tuples, element e equal to ``ltsva`` with ``alpha_e`` on the stream without the traces ``remove_e``
+    (0-based, ascending; a bare number means nothing removed; at most 8 estimators).  The windows of the full array are
+    correlated once, every window is solved once per estimator.  ``ValueError`` before any GPU work for an empty list, a
+    bad alpha or ``remove`` and too few kept elements.  The "ALPHA is 1.0" message prints once per call."""
+    data, fs, _ = engine.stream_rows(st)
+    nchans = len(data)
+    ests = engine.normalize_estimators(estimators, nchans)
+    if len(ests) == 1 and not ests[0][1]:          # one estimator with nothing removed IS the single call
+        return [ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=ests[0][0], rij=rij)]
+    rijs, t0s = [], []
+    for _, remove in ests:
+        kept = engine.kept_elements(nchans, remove)
+        if rij is not None:
+            rijs.append(np.ascontiguousarray(np.asarray(rij)[:, kept]) if remove else rij)
+        else:
+            rijs.append(get_rij([lat_list[i] for i in kept], [lon_list[i] for i in kept], len(kept)))
+        t0s.append(engine.stream_rows([st[kept[0]]])[2])
+    if all(rm for _, rm in ests):
+        rijs.append(get_rij(lat_list, lon_list, nchans) if rij is None else rij)
+    if any(a == 1.0 for a, _ in ests):
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_multi(data, fs, t0s, rijs, [(None, None)], [window_length], window_overlap, ests,
+                                   prefiltered=True, want_uncert=True)
+    keys = {}
+    out = []
+    for (alpha, _), res in zip(ests, results):
+        if alpha != 1.0 and id(res.t) not in keys:
+            keys[id(res.t)] = engine.time_keys(res.t, res.nwin)
+        out.append(_returns(res, res.nchans, alpha, keys.get(id(res.t))))
+    return out

@@ -205,6 +205,90 @@ def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_li
     return out
 
 
+def _reduced(st, lat_list, lon_list, rij, remove):
+    """The stream, coordinates and geometry of the array without the traces in ``remove`` — what a single call on the
+    reduced stream is given: ``rij[:, kept]`` as it stands, else ``get_rij`` of the reduced lists (whose origin is the
+    reduced list's first element)."""
+    nchans = len(st)
+    if not remove:
+        return st, lat_list, lon_list, (get_rij(lat_list, lon_list, nchans) if rij is None else rij)
+    kept = engine.kept_elements(nchans, remove)
+    sub = [st[i] for i in kept]
+    lat = None if lat_list is None else [lat_list[i] for i in kept]
+    lon = None if lon_list is None else [lon_list[i] for i in kept]
+    if rij is not None:
+        return sub, lat, lon, np.ascontiguousarray(np.asarray(rij)[:, kept])
+    return sub, lat, lon, get_rij(lat, lon, len(kept))
+
+
+def narrow_band_least_squares_multi(WINLEN_list, WINOVER, ESTIMATORS, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                    FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None):
+    """``narrow_band_least_squares`` for several estimators in one GPU pass -> a list of 9-tuples.
+
+    ``ESTIMATORS``: a sequence of ``(ALPHA, remove)``, ``remove`` a tuple of ascending 0-based trace indices of ``st``
+    the estimator leaves out (a bare number means ``(ALPHA, ())``); at most 8.  Element e of the result equals
+    ``narrow_band_least_squares(..., ALPHA_e, st without remove_e, ...)`` — with ``rij[:, kept]``, or the reduced
+    ``lat_list`` / ``lon_list`` — : the dictionary's element numbers and ``'size'`` are the reduced array's, OLS estimators
+    return ``stdict_all = None`` and fill ``sig_tau_array``.  The full array is filtered and correlated ONCE (a pair's lag
+    does not depend on ALPHA or on the other elements); only the solve runs per estimator.  ``ValueError`` before any GPU
+    work for an empty list, a bad ALPHA or ``remove`` and too few kept elements.  The BT caution prints once per call.
+    One estimator that removes nothing is the single call.  A trace of which not even one filtered band fits the HBM
+    budget runs as one single call per estimator."""
+    rows, fs, _ = engine.stream_rows(st)
+    nchans = len(rows)
+    ests = engine.normalize_estimators(ESTIMATORS, nchans)
+    single = functools.partial(narrow_band_least_squares, WINLEN_list, WINOVER)
+    tail = (NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE)
+    if len(ests) == 1 and not ests[0][1]:
+        return [single(ests[0][0], st, lat_list, lon_list, *tail, rij=rij)]
+    reduced = [_reduced(st, lat_list, lon_list, rij, rm) for _, rm in ests]
+    if engine.max_bands_per_pass(nchans, len(rows[0])) < 1:        # the time-segmented path: one single call per estimator
+        return [single(a, sub, lat, lon, *tail, rij=r) for (a, _), (sub, lat, lon, r) in zip(ests, reduced)]
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    bands = list(range(NBANDS))
+    edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
+    winlens = [WINLEN_list[ii] for ii in bands]
+    prefixes = [_band_prefix(ii + 1) for ii in bands]
+    rijs = [r for _, _, _, r in reduced]
+    t0s = [engine.stream_rows(sub[:1])[2] for sub, _, _, _ in reduced]
+    if all(rm for _, rm in ests):
+        rijs.append(get_rij(lat_list, lon_list, nchans) if rij is None else rij)
+    shared = {}
+
+    def host_side(results):
+        if len(results[0].sos) == NBANDS:      # (bands in several HBM rounds: their designs are complete only at the end)
+            shared['w'], shared['h'] = filter_responses(results[0].sos, freq_resp_list, fs)
+        _bt_cautions(winlens, edges)
+        keys, cache = {}, engine.new_pattern_cache
+        for res in results:
+            if res.lts:                    # (the key text depends on the window times alone: once per start time)
+                if id(res.t) not in keys:
+                    keys[id(res.t)] = engine.time_key_text(res.t, res.nwin, prefixes)
+                res.keys = keys[id(res.t)]
+                res.stdict = engine.new_stdict(engine.n_keys(res.keys))
+                res.pattern_cache = cache()
+
+    def units_done(e, res, u0, u1):
+        if res.lts:
+            engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, res.nchans, res.keys, into=res.stdict,
+                                    cache=res.pattern_cache, units=(u0, u1))
+
+    results = engine.process_multi(rows, fs, t0s, rijs, edges, winlens, WINOVER, ests, FILTER_TYPE, FILTER_ORDER,
+                                   FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, units_done=units_done)
+    if 'w' not in shared:
+        shared['w'], shared['h'] = filter_responses(results[0].sos, freq_resp_list, fs)
+    out = []
+    for (alpha, _), res in zip(ests, results):
+        if res.lts:
+            if 'size' not in res.stdict:
+                res.stdict['size'] = res.nchans
+            engine.release_later(res.__dict__.pop('pattern_cache', None), res.__dict__.pop('keys', None))
+        out.append(_returns(alpha, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t if len(out) == 0 else res.t.copy(),
+                            getattr(res, 'stdict', None), res.nwin, shared['w'].copy(), shared['h'].copy()))
+    return out
+
+
 def narrow_band_loop(ii, freqlist, FREQ_BAND_TYPE, freq_resp_list, st, FILTER_TYPE, FILTER_ORDER,
                      FILTER_RIPPLE, lat_list, lon_list, WINLEN_list, WINOVER, ALPHA, vector_len, rij=None):
     """One band (the reference's joblib task body, narrow_band_least_squares.py:134-218) ->
