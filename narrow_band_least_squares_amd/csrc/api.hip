@@ -286,6 +286,96 @@ void filter_tables(const double* sos, int S, int C, int G, double* fw, double* m
     }
 }
 
+// Rank of a co-array [npairs][2] (2 unknowns): false for a collinear array.
+bool coarray_full_rank(const double* xij, int npairs) {
+    double sxx = 0, sxy = 0, syy = 0;
+    for (int k = 0; k < npairs; ++k) { sxx += xij[2*k]*xij[2*k]; sxy += xij[2*k]*xij[2*k+1]; syy += xij[2*k+1]*xij[2*k+1]; }
+    const double det = sxx * syy - sxy * sxy;
+    return det > 1e-12 * (sxx + syy) * (sxx + syy);
+}
+
+// The LTS description of an array of P pairs; `who` is the caller's message prefix.
+int check_lts(nbls_handle* h, const nbls_lts_params* l, int P, const std::string& who) {
+    if (l->nstarts < 1 || l->nstarts > NBLS_MAX_STARTS || !l->starts || !l->rew_table) return fail(h, NBLS_ERR_ARG, who + "bad LTS starts");
+    if (l->h < 2 || l->h > P) return fail(h, NBLS_ERR_ARG, who + "LTS h out of range");
+    if (l->ncand < 1 || l->ncand > NBLS_MAX_CAND) return fail(h, NBLS_ERR_ARG, who + "ncand out of range");
+    for (int i = 0; i < l->nstarts * 4; ++i)
+        if (l->starts[i] >= P) return fail(h, NBLS_ERR_ARG, who + "start index out of range");
+    return 0;
+}
+
+// The LTS tables of a record on the device: starts, reweighting table and the standardised co-array xs / xc / xss.
+int upload_lts_tables(nbls_handle* h, nbls_estimator& x) {
+    int rc;
+    const int P = x.npairs;
+    if ((rc = alloc_copy(h, &x.d_starts, x.h_starts.data(), x.h_starts.size()))) return rc;
+    if ((rc = alloc_copy(h, &x.d_rew, x.h_rew.data(), x.h_rew.size()))) return rc;
+    const int PP = P + 16;                           // padding: the large-array LTS kernel fetches one block of pairs ahead
+    std::vector<double> xs((size_t)PP * 2, 0.0), xc((size_t)PP, 0.0);
+    for (int k = 0; k < P; ++k) {
+        xs[2 * k] = x.h_xij[2 * k] / x.ltsp.xij_mad[0];
+        xs[2 * k + 1] = x.h_xij[2 * k + 1] / x.ltsp.xij_mad[1];
+        xc[k] = xs[2 * k] * xs[2 * k + 1];
+    }
+    if ((rc = alloc_copy(h, &x.d_xs, xs.data(), xs.size()))) return rc;
+    if ((rc = alloc_copy(h, &x.d_xc, xc.data(), xc.size()))) return rc;
+    const int NS4 = (P + 3) / 4;                     // every 4th pair: the sample pass of the large-array LTS kernel
+    std::vector<double> xss((size_t)(NS4 + 16) * 2, 0.0);
+    for (int i = 0; i < NS4; ++i) { xss[2 * i] = xs[2 * (4 * i)]; xss[2 * i + 1] = xs[2 * (4 * i) + 1]; }
+    return alloc_copy(h, &x.d_xss, xss.data(), xss.size());
+}
+
+// Size a record's result buffers for `cells` result cells: every buffer has its own capacity (a smaller plan after a
+// bigger one keeps the allocations).  The lag / cmax rows are the pass's own unless the record is a sub-array's
+// (nbls_view_of); min_res: the least allocation of the result block (nbls_reserve_results).
+int size_result_buffers(nbls_handle* h, nbls_estimator& x, size_t cells, size_t min_res) {
+    int rc;
+    const size_t P = x.d_xij ? (size_t)x.npairs : 1;     // (geometry is optional for a filter-only plan)
+    const bool own = x.kept_pair.empty();
+    x.mask_bytes = (int)((P + 7) / 8);
+    x.res_bytes = cells * (4 * sizeof(double) + (size_t)x.mask_bytes);
+    if ((rc = ensure(h, &x.d_res, &x.cap_res, x.res_bytes > min_res ? x.res_bytes : min_res))) return rc;
+    if ((rc = ensure(h, own ? &h->d_lag : &x.d_lag, own ? &h->cap_lag : &x.cap_lag, cells * P * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(h, own ? &h->d_cmax : &x.d_cmax, own ? &h->cap_cmax : &x.cap_cmax, cells * P * sizeof(double)))) return rc;
+    if ((rc = ensure(h, &x.d_z, &x.cap_z, 2 * cells * sizeof(double)))) return rc;
+    if ((rc = ensure(h, &x.d_wts, &x.cap_wts, cells * P))) return rc;
+    if (x.want_unc && (rc = ensure(h, &x.d_unc, &x.cap_unc, 2 * cells * sizeof(double)))) return rc;
+    return 0;
+}
+
+// A streamed pass: the pinned mirror of a record's result block, large enough for the plan's block.
+int ensure_mirror(nbls_handle* h, nbls_estimator& x) {
+    if (x.cap_hres >= x.res_bytes) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->cstream));
+    if (x.h_res) { (void)hipHostFree(x.h_res); x.h_res = nullptr; x.cap_hres = 0; }
+    HIPCHK(h, hipHostMalloc((void**)&x.h_res, x.res_bytes ? x.res_bytes : 8, hipHostMallocDefault));
+    x.cap_hres = x.res_bytes ? x.res_bytes : 8;
+    return 0;
+}
+
+// The first window band b of the plan computed (0 unless window-sharded); it computed nwin[b] from there on.
+int64_t first_window(const nbls_handle* h, int b) { return (int)h->woff.size() == h->nbands ? h->woff[b] : 0; }
+
+// Rows of windows the plan did not compute (beyond a band's count, outside a window slice) are zeros in what a fetch
+// returns: `out` is [B][VL] rows of row_bytes.
+void zero_uncomputed(const nbls_handle* h, void* out, size_t row_bytes) {
+    unsigned char* o = (unsigned char*)out;
+    for (int b = 0; b < h->nbands; ++b) {
+        const int64_t first = first_window(h, b), n = h->nwin[b];
+        unsigned char* band = o + (size_t)b * h->vector_len * row_bytes;
+        if (first > 0) memset(band, 0, (size_t)first * row_bytes);
+        if (first + n < h->vector_len) memset(band + (size_t)(first + n) * row_bytes, 0, (size_t)(h->vector_len - first - n) * row_bytes);
+    }
+}
+
+// Free what a record owns (tables inside the plan arena go with the arena).
+void free_estimator(nbls_estimator& x, const std::unordered_set<const void*>& in_arena) {
+    void* bufs[] = {x.d_xij, x.d_xpinv, x.d_xs, x.d_xc, x.d_xss, x.d_rew, x.d_starts, x.d_kept_pair,
+                    x.d_lag, x.d_cmax, x.d_z, x.d_unc, x.d_wts, x.d_res /* vel, baz, mdccm, sigma_tau, mask */};
+    for (void* b : bufs) if (b && !in_arena.count(b)) (void)hipFree(b);
+    if (x.h_res) (void)hipHostFree(x.h_res);
+}
+
 }  // namespace
 
 extern "C" {
@@ -342,20 +432,14 @@ void nbls_destroy(nbls_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     if (h->up) (void)hipStreamSynchronize(h->up);
     (void)nbls_comm_destroy(h);
-    void* bufs[] = {h->d_trace, h->d_xij, h->d_pair, h->d_xpinv, h->d_sos, h->d_M, h->d_tl, h->d_tr,
+    void* bufs[] = {h->d_trace, h->d_pair, h->d_sos, h->d_M, h->d_tl, h->d_tr,
                     h->d_W, h->d_inc, h->d_nwin, h->d_unit_off, h->d_unit_band, h->d_unit_win, h->d_filt, h->d_cstate, h->d_cstate2, h->d_tstate,
-                    h->d_lag, h->d_cmax, h->d_res /* vel, baz, mdccm, sigma_tau, mask */, h->d_z, h->d_wts,
-                    h->d_unc, h->d_starts, h->d_rew, h->d_xs, h->d_xc, h->d_xss, h->d_qbuf, h->d_qmeta, h->d_cand, h->d_fw, h->d_gend, h->d_gin, h->d_win_off, h->d_stamps, h->d_seg_state};
+                    h->d_lag, h->d_cmax, h->d_qbuf, h->d_qmeta, h->d_cand, h->d_fw, h->d_gend, h->d_gin, h->d_win_off, h->d_stamps, h->d_seg_state};
     {
         std::unordered_set<const void*> in_arena;       // members that point into d_parena
         for (const void* m : h->arena_owned) in_arena.insert(*(void* const*)m);
         for (void* b : bufs) if (b && !in_arena.count(b)) (void)hipFree(b);
-        for (nbls_estimator& x : h->est) {
-            void* eb[] = {x.d_xij, x.d_xpinv, x.d_xs, x.d_xc, x.d_xss, x.d_rew, x.d_starts, x.d_kept_pair,
-                          x.d_lag, x.d_cmax, x.d_z, x.d_unc, x.d_wts, x.d_res};
-            for (void* b : eb) if (b && !in_arena.count(b)) (void)hipFree(b);
-            if (x.h_res) (void)hipHostFree(x.h_res);
-        }
+        for (nbls_estimator& x : h->est) free_estimator(x, in_arena);
         if (h->d_parena) (void)hipFree(h->d_parena);
     }
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
@@ -366,7 +450,6 @@ void nbls_destroy(nbls_handle* h) {
     if (h->ustream) { (void)hipStreamSynchronize(h->ustream); (void)hipStreamDestroy(h->ustream); }
     for (hipEvent_t e : h->uev) (void)hipEventDestroy(e);
     if (h->ev_uprev) (void)hipEventDestroy(h->ev_uprev);
-    if (h->h_res) (void)hipHostFree(h->h_res);
     if (h->ev_xd) (void)hipEventDestroy(h->ev_xd);
     if (h->ev_plan) (void)hipEventDestroy(h->ev_plan);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);
@@ -381,10 +464,11 @@ void nbls_destroy(nbls_handle* h) {
 // divide into the segments: nbls_plan refuses them).  A geometry of another array size is stale.
 static void set_elements(nbls_handle* h, int32_t nchans) {
     const int E = h->nseg > 1 && nchans % h->nseg == 0 ? nchans / h->nseg : nchans;
-    if (h->nelem != E && h->d_xij) {
-        (void)hipFree(h->d_xij); h->d_xij = nullptr;
-        h->caps.erase((const void*)&h->d_xij);
-        h->npairs = 0;
+    nbls_estimator& x = h->est[0];
+    if (h->nelem != E && x.d_xij) {
+        (void)hipFree(x.d_xij); x.d_xij = nullptr;
+        h->caps.erase((const void*)&x.d_xij);
+        h->npairs = x.npairs = 0;
     }
     h->nelem = E;
 }
@@ -567,31 +651,27 @@ int nbls_set_geometry(nbls_handle* h, const double* xij, const int32_t* pair_idx
     if (!xij || !pair_idx || !xpinv) return fail(h, NBLS_ERR_ARG, "nbls_set_geometry: NULL pointer");
     if (npairs < 3) return fail(h, NBLS_ERR_GEOMETRY, "need at least 3 array elements (3 pairs)");
     if (npairs > NBLS_MAX_PAIRS) return fail(h, NBLS_ERR_UNSUPPORTED, "more than 512 pairs (32 elements) not supported");
-    // rank check of the co-array (2 unknowns)
-    double sxx = 0, sxy = 0, syy = 0;
-    for (int k = 0; k < npairs; ++k) { sxx += xij[2*k]*xij[2*k]; sxy += xij[2*k]*xij[2*k+1]; syy += xij[2*k+1]*xij[2*k+1]; }
-    const double det = sxx * syy - sxy * sxy;
-    if (!(det > 1e-12 * (sxx + syy) * (sxx + syy)))
-        return fail(h, NBLS_ERR_GEOMETRY, "co-array is rank deficient (collinear array)");
+    if (!coarray_full_rank(xij, npairs)) return fail(h, NBLS_ERR_GEOMETRY, "co-array is rank deficient (collinear array)");
     // the same geometry as the handle already holds (every band group of every call of one array): nothing to upload
+    nbls_estimator& x = h->est[0];
     const size_t n2 = (size_t)npairs * 2;
-    if (h->d_xij && h->d_pair && h->d_xpinv && h->npairs == npairs && h->h_xij.size() == n2 && h->h_pair.size() == n2 &&
-        h->h_xpinv.size() == n2 && memcmp(h->h_xij.data(), xij, n2 * sizeof(double)) == 0 &&
-        memcmp(h->h_pair.data(), pair_idx, n2 * sizeof(int32_t)) == 0 && memcmp(h->h_xpinv.data(), xpinv, n2 * sizeof(double)) == 0) {
+    if (x.d_xij && h->d_pair && x.d_xpinv && h->npairs == npairs && x.h_xij.size() == n2 && h->h_pair.size() == n2 &&
+        x.h_xpinv.size() == n2 && memcmp(x.h_xij.data(), xij, n2 * sizeof(double)) == 0 &&
+        memcmp(h->h_pair.data(), pair_idx, n2 * sizeof(int32_t)) == 0 && memcmp(x.h_xpinv.data(), xpinv, n2 * sizeof(double)) == 0) {
         h->planned = false;
         return NBLS_OK;
     }
     HIPCHK(h, hipSetDevice(h->device));
     StreamGuard guard(h);
     int rc;
-    h->h_xij.clear();                        // (a failed upload leaves no stale "already there" record)
-    if ((rc = alloc_copy(h, &h->d_xij, xij, n2))) return rc;
+    x.h_xij.clear();                         // (a failed upload leaves no stale "already there" record)
+    if ((rc = alloc_copy(h, &x.d_xij, xij, n2))) return rc;
     if ((rc = alloc_copy(h, &h->d_pair, pair_idx, n2))) return rc;
-    if ((rc = alloc_copy(h, &h->d_xpinv, xpinv, n2))) return rc;
-    h->h_xij.assign(xij, xij + n2);
+    if ((rc = alloc_copy(h, &x.d_xpinv, xpinv, n2))) return rc;
+    x.h_xij.assign(xij, xij + n2);
     h->h_pair.assign(pair_idx, pair_idx + n2);
-    h->h_xpinv.assign(xpinv, xpinv + n2);
-    h->npairs = npairs;
+    x.h_xpinv.assign(xpinv, xpinv + n2);
+    h->npairs = x.npairs = npairs;
     h->planned = false;
     return NBLS_OK;
 }
@@ -653,18 +733,8 @@ int nbls_set_estimators(nbls_handle* h, int32_t n, const nbls_estimator_desc* de
             for (int j = i + 1; j < K; ++j, ++k)
                 if (d.pair_idx[2 * k] != i || d.pair_idx[2 * k + 1] != j)
                     return fail(h, NBLS_ERR_ARG, who + "pair_idx is not the lexicographic pair list of the kept elements");
-        double sxx = 0, sxy = 0, syy = 0;
-        for (int k = 0; k < P; ++k) { sxx += d.xij[2*k]*d.xij[2*k]; sxy += d.xij[2*k]*d.xij[2*k+1]; syy += d.xij[2*k+1]*d.xij[2*k+1]; }
-        const double det = sxx * syy - sxy * sxy;
-        if (!(det > 1e-12 * (sxx + syy) * (sxx + syy))) return fail(h, NBLS_ERR_GEOMETRY, who + "co-array is rank deficient (collinear array)");
-        if (d.lts) {
-            const nbls_lts_params* l = d.lts;
-            if (l->nstarts < 1 || l->nstarts > NBLS_MAX_STARTS || !l->starts || !l->rew_table) return fail(h, NBLS_ERR_ARG, who + "bad LTS starts");
-            if (l->h < 2 || l->h > P) return fail(h, NBLS_ERR_ARG, who + "LTS h out of range");
-            if (l->ncand < 1 || l->ncand > NBLS_MAX_CAND) return fail(h, NBLS_ERR_ARG, who + "ncand out of range");
-            for (int i = 0; i < l->nstarts * 4; ++i)
-                if (l->starts[i] >= P) return fail(h, NBLS_ERR_ARG, who + "start index out of range");
-        }
+        if (!coarray_full_rank(d.xij, P)) return fail(h, NBLS_ERR_GEOMETRY, who + "co-array is rank deficient (collinear array)");
+        if (d.lts) { const int rc = check_lts(h, d.lts, P, who); if (rc) return rc; }
         if (d.eig6 && (!(d.eig6[0] > 0.0) || !(d.eig6[1] > 0.0))) return fail(h, NBLS_ERR_ARG, who + "the eigenvalues of X^T X must be positive");
         Built& b = built[(size_t)e];
         b.kept.assign(d.kept, d.kept + K);
@@ -682,11 +752,12 @@ int nbls_set_estimators(nbls_handle* h, int32_t n, const nbls_estimator_desc* de
             b.rew.assign(d.lts->rew_table, d.lts->rew_table + (size_t)P + 1);
         }
     }
-    for (int e = 0; e < n; ++e) {
-        nbls_estimator& x = h->est[e];
+    for (int e = 0; e < n; ++e) {                // est[0] is the plan's own: not touched here
+        nbls_estimator& x = h->est[1 + e];
         Built& b = built[(size_t)e];
         x.kept.swap(b.kept); x.kept_pair.swap(b.kept_pair);
         x.h_xij.swap(b.xij); x.h_xpinv.swap(b.xpinv); x.h_starts.swap(b.starts); x.h_rew.swap(b.rew);
+        x.npairs = (int)(x.h_xij.size() / 2);
         x.lts = desc[e].lts != nullptr;
         x.ltsp = nbls_lts_params{};
         if (x.lts) { x.ltsp = *desc[e].lts; x.ltsp.starts = nullptr; x.ltsp.rew_table = nullptr; }
@@ -698,18 +769,28 @@ int nbls_set_estimators(nbls_handle* h, int32_t n, const nbls_estimator_desc* de
     return NBLS_OK;
 }
 
-int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsections, int32_t zero_phase,
-              const double* taper_left, const double* taper_right, int32_t taper_len,
-              const int32_t* winlen, const int32_t* wininc, int32_t vector_len,
-              const nbls_lts_params* lts, int32_t xcorr_impl) {
-    if (!h) return NBLS_ERR_ARG;
-    h->planned = false;
+// nbls_plan's arguments and what its argument checks derive from them, handed from step to step.
+struct plan_args {
+    int32_t nbands;
+    const double* sos;
+    int32_t nsections, zero_phase;
+    const double *taper_left, *taper_right;
+    int32_t taper_len;
+    const int32_t *winlen, *wininc;
+    int32_t vector_len;
+    const nbls_lts_params* lts;
+    int32_t xcorr_impl;
+    int NS, E, P, R, D;            // segments, elements, pairs (1 without geometry), result rows, filter state size
+};
+
+// Step 1: the arguments against the handle's trace, geometry and estimators; records the LTS plan of est[0].
+static int plan_check_args(nbls_handle* h, plan_args& a) {
     if (!h->d_trace) return fail(h, NBLS_ERR_STATE, "nbls_plan: no trace set");
-    if (nbands < 1 || (!sos && nsections != 0) || !winlen || !wininc || vector_len < 1)
+    if (a.nbands < 1 || (!a.sos && a.nsections != 0) || !a.winlen || !a.wininc || a.vector_len < 1)
         return fail(h, NBLS_ERR_ARG, "nbls_plan: bad argument");
-    if (nsections < 0 || nsections > NBLS_MAX_SECTIONS)
+    if (a.nsections < 0 || a.nsections > NBLS_MAX_SECTIONS)
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: 0..8 second-order sections supported");
-    if (taper_len < 0 || 2 * (int64_t)taper_len > h->npts || (taper_len > 0 && (!taper_left || !taper_right)))
+    if (a.taper_len < 0 || 2 * (int64_t)a.taper_len > h->npts || (a.taper_len > 0 && (!a.taper_left || !a.taper_right)))
         return fail(h, NBLS_ERR_ARG, "nbls_plan: bad taper");
     // several recordings of one array (nbls_set_segments): nseg blocks of E rows, result row r = b * nseg + s
     const int NS = h->nseg;
@@ -725,71 +806,72 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
-    for (int e = 0; e < h->nest; ++e)
-        if (!h->d_xij || h->est[e].kept.empty() || h->est[e].kept.back() >= E || ((int)h->est[e].kept.size() == E) != h->est[e].kept_pair.empty())
+    nbls_estimator& x0 = h->est[0];
+    for (int e = 1; e <= h->nest; ++e)
+        if (!x0.d_xij || h->est[e].kept.empty() || h->est[e].kept.back() >= E || ((int)h->est[e].kept.size() == E) != h->est[e].kept_pair.empty())
             return fail(h, NBLS_ERR_ARG, "nbls_plan: the further estimators (nbls_set_estimators) do not fit this trace's elements and geometry");
     if (NS > 1 && (E < 3 || E > 32))
         return fail(h, NBLS_ERR_GEOMETRY, "nbls_plan: " + std::to_string(E) + " elements per segment (3..32 supported)");
     // geometry is optional for a filter-only plan (filter_data()); execute checks it
-    const int P = h->d_xij ? h->npairs : 1;
-    if (h->d_xij && (int64_t)E * (E - 1) / 2 != P)
+    const int P = x0.d_xij ? h->npairs : 1;
+    if (x0.d_xij && (int64_t)E * (E - 1) / 2 != P)
         return fail(h, NBLS_ERR_ARG, "nbls_plan: geometry pair count does not match the array's element count");
-    if (lts) {
-        if (!h->d_xij) return fail(h, NBLS_ERR_STATE, "nbls_plan: LTS needs the geometry");
+    if (a.lts) {
+        if (!x0.d_xij) return fail(h, NBLS_ERR_STATE, "nbls_plan: LTS needs the geometry");
         if (E < 4) return fail(h, NBLS_ERR_GEOMETRY, "LTS needs at least 4 array elements");
-        if (lts->nstarts < 1 || lts->nstarts > NBLS_MAX_STARTS || !lts->starts || !lts->rew_table)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: bad LTS starts");
-        if (lts->h < 2 || lts->h > P) return fail(h, NBLS_ERR_ARG, "nbls_plan: LTS h out of range");
-        if (lts->ncand < 1 || lts->ncand > NBLS_MAX_CAND) return fail(h, NBLS_ERR_ARG, "nbls_plan: ncand out of range");
-        for (int i = 0; i < lts->nstarts * 4; ++i)
-            if (lts->starts[i] >= P) return fail(h, NBLS_ERR_ARG, "nbls_plan: start index out of range");
+        const int rc = check_lts(h, a.lts, P, "nbls_plan: ");
+        if (rc) return rc;
+        x0.ltsp = *a.lts;
+        x0.ltsp.starts = nullptr;
+        x0.ltsp.rew_table = nullptr;
+        x0.h_starts.assign(a.lts->starts, a.lts->starts + (size_t)a.lts->nstarts * 4);
+        x0.h_rew.assign(a.lts->rew_table, a.lts->rew_table + (size_t)P + 1);
     }
-    // The filter tables first: pure host arithmetic.  Every HIP call of the plan comes AFTER them — while the trace of a
-    // pipelined call is still going up on another thread (nbls_upload_rows) each HIP call waits for the runtime's lock
-    // behind a row copy (~0.15 ms apiece), and the first launch of the call waits for this plan.
-    const auto tp0 = std::chrono::steady_clock::now();
-    const int D = 2 * nsections;
+    x0.lts = a.lts != nullptr;
+    a.NS = NS; a.E = E; a.P = P;
+    a.R = a.nbands * NS;
+    a.D = 2 * a.nsections;
+    return 0;
+}
+
+// Step 2: the filter tables, pure host arithmetic.  Every HIP call of the plan comes AFTER them — while the trace of a
+// pipelined call is still going up on another thread (nbls_upload_rows) each HIP call waits for the runtime's lock
+// behind a row copy (~0.15 ms apiece), and the first launch of the call waits for this plan.
+static void plan_filter_tables(nbls_handle* h, const plan_args& a) {
+    const int nbands = a.nbands, nsections = a.nsections, D = a.D;
     const int GG = NBLS_FILTER_GROUP;
     // (host tables kept in the handle between plans: a fresh 1.2 MB per plan is 300 page faults on the table threads, on the
     //  critical path of every call — and trimmed back to the OS when it is freed)
-    std::vector<double>& M = h->hp_M;
-    std::vector<double>& FW = h->hp_FW;
-    M.resize((size_t)nbands * (GG + 1) * D * D);
-    FW.resize((size_t)nbands * NBLS_FILTER_CHUNK * D);
-    {
-        // long-double table arithmetic, 30-100 us per band: the bands are dealt to a few host threads (the
-        // plan sits on the critical path of a call: the GPU has nothing to do until it is through)
-        double* const fwp = FW.data();
-        double* const mp = M.data();
-        int nt = nsections > 0 ? std::max(1, std::min(12, nbands / 2)) : 0;     // 2+ bands per thread of the pool (TablePool)
-        const std::function<void(int)> work = [&](int t) {
-            for (int b = t; b < nbands; b += nt)
-                filter_tables(sos + (size_t)b * nsections * 6, nsections, NBLS_FILTER_CHUNK, GG,
-                              fwp + (size_t)b * NBLS_FILTER_CHUNK * D, mp + (size_t)b * (GG + 1) * D * D);
-        };
-        if (nt > 0 && !pool_run(nt, work)) {       // the pool is busy with another handle's plan: all bands here
-            nt = 1;
-            work(0);
-        }
+    h->hp_M.resize((size_t)nbands * (GG + 1) * D * D);
+    h->hp_FW.resize((size_t)nbands * NBLS_FILTER_CHUNK * D);
+    // long-double table arithmetic, 30-100 us per band: the bands are dealt to a few host threads (the
+    // plan sits on the critical path of a call: the GPU has nothing to do until it is through)
+    double* const fwp = h->hp_FW.data();
+    double* const mp = h->hp_M.data();
+    int nt = nsections > 0 ? std::max(1, std::min(12, nbands / 2)) : 0;     // 2+ bands per thread of the pool (TablePool)
+    const std::function<void(int)> work = [&](int t) {
+        for (int b = t; b < nbands; b += nt)
+            filter_tables(a.sos + (size_t)b * nsections * 6, nsections, NBLS_FILTER_CHUNK, GG,
+                          fwp + (size_t)b * NBLS_FILTER_CHUNK * D, mp + (size_t)b * (GG + 1) * D * D);
+    };
+    if (nt > 0 && !pool_run(nt, work)) {       // the pool is busy with another handle's plan: all bands here
+        nt = 1;
+        work(0);
     }
-    const auto tp1 = std::chrono::steady_clock::now();
+}
 
-    HIPCHK(h, hipSetDevice(h->device));
-    StreamGuard guard(h);
-    h->planned = false;
-    h->res_loaded = false;
-    h->arena_mode = true;                                // alloc_copy: places in the arena, ONE upload at the end
-
-    // per result row (R = nbands * nseg, rows of one band consecutive): the filter tables above stay per band
-    const int R = nbands * NS;
+// Step 3: the windows of every result row (R = nbands * nseg, rows of one band consecutive; the filter tables stay per
+// band) and the units they make, on the host.
+static int plan_windows(nbls_handle* h, const plan_args& a) {
+    const int R = a.R, NS = a.NS;
     h->W.resize(R);
     h->inc.resize(R);
-    for (int r = 0; r < R; ++r) { h->W[r] = winlen[r / NS]; h->inc[r] = wininc[r / NS]; }
+    for (int r = 0; r < R; ++r) { h->W[r] = a.winlen[r / NS]; h->inc[r] = a.wininc[r / NS]; }
     h->nwin.resize(R);
     h->unit_off.resize(R + 1);
-    std::vector<int32_t> woff(R, 0);
+    h->woff.assign(R, 0);
     int64_t U = 0;
-    int maxW = 0, uniW = nbands > 0 ? winlen[0] : 0;
+    int maxW = 0, uniW = a.nbands > 0 ? a.winlen[0] : 0;
     for (int b = 0; b < R; ++b) {
         const int W = h->W[b], inc = h->inc[b];
         if (W != uniW) uniW = 0;
@@ -798,7 +880,7 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
         // len(arange(0, npts - W, inc))
         const int64_t span = h->npts - W;
         int64_t n = span > 0 ? (span + inc - 1) / inc : 0;
-        if (n > vector_len) return fail(h, NBLS_ERR_ARG, "nbls_plan: vector_len smaller than a band's window count");
+        if (n > a.vector_len) return fail(h, NBLS_ERR_ARG, "nbls_plan: vector_len smaller than a band's window count");
         int64_t first = 0;
         if ((int)h->win_first.size() == R) {               // window sharding: this handle's slice of the band
             first = h->win_first[b] < n ? h->win_first[b] : n;
@@ -806,69 +888,76 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
             if (cnt > n - first) cnt = n - first;
             n = cnt;
         }
-        woff[b] = (int32_t)first;
+        h->woff[b] = (int32_t)first;
         h->nwin[b] = (int32_t)n;
         h->unit_off[b] = (int32_t)U;
         U += n;
         if (W > maxW) maxW = W;
     }
     h->unit_off[R] = (int32_t)U;
-    h->woff = woff;
-    if (U > 0x7fffffffLL / (P > 0 ? P : 1)) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: too many (unit, pair) items for one launch");
+    if (U > 0x7fffffffLL / (a.P > 0 ? a.P : 1)) return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: too many (unit, pair) items for one launch");
     h->nunits = U;
     h->maxW = maxW;
     h->uniW = uniW;
-    h->fbands = nbands;
+    h->fbands = a.nbands;
     h->nbands = R;
-    h->nsections = nsections;
-    h->zero_phase = zero_phase ? 1 : 0;
-    h->taper_len = taper_len;
-    h->vector_len = vector_len;
-    h->xcorr_impl = xcorr_impl;
+    h->nsections = a.nsections;
+    h->zero_phase = a.zero_phase ? 1 : 0;
+    h->taper_len = a.taper_len;
+    h->vector_len = a.vector_len;
+    h->xcorr_impl = a.xcorr_impl;
     h->nchunks = (h->npts + NBLS_FILTER_CHUNK - 1) / NBLS_FILTER_CHUNK;
+    return 0;
+}
 
+// Step 4: the filter, taper, window and unit tables go to the device (places in the arena; the ramps apart).
+static int plan_upload_tables(nbls_handle* h, const plan_args& a) {
+    const int R = a.R;
+    const int64_t U = h->nunits;
     int rc;
-    if ((rc = alloc_copy(h, &h->d_fw, FW.data(), FW.size()))) return rc;
-    if ((rc = alloc_copy(h, &h->d_sos, sos, (size_t)nbands * nsections * 6))) return rc;
-    if (nsections == 0 && nbands != 1)
+    if ((rc = alloc_copy(h, &h->d_fw, h->hp_FW.data(), h->hp_FW.size()))) return rc;
+    if ((rc = alloc_copy(h, &h->d_sos, a.sos, (size_t)a.nbands * a.nsections * 6))) return rc;
+    if (a.nsections == 0 && a.nbands != 1)
         return fail(h, NBLS_ERR_ARG, "nbls_plan: an unfiltered plan has exactly one band");
-    if ((rc = alloc_copy(h, &h->d_M, M.data(), M.size()))) return rc;
+    if ((rc = alloc_copy(h, &h->d_M, h->hp_M.data(), h->hp_M.size()))) return rc;
     {   // the ramps (1 % of the trace each: 0.14 MB at cfg-3, a quarter of a plan's upload) only when they differ from what is there
-        const size_t tn = (size_t)taper_len;
+        const size_t tn = (size_t)a.taper_len;
         const bool same = h->d_tl && h->d_tr && h->h_tl.size() == tn && h->h_tr.size() == tn &&
-                          (tn == 0 || (memcmp(h->h_tl.data(), taper_left, tn * sizeof(double)) == 0 &&
-                                       memcmp(h->h_tr.data(), taper_right, tn * sizeof(double)) == 0));
+                          (tn == 0 || (memcmp(h->h_tl.data(), a.taper_left, tn * sizeof(double)) == 0 &&
+                                       memcmp(h->h_tr.data(), a.taper_right, tn * sizeof(double)) == 0));
         if (!same) {
             h->h_tl.clear();
             h->h_tr.clear();
             h->arena_mode = false;                       // allocations of their own: they outlive the plan
-            rc = alloc_copy(h, &h->d_tl, taper_left, tn);
-            if (!rc) rc = alloc_copy(h, &h->d_tr, taper_right, tn);
+            rc = alloc_copy(h, &h->d_tl, a.taper_left, tn);
+            if (!rc) rc = alloc_copy(h, &h->d_tr, a.taper_right, tn);
             h->arena_mode = true;
             if (rc) return rc;
-            if (tn) { h->h_tl.assign(taper_left, taper_left + tn); h->h_tr.assign(taper_right, taper_right + tn); }
+            if (tn) { h->h_tl.assign(a.taper_left, a.taper_left + tn); h->h_tr.assign(a.taper_right, a.taper_right + tn); }
         }
     }
     if ((rc = alloc_copy(h, &h->d_W, h->W.data(), (size_t)R))) return rc;
     if ((rc = alloc_copy(h, &h->d_inc, h->inc.data(), (size_t)R))) return rc;
     if ((rc = alloc_copy(h, &h->d_nwin, h->nwin.data(), (size_t)R))) return rc;
     if ((rc = alloc_copy(h, &h->d_unit_off, h->unit_off.data(), (size_t)R + 1))) return rc;
-    if ((rc = alloc_copy(h, &h->d_win_off, woff.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, &h->d_win_off, h->woff.data(), (size_t)R))) return rc;
     std::vector<int32_t>& ub = h->hp_ub;
     ub.resize((size_t)U);
     for (int b = 0; b < R; ++b)
         for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) ub[(size_t)u] = b;
     if ((rc = alloc_copy(h, &h->d_unit_band, ub.data(), (size_t)U))) return rc;
-    {
-        std::vector<int32_t>& uw = h->hp_uw;
-        uw.resize((size_t)(U > 0 ? U : 1));
-        for (int b = 0; b < R; ++b)
-            for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) uw[(size_t)u] = (int32_t)(u - h->unit_off[b]) + woff[b];
-        if ((rc = alloc_copy(h, &h->d_unit_win, uw.data(), (size_t)U))) return rc;
-    }
+    std::vector<int32_t>& uw = h->hp_uw;
+    uw.resize((size_t)(U > 0 ? U : 1));
+    for (int b = 0; b < R; ++b)
+        for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) uw[(size_t)u] = (int32_t)(u - h->unit_off[b]) + h->woff[b];
+    return alloc_copy(h, &h->d_unit_win, uw.data(), (size_t)U);
+}
 
-    const auto tp2 = std::chrono::steady_clock::now();
-    const size_t nseries = (size_t)nbands * h->nchans;      // (= R * E)
+// Step 5: the work buffers of the filter, and the pass's lag / cmax rows with the result buffers of est[0].
+static int plan_work_buffers(nbls_handle* h, const plan_args& a) {
+    const int D = a.D, nsections = a.nsections;
+    int rc;
+    const size_t nseries = (size_t)a.nbands * h->nchans;      // (= R * E)
     // + 64 bytes: the verifier's 16-byte copies of a window that starts on an odd sample read one sample past its end
     if ((rc = ensure(h, &h->d_filt, &h->cap_filt, nseries * h->npts_pad * sizeof(double) + 64))) return rc;
     if ((rc = ensure(h, &h->d_cstate, &h->cap_cstate, nseries * h->nchunks * D * sizeof(double)))) return rc;
@@ -890,135 +979,122 @@ int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsectio
     const size_t ngroups = (size_t)((h->nchunks + NBLS_FILTER_GROUP - 1) / NBLS_FILTER_GROUP);
     if ((rc = ensure(h, &h->d_gend, &h->cap_gend, nseries * ngroups * D * sizeof(double)))) return rc;
     if ((rc = ensure(h, &h->d_gin, &h->cap_gin, nseries * ngroups * D * sizeof(double)))) return rc;
-    // results: every buffer has its own capacity; the views into the result block are recomputed by
-    // every plan (a smaller plan after a bigger one keeps the allocation but must move the grid offsets)
-    const size_t cells = (size_t)R * vector_len;
-    h->mask_bytes = (P + 7) / 8;
-    h->res_bytes = cells * (4 * sizeof(double) + (size_t)h->mask_bytes);
-    h->d_vel = h->d_baz = h->d_mdccm = h->d_sig = nullptr;
-    h->d_mask = nullptr;
-    if ((rc = ensure(h, &h->d_res, &h->cap_res, h->res_bytes > h->reserve_res ? h->res_bytes : h->reserve_res))) return rc;
-    if ((rc = ensure(h, &h->d_lag, &h->cap_lag, cells * P * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(h, &h->d_cmax, &h->cap_cmax, cells * P * sizeof(double)))) return rc;
-    if ((rc = ensure(h, &h->d_z, &h->cap_z, 2 * cells * sizeof(double)))) return rc;
-    if ((rc = ensure(h, &h->d_wts, &h->cap_wts, cells * P))) return rc;
-    if (h->want_unc && (rc = ensure(h, &h->d_unc, &h->cap_unc, 2 * cells * sizeof(double)))) return rc;
-    h->d_vel = (double*)h->d_res;
-    h->d_baz = h->d_vel + cells;
-    h->d_mdccm = h->d_baz + cells;
-    h->d_sig = h->d_mdccm + cells;
-    h->d_mask = h->d_res + 4 * cells * sizeof(double);
+    return size_result_buffers(h, h->est[0], (size_t)a.R * a.vector_len, h->reserve_res);
+}
 
-    {   // window groups (consecutive bands of one window length) and, per group, whether the int8 screening correlator
-        // applies; "auto" = screening wherever it applies, the faster general correlator elsewhere
-        h->wgroups.clear();
-        int maxWP = 0;
-        bool all_ok = true, any_ok = false;
-        for (int b = 0; b < R; ) {
-            int e = b + 1;
-            while (e < R && h->W[e] == h->W[b]) ++e;
-            nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
-            nbls_route r;                               // (xcorr_route.hip: the launchers take the same route)
-            nbls_route_compute(nbls_route_query_of(h, g.W, R, 3, false), &r);
-            g.screen = h->d_xij && r.correlator == NBLS_ROUTE_SCREEN;
-            if (g.screen) { any_ok = true; if (r.WP > maxWP) maxWP = r.WP; }
-            else if (g.u1 > g.u0) all_ok = false;
-            h->wgroups.push_back(g);
-            b = e;
-        }
-        if (xcorr_impl == 3 && !all_ok)
-            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the int8 screening correlator needs 3..33 channels and channel images that fit a CU's LDS");
-        if (xcorr_impl == 0 && any_ok) xcorr_impl = 3;
-        h->xcorr_impl = xcorr_impl;
-        if (xcorr_impl != 3) for (nbls_wgroup& g : h->wgroups) g.screen = false;
-        h->screen_wp = maxWP;
+// Step 6: window groups (consecutive bands of one window length) and, per group, whether the int8 screening correlator
+// applies; "auto" = screening wherever it applies, the faster general correlator elsewhere.
+static int plan_window_groups(nbls_handle* h, const plan_args& a) {
+    const int R = a.R;
+    int xcorr_impl = a.xcorr_impl;
+    h->wgroups.clear();
+    int maxWP = 0;
+    bool all_ok = true, any_ok = false;
+    for (int b = 0; b < R; ) {
+        int e = b + 1;
+        while (e < R && h->W[e] == h->W[b]) ++e;
+        nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
+        nbls_route r;                               // (xcorr_route.hip: the launchers take the same route)
+        nbls_route_compute(nbls_route_query_of(h, g.W, R, 3, false), &r);
+        g.screen = h->est[0].d_xij && r.correlator == NBLS_ROUTE_SCREEN;
+        if (g.screen) { any_ok = true; if (r.WP > maxWP) maxWP = r.WP; }
+        else if (g.u1 > g.u0) all_ok = false;
+        h->wgroups.push_back(g);
+        b = e;
     }
-    if (xcorr_impl == 3) {
-        const int WP_ = h->screen_wp;
-        // unit batches small enough for the quantised windows to stay in the 256 MiB Infinity Cache (192 MB: measured
-        // against 96 — the value of rounds 1-2 — and 384 at every BASELINE shape: 0.2-1.2 % of the pass, fewer launch tails)
-        const int64_t batch_mb = h->opt.screen_batch_mb > 0 ? h->opt.screen_batch_mb : 192;
-        int64_t batch = (int64_t)(batch_mb << 20) / ((int64_t)E * 2 * WP_);
-        if (batch < 64) batch = 64;
-        if (batch > U) batch = U > 0 ? U : 1;
-        // equal batches (a multiple of 8 units, the XCD grouping of the screening grid) instead of full ones plus a
-        // remainder: a 200-unit tail batch pays four kernel launches and their drain for next to nothing
-        if (U > batch) {
-            const int64_t nb_ = (U + batch - 1) / batch;
-            int64_t eq = ((U + nb_ - 1) / nb_ + 7) / 8 * 8;
-            if (eq < batch) batch = eq;
-        }
-        h->screen_batch = batch;
-        if ((rc = ensure(h, &h->d_qbuf, &h->cap_qbuf, (size_t)batch * E * 2 * WP_))) return rc;
-        if ((rc = ensure(h, &h->d_qmeta, &h->cap_qmeta, (size_t)batch * E * (10 + WP_ / 32) * sizeof(double)))) return rc;
-        if (h->opt.screen_stamps || h->opt.lts_stamps) {
-            if ((rc = ensure(h, &h->d_stamps, &h->cap_stamps, (size_t)(batch + 8) * E * ((E + 1) / 2) * 8 * sizeof(unsigned long long)))) return rc;   // one record per screening workgroup: (unit, sliding channel, partner group)
-        }
-        if ((rc = ensure(h, &h->d_cand, &h->cap_cand, (size_t)batch * E * E * 32 * sizeof(int32_t)))) return rc;
+    if (xcorr_impl == 3 && !all_ok)
+        return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the int8 screening correlator needs 3..33 channels and channel images that fit a CU's LDS");
+    if (xcorr_impl == 0 && any_ok) xcorr_impl = 3;
+    h->xcorr_impl = xcorr_impl;
+    if (xcorr_impl != 3) for (nbls_wgroup& g : h->wgroups) g.screen = false;
+    h->screen_wp = maxWP;
+    return 0;
+}
+
+// Step 7: the unit batch of the screening correlator and its buffers.
+static int plan_screen_batch(nbls_handle* h, const plan_args& a) {
+    if (h->xcorr_impl != 3) return 0;
+    const int E = a.E, WP_ = h->screen_wp;
+    const int64_t U = h->nunits;
+    int rc;
+    // unit batches small enough for the quantised windows to stay in the 256 MiB Infinity Cache (192 MB: measured
+    // against 96 — the value of rounds 1-2 — and 384 at every BASELINE shape: 0.2-1.2 % of the pass, fewer launch tails)
+    const int64_t batch_mb = h->opt.screen_batch_mb > 0 ? h->opt.screen_batch_mb : 192;
+    int64_t batch = (int64_t)(batch_mb << 20) / ((int64_t)E * 2 * WP_);
+    if (batch < 64) batch = 64;
+    if (batch > U) batch = U > 0 ? U : 1;
+    // equal batches (a multiple of 8 units, the XCD grouping of the screening grid) instead of full ones plus a
+    // remainder: a 200-unit tail batch pays four kernel launches and their drain for next to nothing
+    if (U > batch) {
+        const int64_t nb_ = (U + batch - 1) / batch;
+        int64_t eq = ((U + nb_ - 1) / nb_ + 7) / 8 * 8;
+        if (eq < batch) batch = eq;
     }
-    h->lts = lts != nullptr;
-    if (lts) {
-        h->ltsp = *lts;
-        h->ltsp.starts = nullptr;
-        h->ltsp.rew_table = nullptr;
-        if ((rc = alloc_copy(h, &h->d_starts, lts->starts, (size_t)lts->nstarts * 4))) return rc;
-        if ((rc = alloc_copy(h, &h->d_rew, lts->rew_table, (size_t)P + 1))) return rc;
-        const int PP = P + 16;                           // padding: the large-array LTS kernel fetches one block of pairs ahead
-        std::vector<double> xs((size_t)PP * 2, 0.0), xc((size_t)PP, 0.0);
-        for (int k = 0; k < P; ++k) {
-            xs[2 * k] = h->h_xij[2 * k] / lts->xij_mad[0];
-            xs[2 * k + 1] = h->h_xij[2 * k + 1] / lts->xij_mad[1];
-            xc[k] = xs[2 * k] * xs[2 * k + 1];
-        }
-        if ((rc = alloc_copy(h, &h->d_xs, xs.data(), xs.size()))) return rc;
-        if ((rc = alloc_copy(h, &h->d_xc, xc.data(), xc.size()))) return rc;
-        const int NS = (P + 3) / 4;                      // every 4th pair: the sample pass of the large-array LTS kernel
-        std::vector<double> xss((size_t)(NS + 16) * 2, 0.0);
-        for (int i = 0; i < NS; ++i) { xss[2 * i] = xs[2 * (4 * i)]; xss[2 * i + 1] = xs[2 * (4 * i) + 1]; }
-        if ((rc = alloc_copy(h, &h->d_xss, xss.data(), xss.size()))) return rc;
+    h->screen_batch = batch;
+    if ((rc = ensure(h, &h->d_qbuf, &h->cap_qbuf, (size_t)batch * E * 2 * WP_))) return rc;
+    if ((rc = ensure(h, &h->d_qmeta, &h->cap_qmeta, (size_t)batch * E * (10 + WP_ / 32) * sizeof(double)))) return rc;
+    if (h->opt.screen_stamps || h->opt.lts_stamps) {
+        if ((rc = ensure(h, &h->d_stamps, &h->cap_stamps, (size_t)(batch + 8) * E * ((E + 1) / 2) * 8 * sizeof(unsigned long long)))) return rc;   // one record per screening workgroup: (unit, sliding channel, partner group)
     }
-    for (int e = 0; e < h->nest; ++e) {         // the further estimators: their arrays' tables and their own result buffers
+    return ensure(h, &h->d_cand, &h->cap_cand, (size_t)batch * E * E * 32 * sizeof(int32_t));
+}
+
+// Step 8: per estimator, its array's tables (est[0]'s geometry is nbls_set_geometry's and stays where that put it) and,
+// for the further ones, their own result buffers (est[0]'s were sized with the work buffers).
+static int plan_estimators(nbls_handle* h, const plan_args& a) {
+    int rc;
+    for (int e = 0; e <= h->nest; ++e) {
         nbls_estimator& x = h->est[e];
-        const int Pe = (int)(x.h_xij.size() / 2);
-        if ((rc = alloc_copy(h, &x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
-        if ((rc = alloc_copy(h, &x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
-        if (!x.kept_pair.empty() && (rc = alloc_copy(h, &x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
-        if (x.lts) {                             // (as for estimator 0 above)
-            if ((rc = alloc_copy(h, &x.d_starts, x.h_starts.data(), x.h_starts.size()))) return rc;
-            if ((rc = alloc_copy(h, &x.d_rew, x.h_rew.data(), x.h_rew.size()))) return rc;
-            const int PP = Pe + 16;
-            std::vector<double> xs((size_t)PP * 2, 0.0), xc((size_t)PP, 0.0);
-            for (int k = 0; k < Pe; ++k) {
-                xs[2 * k] = x.h_xij[2 * k] / x.ltsp.xij_mad[0];
-                xs[2 * k + 1] = x.h_xij[2 * k + 1] / x.ltsp.xij_mad[1];
-                xc[k] = xs[2 * k] * xs[2 * k + 1];
-            }
-            if ((rc = alloc_copy(h, &x.d_xs, xs.data(), xs.size()))) return rc;
-            if ((rc = alloc_copy(h, &x.d_xc, xc.data(), xc.size()))) return rc;
-            const int NS4 = (Pe + 3) / 4;
-            std::vector<double> xss((size_t)(NS4 + 16) * 2, 0.0);
-            for (int i = 0; i < NS4; ++i) { xss[2 * i] = xs[2 * (4 * i)]; xss[2 * i + 1] = xs[2 * (4 * i) + 1]; }
-            if ((rc = alloc_copy(h, &x.d_xss, xss.data(), xss.size()))) return rc;
+        if (e > 0) {
+            if ((rc = alloc_copy(h, &x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
+            if ((rc = alloc_copy(h, &x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
+            if (!x.kept_pair.empty() && (rc = alloc_copy(h, &x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
         }
-        x.mask_bytes = (Pe + 7) / 8;
-        x.res_bytes = cells * (4 * sizeof(double) + (size_t)x.mask_bytes);
-        if ((rc = ensure(h, &x.d_res, &x.cap_res, x.res_bytes))) return rc;
-        if (!x.kept_pair.empty()) {
-            if ((rc = ensure(h, &x.d_lag, &x.cap_lag, cells * Pe * sizeof(int32_t)))) return rc;
-            if ((rc = ensure(h, &x.d_cmax, &x.cap_cmax, cells * Pe * sizeof(double)))) return rc;
-        }
-        if ((rc = ensure(h, &x.d_z, &x.cap_z, 2 * cells * sizeof(double)))) return rc;
-        if ((rc = ensure(h, &x.d_wts, &x.cap_wts, cells * Pe))) return rc;
-        if (x.want_unc && (rc = ensure(h, &x.d_unc, &x.cap_unc, 2 * cells * sizeof(double)))) return rc;
+        if (x.lts && (rc = upload_lts_tables(h, x))) return rc;
+        if (e > 0 && (rc = size_result_buffers(h, x, (size_t)a.R * a.vector_len, 0))) return rc;
     }
-    // the arena's tables in one piece (copies queued before it on the same stream came from other parts of the staging arena)
+    return 0;
+}
+
+// Step 9: the arena's tables in one piece (copies queued before it on the same stream came from other parts of the staging arena).
+static int plan_upload_arena(nbls_handle* h) {
     h->arena_mode = false;
     if (h->stage && h->d_parena && h->stage_used)
         HIPCHK(h, hipMemcpyAsync(h->d_parena, h->stage, h->stage_used, hipMemcpyHostToDevice, h->up));
+    return 0;
+}
+
+int nbls_plan(nbls_handle* h, int32_t nbands, const double* sos, int32_t nsections, int32_t zero_phase,
+              const double* taper_left, const double* taper_right, int32_t taper_len,
+              const int32_t* winlen, const int32_t* wininc, int32_t vector_len,
+              const nbls_lts_params* lts, int32_t xcorr_impl) {
+    if (!h) return NBLS_ERR_ARG;
+    h->planned = false;
+    plan_args a{nbands, sos, nsections, zero_phase, taper_left, taper_right, taper_len, winlen, wininc, vector_len, lts, xcorr_impl,
+                0, 0, 0, 0, 0};
+    int rc;
+    if ((rc = plan_check_args(h, a))) return rc;
+    const auto tp0 = std::chrono::steady_clock::now();
+    plan_filter_tables(h, a);
+    const auto tp1 = std::chrono::steady_clock::now();
+
+    HIPCHK(h, hipSetDevice(h->device));
+    StreamGuard guard(h);
+    h->planned = false;
+    h->res_loaded = false;
+    h->arena_mode = true;                                // alloc_copy: places in the arena, ONE upload at the end
+    if ((rc = plan_windows(h, a))) return rc;
+    if ((rc = plan_upload_tables(h, a))) return rc;
+    const auto tp2 = std::chrono::steady_clock::now();
+    if ((rc = plan_work_buffers(h, a))) return rc;
+    if ((rc = plan_window_groups(h, a))) return rc;
+    if ((rc = plan_screen_batch(h, a))) return rc;
+    if ((rc = plan_estimators(h, a))) return rc;
+    if ((rc = plan_upload_arena(h))) return rc;
     h->planned = true;
     if (h->opt.plan_timing) {
         const auto tp3 = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        auto ms = [](auto t0, auto t1) { return std::chrono::duration<double, std::milli>(t1 - t0).count(); };
         fprintf(stderr, "nbls_plan: tables %.3f ms, uploads %.3f ms, buffers+rest %.3f ms\n", ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3));
     }
     return NBLS_OK;
@@ -1039,7 +1115,7 @@ int nbls_execute_after(nbls_handle* h, nbls_handle* prev) {
 int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_execute: no plan");
-    if ((stage_mask & 6) && !h->d_xij) return fail(h, NBLS_ERR_STATE, "nbls_execute: no geometry set");
+    if ((stage_mask & 6) && !h->est[0].d_xij) return fail(h, NBLS_ERR_STATE, "nbls_execute: no geometry set");
     // the samples: uploaded — or on their way (nbls_upload_rows on another thread): a pass with a filter stage then takes
     // the channels as they land; any other pass needs them all before it is queued
     const int upload_st = h->upload_state.load(std::memory_order_acquire);      // (read BEFORE trace_loaded: the upload thread sets that first)
@@ -1048,18 +1124,14 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     HIPCHK(h, hipSetDevice(h->device));
     wait_uploads(h);
     h->work_queued = true;
-    const size_t cells = (size_t)h->nbands * h->vector_len;
-    const int P = h->d_xij ? h->npairs : 1;
     // padding beyond nwin[b] is zeros (narrow_band_least_squares.py:268-272): the result block (grids + weight mask) is
     // cleared here; the per-pair side arrays (lag, cmax, weights, z: 25 MB at cfg-3, five fill kernels per band group) are
     // written for every computed window and read for no other — the rows nobody computed are zeroed on the host by the
     // rare caller that fetches them (nbls_fetch: zero_uncomputed)
-    (void)cells; (void)P;
     // (a caller that did not wait for every streamed batch of the previous pass: its copies still read the block)
     if (!h->rbatches.empty() && h->cstream) HIPCHK(h, hipStreamWaitEvent(h->stream, h->rev[2 * (h->rbatches.size() - 1) + 1], 0));
     h->rbatches.clear();
-    HIPCHK(h, hipMemsetAsync(h->d_res, 0, h->res_bytes, h->stream));
-    for (int e = 0; e < h->nest; ++e) HIPCHK(h, hipMemsetAsync(h->est[e].d_res, 0, h->est[e].res_bytes, h->stream));
+    for (int e = 0; e <= h->nest; ++e) HIPCHK(h, hipMemsetAsync(h->est[e].d_res, 0, h->est[e].res_bytes, h->stream));
     if (h->prof) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (stage_mask & 1) {
         // every (band, channel) series is filtered on its own: the channels that have landed so far, then the next ones
@@ -1093,20 +1165,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     h->solve_on_stream2 = h->fuse_solve && h->stream2 && (h->opt.overlap > 0 || (h->opt.overlap == 0 && h->stream_results && small_batches));
     if (h->stream_results) {
         if (!h->cstream) HIPCHK(h, hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking));
-        if (h->cap_hres < h->res_bytes) {
-            HIPCHK(h, hipStreamSynchronize(h->cstream));
-            if (h->h_res) { (void)hipHostFree(h->h_res); h->h_res = nullptr; h->cap_hres = 0; }
-            HIPCHK(h, hipHostMalloc((void**)&h->h_res, h->res_bytes ? h->res_bytes : 8, hipHostMallocDefault));
-            h->cap_hres = h->res_bytes ? h->res_bytes : 8;
-        }
-        for (int e = 0; e < h->nest; ++e) {
-            nbls_estimator& x = h->est[e];
-            if (x.cap_hres >= x.res_bytes) continue;
-            HIPCHK(h, hipStreamSynchronize(h->cstream));
-            if (x.h_res) { (void)hipHostFree(x.h_res); x.h_res = nullptr; x.cap_hres = 0; }
-            HIPCHK(h, hipHostMalloc((void**)&x.h_res, x.res_bytes ? x.res_bytes : 8, hipHostMallocDefault));
-            x.cap_hres = x.res_bytes ? x.res_bytes : 8;
-        }
+        for (int e = 0; e <= h->nest; ++e) { const int rc = ensure_mirror(h, h->est[e]); if (rc) return rc; }
     }
     // nbls_execute_after: this pass's filter may run beside the other handle's correlation stage (memory-bound next to
     // matrix-core-bound), its own correlation stage starts when the other one's is through
@@ -1128,7 +1187,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
 // (the cell range [c0, c1) of each of the four grids and of the mask; padding cells between two bands ride along, they
 // are zero) goes to the pinned mirror on the copy stream, and an event marks the landing (nbls_wait_result_batch).
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer) {
-    if (!h->stream_results || !h->cstream || !h->h_res) return hipSuccess;
+    if (!h->stream_results || !h->cstream || !h->est[0].h_res) return hipSuccess;
     const size_t k = h->rbatches.size();
     while (h->rev.size() < 2 * (k + 1)) {
         hipEvent_t e;
@@ -1140,8 +1199,7 @@ hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipSt
     if (u1 > u0) {
         auto cell = [&](int64_t u) {
             const int b = (int)(std::upper_bound(h->unit_off.begin(), h->unit_off.end(), (int32_t)u) - h->unit_off.begin()) - 1;
-            const int64_t first = (int)h->woff.size() == h->nbands ? h->woff[b] : 0;
-            return (int64_t)b * h->vector_len + first + (u - h->unit_off[b]);
+            return (int64_t)b * h->vector_len + first_window(h, b) + (u - h->unit_off[b]);
         };
         rb.c0 = cell(u0);
         rb.c1 = cell(u1 - 1) + 1;
@@ -1149,12 +1207,12 @@ hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipSt
     hipError_t e = hipEventRecord(h->rev[2 * k], producer);
     if (e != hipSuccess) return e;
     if ((e = hipStreamWaitEvent(h->cstream, h->rev[2 * k], 0)) != hipSuccess) return e;
-    // (estimator 0, then the further ones: the event behind them marks the batch of EVERY estimator)
+    // (the plan's own estimator, then the further ones: the event behind them marks the batch of EVERY estimator)
     for (int q = 0; q <= h->nest && rb.c1 > rb.c0; ++q) {
         const size_t cells = (size_t)h->nbands * h->vector_len;
-        unsigned char* const hres = q ? h->est[q - 1].h_res : h->h_res;
-        const unsigned char* const dres = q ? h->est[q - 1].d_res : h->d_res;
-        const size_t mbytes = (size_t)(q ? h->est[q - 1].mask_bytes : h->mask_bytes);
+        unsigned char* const hres = h->est[q].h_res;
+        const unsigned char* const dres = h->est[q].d_res;
+        const size_t mbytes = (size_t)h->est[q].mask_bytes;
         if (!hres) return hipErrorInvalidValue;
         for (int g = 0; g < 4; ++g) {
             const size_t off = ((size_t)g * cells + (size_t)rb.c0) * sizeof(double);
@@ -1195,7 +1253,7 @@ int nbls_est_wait_result_batch(nbls_handle* h, int32_t est, int32_t k, int64_t* 
     HIPCHK(h, hipEventSynchronize(h->rev[2 * (size_t)k + 1]));
     const nbls_handle::result_batch& rb = h->rbatches[(size_t)k];
     if (out4) { out4[0] = rb.u0; out4[1] = rb.u1; out4[2] = rb.c0; out4[3] = rb.c1; }
-    if (host_block) *host_block = est ? h->est[est - 1].h_res : h->h_res;
+    if (host_block) *host_block = h->est[est].h_res;
     return NBLS_OK;
 }
 
@@ -1252,47 +1310,39 @@ int nbls_est_fetch(nbls_handle* h, int32_t est, double* vel, double* baz, double
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch: no such estimator");
     { const int rc = finish_pass(h); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    const nbls_solve_set s = nbls_solve_set_of(h, est);
+    const nbls_estimator& s = h->est[est];
+    const nbls_est_view v = nbls_view_of(h, s);
     const size_t P = (size_t)s.npairs;
-    const double* dg[4] = {s.d_vel, s.d_baz, s.d_mdccm, s.d_sig};
+    const double* dg[4] = {v.vel, v.baz, v.mdccm, v.sig};
     double* hg[4] = {vel, baz, mdccm, sigma_tau};
     if (vel && baz == vel + cells && mdccm == baz + cells && sigma_tau == mdccm + cells) {
-        HIPCHK(h, copy_sync(h, vel, s.d_vel, 4 * cells * sizeof(double), hipMemcpyDeviceToHost));   // caller's grids are one block too
+        HIPCHK(h, copy_sync(h, vel, v.vel, 4 * cells * sizeof(double), hipMemcpyDeviceToHost));   // caller's grids are one block too
     } else {
         for (int g = 0; g < 4; ++g)
             if (hg[g]) HIPCHK(h, copy_sync(h, hg[g], dg[g], cells * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (nwin) memcpy(nwin, h->nwin.data(), h->nbands * sizeof(int32_t));
-    // rows of windows this plan did not compute (beyond a band's count, outside a window slice) are zeros
-    auto zero_uncomputed = [&](void* out, size_t row_bytes) {
-        unsigned char* o = (unsigned char*)out;
-        for (int b = 0; b < h->nbands; ++b) {
-            const int64_t first = (int)h->woff.size() == h->nbands ? h->woff[b] : 0, n = h->nwin[b];
-            unsigned char* band = o + (size_t)b * h->vector_len * row_bytes;
-            if (first > 0) memset(band, 0, (size_t)first * row_bytes);
-            if (first + n < h->vector_len) memset(band + (size_t)(first + n) * row_bytes, 0, (size_t)(h->vector_len - first - n) * row_bytes);
-        }
-    };
+    // rows of windows this plan did not compute are zeros (zero_uncomputed)
     // the side arrays are not cleared by a pass (see nbls_execute_stages): what a stage that did NOT run in the last pass
     // would have written is zeros here, not the previous pass's values
     const bool ran_x = (h->last_stage_mask & 2) != 0, ran_s = (h->last_stage_mask & 4) != 0;
     if (lag) {
         // (a sub-array's compact rows are gathered behind the verifier as part of its solve)
-        const bool have = ran_x && (!s.d_kept_pair || ran_s);
-        if (have) { HIPCHK(h, copy_sync(h, lag, s.d_lag, cells * P * sizeof(int32_t), hipMemcpyDeviceToHost)); zero_uncomputed(lag, P * sizeof(int32_t)); }
+        const bool have = ran_x && (s.kept_pair.empty() || ran_s);
+        if (have) { HIPCHK(h, copy_sync(h, lag, v.lag, cells * P * sizeof(int32_t), hipMemcpyDeviceToHost)); zero_uncomputed(h, lag, P * sizeof(int32_t)); }
         else memset(lag, 0, cells * P * sizeof(int32_t));
     }
     if (cmax) {
-        const bool have = ran_x && (!s.d_kept_pair || ran_s);
-        if (have) { HIPCHK(h, copy_sync(h, cmax, s.d_cmax, cells * P * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(cmax, P * sizeof(double)); }
+        const bool have = ran_x && (s.kept_pair.empty() || ran_s);
+        if (have) { HIPCHK(h, copy_sync(h, cmax, v.cmax, cells * P * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(h, cmax, P * sizeof(double)); }
         else memset(cmax, 0, cells * P * sizeof(double));
     }
     if (weights) {
-        if (ran_s) { HIPCHK(h, copy_sync(h, weights, s.d_wts, cells * P, hipMemcpyDeviceToHost)); zero_uncomputed(weights, P); }
+        if (ran_s) { HIPCHK(h, copy_sync(h, weights, s.d_wts, cells * P, hipMemcpyDeviceToHost)); zero_uncomputed(h, weights, P); }
         else memset(weights, 0, cells * P);
     }
     if (z) {
-        if (ran_s) { HIPCHK(h, copy_sync(h, z, s.d_z, 2 * cells * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(z, 2 * sizeof(double)); }
+        if (ran_s) { HIPCHK(h, copy_sync(h, z, s.d_z, 2 * cells * sizeof(double), hipMemcpyDeviceToHost)); zero_uncomputed(h, z, 2 * sizeof(double)); }
         else memset(z, 0, 2 * cells * sizeof(double));
     }
     return NBLS_OK;
@@ -1300,10 +1350,10 @@ int nbls_est_fetch(nbls_handle* h, int32_t est, double* vel, double* baz, double
 
 int nbls_set_uncertainty(nbls_handle* h, const double* eig6) {
     if (!h) return NBLS_ERR_ARG;
-    h->want_unc = eig6 != nullptr;
+    h->est[0].want_unc = eig6 != nullptr;
     if (eig6) {
         if (!(eig6[0] > 0.0) || !(eig6[1] > 0.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_uncertainty: the eigenvalues of X^T X must be positive");
-        for (int i = 0; i < 6; ++i) h->unc_par[i] = eig6[i];
+        for (int i = 0; i < 6; ++i) h->est[0].unc_par[i] = eig6[i];
     }
     h->planned = false;                      // (the next plan sizes the output buffer)
     return NBLS_OK;
@@ -1317,7 +1367,7 @@ int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t est, double* vel_uncert, 
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_uncertainty: no plan");
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_uncertainty: no such estimator");
-    const nbls_solve_set s = nbls_solve_set_of(h, est);
+    const nbls_estimator& s = h->est[est];
     if (!s.want_unc || !s.d_unc) return fail(h, NBLS_ERR_STATE, "nbls_fetch_uncertainty: nbls_set_uncertainty (or the estimator's eig6) before nbls_plan");
     { const int rc = finish_pass(h); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len;
@@ -1326,13 +1376,7 @@ int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t est, double* vel_uncert, 
         if (!outs[g]) continue;
         if (!(h->last_stage_mask & 4)) { memset(outs[g], 0, cells * sizeof(double)); continue; }
         HIPCHK(h, copy_sync(h, outs[g], s.d_unc + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
-        // rows of windows this plan did not compute are zeros, like the grids
-        for (int b = 0; b < h->nbands; ++b) {
-            const int64_t first = (int)h->woff.size() == h->nbands ? h->woff[b] : 0, n = h->nwin[b];
-            double* band = outs[g] + (size_t)b * h->vector_len;
-            for (int64_t w = 0; w < first; ++w) band[w] = 0.0;
-            for (int64_t w = first + n; w < h->vector_len; ++w) band[w] = 0.0;
-        }
+        zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
     }
     return NBLS_OK;
 }
@@ -1390,7 +1434,8 @@ int nbls_filter_segment(nbls_handle* h, int32_t reverse, const double* state_in,
 int nbls_device_results(nbls_handle* h, void** ptrs, int64_t* bytes_per_grid) {
     if (!h || !ptrs) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_device_results: no plan");
-    ptrs[0] = h->d_vel; ptrs[1] = h->d_baz; ptrs[2] = h->d_mdccm; ptrs[3] = h->d_sig; ptrs[4] = h->d_nwin;
+    const nbls_est_view v = nbls_view_of(h, h->est[0]);
+    ptrs[0] = v.vel; ptrs[1] = v.baz; ptrs[2] = v.mdccm; ptrs[3] = v.sig; ptrs[4] = h->d_nwin;
     if (bytes_per_grid) *bytes_per_grid = (int64_t)h->nbands * h->vector_len * (int64_t)sizeof(double);
     return NBLS_OK;
 }
@@ -1402,8 +1447,8 @@ int nbls_est_result_layout(nbls_handle* h, int32_t est, int64_t* out4) {
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_result_layout: no plan");
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_result_layout: no such estimator");
     out4[0] = (int64_t)h->nbands * h->vector_len;
-    out4[1] = est ? h->est[est - 1].mask_bytes : h->mask_bytes;
-    out4[2] = (int64_t)(est ? h->est[est - 1].res_bytes : h->res_bytes);
+    out4[1] = h->est[est].mask_bytes;
+    out4[2] = (int64_t)h->est[est].res_bytes;
     out4[3] = (int64_t)(4 * sizeof(double)) * out4[0];      // byte offset of the mask
     return NBLS_OK;
 }
@@ -1414,8 +1459,8 @@ int nbls_est_fetch_packed(nbls_handle* h, int32_t est, void* out, int64_t nbytes
     if (!h || !out) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_packed: no plan");
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_packed: no such estimator");
-    const unsigned char* dres = est ? h->est[est - 1].d_res : h->d_res;
-    const size_t rbytes = est ? h->est[est - 1].res_bytes : h->res_bytes;
+    const unsigned char* dres = h->est[est].d_res;
+    const size_t rbytes = h->est[est].res_bytes;
     if (nbytes != (int64_t)rbytes) return fail(h, NBLS_ERR_ARG, "nbls_fetch_packed: size does not match nbls_result_layout");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(out, dres, rbytes, hipMemcpyDeviceToHost, h->stream));   // ordered after the pass
@@ -1429,14 +1474,13 @@ int nbls_load_result_block(nbls_handle* h, const void* block, int64_t nbytes) {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t need = std::max((size_t)nbytes + 8, h->reserve_res);
     int rc;
-    if ((rc = ensure(h, &h->d_res, &h->cap_res, need))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_res, 0, h->cap_res, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_res, block, (size_t)nbytes, hipMemcpyHostToDevice, h->stream));
+    nbls_estimator& x = h->est[0];
+    if ((rc = ensure(h, &x.d_res, &x.cap_res, need))) return rc;
+    HIPCHK(h, hipMemsetAsync(x.d_res, 0, x.cap_res, h->stream));
+    HIPCHK(h, hipMemcpyAsync(x.d_res, block, (size_t)nbytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));              // the host buffer may go away
-    h->res_bytes = (size_t)nbytes;
-    h->d_vel = h->d_baz = h->d_mdccm = h->d_sig = nullptr;   // the views of the last plan no longer describe the block
-    h->d_mask = nullptr;
-    h->planned = false;                                      // ... and a new pass needs a new plan
+    x.res_bytes = (size_t)nbytes;
+    h->planned = false;                                      // the last plan no longer describes the block: a new pass needs a new plan
     h->res_loaded = true;                                    // (nbls_comm_gather: this block is a result, whatever its allocation's size)
     return NBLS_OK;
 }

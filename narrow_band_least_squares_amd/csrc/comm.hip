@@ -229,43 +229,44 @@ int nbls_comm_gather(nbls_handle* const* hs, int32_t n, int32_t root, int64_t bl
     std::vector<unsigned char*> standin(n, nullptr);          // freed at the end
     for (int i = 0; i < n; ++i) {
         nbls_handle* h = hs[i];
+        nbls_estimator& x = h->est[0];            // the block a rank sends is its plan's own
         bool ok = hipnote(h, hipSetDevice(h->device), "hipSetDevice");
         bool use_own = ok;
-        if (ok && (h->planned || h->res_loaded) && (int64_t)h->res_bytes + 8 > block_bytes) {
+        if (ok && (h->planned || h->res_loaded) && (int64_t)x.res_bytes + 8 > block_bytes) {
             note(h, NBLS_ERR_ARG, "nbls_comm_gather: block_bytes smaller than the result block + status word");
             use_own = false;
         }
-        if (ok && use_own && h->res_loaded && h->d_res && h->cap_res < (size_t)block_bytes) {
+        if (ok && use_own && h->res_loaded && x.d_res && x.cap_res < (size_t)block_bytes) {
             // a block assembled on the host (nbls_load_result_block) without nbls_reserve_results(block_bytes): it is
             // this rank's RESULT, not a failed rank's leftovers — move it into an allocation of the gather's size
             unsigned char* nb_ = nullptr;
             if (hipnote(h, hipMalloc((void**)&nb_, (size_t)block_bytes), "hipMalloc(result block)")) {
                 (void)hipnote(h, hipMemsetAsync(nb_, 0, (size_t)block_bytes, h->stream), "hipMemsetAsync");
-                (void)hipnote(h, hipMemcpyAsync(nb_, h->d_res, h->res_bytes, hipMemcpyDeviceToDevice, h->stream), "hipMemcpyAsync(loaded block)");
+                (void)hipnote(h, hipMemcpyAsync(nb_, x.d_res, x.res_bytes, hipMemcpyDeviceToDevice, h->stream), "hipMemcpyAsync(loaded block)");
                 (void)hipnote(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize");
-                (void)hipFree(h->d_res);
-                h->d_res = nb_;
-                h->cap_res = (size_t)block_bytes;
+                (void)hipFree(x.d_res);
+                x.d_res = nb_;
+                x.cap_res = (size_t)block_bytes;
             } else use_own = false;
         }
-        if (ok && use_own && (!h->d_res || h->cap_res < (size_t)block_bytes)) {
+        if (ok && use_own && (!x.d_res || x.cap_res < (size_t)block_bytes)) {
             if (h->planned) {
                 note(h, NBLS_ERR_STATE, "nbls_comm_gather: call nbls_reserve_results(block_bytes) before nbls_plan");
                 use_own = false;
             } else {
                 // a rank that failed before it could plan: an empty block of its own
-                if (h->d_res) { (void)hipFree(h->d_res); h->d_res = nullptr; h->cap_res = 0; }
-                if (hipnote(h, hipMalloc((void**)&h->d_res, (size_t)block_bytes), "hipMalloc(result block)")) {
-                    h->cap_res = (size_t)block_bytes;
-                    (void)hipnote(h, hipMemsetAsync(h->d_res, 0, (size_t)block_bytes, h->stream), "hipMemsetAsync");
+                if (x.d_res) { (void)hipFree(x.d_res); x.d_res = nullptr; x.cap_res = 0; }
+                if (hipnote(h, hipMalloc((void**)&x.d_res, (size_t)block_bytes), "hipMalloc(result block)")) {
+                    x.cap_res = (size_t)block_bytes;
+                    (void)hipnote(h, hipMemsetAsync(x.d_res, 0, (size_t)block_bytes, h->stream), "hipMemsetAsync");
                 } else {
-                    h->d_res = nullptr;
+                    x.d_res = nullptr;
                     use_own = false;
                 }
             }
         }
         if (use_own) {
-            send[i] = h->d_res;
+            send[i] = x.d_res;
         } else if (hipMalloc((void**)&standin[i], (size_t)block_bytes) == hipSuccess) {
             (void)hipMemsetAsync(standin[i], 0, (size_t)block_bytes, h->stream);
             send[i] = standin[i];

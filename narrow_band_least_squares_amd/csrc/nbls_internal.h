@@ -60,62 +60,44 @@ struct nbls_options {
 // Consecutive bands of one window length: the unit of the correlator choice (nbls_plan / nbls_launch_xcorr).
 struct nbls_wgroup { int b0, b1, W; int64_t u0, u1; bool screen; };
 
-// What one solve of a pass reads and writes: the geometry and LTS tables of ONE array (the full one or a sub-array),
-// the lag / cmax rows it takes them from and the result block it fills.  Estimator 0 is what nbls_set_geometry and
-// nbls_plan describe (nbls_solve_set_of copies the handle's members); further estimators (nbls_set_estimators) own theirs.
-struct nbls_solve_set {
-    int npairs = 0;
-    const double* d_xij = nullptr;     // [P'][2]
-    const double* d_xpinv = nullptr;   // [2][P']
-    bool lts = false;
-    nbls_lts_params ltsp{};
-    const double* d_xs = nullptr;
-    const double* d_xc = nullptr;
-    const double* d_xss = nullptr;
-    const int32_t* d_starts = nullptr;
-    const double* d_rew = nullptr;
-    bool want_unc = false;
-    double unc_par[6] = {0, 0, 0, 0, 0, 0};
-    double* d_unc = nullptr;           // [2][B][VL]
-    // a sub-array's solve reads compact copies of its pairs' rows (gather_pairs_kernel): d_lag / d_cmax are then the
-    // estimator's own [B][VL][P'] buffers, filled per unit batch from the handle's through d_kept_pair [P']
-    const int32_t* d_kept_pair = nullptr;
-    int32_t* d_lag = nullptr;          // [B][VL][P']
-    double* d_cmax = nullptr;
-    double* d_vel = nullptr;           // [B][VL] (views into d_res)
-    double* d_baz = nullptr;
-    double* d_mdccm = nullptr;
-    double* d_sig = nullptr;
-    uint8_t* d_mask = nullptr;
-    double* d_z = nullptr;
-    uint8_t* d_wts = nullptr;
-    int mask_bytes = 0;
-    unsigned char* d_res = nullptr;    // result block, layout as nbls_handle::d_res
-    size_t res_bytes = 0;
-    unsigned char* h_res = nullptr;    // its pinned mirror (streamed passes)
-};
-
-// A further estimator of the pass (nbls_set_estimators): host copies of what the caller described, the device tables
-// nbls_plan makes of them, and the buffers of its own results.
+// One estimator of a pass: the geometry and LTS plan of ONE array (the full one or a sub-array) as the caller described
+// them, the device tables nbls_plan makes of them, and the buffers of its own results.  The handle holds 1 + 8 of these
+// records: est[0] is the plan's own estimator (nbls_set_geometry, nbls_plan(lts = ...), nbls_set_uncertainty), est[1..nest]
+// are the further ones (nbls_set_estimators).  What a record does not store is derived by nbls_view_of below.
 struct nbls_estimator {
-    std::vector<int32_t> kept;         // element indices, ascending
+    std::vector<int32_t> kept;         // element indices, ascending (est[0]: empty, it is the whole array)
     std::vector<int32_t> kept_pair;    // [P']: index of pair k of the sub-array in the full array's pair list (empty: all elements kept)
+    int npairs = 0;                    // P'
     std::vector<double> h_xij, h_xpinv;
     bool lts = false;
-    nbls_lts_params ltsp{};            // starts / rew_table point into the two vectors below
+    nbls_lts_params ltsp{};            // starts / rew_table are NULL here: the tables are the two vectors below
     std::vector<int32_t> h_starts;
     std::vector<double> h_rew;
-    bool want_unc = false;
-    double unc_par[6] = {0, 0, 0, 0, 0, 0};
+    bool want_unc = false;             // confidence intervals of the slowness estimate: computed behind the solve when wanted
+    double unc_par[6] = {0, 0, 0, 0, 0, 0};   // eigenvalues of X^T X, rotation into the eigen-frame (row major)
     // device side
-    double *d_xij = nullptr, *d_xpinv = nullptr, *d_xs = nullptr, *d_xc = nullptr, *d_xss = nullptr, *d_rew = nullptr;
-    int32_t *d_starts = nullptr, *d_kept_pair = nullptr;
+    double* d_xij = nullptr;           // [P'][2]
+    double* d_xpinv = nullptr;         // [2][P']
+    int32_t* d_starts = nullptr;       // [S][4]
+    double* d_rew = nullptr;           // [P'+1]
+    double* d_xs = nullptr;            // [P'][2] standardised co-array
+    double* d_xc = nullptr;            // [P'] c0*c1 of the standardised co-array; d_xs and d_xc are padded by 16 pairs (solve_bucket.inc reads one block ahead)
+    double* d_xss = nullptr;           // [ceil(P'/4)][2] every 4th row of d_xs (padded likewise)
+    // a sub-array's solve reads compact copies of its pairs' rows (gather_pairs_kernel): its own [B][VL][P'] buffers,
+    // filled per unit batch from the handle's through d_kept_pair [P']; a full array reads the handle's d_lag / d_cmax
+    int32_t* d_kept_pair = nullptr;
     int32_t* d_lag = nullptr;
-    double *d_cmax = nullptr, *d_z = nullptr, *d_unc = nullptr;
-    uint8_t* d_wts = nullptr;
-    unsigned char *d_res = nullptr, *h_res = nullptr;
+    double* d_cmax = nullptr;
+    double* d_z = nullptr;             // [B][VL][2]
+    uint8_t* d_wts = nullptr;          // [B][VL][P'] one byte per pair (kernel-side form; packed into the mask after the solve)
+    double* d_unc = nullptr;           // [2][B][VL]: vel_uncert | baz_uncert
+    // result block, ONE allocation = one D2H copy / one RCCL gather:
+    //   [vel | baz | mdccm | sigma_tau] double[4][B][VL], then the LTS weight bit mask uint8[B][VL][MB],
+    //   MB = ceil(P'/8), bit k & 7 of byte k >> 3 = weight of pair k (ceil(P/8) bytes per unit)
+    unsigned char* d_res = nullptr;
+    unsigned char* h_res = nullptr;    // its pinned mirror, filled batch by batch (nbls_stream_results)
     size_t cap_lag = 0, cap_cmax = 0, cap_z = 0, cap_unc = 0, cap_wts = 0, cap_res = 0, cap_hres = 0, res_bytes = 0;
-    int mask_bytes = 0;
+    int mask_bytes = 0;                // MB
 };
 
 #define NBLS_MAX_ESTIMATORS 8      // further estimators of one pass, beside estimator 0
@@ -141,8 +123,6 @@ struct nbls_handle {
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
-    unsigned char* h_res = nullptr; // pinned mirror of d_res
-    size_t cap_hres = 0;
     hipStream_t cstream = nullptr;  // the D2H copies of the batches (a DMA engine beside the compute streams)
     struct result_batch { int64_t u0, u1, c0, c1; };
     std::vector<result_batch> rbatches;   // batches queued by the last nbls_execute*, in the order they finish
@@ -168,15 +148,11 @@ struct nbls_handle {
     int64_t npts = 0, npts_pad = 0;
     double fs = 0.0;
 
-    // ---- geometry ----
+    // ---- geometry: the pass's array, what the correlators see (its co-array is est[0]'s) ----
     int npairs = 0;
-    double* d_xij = nullptr;       // [P][2]
     int32_t* d_pair = nullptr;     // [P][2]
-    double* d_xpinv = nullptr;     // [2][P]
-    std::vector<double> h_xij;
+    std::vector<int32_t> h_pair;   // host copy (as est[0].h_xij / h_xpinv): an identical nbls_set_geometry uploads nothing
     std::vector<double> h_tl, h_tr;   // host copies of the taper ramps (the same for every band group and call of one trace length: uploaded once)
-    std::vector<int32_t> h_pair;   // host copies of the other two geometry tables: an identical nbls_set_geometry uploads nothing
-    std::vector<double> h_xpinv;
 
     // ---- plan ----
     bool planned = false;
@@ -218,33 +194,15 @@ struct nbls_handle {
     size_t cap_tstate = 0;
     int32_t* d_lag = nullptr;      // [B][VL][P]
     double* d_cmax = nullptr;      // [B][VL][P]
-    // result block, ONE allocation = one D2H copy / one RCCL gather:
-    //   [vel | baz | mdccm | sigma_tau] double[4][B][VL], then the LTS weight bit mask uint8[B][VL][MB],
-    //   MB = ceil(P/8), bit k & 7 of byte k >> 3 = weight of pair k (ceil(P/8) bytes per unit)
-    unsigned char* d_res = nullptr;
-    size_t cap_res = 0, res_bytes = 0;
-    bool res_loaded = false;       // d_res holds a block put there by nbls_load_result_block (cleared by the next nbls_plan)
-    size_t reserve_res = 0;        // minimum allocation of the result block (nbls_reserve_results: equal gather blocks)
+    size_t cap_filt = 0, cap_cstate = 0, cap_lag = 0, cap_cmax = 0;
+    bool res_loaded = false;       // est[0].d_res holds a block put there by nbls_load_result_block (cleared by the next nbls_plan)
+    size_t reserve_res = 0;        // minimum allocation of est[0]'s result block (nbls_reserve_results: equal gather blocks)
     // ---- RCCL gather (comm.hip) ----
     void* comm = nullptr;          // ncclComm_t
     int comm_world = 1, comm_rank = 0;
     unsigned char* d_gather = nullptr;   // [world][block_bytes] receive side
     size_t cap_gather = 0;
     int64_t gather_status = 0;     // host copy of the status word while its H2D copy is in flight
-    int mask_bytes = 0;            // MB
-    double* d_vel = nullptr;       // [B][VL]   (views into d_res)
-    double* d_baz = nullptr;
-    double* d_mdccm = nullptr;
-    double* d_sig = nullptr;
-    uint8_t* d_mask = nullptr;     // [B][VL][MB] (view into d_res)
-    // confidence intervals of the slowness estimate (nbls_set_uncertainty): computed behind the solve when wanted
-    bool want_unc = false;
-    double unc_par[6] = {0, 0, 0, 0, 0, 0};   // eigenvalues of X^T X, rotation into the eigen-frame (row major)
-    double* d_unc = nullptr;       // [2][B][VL]: vel_uncert | baz_uncert
-    size_t cap_unc = 0;
-    double* d_z = nullptr;         // [B][VL][2]
-    uint8_t* d_wts = nullptr;      // [B][VL][P] one byte per pair (kernel-side form; packed into d_mask after the solve)
-    size_t cap_filt = 0, cap_cstate = 0, cap_lag = 0, cap_cmax = 0, cap_z = 0, cap_wts = 0;
     std::unordered_map<const void*, size_t> caps;   // capacities of the small plan tables, keyed by the address of the pointer member
     // pinned staging of the plan tables (api.hip: alloc_copy): a copy from pinned memory goes through the DMA engines,
     // a copy from pageable memory is a shader copy that has to find a free CU — with three other band groups of the
@@ -283,19 +241,10 @@ struct nbls_handle {
     unsigned long long* d_stamps = nullptr;   // developer: s_memtime stamps of the screen kernel's workgroups
     size_t cap_stamps = 0;
 
-    // ---- LTS ----
-    bool lts = false;
-    nbls_lts_params ltsp{};
-    int32_t* d_starts = nullptr;   // [S][4]
-    double* d_rew = nullptr;       // [P+1]
-    double* d_xs = nullptr;        // [P][2] standardised co-array
-    double* d_xss = nullptr;       // [ceil(P/4)][2] every 4th row of d_xs (padded likewise)
-    double* d_xc = nullptr;        // [P] c0*c1 of the standardised co-array; d_xs and d_xc are padded by 16 pairs (solve_bucket.inc reads one block ahead)
-    size_t cap_starts = 0;
-
-    // ---- further estimators of the pass (nbls_set_estimators); nest == 0: the plain pass ----
+    // ---- the estimators of the pass: est[0] the plan's own, est[1..nest] the further ones (nest == 0: the plain pass).
+    // A fixed member: the capacities and the arena ownership of a record's tables are keyed by the address of its pointers
     int nest = 0;
-    nbls_estimator est[NBLS_MAX_ESTIMATORS];
+    nbls_estimator est[1 + NBLS_MAX_ESTIMATORS];
 
     // ---- profiling ----
     bool prof = false;
@@ -315,10 +264,18 @@ hipError_t nbls_launch_xcorr(nbls_handle* h);
 hipError_t nbls_launch_solve(nbls_handle* h);
 hipError_t nbls_launch_solve_range(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
-// the solve set of estimator e of the handle's plan (0: the handle's own geometry, LTS plan and result block)
-nbls_solve_set nbls_solve_set_of(const nbls_handle* h, int e);
-// [gather ->] solve -> [uncertainty ->] pack of units [u0, u0 + nu) for one solve set
-hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st);
+// What a record does not store: the four grids [B][VL] and the mask inside its result block, and the lag / cmax rows its
+// solve reads (the pass's own for a full array, the record's compact ones for a sub-array).
+struct nbls_est_view { double *vel, *baz, *mdccm, *sig; uint8_t* mask; int32_t* lag; double* cmax; };
+inline nbls_est_view nbls_view_of(const nbls_handle* h, const nbls_estimator& x) {
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    double* const g = (double*)x.d_res;
+    const bool own = x.kept_pair.empty();
+    return {g, g + cells, g + 2 * cells, g + 3 * cells, x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr,
+            own ? h->d_lag : x.d_lag, own ? h->d_cmax : x.d_cmax};
+}
+// [gather ->] solve -> [uncertainty ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
+hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);
 hipError_t nbls_launch_probe_mfma(nbls_handle* h, const double* da, const double* db, double* dout);

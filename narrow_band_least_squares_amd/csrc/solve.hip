@@ -1384,76 +1384,40 @@ __global__ __launch_bounds__(GATHER_WAVES * 64) void gather_pairs_kernel(const i
     }
 }
 
-static hipError_t solve_range_impl(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st);
+static hipError_t solve_range_impl(nbls_handle* h, const nbls_estimator& s, const nbls_est_view& v, int64_t u0, int64_t nu, hipStream_t st);
 
-static hipError_t pack_weights_of(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st) {
+static hipError_t pack_weights_of(nbls_handle* h, const nbls_estimator& s, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
     const int MB = s.mask_bytes;
     const int64_t items = nu * MB;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s.d_wts, s.d_mask,
+    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s.d_wts, nbls_view_of(h, s).mask,
                        h->d_unit_band, h->d_unit_win, h->vector_len, s.npairs, MB, (int)u0, (int)nu);
     return hipGetLastError();
 }
 
 hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
-    return pack_weights_of(h, nbls_solve_set_of(h, 0), u0, nu, st);
+    return pack_weights_of(h, h->est[0], u0, nu, st);
 }
 
-nbls_solve_set nbls_solve_set_of(const nbls_handle* h, int e) {
-    nbls_solve_set s;
-    const size_t cells = (size_t)h->nbands * h->vector_len;
-    if (e <= 0) {
-        s.npairs = h->npairs;
-        s.d_xij = h->d_xij; s.d_xpinv = h->d_xpinv;
-        s.lts = h->lts; s.ltsp = h->ltsp;
-        s.d_xs = h->d_xs; s.d_xc = h->d_xc; s.d_xss = h->d_xss; s.d_starts = h->d_starts; s.d_rew = h->d_rew;
-        s.want_unc = h->want_unc;
-        for (int i = 0; i < 6; ++i) s.unc_par[i] = h->unc_par[i];
-        s.d_unc = h->d_unc;
-        s.d_lag = h->d_lag; s.d_cmax = h->d_cmax;
-        s.d_vel = h->d_vel; s.d_baz = h->d_baz; s.d_mdccm = h->d_mdccm; s.d_sig = h->d_sig; s.d_mask = h->d_mask;
-        s.d_z = h->d_z; s.d_wts = h->d_wts;
-        s.mask_bytes = h->mask_bytes;
-        s.d_res = h->d_res; s.res_bytes = h->res_bytes; s.h_res = h->h_res;
-        return s;
-    }
-    const nbls_estimator& x = h->est[e - 1];
-    s.npairs = (int)(x.h_xij.size() / 2);
-    s.d_xij = x.d_xij; s.d_xpinv = x.d_xpinv;
-    s.lts = x.lts; s.ltsp = x.ltsp;
-    s.d_xs = x.d_xs; s.d_xc = x.d_xc; s.d_xss = x.d_xss; s.d_starts = x.d_starts; s.d_rew = x.d_rew;
-    s.want_unc = x.want_unc;
-    for (int i = 0; i < 6; ++i) s.unc_par[i] = x.unc_par[i];
-    s.d_unc = x.d_unc;
-    if (x.kept_pair.empty()) { s.d_lag = h->d_lag; s.d_cmax = h->d_cmax; }          // the full array: the pass's own rows
-    else { s.d_kept_pair = x.d_kept_pair; s.d_lag = x.d_lag; s.d_cmax = x.d_cmax; }
-    s.d_vel = (double*)x.d_res;
-    s.d_baz = s.d_vel + cells; s.d_mdccm = s.d_baz + cells; s.d_sig = s.d_mdccm + cells;
-    s.d_mask = x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr;
-    s.d_z = x.d_z; s.d_wts = x.d_wts;
-    s.mask_bytes = x.mask_bytes;
-    s.d_res = x.d_res; s.res_bytes = x.res_bytes; s.h_res = x.h_res;
-    return s;
-}
-
-hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st) {
+hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_t u0, int64_t nu, hipStream_t st) {
     hipError_t e;
-    if (s.d_kept_pair && nu > 0) {
+    const nbls_est_view v = nbls_view_of(h, s);
+    if (!s.kept_pair.empty() && nu > 0) {
         const int P = h->npairs, Pc = s.npairs;
         const size_t shm = (size_t)GATHER_WAVES * P * (sizeof(double) + sizeof(int32_t)) + (size_t)Pc * sizeof(int32_t);
         int64_t grid = (nu + GATHER_WAVES - 1) / GATHER_WAVES;
         const int64_t cap = (int64_t)(h->num_cus > 0 ? h->num_cus : 256) * 8;       // a few trips per wave: the map is loaded once
         if (grid > cap) grid = cap;
         hipLaunchKernelGGL(gather_pairs_kernel, dim3((unsigned)grid), dim3(GATHER_WAVES * 64), shm, st, (const int32_t*)h->d_lag,
-                           (const double*)h->d_cmax, s.d_lag, s.d_cmax, s.d_kept_pair, (const int32_t*)h->d_unit_band,
+                           (const double*)h->d_cmax, v.lag, v.cmax, (const int32_t*)s.d_kept_pair, (const int32_t*)h->d_unit_band,
                            (const int32_t*)h->d_unit_win, h->vector_len, P, Pc, (int)u0, (int)nu);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if ((e = solve_range_impl(h, s, u0, nu, st)) != hipSuccess) return e;
+    if ((e = solve_range_impl(h, s, v, u0, nu, st)) != hipSuccess) return e;
     if (s.want_unc && s.d_unc && nu > 0) {
         UArgs a{};
         const size_t cells = (size_t)h->nbands * h->vector_len;
-        a.z = s.d_z; a.sig = s.d_sig; a.vunc = s.d_unc; a.bunc = s.d_unc + cells;
+        a.z = s.d_z; a.sig = v.sig; a.vunc = s.d_unc; a.bunc = s.d_unc + cells;
         a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
         a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
         a.ev0 = s.unc_par[0]; a.ev1 = s.unc_par[1];
@@ -1464,21 +1428,21 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_solve_set& s, int64_
     return pack_weights_of(h, s, u0, nu, st);
 }
 
-// Every estimator of the pass, one after the other on `st`: estimator 0, then the further ones (nbls_set_estimators).
+// Every estimator of the pass, one after the other on `st`: the plan's own, then the further ones (nbls_set_estimators).
 hipError_t nbls_launch_solve_range(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
     for (int e = 0; e <= h->nest; ++e) {
-        const hipError_t err = nbls_launch_solve_set(h, nbls_solve_set_of(h, e), u0, nu, st);
+        const hipError_t err = nbls_launch_solve_set(h, h->est[e], u0, nu, st);
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
 }
 
-static hipError_t solve_range_impl(nbls_handle* h, const nbls_solve_set& s, int64_t u0, int64_t nu, hipStream_t st) {
+static hipError_t solve_range_impl(nbls_handle* h, const nbls_estimator& s, const nbls_est_view& v, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
     SArgs a{};
     a.u0 = (int)u0;
-    a.lag = s.d_lag;
-    a.cmax = s.d_cmax;
+    a.lag = v.lag;
+    a.cmax = v.cmax;
     a.npairs = s.npairs;
     a.vector_len = h->vector_len;
     a.unit_off = h->d_unit_off;
@@ -1488,10 +1452,10 @@ static hipError_t solve_range_impl(nbls_handle* h, const nbls_solve_set& s, int6
     a.fs = h->fs;
     a.xij = s.d_xij;
     a.xpinv = s.d_xpinv;
-    a.vel = s.d_vel;
-    a.baz = s.d_baz;
-    a.mdccm = s.d_mdccm;
-    a.sig = s.d_sig;
+    a.vel = v.vel;
+    a.baz = v.baz;
+    a.mdccm = v.mdccm;
+    a.sig = v.sig;
     a.z = s.d_z;
     a.wts = s.d_wts;
     const int nunits = (int)nu;
