@@ -43,46 +43,38 @@ hipError_t copy_sync(nbls_handle* h, void* dst, const void* src, size_t bytes, h
     return e;
 }
 
+// A buffer's grow as the API's result: `what` is the allocator call the error text names.
+int grown(nbls_handle* h, hipError_t e, const char* what) {
+    if (e == hipSuccess) return 0;
+    return fail(h, e == hipErrorOutOfMemory ? NBLS_ERR_NOMEM : NBLS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// A work or result buffer of at least need_bytes; contents are not kept.
 template <typename T>
-int ensure(nbls_handle* h, T** p, size_t* cap, size_t need_bytes) {
-    if (*p && *cap >= need_bytes) return 0;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if (need_bytes == 0) need_bytes = 8;
-    hipError_t e = hipMalloc((void**)p, need_bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(h, NBLS_ERR_NOMEM, std::string("hipMalloc(") + std::to_string(need_bytes) + "): " + hipGetErrorString(e));
-    }
-    *cap = need_bytes;
+int ensure(nbls_handle* h, dev_buf<T>& b, size_t need_bytes) {
+    const hipError_t e = b.grow(need_bytes);
+    if (e != hipSuccess)
+        return fail(h, NBLS_ERR_NOMEM, std::string("hipMalloc(") + std::to_string(need_bytes ? need_bytes : 8) + "): " + hipGetErrorString(e));
     return 0;
 }
 
 // Upload a small plan table.  The allocation is kept and reused while it is big enough (hipFree
-// synchronises the device and hipMalloc is slow: a plan uploads ~15 of these); its capacity is
-// remembered in h->caps under the address of the pointer member.
+// synchronises the device and hipMalloc is slow: a plan uploads ~15 of these).
 template <typename T>
-int alloc_copy(nbls_handle* h, T** p, const T* src, size_t n) {
+int alloc_copy(nbls_handle* h, dev_buf<T>& p, const T* src, size_t n) {
     const size_t need = (n ? n : 1) * sizeof(T);
-    const bool owned = h->arena_owned.count((const void*)p) != 0;
     {
         const size_t slot = (need + 63) & ~(size_t)63;
-        if (h->arena_mode && h->stage && h->d_parena && h->stage_used + slot <= h->stage_cap) {
+        if (h->arena_mode && h->stage && h->d_parena && h->stage_used + slot <= h->stage.cap) {
             // a table of nbls_plan: a place in the arena, no copy of its own (StreamGuard sends the arena in one piece)
-            if (*p && !owned) { (void)hipFree(*p); h->caps.erase((const void*)p); }
             if (n) memcpy(h->stage + h->stage_used, src, n * sizeof(T));
-            *p = (T*)(h->d_parena + h->stage_used);
+            p.place((T*)(h->d_parena + h->stage_used));
             h->stage_used += slot;
-            h->arena_owned.insert((const void*)p);
             return 0;
         }
     }
-    if (owned) { *p = nullptr; h->arena_owned.erase((const void*)p); h->caps[(const void*)p] = 0; }   // back to an allocation of its own
-    size_t& cap = h->caps[(const void*)p];
-    if (!*p || cap < need) {
-        if (*p) { (void)hipFree(*p); *p = nullptr; cap = 0; }
-        HIPCHK(h, hipMalloc((void**)p, need));
-        cap = need;
-    }
+    p.leave_arena();                                                 // back to an allocation of its own
+    if (int rc = grown(h, p.grow(need), "hipMalloc((void**)p, need)")) return rc;
     // queued on the handle's UPLOAD stream (highest priority: a plan made while other handles' passes fill the GPU
     // must not wait behind them — on a low-priority compute stream the ~15 small copies of a plan took 5 ms instead
     // of 0.3); nbls_plan / nbls_set_geometry wait for that stream before they return (StreamGuard), i.e. before the
@@ -90,14 +82,14 @@ int alloc_copy(nbls_handle* h, T** p, const T* src, size_t n) {
     if (n) {
         const size_t bytes = n * sizeof(T), slot = (bytes + 63) & ~(size_t)63;
         const void* from = src;
-        if (h->stage && h->stage_used + slot <= h->stage_cap) {      // through the pinned arena (reset by StreamGuard)
+        if (h->stage && h->stage_used + slot <= h->stage.cap) {      // through the pinned arena (reset by StreamGuard)
             memcpy(h->stage + h->stage_used, src, bytes);
             from = h->stage + h->stage_used;
             h->stage_used += slot;
         } else {
             h->stage_bypass = true;                                  // the caller's buffer is read: the guard has to wait
         }
-        HIPCHK(h, hipMemcpyAsync(*p, from, bytes, hipMemcpyHostToDevice, h->up));
+        HIPCHK(h, hipMemcpyAsync(p, from, bytes, hipMemcpyHostToDevice, h->up));
     }
     return 0;
 }
@@ -115,15 +107,11 @@ struct StreamGuard {
     nbls_handle* h;
     explicit StreamGuard(nbls_handle* hh) : h(hh) {
         // the staging arena of alloc_copy: everything queued from it has been read when the previous guard left
-        if (!h->stage) {
-            constexpr size_t kStage = (size_t)8 << 20;
-            if (hipHostMalloc((void**)&h->stage, kStage, hipHostMallocDefault) == hipSuccess) h->stage_cap = kStage;
-            else { h->stage = nullptr; h->stage_cap = 0; (void)hipGetLastError(); }
-        }
+        if (!h->stage && h->stage.grow((size_t)8 << 20) != hipSuccess) (void)hipGetLastError();
         if (h->up_pending) { (void)hipStreamSynchronize(h->up); h->up_pending = false; }     // the arena is free again
         h->stage_used = 0;
         h->stage_bypass = false;
-        if (h->stage && !h->d_parena && hipMalloc((void**)&h->d_parena, h->stage_cap) != hipSuccess) { h->d_parena = nullptr; (void)hipGetLastError(); }
+        if (h->stage && !h->d_parena && h->d_parena.grow(h->stage.cap) != hipSuccess) (void)hipGetLastError();
         if (!h->ev_up && hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming) != hipSuccess) { h->ev_up = nullptr; (void)hipGetLastError(); }
         if (h->work_queued && h->up != h->stream && h->ev_plan) {
             for (hipStream_t s : {h->stream, h->stream2}) {
@@ -308,8 +296,8 @@ int check_lts(nbls_handle* h, const nbls_lts_params* l, int P, const std::string
 int upload_lts_tables(nbls_handle* h, nbls_estimator& x) {
     int rc;
     const int P = x.npairs;
-    if ((rc = alloc_copy(h, &x.d_starts, x.h_starts.data(), x.h_starts.size()))) return rc;
-    if ((rc = alloc_copy(h, &x.d_rew, x.h_rew.data(), x.h_rew.size()))) return rc;
+    if ((rc = alloc_copy(h, x.d_starts, x.h_starts.data(), x.h_starts.size()))) return rc;
+    if ((rc = alloc_copy(h, x.d_rew, x.h_rew.data(), x.h_rew.size()))) return rc;
     const int PP = P + 16;                           // padding: the large-array LTS kernel fetches one block of pairs ahead
     std::vector<double> xs((size_t)PP * 2, 0.0), xc((size_t)PP, 0.0);
     for (int k = 0; k < P; ++k) {
@@ -317,12 +305,12 @@ int upload_lts_tables(nbls_handle* h, nbls_estimator& x) {
         xs[2 * k + 1] = x.h_xij[2 * k + 1] / x.ltsp.xij_mad[1];
         xc[k] = xs[2 * k] * xs[2 * k + 1];
     }
-    if ((rc = alloc_copy(h, &x.d_xs, xs.data(), xs.size()))) return rc;
-    if ((rc = alloc_copy(h, &x.d_xc, xc.data(), xc.size()))) return rc;
+    if ((rc = alloc_copy(h, x.d_xs, xs.data(), xs.size()))) return rc;
+    if ((rc = alloc_copy(h, x.d_xc, xc.data(), xc.size()))) return rc;
     const int NS4 = (P + 3) / 4;                     // every 4th pair: the sample pass of the large-array LTS kernel
     std::vector<double> xss((size_t)(NS4 + 16) * 2, 0.0);
     for (int i = 0; i < NS4; ++i) { xss[2 * i] = xs[2 * (4 * i)]; xss[2 * i + 1] = xs[2 * (4 * i) + 1]; }
-    return alloc_copy(h, &x.d_xss, xss.data(), xss.size());
+    return alloc_copy(h, x.d_xss, xss.data(), xss.size());
 }
 
 // Size a record's result buffers for `cells` result cells: every buffer has its own capacity (a smaller plan after a
@@ -334,23 +322,20 @@ int size_result_buffers(nbls_handle* h, nbls_estimator& x, size_t cells, size_t 
     const bool own = x.kept_pair.empty();
     x.mask_bytes = (int)((P + 7) / 8);
     x.res_bytes = cells * (4 * sizeof(double) + (size_t)x.mask_bytes);
-    if ((rc = ensure(h, &x.d_res, &x.cap_res, x.res_bytes > min_res ? x.res_bytes : min_res))) return rc;
-    if ((rc = ensure(h, own ? &h->d_lag : &x.d_lag, own ? &h->cap_lag : &x.cap_lag, cells * P * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(h, own ? &h->d_cmax : &x.d_cmax, own ? &h->cap_cmax : &x.cap_cmax, cells * P * sizeof(double)))) return rc;
-    if ((rc = ensure(h, &x.d_z, &x.cap_z, 2 * cells * sizeof(double)))) return rc;
-    if ((rc = ensure(h, &x.d_wts, &x.cap_wts, cells * P))) return rc;
-    if (x.want_unc && (rc = ensure(h, &x.d_unc, &x.cap_unc, 2 * cells * sizeof(double)))) return rc;
+    if ((rc = ensure(h, x.d_res, x.res_bytes > min_res ? x.res_bytes : min_res))) return rc;
+    if ((rc = ensure(h, own ? h->d_lag : x.d_lag, cells * P * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(h, own ? h->d_cmax : x.d_cmax, cells * P * sizeof(double)))) return rc;
+    if ((rc = ensure(h, x.d_z, 2 * cells * sizeof(double)))) return rc;
+    if ((rc = ensure(h, x.d_wts, cells * P))) return rc;
+    if (x.want_unc && (rc = ensure(h, x.d_unc, 2 * cells * sizeof(double)))) return rc;
     return 0;
 }
 
 // A streamed pass: the pinned mirror of a record's result block, large enough for the plan's block.
 int ensure_mirror(nbls_handle* h, nbls_estimator& x) {
-    if (x.cap_hres >= x.res_bytes) return 0;
-    HIPCHK(h, hipStreamSynchronize(h->cstream));
-    if (x.h_res) { (void)hipHostFree(x.h_res); x.h_res = nullptr; x.cap_hres = 0; }
-    HIPCHK(h, hipHostMalloc((void**)&x.h_res, x.res_bytes ? x.res_bytes : 8, hipHostMallocDefault));
-    x.cap_hres = x.res_bytes ? x.res_bytes : 8;
-    return 0;
+    if (x.h_res.cap >= x.res_bytes) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->cstream));             // (copies of the last pass may still write the old one)
+    return grown(h, x.h_res.grow(x.res_bytes), "hipHostMalloc((void**)&x.h_res, x.res_bytes ? x.res_bytes : 8, hipHostMallocDefault)");
 }
 
 // The first window band b of the plan computed (0 unless window-sharded); it computed nwin[b] from there on.
@@ -366,14 +351,6 @@ void zero_uncomputed(const nbls_handle* h, void* out, size_t row_bytes) {
         if (first > 0) memset(band, 0, (size_t)first * row_bytes);
         if (first + n < h->vector_len) memset(band + (size_t)(first + n) * row_bytes, 0, (size_t)(h->vector_len - first - n) * row_bytes);
     }
-}
-
-// Free what a record owns (tables inside the plan arena go with the arena).
-void free_estimator(nbls_estimator& x, const std::unordered_set<const void*>& in_arena) {
-    void* bufs[] = {x.d_xij, x.d_xpinv, x.d_xs, x.d_xc, x.d_xss, x.d_rew, x.d_starts, x.d_kept_pair,
-                    x.d_lag, x.d_cmax, x.d_z, x.d_unc, x.d_wts, x.d_res /* vel, baz, mdccm, sigma_tau, mask */};
-    for (void* b : bufs) if (b && !in_arena.count(b)) (void)hipFree(b);
-    if (x.h_res) (void)hipHostFree(x.h_res);
 }
 
 }  // namespace
@@ -429,35 +406,23 @@ int nbls_create(int device_id, nbls_handle** out) {
 void nbls_destroy(nbls_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->up) (void)hipStreamSynchronize(h->up);
+    // nothing is freed or destroyed under queued work (the solve stream is joined into `stream` at the end of a pass)
+    for (hipStream_t s : {h->stream, h->stream2, h->up, h->cstream, h->ustream})
+        if (s) (void)hipStreamSynchronize(s);
     (void)nbls_comm_destroy(h);
-    void* bufs[] = {h->d_trace, h->d_pair, h->d_sos, h->d_M, h->d_tl, h->d_tr,
-                    h->d_W, h->d_inc, h->d_nwin, h->d_unit_off, h->d_unit_band, h->d_unit_win, h->d_filt, h->d_cstate, h->d_cstate2, h->d_tstate,
-                    h->d_lag, h->d_cmax, h->d_qbuf, h->d_qmeta, h->d_cand, h->d_fw, h->d_gend, h->d_gin, h->d_win_off, h->d_stamps, h->d_seg_state};
-    {
-        std::unordered_set<const void*> in_arena;       // members that point into d_parena
-        for (const void* m : h->arena_owned) in_arena.insert(*(void* const*)m);
-        for (void* b : bufs) if (b && !in_arena.count(b)) (void)hipFree(b);
-        for (nbls_estimator& x : h->est) free_estimator(x, in_arena);
-        if (h->d_parena) (void)hipFree(h->d_parena);
-    }
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (hipEvent_t e : h->bev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->pev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->rev) (void)hipEventDestroy(e);
-    if (h->cstream) { (void)hipStreamSynchronize(h->cstream); (void)hipStreamDestroy(h->cstream); }
-    if (h->ustream) { (void)hipStreamSynchronize(h->ustream); (void)hipStreamDestroy(h->ustream); }
     for (hipEvent_t e : h->uev) (void)hipEventDestroy(e);
-    if (h->ev_uprev) (void)hipEventDestroy(h->ev_uprev);
-    if (h->ev_xd) (void)hipEventDestroy(h->ev_xd);
-    if (h->ev_plan) (void)hipEventDestroy(h->ev_plan);
-    if (h->ev_up) (void)hipEventDestroy(h->ev_up);
+    for (hipEvent_t e : {h->ev_uprev, h->ev_xd, h->ev_plan, h->ev_up})
+        if (e) (void)hipEventDestroy(e);
+    if (h->cstream) (void)hipStreamDestroy(h->cstream);
+    if (h->ustream) (void)hipStreamDestroy(h->ustream);
     if (h->up && h->up != h->stream) (void)hipStreamDestroy(h->up);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->stage) (void)hipHostFree(h->stage);
-    delete h;
+    delete h;                                // the buffers free themselves (dev_buf.h), on the handle's device
 }
 
 // Array elements of a trace of `nchans` rows under the handle's segment count (nbls_set_segments; rows that do not
@@ -466,8 +431,7 @@ static void set_elements(nbls_handle* h, int32_t nchans) {
     const int E = h->nseg > 1 && nchans % h->nseg == 0 ? nchans / h->nseg : nchans;
     nbls_estimator& x = h->est[0];
     if (h->nelem != E && x.d_xij) {
-        (void)hipFree(x.d_xij); x.d_xij = nullptr;
-        h->caps.erase((const void*)&x.d_xij);
+        x.d_xij.release();
         h->npairs = x.npairs = 0;
     }
     h->nelem = E;
@@ -478,11 +442,7 @@ static int trace_shape_impl(nbls_handle* h, int32_t nchans, int64_t npts, double
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t pad = (npts + 63) / 64 * 64;
     const size_t need = (size_t)nchans * pad * sizeof(double);
-    if (!h->d_trace || h->cap_trace < need) {
-        if (h->d_trace) { (void)hipFree(h->d_trace); h->d_trace = nullptr; h->cap_trace = 0; }
-        HIPCHK(h, hipMalloc((void**)&h->d_trace, need));
-        h->cap_trace = need;
-    }
+    if (int rc = grown(h, h->d_trace.grow(need), "hipMalloc((void**)&h->d_trace, need)")) return rc;
     set_elements(h, nchans);
     h->nchans = nchans;
     h->npts = npts;
@@ -610,11 +570,7 @@ int nbls_set_trace_from(nbls_handle* h, const nbls_handle* src) {
     if (h->device != src->device) return fail(h, NBLS_ERR_ARG, "nbls_set_trace_from: handles are on different devices");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t need = (size_t)src->nchans * src->npts_pad * sizeof(double);
-    if (!h->d_trace || h->cap_trace < need) {
-        if (h->d_trace) { (void)hipFree(h->d_trace); h->d_trace = nullptr; h->cap_trace = 0; }
-        HIPCHK(h, hipMalloc((void**)&h->d_trace, need));
-        h->cap_trace = need;
-    }
+    if (int rc = grown(h, h->d_trace.grow(need), "hipMalloc((void**)&h->d_trace, need)")) return rc;
     // the source's upload has completed (nbls_set_trace* return after it) or is still running on another thread
     // (nbls_upload_rows): wait for its last row; the copy is ordered on THIS handle's stream
     {
@@ -665,9 +621,9 @@ int nbls_set_geometry(nbls_handle* h, const double* xij, const int32_t* pair_idx
     StreamGuard guard(h);
     int rc;
     x.h_xij.clear();                         // (a failed upload leaves no stale "already there" record)
-    if ((rc = alloc_copy(h, &x.d_xij, xij, n2))) return rc;
-    if ((rc = alloc_copy(h, &h->d_pair, pair_idx, n2))) return rc;
-    if ((rc = alloc_copy(h, &x.d_xpinv, xpinv, n2))) return rc;
+    if ((rc = alloc_copy(h, x.d_xij, xij, n2))) return rc;
+    if ((rc = alloc_copy(h, h->d_pair, pair_idx, n2))) return rc;
+    if ((rc = alloc_copy(h, x.d_xpinv, xpinv, n2))) return rc;
     x.h_xij.assign(xij, xij + n2);
     h->h_pair.assign(pair_idx, pair_idx + n2);
     x.h_xpinv.assign(xpinv, xpinv + n2);
@@ -915,11 +871,11 @@ static int plan_upload_tables(nbls_handle* h, const plan_args& a) {
     const int R = a.R;
     const int64_t U = h->nunits;
     int rc;
-    if ((rc = alloc_copy(h, &h->d_fw, h->hp_FW.data(), h->hp_FW.size()))) return rc;
-    if ((rc = alloc_copy(h, &h->d_sos, a.sos, (size_t)a.nbands * a.nsections * 6))) return rc;
+    if ((rc = alloc_copy(h, h->d_fw, h->hp_FW.data(), h->hp_FW.size()))) return rc;
+    if ((rc = alloc_copy(h, h->d_sos, a.sos, (size_t)a.nbands * a.nsections * 6))) return rc;
     if (a.nsections == 0 && a.nbands != 1)
         return fail(h, NBLS_ERR_ARG, "nbls_plan: an unfiltered plan has exactly one band");
-    if ((rc = alloc_copy(h, &h->d_M, h->hp_M.data(), h->hp_M.size()))) return rc;
+    if ((rc = alloc_copy(h, h->d_M, h->hp_M.data(), h->hp_M.size()))) return rc;
     {   // the ramps (1 % of the trace each: 0.14 MB at cfg-3, a quarter of a plan's upload) only when they differ from what is there
         const size_t tn = (size_t)a.taper_len;
         const bool same = h->d_tl && h->d_tr && h->h_tl.size() == tn && h->h_tr.size() == tn &&
@@ -929,28 +885,28 @@ static int plan_upload_tables(nbls_handle* h, const plan_args& a) {
             h->h_tl.clear();
             h->h_tr.clear();
             h->arena_mode = false;                       // allocations of their own: they outlive the plan
-            rc = alloc_copy(h, &h->d_tl, a.taper_left, tn);
-            if (!rc) rc = alloc_copy(h, &h->d_tr, a.taper_right, tn);
+            rc = alloc_copy(h, h->d_tl, a.taper_left, tn);
+            if (!rc) rc = alloc_copy(h, h->d_tr, a.taper_right, tn);
             h->arena_mode = true;
             if (rc) return rc;
             if (tn) { h->h_tl.assign(a.taper_left, a.taper_left + tn); h->h_tr.assign(a.taper_right, a.taper_right + tn); }
         }
     }
-    if ((rc = alloc_copy(h, &h->d_W, h->W.data(), (size_t)R))) return rc;
-    if ((rc = alloc_copy(h, &h->d_inc, h->inc.data(), (size_t)R))) return rc;
-    if ((rc = alloc_copy(h, &h->d_nwin, h->nwin.data(), (size_t)R))) return rc;
-    if ((rc = alloc_copy(h, &h->d_unit_off, h->unit_off.data(), (size_t)R + 1))) return rc;
-    if ((rc = alloc_copy(h, &h->d_win_off, h->woff.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, h->d_W, h->W.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, h->d_inc, h->inc.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, h->d_nwin, h->nwin.data(), (size_t)R))) return rc;
+    if ((rc = alloc_copy(h, h->d_unit_off, h->unit_off.data(), (size_t)R + 1))) return rc;
+    if ((rc = alloc_copy(h, h->d_win_off, h->woff.data(), (size_t)R))) return rc;
     std::vector<int32_t>& ub = h->hp_ub;
     ub.resize((size_t)U);
     for (int b = 0; b < R; ++b)
         for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) ub[(size_t)u] = b;
-    if ((rc = alloc_copy(h, &h->d_unit_band, ub.data(), (size_t)U))) return rc;
+    if ((rc = alloc_copy(h, h->d_unit_band, ub.data(), (size_t)U))) return rc;
     std::vector<int32_t>& uw = h->hp_uw;
     uw.resize((size_t)(U > 0 ? U : 1));
     for (int b = 0; b < R; ++b)
         for (int64_t u = h->unit_off[b]; u < h->unit_off[b + 1]; ++u) uw[(size_t)u] = (int32_t)(u - h->unit_off[b]) + h->woff[b];
-    return alloc_copy(h, &h->d_unit_win, uw.data(), (size_t)U);
+    return alloc_copy(h, h->d_unit_win, uw.data(), (size_t)U);
 }
 
 // Step 5: the work buffers of the filter, and the pass's lag / cmax rows with the result buffers of est[0].
@@ -959,26 +915,21 @@ static int plan_work_buffers(nbls_handle* h, const plan_args& a) {
     int rc;
     const size_t nseries = (size_t)a.nbands * h->nchans;      // (= R * E)
     // + 64 bytes: the verifier's 16-byte copies of a window that starts on an odd sample read one sample past its end
-    if ((rc = ensure(h, &h->d_filt, &h->cap_filt, nseries * h->npts_pad * sizeof(double) + 64))) return rc;
-    if ((rc = ensure(h, &h->d_cstate, &h->cap_cstate, nseries * h->nchunks * D * sizeof(double)))) return rc;
-    if ((rc = ensure(h, &h->d_cstate2, &h->cap_cstate2, nseries * h->nchunks * D * sizeof(double)))) return rc;
-    if (h->d_tstate && !(h->zero_phase && nsections > 0 && nsections <= 4)) {
-        (void)hipFree(h->d_tstate); h->d_tstate = nullptr; h->cap_tstate = 0;     // this plan filters in the stored form
-    }
-    if (h->zero_phase && nsections > 0 && nsections <= 4) {
+    if ((rc = ensure(h, h->d_filt, nseries * h->npts_pad * sizeof(double) + 64))) return rc;
+    if ((rc = ensure(h, h->d_cstate, nseries * h->nchunks * D * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->d_cstate2, nseries * h->nchunks * D * sizeof(double)))) return rc;
+    if (!(h->zero_phase && nsections > 0 && nsections <= 4)) {
+        h->d_tstate.release();               // this plan filters in the stored form
+    } else {
         // tile-boundary states of the recompute form (2S doubles per 16 samples: a quarter of the filtered buffer at
         // two sections; beyond four sections they would be as large as the samples they replace, and the stored form
         // is used).  Without room for them the filter writes and re-reads the forward output instead: same results.
         const size_t need = nseries * h->nchunks * (NBLS_FILTER_CHUNK / NBLS_FILTER_TILE) * D * sizeof(double);
-        if (need > h->cap_tstate) {
-            if (h->d_tstate) { (void)hipFree(h->d_tstate); h->d_tstate = nullptr; h->cap_tstate = 0; }
-            if (hipMalloc((void**)&h->d_tstate, need) == hipSuccess) h->cap_tstate = need;
-            else { h->d_tstate = nullptr; (void)hipGetLastError(); }
-        }
+        if (h->d_tstate.grow(need) != hipSuccess) (void)hipGetLastError();
     }
     const size_t ngroups = (size_t)((h->nchunks + NBLS_FILTER_GROUP - 1) / NBLS_FILTER_GROUP);
-    if ((rc = ensure(h, &h->d_gend, &h->cap_gend, nseries * ngroups * D * sizeof(double)))) return rc;
-    if ((rc = ensure(h, &h->d_gin, &h->cap_gin, nseries * ngroups * D * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->d_gend, nseries * ngroups * D * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->d_gin, nseries * ngroups * D * sizeof(double)))) return rc;
     return size_result_buffers(h, h->est[0], (size_t)a.R * a.vector_len, h->reserve_res);
 }
 
@@ -1031,12 +982,12 @@ static int plan_screen_batch(nbls_handle* h, const plan_args& a) {
         if (eq < batch) batch = eq;
     }
     h->screen_batch = batch;
-    if ((rc = ensure(h, &h->d_qbuf, &h->cap_qbuf, (size_t)batch * E * 2 * WP_))) return rc;
-    if ((rc = ensure(h, &h->d_qmeta, &h->cap_qmeta, (size_t)batch * E * (10 + WP_ / 32) * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->d_qbuf, (size_t)batch * E * 2 * WP_))) return rc;
+    if ((rc = ensure(h, h->d_qmeta, (size_t)batch * E * (10 + WP_ / 32) * sizeof(double)))) return rc;
     if (h->opt.screen_stamps || h->opt.lts_stamps) {
-        if ((rc = ensure(h, &h->d_stamps, &h->cap_stamps, (size_t)(batch + 8) * E * ((E + 1) / 2) * 8 * sizeof(unsigned long long)))) return rc;   // one record per screening workgroup: (unit, sliding channel, partner group)
+        if ((rc = ensure(h, h->d_stamps, (size_t)(batch + 8) * E * ((E + 1) / 2) * 8 * sizeof(unsigned long long)))) return rc;   // one record per screening workgroup: (unit, sliding channel, partner group)
     }
-    return ensure(h, &h->d_cand, &h->cap_cand, (size_t)batch * E * E * 32 * sizeof(int32_t));
+    return ensure(h, h->d_cand, (size_t)batch * E * E * 32 * sizeof(int32_t));
 }
 
 // Step 8: per estimator, its array's tables (est[0]'s geometry is nbls_set_geometry's and stays where that put it) and,
@@ -1046,9 +997,9 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
     for (int e = 0; e <= h->nest; ++e) {
         nbls_estimator& x = h->est[e];
         if (e > 0) {
-            if ((rc = alloc_copy(h, &x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
-            if ((rc = alloc_copy(h, &x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
-            if (!x.kept_pair.empty() && (rc = alloc_copy(h, &x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
+            if ((rc = alloc_copy(h, x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
+            if ((rc = alloc_copy(h, x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
+            if (!x.kept_pair.empty() && (rc = alloc_copy(h, x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
         }
         if (x.lts && (rc = upload_lts_tables(h, x))) return rc;
         if (e > 0 && (rc = size_result_buffers(h, x, (size_t)a.R * a.vector_len, 0))) return rc;
@@ -1418,7 +1369,7 @@ int nbls_filter_segment(nbls_handle* h, int32_t reverse, const double* state_in,
     h->work_queued = true;
     const size_t n = (size_t)h->fbands * h->nchans * 2 * h->nsections;
     int rc;
-    if ((rc = ensure(h, &h->d_seg_state, &h->cap_seg_state, 2 * n * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->d_seg_state, 2 * n * sizeof(double)))) return rc;
     double* d_init = nullptr;
     double* d_fin = state_out ? h->d_seg_state + n : nullptr;
     if (state_in) {
@@ -1475,8 +1426,8 @@ int nbls_load_result_block(nbls_handle* h, const void* block, int64_t nbytes) {
     const size_t need = std::max((size_t)nbytes + 8, h->reserve_res);
     int rc;
     nbls_estimator& x = h->est[0];
-    if ((rc = ensure(h, &x.d_res, &x.cap_res, need))) return rc;
-    HIPCHK(h, hipMemsetAsync(x.d_res, 0, x.cap_res, h->stream));
+    if ((rc = ensure(h, x.d_res, need))) return rc;
+    HIPCHK(h, hipMemsetAsync(x.d_res, 0, x.d_res.cap, h->stream));
     HIPCHK(h, hipMemcpyAsync(x.d_res, block, (size_t)nbytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));              // the host buffer may go away
     x.res_bytes = (size_t)nbytes;

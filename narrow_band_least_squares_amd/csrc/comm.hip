@@ -134,7 +134,7 @@ int nbls_comm_destroy(nbls_handle* h) {
         if (api) (void)api->CommDestroy((ncclComm_t)h->comm);
         h->comm = nullptr;
     }
-    if (h->d_gather) { (void)hipFree(h->d_gather); h->d_gather = nullptr; h->cap_gather = 0; }
+    h->d_gather.release();
     h->comm_world = 1;
     h->comm_rank = 0;
     return NBLS_OK;
@@ -236,7 +236,7 @@ int nbls_comm_gather(nbls_handle* const* hs, int32_t n, int32_t root, int64_t bl
             note(h, NBLS_ERR_ARG, "nbls_comm_gather: block_bytes smaller than the result block + status word");
             use_own = false;
         }
-        if (ok && use_own && h->res_loaded && x.d_res && x.cap_res < (size_t)block_bytes) {
+        if (ok && use_own && h->res_loaded && x.d_res && x.d_res.cap < (size_t)block_bytes) {
             // a block assembled on the host (nbls_load_result_block) without nbls_reserve_results(block_bytes): it is
             // this rank's RESULT, not a failed rank's leftovers — move it into an allocation of the gather's size
             unsigned char* nb_ = nullptr;
@@ -244,25 +244,18 @@ int nbls_comm_gather(nbls_handle* const* hs, int32_t n, int32_t root, int64_t bl
                 (void)hipnote(h, hipMemsetAsync(nb_, 0, (size_t)block_bytes, h->stream), "hipMemsetAsync");
                 (void)hipnote(h, hipMemcpyAsync(nb_, x.d_res, x.res_bytes, hipMemcpyDeviceToDevice, h->stream), "hipMemcpyAsync(loaded block)");
                 (void)hipnote(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize");
-                (void)hipFree(x.d_res);
-                x.d_res = nb_;
-                x.cap_res = (size_t)block_bytes;
+                x.d_res.adopt(nb_, (size_t)block_bytes);
             } else use_own = false;
         }
-        if (ok && use_own && (!x.d_res || x.cap_res < (size_t)block_bytes)) {
+        if (ok && use_own && (!x.d_res || x.d_res.cap < (size_t)block_bytes)) {
             if (h->planned) {
                 note(h, NBLS_ERR_STATE, "nbls_comm_gather: call nbls_reserve_results(block_bytes) before nbls_plan");
                 use_own = false;
             } else {
                 // a rank that failed before it could plan: an empty block of its own
-                if (x.d_res) { (void)hipFree(x.d_res); x.d_res = nullptr; x.cap_res = 0; }
-                if (hipnote(h, hipMalloc((void**)&x.d_res, (size_t)block_bytes), "hipMalloc(result block)")) {
-                    x.cap_res = (size_t)block_bytes;
+                if (hipnote(h, x.d_res.grow((size_t)block_bytes), "hipMalloc(result block)"))
                     (void)hipnote(h, hipMemsetAsync(x.d_res, 0, (size_t)block_bytes, h->stream), "hipMemsetAsync");
-                } else {
-                    x.d_res = nullptr;
-                    use_own = false;
-                }
+                else use_own = false;
             }
         }
         if (use_own) {
@@ -277,14 +270,9 @@ int nbls_comm_gather(nbls_handle* const* hs, int32_t n, int32_t root, int64_t bl
             return cfail(h, NBLS_ERR_NOMEM, "nbls_comm_gather: no memory for a " + std::to_string(block_bytes) + "-byte block");
         }
         const bool recv_side = root < 0 || h->comm_rank == root;
-        if (recv_side && (!h->d_gather || h->cap_gather < total)) {
-            if (h->d_gather) { (void)hipFree(h->d_gather); h->d_gather = nullptr; h->cap_gather = 0; }
-            if (hipnote(h, hipMalloc((void**)&h->d_gather, total), "hipMalloc(gather buffer)")) h->cap_gather = total;
-            else {
-                h->d_gather = nullptr;
-                for (int j = 0; j <= i; ++j) if (standin[j]) (void)hipFree(standin[j]);
-                return first_rc;                   // no receive buffer: cannot take part
-            }
+        if (recv_side && !hipnote(h, h->d_gather.grow(total), "hipMalloc(gather buffer)")) {
+            for (int j = 0; j <= i; ++j) if (standin[j]) (void)hipFree(standin[j]);
+            return first_rc;                       // no receive buffer: cannot take part
         }
     }
     // the status word: the caller's, or this process's first failure (every local block carries it)

@@ -5,10 +5,9 @@
 #include <atomic>
 #include <mutex>
 #include <string>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 #include "../../include/nbls.h"
+#include "dev_buf.h"
 
 #define NBLS_MAX_SECTIONS 8
 #define NBLS_FILTER_CHUNK 512      // samples per scan chunk (one lane each)
@@ -64,6 +63,8 @@ struct nbls_wgroup { int b0, b1, W; int64_t u0, u1; bool screen; };
 // them, the device tables nbls_plan makes of them, and the buffers of its own results.  The handle holds 1 + 8 of these
 // records: est[0] is the plan's own estimator (nbls_set_geometry, nbls_plan(lts = ...), nbls_set_uncertainty), est[1..nest]
 // are the further ones (nbls_set_estimators).  What a record does not store is derived by nbls_view_of below.
+// Every device and pinned buffer, here and in the handle, is a dev_buf / pinned_buf (dev_buf.h): it knows its own capacity
+// and whether it is a place in the plan arena, and it is freed when the handle is deleted.
 struct nbls_estimator {
     std::vector<int32_t> kept;         // element indices, ascending (est[0]: empty, it is the whole array)
     std::vector<int32_t> kept_pair;    // [P']: index of pair k of the sub-array in the full array's pair list (empty: all elements kept)
@@ -76,27 +77,27 @@ struct nbls_estimator {
     bool want_unc = false;             // confidence intervals of the slowness estimate: computed behind the solve when wanted
     double unc_par[6] = {0, 0, 0, 0, 0, 0};   // eigenvalues of X^T X, rotation into the eigen-frame (row major)
     // device side
-    double* d_xij = nullptr;           // [P'][2]
-    double* d_xpinv = nullptr;         // [2][P']
-    int32_t* d_starts = nullptr;       // [S][4]
-    double* d_rew = nullptr;           // [P'+1]
-    double* d_xs = nullptr;            // [P'][2] standardised co-array
-    double* d_xc = nullptr;            // [P'] c0*c1 of the standardised co-array; d_xs and d_xc are padded by 16 pairs (solve_bucket.inc reads one block ahead)
-    double* d_xss = nullptr;           // [ceil(P'/4)][2] every 4th row of d_xs (padded likewise)
+    dev_buf<double> d_xij;             // [P'][2]
+    dev_buf<double> d_xpinv;           // [2][P']
+    dev_buf<int32_t> d_starts;         // [S][4]
+    dev_buf<double> d_rew;             // [P'+1]
+    dev_buf<double> d_xs;              // [P'][2] standardised co-array
+    dev_buf<double> d_xc;              // [P'] c0*c1 of the standardised co-array; d_xs and d_xc are padded by 16 pairs (solve_bucket.inc reads one block ahead)
+    dev_buf<double> d_xss;             // [ceil(P'/4)][2] every 4th row of d_xs (padded likewise)
     // a sub-array's solve reads compact copies of its pairs' rows (gather_pairs_kernel): its own [B][VL][P'] buffers,
     // filled per unit batch from the handle's through d_kept_pair [P']; a full array reads the handle's d_lag / d_cmax
-    int32_t* d_kept_pair = nullptr;
-    int32_t* d_lag = nullptr;
-    double* d_cmax = nullptr;
-    double* d_z = nullptr;             // [B][VL][2]
-    uint8_t* d_wts = nullptr;          // [B][VL][P'] one byte per pair (kernel-side form; packed into the mask after the solve)
-    double* d_unc = nullptr;           // [2][B][VL]: vel_uncert | baz_uncert
+    dev_buf<int32_t> d_kept_pair;
+    dev_buf<int32_t> d_lag;
+    dev_buf<double> d_cmax;
+    dev_buf<double> d_z;               // [B][VL][2]
+    dev_buf<uint8_t> d_wts;            // [B][VL][P'] one byte per pair (kernel-side form; packed into the mask after the solve)
+    dev_buf<double> d_unc;             // [2][B][VL]: vel_uncert | baz_uncert
     // result block, ONE allocation = one D2H copy / one RCCL gather:
     //   [vel | baz | mdccm | sigma_tau] double[4][B][VL], then the LTS weight bit mask uint8[B][VL][MB],
     //   MB = ceil(P'/8), bit k & 7 of byte k >> 3 = weight of pair k (ceil(P/8) bytes per unit)
-    unsigned char* d_res = nullptr;
-    unsigned char* h_res = nullptr;    // its pinned mirror, filled batch by batch (nbls_stream_results)
-    size_t cap_lag = 0, cap_cmax = 0, cap_z = 0, cap_unc = 0, cap_wts = 0, cap_res = 0, cap_hres = 0, res_bytes = 0;
+    dev_buf<unsigned char> d_res;
+    pinned_buf h_res;                  // its pinned mirror, filled batch by batch (nbls_stream_results)
+    size_t res_bytes = 0;              // the plan's block (d_res.cap may be more: a bigger plan before, nbls_reserve_results)
     int mask_bytes = 0;                // MB
 };
 
@@ -140,8 +141,7 @@ struct nbls_handle {
     std::atomic<int> upload_state{0};  // 0 no upload under way, 1 running, 2 shape declared (no samples yet), -1 the upload failed
 
     // ---- trace (HBM resident) ----
-    double* d_trace = nullptr;     // [nchans][npts_pad]
-    size_t cap_trace = 0;
+    dev_buf<double> d_trace;       // [nchans][npts_pad]
     int nchans = 0;                // trace rows
     int nseg = 1;                  // recordings in the trace (nbls_set_segments): nseg blocks of nelem consecutive rows
     int nelem = 0;                 // array elements = nchans / nseg: what the correlators, the screening buffers and the geometry see
@@ -150,7 +150,7 @@ struct nbls_handle {
 
     // ---- geometry: the pass's array, what the correlators see (its co-array is est[0]'s) ----
     int npairs = 0;
-    int32_t* d_pair = nullptr;     // [P][2]
+    dev_buf<int32_t> d_pair;       // [P][2]
     std::vector<int32_t> h_pair;   // host copy (as est[0].h_xij / h_xpinv): an identical nbls_set_geometry uploads nothing
     std::vector<double> h_tl, h_tr;   // host copies of the taper ramps (the same for every band group and call of one trace length: uploaded once)
 
@@ -166,49 +166,42 @@ struct nbls_handle {
     int maxW = 0;
     int uniW = 0;                  // the window length if every band has the same one, else 0
     int64_t nchunks = 0;
-    double* d_sos = nullptr;       // [B][S][6]
-    double* d_M = nullptr;         // [B][G+1][D][D] powers M^0..M^G of the chunk transition (D = 2S)
-    double* d_fw = nullptr;        // [B][C][D] zero-state end-state weights
-    double* d_gend = nullptr;      // [ngroups][B*N][D]
-    double* d_gin = nullptr;       // [ngroups][B*N][D]
-    size_t cap_gend = 0, cap_gin = 0;
-    double* d_seg_state = nullptr; // [2][B*N][D] initial / final state of a time segment (nbls_filter_segment)
-    size_t cap_seg_state = 0;
-    double* d_tl = nullptr;        // [taper_len]
-    double* d_tr = nullptr;        // [taper_len]
-    int32_t* d_W = nullptr;        // [B]
-    int32_t* d_inc = nullptr;      // [B]
-    int32_t* d_nwin = nullptr;     // [B]
-    int32_t* d_unit_off = nullptr; // [B+1]
-    int32_t* d_win_off = nullptr;  // [B] first window processed per band
+    dev_buf<double> d_sos;         // [B][S][6]
+    dev_buf<double> d_M;           // [B][G+1][D][D] powers M^0..M^G of the chunk transition (D = 2S)
+    dev_buf<double> d_fw;          // [B][C][D] zero-state end-state weights
+    dev_buf<double> d_gend;        // [ngroups][B*N][D]
+    dev_buf<double> d_gin;         // [ngroups][B*N][D]
+    dev_buf<double> d_seg_state;   // [2][B*N][D] initial / final state of a time segment (nbls_filter_segment)
+    dev_buf<double> d_tl;          // [taper_len]
+    dev_buf<double> d_tr;          // [taper_len]
+    dev_buf<int32_t> d_W;          // [B]
+    dev_buf<int32_t> d_inc;        // [B]
+    dev_buf<int32_t> d_nwin;       // [B]
+    dev_buf<int32_t> d_unit_off;   // [B+1]
+    dev_buf<int32_t> d_win_off;    // [B] first window processed per band
     std::vector<int32_t> win_first, win_count;   // optional per-band window ranges (nbls_set_window_ranges)
-    int32_t* d_unit_band = nullptr;// [U]
-    int32_t* d_unit_win = nullptr; // [U] window index (global, inside the band) of every unit: saves the kernels a dependent load
+    dev_buf<int32_t> d_unit_band;// [U]
+    dev_buf<int32_t> d_unit_win;   // [U] window index (global, inside the band) of every unit: saves the kernels a dependent load
 
     // ---- work + results ----
-    double* d_filt = nullptr;      // [B][N][npts_pad]
-    double* d_cstate = nullptr;    // [B*N][nchunks][D]
-    double* d_cstate2 = nullptr;   // same, for the backward pass (its chunk states are produced by the forward apply)
-    size_t cap_cstate2 = 0;
-    double* d_tstate = nullptr;    // [B*N][C/T][nchunks][D] forward states at the tile boundaries (zero-phase, recompute form)
-    size_t cap_tstate = 0;
-    int32_t* d_lag = nullptr;      // [B][VL][P]
-    double* d_cmax = nullptr;      // [B][VL][P]
-    size_t cap_filt = 0, cap_cstate = 0, cap_lag = 0, cap_cmax = 0;
+    dev_buf<double> d_filt;        // [B][N][npts_pad]
+    dev_buf<double> d_cstate;      // [B*N][nchunks][D]
+    dev_buf<double> d_cstate2;     // same, for the backward pass (its chunk states are produced by the forward apply)
+    dev_buf<double> d_tstate;      // [B*N][C/T][nchunks][D] forward states at the tile boundaries (zero-phase, recompute form)
+    dev_buf<int32_t> d_lag;        // [B][VL][P]
+    dev_buf<double> d_cmax;        // [B][VL][P]
     bool res_loaded = false;       // est[0].d_res holds a block put there by nbls_load_result_block (cleared by the next nbls_plan)
     size_t reserve_res = 0;        // minimum allocation of est[0]'s result block (nbls_reserve_results: equal gather blocks)
     // ---- RCCL gather (comm.hip) ----
     void* comm = nullptr;          // ncclComm_t
     int comm_world = 1, comm_rank = 0;
-    unsigned char* d_gather = nullptr;   // [world][block_bytes] receive side
-    size_t cap_gather = 0;
+    dev_buf<unsigned char> d_gather; // [world][block_bytes] receive side
     int64_t gather_status = 0;     // host copy of the status word while its H2D copy is in flight
-    std::unordered_map<const void*, size_t> caps;   // capacities of the small plan tables, keyed by the address of the pointer member
     // pinned staging of the plan tables (api.hip: alloc_copy): a copy from pinned memory goes through the DMA engines,
     // a copy from pageable memory is a shader copy that has to find a free CU — with three other band groups of the
     // call filling the GPU each of a plan's ~25 small uploads took ~60 us instead of ~5
-    unsigned char* stage = nullptr;
-    size_t stage_cap = 0, stage_used = 0;
+    pinned_buf stage;
+    size_t stage_used = 0;
     // a plan whose tables all went through the arena does not wait for their copies: the upload stream records ev_up,
     // and whatever launches kernels that read the tables (nbls_execute*, nbls_filter_segment) makes its streams wait
     // for it on the GPU; the next plan / geometry call waits for the upload stream before it reuses the arena
@@ -222,15 +215,13 @@ struct nbls_handle {
     std::vector<int32_t> woff;     // first computed window of every band of the plan (0 unless window-sharded)
     bool work_queued = false;      // kernels that read the plan / geometry tables may still be queued (set by nbls_execute*, cleared by
                                    // the calls that wait for the handle's stream): a plan has to order its uploads behind them only then
-    unsigned char* d_parena = nullptr;
+    dev_buf<unsigned char> d_parena; // the tables placed in it say so themselves (dev_buf::in_arena) and are never freed one by one
     bool arena_mode = false;
-    std::unordered_set<const void*> arena_owned;    // pointer members that point into d_parena (never freed one by one)
 
     // ---- int8 screening correlator (xcorr_screen.hip) ----
-    int8_t* d_qbuf = nullptr;      // [batch][N][2][WP]
-    double* d_qmeta = nullptr;     // [batch][N][4]
-    int32_t* d_cand = nullptr;     // [batch][N][N][16]
-    size_t cap_qbuf = 0, cap_qmeta = 0, cap_cand = 0;
+    dev_buf<int8_t> d_qbuf;        // [batch][N][2][WP]
+    dev_buf<double> d_qmeta;       // [batch][N][4]
+    dev_buf<int32_t> d_cand;       // [batch][N][N][16]
     int64_t screen_batch = 0;
     int screen_wp = 0;             // padded window length the screening buffers are sized for (largest screened group)
     int64_t last_batch = 0;        // units of the last screening batch queued (developer statistics)
@@ -238,11 +229,9 @@ struct nbls_handle {
     int skew_n = -1, skew_s = -1;  // partner-image skew of the screening kernel, solved once per (array size, tile shape)
     int skew_o[32] = {0};
     int64_t lts_stamp_waves = 0;              // developer: waves of the last LTS launch that wrote stamps
-    unsigned long long* d_stamps = nullptr;   // developer: s_memtime stamps of the screen kernel's workgroups
-    size_t cap_stamps = 0;
+    dev_buf<unsigned long long> d_stamps; // developer: s_memtime stamps of the screen kernel's workgroups
 
-    // ---- the estimators of the pass: est[0] the plan's own, est[1..nest] the further ones (nest == 0: the plain pass).
-    // A fixed member: the capacities and the arena ownership of a record's tables are keyed by the address of its pointers
+    // ---- the estimators of the pass: est[0] the plan's own, est[1..nest] the further ones (nest == 0: the plain pass)
     int nest = 0;
     nbls_estimator est[1 + NBLS_MAX_ESTIMATORS];
 
@@ -269,7 +258,7 @@ hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipS
 struct nbls_est_view { double *vel, *baz, *mdccm, *sig; uint8_t* mask; int32_t* lag; double* cmax; };
 inline nbls_est_view nbls_view_of(const nbls_handle* h, const nbls_estimator& x) {
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    double* const g = (double*)x.d_res;
+    double* const g = (double*)x.d_res.p;
     const bool own = x.kept_pair.empty();
     return {g, g + cells, g + 2 * cells, g + 3 * cells, x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr,
             own ? h->d_lag : x.d_lag, own ? h->d_cmax : x.d_cmax};

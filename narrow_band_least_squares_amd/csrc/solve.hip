@@ -1483,7 +1483,7 @@ static hipError_t solve_range_impl(nbls_handle* h, const nbls_estimator& s, cons
     {
         if (h->opt.lts_stamps && h->d_stamps) {
             a.stamps = h->d_stamps;
-            const int64_t cap = (int64_t)(h->cap_stamps / (8 * sizeof(unsigned long long))) / 2;   // second half: the cooperative kernel's C-step breakdown
+            const int64_t cap = (int64_t)(h->d_stamps.cap / (8 * sizeof(unsigned long long))) / 2;   // second half: the cooperative kernel's C-step breakdown
             a.stamp_waves = (int)(nunits < cap ? nunits : cap);
             h->lts_stamp_waves = a.stamp_waves;
             a.stamp_mode = h->opt.lts_stamps;

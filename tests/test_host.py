@@ -303,6 +303,22 @@ def test_bucket_selection_state_machine(tmp_path):
     assert r.stdout.startswith('ok 240000 ')
 
 
+def test_buffer_ownership_under_sanitizers(tmp_path):
+    """csrc/dev_buf.h — the types that own every device and pinned buffer of a handle — against an allocator the test
+    program defines itself (no HIP library, no GPU), under AddressSanitizer and UBSan: when grow keeps, frees and
+    allocates, what a failed allocation leaves, that a place in the plan arena is never handed to hipFree by place,
+    leave_arena, grow, release or the destructor, adopt, the same for the pinned type, and nothing live at exit."""
+    exe = tmp_path / 'dev_buf_test'
+    subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-Werror', '-fsanitize=address,undefined',
+                    '-fno-sanitize-recover=undefined', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include',
+                    '-I', os.path.join(ROOT, 'narrow_band_least_squares_amd', 'csrc'),
+                    os.path.join(ROOT, 'tests', 'c_caller', 'dev_buf_test.cpp'), '-o', str(exe)], check=True, timeout=300)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stderr == '', r.stdout + r.stderr
+    m = re.fullmatch(r'ok (\d+)\n', r.stdout)
+    assert m and int(m.group(1)) >= 70, r.stdout
+
+
 def test_sequential_rounds_build_the_dictionary_after_the_skeleton(monkeypatch):
     """More bands than the HBM budget of one pass, ALPHA < 1 (engine.py): the rounds are collected inside
     the launch loop, before the result skeleton / key text exist; their dictionary entries must wait for
