@@ -20,7 +20,7 @@ import numpy as np
 from scipy import signal
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from narrow_band_least_squares_amd import ltsva                                              # noqa: E402
+from narrow_band_least_squares_amd import ltsva, ltsva_beam                                  # noqa: E402
 from narrow_band_least_squares_amd import narrow_band_least_squares, narrow_band_least_squares_parallel  # noqa: E402
 from narrow_band_least_squares_amd import (get_freqlist, get_winlenlist, filter_data, get_rij, write_txtfile,  # noqa: E402
                                            read_txtfile, synthetic)
@@ -54,6 +54,10 @@ def main():
      baz_uncert_broad) = ltsva(stf_broad, latlist, lonlist, WINLEN, WINOVER, ALPHA, PLOT_ARRAY_COORDINATES)
     print('broadband: %d windows, median back-azimuth %.1f deg, trace velocity %.3f km/s, MdCCM %.2f'
           % (len(vel_broad), np.median(baz_broad), np.median(vel_broad), np.median(mdccm_broad)))
+    # (an extension: the same call with the delay-and-sum beam's power and Fisher F-statistic at the solved slowness)
+    beam_power_broad, fstat_broad = ltsva_beam(stf_broad, latlist, lonlist, WINLEN, WINOVER, ALPHA)[8:]
+    print('broadband beam: median power %.3g, median F %.1f, %d of %d windows above F = 5'
+          % (np.median(beam_power_broad), np.median(fstat_broad), int(np.sum(fstat_broad > 5.0)), len(fstat_broad)))
     freq_resp_list = np.logspace(math.log(0.01, 10), math.log(Fs / 2, 10), num=1000)
     w_broad, h_broad = signal.sosfreqz(sos, freq_resp_list, fs=Fs)
 

@@ -202,6 +202,31 @@ int nbls_fetch(nbls_handle* h, double* vel, double* baz, double* mdccm, double* 
 int nbls_set_uncertainty(nbls_handle* h, const double* eig6);
 int nbls_fetch_uncertainty(nbls_handle* h, double* vel_uncert, double* baz_uncert);
 
+/* Beam power and Fisher F-statistic of the delay-and-sum beam at the solved slowness, computed on
+ * the GPU behind every unit's solve when wanted — per estimator, with that estimator's N elements (estimator 0: every
+ * element of the row's recording; a further one: the trace rows kept[]) and its own slowness z.  For the unit of result
+ * row r, window w (start s0 = w * wininc, length W):
+ *   delays   d_0 = 0, d_i = rint(fs * (xij[k][0] z0 + xij[k][1] z1)), ties to even, k = i - 1 the index of pair (0, i) in
+ *            the estimator's own pair list: the modelled lag of pair (0, i) in samples, in the sign convention of the
+ *            measured lag of nbls_fetch (lag = W-1-argmax, tau = xij . z) — element i lags element 0 by d_i samples
+ *   samples  x_i[t] = filt[row of element i][s0 + t + d_i] for t in [0, W), 0.0 where the index is outside [0, npts)
+ *   sums     b[t] = sum_i x_i[t], S_b = sum_t b[t]^2, S_t = sum_t sum_i x_i[t]^2, D = N S_t - S_b
+ *   outputs  beam_power = S_b / (N^2 W), fstat = (N - 1) S_b / D; fstat = +inf if D <= 0 and S_b > 0; fstat = NaN and
+ *            beam_power = 0 if S_t == 0; both NaN if z is not finite, some |fs xij . z| is at least 2^30, or a sample
+ *            read is NaN.  Cells beyond nwin[r] (and outside a window slice) are zeros.
+ * The order of every sum is fixed per (N, W) and no floating-point atomics are used: single, batched and streamed passes
+ * agree bit for bit.
+ *   nbls_set_beam(h, on)     read by the next nbls_plan; a plan without it is launch for launch the plain pass.
+ *                            NBLS_ERR_UNSUPPORTED from nbls_plan with an RCCL communicator (the gathered block does
+ *                            not carry the two grids).
+ *   nbls_fetch_beam(h, beam_power, fstat)   [rows][vector_len] each (either may be NULL), rows as for nbls_fetch; waits for
+ *                            the pass like nbls_fetch_uncertainty.  NBLS_ERR_STATE if the plan did not ask for beam results.
+ *                            The grids are written by the solve stage alone: zeros until a pass of the plan has run it,
+ *                            and nbls_execute_stages without the solve bit leaves them as they are.
+ * nbls_timings is unchanged: the kernel's time falls inside the solve interval. */
+int nbls_set_beam(nbls_handle* h, int32_t on);
+int nbls_fetch_beam(nbls_handle* h, double* beam_power, double* fstat);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 
@@ -295,6 +320,7 @@ int nbls_est_fetch_packed(nbls_handle* h, int32_t e, void* out, int64_t nbytes);
 int nbls_est_fetch(nbls_handle* h, int32_t e, double* vel, double* baz, double* mdccm, double* sigma_tau, int32_t* nwin,
                    int32_t* lag, double* cmax, uint8_t* weights, double* z);
 int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t e, double* vel_uncert, double* baz_uncert);
+int nbls_est_fetch_beam(nbls_handle* h, int32_t e, double* beam_power, double* fstat);
 int nbls_est_wait_result_batch(nbls_handle* h, int32_t e, int32_t k, int64_t* out4, const void** host_block);
 
 /* ---- multi-GPU: ONE grouped RCCL operation collects every GPU's result block ----------------------

@@ -24,6 +24,7 @@ EXPORTS = [
     'nbls_comm_set_library', 'nbls_set_uncertainty', 'nbls_fetch_uncertainty', 'nbls_expect_upload', 'nbls_abort_upload',
     'nbls_set_segments', 'nbls_route_xcorr', 'nbls_route_table', 'nbls_set_estimators', 'nbls_est_result_layout',
     'nbls_est_fetch_packed', 'nbls_est_fetch', 'nbls_est_fetch_uncertainty', 'nbls_est_wait_result_batch',
+    'nbls_set_beam', 'nbls_fetch_beam', 'nbls_est_fetch_beam',
 ]
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
@@ -140,6 +141,9 @@ def load_library(path=None):
     lib.nbls_est_fetch.argtypes = [vp, C.c_int32] + fetch_args
     lib.nbls_est_fetch_uncertainty.argtypes = [vp, C.c_int32, dp, dp]
     lib.nbls_est_wait_result_batch.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
+    lib.nbls_set_beam.argtypes = [vp, C.c_int32]
+    lib.nbls_fetch_beam.argtypes = [vp, dp, dp]
+    lib.nbls_est_fetch_beam.argtypes = [vp, C.c_int32, dp, dp]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -472,6 +476,20 @@ class Handle:
             self._chk(self.lib.nbls_fetch_uncertainty(self._h, _dptr(out[0]), _dptr(out[1])))
         else:
             self._chk(self.lib.nbls_est_fetch_uncertainty(self._h, int(est), _dptr(out[0]), _dptr(out[1])))
+        return out[0], out[1]
+
+    def set_beam(self, on=True):
+        """The next plans also compute, behind every unit's solve, the power and Fisher F-statistic of the delay-and-sum
+        beam at the solved slowness (``nbls_set_beam``); False switches that off."""
+        self._chk(self.lib.nbls_set_beam(self._h, int(bool(on))))
+
+    def fetch_beam(self, e=0):
+        """-> (beam_power, fstat) of estimator ``e``, each (rows, vector_len)."""
+        out = np.empty((2, self.nbands, self.vector_len))
+        if e == 0:
+            self._chk(self.lib.nbls_fetch_beam(self._h, _dptr(out[0]), _dptr(out[1])))
+        else:
+            self._chk(self.lib.nbls_est_fetch_beam(self._h, int(e), _dptr(out[0]), _dptr(out[1])))
         return out[0], out[1]
 
     def stream_results(self, on=True):

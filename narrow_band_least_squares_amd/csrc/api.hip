@@ -328,6 +328,7 @@ int size_result_buffers(nbls_handle* h, nbls_estimator& x, size_t cells, size_t 
     if ((rc = ensure(h, x.d_z, 2 * cells * sizeof(double)))) return rc;
     if ((rc = ensure(h, x.d_wts, cells * P))) return rc;
     if (x.want_unc && (rc = ensure(h, x.d_unc, 2 * cells * sizeof(double)))) return rc;
+    if (h->beam && (rc = ensure(h, x.d_beam, 2 * cells * sizeof(double)))) return rc;
     return 0;
 }
 
@@ -760,6 +761,10 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     }
     if (h->nest > 0 && (NS > 1 || !h->win_first.empty() || h->comm))
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
+    if (h->want_beam && h->comm)
+        return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: beam results (nbls_set_beam) are not supported with an RCCL communicator (the gathered block does not carry them)");
+    h->beam = h->want_beam;
+    h->beam_valid = false;
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
     nbls_estimator& x0 = h->est[0];
@@ -1000,6 +1005,7 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
             if ((rc = alloc_copy(h, x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
             if ((rc = alloc_copy(h, x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
             if (!x.kept_pair.empty() && (rc = alloc_copy(h, x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
+            if (h->beam && (rc = alloc_copy(h, x.d_kept, x.kept.data(), x.kept.size()))) return rc;
         }
         if (x.lts && (rc = upload_lts_tables(h, x))) return rc;
         if (e > 0 && (rc = size_result_buffers(h, x, (size_t)a.R * a.vector_len, 0))) return rc;
@@ -1102,6 +1108,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (h->prof) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     h->solve_done = false;
     h->last_stage_mask = stage_mask;
+    if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
     // per-batch solves: behind each unit batch of the correlation stage (streamed results: a batch's rows are complete
     // while later batches are still being correlated), on the second stream with option "overlap"
     h->fuse_solve = ((stage_mask & 6) == 6) && h->xcorr_impl == 3 && (h->opt.overlap > 0 || h->stream_results);
@@ -1327,6 +1334,34 @@ int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t est, double* vel_uncert, 
         if (!outs[g]) continue;
         if (!(h->last_stage_mask & 4)) { memset(outs[g], 0, cells * sizeof(double)); continue; }
         HIPCHK(h, copy_sync(h, outs[g], s.d_unc + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
+        zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
+    }
+    return NBLS_OK;
+}
+
+int nbls_set_beam(nbls_handle* h, int32_t on) {
+    if (!h) return NBLS_ERR_ARG;
+    h->want_beam = on != 0;                  // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    return NBLS_OK;
+}
+
+int nbls_fetch_beam(nbls_handle* h, double* beam_power, double* fstat) { return nbls_est_fetch_beam(h, 0, beam_power, fstat); }
+
+int nbls_est_fetch_beam(nbls_handle* h, int32_t est, double* beam_power, double* fstat) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam: no plan");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_beam: no such estimator");
+    const nbls_estimator& s = h->est[est];
+    if (!h->beam || !s.d_beam) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam: nbls_set_beam before nbls_plan");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    double* outs[2] = {beam_power, fstat};
+    for (int g = 0; g < 2; ++g) {
+        if (!outs[g]) continue;
+        // the grids are written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass
+        // without it leaves them as they are
+        if (!h->beam_valid) { memset(outs[g], 0, cells * sizeof(double)); continue; }
+        HIPCHK(h, copy_sync(h, outs[g], s.d_beam + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
         zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
     }
     return NBLS_OK;

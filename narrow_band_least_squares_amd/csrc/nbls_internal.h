@@ -92,6 +92,8 @@ struct nbls_estimator {
     dev_buf<double> d_z;               // [B][VL][2]
     dev_buf<uint8_t> d_wts;            // [B][VL][P'] one byte per pair (kernel-side form; packed into the mask after the solve)
     dev_buf<double> d_unc;             // [2][B][VL]: vel_uncert | baz_uncert
+    dev_buf<int32_t> d_kept;           // [K] the kept elements' rows (a plan with beam results, est[1..]; est[0] takes every row)
+    dev_buf<double> d_beam;            // [2][B][VL]: beam_power | fstat (a plan with beam results, nbls_set_beam)
     // result block, ONE allocation = one D2H copy / one RCCL gather:
     //   [vel | baz | mdccm | sigma_tau] double[4][B][VL], then the LTS weight bit mask uint8[B][VL][MB],
     //   MB = ceil(P'/8), bit k & 7 of byte k >> 3 = weight of pair k (ceil(P/8) bytes per unit)
@@ -121,6 +123,9 @@ struct nbls_handle {
     bool solve_on_stream2 = false;  // ... on the second stream (option "overlap"), else behind the batch on `stream`
     bool solve_done = false;
     int last_stage_mask = 7;        // stages of the last pass (nbls_fetch zeroes the outputs of stages that did not run)
+    bool want_beam = false;         // nbls_set_beam: read by the next nbls_plan
+    bool beam = false;              // the plan computes beam power and F-statistic behind every estimator's solve (beam.hip)
+    bool beam_valid = false;        // a pass of this plan has run the solve stage: est[].d_beam holds results
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -263,7 +268,9 @@ inline nbls_est_view nbls_view_of(const nbls_handle* h, const nbls_estimator& x)
     return {g, g + cells, g + 2 * cells, g + 3 * cells, x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr,
             own ? h->d_lag : x.d_lag, own ? h->d_cmax : x.d_cmax};
 }
-// [gather ->] solve -> [uncertainty ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
+// beam power and F-statistic of units [u0, u0 + nu) at the slowness estimator x has solved for them (beam.hip)
+hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
+// [gather ->] solve -> [uncertainty ->] [beam ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
 hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);

@@ -1425,6 +1425,7 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         hipLaunchKernelGGL(uncertainty_kernel, dim3((unsigned)((nu + 63) / 64)), dim3(64), 0, st, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    if (h->beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
     return pack_weights_of(h, s, u0, nu, st);
 }
 

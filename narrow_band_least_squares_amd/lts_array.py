@@ -22,16 +22,14 @@ def _returns(res, nchans, alpha, keys=None):
     return vel, baz, t, mdccm, stdict, sigma_tau, conf_int_vel, conf_int_baz
 
 
-def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
-          plot_array_coordinates=False, rij=None):
-    """Window the (already filtered) stream, pick pairwise cross-correlation lags and solve for
-    the slowness vector by OLS (``alpha == 1.0``) or FAST-LTS (``0.5 <= alpha < 1``).
+def _returns_beam(res, nchans, alpha, keys=None):
+    """``_returns`` followed by the band's ``beam_power`` and ``fstat`` (csrc/beam.hip: beam_fstat_kernel)."""
+    n = int(res.nwin[0])
+    return _returns(res, nchans, alpha, keys) + (res.beam_power[0, :n].copy(), res.fstat[0, :n].copy())
 
-    Returns ``(vel, baz, t, mdccm, stdict, sigma_tau, conf_int_vel, conf_int_baz)``:
-    trace velocity km/s, back-azimuth degrees in [0, 360), window-centre times as matplotlib
-    date numbers, median cross-correlation maximum, dropped-element dictionary (``{}`` for
-    OLS), sigma_tau seconds, and the 90 % confidence half-widths of trace velocity (km/s) and
-    back-azimuth (degrees; NaN where the direction is undetermined).  ``rij`` (2, N) km overrides the lat/lon geometry."""
+
+def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam):
+    """The one body of ``ltsva`` and ``ltsva_beam``: the checks, the geometry, the device pass, the returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
     engine.check_elements(nchans, alpha)
@@ -47,20 +45,53 @@ def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
             res.keys = engine.time_keys(res.t, res.nwin)
 
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
-                         prefiltered=True, host_overlap=host_side, want_uncert=True)
-    return _returns(res, nchans, alpha, getattr(res, 'keys', None))
+                         prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam)
+    return (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
 
 
-def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None):
+def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
+          plot_array_coordinates=False, rij=None):
+    """Window the (already filtered) stream, pick pairwise cross-correlation lags and solve for
+    the slowness vector by OLS (``alpha == 1.0``) or FAST-LTS (``0.5 <= alpha < 1``).
+
+    Returns ``(vel, baz, t, mdccm, stdict, sigma_tau, conf_int_vel, conf_int_baz)``:
+    trace velocity km/s, back-azimuth degrees in [0, 360), window-centre times as matplotlib
+    date numbers, median cross-correlation maximum, dropped-element dictionary (``{}`` for
+    OLS), sigma_tau seconds, and the 90 % confidence half-widths of trace velocity (km/s) and
+    back-azimuth (degrees; NaN where the direction is undetermined).  ``rij`` (2, N) km overrides the lat/lon geometry."""
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, False)
+
+
+def ltsva_beam(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None):
+    """``ltsva`` followed by two more returns per window: ``beam_power``, the mean power of the delay-and-sum beam at the
+    solved slowness, and ``fstat``, its Fisher ratio (N-1) S_b / (N S_t - S_b) — the array detector users threshold on
+    beside MdCCM.  The elements are shifted by whole samples, the modelled lags of the pairs (0, i) rounded to even;
+    samples outside the trace count as zeros (DESIGN.md section 12 has the definition).  ``fstat`` is ``inf`` for channels
+    that line up exactly and NaN for an all-zero window or a slowness that is not finite.  Both are computed on the GPU
+    behind each window's solve, from the filtered samples already there.  The first eight returns are ``ltsva``'s.
+    Too few elements raise ``ValueError`` here (``ltsva`` keeps the reference's ``RuntimeError``)."""
+    nchans = len(st)
+    if nchans < 3 or (alpha < 1.0 and nchans < 4):
+        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
+                         'squares' % nchans)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, True)
+
+
+def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False):
     """``ltsva`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of 8-tuples,
     element i equal to ``ltsva(streams[i], ...)``.  Every stream must have the same element count, trace length and
     sampling rate, and all share the geometry; ``ValueError`` names a mismatch before any GPU work.  The "ALPHA is
-    1.0" message prints once per batch.  An empty sequence gives ``[]``."""
+    1.0" message prints once per batch.  An empty sequence gives ``[]``.  ``beam=True``: 10-tuples, element i equal to
+    ``ltsva_beam(streams[i], ...)``."""
+    if not isinstance(beam, (bool, np.bool_)):
+        raise ValueError('beam must be True or False, not %r' % (beam,))
     streams = list(streams)
     if not streams:
         return []
     recs, fs, t0s = engine.batch_rows(streams)
     if len(streams) == 1:          # a batch of one IS the single call
+        if beam:
+            return [ltsva_beam(streams[0], lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)]
         return [ltsva(streams[0], lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)]
     nchans = len(recs[0])
     engine.check_elements(nchans, alpha)
@@ -69,20 +100,26 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     if alpha == 1.0:
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
-                                   prefiltered=True, want_uncert=True)
-    return [_returns(res, nchans, alpha) for res in results]
+                                   prefiltered=True, want_uncert=True, want_beam=bool(beam))
+    return [(_returns_beam if beam else _returns)(res, nchans, alpha) for res in results]
 
 
-def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None):
+def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False):
     """``ltsva`` of one (already filtered) stream for several estimators ``(alpha, remove)`` in one GPU pass -> a list of
     ``ltsva``'s 8-tuples, element e equal to ``ltsva`` with ``alpha_e`` on the stream without the traces ``remove_e``
     (0-based, ascending; a bare number means nothing removed; at most 8 estimators).  The windows of the full array are
     correlated once, every window is solved once per estimator.  ``ValueError`` before any GPU work for an empty list, a
-    bad alpha or ``remove`` and too few kept elements.  The "ALPHA is 1.0" message prints once per call."""
+    bad alpha or ``remove`` and too few kept elements.  The "ALPHA is 1.0" message prints once per call.  ``beam=True``:
+    10-tuples, element e equal to ``ltsva_beam`` on the reduced stream (the beam of estimator e's elements at its
+    slowness)."""
+    if not isinstance(beam, (bool, np.bool_)):
+        raise ValueError('beam must be True or False, not %r' % (beam,))
     data, fs, _ = engine.stream_rows(st)
     nchans = len(data)
     ests = engine.normalize_estimators(estimators, nchans)
     if len(ests) == 1 and not ests[0][1]:          # one estimator with nothing removed IS the single call
+        if beam:
+            return [ltsva_beam(st, lat_list, lon_list, window_length, window_overlap, alpha=ests[0][0], rij=rij)]
         return [ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=ests[0][0], rij=rij)]
     rijs, t0s = [], []
     for _, remove in ests:
@@ -97,11 +134,11 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     if any(a == 1.0 for a, _ in ests):
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_multi(data, fs, t0s, rijs, [(None, None)], [window_length], window_overlap, ests,
-                                   prefiltered=True, want_uncert=True)
+                                   prefiltered=True, want_uncert=True, want_beam=bool(beam))
     keys = {}
     out = []
     for (alpha, _), res in zip(ests, results):
         if alpha != 1.0 and id(res.t) not in keys:
             keys[id(res.t)] = engine.time_keys(res.t, res.nwin)
-        out.append(_returns(res, res.nchans, alpha, keys.get(id(res.t))))
+        out.append((_returns_beam if beam else _returns)(res, res.nchans, alpha, keys.get(id(res.t))))
     return out
