@@ -4,7 +4,7 @@ arguments (filter_data -> ltsva broadband; get_freqlist / get_winlenlist -> narr
 write_txtfile), on a synthetic 8-element plane wave instead of an IRIS download (there is no network here), and
 without the matplotlib figures.  Needs an MI355X.
 
-    python examples/synthetic_example.py [--alpha 0.5] [--parallel]
+    python examples/synthetic_example.py [--alpha 0.5] [--parallel] [--subsample]
 
 The three import lines are the only difference from a script written against the reference: they name this
 package instead of `narrow_band_least_squares`, `helpers` and `lts_array`
@@ -20,8 +20,9 @@ import numpy as np
 from scipy import signal
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from narrow_band_least_squares_amd import ltsva, ltsva_beam                                  # noqa: E402
+from narrow_band_least_squares_amd import ltsva, ltsva_beam, ltsva_subsample                 # noqa: E402
 from narrow_band_least_squares_amd import narrow_band_least_squares, narrow_band_least_squares_parallel  # noqa: E402
+from narrow_band_least_squares_amd import narrow_band_least_squares_subsample              # noqa: E402
 from narrow_band_least_squares_amd import (get_freqlist, get_winlenlist, filter_data, get_rij, write_txtfile,  # noqa: E402
                                            read_txtfile, synthetic)
 
@@ -30,7 +31,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--alpha', type=float, default=1.0, help='1.0 = ordinary least squares, < 1 = least trimmed squares')
     ap.add_argument('--parallel', action='store_true', help='use narrow_band_least_squares_parallel (all visible GPUs)')
+    ap.add_argument('--subsample', action='store_true',
+                    help='fit the slowness to lags refined to sub-sample precision (an extension; not with --parallel)')
     args = ap.parse_args()
+    if args.subsample and args.parallel:
+        ap.error('--subsample has no multi-GPU form')
 
     # ---- user input, as in example.py ----
     FMIN, FMAX, NBANDS = 0.1, 5.0, 8
@@ -58,6 +63,11 @@ def main():
     beam_power_broad, fstat_broad = ltsva_beam(stf_broad, latlist, lonlist, WINLEN, WINOVER, ALPHA)[8:]
     print('broadband beam: median power %.3g, median F %.1f, %d of %d windows above F = 5'
           % (np.median(beam_power_broad), np.median(fstat_broad), int(np.sum(fstat_broad > 5.0)), len(fstat_broad)))
+    if args.subsample:
+        # (an extension: the lags refined by the parabola through the three correlation values around each maximum)
+        sig_tau_sub = ltsva_subsample(stf_broad, latlist, lonlist, WINLEN, WINOVER, ALPHA)[5]
+        print('broadband sigma_tau: median %.4f s with whole-sample lags, %.4f s with refined lags (quantisation floor %.4f s)'
+              % (np.nanmedian(sig_tau_broad), np.nanmedian(sig_tau_sub), 1.0 / (Fs * math.sqrt(12.0))))
     freq_resp_list = np.logspace(math.log(0.01, 10), math.log(Fs / 2, 10), num=1000)
     w_broad, h_broad = signal.sosfreqz(sos, freq_resp_list, fs=Fs)
 
@@ -65,6 +75,8 @@ def main():
     freqlist, NBANDS, FMAX = get_freqlist(FMIN, FMAX, FREQ_BAND_TYPE, NBANDS)
     WINLEN_list = get_winlenlist(WINDOW_LENGTH_TYPE, NBANDS, WINLEN, WINLEN_1, WINLEN_X)
     run = narrow_band_least_squares_parallel if args.parallel else narrow_band_least_squares
+    if args.subsample:
+        run = narrow_band_least_squares_subsample
     (vel_array, baz_array, mdccm_array, t_array, stdict_all, sig_tau_array, num_compute_list, w_array,
      h_array) = run(WINLEN_list, WINOVER, ALPHA, st, latlist, lonlist, NBANDS, w_broad, h_broad, freqlist, FREQ_BAND_TYPE,
                     freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE)

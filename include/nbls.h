@@ -227,6 +227,41 @@ int nbls_fetch_uncertainty(nbls_handle* h, double* vel_uncert, double* baz_uncer
 int nbls_set_beam(nbls_handle* h, int32_t on);
 int nbls_fetch_beam(nbls_handle* h, double* beam_power, double* fstat);
 
+/* Sub-sample refinement of the picked lags, computed on the GPU in the correlation stage behind
+ * the verifier of each unit batch when wanted.  For one unit and one pair (i, j) with picked lag l = W-1-argmax, which stays
+ * exactly what it is today, let a, b be the unit's windows of elements i and j as the correlator saw them.  Define
+ *   R(m) = sum_n a[n-m] b[n]  over the n for which both indices are in [0, W): np.correlate(a, b, 'full')[W-1-m], raw and
+ *            not normalised
+ *   Nn   = R(l-1) - R(l+1)
+ *   D    = R(l-1) - 2 R(l) + R(l+1)
+ *   frac = 1/2 Nn / D, clamped to [-1/2, 1/2]
+ *   frac = 0.0 in each of these cases: |l| >= W-1; D >= 0 (no strict maximum: dead channel, plateau); any of the three
+ *            values or the quotient is not finite (NaN / Inf windows keep today's behaviour)
+ *   tau  = ((double)lag + frac) / fs, in un-fused IEEE double, in exactly this form at every site that reads a lag
+ * All three R are computed by the refinement kernel itself, in one summation order (R(l) is not cmax * norm).  The
+ * summation order depends on (W, l) alone; no atomics are used, and nothing depends on the launch's unit range: single,
+ * streamed, batched, window-sliced and multi-estimator passes agree bit for bit, and a sub-array estimator agrees with a
+ * separate call on the sub-array.  cmax, MdCCM, nbls_fetch's lag, the key text of stdict and the MAD(tau) == 0 -> NaN rule
+ * are unchanged.  Cells beyond nwin are zeros.
+ *   nbls_set_lag_refinement(h, on)   read by the next nbls_plan, like nbls_set_beam; a plan without it is launch for launch
+ *                            the plain pass.  An RCCL communicator is not refused: the gathered block carries everything
+ *                            that changes; the fractions themselves are fetched locally only.
+ *   nbls_fetch_lag_fraction(h, frac)   [rows][vector_len][npairs]; waits for the pass like nbls_fetch.
+ *   nbls_est_fetch_lag_fraction(h, e, frac)   the same for estimator e, [rows][vector_len][P'] (nbls_set_estimators).
+ *                            Both return NBLS_ERR_STATE if the plan did not ask for refinement.  The fractions are written by
+ *                            the correlation stage alone: zeros until a pass of the plan has run it, and
+ *                            nbls_execute_stages without that bit keeps the fractions it has (the solve goes on using them).
+ * nbls_timings is unchanged: the kernel's time falls inside the correlation interval (on the screening path inside
+ * verify_ms). */
+int nbls_set_lag_refinement(nbls_handle* h, int32_t on);
+/* Which of its two forms the refinement kernel takes for windows of W samples of an array of nelem elements (a pure host
+ * function, like nbls_route_xcorr): the dynamic LDS bytes of the form that stages the unit's nelem windows in LDS
+ * (nelem * W * 8, up to 80 KiB), or 0 for the form that reads them from global memory.  Both give the same bits.
+ * NBLS_ERR_ARG for nelem < 1 or W < 1. */
+int nbls_refine_lds_bytes(int32_t nelem, int32_t W);
+int nbls_fetch_lag_fraction(nbls_handle* h, double* frac);
+int nbls_est_fetch_lag_fraction(nbls_handle* h, int32_t e, double* frac);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -8,8 +8,9 @@ import sys as _sys
 
 from .narrow_band_least_squares import (narrow_band_least_squares, narrow_band_loop,
                                         narrow_band_least_squares_parallel, narrow_band_least_squares_batch,
-                                        narrow_band_least_squares_multi, narrow_band_least_squares_beam)
-from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam
+                                        narrow_band_least_squares_multi, narrow_band_least_squares_beam,
+                                        narrow_band_least_squares_subsample)
+from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample
 from .helpers import (get_freqlist, get_winlenlist, filter_data, make_float, get_rij,
                       write_txtfile, read_txtfile)
 from .stream import Stream, Trace, Stats
@@ -19,7 +20,7 @@ __all__ = ['narrow_band_least_squares', 'narrow_band_loop', 'narrow_band_least_s
            'ltsva', 'get_freqlist', 'get_winlenlist', 'filter_data', 'make_float', 'get_rij',
            'write_txtfile', 'read_txtfile', 'Stream', 'Trace', 'Stats', 'install_as_reference_modules', 'resident_trace',
            'narrow_band_least_squares_batch', 'ltsva_batch', 'narrow_band_least_squares_multi', 'ltsva_multi',
-           'narrow_band_least_squares_beam', 'ltsva_beam']
+           'narrow_band_least_squares_beam', 'ltsva_beam', 'narrow_band_least_squares_subsample', 'ltsva_subsample']
 
 
 def install_as_reference_modules():

@@ -25,6 +25,7 @@ EXPORTS = [
     'nbls_set_segments', 'nbls_route_xcorr', 'nbls_route_table', 'nbls_set_estimators', 'nbls_est_result_layout',
     'nbls_est_fetch_packed', 'nbls_est_fetch', 'nbls_est_fetch_uncertainty', 'nbls_est_wait_result_batch',
     'nbls_set_beam', 'nbls_fetch_beam', 'nbls_est_fetch_beam',
+    'nbls_set_lag_refinement', 'nbls_fetch_lag_fraction', 'nbls_est_fetch_lag_fraction', 'nbls_refine_lds_bytes',
 ]
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
@@ -144,6 +145,10 @@ def load_library(path=None):
     lib.nbls_set_beam.argtypes = [vp, C.c_int32]
     lib.nbls_fetch_beam.argtypes = [vp, dp, dp]
     lib.nbls_est_fetch_beam.argtypes = [vp, C.c_int32, dp, dp]
+    lib.nbls_set_lag_refinement.argtypes = [vp, C.c_int32]
+    lib.nbls_fetch_lag_fraction.argtypes = [vp, dp]
+    lib.nbls_refine_lds_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.nbls_est_fetch_lag_fraction.argtypes = [vp, C.c_int32, dp]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -492,6 +497,20 @@ class Handle:
             self._chk(self.lib.nbls_est_fetch_beam(self._h, int(e), _dptr(out[0]), _dptr(out[1])))
         return out[0], out[1]
 
+    def set_lag_refinement(self, on=True):
+        """The next plans also refine every picked lag to sub-sample precision behind its verifier, and their solves read
+        ``tau = (lag + frac) / fs`` (``nbls_set_lag_refinement``); False switches that off."""
+        self._chk(self.lib.nbls_set_lag_refinement(self._h, int(bool(on))))
+
+    def fetch_lag_fraction(self, e=0):
+        """-> the sub-sample fractions of estimator ``e``'s lags, (rows, vector_len, pairs of that estimator)."""
+        out = np.empty((self.nbands, self.vector_len, self._est_pairs(e)))
+        if e == 0:
+            self._chk(self.lib.nbls_fetch_lag_fraction(self._h, _dptr(out)))
+        else:
+            self._chk(self.lib.nbls_est_fetch_lag_fraction(self._h, int(e), _dptr(out)))
+        return out
+
     def stream_results(self, on=True):
         """The next passes deliver their rows batch by batch into a pinned host mirror of the result block
         (``nbls_stream_results``); see ``result_batches`` / ``wait_result_batch``."""
@@ -592,6 +611,15 @@ class Handle:
         out = np.empty(256)
         self._chk(self.lib.nbls_probe_mfma_f64(self._h, _dptr(a), _dptr(b), _dptr(out)))
         return out.reshape(64, 4)
+
+
+def refine_lds_bytes(nelem, W):
+    """Dynamic LDS bytes of the form ``refine_lag_kernel`` takes for windows of W samples of ``nelem`` elements; 0: the
+    form that reads global memory (``nbls_refine_lds_bytes``)."""
+    rc = load_library().nbls_refine_lds_bytes(int(nelem), int(W))
+    if rc < 0:
+        raise ValueError('nbls_refine_lds_bytes: bad arguments')
+    return int(rc)
 
 
 def _route_args(nelem, npairs):

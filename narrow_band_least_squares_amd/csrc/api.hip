@@ -325,6 +325,7 @@ int size_result_buffers(nbls_handle* h, nbls_estimator& x, size_t cells, size_t 
     if ((rc = ensure(h, x.d_res, x.res_bytes > min_res ? x.res_bytes : min_res))) return rc;
     if ((rc = ensure(h, own ? h->d_lag : x.d_lag, cells * P * sizeof(int32_t)))) return rc;
     if ((rc = ensure(h, own ? h->d_cmax : x.d_cmax, cells * P * sizeof(double)))) return rc;
+    if (h->refine && (rc = ensure(h, own ? h->d_lagfrac : x.d_lagfrac, cells * P * sizeof(double)))) return rc;
     if ((rc = ensure(h, x.d_z, 2 * cells * sizeof(double)))) return rc;
     if ((rc = ensure(h, x.d_wts, cells * P))) return rc;
     if (x.want_unc && (rc = ensure(h, x.d_unc, 2 * cells * sizeof(double)))) return rc;
@@ -765,6 +766,9 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: beam results (nbls_set_beam) are not supported with an RCCL communicator (the gathered block does not carry them)");
     h->beam = h->want_beam;
     h->beam_valid = false;
+    h->refine = h->want_refine;
+    h->frac_valid = false;
+    h->solve_ran = false;
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
     nbls_estimator& x0 = h->est[0];
@@ -1109,6 +1113,8 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     h->solve_done = false;
     h->last_stage_mask = stage_mask;
     if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
+    if (stage_mask & 4) h->solve_ran = true;
+    if (stage_mask & 2) h->frac_valid = true;            // (... one without the correlation stage the lag fractions)
     // per-batch solves: behind each unit batch of the correlation stage (streamed results: a batch's rows are complete
     // while later batches are still being correlated), on the second stream with option "overlap"
     h->fuse_solve = ((stage_mask & 6) == 6) && h->xcorr_impl == 3 && (h->opt.overlap > 0 || h->stream_results);
@@ -1364,6 +1370,37 @@ int nbls_est_fetch_beam(nbls_handle* h, int32_t est, double* beam_power, double*
         HIPCHK(h, copy_sync(h, outs[g], s.d_beam + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
         zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
     }
+    return NBLS_OK;
+}
+
+int nbls_set_lag_refinement(nbls_handle* h, int32_t on) {
+    if (!h) return NBLS_ERR_ARG;
+    h->want_refine = on != 0;                // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    return NBLS_OK;
+}
+
+int nbls_refine_lds_bytes(int32_t nelem, int32_t W) {
+    if (nelem < 1 || W < 1) return NBLS_ERR_ARG;
+    return (int)nbls_refine_lds_bytes_of(nelem, W);
+}
+
+int nbls_fetch_lag_fraction(nbls_handle* h, double* frac) { return nbls_est_fetch_lag_fraction(h, 0, frac); }
+
+int nbls_est_fetch_lag_fraction(nbls_handle* h, int32_t est, double* frac) {
+    if (!h || !frac) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_lag_fraction: no plan");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_lag_fraction: no such estimator");
+    const nbls_estimator& s = h->est[est];
+    const nbls_est_view v = nbls_view_of(h, s);
+    if (!h->refine || !v.frac) return fail(h, NBLS_ERR_STATE, "nbls_fetch_lag_fraction: nbls_set_lag_refinement before nbls_plan");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len, P = (size_t)s.npairs;
+    // the fractions are written by the correlation stage alone (a sub-array's compact rows: gathered as part of its solve):
+    // zeros until a pass of this plan has run it, and a later pass without it leaves them as they are
+    const bool have = h->frac_valid && (s.kept_pair.empty() || h->solve_ran);
+    if (!have) { memset(frac, 0, cells * P * sizeof(double)); return NBLS_OK; }
+    HIPCHK(h, copy_sync(h, frac, v.frac, cells * P * sizeof(double), hipMemcpyDeviceToHost));
+    zero_uncomputed(h, frac, P * sizeof(double));
     return NBLS_OK;
 }
 

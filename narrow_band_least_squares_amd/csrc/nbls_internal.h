@@ -89,6 +89,7 @@ struct nbls_estimator {
     dev_buf<int32_t> d_kept_pair;
     dev_buf<int32_t> d_lag;
     dev_buf<double> d_cmax;
+    dev_buf<double> d_lagfrac;         // ... and of their sub-sample fractions (a plan with lag refinement)
     dev_buf<double> d_z;               // [B][VL][2]
     dev_buf<uint8_t> d_wts;            // [B][VL][P'] one byte per pair (kernel-side form; packed into the mask after the solve)
     dev_buf<double> d_unc;             // [2][B][VL]: vel_uncert | baz_uncert
@@ -126,6 +127,11 @@ struct nbls_handle {
     bool want_beam = false;         // nbls_set_beam: read by the next nbls_plan
     bool beam = false;              // the plan computes beam power and F-statistic behind every estimator's solve (beam.hip)
     bool beam_valid = false;        // a pass of this plan has run the solve stage: est[].d_beam holds results
+    bool want_refine = false;       // nbls_set_lag_refinement: read by the next nbls_plan
+    bool refine = false;            // the plan refines the picked lags to sub-sample precision behind the verifier (refine.hip)
+    bool frac_valid = false;        // a pass of this plan has run the correlation stage: d_lagfrac holds results
+    bool solve_ran = false;         // a pass of this plan has run the solve stage (a sub-array's compact rows are gathered there)
+    bool refine_attr_set = false;   // the LDS form of refine_lag_kernel has been given its dynamic LDS limit on this handle's device
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -195,6 +201,7 @@ struct nbls_handle {
     dev_buf<double> d_tstate;      // [B*N][C/T][nchunks][D] forward states at the tile boundaries (zero-phase, recompute form)
     dev_buf<int32_t> d_lag;        // [B][VL][P]
     dev_buf<double> d_cmax;        // [B][VL][P]
+    dev_buf<double> d_lagfrac;     // [B][VL][P] sub-sample fraction of every lag (a plan with lag refinement, else not allocated)
     bool res_loaded = false;       // est[0].d_res holds a block put there by nbls_load_result_block (cleared by the next nbls_plan)
     size_t reserve_res = 0;        // minimum allocation of est[0]'s result block (nbls_reserve_results: equal gather blocks)
     // ---- RCCL gather (comm.hip) ----
@@ -259,15 +266,20 @@ hipError_t nbls_launch_solve(nbls_handle* h);
 hipError_t nbls_launch_solve_range(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 hipError_t nbls_launch_pack_weights(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 // What a record does not store: the four grids [B][VL] and the mask inside its result block, and the lag / cmax rows its
-// solve reads (the pass's own for a full array, the record's compact ones for a sub-array).
-struct nbls_est_view { double *vel, *baz, *mdccm, *sig; uint8_t* mask; int32_t* lag; double* cmax; };
+// solve reads (the pass's own for a full array, the record's compact ones for a sub-array; frac only under lag refinement).
+struct nbls_est_view { double *vel, *baz, *mdccm, *sig; uint8_t* mask; int32_t* lag; double* cmax; double* frac; };
 inline nbls_est_view nbls_view_of(const nbls_handle* h, const nbls_estimator& x) {
     const size_t cells = (size_t)h->nbands * h->vector_len;
     double* const g = (double*)x.d_res.p;
     const bool own = x.kept_pair.empty();
     return {g, g + cells, g + 2 * cells, g + 3 * cells, x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr,
-            own ? h->d_lag : x.d_lag, own ? h->d_cmax : x.d_cmax};
+            own ? h->d_lag : x.d_lag, own ? h->d_cmax : x.d_cmax,
+            h->refine ? (own ? h->d_lagfrac.p : x.d_lagfrac.p) : nullptr};       // (NULL: the solve reads tau = lag / fs)
 }
+// sub-sample fractions of the lags of units [u0, u0 + nu), behind their verifier (refine.hip; a plan with lag refinement)
+hipError_t nbls_launch_refine(nbls_handle* h, int64_t u0, int64_t nu, int gW, hipStream_t st);
+// dynamic LDS bytes of the form refine_lag_kernel takes for windows of W samples of nelem elements; 0: the global-memory form
+size_t nbls_refine_lds_bytes_of(int nelem, int W);
 // beam power and F-statistic of units [u0, u0 + nu) at the slowness estimator x has solved for them (beam.hip)
 hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // [gather ->] solve -> [uncertainty ->] [beam ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan

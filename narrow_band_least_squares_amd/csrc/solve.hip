@@ -31,6 +31,7 @@ namespace {
 
 struct SArgs {
     const int32_t* lag;
+    const double* frac;    // sub-sample fractions beside the lags (refine.hip), NULL: the plan does not refine
     const double* cmax;
     int npairs;
     int vector_len;
@@ -67,6 +68,12 @@ struct SArgs {
 };
 
 __device__ inline double dnan() { return __builtin_nan(""); }
+
+// The delay (s) of entry i of the lag rows: the picked lag, plus its sub-sample fraction where the plan computes one.
+__device__ __forceinline__ double tau_of(const SArgs& a, int64_t i) {
+    const double l = (double)a.lag[i];
+    return a.frac ? (l + a.frac[i]) / a.fs : l / a.fs;
+}
 
 __device__ inline void vel_baz(double z0, double z1, double* vel, double* baz) {
     *vel = 1.0 / sqrt(z0 * z0 + z1 * z1);
@@ -135,16 +142,15 @@ __global__ __launch_bounds__(64) void solve_ols_kernel(SArgs a, int nunits, int 
     if (smem_pairs)
         for (int k = 0; k < P; ++k) ols_col[k * 64 + threadIdx.x] = a.cmax[o * P + k];
     if (!live) return;
-    const int32_t* lag = a.lag + o * P;
     double z0 = 0.0, z1 = 0.0;
     for (int k = 0; k < P; ++k) {
-        const double t = (double)lag[k] / a.fs;
+        const double t = tau_of(a, o * P + k);
         z0 = z0 + a.xpinv[k] * t;
         z1 = z1 + a.xpinv[P + k] * t;
     }
     double acc = 0.0;
     for (int k = 0; k < P; ++k) {
-        const double t = (double)lag[k] / a.fs;
+        const double t = tau_of(a, o * P + k);
         const double r = t - (a.xij[2 * k] * z0 + a.xij[2 * k + 1] * z1);
         acc = acc + t * r;
         a.wts[o * P + k] = 1;
@@ -315,7 +321,7 @@ __global__ __launch_bounds__(LT) void solve_lts_kernel(SArgs a, int nunits) {
     double* absr = ABSR ? (double*)((uint8_t*)sm + off_bytes) : nullptr;
 
     for (int k = tid; k < P; k += LT) {
-        const double t = (double)a.lag[o * P + k] / a.fs;
+        const double t = tau_of(a, o * P + k);
         tauv[k] = t;
         tmp[k] = fabs(t);
         X0[k] = a.xs[2 * k];
@@ -847,7 +853,7 @@ __global__ __launch_bounds__(256, 2) void solve_lts_wave_kernel(SArgs a, int nun
 
     if (lane < P) {
         const int k = lane;
-        const double t = (double)a.lag[o * P + k] / a.fs;
+        const double t = tau_of(a, o * P + k);
         tauv[k] = t;
         tmp[k] = fabs(t);
         X0[k] = a.xs[2 * k];
@@ -1355,7 +1361,8 @@ __global__ __launch_bounds__(GATHER_WAVES * 64) void gather_pairs_kernel(const i
                                                                          const int32_t* __restrict__ kept_pair,
                                                                          const int32_t* __restrict__ unit_band,
                                                                          const int32_t* __restrict__ unit_win, int vector_len, int P,
-                                                                         int Pc, int u0, int nunits) {
+                                                                         int Pc, int u0, int nunits, const double* __restrict__ frac,
+                                                                         double* __restrict__ frac_c) {
     extern __shared__ double gather_lds[];
     double* row_c = gather_lds;                                          // [GATHER_WAVES][P]
     int32_t* row_l = (int32_t*)(gather_lds + GATHER_WAVES * P);          // [GATHER_WAVES][P]
@@ -1379,6 +1386,7 @@ __global__ __launch_bounds__(GATHER_WAVES * 64) void gather_pairs_kernel(const i
                 const int src = map[k];
                 lag_c[o * Pc + k] = rl[src];
                 cmax_c[o * Pc + k] = rc[src];
+                if (frac) frac_c[o * Pc + k] = frac[o * P + src];      // (a plan with lag refinement: the fraction rows too)
             }
         __syncthreads();
     }
@@ -1410,7 +1418,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         if (grid > cap) grid = cap;
         hipLaunchKernelGGL(gather_pairs_kernel, dim3((unsigned)grid), dim3(GATHER_WAVES * 64), shm, st, (const int32_t*)h->d_lag,
                            (const double*)h->d_cmax, v.lag, v.cmax, (const int32_t*)s.d_kept_pair, (const int32_t*)h->d_unit_band,
-                           (const int32_t*)h->d_unit_win, h->vector_len, P, Pc, (int)u0, (int)nu);
+                           (const int32_t*)h->d_unit_win, h->vector_len, P, Pc, (int)u0, (int)nu,
+                           h->refine ? (const double*)h->d_lagfrac : nullptr, v.frac);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if ((e = solve_range_impl(h, s, v, u0, nu, st)) != hipSuccess) return e;
@@ -1443,6 +1452,7 @@ static hipError_t solve_range_impl(nbls_handle* h, const nbls_estimator& s, cons
     SArgs a{};
     a.u0 = (int)u0;
     a.lag = v.lag;
+    a.frac = v.frac;
     a.cmax = v.cmax;
     a.npairs = s.npairs;
     a.vector_len = h->vector_len;

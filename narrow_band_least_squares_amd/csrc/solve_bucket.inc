@@ -410,7 +410,7 @@ __global__ __launch_bounds__(512, 3) void solve_lts_bucket_kernel(SArgs a, const
     // ---- prologue: tau, its MAD, MdCCM; scratch in the histogram space ----
     double* tmp = (double*)L.hist;
     double* srt = tmp + P;
-    for (int k = tid; k < P; k += nthr) tmp[k] = fabs((double)a.lag[o * P + k] / a.fs);
+    for (int k = tid; k < P; k += nthr) tmp[k] = fabs(tau_of(a, o * P + k));
     if (tid == 0) L.misc[0] = 0;
     __syncthreads();
     for (int k = tid; k < P; k += nthr) {
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(512, 3) void solve_lts_bucket_kernel(SArgs a, const
         return;
     }
     for (int k = tid; k < P; k += nthr) {
-        const double yk = ((double)a.lag[o * P + k] / a.fs) / tmad;
+        const double yk = tau_of(a, o * P + k) / tmad;
         L.y[k] = yk;
         if ((k & 3) == 0) L.ys[k >> 2] = yk;
     }
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(512, 3) void solve_lts_bucket_kernel(SArgs a, const
     uint8_t* wsh = (uint8_t*)L.hist + bk_align16((size_t)4 * P * sizeof(double));
     __syncthreads();
     for (int k = tid; k < P; k += nthr) {
-        const double tk = (double)a.lag[o * P + k] / a.fs;
+        const double tk = tau_of(a, o * P + k);
         const double c0 = a.xij[2 * k], c1 = a.xij[2 * k + 1];
         tauv[k] = tk;
         x0[k] = c0;

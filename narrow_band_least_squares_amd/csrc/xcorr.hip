@@ -308,7 +308,8 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
         if (e != hipSuccess) return e;
         *used = 2;
         hipLaunchKernelGGL(xcorr_mfma_kernel, dim3((unsigned)nu), dim3(64 * h->nelem), shm, h->stream, a);
-        return hipGetLastError();
+        if ((e = hipGetLastError()) != hipSuccess || !h->refine) return e;
+        return nbls_launch_refine(h, ub, nu, gW, h->stream);
     }
     const int64_t nblocks = nu * h->npairs;
     a.from_global = r.correlator == NBLS_ROUTE_VALU_GLOBAL ? 1 : 0;
@@ -318,7 +319,9 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
     }
     *used = 1;
     hipLaunchKernelGGL(xcorr_simple_kernel, dim3((unsigned)nblocks), dim3(256), shm, h->stream, a);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !h->refine) return e;
+    return nbls_launch_refine(h, ub, nu, gW, h->stream);        // the lags' sub-sample fractions (refine.hip), behind the lag pick
 }
 
 // The correlation stage of a pass.  The plan's bands come in window groups (h->wgroups: consecutive bands of one

@@ -362,10 +362,11 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 
 
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
-               want_uncert=False, want_beam=False):
+               want_uncert=False, want_beam=False, want_subsample=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
-    ``handle`` are the driver's to set."""
+    ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
+    lags are wanted."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
     grids = np.zeros((4, nb, vector_len))
     unc = np.zeros((2, nb, vector_len)) if want_uncert else (None, None)
@@ -373,6 +374,7 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     return BandBatch(grids=grids, vel=grids[0], baz=grids[1], mdccm=grids[2], sigma_tau=grids[3], nwin=nwin.astype(int), t=None,
                      mask=np.zeros((nb, vector_len, (P + 7) // 8), dtype=np.uint8),
                      lag=np.zeros((nb, vector_len, P), dtype=np.int32) if want_lag else None,
+                     lag_frac=np.zeros((nb, vector_len, P)) if (want_lag and want_subsample) else None,
                      cmax=np.zeros((nb, vector_len, P)) if want_cmax else None,
                      z=np.zeros((nb, vector_len, 2)) if want_z else None, vel_uncert=unc[0], baz_uncert=unc[1],
                      beam_power=beam[0], fstat=beam[1], sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
@@ -454,13 +456,18 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
-                      host_overlap=None, group_done=None, want_beam=False):
+                      host_overlap=None, group_done=None, want_beam=False, want_subsample=False):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
     (the ``ltsva`` entry of the device pass).  Same rows as the in-core pass up to the rounding of the carried filter
     states; HBM holds one segment / one window slice at a time.  The filtered band stays on the host and the windows reach
-    the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``."""
+    the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``; nor is
+    the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM."""
+    if want_subsample:
+        raise ValueError('want_subsample: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
+                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
+                         'sub-sample lag refinement is not available there' % _shape_of(data))
     if want_beam:
         raise ValueError('want_beam: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -559,7 +566,8 @@ def upload_trace(h, data, fs):
 
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
-           trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False):
+           trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
+           subsample=False):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -567,7 +575,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     of the band group queued before this one (``Handle.execute``).  ``before_execute()``: called between plan and
     execute (the caller joins its upload thread there).  ``estimators``: the further estimators of the pass
     (``Handle.set_estimators``); a handle that still carries some from an earlier call is reset.  ``beam``: the plan also
-    computes beam power and F-statistic behind every solve (``Handle.set_beam``; for this plan only)."""
+    computes beam power and F-statistic behind every solve (``Handle.set_beam``; for this plan only).  ``subsample``: the
+    plan refines the picked lags to sub-sample precision before the solve (``Handle.set_lag_refinement``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -589,12 +598,16 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     h.set_uncertainty(planner.uncertainty_frame(prep.xij) if uncert else None)     # (ltsva's confidence intervals, on request)
     if beam:
         h.set_beam(True)
+    if subsample:
+        h.set_lag_refinement(True)
     try:
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
     finally:
         if beam:
             h.set_beam(False)            # (the handle is shared with calls that plan for themselves)
+        if subsample:
+            h.set_lag_refinement(False)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -711,6 +724,8 @@ def collect(res, h, b0, b1, streamed, note):
         res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty()
     if res.beam_power is not None:
         res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam()
+    if res.lag_frac is not None:
+        res.lag_frac[b0:b1] = h.fetch_lag_fraction()
     if not live:
         note.bands(b0, b1)
 
@@ -769,7 +784,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
-            want_uncert=False, want_beam=False):
+            want_uncert=False, want_beam=False, want_subsample=False):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -782,6 +797,9 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     want_beam=True: also ``res.beam_power`` / ``res.fstat`` (nbands, vector_len), power and Fisher F-statistic of the
     delay-and-sum beam at the solved slowness, computed on the GPU behind each unit's solve (``nbls_set_beam``,
     DESIGN.md section 12); ``process_segmented`` refuses it.
+    want_subsample=True: every picked lag is refined to sub-sample precision behind its verifier and the solve reads
+    ``tau = (lag + frac) / fs`` (``nbls_set_lag_refinement``); with ``want_lag`` also ``res.lag_frac``
+    (nbands, vector_len, P) beside ``res.lag``; ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -809,14 +827,16 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam)
+                                     group_done, want_beam, want_subsample)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
-        res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam)
+        res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
+                         want_subsample)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
-                                 window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam)
+                                 window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
+                                 subsample=want_subsample)
     finally:
         if up is not None:
             up.close()
@@ -906,7 +926,7 @@ class _EstimatorResults:
 
 def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_lag=False,
-                  want_cmax=False, host_overlap=None, units_done=None, want_beam=False):
+                  want_cmax=False, host_overlap=None, units_done=None, want_beam=False, want_subsample=False):
     """``process`` for several estimators ``(alpha, remove)`` of ONE trace in one device pass -> a list of ``BandBatch``,
     element e what ``process`` gives for ``alpha_e`` on the rows that ``remove_e`` leaves (``estimators`` as
     ``normalize_estimators`` returns them; ``rijs[e]``: the (2, kept) geometry of estimator e, ``t0s[e]`` its start date).
@@ -919,7 +939,8 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     piece or, where ``stream_pays`` for the most demanding estimator, batch by batch — estimator by estimator, each through
     ``drain``.  ``host_overlap(results)`` runs once the first pass is queued; ``units_done(e, res, u0, u1)`` when the
     units [u0, u1) (flat over all bands) of estimator e are in ``results[e]``.  ``want_beam``: every estimator's
-    ``beam_power`` / ``fstat``, of ITS elements at ITS slowness (``process``)."""
+    ``beam_power`` / ``fstat``, of ITS elements at ITS slowness (``process``).  ``want_subsample``: the pass refines the full
+    array's lags once and every estimator solves on the refined delays of ITS pairs (``lag_frac`` with ``want_lag``)."""
     rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
     nchans, npts = _shape_of(rows)
     nb = len(band_edges)
@@ -944,7 +965,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     results = [None] * len(estimators)
     for i, (alpha, remove) in enumerate(estimators):
         res = new_result(nchans - len(remove), alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax,
-                         want_uncert=want_uncert, want_beam=want_beam)
+                         want_uncert=want_uncert, want_beam=want_beam, want_subsample=want_subsample)
         res.xij, res.pair_idx, _ = planner.co_array(rijs[i])
         results[i] = res
     streamed = stream_pays(min(a for a, _ in estimators), nwin, nchans * (nchans - 1) // 2)
@@ -962,7 +983,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
             try:
                 launch(h, rows, prep, trace_ready=joins or resident or b0 > 0, stream=streamed, uncert=want_uncert,
                        before_execute=up.landed if (joins and not up.row_pipeline) else None, estimators=extras,
-                       beam=want_beam)
+                       beam=want_beam, subsample=want_subsample)
             finally:
                 if joins:
                     up.landed()
@@ -997,6 +1018,8 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
                     res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty(est=est)
                 if want_beam:
                     res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam(est)
+                if res.lag_frac is not None:
+                    res.lag_frac[b0:b1] = h.fetch_lag_fraction(est)
     finally:
         if up is not None:
             up.close()
@@ -1031,7 +1054,8 @@ def batch_rows(streams):
 
 
 def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
-                  filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False):
+                  filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
+                  want_subsample=False):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1066,7 +1090,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 b1 = min(nb, b0 + cap)
                 R = (b1 - b0) * k
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
-                       beam=want_beam)
+                       beam=want_beam, subsample=want_subsample)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)

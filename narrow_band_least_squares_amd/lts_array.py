@@ -28,8 +28,10 @@ def _returns_beam(res, nchans, alpha, keys=None):
     return _returns(res, nchans, alpha, keys) + (res.beam_power[0, :n].copy(), res.fstat[0, :n].copy())
 
 
-def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam):
-    """The one body of ``ltsva`` and ``ltsva_beam``: the checks, the geometry, the device pass, the returns."""
+def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
+           want_subsample=False):
+    """The one body of ``ltsva``, ``ltsva_beam`` and ``ltsva_subsample``: the checks, the geometry, the device pass, the
+    returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
     engine.check_elements(nchans, alpha)
@@ -45,7 +47,8 @@ def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_ar
             res.keys = engine.time_keys(res.t, res.nwin)
 
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
-                         prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam)
+                         prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
+                         want_subsample=want_subsample)
     return (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
 
 
@@ -70,29 +73,50 @@ def ltsva_beam(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
     that line up exactly and NaN for an all-zero window or a slowness that is not finite.  Both are computed on the GPU
     behind each window's solve, from the filtered samples already there.  The first eight returns are ``ltsva``'s.
     Too few elements raise ``ValueError`` here (``ltsva`` keeps the reference's ``RuntimeError``)."""
-    nchans = len(st)
-    if nchans < 3 or (alpha < 1.0 and nchans < 4):
-        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
-                         'squares' % nchans)
+    _check_elements_strict(len(st), alpha)
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, True)
 
 
-def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False):
+def _check_elements_strict(nchans, alpha):
+    if nchans < 3 or (alpha < 1.0 and nchans < 4):
+        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
+                         'squares' % nchans)
+
+
+def _check_flag(name, value):
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError('%s must be True or False, not %r' % (name, value))
+
+
+def ltsva_subsample(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None):
+    """``ltsva`` on lags refined to sub-sample precision: behind the lag pick every pair's lag l gets the vertex offset of
+    the parabola through the raw cross-correlation values at l-1, l, l+1 (clamped to half a sample; 0 where there is no
+    strict maximum, at the ends of the lag range and for windows that are not finite), and the slowness is fitted to
+    ``tau = (lag + frac) / fs`` instead of ``lag / fs`` (DESIGN.md section 13 has the definition).  ``sigma_tau`` then no
+    longer sits on the quantisation floor 1 / (fs sqrt(12)) of whole-sample lags, and the confidence intervals follow.
+    MdCCM and the key text of ``stdict`` are those of ``ltsva``; which pairs LTS drops may differ, as the residuals do.
+    The fractions are computed on the GPU from the filtered samples already there (csrc/refine.hip).  Returns ``ltsva``'s
+    8-tuple.  Too few elements raise ``ValueError`` here (``ltsva`` keeps the reference's ``RuntimeError``)."""
+    _check_elements_strict(len(st), alpha)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, True)
+
+
+def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False,
+                subsample=False):
     """``ltsva`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of 8-tuples,
     element i equal to ``ltsva(streams[i], ...)``.  Every stream must have the same element count, trace length and
     sampling rate, and all share the geometry; ``ValueError`` names a mismatch before any GPU work.  The "ALPHA is
     1.0" message prints once per batch.  An empty sequence gives ``[]``.  ``beam=True``: 10-tuples, element i equal to
-    ``ltsva_beam(streams[i], ...)``."""
-    if not isinstance(beam, (bool, np.bool_)):
-        raise ValueError('beam must be True or False, not %r' % (beam,))
+    ``ltsva_beam(streams[i], ...)``.  ``subsample=True``: element i equal to ``ltsva_subsample(streams[i], ...)``; with both,
+    the beam is steered by the slowness fitted to the refined delays."""
+    _check_flag('beam', beam)
+    _check_flag('subsample', subsample)
     streams = list(streams)
     if not streams:
         return []
     recs, fs, t0s = engine.batch_rows(streams)
     if len(streams) == 1:          # a batch of one IS the single call
-        if beam:
-            return [ltsva_beam(streams[0], lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)]
-        return [ltsva(streams[0], lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)]
+        return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample)]
     nchans = len(recs[0])
     engine.check_elements(nchans, alpha)
     if rij is None:
@@ -100,27 +124,35 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     if alpha == 1.0:
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
-                                   prefiltered=True, want_uncert=True, want_beam=bool(beam))
+                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample))
     return [(_returns_beam if beam else _returns)(res, nchans, alpha) for res in results]
 
 
-def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False):
+def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample):
+    """The single call a batch of one recording / one estimator with nothing removed is: ``ltsva`` itself for the plain
+    one, else the strict element check of ``ltsva_beam`` / ``ltsva_subsample`` and the shared body."""
+    if not beam and not subsample:
+        return ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)
+    _check_elements_strict(len(st), alpha)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample))
+
+
+def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False):
     """``ltsva`` of one (already filtered) stream for several estimators ``(alpha, remove)`` in one GPU pass -> a list of
     ``ltsva``'s 8-tuples, element e equal to ``ltsva`` with ``alpha_e`` on the stream without the traces ``remove_e``
     (0-based, ascending; a bare number means nothing removed; at most 8 estimators).  The windows of the full array are
     correlated once, every window is solved once per estimator.  ``ValueError`` before any GPU work for an empty list, a
     bad alpha or ``remove`` and too few kept elements.  The "ALPHA is 1.0" message prints once per call.  ``beam=True``:
     10-tuples, element e equal to ``ltsva_beam`` on the reduced stream (the beam of estimator e's elements at its
-    slowness)."""
-    if not isinstance(beam, (bool, np.bool_)):
-        raise ValueError('beam must be True or False, not %r' % (beam,))
+    slowness).  ``subsample=True``: the full array's lags are refined once (``ltsva_subsample``) and element e equals
+    ``ltsva_subsample`` on the reduced stream."""
+    _check_flag('beam', beam)
+    _check_flag('subsample', subsample)
     data, fs, _ = engine.stream_rows(st)
     nchans = len(data)
     ests = engine.normalize_estimators(estimators, nchans)
     if len(ests) == 1 and not ests[0][1]:          # one estimator with nothing removed IS the single call
-        if beam:
-            return [ltsva_beam(st, lat_list, lon_list, window_length, window_overlap, alpha=ests[0][0], rij=rij)]
-        return [ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=ests[0][0], rij=rij)]
+        return [_single(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij, beam, subsample)]
     rijs, t0s = [], []
     for _, remove in ests:
         kept = engine.kept_elements(nchans, remove)
@@ -134,7 +166,7 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     if any(a == 1.0 for a, _ in ests):
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_multi(data, fs, t0s, rijs, [(None, None)], [window_length], window_overlap, ests,
-                                   prefiltered=True, want_uncert=True, want_beam=bool(beam))
+                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample))
     keys = {}
     out = []
     for (alpha, _), res in zip(ests, results):

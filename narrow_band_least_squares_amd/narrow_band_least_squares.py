@@ -90,7 +90,7 @@ def _prefix_stdict(stdict, band_number):
 
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
-               key_prefixes=None, want_beam=False):
+               key_prefixes=None, want_beam=False, want_subsample=False):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -128,7 +128,7 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
 
     res = engine.process(rows, fs, t0, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
-                         units_done=units_done, want_beam=want_beam)
+                         units_done=units_done, want_beam=want_beam, want_subsample=want_subsample)
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -182,6 +182,27 @@ def narrow_band_least_squares_beam(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=True)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (res.beam_power, res.fstat)
+
+
+def narrow_band_least_squares_subsample(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                        FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None):
+    """``narrow_band_least_squares`` on lags refined to sub-sample precision (``lts_array.ltsva_subsample``; DESIGN.md
+    section 13): in every band each pair's picked lag gets the vertex offset of the parabola through its three nearest raw
+    cross-correlation values, computed on the GPU behind the lag pick, and the slowness is fitted to the refined delays.
+    Returns ``narrow_band_least_squares``'s nine values; ``t`` and the window counts are the same.  A trace so long that
+    not one filtered band fits the HBM budget of a pass raises ``ValueError`` (the time-segmented path keeps the band on
+    the host)."""
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_subsample=True)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array)
 
 
 def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
