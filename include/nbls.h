@@ -75,7 +75,7 @@ typedef struct {
     double quantize_ms;       /* int8 screening path only: sums over the batches               */
     double screen_ms;         /*   the int8-MFMA screening kernel (dominant kernel)            */
     double verify_ms;         /*   the FP64 verification kernel                                */
-    int32_t xcorr_impl;       /* correlator actually used: 1 VALU, 2 f64 MFMA, 3 int8 screening */
+    int32_t xcorr_impl;       /* correlator actually used: 1 VALU, 2 f64 MFMA, 3 int8 screening, 4 bounded-lag correlator */
     int32_t xcorr_fallback_bands; /* xcorr_impl == 3: bands whose window length does not fit the screening
                                    * kernel's LDS even with partner groups (> ~7900 samples) and ran on a general
                                    * correlator; the other bands of the plan were screened                    */
@@ -261,6 +261,42 @@ int nbls_set_lag_refinement(nbls_handle* h, int32_t on);
 int nbls_refine_lds_bytes(int32_t nelem, int32_t W);
 int nbls_fetch_lag_fraction(nbls_handle* h, double* frac);
 int nbls_est_fetch_lag_fraction(nbls_handle* h, int32_t e, double* frac);
+
+/* Per-pair lag limits: the lag pick of pair k searched only within |lag| <= max_lag[k] samples, the
+ * range a plane wave no slower than v_min can delay that pair (|tau_k| <= |xij_k| / v_min), instead of over all 2W-1 lags —
+ * in a narrow band the correlation is nearly periodic and noise lifts a neighbouring cycle above the true one.  For one unit
+ * and pair k = (i, j), a, b the unit's windows of elements i and j, R(m) = sum_n a[n-m] b[n] over the indices inside [0, W)
+ * (np.correlate(a, b, 'full')[W-1-m], the definition of nbls_set_lag_refinement), max_lag[k] >= 0 and L = min(max_lag[k], W-1):
+ *   lag  = L - np.argmax(cij[W-1-L : W+L]),  cij = np.correlate(a, b, 'full') / sqrt(sum a^2 * sum b^2); quotients are
+ *          compared as the plain pass compares them, and the first maximum in np.correlate index order wins: among equal
+ *          maxima the LARGEST lag
+ *   cmax = R(lag) / sqrt(sum a^2 * sum b^2)
+ *   an all-zero range gives lag = +L, cmax = 0; a dead channel lag = +L, cmax = NaN; windows whose sum of squares is not
+ *          finite (NaN or +-Inf samples) give cmax = NaN and lag = min(the plain pass's lag, L) — NumPy's first NaN of the slice
+ *   max_lag[k] >= W-1 is the full search for that pair: the plain pass's lag
+ * MdCCM, the solve, the uncertainty, beam and refinement kernels read these picks as they read the plain pass's.  The order
+ * of every sum depends on (number of elements, W, the limit table, lag) alone, no atomics are used and nothing depends on
+ * the launch's unit range: single, streamed, batched (nbls_set_segments) and window-sliced passes agree bit for bit.  A
+ * sub-array estimator reads the full array's picks; against a separate call on the sub-array it agrees in lags and weights
+ * exactly and in cmax to 1e-12 (the tile origins differ with the element count).
+ *   nbls_set_lag_limits(h, max_lag, npairs)   the table is copied and read by the next nbls_plan, like nbls_set_beam; max_lag
+ *                            NULL switches it off (the default: a plan without it is launch for launch the plain pass).
+ *                            NBLS_ERR_ARG for a negative entry or npairs < 1, and the handle is then unchanged.  nbls_plan
+ *                            returns NBLS_ERR_ARG if npairs differs from the geometry's, NBLS_ERR_UNSUPPORTED if limits are
+ *                            set and xcorr_impl != 0.  An RCCL communicator, segments, window ranges and estimators are not
+ *                            refused: the result block carries everything that changes.
+ *   nbls_lag_limit_form(nelem, W, min_limit)   a pure host function, like nbls_refine_lds_bytes: the form a window group of
+ *                            W-sample windows of nelem elements takes when the SMALLEST limit of the table is min_limit
+ *                            (values above W-1 count as W-1): 0 the plan's ordinary route — every pair's limit reaches
+ *                            W-1, the full search is the bounded one; 1 the matrix-core form (3..16 elements whose
+ *                            zero-padded windows fit a CU's LDS: the fit rule of NBLS_ROUTE_MFMA); 2 the general form
+ *                            (everything else).  NBLS_ERR_ARG for nelem outside 3..32, W < 2 or min_limit < 0.  The
+ *                            launcher decides through the same function.
+ * A group in form 1 or 2 takes the place a general correlator has in the pass: one launch over the group's units (and one
+ * result batch of a streamed pass), refinement behind it when the plan refines.  nbls_timings.xcorr_impl is 4 for a pass in
+ * which at least one window group ran the bounded-lag correlator; its time falls inside xcorr_ms. */
+int nbls_set_lag_limits(nbls_handle* h, const int32_t* max_lag, int32_t npairs);
+int nbls_lag_limit_form(int32_t nelem, int32_t W, int32_t min_limit);
 
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);

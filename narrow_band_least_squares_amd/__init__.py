@@ -9,8 +9,8 @@ import sys as _sys
 from .narrow_band_least_squares import (narrow_band_least_squares, narrow_band_loop,
                                         narrow_band_least_squares_parallel, narrow_band_least_squares_batch,
                                         narrow_band_least_squares_multi, narrow_band_least_squares_beam,
-                                        narrow_band_least_squares_subsample)
-from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample
+                                        narrow_band_least_squares_subsample, narrow_band_least_squares_bounded)
+from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample, ltsva_bounded
 from .helpers import (get_freqlist, get_winlenlist, filter_data, make_float, get_rij,
                       write_txtfile, read_txtfile)
 from .stream import Stream, Trace, Stats
@@ -20,7 +20,8 @@ __all__ = ['narrow_band_least_squares', 'narrow_band_loop', 'narrow_band_least_s
            'ltsva', 'get_freqlist', 'get_winlenlist', 'filter_data', 'make_float', 'get_rij',
            'write_txtfile', 'read_txtfile', 'Stream', 'Trace', 'Stats', 'install_as_reference_modules', 'resident_trace',
            'narrow_band_least_squares_batch', 'ltsva_batch', 'narrow_band_least_squares_multi', 'ltsva_multi',
-           'narrow_band_least_squares_beam', 'ltsva_beam', 'narrow_band_least_squares_subsample', 'ltsva_subsample']
+           'narrow_band_least_squares_beam', 'ltsva_beam', 'narrow_band_least_squares_subsample', 'ltsva_subsample',
+           'narrow_band_least_squares_bounded', 'ltsva_bounded']
 
 
 def install_as_reference_modules():

@@ -26,6 +26,7 @@ EXPORTS = [
     'nbls_est_fetch_packed', 'nbls_est_fetch', 'nbls_est_fetch_uncertainty', 'nbls_est_wait_result_batch',
     'nbls_set_beam', 'nbls_fetch_beam', 'nbls_est_fetch_beam',
     'nbls_set_lag_refinement', 'nbls_fetch_lag_fraction', 'nbls_est_fetch_lag_fraction', 'nbls_refine_lds_bytes',
+    'nbls_set_lag_limits', 'nbls_lag_limit_form',
 ]
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
@@ -149,6 +150,8 @@ def load_library(path=None):
     lib.nbls_fetch_lag_fraction.argtypes = [vp, dp]
     lib.nbls_refine_lds_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.nbls_est_fetch_lag_fraction.argtypes = [vp, C.c_int32, dp]
+    lib.nbls_set_lag_limits.argtypes = [vp, ip, C.c_int32]
+    lib.nbls_lag_limit_form.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -511,6 +514,15 @@ class Handle:
             self._chk(self.lib.nbls_est_fetch_lag_fraction(self._h, int(e), _dptr(out)))
         return out
 
+    def set_lag_limits(self, max_lag=None):
+        """The next plans search the lag of pair k only within ``|lag| <= max_lag[k]`` samples (``nbls_set_lag_limits``,
+        DESIGN.md section 14; ``planner.lag_limits`` makes the table); None switches that off."""
+        if max_lag is None:
+            self._chk(self.lib.nbls_set_lag_limits(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(max_lag, dtype=np.int32).ravel()
+        self._chk(self.lib.nbls_set_lag_limits(self._h, _iptr(t), len(t)))
+
     def stream_results(self, on=True):
         """The next passes deliver their rows batch by batch into a pinned host mirror of the result block
         (``nbls_stream_results``); see ``result_batches`` / ``wait_result_batch``."""
@@ -619,6 +631,15 @@ def refine_lds_bytes(nelem, W):
     rc = load_library().nbls_refine_lds_bytes(int(nelem), int(W))
     if rc < 0:
         raise ValueError('nbls_refine_lds_bytes: bad arguments')
+    return int(rc)
+
+
+def lag_limit_form(nelem, W, min_limit):
+    """The form a window group of W-sample windows of ``nelem`` elements takes under lag limits whose smallest is
+    ``min_limit`` (``nbls_lag_limit_form``): 0 the plan's ordinary route, 1 the matrix-core form, 2 the general form."""
+    rc = load_library().nbls_lag_limit_form(int(nelem), int(W), int(min(int(min_limit), 2 ** 31 - 1)))
+    if rc < 0:
+        raise ValueError('nbls_lag_limit_form: arguments out of range')
     return int(rc)
 
 

@@ -764,6 +764,14 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
     if (h->want_beam && h->comm)
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: beam results (nbls_set_beam) are not supported with an RCCL communicator (the gathered block does not carry them)");
+    if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
+        if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
+                                             std::to_string(h->est[0].d_xij ? h->npairs : 0) + " pairs");
+        if (a.xcorr_impl != 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: lag limits (nbls_set_lag_limits) need xcorr_impl 0: the forced correlators search every lag");
+    }
+    h->lim = h->want_lim;
     h->beam = h->want_beam;
     h->beam_valid = false;
     h->refine = h->want_refine;
@@ -950,6 +958,17 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
     h->wgroups.clear();
     int maxWP = 0;
     bool all_ok = true, any_ok = false;
+    const int32_t min_lim = h->lim.empty() ? 0 : *std::min_element(h->lim.begin(), h->lim.end());
+    if (!h->lim.empty()) {
+        const int E = h->nelem;
+        std::vector<int32_t> sq((size_t)E * E, 0);
+        for (int k = 0; k < h->npairs; ++k) {
+            const int i = h->h_pair[2 * k], j = h->h_pair[2 * k + 1];
+            if (i < 0 || j < 0 || i >= E || j >= E) return fail(h, NBLS_ERR_ARG, "nbls_plan: a pair of the geometry names an element the trace does not have");
+            sq[(size_t)i * E + j] = sq[(size_t)j * E + i] = h->lim[(size_t)k];
+        }
+        if (int rc = alloc_copy(h, h->d_limsq, sq.data(), sq.size())) return rc;
+    }
     for (int b = 0; b < R; ) {
         int e = b + 1;
         while (e < R && h->W[e] == h->W[b]) ++e;
@@ -957,6 +976,10 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
         nbls_route r;                               // (xcorr_route.hip: the launchers take the same route)
         nbls_route_compute(nbls_route_query_of(h, g.W, R, 3, false), &r);
         g.screen = h->est[0].d_xij && r.correlator == NBLS_ROUTE_SCREEN;
+        // a plan with lag limits: a group whose windows are longer than the smallest limit takes the bounded-lag correlator
+        // in the general correlators' slot; where every limit reaches W-1 the full search is the bounded one
+        if (!h->lim.empty()) g.bform = nbls_lag_limit_form_of(h->nelem, g.W, std::min(min_lim, g.W - 1));
+        if (g.bform) { g.screen = false; h->wgroups.push_back(g); b = e; continue; }
         if (g.screen) { any_ok = true; if (r.WP > maxWP) maxWP = r.WP; }
         else if (g.u1 > g.u0) all_ok = false;
         h->wgroups.push_back(g);
@@ -1377,6 +1400,21 @@ int nbls_set_lag_refinement(nbls_handle* h, int32_t on) {
     if (!h) return NBLS_ERR_ARG;
     h->want_refine = on != 0;                // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
+}
+
+int nbls_set_lag_limits(nbls_handle* h, const int32_t* max_lag, int32_t npairs) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!max_lag) { h->want_lim.clear(); return NBLS_OK; }      // off: the next plan searches every lag
+    if (npairs < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_limits: npairs must be at least 1");
+    for (int32_t k = 0; k < npairs; ++k)                         // everything is checked before the handle changes
+        if (max_lag[k] < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_limits: negative limit of pair " + std::to_string(k));
+    h->want_lim.assign(max_lag, max_lag + npairs);               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    return NBLS_OK;
+}
+
+int nbls_lag_limit_form(int32_t nelem, int32_t W, int32_t min_limit) {
+    if (nelem < 3 || nelem > 32 || W < 2 || min_limit < 0) return NBLS_ERR_ARG;
+    return nbls_lag_limit_form_of(nelem, W, min_limit);
 }
 
 int nbls_refine_lds_bytes(int32_t nelem, int32_t W) {

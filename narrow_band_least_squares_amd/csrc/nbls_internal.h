@@ -57,7 +57,10 @@ struct nbls_options {
 };
 
 // Consecutive bands of one window length: the unit of the correlator choice (nbls_plan / nbls_launch_xcorr).
-struct nbls_wgroup { int b0, b1, W; int64_t u0, u1; bool screen; };
+struct nbls_wgroup {
+    int b0, b1, W; int64_t u0, u1; bool screen;
+    int bform = 0;     // a plan with lag limits (nbls_set_lag_limits): 0 the ordinary route, 1 / 2 the form of the bounded-lag correlator
+};
 
 // One estimator of a pass: the geometry and LTS plan of ONE array (the full one or a sub-array) as the caller described
 // them, the device tables nbls_plan makes of them, and the buffers of its own results.  The handle holds 1 + 8 of these
@@ -131,6 +134,9 @@ struct nbls_handle {
     bool refine = false;            // the plan refines the picked lags to sub-sample precision behind the verifier (refine.hip)
     bool frac_valid = false;        // a pass of this plan has run the correlation stage: d_lagfrac holds results
     bool solve_ran = false;         // a pass of this plan has run the solve stage (a sub-array's compact rows are gathered there)
+    std::vector<int32_t> want_lim;  // nbls_set_lag_limits: [npairs] max_lag per pair, read by the next nbls_plan (empty: off)
+    std::vector<int32_t> lim;       // the plan's copy (empty: the plan searches every lag)
+    dev_buf<int32_t> d_limsq;       // [nelem][nelem] the plan's limit of the pair of two elements, symmetric, 0 on the diagonal
     bool refine_attr_set = false;   // the LDS form of refine_lag_kernel has been given its dynamic LDS limit on this handle's device
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
@@ -254,7 +260,7 @@ struct nbls_handle {
     std::vector<hipEvent_t> bev;   // per-batch events of the screening path (5 per batch: quantize | screen | verify | solve)
     int bev_used = 0;
     bool prof_fused = false;       // the last profiled pass ran its solves per batch (bev[5k+4] recorded)
-    int xcorr_impl_used = 0;       // 1 VALU, 2 f64 MFMA, 3 int8 screening
+    int xcorr_impl_used = 0;       // 1 VALU, 2 f64 MFMA, 3 int8 screening, 4 bounded-lag correlator (at least one window group)
     nbls_timings tim{};
 };
 
@@ -300,4 +306,8 @@ void nbls_route_compute(const nbls_route_query& q, nbls_route* r);
 nbls_route_query nbls_route_query_of(const nbls_handle* h, int W, int vrows, int impl, bool no_screen);
 hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue, int gW, int64_t* launches_io);
 hipError_t nbls_xcorr_screen_finish(nbls_handle* h, int64_t launches);
+// bounded-lag correlator (xcorr_bounded.hip): the form a window group takes (nbls_lag_limit_form is its C ABI form;
+// min_limit: the smallest limit of the table) and the launch of units [ub, ue) of a group in form 1 / 2
+int nbls_lag_limit_form_of(int nelem, int W, int min_limit);
+hipError_t nbls_launch_xcorr_bounded(nbls_handle* h, int64_t ub, int64_t ue, int gW, int form);
 hipError_t nbls_launch_probe_mfma_i8(nbls_handle* h, const int* da, const int* db, int* dout);

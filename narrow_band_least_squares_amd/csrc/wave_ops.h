@@ -82,6 +82,12 @@ __device__ inline int nonfinite_argmax(const double* xa, const double* xb, int W
     if (last_b >= 0 && W - 1 - last_b < k) k = W - 1 - last_b;
     return k == 0x7fffffff ? 0 : k;
 }
+// The same for a search restricted to |lag| <= L (np.correlate indices W-1-L .. W-1+L; xcorr_bounded.hip): the first NaN of
+// the slice.  Every non-finite sample's index range contains the centre index W-1, so the range that starts at the full
+// search's index k reaches into the slice whenever k lies in front of it: max(k, W-1-L), i.e. lag = min(plain lag, L).
+__device__ inline int nonfinite_argmax_clamped(const double* xa, const double* xb, int W, int L, int lane) {
+    return max(nonfinite_argmax(xa, xb, W, lane), W - 1 - L);
+}
 __device__ inline bool finite_f64(double v) { return fabs(v) < __builtin_inf(); }   // false for NaN and +-Inf
 
 // Arg-max order of the reference for one pair: np.argmax(np.correlate(a, b, 'full') / norm) compares the QUOTIENTS, the

@@ -335,7 +335,7 @@ hipError_t nbls_launch_xcorr(nbls_handle* h) {
     h->bev_used = 0;
     int64_t launches = 0;
     int used = 0, fallback_bands = 0;
-    bool any_screen = false;
+    bool any_screen = false, any_bounded = false;
     for (const nbls_wgroup& g : h->wgroups) {
         if (g.u1 <= g.u0) continue;
         hipError_t e;
@@ -343,10 +343,15 @@ hipError_t nbls_launch_xcorr(nbls_handle* h) {
             any_screen = true;
             e = nbls_launch_xcorr_screen_range(h, g.u0, g.u1, g.W, &launches);
         } else {
-            int u_ = 0;
-            e = launch_general_range(h, g.u0, g.u1, g.W, h->xcorr_impl == 3 ? 0 : h->xcorr_impl, &u_);
-            used = u_ > used ? u_ : used;
-            fallback_bands += g.b1 - g.b0;
+            if (g.bform) {       // a plan with lag limits: the bounded-lag correlator in the general correlators' slot
+                any_bounded = true;
+                e = nbls_launch_xcorr_bounded(h, g.u0, g.u1, g.W, g.bform);
+            } else {
+                int u_ = 0;
+                e = launch_general_range(h, g.u0, g.u1, g.W, h->xcorr_impl == 3 ? 0 : h->xcorr_impl, &u_);
+                used = u_ > used ? u_ : used;
+                fallback_bands += g.b1 - g.b0;
+            }
             if (h->xcorr_impl != 3) ++launches;
             // per-batch solves (nbls_execute_stages: fuse_solve): a window group that does not take the screening path
             // is one batch of its own — without this its units were never solved (nbls_xcorr_screen_finish marks the
@@ -359,11 +364,11 @@ hipError_t nbls_launch_xcorr(nbls_handle* h) {
         if (e != hipSuccess) return e;
     }
     if (h->xcorr_impl == 3 && (any_screen || h->fuse_solve)) {
-        h->xcorr_impl_used = 3;
+        h->xcorr_impl_used = any_bounded ? 4 : 3;
         h->tim.xcorr_fallback_bands = fallback_bands;          // bands of this pass that ran on a general correlator
         return nbls_xcorr_screen_finish(h, launches);
     }
-    h->xcorr_impl_used = used;
+    h->xcorr_impl_used = any_bounded ? 4 : used;
     h->tim.xcorr_launches = launches;
     return hipGetLastError();
 }

@@ -456,14 +456,19 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
-                      host_overlap=None, group_done=None, want_beam=False, want_subsample=False):
+                      host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
     (the ``ltsva`` entry of the device pass).  Same rows as the in-core pass up to the rounding of the carried filter
     states; HBM holds one segment / one window slice at a time.  The filtered band stays on the host and the windows reach
     the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``; nor is
-    the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM."""
+    the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM, nor the bounded lag
+    search (``min_velocity``)."""
+    if min_velocity is not None:
+        raise ValueError('min_velocity: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
+                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which correlates the band slice by slice: '
+                         'the bounded lag search is not available there' % _shape_of(data))
     if want_subsample:
         raise ValueError('want_subsample: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -567,7 +572,7 @@ def upload_trace(h, data, fs):
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False):
+           subsample=False, lag_limits=None):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -576,7 +581,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     execute (the caller joins its upload thread there).  ``estimators``: the further estimators of the pass
     (``Handle.set_estimators``); a handle that still carries some from an earlier call is reset.  ``beam``: the plan also
     computes beam power and F-statistic behind every solve (``Handle.set_beam``; for this plan only).  ``subsample``: the
-    plan refines the picked lags to sub-sample precision before the solve (``Handle.set_lag_refinement``; likewise)."""
+    plan refines the picked lags to sub-sample precision before the solve (``Handle.set_lag_refinement``; likewise).
+    ``lag_limits``: the plan searches the lag of pair k only within ``|lag| <= lag_limits[k]`` samples
+    (``Handle.set_lag_limits``, ``planner.lag_limits``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -600,6 +607,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_beam(True)
     if subsample:
         h.set_lag_refinement(True)
+    if lag_limits is not None:
+        h.set_lag_limits(lag_limits)
     try:
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
@@ -608,6 +617,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_beam(False)            # (the handle is shared with calls that plan for themselves)
         if subsample:
             h.set_lag_refinement(False)
+        if lag_limits is not None:
+            h.set_lag_limits(None)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -784,7 +795,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
-            want_uncert=False, want_beam=False, want_subsample=False):
+            want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -800,6 +811,9 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     want_subsample=True: every picked lag is refined to sub-sample precision behind its verifier and the solve reads
     ``tau = (lag + frac) / fs`` (``nbls_set_lag_refinement``); with ``want_lag`` also ``res.lag_frac``
     (nbands, vector_len, P) beside ``res.lag``; ``process_segmented`` refuses it.
+    min_velocity (km/s): every pair's lag is searched only within the range a plane wave no slower than that can delay the
+    pair (``planner.lag_limits``, ``nbls_set_lag_limits``); ``ValueError`` before any GPU work unless
+    it is a finite real > 0; ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -818,6 +832,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
        while the GPU works on the next one —; without it ``group_done(res, b0, b1)`` runs for the bands a batch or a
        group completes (the caller builds its dictionary there).  Rounds collected in step 4 are reported after step 5."""
     nchans, npts = _shape_of(data)
+    limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij)[0], fs, min_velocity)
     cap = max_bands_per_pass(nchans, npts)
     single = prefiltered or handle is not None or not upload
     up, resident = start_upload(data, fs, device) if upload and handle is None and (cap >= 1 or prefiltered) else (None, False)
@@ -827,7 +842,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam, want_subsample)
+                                     group_done, want_beam, want_subsample, min_velocity)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample)
@@ -836,7 +851,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
-                                 subsample=want_subsample)
+                                 subsample=want_subsample, lag_limits=limits)
     finally:
         if up is not None:
             up.close()
@@ -926,7 +941,8 @@ class _EstimatorResults:
 
 def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_lag=False,
-                  want_cmax=False, host_overlap=None, units_done=None, want_beam=False, want_subsample=False):
+                  want_cmax=False, host_overlap=None, units_done=None, want_beam=False, want_subsample=False,
+                  min_velocity=None):
     """``process`` for several estimators ``(alpha, remove)`` of ONE trace in one device pass -> a list of ``BandBatch``,
     element e what ``process`` gives for ``alpha_e`` on the rows that ``remove_e`` leaves (``estimators`` as
     ``normalize_estimators`` returns them; ``rijs[e]``: the (2, kept) geometry of estimator e, ``t0s[e]`` its start date).
@@ -940,7 +956,8 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     ``drain``.  ``host_overlap(results)`` runs once the first pass is queued; ``units_done(e, res, u0, u1)`` when the
     units [u0, u1) (flat over all bands) of estimator e are in ``results[e]``.  ``want_beam``: every estimator's
     ``beam_power`` / ``fstat``, of ITS elements at ITS slowness (``process``).  ``want_subsample``: the pass refines the full
-    array's lags once and every estimator solves on the refined delays of ITS pairs (``lag_frac`` with ``want_lag``)."""
+    array's lags once and every estimator solves on the refined delays of ITS pairs (``lag_frac`` with ``want_lag``).
+    ``min_velocity``: the full array's lags are searched within their physical range (``process``); a sub-array reads them."""
     rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
     nchans, npts = _shape_of(rows)
     nb = len(band_edges)
@@ -953,6 +970,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     alpha0 = estimators[full][0] if full is not None else 1.0
     rij0 = rijs[full] if full is not None else rijs[-1]        # (no full-array estimator: ``rijs`` ends with the full geometry)
     first_est = 0 if full is not None else 1                   # device index of order[0]
+    limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij0)[0], fs, min_velocity)
     extras = []
     for i in (order[1:] if full is not None else order):
         alpha, remove = estimators[i]
@@ -983,7 +1001,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
             try:
                 launch(h, rows, prep, trace_ready=joins or resident or b0 > 0, stream=streamed, uncert=want_uncert,
                        before_execute=up.landed if (joins and not up.row_pipeline) else None, estimators=extras,
-                       beam=want_beam, subsample=want_subsample)
+                       beam=want_beam, subsample=want_subsample, lag_limits=limits)
             finally:
                 if joins:
                     up.landed()
@@ -1055,7 +1073,7 @@ def batch_rows(streams):
 
 def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
-                  want_subsample=False):
+                  want_subsample=False, min_velocity=None):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1072,6 +1090,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     prep = prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type, filter_order, filter_ripple,
                    vector_len, prefiltered)
     VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
+    limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
     per_sub = S if max_bands_per_pass(S * nchans, npts) >= 1 else max_bands_per_pass(nchans, npts)
     if per_sub < 1:
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
@@ -1090,7 +1109,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 b1 = min(nb, b0 + cap)
                 R = (b1 - b0) * k
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
-                       beam=want_beam, subsample=want_subsample)
+                       beam=want_beam, subsample=want_subsample, lag_limits=limits)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)

@@ -5,7 +5,7 @@ summarised in SURVEY.md §3.3).
 """
 import numpy as np
 
-from . import engine
+from . import engine, planner
 from .helpers import get_rij
 
 
@@ -29,9 +29,9 @@ def _returns_beam(res, nchans, alpha, keys=None):
 
 
 def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
-           want_subsample=False):
-    """The one body of ``ltsva``, ``ltsva_beam`` and ``ltsva_subsample``: the checks, the geometry, the device pass, the
-    returns."""
+           want_subsample=False, min_velocity=None):
+    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample`` and ``ltsva_bounded``: the checks, the geometry, the
+    device pass, the returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
     engine.check_elements(nchans, alpha)
@@ -48,7 +48,7 @@ def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_ar
 
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
                          prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
-                         want_subsample=want_subsample)
+                         want_subsample=want_subsample, min_velocity=min_velocity)
     return (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
 
 
@@ -101,22 +101,40 @@ def ltsva_subsample(st, lat_list, lon_list, window_length, window_overlap, alpha
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, True)
 
 
+def ltsva_bounded(st, lat_list, lon_list, window_length, window_overlap, min_velocity, alpha=1.0, rij=None):
+    """``ltsva`` with every pair's lag searched only within its physical range: ``|lag_k| <= L_k`` samples,
+    ``L_k = ceil(fs |xij_k| / min_velocity) + 1`` (``planner.lag_limits``), the delay a plane wave no slower than
+    ``min_velocity`` km/s can put between the pair's elements plus one sample of guard, instead of over all 2W-1 lags.  In
+    a narrow band the correlation is nearly periodic and noise lifts a neighbouring cycle above the true one; such
+    cycle-skipped picks land outside the range and are the outliers the fit then has to survive (DESIGN.md section 14 has
+    the definition and the counts).  The pick, its ``cmax`` (so MdCCM) and everything fitted to it follow the restricted
+    search; the search runs on the GPU (csrc/xcorr_bounded.hip).  Returns ``ltsva``'s 8-tuple.  ``min_velocity`` must be a
+    finite real > 0 and too few elements raise ``ValueError`` before any GPU work."""
+    planner.check_min_velocity(min_velocity)
+    _check_elements_strict(len(st), alpha)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, min_velocity)
+
+
 def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False,
-                subsample=False):
+                subsample=False, min_velocity=None):
     """``ltsva`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of 8-tuples,
     element i equal to ``ltsva(streams[i], ...)``.  Every stream must have the same element count, trace length and
     sampling rate, and all share the geometry; ``ValueError`` names a mismatch before any GPU work.  The "ALPHA is
     1.0" message prints once per batch.  An empty sequence gives ``[]``.  ``beam=True``: 10-tuples, element i equal to
     ``ltsva_beam(streams[i], ...)``.  ``subsample=True``: element i equal to ``ltsva_subsample(streams[i], ...)``; with both,
-    the beam is steered by the slowness fitted to the refined delays."""
+    the beam is steered by the slowness fitted to the refined delays.  ``min_velocity`` (km/s, default None: every lag):
+    the lags are searched within their physical range as in ``ltsva_bounded``; it combines with both flags, the fractions
+    and the beam then follow the bounded picks."""
     _check_flag('beam', beam)
     _check_flag('subsample', subsample)
+    if min_velocity is not None:
+        planner.check_min_velocity(min_velocity)
     streams = list(streams)
     if not streams:
         return []
     recs, fs, t0s = engine.batch_rows(streams)
     if len(streams) == 1:          # a batch of one IS the single call
-        return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample)]
+        return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity)]
     nchans = len(recs[0])
     engine.check_elements(nchans, alpha)
     if rij is None:
@@ -124,20 +142,23 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     if alpha == 1.0:
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
-                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample))
+                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
+                                   min_velocity=min_velocity)
     return [(_returns_beam if beam else _returns)(res, nchans, alpha) for res in results]
 
 
-def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample):
+def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity=None):
     """The single call a batch of one recording / one estimator with nothing removed is: ``ltsva`` itself for the plain
     one, else the strict element check of ``ltsva_beam`` / ``ltsva_subsample`` and the shared body."""
-    if not beam and not subsample:
+    if not beam and not subsample and min_velocity is None:
         return ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)
     _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample))
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample),
+                  min_velocity)
 
 
-def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False):
+def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False,
+                min_velocity=None):
     """``ltsva`` of one (already filtered) stream for several estimators ``(alpha, remove)`` in one GPU pass -> a list of
     ``ltsva``'s 8-tuples, element e equal to ``ltsva`` with ``alpha_e`` on the stream without the traces ``remove_e``
     (0-based, ascending; a bare number means nothing removed; at most 8 estimators).  The windows of the full array are
@@ -145,14 +166,17 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     bad alpha or ``remove`` and too few kept elements.  The "ALPHA is 1.0" message prints once per call.  ``beam=True``:
     10-tuples, element e equal to ``ltsva_beam`` on the reduced stream (the beam of estimator e's elements at its
     slowness).  ``subsample=True``: the full array's lags are refined once (``ltsva_subsample``) and element e equals
-    ``ltsva_subsample`` on the reduced stream."""
+    ``ltsva_subsample`` on the reduced stream.  ``min_velocity`` (km/s, default None): the full array's lags are searched
+    within their physical range once (``ltsva_bounded``) and every estimator reads the picks of its pairs."""
     _check_flag('beam', beam)
     _check_flag('subsample', subsample)
+    if min_velocity is not None:
+        planner.check_min_velocity(min_velocity)
     data, fs, _ = engine.stream_rows(st)
     nchans = len(data)
     ests = engine.normalize_estimators(estimators, nchans)
     if len(ests) == 1 and not ests[0][1]:          # one estimator with nothing removed IS the single call
-        return [_single(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij, beam, subsample)]
+        return [_single(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij, beam, subsample, min_velocity)]
     rijs, t0s = [], []
     for _, remove in ests:
         kept = engine.kept_elements(nchans, remove)
@@ -166,7 +190,8 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     if any(a == 1.0 for a, _ in ests):
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_multi(data, fs, t0s, rijs, [(None, None)], [window_length], window_overlap, ests,
-                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample))
+                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
+                                   min_velocity=min_velocity)
     keys = {}
     out = []
     for (alpha, _), res in zip(ests, results):

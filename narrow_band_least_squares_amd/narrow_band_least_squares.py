@@ -90,7 +90,7 @@ def _prefix_stdict(stdict, band_number):
 
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
-               key_prefixes=None, want_beam=False, want_subsample=False):
+               key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -128,7 +128,8 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
 
     res = engine.process(rows, fs, t0, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
-                         units_done=units_done, want_beam=want_beam, want_subsample=want_subsample)
+                         units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
+                         min_velocity=min_velocity)
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -201,6 +202,29 @@ def narrow_band_least_squares_subsample(WINLEN_list, WINOVER, ALPHA, st, lat_lis
                                        FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
                                        FILTER_RIPPLE, vector_len, rij=rij,
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_subsample=True)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array)
+
+
+def narrow_band_least_squares_bounded(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                      FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                      min_velocity):
+    """``narrow_band_least_squares`` with every pair's lag searched only within its physical range
+    (``lts_array.ltsva_bounded``): in every band ``|lag_k| <= ceil(fs |xij_k| / min_velocity) + 1``
+    samples instead of all 2W-1 lags, on the GPU (csrc/xcorr_bounded.hip).  Returns ``narrow_band_least_squares``'s nine
+    values; ``t`` and the window counts are the same.  ``min_velocity`` (km/s) must be a finite real > 0: ``ValueError``
+    before any GPU work.  A trace so long that not one filtered band fits the HBM budget of a pass raises ``ValueError``
+    (the time-segmented path correlates the band slice by slice)."""
+    planner.check_min_velocity(min_velocity)
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], min_velocity=min_velocity)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array)
 

@@ -440,3 +440,24 @@ def uncertainty_frame(xij):
     evals, evecs = np.linalg.eigh(xij.T @ xij)
     ang = np.arccos(np.clip(evecs[0, 0], -1.0, 1.0))
     return np.array([evals[0], evals[1], np.cos(ang), np.sin(ang), -np.sin(ang), np.cos(ang)])
+
+
+def check_min_velocity(min_velocity):
+    """``min_velocity`` (km/s) of the bounded lag search -> float; ``ValueError`` unless it is a finite real > 0 (not a bool)."""
+    if isinstance(min_velocity, (bool, np.bool_)) or not isinstance(min_velocity, (int, float, np.integer, np.floating)):
+        raise ValueError('min_velocity must be a finite number of km/s above 0, not %r' % (min_velocity,))
+    v = float(min_velocity)
+    if not np.isfinite(v) or v <= 0.0:
+        raise ValueError('min_velocity must be a finite number of km/s above 0, not %r' % (min_velocity,))
+    return v
+
+
+def lag_limits(xij, fs, min_velocity):
+    """Per-pair lag limits of the bounded search (``nbls_set_lag_limits``) -> int32 (P,):
+    ``L_k = int(ceil(fs * hypot(xij[k, 0], xij[k, 1]) / min_velocity)) + 1`` samples — the delay a plane wave no slower
+    than ``min_velocity`` km/s can put between the two elements of pair k, plus one sample of guard for the lag's own
+    quantisation.  A sub-array needs no table of its own: its pairs are a subset of the full array's with the same ``xij``."""
+    v = check_min_velocity(min_velocity)
+    xij = np.asarray(xij, dtype=np.float64)
+    L = np.ceil(float(fs) * np.hypot(xij[:, 0], xij[:, 1]) / v) + 1.0
+    return np.minimum(L, 2.0 ** 31 - 1).astype(np.int32)
