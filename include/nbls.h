@@ -298,6 +298,53 @@ int nbls_est_fetch_lag_fraction(nbls_handle* h, int32_t e, double* frac);
 int nbls_set_lag_limits(nbls_handle* h, const int32_t* max_lag, int32_t npairs);
 int nbls_lag_limit_form(int32_t nelem, int32_t W, int32_t min_limit);
 
+/* Slowness-grid search of the beam F-statistic: per window, the delay-and-sum beam of the plan's full
+ * array steered over G caller-given slowness vectors, and the vector with the largest Fisher ratio — the estimate that does
+ * not rest on pairwise lag picks.  grid[G][2] is in s/km, in the (z0, z1) convention of the solved z of nbls_fetch,
+ * 1 <= G <= 65536 (NBLS_BEAM_GRID_MAX).  N = nelem, every element of the row's recording; the geometry's first N-1 pairs are
+ * the pairs (0, i).
+ *   delays   once per plan: d[g][0] = 0, d[g][i] = rint(fs * (xij[i-1][0] s_g0 + xij[i-1][1] s_g1)), un-fused IEEE double,
+ *            ties to even; the sign is nbls_set_beam's: element i is read at +d_i.  H = max |d[g][i]| is the plan's halo.
+ *   samples  for the unit of result row r, window w (start s0 = w * wininc, length W) and grid point g:
+ *            x_i[t] = filt[row of element i][s0 + t + d[g][i]] for t in [0, W), 0.0 where the index is outside [0, npts)
+ *   sums     b[t] = sum_i x_i[t], S_b = sum_t b[t]^2, S_t = sum_t sum_i x_i[t]^2, D = N S_t - S_b
+ *   values   F(g) = (N - 1) S_b / D; F(g) = +inf if D <= 0 and S_b > 0; F(g) = NaN if S_t == 0 or a NaN sample was read;
+ *            P(g) = S_b / (N^2 W)
+ *   outputs  grid_index (int32): the g with the largest F under the total order "F descending (+inf first), g ascending";
+ *            NaN values of F are not candidates; -1 if no g has a non-NaN F.  grid_fstat = F(grid_index), grid_power =
+ *            P(grid_index), both NaN when the index is -1.  The map, if the plan asked: every F(g); grid_fstat is bit-equal
+ *            to the map's entry at grid_index.  Cells beyond nwin[r] (and outside a window slice) are zeros.
+ * One wave sums one (unit, grid point): the order of every sum depends on (N, W) alone, the arg-max is a total order, no
+ * atomics are used and nothing depends on the launch's unit range: single, streamed, batched (nbls_set_segments) and
+ * window-sliced passes agree bit for bit, and grid points with identical delay rows give identical bits.
+ *   nbls_set_beam_grid(h, grid, G, want_map)   the grid is copied and read by the next nbls_plan, like nbls_set_beam; grid
+ *                            NULL switches the search off (the default: a plan without it is launch for launch the plain
+ *                            pass).  NBLS_ERR_ARG for G outside 1..65536 or an entry that is not finite, and the handle is
+ *                            then unchanged.  nbls_plan returns NBLS_ERR_ARG if some |fs xij . s_g| is at least 2^30,
+ *                            NBLS_ERR_STATE without the geometry, NBLS_ERR_UNSUPPORTED with an RCCL communicator (the
+ *                            gathered block does not carry the grids).  Further estimators (nbls_set_estimators) get no
+ *                            grid results: the search is over the full array, behind estimator 0's solve.
+ *   nbls_fetch_beam_grid(h, index, fstat, power)   [rows][vector_len] each (any may be NULL), rows as for nbls_fetch; waits
+ *                            for the pass like nbls_fetch_beam.  NBLS_ERR_STATE if the plan did not ask for the search.
+ *   nbls_fetch_beam_grid_map(h, map)   [rows][vector_len][G]; NBLS_ERR_STATE if the plan did not ask for the map.
+ *   nbls_fetch_beam_grid_delays(h, d)  [G][nelem] int32, the plan's own delay table.
+ *                            The grids and the map are written by the solve stage alone: zeros until a pass of the plan
+ *                            has run it, and nbls_execute_stages without the solve bit leaves them as they are.
+ *   nbls_beam_grid_lds_bytes(nelem, W, halo)   a pure host function, like nbls_refine_lds_bytes: which of its two forms the
+ *                            kernel takes for windows of up to W samples of nelem elements under a halo of `halo` samples:
+ *                            the dynamic LDS bytes of the form that stages the unit's rows over [s0 - H, s0 + W + H) in LDS
+ *                            (nelem * (W + 2 halo) * 8, up to 156 KiB), or 0 for the form that reads them from global
+ *                            memory.  Both give the same bits.  NBLS_ERR_ARG for nelem < 1, W < 1 or halo < 0.  A workgroup
+ *                            has NBLS_BEAM_GRID_WAVES waves; wave j takes the grid points j, j + NBLS_BEAM_GRID_WAVES, ...
+ * nbls_timings is unchanged: the kernel's time falls inside the solve interval. */
+#define NBLS_BEAM_GRID_MAX 65536
+#define NBLS_BEAM_GRID_WAVES 16
+int nbls_set_beam_grid(nbls_handle* h, const double* grid, int32_t G, int32_t want_map);
+int nbls_beam_grid_lds_bytes(int32_t nelem, int32_t W, int32_t halo);
+int nbls_fetch_beam_grid(nbls_handle* h, int32_t* index, double* fstat, double* power);
+int nbls_fetch_beam_grid_map(nbls_handle* h, double* map);
+int nbls_fetch_beam_grid_delays(nbls_handle* h, int32_t* d);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

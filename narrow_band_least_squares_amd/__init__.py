@@ -9,8 +9,9 @@ import sys as _sys
 from .narrow_band_least_squares import (narrow_band_least_squares, narrow_band_loop,
                                         narrow_band_least_squares_parallel, narrow_band_least_squares_batch,
                                         narrow_band_least_squares_multi, narrow_band_least_squares_beam,
-                                        narrow_band_least_squares_subsample, narrow_band_least_squares_bounded)
-from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample, ltsva_bounded
+                                        narrow_band_least_squares_subsample, narrow_band_least_squares_bounded,
+                                        narrow_band_least_squares_grid)
+from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample, ltsva_bounded, ltsva_grid
 from .helpers import (get_freqlist, get_winlenlist, filter_data, make_float, get_rij,
                       write_txtfile, read_txtfile)
 from .stream import Stream, Trace, Stats
@@ -21,7 +22,7 @@ __all__ = ['narrow_band_least_squares', 'narrow_band_loop', 'narrow_band_least_s
            'write_txtfile', 'read_txtfile', 'Stream', 'Trace', 'Stats', 'install_as_reference_modules', 'resident_trace',
            'narrow_band_least_squares_batch', 'ltsva_batch', 'narrow_band_least_squares_multi', 'ltsva_multi',
            'narrow_band_least_squares_beam', 'ltsva_beam', 'narrow_band_least_squares_subsample', 'ltsva_subsample',
-           'narrow_band_least_squares_bounded', 'ltsva_bounded']
+           'narrow_band_least_squares_bounded', 'ltsva_bounded', 'narrow_band_least_squares_grid', 'ltsva_grid']
 
 
 def install_as_reference_modules():

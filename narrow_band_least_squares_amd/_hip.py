@@ -27,7 +27,11 @@ EXPORTS = [
     'nbls_set_beam', 'nbls_fetch_beam', 'nbls_est_fetch_beam',
     'nbls_set_lag_refinement', 'nbls_fetch_lag_fraction', 'nbls_est_fetch_lag_fraction', 'nbls_refine_lds_bytes',
     'nbls_set_lag_limits', 'nbls_lag_limit_form',
+    'nbls_set_beam_grid', 'nbls_fetch_beam_grid', 'nbls_fetch_beam_grid_map', 'nbls_fetch_beam_grid_delays',
+    'nbls_beam_grid_lds_bytes',
 ]
+BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
+BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -152,6 +156,11 @@ def load_library(path=None):
     lib.nbls_est_fetch_lag_fraction.argtypes = [vp, C.c_int32, dp]
     lib.nbls_set_lag_limits.argtypes = [vp, ip, C.c_int32]
     lib.nbls_lag_limit_form.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.nbls_set_beam_grid.argtypes = [vp, dp, C.c_int32, C.c_int32]
+    lib.nbls_fetch_beam_grid.argtypes = [vp, ip, dp, dp]
+    lib.nbls_fetch_beam_grid_map.argtypes = [vp, dp]
+    lib.nbls_fetch_beam_grid_delays.argtypes = [vp, ip]
+    lib.nbls_beam_grid_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -254,6 +263,7 @@ class Handle:
         self.nbands = self.vector_len = 0
         self.nseg = 1
         self.est_npairs = []            # pair counts of the further estimators (set_estimators)
+        self._want_grid_n = self.grid_n = 0   # grid points of set_beam_grid / of the plan
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -376,6 +386,7 @@ class Handle:
         self.nbands, self.vector_len = nb * self.nseg, int(vector_len)     # result rows: band-major, nseg per band
         self.fbands = nb
         self._nsec = nsec
+        self.grid_n = self._want_grid_n
 
     def set_option(self, key, value):
         """Per-handle implementation switch (``nbls_set_option``; identical results unless the library is the
@@ -499,6 +510,39 @@ class Handle:
         else:
             self._chk(self.lib.nbls_est_fetch_beam(self._h, int(e), _dptr(out[0]), _dptr(out[1])))
         return out[0], out[1]
+
+    def set_beam_grid(self, grid=None, want_map=False):
+        """The next plans also search, per window, the beam F-statistic of the full array over the slowness vectors
+        ``grid`` (G, 2) in s/km (``nbls_set_beam_grid``, DESIGN.md section 15; ``planner.slowness_grid`` makes one);
+        ``want_map``: they keep every F(g) too.  None switches that off."""
+        if grid is None:
+            self._chk(self.lib.nbls_set_beam_grid(self._h, None, 0, 0))
+            self._want_grid_n = 0
+            return
+        g = _f64(grid)
+        if g.ndim != 2 or g.shape[1] != 2:
+            raise ValueError('the slowness grid must be (G, 2), not %r' % (g.shape,))
+        self._chk(self.lib.nbls_set_beam_grid(self._h, _dptr(g), g.shape[0], int(bool(want_map))))
+        self._want_grid_n = g.shape[0]
+
+    def fetch_beam_grid(self):
+        """-> (grid_index int32, grid_fstat, grid_power) of the plan's slowness-grid search, each (rows, vector_len)."""
+        idx = np.empty((self.nbands, self.vector_len), dtype=np.int32)
+        out = np.empty((2, self.nbands, self.vector_len))
+        self._chk(self.lib.nbls_fetch_beam_grid(self._h, _iptr(idx), _dptr(out[0]), _dptr(out[1])))
+        return idx, out[0], out[1]
+
+    def fetch_beam_grid_map(self):
+        """-> F of every grid point, (rows, vector_len, G) (a plan made with ``want_map``)."""
+        out = np.empty((self.nbands, self.vector_len, max(self.grid_n, 1)))
+        self._chk(self.lib.nbls_fetch_beam_grid_map(self._h, _dptr(out)))
+        return out
+
+    def fetch_beam_grid_delays(self):
+        """-> the plan's delay table, (G, nelem) int32."""
+        out = np.empty((max(self.grid_n, 1), self.nchans // self.nseg), dtype=np.int32)
+        self._chk(self.lib.nbls_fetch_beam_grid_delays(self._h, _iptr(out)))
+        return out
 
     def set_lag_refinement(self, on=True):
         """The next plans also refine every picked lag to sub-sample precision behind its verifier, and their solves read

@@ -764,6 +764,19 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
     if (h->want_beam && h->comm)
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: beam results (nbls_set_beam) are not supported with an RCCL communicator (the gathered block does not carry them)");
+    std::vector<int32_t> gdel;       // the slowness grid (nbls_set_beam_grid): its delay table for this trace's array
+    int ghalo = 0;
+    if (!h->want_grid.empty()) {
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the slowness-grid search (nbls_set_beam_grid) is not supported with an RCCL communicator (the gathered block does not carry its grids)");
+        const int En = h->nchans / NS;
+        if (!h->est[0].d_xij || (int64_t)En * (En - 1) / 2 != h->npairs)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: the slowness-grid search (nbls_set_beam_grid) needs the geometry of the trace's array");
+        const int G = (int)(h->want_grid.size() / 2);
+        gdel.resize((size_t)G * En);
+        if (!nbls_beam_grid_delays_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, gdel.data(), &ghalo))
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: a delay of the slowness grid (nbls_set_beam_grid) reaches 2^30 samples");
+    }
     if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
         if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
@@ -777,6 +790,12 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->refine = h->want_refine;
     h->frac_valid = false;
     h->solve_ran = false;
+    h->h_grid = h->want_grid;
+    h->h_grid_delay.swap(gdel);
+    h->grid_n = (int)(h->h_grid.size() / 2);
+    h->grid_halo = ghalo;
+    h->grid_map = h->grid_n > 0 && h->want_grid_map;
+    h->grid_valid = false;
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
     nbls_estimator& x0 = h->est[0];
@@ -1037,6 +1056,14 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if (x.lts && (rc = upload_lts_tables(h, x))) return rc;
         if (e > 0 && (rc = size_result_buffers(h, x, (size_t)a.R * a.vector_len, 0))) return rc;
     }
+    if (h->grid_n > 0) {             // the slowness-grid search: its two tables and its result buffers, for a plan that asks only
+        const size_t cells = (size_t)a.R * a.vector_len;
+        if ((rc = alloc_copy(h, h->d_grid, h->h_grid.data(), h->h_grid.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_grid_delay, h->h_grid_delay.data(), h->h_grid_delay.size()))) return rc;
+        if ((rc = ensure(h, h->d_grid_index, cells * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(h, h->d_grid_fp, 2 * cells * sizeof(double)))) return rc;
+        if (h->grid_map && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->grid_n * sizeof(double)))) return rc;
+    }
     return 0;
 }
 
@@ -1137,6 +1164,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     h->last_stage_mask = stage_mask;
     if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
     if (stage_mask & 4) h->solve_ran = true;
+    if (stage_mask & 4) h->grid_valid = true;            // (... and the grids of the slowness-grid search)
     if (stage_mask & 2) h->frac_valid = true;            // (... one without the correlation stage the lag fractions)
     // per-batch solves: behind each unit batch of the correlation stage (streamed results: a batch's rows are complete
     // while later batches are still being correlated), on the second stream with option "overlap"
@@ -1393,6 +1421,71 @@ int nbls_est_fetch_beam(nbls_handle* h, int32_t est, double* beam_power, double*
         HIPCHK(h, copy_sync(h, outs[g], s.d_beam + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
         zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
     }
+    return NBLS_OK;
+}
+
+int nbls_set_beam_grid(nbls_handle* h, const double* grid, int32_t G, int32_t want_map) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!grid) { h->want_grid.clear(); h->want_grid_map = false; return NBLS_OK; }      // off: the next plan does not search
+    if (G < 1 || G > NBLS_BEAM_GRID_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_grid: G must be 1.." + std::to_string(NBLS_BEAM_GRID_MAX));
+    for (int64_t k = 0; k < 2 * (int64_t)G; ++k)                 // everything is checked before the handle changes
+        if (!(fabs(grid[k]) < INFINITY)) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_grid: slowness vector " + std::to_string(k / 2) + " is not finite");
+    h->want_grid.assign(grid, grid + 2 * (size_t)G);             // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want_grid_map = want_map != 0;
+    return NBLS_OK;
+}
+
+int nbls_beam_grid_lds_bytes(int32_t nelem, int32_t W, int32_t halo) {
+    if (nelem < 1 || W < 1 || halo < 0) return NBLS_ERR_ARG;
+    return (int)nbls_beam_grid_lds_bytes_of(nelem, W, halo);
+}
+
+// what the three grid fetches share: the plan asked, and the pass is through
+static int grid_fetch_ready(nbls_handle* h, const char* who, bool map) {
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, std::string(who) + ": no plan");
+    if (h->grid_n < 1 || !h->d_grid_index) return fail(h, NBLS_ERR_STATE, std::string(who) + ": nbls_set_beam_grid before nbls_plan");
+    if (map && (!h->grid_map || !h->d_grid_map)) return fail(h, NBLS_ERR_STATE, std::string(who) + ": the plan did not ask for the map (nbls_set_beam_grid, want_map)");
+    return finish_pass(h);
+}
+
+int nbls_fetch_beam_grid(nbls_handle* h, int32_t* index, double* fstat, double* power) {
+    if (!h) return NBLS_ERR_ARG;
+    { const int rc = grid_fetch_ready(h, "nbls_fetch_beam_grid", false); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    // the grids are written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass
+    // without it leaves them as they are
+    if (index) {
+        if (!h->grid_valid) memset(index, 0, cells * sizeof(int32_t));
+        else {
+            HIPCHK(h, copy_sync(h, index, h->d_grid_index, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+            zero_uncomputed(h, index, sizeof(int32_t));
+        }
+    }
+    double* outs[2] = {fstat, power};
+    for (int g = 0; g < 2; ++g) {
+        if (!outs[g]) continue;
+        if (!h->grid_valid) { memset(outs[g], 0, cells * sizeof(double)); continue; }
+        HIPCHK(h, copy_sync(h, outs[g], h->d_grid_fp + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
+        zero_uncomputed(h, outs[g], sizeof(double));
+    }
+    return NBLS_OK;
+}
+
+int nbls_fetch_beam_grid_map(nbls_handle* h, double* map) {
+    if (!h || !map) return NBLS_ERR_ARG;
+    { const int rc = grid_fetch_ready(h, "nbls_fetch_beam_grid_map", true); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len, row = (size_t)h->grid_n * sizeof(double);
+    if (!h->grid_valid) { memset(map, 0, cells * row); return NBLS_OK; }
+    HIPCHK(h, copy_sync(h, map, h->d_grid_map, cells * row, hipMemcpyDeviceToHost));
+    zero_uncomputed(h, map, row);
+    return NBLS_OK;
+}
+
+int nbls_fetch_beam_grid_delays(nbls_handle* h, int32_t* d) {
+    if (!h || !d) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: no plan");
+    if (h->grid_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: nbls_set_beam_grid before nbls_plan");
+    memcpy(d, h->h_grid_delay.data(), h->h_grid_delay.size() * sizeof(int32_t));   // the plan's own table (the device holds a copy)
     return NBLS_OK;
 }
 

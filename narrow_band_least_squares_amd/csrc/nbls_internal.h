@@ -138,6 +138,20 @@ struct nbls_handle {
     std::vector<int32_t> lim;       // the plan's copy (empty: the plan searches every lag)
     dev_buf<int32_t> d_limsq;       // [nelem][nelem] the plan's limit of the pair of two elements, symmetric, 0 on the diagonal
     bool refine_attr_set = false;   // the LDS form of refine_lag_kernel has been given its dynamic LDS limit on this handle's device
+    // ---- slowness-grid search of the beam F-statistic (nbls_set_beam_grid, beam_grid.hip) ----
+    std::vector<double> want_grid;  // nbls_set_beam_grid: [G][2] slowness vectors, read by the next nbls_plan (empty: off)
+    bool want_grid_map = false;     // ... and whether that plan keeps every F(g)
+    std::vector<double> h_grid;     // the plan's copy (empty: the plan does not search)
+    std::vector<int32_t> h_grid_delay;   // [G][nelem] the plan's delay table
+    int grid_n = 0, grid_halo = 0;  // G and H = max |delay| of the plan
+    bool grid_map = false;          // the plan keeps the map
+    bool grid_valid = false;        // a pass of this plan has run the solve stage: the grid results are there
+    bool grid_attr_set = false;     // the LDS form of beam_grid_kernel has been given its dynamic LDS limit
+    dev_buf<double> d_grid;         // [G][2]
+    dev_buf<int32_t> d_grid_delay;  // [G][nelem]
+    dev_buf<int32_t> d_grid_index;  // [B][VL]
+    dev_buf<double> d_grid_fp;      // [2][B][VL]: grid_fstat | grid_power
+    dev_buf<double> d_grid_map;     // [B][VL][G] (a plan that asked for the map)
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -288,7 +302,14 @@ hipError_t nbls_launch_refine(nbls_handle* h, int64_t u0, int64_t nu, int gW, hi
 size_t nbls_refine_lds_bytes_of(int nelem, int W);
 // beam power and F-statistic of units [u0, u0 + nu) at the slowness estimator x has solved for them (beam.hip)
 hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
-// [gather ->] solve -> [uncertainty ->] [beam ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
+// slowness-grid search of the beam F-statistic over units [u0, u0 + nu) for the plan's full array (beam_grid.hip)
+hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// dynamic LDS bytes of the form beam_grid_kernel takes for windows of W samples of nelem elements and a halo of `halo`
+// samples; 0: the global-memory form
+size_t nbls_beam_grid_lds_bytes_of(int nelem, int W, int halo);
+// the delay table d[G][nelem] of a grid and its halo (host, un-fused arithmetic); false: some |fs xij . s_g| reaches 2^30
+bool nbls_beam_grid_delays_of(const double* xij, int nelem, double fs, const double* grid, int G, int32_t* d, int* halo);
+// [gather ->] solve -> [uncertainty ->] [beam ->] [grid search ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
 hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);

@@ -1435,6 +1435,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (h->beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
+    // the slowness-grid search of a plan that asked for one: the full array only, behind the plan's own estimator
+    if (h->grid_n > 0 && &s == &h->est[0] && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;
     return pack_weights_of(h, s, u0, nu, st);
 }
 

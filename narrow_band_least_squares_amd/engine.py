@@ -362,12 +362,14 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 
 
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
-               want_uncert=False, want_beam=False, want_subsample=False):
+               want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
-    lags are wanted."""
+    lags are wanted.  ``grid_points`` > 0: ``grid_index`` / ``grid_fstat`` / ``grid_power`` of a slowness-grid search over that
+    many points, and with ``want_grid_map`` its ``grid_map`` (nbands, vector_len, grid_points)."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
+    gfp = np.zeros((2, nb, vector_len)) if grid_points else (None, None)
     grids = np.zeros((4, nb, vector_len))
     unc = np.zeros((2, nb, vector_len)) if want_uncert else (None, None)
     beam = np.zeros((2, nb, vector_len)) if want_beam else (None, None)
@@ -377,7 +379,10 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      lag_frac=np.zeros((nb, vector_len, P)) if (want_lag and want_subsample) else None,
                      cmax=np.zeros((nb, vector_len, P)) if want_cmax else None,
                      z=np.zeros((nb, vector_len, 2)) if want_z else None, vel_uncert=unc[0], baz_uncert=unc[1],
-                     beam_power=beam[0], fstat=beam[1], sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
+                     beam_power=beam[0], fstat=beam[1],
+                     grid_index=np.zeros((nb, vector_len), dtype=np.int32) if grid_points else None, grid_fstat=gfp[0],
+                     grid_power=gfp[1],
+                     grid_map=np.zeros((nb, vector_len, grid_points)) if (grid_points and want_grid_map) else None, sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
                      lts=alpha < 1.0, fs=fs)
 
 
@@ -456,7 +461,8 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
-                      host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None):
+                      host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None,
+                      slowness_grid=None):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
@@ -464,7 +470,11 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     states; HBM holds one segment / one window slice at a time.  The filtered band stays on the host and the windows reach
     the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``; nor is
     the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM, nor the bounded lag
-    search (``min_velocity``)."""
+    search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too."""
+    if slowness_grid is not None:
+        raise ValueError('slowness_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
+                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
+                         'the slowness-grid search is not available there' % _shape_of(data))
     if min_velocity is not None:
         raise ValueError('min_velocity: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which correlates the band slice by slice: '
@@ -572,7 +582,7 @@ def upload_trace(h, data, fs):
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False, lag_limits=None):
+           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -583,7 +593,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     computes beam power and F-statistic behind every solve (``Handle.set_beam``; for this plan only).  ``subsample``: the
     plan refines the picked lags to sub-sample precision before the solve (``Handle.set_lag_refinement``; likewise).
     ``lag_limits``: the plan searches the lag of pair k only within ``|lag| <= lag_limits[k]`` samples
-    (``Handle.set_lag_limits``, ``planner.lag_limits``; likewise)."""
+    (``Handle.set_lag_limits``, ``planner.lag_limits``; likewise).  ``beam_grid`` (G, 2): the plan also searches the beam
+    F-statistic of the full array over these slowness vectors, ``beam_grid_map``: and keeps every F(g)
+    (``Handle.set_beam_grid``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -609,6 +621,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_lag_refinement(True)
     if lag_limits is not None:
         h.set_lag_limits(lag_limits)
+    if beam_grid is not None:
+        h.set_beam_grid(beam_grid, beam_grid_map)
     try:
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
@@ -619,6 +633,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_lag_refinement(False)
         if lag_limits is not None:
             h.set_lag_limits(None)
+        if beam_grid is not None:
+            h.set_beam_grid(None)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -737,6 +753,10 @@ def collect(res, h, b0, b1, streamed, note):
         res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam()
     if res.lag_frac is not None:
         res.lag_frac[b0:b1] = h.fetch_lag_fraction()
+    if res.grid_index is not None:
+        res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = h.fetch_beam_grid()
+    if res.grid_map is not None:
+        res.grid_map[b0:b1] = h.fetch_beam_grid_map()
     if not live:
         note.bands(b0, b1)
 
@@ -795,7 +815,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
-            want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None):
+            want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
+            want_grid_map=False):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -814,6 +835,11 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     min_velocity (km/s): every pair's lag is searched only within the range a plane wave no slower than that can delay the
     pair (``planner.lag_limits``, ``nbls_set_lag_limits``); ``ValueError`` before any GPU work unless
     it is a finite real > 0; ``process_segmented`` refuses it.
+    slowness_grid (G, 2) s/km: also ``res.grid_index`` (int32) / ``res.grid_fstat`` / ``res.grid_power`` (nbands, vector_len),
+    per window the grid point at which the Fisher ratio of the full array's delay-and-sum beam is largest and the ratio
+    and beam power there, searched on the GPU behind each unit's solve (``nbls_set_beam_grid``, DESIGN.md section 15);
+    want_grid_map=True: also ``res.grid_map`` (nbands, vector_len, G), the ratio at every grid point.  ``ValueError`` before
+    any GPU work for a bad grid (``planner.check_slowness_grid``); ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -833,6 +859,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
        group completes (the caller builds its dictionary there).  Rounds collected in step 4 are reported after step 5."""
     nchans, npts = _shape_of(data)
     limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij)[0], fs, min_velocity)
+    sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
     cap = max_bands_per_pass(nchans, npts)
     single = prefiltered or handle is not None or not upload
     up, resident = start_upload(data, fs, device) if upload and handle is None and (cap >= 1 or prefiltered) else (None, False)
@@ -842,16 +869,16 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam, want_subsample, min_velocity)
+                                     group_done, want_beam, want_subsample, min_velocity, sgrid)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
-                         want_subsample)
+                         want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
-                                 subsample=want_subsample, lag_limits=limits)
+                                 subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map))
     finally:
         if up is not None:
             up.close()
@@ -1073,7 +1100,7 @@ def batch_rows(streams):
 
 def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
-                  want_subsample=False, min_velocity=None):
+                  want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1087,6 +1114,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     S = len(recordings)
     nchans, npts = len(recordings[0]), len(recordings[0][0])
     nb = len(band_edges)
+    sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
+    G = 0 if sgrid is None else len(sgrid)
     prep = prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type, filter_order, filter_ripple,
                    vector_len, prefiltered)
     VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
@@ -1095,7 +1124,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     if per_sub < 1:
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
                          'process it on its own' % (nchans, npts))
-    out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam)
+    out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
+                      grid_points=G, want_grid_map=want_grid_map)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1109,7 +1139,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 b1 = min(nb, b0 + cap)
                 R = (b1 - b0) * k
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
-                       beam=want_beam, subsample=want_subsample, lag_limits=limits)
+                       beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
+                       beam_grid_map=bool(want_grid_map))
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
@@ -1117,6 +1148,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 m = m.reshape(b1 - b0, k, VL, MB)
                 unc = np.stack(h.fetch_uncertainty()).reshape(2, b1 - b0, k, VL) if want_uncert else None
                 beam = np.stack(h.fetch_beam()).reshape(2, b1 - b0, k, VL) if want_beam else None
+                sg = [a.reshape(b1 - b0, k, VL) for a in h.fetch_beam_grid()] if G else None
+                sgmap = h.fetch_beam_grid_map().reshape(b1 - b0, k, VL, G) if (G and want_grid_map) else None
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
@@ -1124,6 +1157,10 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                         res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = unc[:, :, j]
                     if want_beam:
                         res.beam_power[b0:b1], res.fstat[b0:b1] = beam[:, :, j]
+                    if G:
+                        res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = [a[:, j] for a in sg]
+                    if sgmap is not None:
+                        res.grid_map[b0:b1] = sgmap[:, j]
     finally:
         h.set_segments(1)
     for res, t0 in zip(out, t0s):

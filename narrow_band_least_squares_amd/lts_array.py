@@ -28,10 +28,33 @@ def _returns_beam(res, nchans, alpha, keys=None):
     return _returns(res, nchans, alpha, keys) + (res.beam_power[0, :n].copy(), res.fstat[0, :n].copy())
 
 
+def grid_slowness(grid, index):
+    """The slowness vectors ``grid[index]`` of a grid search as ``ltsva`` reports a slowness -> (grid_vel, grid_baz):
+    ``grid_vel = 1 / |s|`` km/s (``inf`` for s = 0), ``grid_baz = (atan2(s0, s1) * 180 / pi - 360) mod 360`` degrees, the
+    formula of the solve kernel (csrc/solve.hip); both NaN where the index is -1."""
+    index = np.asarray(index)
+    s = np.asarray(grid, dtype=np.float64)[np.maximum(index, 0)]
+    with np.errstate(divide='ignore'):
+        vel = 1.0 / np.hypot(s[..., 0], s[..., 1])
+    baz = np.mod(np.arctan2(s[..., 0], s[..., 1]) * 180.0 / np.pi - 360.0, 360.0)
+    none = index < 0
+    return np.where(none, np.nan, vel), np.where(none, np.nan, baz)
+
+
+def _returns_grid(res, grid, want_map):
+    """The band's slowness-grid results behind ``_returns``: ``grid_vel, grid_baz, grid_fstat, grid_power, grid_index`` and,
+    when asked, the map (csrc/beam_grid.hip: beam_grid_kernel)."""
+    n = int(res.nwin[0])
+    idx = res.grid_index[0, :n].copy()
+    vel, baz = grid_slowness(grid, idx)
+    out = (vel, baz, res.grid_fstat[0, :n].copy(), res.grid_power[0, :n].copy(), idx)
+    return out + ((res.grid_map[0, :n].copy(),) if want_map else ())
+
+
 def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
-           want_subsample=False, min_velocity=None):
-    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample`` and ``ltsva_bounded``: the checks, the geometry, the
-    device pass, the returns."""
+           want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False):
+    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded`` and ``ltsva_grid``: the checks, the
+    geometry, the device pass, the returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
     engine.check_elements(nchans, alpha)
@@ -48,8 +71,10 @@ def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_ar
 
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
                          prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
-                         want_subsample=want_subsample, min_velocity=min_velocity)
-    return (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
+                         want_subsample=want_subsample, min_velocity=min_velocity, slowness_grid=slowness_grid,
+                         want_grid_map=grid_map)
+    out = (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
+    return out if slowness_grid is None else out + _returns_grid(res, slowness_grid, grid_map)
 
 
 def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
@@ -115,8 +140,27 @@ def ltsva_bounded(st, lat_list, lon_list, window_length, window_overlap, min_vel
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, min_velocity)
 
 
+def ltsva_grid(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, alpha=1.0, rij=None, grid_map=False):
+    """``ltsva`` followed by the slowness-grid search of the beam F-statistic: per window the delay-and-sum beam of the
+    full array is steered over the slowness vectors ``slowness_grid`` (G, 2) s/km (``planner.slowness_grid`` makes a
+    Cartesian one) by whole-sample delays, and the grid point with the largest Fisher ratio (N-1) S_b / (N S_t - S_b) is
+    reported — the estimate that does not rest on pairwise lag picks, which at low SNR fail pair by pair where the whole
+    array still sees the wave (DESIGN.md section 15 has the definition and the counts).  Returns ``ltsva``'s 8-tuple followed
+    by ``grid_vel`` (1 / |s| km/s at the maximum, ``inf`` for s = 0), ``grid_baz`` (degrees, the solve's formula),
+    ``grid_fstat``, ``grid_power``, ``grid_index`` (int32, -1 with NaN in the other four where no grid point has a ratio: an
+    all-zero window) and, with ``grid_map=True``, the ratio at every grid point (nwin, G).  Among equal ratios the lowest
+    index wins.  The search runs on the GPU behind each window's solve, from the filtered samples already there
+    (csrc/beam_grid.hip).  A bad grid, a ``grid_map`` that is not a bool and too few elements raise ``ValueError`` before
+    any GPU work."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    _check_flag('grid_map', grid_map)
+    _check_elements_strict(len(st), alpha)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, None, grid,
+                  bool(grid_map))
+
+
 def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False,
-                subsample=False, min_velocity=None):
+                subsample=False, min_velocity=None, slowness_grid=None):
     """``ltsva`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of 8-tuples,
     element i equal to ``ltsva(streams[i], ...)``.  Every stream must have the same element count, trace length and
     sampling rate, and all share the geometry; ``ValueError`` names a mismatch before any GPU work.  The "ALPHA is
@@ -124,17 +168,22 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     ``ltsva_beam(streams[i], ...)``.  ``subsample=True``: element i equal to ``ltsva_subsample(streams[i], ...)``; with both,
     the beam is steered by the slowness fitted to the refined delays.  ``min_velocity`` (km/s, default None: every lag):
     the lags are searched within their physical range as in ``ltsva_bounded``; it combines with both flags, the fractions
-    and the beam then follow the bounded picks."""
+    and the beam then follow the bounded picks.  ``slowness_grid`` (G, 2) s/km, default None: every tuple is followed by the
+    five grid returns of ``ltsva_grid`` (no map), element i equal to ``ltsva_grid(streams[i], ...)``; it combines with the
+    others, because it reads none of their results."""
     _check_flag('beam', beam)
     _check_flag('subsample', subsample)
     if min_velocity is not None:
         planner.check_min_velocity(min_velocity)
+    if slowness_grid is not None:
+        slowness_grid = planner.check_slowness_grid(slowness_grid)
     streams = list(streams)
     if not streams:
         return []
     recs, fs, t0s = engine.batch_rows(streams)
     if len(streams) == 1:          # a batch of one IS the single call
-        return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity)]
+        return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
+                        slowness_grid)]
     nchans = len(recs[0])
     engine.check_elements(nchans, alpha)
     if rij is None:
@@ -143,18 +192,20 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
                                    prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
-                                   min_velocity=min_velocity)
-    return [(_returns_beam if beam else _returns)(res, nchans, alpha) for res in results]
+                                   min_velocity=min_velocity, slowness_grid=slowness_grid)
+    return [(_returns_beam if beam else _returns)(res, nchans, alpha) +
+            (() if slowness_grid is None else _returns_grid(res, slowness_grid, False)) for res in results]
 
 
-def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity=None):
+def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity=None,
+            slowness_grid=None):
     """The single call a batch of one recording / one estimator with nothing removed is: ``ltsva`` itself for the plain
     one, else the strict element check of ``ltsva_beam`` / ``ltsva_subsample`` and the shared body."""
-    if not beam and not subsample and min_velocity is None:
+    if not beam and not subsample and min_velocity is None and slowness_grid is None:
         return ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)
     _check_elements_strict(len(st), alpha)
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample),
-                  min_velocity)
+                  min_velocity, slowness_grid)
 
 
 def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False,

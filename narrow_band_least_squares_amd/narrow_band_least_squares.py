@@ -15,6 +15,7 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
+from .lts_array import grid_slowness
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -90,7 +91,8 @@ def _prefix_stdict(stdict, band_number):
 
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
-               key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None):
+               key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
+               want_grid_map=False):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -129,7 +131,7 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
     res = engine.process(rows, fs, t0, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
-                         min_velocity=min_velocity)
+                         min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map)
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -227,6 +229,38 @@ def narrow_band_least_squares_bounded(WINLEN_list, WINOVER, ALPHA, st, lat_list,
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], min_velocity=min_velocity)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array)
+
+
+def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                   FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                   slowness_grid, grid_map=False):
+    """``narrow_band_least_squares`` followed by the slowness-grid search of the beam F-statistic in every band
+    (``lts_array.ltsva_grid``): ``grid_vel_array``, ``grid_baz_array``, ``grid_fstat_array``,
+    ``grid_power_array`` and ``grid_index_array`` (int32), each (NBANDS, vector_len) and zero-padded like ``vel_array``, and
+    with ``grid_map=True`` the Fisher ratio at every grid point (NBANDS, vector_len, G).  Per band and window the
+    delay-and-sum beam of the full array is steered over ``slowness_grid`` (G, 2) s/km on the GPU behind the window's
+    solve, from the filtered band that is already there.  The first nine returns are those of
+    ``narrow_band_least_squares``.  A bad grid raises ``ValueError`` before any GPU work, and so does a trace so long that
+    not one filtered band fits the HBM budget of a pass (the time-segmented path keeps the band on the host)."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    if not isinstance(grid_map, (bool, np.bool_)):
+        raise ValueError('grid_map must be True or False, not %r' % (grid_map,))
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], slowness_grid=grid,
+                                       want_grid_map=bool(grid_map))
+    gvel, gbaz = grid_slowness(grid, res.grid_index)
+    computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + \
+        ((res.grid_map,) if grid_map else ())
 
 
 def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,

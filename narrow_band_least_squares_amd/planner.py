@@ -452,6 +452,43 @@ def check_min_velocity(min_velocity):
     return v
 
 
+MAX_GRID_POINTS = 65536      # grid points of one slowness-grid search (NBLS_BEAM_GRID_MAX)
+
+
+def slowness_grid(max_slowness, n):
+    """The ``n`` x ``n`` Cartesian grid of slowness vectors over ``+-max_slowness`` s/km (``n`` odd, so s = 0 is a point;
+    ``numpy.meshgrid(..., indexing='ij')`` order), the points with ``|s| > max_slowness`` dropped -> (G, 2) float64, the
+    table ``ltsva_grid`` and ``nbls_set_beam_grid`` take.  ``slowness_grid(4.0, 41)`` has 1257 points."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1 or n % 2 == 0:
+        raise ValueError('n must be an odd number of grid points per axis, not %r' % (n,))
+    s = float(max_slowness)
+    if not np.isfinite(s) or s <= 0.0:
+        raise ValueError('max_slowness must be a finite number of s/km above 0, not %r' % (max_slowness,))
+    ax = np.linspace(-s, s, int(n)) if n > 1 else np.zeros(1)           # (one point per axis: the centre)
+    g0, g1 = np.meshgrid(ax, ax, indexing='ij')
+    grid = np.stack([g0.ravel(), g1.ravel()], axis=1)
+    return np.ascontiguousarray(grid[np.hypot(grid[:, 0], grid[:, 1]) <= s])
+
+
+def check_slowness_grid(grid):
+    """``slowness_grid`` of the grid search -> C-contiguous (G, 2) float64; ``ValueError`` (before any GPU work) unless it
+    is a real array of that shape with 1 <= G <= ``MAX_GRID_POINTS`` and finite entries."""
+    try:
+        g = np.asarray(grid)
+    except Exception:
+        raise ValueError('slowness_grid must be a (G, 2) array of slowness vectors in s/km')
+    if g.dtype == object or g.dtype.kind not in 'iuf':
+        raise ValueError('slowness_grid must hold real numbers (s/km), not dtype %s' % g.dtype)
+    if g.ndim != 2 or g.shape[1] != 2:
+        raise ValueError('slowness_grid must be (G, 2), not %r' % (g.shape,))
+    if not (1 <= g.shape[0] <= MAX_GRID_POINTS):
+        raise ValueError('slowness_grid has %d points: 1 to %d are supported' % (g.shape[0], MAX_GRID_POINTS))
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    if not np.all(np.isfinite(g)):
+        raise ValueError('slowness_grid holds entries that are not finite')
+    return g
+
+
 def lag_limits(xij, fs, min_velocity):
     """Per-pair lag limits of the bounded search (``nbls_set_lag_limits``) -> int32 (P,):
     ``L_k = int(ceil(fs * hypot(xij[k, 0], xij[k, 1]) / min_velocity)) + 1`` samples — the delay a plane wave no slower
