@@ -64,8 +64,11 @@ def _against_reference(res, filt, band=0, label=''):
 @pytest.mark.parametrize('N,alpha', [(3, 1.0), (4, 0.5), (9, 0.5)])
 def test_matches_the_reference(N, alpha, W):
     """3 elements under OLS, 4 under LTS with one mistimed element, 9 under LTS (the bucket kernel); windows of 16 samples
-    (one wave per unit, shorter than the delays), 65 and 257 (one past the wave and the workgroup), 1200 (four waves per
-    unit).  The first and last windows read outside the trace: zeros there."""
+    (a quarter of a wave's lanes, shorter than the delays), 65 (one sample past the 64 lanes: lane 0 alone has a second
+    sample) and 257 (one past a wave's trip of 64 * BEAM_TU = 256 samples: a second trip of one sample) — all three
+    summed by ONE wave per unit, as every window up to BEAM_WAVE_W = 512 samples is — and 1200 (the four waves of the
+    workgroup per unit: one whole trip of 1024 samples and a part).  The lengths at the edges themselves are
+    tests/test_gpu_seams.py's.  The first or the last windows read outside the trace: zeros there."""
     npts = NPTS[W]
     data, rij = _wave(N, npts, mistimed=alpha < 1.0)
     res = _process(data, rij, W, alpha, overlap=0.75 if W == 1200 else 0.5)

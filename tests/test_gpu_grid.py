@@ -72,9 +72,10 @@ def _against_reference(res, filt, grid, band=0, label='', noisy=True):
 @pytest.mark.parametrize('W', [16, 65, 257, 1200])
 @pytest.mark.parametrize('N,alpha', [(3, 1.0), (4, 0.5), (9, 0.5)])
 def test_matches_the_truth(N, alpha, W):
-    """3 elements under OLS, 4 and 9 under LTS; windows of 16 samples (a quarter of a wave's step, shorter than the delays),
-    65 and 257 (one past a lane step and a wave's step of 256), 1200 (four whole steps and a part).  The first window
-    reads before the trace's start: zeros there."""
+    """3 elements under OLS, 4 and 9 under LTS; windows of 16 samples (a quarter of a wave's 64 lanes, shorter than the
+    delays), 65 (one past the 64 lanes) and 257 (one past a wave's step of GRID_BLOCK = 256 samples: a whole step and a
+    partial one of one sample), 1200 (four whole steps and a part).  The lengths at the step's edges themselves are
+    tests/test_gpu_seams.py's.  The first window reads before the trace's start: zeros there."""
     npts = NPTS[W]
     data, rij = _wave(N, npts, mistimed=alpha < 1.0)
     xij = planner.co_array(rij)[0]
