@@ -564,6 +564,11 @@ int nbls_probe_mfma_i8(nbls_handle* h, const int32_t* a, const int32_t* b, int32
  * pairs whose candidate buffer overflowed, total candidates, max candidates per ordered pair, runs of consecutive
  * listed lags, listed lags that sit in a run of two or more, 0, 0}. */
 int nbls_debug_screen_stats(nbls_handle* h, int64_t* out8);
+/* Developer / tests: the candidate records the screening kernel left for the last unit batch, [units][N][N][32] int32,
+ * record (unit, sliding channel i, partner j) = {count, flags (1 interval, 2 list overflow), kk_lo, kk_hi, screening
+ * maximum (f32 bits), theta (f32 bits), up to 26 np.correlate indices kk}; the diagonal is not written.  *units = units
+ * of that batch; out NULL: only that.  capacity: int32 elements of out. */
+int nbls_debug_screen_records(nbls_handle* h, int32_t* out, int64_t capacity, int64_t* units);
 /* Developer: mean s_memtime cycle counts of the phases of the wave-per-unit FAST-LTS kernel
 (developer build, options "screen_stamps" / "lts_stamps"): out8 = {setup+medians, elemental starts,
  * C-steps, candidate peel, refinement, finish, 0, total}. */

@@ -16,7 +16,7 @@ EXPORTS = [
     'nbls_version', 'nbls_device_count', 'nbls_create', 'nbls_destroy', 'nbls_last_error', 'nbls_set_trace',
     'nbls_set_geometry', 'nbls_plan', 'nbls_execute', 'nbls_execute_stages', 'nbls_execute_after', 'nbls_set_trace_shape', 'nbls_upload_rows', 'nbls_sync',
     'nbls_fetch', 'nbls_fetch_filtered', 'nbls_device_results', 'nbls_set_profiling',
-    'nbls_get_timings', 'nbls_run', 'nbls_probe_mfma_f64', 'nbls_probe_mfma_i8', 'nbls_debug_screen_stats', 'nbls_set_window_ranges', 'nbls_debug_screen_stamps', 'nbls_debug_lts_stamps',
+    'nbls_get_timings', 'nbls_run', 'nbls_probe_mfma_f64', 'nbls_probe_mfma_i8', 'nbls_debug_screen_stats', 'nbls_debug_screen_records', 'nbls_set_window_ranges', 'nbls_debug_screen_stamps', 'nbls_debug_lts_stamps',
     'nbls_set_trace_rows', 'nbls_result_layout', 'nbls_fetch_packed', 'nbls_comm_init_all', 'nbls_comm_unique_id',
     'nbls_comm_init_rank', 'nbls_reserve_results', 'nbls_comm_gather', 'nbls_comm_destroy', 'nbls_set_option',
     'nbls_developer_build', 'nbls_set_trace_from', 'nbls_debug_lts_coop_breakdown', 'nbls_filter_segment',
@@ -169,6 +169,7 @@ def load_library(path=None):
     lib.nbls_probe_mfma_f64.argtypes = [vp, dp, dp, dp]
     lib.nbls_probe_mfma_i8.argtypes = [vp, ip, ip, ip]
     lib.nbls_debug_screen_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.nbls_debug_screen_records.argtypes = [vp, ip, C.c_int64, C.POINTER(C.c_int64)]
     lib.nbls_set_window_ranges.argtypes = [vp, C.c_int32, ip, ip]
     lib.nbls_set_segments.argtypes = [vp, C.c_int32]
     lib.nbls_debug_screen_stamps.argtypes = [vp, dp]
@@ -653,6 +654,19 @@ class Handle:
         self._chk(self.lib.nbls_debug_screen_stats(self._h, out))
         return dict(pairs=out[0], overflow=out[1], candidates=out[2], max_candidates=out[3], lag_runs=out[4],
                     lags_in_runs_of_2_or_more=out[5])
+
+    def screen_records(self):
+        """The candidate records of the last screened unit batch (``nbls_debug_screen_records``) -> (units, N, N, 32)
+        int32, N the elements of one recording: record [u, i, j] of sliding channel i and partner j = count, flags
+        (1 interval, 2 list overflow), kk_lo, kk_hi, screening maximum and theta (f32 bits), up to 26 np.correlate
+        indices.  The diagonal, which the kernel does not write, comes back as zeros."""
+        units = C.c_int64()
+        self._chk(self.lib.nbls_debug_screen_records(self._h, None, 0, C.byref(units)))
+        n = self.nchans // self.nseg
+        out = np.zeros((units.value, n, n, 32), dtype=np.int32)
+        self._chk(self.lib.nbls_debug_screen_records(self._h, _iptr(out), out.size, C.byref(units)))
+        out[:, np.arange(n), np.arange(n)] = 0
+        return out
 
     def probe_mfma_i8(self, a, b):
         """a, b: (64, 16) int8 per-lane fragments -> (64, 4) int32 accumulators."""

@@ -1754,17 +1754,37 @@ int nbls_probe_mfma_f64(nbls_handle* h, const double* a, const double* b, double
     return NBLS_OK;
 }
 
-int nbls_debug_screen_stats(nbls_handle* h, int64_t* out4) {
-    // out4 = {ordered pairs in the last batch, pairs whose candidate buffer overflowed,
-    //         total candidates, max candidates}  (developer statistic of the int8 screening path)
-    if (!h || !out4) return NBLS_ERR_ARG;
+// The candidate records the screening kernel left for the last unit batch, [units][N][N][32] int32 (layout: CHDR in
+// xcorr_screen.hip), copied to `out`; -> the number of units.  Shared by the two developer read-outs below.
+static int screen_records_copy(nbls_handle* h, int32_t* out, int64_t capacity, int64_t* units) {
     if (!h->d_cand || h->screen_batch <= 0) return fail(h, NBLS_ERR_STATE, "no screening run yet");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int N = h->nelem;
     const int64_t last = h->last_batch > 0 ? h->last_batch : h->nunits - ((h->nunits - 1) / h->screen_batch) * h->screen_batch;
+    *units = last;
+    if (!out) return NBLS_OK;
+    const int64_t n = last * N * N * 32;
+    if (capacity < n) return fail(h, NBLS_ERR_ARG, "candidate records: the buffer is too small");
+    HIPCHK(h, copy_sync(h, out, h->d_cand, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NBLS_OK;
+}
+
+int nbls_debug_screen_records(nbls_handle* h, int32_t* out, int64_t capacity, int64_t* units) {
+    if (!h || !units || capacity < 0) return NBLS_ERR_ARG;
+    return screen_records_copy(h, out, capacity, units);
+}
+
+int nbls_debug_screen_stats(nbls_handle* h, int64_t* out4) {
+    // out4 = {ordered pairs in the last batch, pairs whose candidate buffer overflowed,
+    //         total candidates, max candidates}  (developer statistic of the int8 screening path)
+    if (!h || !out4) return NBLS_ERR_ARG;
+    const int N = h->nelem;
+    int64_t last = 0;
+    int rc = screen_records_copy(h, nullptr, 0, &last);
+    if (rc) return rc;
     std::vector<int32_t> c((size_t)last * N * N * 32);
-    HIPCHK(h, copy_sync(h, c.data(), h->d_cand, c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if ((rc = screen_records_copy(h, c.data(), (int64_t)c.size(), &last))) return rc;
     for (int q = 0; q < 8; ++q) out4[q] = 0;
     for (int64_t u = 0; u < last; ++u)
         for (int i = 0; i < N; ++i)

@@ -40,8 +40,19 @@ namespace {
 constexpr int QMAX = 16256;      // 127 * 128
 constexpr int KOUT = 26;         // candidates kept per ordered pair
 constexpr int NSLOT = 6;         // candidate slots per lane
-constexpr int CHDR = 6;          // record header: count, flags (1 interval, 2 list overflow), kk_lo, kk_hi,
-                                 //                screening maximum of this direction (f32 bits), theta (f32 bits)
+// The candidate record of one ORDERED pair (sliding channel i, partner j): the lags d >= 0 of q_i slid over q_j, as
+// np.correlate indices kk of the unordered pair (W - 1 + d for i < j, W - 1 - d for i > j).  32 ints:
+//   [0] count    listed lags, min(candidates that reached the list, KOUT)
+//   [1] flags    1: the interval [kk_lo, kk_hi] holds candidates that found no slot in their lane (verified lag by lag;
+//                   kept only if one of them is within theta of the direction's final maximum)
+//                2: more than KOUT candidates reached the list (the verifier evaluates every lag of the pair)
+//   [2] kk_lo    } valid with flag 1 (0x7fffffff / -1 without)
+//   [3] kk_hi    }
+//   [4] maximum  the screening maximum I' of this direction (f32 bits)
+//   [5] theta    the candidate threshold of the pair (f32 bits; the same in both directions)
+//   [6..31]      up to KOUT kk, in no particular order; 0 behind the count
+// Read back by nbls_debug_screen_records (api.hip); tests/test_gpu_ties.py designs inputs for each of its seams.
+constexpr int CHDR = 6;
 constexpr int CSTRIDE = KOUT + CHDR;   // = 32 ints
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -694,7 +705,13 @@ __global__ __launch_bounds__(512, TBV == 8 ? 2 : 4) void screen_kernel(QArgs a) 
     int sd[NSLOT];
 #pragma unroll
     for (int q = 0; q < NSLOT; ++q) { sv[q] = -__builtin_inff(); sd[q] = 0; }
-    int ilo = 0x7fffffff, ihi = -1;      // lag interval that absorbs what does not fit the slots
+    // lag interval that absorbs what does not fit the slots: ihi << 16 | ilo (a window that screens has fewer than 2^15
+    // samples: its images would not fit a CU's LDS, xcorr_route.hip), and the largest value
+    // it absorbed — like a slot, the interval is stale once that value lies more than theta below the final maximum (a
+    // wave that meets a flat stretch before any maximum is published absorbs it whole; unfiltered, the verifier
+    // evaluated every lag of such a stretch in FP64).  Packed so that the pair costs the two registers the bounds did.
+    unsigned int ipk = 0xffffu;
+    float iv = -__builtin_inff();
     const int step = 16 * S;
     const int ntile = (W + step - 1) / step;
     const int ngrp4 = (ntile + TBV - 1) / TBV;
@@ -762,7 +779,11 @@ __global__ __launch_bounds__(512, TBV == 8 ? 2 : 4) void screen_kernel(QArgs a) 
                         rem &= ~take;                                                                     \
                         if (rem == 0) break;                                                              \
                     }                                                                                     \
-                    if (rem != 0 && ((rem >> lane) & 1)) { ilo = d < ilo ? d : ilo; ihi = d > ihi ? d : ihi; } \
+                    if (rem != 0 && ((rem >> lane) & 1)) {                                                \
+                        const unsigned int lo_ = ipk & 0xffffu, hi_ = ipk >> 16, du_ = (unsigned int)d;   \
+                        ipk = ((du_ > hi_ ? du_ : hi_) << 16) | (du_ < lo_ ? du_ : lo_);                  \
+                        iv = fmaxf(iv, v[e]);                                                             \
+                    }                                                                                     \
                 }                                                                                         \
             }                                                                                             \
         }                                                                                                 \
@@ -921,15 +942,16 @@ __global__ __launch_bounds__(512, TBV == 8 ? 2 : 4) void screen_kernel(QArgs a) 
     const int hj = 16 * half + jj;
     if (colvalid && lmax > -__builtin_inff()) atomicMax(&Mj[hj], f2ord(lmax));
     if (colvalid && s == 0 && g == 0) thS[hj] = __float_as_int(theta);
-    if (colvalid && ihi >= 0) {
-        const int k1 = (ci < j) ? (W - 1 + ilo) : (W - 1 - ihi);
-        const int k2 = (ci < j) ? (W - 1 + ihi) : (W - 1 - ilo);
-        atomicMin(&klo[hj], k1);
-        atomicMax(&khi[hj], k2);
-    }
     __syncthreads();
     if (colvalid) {
         const float thr = ord2f(Mj[hj]) - theta;
+        if (iv >= thr) {                            // (nothing absorbed: iv = -inf)
+            const int ilo = (int)(ipk & 0xffffu), ihi = (int)(ipk >> 16);
+            const int k1 = (ci < j) ? (W - 1 + ilo) : (W - 1 - ihi);
+            const int k2 = (ci < j) ? (W - 1 + ihi) : (W - 1 - ilo);
+            atomicMin(&klo[hj], k1);
+            atomicMax(&khi[hj], k2);
+        }
 #pragma unroll
         for (int q = 0; q < NSLOT; ++q) {
             if (sv[q] >= thr) {
