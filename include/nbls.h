@@ -75,7 +75,8 @@ typedef struct {
     double quantize_ms;       /* int8 screening path only: sums over the batches               */
     double screen_ms;         /*   the int8-MFMA screening kernel (dominant kernel)            */
     double verify_ms;         /*   the FP64 verification kernel                                */
-    int32_t xcorr_impl;       /* correlator actually used: 1 VALU, 2 f64 MFMA, 3 int8 screening, 4 bounded-lag correlator */
+    int32_t xcorr_impl;       /* correlator actually used: 1 VALU, 2 f64 MFMA, 3 int8 screening, 4 bounded-lag correlator,
+                                 5 seeded correlator (nbls_set_lag_seed) */
     int32_t xcorr_fallback_bands; /* xcorr_impl == 3: bands whose window length does not fit the screening
                                    * kernel's LDS even with partner groups (> ~7900 samples) and ran on a general
                                    * correlator; the other bands of the plan were screened                    */
@@ -344,6 +345,52 @@ int nbls_beam_grid_lds_bytes(int32_t nelem, int32_t W, int32_t halo);
 int nbls_fetch_beam_grid(nbls_handle* h, int32_t* index, double* fstat, double* power);
 int nbls_fetch_beam_grid_map(nbls_handle* h, double* map);
 int nbls_fetch_beam_grid_delays(nbls_handle* h, int32_t* d);
+
+/* Seeded lag search: a plan with a slowness grid (nbls_set_beam_grid) and a seed table searches every
+ * pair's lag only near the delay the unit's grid maximum predicts — the whole-array beam chooses the cycle, the pairwise
+ * correlation is searched within half a period of it, and the existing solve runs on those picks.  For the unit of result
+ * row r, window w, band b of row r, g = grid_index[r][w], and pair k = (i, j), i < j, a, b the unit's windows of elements i
+ * and j, R(m) = sum_n a[n-m] b[n] (np.correlate(a, b, 'full')[W-1-m], as for nbls_set_lag_limits),
+ * cij = np.correlate(a, b, 'full') / sqrt(sum a^2 * sum b^2) and K = halfwidth[b] >= 0:
+ *   centre  c  = d[g][j] - d[g][i]   (int32 arithmetic on the plan's delay table, nbls_fetch_beam_grid_delays);  c = 0 if g == -1
+ *           c' = min(max(c, -(W-1)), W-1)
+ *   range   lo = max(c' - K, -(W-1)),  hi = min(c' + K, W-1)          (never empty)
+ *   lag     = hi - np.argmax(cij[W-1-hi : W-lo]);  quotients are compared as the plain pass compares them, with "no lag seen
+ *           yet" as the least element, and the first maximum in np.correlate index order wins: among equal maxima the LARGEST lag
+ *   cmax    = R(lag) / sqrt(sum a^2 * sum b^2)
+ *   an all-zero range gives lag = hi, cmax = 0; a dead channel lag = hi, cmax = NaN; a pair whose sum of squares of either
+ *           window is not finite (NaN or +-Inf samples) lag = hi, cmax = NaN — NumPy's answer for NaN samples, a deliberate
+ *           simplification for Inf samples (the reference has no seeded search: the contract is this library's)
+ *   K >= 2 (W-1) is the full search: the plain pass's lag
+ * The centre is d_j - d_i, the steering the beam used, not rint(fs xij_k . s): integer arithmetic on a table the caller can
+ * fetch.  MdCCM, the solve, the uncertainty, beam and refinement kernels and the gather of sub-array estimators read these
+ * picks as they read the plain pass's.  The order of every sum depends on (number of elements, W, range, lag) alone, no
+ * atomics are used and nothing depends on the launch's unit range: single, streamed, batched (nbls_set_segments) and
+ * window-sliced passes agree bit for bit.
+ *   nbls_set_lag_seed(h, halfwidth, nbands)   the table is copied and read by the next nbls_plan, like nbls_set_lag_limits;
+ *                            halfwidth NULL switches it off (the default: a plan without it queues the launches it queued
+ *                            before).  NBLS_ERR_ARG for a negative entry or nbands < 1, and the handle is then unchanged.
+ *                            nbls_plan returns NBLS_ERR_ARG if nbands differs from the plan's, NBLS_ERR_STATE if no grid is
+ *                            set, NBLS_ERR_UNSUPPORTED together with nbls_set_lag_limits (the grid's own extent bounds the
+ *                            slowness: one restriction at a time) or with xcorr_impl != 0.  Segments, window ranges and
+ *                            estimators are not refused: with segments halfwidth is indexed by band b of row r = b nseg + s,
+ *                            and a sub-array estimator reads the full array's picks.
+ *   nbls_lag_seed_form(nelem, W, max_halfwidth, halo)   a pure host function, like nbls_lag_limit_form: the form a window
+ *                            group of W-sample windows of nelem elements takes: 1 the staged form (3..16 elements whose
+ *                            windows and sums of squares, nelem (W + 1) doubles, fit 156 KiB of a CU's LDS; the staged block
+ *                            has no padding, so max_halfwidth and halo do not enter the rule), 2 the general form
+ *                            (everything else).  Never 0: every window group of a seeded plan takes the seeded correlator.
+ *                            NBLS_ERR_ARG for nelem outside 3..32, W < 2, max_halfwidth < 0 or halo < 0.  The launcher
+ *                            decides through the same function.  The two forms give the same bits.
+ * Stage order.  In a seeded plan the grid search belongs to the CORRELATION stage: per window group, on the handle's stream,
+ * the grid kernel over the group's units, then the seeded correlator, then refinement if the plan refines (and, when a pass
+ * solves per batch, the group's solve and result batch: a seeded group is one result batch of a streamed pass).  The solve
+ * stage does not run the grid kernel for such a plan.  The grid kernel and its outputs are those of the same plan without a
+ * seed, bit for bit, but they are written by stage bit 2 (the correlation stage) — zeros until a pass of the plan has run
+ * it, and nbls_execute_stages with only the solve bit leaves picks and grid results as they are — and the grid kernel's time
+ * falls inside xcorr_ms.  nbls_timings.xcorr_impl is 5 for a pass of a seeded plan. */
+int nbls_set_lag_seed(nbls_handle* h, const int32_t* halfwidth, int32_t nbands);
+int nbls_lag_seed_form(int32_t nelem, int32_t W, int32_t max_halfwidth, int32_t halo);
 
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);

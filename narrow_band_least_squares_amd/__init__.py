@@ -10,8 +10,9 @@ from .narrow_band_least_squares import (narrow_band_least_squares, narrow_band_l
                                         narrow_band_least_squares_parallel, narrow_band_least_squares_batch,
                                         narrow_band_least_squares_multi, narrow_band_least_squares_beam,
                                         narrow_band_least_squares_subsample, narrow_band_least_squares_bounded,
-                                        narrow_band_least_squares_grid)
-from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample, ltsva_bounded, ltsva_grid
+                                        narrow_band_least_squares_grid, narrow_band_least_squares_seeded)
+from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample, ltsva_bounded, ltsva_grid, \
+    ltsva_seeded
 from .helpers import (get_freqlist, get_winlenlist, filter_data, make_float, get_rij,
                       write_txtfile, read_txtfile)
 from .stream import Stream, Trace, Stats
@@ -22,7 +23,8 @@ __all__ = ['narrow_band_least_squares', 'narrow_band_loop', 'narrow_band_least_s
            'write_txtfile', 'read_txtfile', 'Stream', 'Trace', 'Stats', 'install_as_reference_modules', 'resident_trace',
            'narrow_band_least_squares_batch', 'ltsva_batch', 'narrow_band_least_squares_multi', 'ltsva_multi',
            'narrow_band_least_squares_beam', 'ltsva_beam', 'narrow_band_least_squares_subsample', 'ltsva_subsample',
-           'narrow_band_least_squares_bounded', 'ltsva_bounded', 'narrow_band_least_squares_grid', 'ltsva_grid']
+           'narrow_band_least_squares_bounded', 'ltsva_bounded', 'narrow_band_least_squares_grid', 'ltsva_grid',
+           'narrow_band_least_squares_seeded', 'ltsva_seeded']
 
 
 def install_as_reference_modules():

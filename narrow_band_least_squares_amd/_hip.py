@@ -26,7 +26,7 @@ EXPORTS = [
     'nbls_est_fetch_packed', 'nbls_est_fetch', 'nbls_est_fetch_uncertainty', 'nbls_est_wait_result_batch',
     'nbls_set_beam', 'nbls_fetch_beam', 'nbls_est_fetch_beam',
     'nbls_set_lag_refinement', 'nbls_fetch_lag_fraction', 'nbls_est_fetch_lag_fraction', 'nbls_refine_lds_bytes',
-    'nbls_set_lag_limits', 'nbls_lag_limit_form',
+    'nbls_set_lag_limits', 'nbls_lag_limit_form', 'nbls_set_lag_seed', 'nbls_lag_seed_form',
     'nbls_set_beam_grid', 'nbls_fetch_beam_grid', 'nbls_fetch_beam_grid_map', 'nbls_fetch_beam_grid_delays',
     'nbls_beam_grid_lds_bytes',
 ]
@@ -156,6 +156,8 @@ def load_library(path=None):
     lib.nbls_est_fetch_lag_fraction.argtypes = [vp, C.c_int32, dp]
     lib.nbls_set_lag_limits.argtypes = [vp, ip, C.c_int32]
     lib.nbls_lag_limit_form.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.nbls_set_lag_seed.argtypes = [vp, ip, C.c_int32]
+    lib.nbls_lag_seed_form.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.nbls_set_beam_grid.argtypes = [vp, dp, C.c_int32, C.c_int32]
     lib.nbls_fetch_beam_grid.argtypes = [vp, ip, dp, dp]
     lib.nbls_fetch_beam_grid_map.argtypes = [vp, dp]
@@ -568,6 +570,16 @@ class Handle:
         t = np.ascontiguousarray(max_lag, dtype=np.int32).ravel()
         self._chk(self.lib.nbls_set_lag_limits(self._h, _iptr(t), len(t)))
 
+    def set_lag_seed(self, halfwidth=None):
+        """The next plans — plans with a slowness grid (``set_beam_grid``) — search every pair's lag only within
+        ``halfwidth[b]`` samples of the delay the unit's grid maximum predicts for the pair (``nbls_set_lag_seed``,
+        DESIGN.md section 16; ``planner.seed_halfwidths`` makes the table, one entry per band); None switches that off."""
+        if halfwidth is None:
+            self._chk(self.lib.nbls_set_lag_seed(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(halfwidth, dtype=np.int32).ravel()
+        self._chk(self.lib.nbls_set_lag_seed(self._h, _iptr(t), len(t)))
+
     def stream_results(self, on=True):
         """The next passes deliver their rows batch by batch into a pinned host mirror of the result block
         (``nbls_stream_results``); see ``result_batches`` / ``wait_result_batch``."""
@@ -698,6 +710,15 @@ def lag_limit_form(nelem, W, min_limit):
     rc = load_library().nbls_lag_limit_form(int(nelem), int(W), int(min(int(min_limit), 2 ** 31 - 1)))
     if rc < 0:
         raise ValueError('nbls_lag_limit_form: arguments out of range')
+    return int(rc)
+
+
+def lag_seed_form(nelem, W, max_halfwidth=0, halo=0):
+    """The form a window group of W-sample windows of ``nelem`` elements takes in a seeded plan (``nbls_lag_seed_form``):
+    1 the staged form, 2 the general form."""
+    rc = load_library().nbls_lag_seed_form(int(nelem), int(W), int(min(int(max_halfwidth), 2 ** 31 - 1)), int(halo))
+    if rc < 0:
+        raise ValueError('nbls_lag_seed_form: arguments out of range')
     return int(rc)
 
 

@@ -784,7 +784,19 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if (a.xcorr_impl != 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: lag limits (nbls_set_lag_limits) need xcorr_impl 0: the forced correlators search every lag");
     }
+    if (!h->want_seed.empty()) {     // the lag seed (nbls_set_lag_seed): one half-width per band, a plan with a slowness grid, the auto route only
+        if ((int)h->want_seed.size() != a.nbands)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_seed.size()) + " seed half-widths (nbls_set_lag_seed) for a plan of " +
+                                             std::to_string(a.nbands) + " bands");
+        if (h->want_grid.empty())
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: the lag seed (nbls_set_lag_seed) needs a slowness grid (nbls_set_beam_grid)");
+        if (!h->want_lim.empty())
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the lag seed (nbls_set_lag_seed) is not supported together with lag limits (nbls_set_lag_limits): the grid's extent bounds the slowness, one restriction at a time");
+        if (a.xcorr_impl != 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the lag seed (nbls_set_lag_seed) needs xcorr_impl 0: the forced correlators search every lag");
+    }
     h->lim = h->want_lim;
+    h->seed = h->want_seed;
     h->beam = h->want_beam;
     h->beam_valid = false;
     h->refine = h->want_refine;
@@ -988,10 +1000,26 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
         }
         if (int rc = alloc_copy(h, h->d_limsq, sq.data(), sq.size())) return rc;
     }
+    int32_t max_seed = 0;
+    if (!h->seed.empty()) {          // the half-width of every result row: row r is band r / nseg
+        std::vector<int32_t> rows((size_t)R);
+        for (int r = 0; r < R; ++r) rows[(size_t)r] = h->seed[(size_t)(r / h->nseg)];
+        max_seed = *std::max_element(h->seed.begin(), h->seed.end());
+        for (size_t k = 0; k < h->h_pair.size(); ++k)
+            if (h->h_pair[k] < 0 || h->h_pair[k] >= h->nelem) return fail(h, NBLS_ERR_ARG, "nbls_plan: a pair of the geometry names an element the trace does not have");
+        if (int rc = alloc_copy(h, h->d_seed, rows.data(), rows.size())) return rc;
+    }
     for (int b = 0; b < R; ) {
         int e = b + 1;
         while (e < R && h->W[e] == h->W[b]) ++e;
         nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
+        // a plan with a lag seed: every group takes the seeded correlator in the general correlators' slot
+        if (!h->seed.empty()) {
+            g.sform = nbls_lag_seed_form_of(h->nelem, g.W, max_seed, h->grid_halo);
+            h->wgroups.push_back(g);
+            b = e;
+            continue;
+        }
         nbls_route r;                               // (xcorr_route.hip: the launchers take the same route)
         nbls_route_compute(nbls_route_query_of(h, g.W, R, 3, false), &r);
         g.screen = h->est[0].d_xij && r.correlator == NBLS_ROUTE_SCREEN;
@@ -1164,7 +1192,8 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     h->last_stage_mask = stage_mask;
     if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
     if (stage_mask & 4) h->solve_ran = true;
-    if (stage_mask & 4) h->grid_valid = true;            // (... and the grids of the slowness-grid search)
+    // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
+    if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
     if (stage_mask & 2) h->frac_valid = true;            // (... one without the correlation stage the lag fractions)
     // per-batch solves: behind each unit batch of the correlation stage (streamed results: a batch's rows are complete
     // while later batches are still being correlated), on the second stream with option "overlap"
@@ -1503,6 +1532,21 @@ int nbls_set_lag_limits(nbls_handle* h, const int32_t* max_lag, int32_t npairs) 
         if (max_lag[k] < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_limits: negative limit of pair " + std::to_string(k));
     h->want_lim.assign(max_lag, max_lag + npairs);               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
+}
+
+int nbls_set_lag_seed(nbls_handle* h, const int32_t* halfwidth, int32_t nbands) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!halfwidth) { h->want_seed.clear(); return NBLS_OK; }   // off: the next plan does not seed its lag search
+    if (nbands < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_seed: nbands must be at least 1");
+    for (int32_t b = 0; b < nbands; ++b)
+        if (halfwidth[b] < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_seed: negative half-width of band " + std::to_string(b));
+    h->want_seed.assign(halfwidth, halfwidth + nbands);         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    return NBLS_OK;
+}
+
+int nbls_lag_seed_form(int32_t nelem, int32_t W, int32_t max_halfwidth, int32_t halo) {
+    if (nelem < 3 || nelem > 32 || W < 2 || max_halfwidth < 0 || halo < 0) return NBLS_ERR_ARG;
+    return nbls_lag_seed_form_of(nelem, W, max_halfwidth, halo);
 }
 
 int nbls_lag_limit_form(int32_t nelem, int32_t W, int32_t min_limit) {

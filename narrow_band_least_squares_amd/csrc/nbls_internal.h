@@ -60,6 +60,7 @@ struct nbls_options {
 struct nbls_wgroup {
     int b0, b1, W; int64_t u0, u1; bool screen;
     int bform = 0;     // a plan with lag limits (nbls_set_lag_limits): 0 the ordinary route, 1 / 2 the form of the bounded-lag correlator
+    int sform = 0;     // a plan with a lag seed (nbls_set_lag_seed): 1 / 2 the form of the seeded correlator (0: no seed)
 };
 
 // One estimator of a pass: the geometry and LTS plan of ONE array (the full one or a sub-array) as the caller described
@@ -137,6 +138,12 @@ struct nbls_handle {
     std::vector<int32_t> want_lim;  // nbls_set_lag_limits: [npairs] max_lag per pair, read by the next nbls_plan (empty: off)
     std::vector<int32_t> lim;       // the plan's copy (empty: the plan searches every lag)
     dev_buf<int32_t> d_limsq;       // [nelem][nelem] the plan's limit of the pair of two elements, symmetric, 0 on the diagonal
+    // ---- seeded lag search (nbls_set_lag_seed, xcorr_seeded.hip): a plan with a slowness grid picks every pair's lag near the
+    // delay the unit's grid maximum predicts; the grid search then belongs to the correlation stage ----
+    std::vector<int32_t> want_seed; // nbls_set_lag_seed: [nbands] half-width per band, read by the next nbls_plan (empty: off)
+    std::vector<int32_t> seed;      // the plan's copy (empty: the plan does not seed)
+    dev_buf<int32_t> d_seed;        // [rows] the half-width of every result row (row r: band r / nseg)
+    bool seed_attr_set = false;     // the staged form of the seeded correlator has been given its dynamic LDS limit
     bool refine_attr_set = false;   // the LDS form of refine_lag_kernel has been given its dynamic LDS limit on this handle's device
     // ---- slowness-grid search of the beam F-statistic (nbls_set_beam_grid, beam_grid.hip) ----
     std::vector<double> want_grid;  // nbls_set_beam_grid: [G][2] slowness vectors, read by the next nbls_plan (empty: off)
@@ -274,7 +281,7 @@ struct nbls_handle {
     std::vector<hipEvent_t> bev;   // per-batch events of the screening path (5 per batch: quantize | screen | verify | solve)
     int bev_used = 0;
     bool prof_fused = false;       // the last profiled pass ran its solves per batch (bev[5k+4] recorded)
-    int xcorr_impl_used = 0;       // 1 VALU, 2 f64 MFMA, 3 int8 screening, 4 bounded-lag correlator (at least one window group)
+    int xcorr_impl_used = 0;       // 1 VALU, 2 f64 MFMA, 3 int8 screening, 4 bounded-lag correlator (at least one window group), 5 seeded correlator
     nbls_timings tim{};
 };
 
@@ -331,4 +338,8 @@ hipError_t nbls_xcorr_screen_finish(nbls_handle* h, int64_t launches);
 // min_limit: the smallest limit of the table) and the launch of units [ub, ue) of a group in form 1 / 2
 int nbls_lag_limit_form_of(int nelem, int W, int min_limit);
 hipError_t nbls_launch_xcorr_bounded(nbls_handle* h, int64_t ub, int64_t ue, int gW, int form);
+// seeded correlator (xcorr_seeded.hip): the form a window group takes (nbls_lag_seed_form is its C ABI form) and the launch
+// of units [ub, ue) of a group in form 1 / 2, behind the grid search of the same units on the handle's stream
+int nbls_lag_seed_form_of(int nelem, int W, int max_halfwidth, int halo);
+hipError_t nbls_launch_xcorr_seeded(nbls_handle* h, int64_t ub, int64_t ue, int gW, int form);
 hipError_t nbls_launch_probe_mfma_i8(nbls_handle* h, const int* da, const int* db, int* dout);

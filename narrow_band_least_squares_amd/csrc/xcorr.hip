@@ -335,7 +335,7 @@ hipError_t nbls_launch_xcorr(nbls_handle* h) {
     h->bev_used = 0;
     int64_t launches = 0;
     int used = 0, fallback_bands = 0;
-    bool any_screen = false, any_bounded = false;
+    bool any_screen = false, any_bounded = false, any_seeded = false;
     for (const nbls_wgroup& g : h->wgroups) {
         if (g.u1 <= g.u0) continue;
         hipError_t e;
@@ -343,7 +343,11 @@ hipError_t nbls_launch_xcorr(nbls_handle* h) {
             any_screen = true;
             e = nbls_launch_xcorr_screen_range(h, g.u0, g.u1, g.W, &launches);
         } else {
-            if (g.bform) {       // a plan with lag limits: the bounded-lag correlator in the general correlators' slot
+            if (g.sform) {       // a plan with a lag seed: the group's grid search, then the seeded correlator in the general correlators' slot
+                any_seeded = true;
+                e = nbls_launch_beam_grid(h, g.u0, g.u1 - g.u0, h->stream);
+                if (e == hipSuccess) e = nbls_launch_xcorr_seeded(h, g.u0, g.u1, g.W, g.sform);
+            } else if (g.bform) {       // a plan with lag limits: the bounded-lag correlator in the general correlators' slot
                 any_bounded = true;
                 e = nbls_launch_xcorr_bounded(h, g.u0, g.u1, g.W, g.bform);
             } else {
@@ -364,11 +368,11 @@ hipError_t nbls_launch_xcorr(nbls_handle* h) {
         if (e != hipSuccess) return e;
     }
     if (h->xcorr_impl == 3 && (any_screen || h->fuse_solve)) {
-        h->xcorr_impl_used = any_bounded ? 4 : 3;
+        h->xcorr_impl_used = any_seeded ? 5 : any_bounded ? 4 : 3;
         h->tim.xcorr_fallback_bands = fallback_bands;          // bands of this pass that ran on a general correlator
         return nbls_xcorr_screen_finish(h, launches);
     }
-    h->xcorr_impl_used = any_bounded ? 4 : used;
+    h->xcorr_impl_used = any_seeded ? 5 : any_bounded ? 4 : used;
     h->tim.xcorr_launches = launches;
     return hipGetLastError();
 }

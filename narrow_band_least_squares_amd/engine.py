@@ -462,7 +462,7 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
                       host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None,
-                      slowness_grid=None):
+                      slowness_grid=None, seed_halfwidths=None):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
@@ -470,7 +470,12 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     states; HBM holds one segment / one window slice at a time.  The filtered band stays on the host and the windows reach
     the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``; nor is
     the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM, nor the bounded lag
-    search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too."""
+    search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too,
+    nor the seeded lag search (``seed_halfwidths``), which rests on it."""
+    if seed_halfwidths is not None:
+        raise ValueError('seed_halfwidths: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
+                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
+                         'the seeded lag search is not available there' % _shape_of(data))
     if slowness_grid is not None:
         raise ValueError('slowness_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -582,7 +587,7 @@ def upload_trace(h, data, fs):
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False):
+           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -595,7 +600,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     ``lag_limits``: the plan searches the lag of pair k only within ``|lag| <= lag_limits[k]`` samples
     (``Handle.set_lag_limits``, ``planner.lag_limits``; likewise).  ``beam_grid`` (G, 2): the plan also searches the beam
     F-statistic of the full array over these slowness vectors, ``beam_grid_map``: and keeps every F(g)
-    (``Handle.set_beam_grid``; likewise)."""
+    (``Handle.set_beam_grid``; likewise).  ``lag_seed``: one half-width in samples per band of THIS plan (the bands
+    ``bands`` of the Prep, in their order): the plan searches every pair's lag only that near the delay the grid maximum
+    predicts (``Handle.set_lag_seed``, ``planner.seed_halfwidths``; needs ``beam_grid``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -623,6 +630,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_lag_limits(lag_limits)
     if beam_grid is not None:
         h.set_beam_grid(beam_grid, beam_grid_map)
+    if lag_seed is not None:
+        h.set_lag_seed(lag_seed)
     try:
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
@@ -635,6 +644,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_lag_limits(None)
         if beam_grid is not None:
             h.set_beam_grid(None)
+        if lag_seed is not None:
+            h.set_lag_seed(None)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -780,6 +791,7 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
     ``winlens`` — then ``launch``), group 0 while the trace is still going up (``up``).  Sequential rounds share one
     handle: each is collected before the next is planned.  -> the (handle, b0, b1) still to collect."""
     launched, prep = [], None
+    seed_all = launch_kw.get('lag_seed')
     nchans, npts = _shape_of(data)
     for g, (b0, b1) in enumerate(bounds):
         prep = prepare(nchans, npts, res.fs, rij, band_edges[b0:b1], winlens[b0:b1], *prep_tail, common=prep,
@@ -796,6 +808,8 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
         # itself between the passes and all of them land together at the end (stream priorities alone did the
         # job on some boxes and not on others)
         ordered = launched and not sequential and GROUP_ORDER
+        if launch_kw.get('lag_seed') is not None:         # (one half-width per band of the call: this group's)
+            launch_kw = dict(launch_kw, lag_seed=seed_all[b0:b1])
         try:
             launch(h, data, prep, trace_from=launched[0][0] if (launched and not sequential) else None, trace_ready=early,
                    after=launched[-1][0] if ordered else None, stream=streamed,
@@ -811,12 +825,25 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
     return launched
 
 
+def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
+    """``seed_halfwidths`` of ``process`` / ``process_batch`` -> int32 (nbands,) or None; ``ValueError`` before any GPU work."""
+    if seed_halfwidths is None:
+        return None
+    seeds = planner.check_seed_halfwidths(seed_halfwidths, nbands)
+    if sgrid is None:
+        raise ValueError('seed_halfwidths needs slowness_grid: the lag search is seeded by the grid maximum')
+    if min_velocity is not None:
+        raise ValueError('seed_halfwidths does not combine with min_velocity: the grid\'s own extent bounds the slowness, '
+                         'one restriction of the lag search at a time')
+    return seeds
+
+
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-            want_grid_map=False):
+            want_grid_map=False, seed_halfwidths=None):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -840,6 +867,11 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     and beam power there, searched on the GPU behind each unit's solve (``nbls_set_beam_grid``, DESIGN.md section 15);
     want_grid_map=True: also ``res.grid_map`` (nbands, vector_len, G), the ratio at every grid point.  ``ValueError`` before
     any GPU work for a bad grid (``planner.check_slowness_grid``); ``process_segmented`` refuses it.
+    seed_halfwidths (samples; one integer or one per band; needs ``slowness_grid``): every pair's lag is searched only
+    within that many samples of the delay the window's grid maximum predicts for the pair, and the grid search runs in the
+    correlation stage, ahead of the lag pick (``planner.seed_halfwidths``, ``nbls_set_lag_seed``, DESIGN.md section 16);
+    it does not combine with ``min_velocity``.  ``ValueError`` before any GPU work for a bad table
+    (``planner.check_seed_halfwidths``); ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -860,6 +892,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     nchans, npts = _shape_of(data)
     limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij)[0], fs, min_velocity)
     sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
+    seeds = _check_seed(seed_halfwidths, len(band_edges), sgrid, min_velocity)
     cap = max_bands_per_pass(nchans, npts)
     single = prefiltered or handle is not None or not upload
     up, resident = start_upload(data, fs, device) if upload and handle is None and (cap >= 1 or prefiltered) else (None, False)
@@ -869,7 +902,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam, want_subsample, min_velocity, sgrid)
+                                     group_done, want_beam, want_subsample, min_velocity, sgrid, seeds)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map)
@@ -878,7 +911,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
-                                 subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map))
+                                 subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
+                                 lag_seed=seeds)
     finally:
         if up is not None:
             up.close()
@@ -1100,7 +1134,7 @@ def batch_rows(streams):
 
 def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
-                  want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False):
+                  want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1116,6 +1150,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     nb = len(band_edges)
     sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
     G = 0 if sgrid is None else len(sgrid)
+    seeds = _check_seed(seed_halfwidths, nb, sgrid, min_velocity)
     prep = prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type, filter_order, filter_ripple,
                    vector_len, prefiltered)
     VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
@@ -1140,7 +1175,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 R = (b1 - b0) * k
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
-                       beam_grid_map=bool(want_grid_map))
+                       beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1])
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)

@@ -52,8 +52,8 @@ def _returns_grid(res, grid, want_map):
 
 
 def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
-           want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False):
-    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded`` and ``ltsva_grid``: the checks, the
+           want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False, seed_halfwidths=None):
+    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded``, ``ltsva_grid`` and ``ltsva_seeded``: the checks, the
     geometry, the device pass, the returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
@@ -72,7 +72,7 @@ def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_ar
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
                          prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
                          want_subsample=want_subsample, min_velocity=min_velocity, slowness_grid=slowness_grid,
-                         want_grid_map=grid_map)
+                         want_grid_map=grid_map, seed_halfwidths=seed_halfwidths)
     out = (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
     return out if slowness_grid is None else out + _returns_grid(res, slowness_grid, grid_map)
 
@@ -157,6 +157,25 @@ def ltsva_grid(st, lat_list, lon_list, window_length, window_overlap, slowness_g
     _check_elements_strict(len(st), alpha)
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, None, grid,
                   bool(grid_map))
+
+
+def ltsva_seeded(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, halfwidth, alpha=1.0, rij=None,
+                 grid_map=False):
+    """``ltsva_grid`` whose lag picks are seeded by the grid maximum — the two-step estimate: per window the whole-array
+    beam steered over ``slowness_grid`` chooses the cycle, every pair's cross-correlation is then searched only within
+    ``halfwidth`` samples of the delay ``d_j - d_i`` that grid point predicts for the pair (whole samples, the steering
+    the beam used), and the usual OLS / LTS solve runs on those picks with everything that hangs on them: ``sigma_tau``,
+    confidence intervals, dropped elements (DESIGN.md section 16 has the definition and the counts).  ``halfwidth`` is in
+    samples (an integer >= 0) because a filtered stream has no band edges to derive it from: half a period of the band's
+    upper edge, ``planner.seed_halfwidths([fmax], fs)[0]``, keeps the neighbouring cycle outside.  Returns ``ltsva_grid``'s
+    tuple; the grid returns are those of ``ltsva_grid``.  The search runs on the GPU (csrc/xcorr_seeded.hip).  A bad grid
+    or half-width, a ``grid_map`` that is not a bool and too few elements raise ``ValueError`` before any GPU work."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    seeds = planner.check_seed_halfwidths(halfwidth, 1)
+    _check_flag('grid_map', grid_map)
+    _check_elements_strict(len(st), alpha)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, None, grid,
+                  bool(grid_map), seeds)
 
 
 def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False,

@@ -92,7 +92,7 @@ def _prefix_stdict(stdict, band_number):
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
                key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-               want_grid_map=False):
+               want_grid_map=False, seed_period_fraction=None):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -105,6 +105,8 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
     edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
     winlens = [WINLEN_list[ii] for ii in bands]
     out_rows = {}
+    # the seeded lag search: half-widths from every band's upper edge (planner.seed_halfwidths)
+    seeds = None if seed_period_fraction is None else planner.seed_halfwidths([e[1] for e in edges], fs, seed_period_fraction)
 
     def host_side(res):
         # (the two response arrays are made here, while the GPU works: 1.5 MB of fresh pages before the first launch
@@ -131,7 +133,8 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
     res = engine.process(rows, fs, t0, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
-                         min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map)
+                         min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map,
+                         seed_halfwidths=seeds)
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -255,6 +258,38 @@ def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
                                        FILTER_RIPPLE, vector_len, rij=rij,
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], slowness_grid=grid,
                                        want_grid_map=bool(grid_map))
+    gvel, gbaz = grid_slowness(grid, res.grid_index)
+    computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + \
+        ((res.grid_map,) if grid_map else ())
+
+
+def narrow_band_least_squares_seeded(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                     FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                     slowness_grid, period_fraction=0.5, grid_map=False):
+    """``narrow_band_least_squares_grid`` whose lag picks are seeded by the grid maximum (``lts_array.ltsva_seeded``;
+    DESIGN.md section 16): in every band and window the whole-array beam steered over ``slowness_grid`` chooses the cycle,
+    every pair's lag is searched only within ``K_b = max(1, floor(period_fraction fs / fmax_b))`` samples of the delay that
+    grid point predicts for the pair (``planner.seed_halfwidths``: by default half a period of the band's upper edge), and
+    the solve runs on those picks, on the GPU (csrc/xcorr_seeded.hip).  Returns ``narrow_band_least_squares_grid``'s tuple;
+    ``t``, the window counts and the grid returns are the same.  A bad grid or ``period_fraction`` raises ``ValueError``
+    before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    planner.seed_halfwidths([1.0], 1.0, period_fraction)         # (the check of period_fraction, before any GPU work)
+    if not isinstance(grid_map, (bool, np.bool_)):
+        raise ValueError('grid_map must be True or False, not %r' % (grid_map,))
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], slowness_grid=grid,
+                                       want_grid_map=bool(grid_map), seed_period_fraction=period_fraction)
     gvel, gbaz = grid_slowness(grid, res.grid_index)
     computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
     gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)

@@ -489,6 +489,50 @@ def check_slowness_grid(grid):
     return g
 
 
+def seed_halfwidths(fmax_list, fs, period_fraction=0.5):
+    """Per-band half-widths of the seeded lag search (``nbls_set_lag_seed``) -> int32 (nbands,):
+    ``K_b = max(1, int(floor(period_fraction * fs / fmax_b)))`` samples — by default half a period of the band's upper edge,
+    so that the neighbouring cycle, one period away from the delay the grid maximum predicts, stays outside the range
+    (18 samples for 1.1 Hz at 40 Hz).  ``ValueError`` unless every ``fmax_b`` and ``fs`` is a finite real > 0 and
+    ``period_fraction`` a finite real in (0, 1]."""
+    def real(v):
+        return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+    if not real(fs) or not np.isfinite(float(fs)) or float(fs) <= 0.0:
+        raise ValueError('fs must be a finite sampling rate in Hz above 0, not %r' % (fs,))
+    if not real(period_fraction) or not (0.0 < float(period_fraction) <= 1.0):
+        raise ValueError('period_fraction must be a number in (0, 1], not %r' % (period_fraction,))
+    try:
+        f = np.asarray(fmax_list)
+    except Exception:
+        raise ValueError('fmax_list must be a list of upper band edges in Hz')
+    if f.dtype == object or f.dtype.kind not in 'iuf' or f.ndim != 1 or f.size < 1:
+        raise ValueError('fmax_list must be a non-empty list of upper band edges in Hz, not %r' % (fmax_list,))
+    f = f.astype(np.float64)
+    if not np.all(np.isfinite(f)) or np.any(f <= 0.0):
+        raise ValueError('fmax_list must hold finite frequencies above 0 Hz')
+    K = np.floor(float(period_fraction) * float(fs) / f)
+    return np.maximum(1.0, np.minimum(K, 2.0 ** 31 - 1)).astype(np.int32)
+
+
+def check_seed_halfwidths(halfwidth, nbands):
+    """``halfwidth`` of the seeded lag search (samples; one integer for every band, or ``nbands`` of them) -> int32
+    (nbands,); ``ValueError`` (before any GPU work) unless the entries are integers in 0 .. 2^31-1 and their number fits."""
+    try:
+        k = np.asarray(halfwidth)
+    except Exception:
+        raise ValueError('halfwidth must be an integer number of samples or one per band')
+    if k.dtype == object or k.dtype.kind not in 'iu' or k.ndim > 1:
+        raise ValueError('halfwidth must be an integer number of samples (or one per band), not %r' % (halfwidth,))
+    k = np.atleast_1d(k).astype(np.int64)
+    if k.size == 1 and nbands > 1:
+        k = np.repeat(k, nbands)
+    if k.size != nbands:
+        raise ValueError('halfwidth has %d entries for %d bands' % (k.size, nbands))
+    if np.any(k < 0) or np.any(k > 2 ** 31 - 1):
+        raise ValueError('halfwidth must be 0 .. 2^31-1 samples, not %r' % (halfwidth,))
+    return np.ascontiguousarray(k, dtype=np.int32)
+
+
 def lag_limits(xij, fs, min_velocity):
     """Per-pair lag limits of the bounded search (``nbls_set_lag_limits``) -> int32 (P,):
     ``L_k = int(ceil(fs * hypot(xij[k, 0], xij[k, 1]) / min_velocity)) + 1`` samples — the delay a plane wave no slower
