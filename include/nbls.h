@@ -392,6 +392,42 @@ int nbls_fetch_beam_grid_delays(nbls_handle* h, int32_t* d);
 int nbls_set_lag_seed(nbls_handle* h, const int32_t* halfwidth, int32_t nbands);
 int nbls_lag_seed_form(int32_t nelem, int32_t W, int32_t max_halfwidth, int32_t halo);
 
+/* Closure (consistency) of the picked lags, computed on the GPU behind every unit's solve when
+ * wanted: for three elements i < j < k the lags of any single coherent arrival satisfy l_ij + l_jk - l_ik = 0, whatever its
+ * slowness, its wavefront's curvature or the elements' clock offsets (Cansi 1995); only noise, cycle skips and several
+ * arrivals break it.  The definition is per estimator: N is that estimator's element count (estimator 0: every element; a
+ * further one: its nkept elements), its pair list the lexicographic one of P' = N (N-1) / 2 pairs, k(i,j) the index of pair
+ * (i, j), i < j, in that list.  For the unit of result row r, window w:
+ *   t_ij     plan without lag refinement:  t_ij = lag[k(i,j)]                     (int32, exactly the lag of nbls_fetch / nbls_est_fetch)
+ *            plan with lag refinement:     t_ij = (double)lag[k(i,j)] + frac[k(i,j)]   (the sum every other site forms, un-fused double)
+ *   closure  c_ijk = (t_ij + t_jk) − t_ik           for i < j < k;  T = N (N−1)(N−2) / 6 triplets
+ *   sums     Q = Σ_{i<j<k} c_ijk²,   E_m = Σ_{triplets that contain element m} c_ijk²,   T_m = (N−1)(N−2) / 2
+ *   outputs  consistency            = sqrt(Q / T) / fs                          seconds, [rows][VL]
+ *            closure_max            = max_{i<j<k} |c_ijk| / fs                  seconds, [rows][VL]
+ *            element_consistency[m] = sqrt(E_m / T_m) / fs                      seconds, [rows][VL][N]
+ * Without refinement c, Q and E_m are computed exactly in integers (int64: |c| <= 3 (W-1)), converted to double once, and
+ * the three double operations are done in that order.  With refinement everything is un-fused IEEE double and the order of
+ * every sum depends on N alone; no floating-point atomics are used and nothing depends on the launch's unit range: single,
+ * streamed, batched (nbls_set_segments) and window-sliced passes agree bit for bit, and a sub-array estimator agrees bit
+ * for bit with a separate call on the sub-array.  Cells beyond nwin[r] (and outside a window slice) are zeros, and so is
+ * everything for an array of fewer than three elements.  The results follow whatever picks the plan made: full, bounded
+ * (nbls_set_lag_limits) or seeded (nbls_set_lag_seed).  Lags are finite integers and fractions are finite: no NaN rule.
+ *   nbls_set_closure(h, on)  read by the next nbls_plan, like nbls_set_beam; a plan without it is launch for launch the
+ *                            plain pass.  nbls_plan returns NBLS_ERR_UNSUPPORTED with an RCCL communicator (the gathered
+ *                            block does not carry the grids) and NBLS_ERR_STATE without the geometry of the trace's array
+ *                            (every pair, in lexicographic order).  Segments, window ranges, estimators, lag limits, grid,
+ *                            seed and refinement are not refused.
+ *   nbls_fetch_closure(h, consistency, closure_max, element_consistency)   [rows][vector_len], [rows][vector_len] and
+ *                            [rows][vector_len][nelem] (any may be NULL), rows as for nbls_fetch; waits for the pass like
+ *                            nbls_fetch_beam.  NBLS_ERR_STATE if the plan did not ask for closure results.  The grids are
+ *                            written by the solve stage alone: zeros until a pass of the plan has run it, and
+ *                            nbls_execute_stages without the solve bit leaves them as they are.
+ *   nbls_est_fetch_closure(h, e, ...)   the same for estimator e, element rows [rows][vector_len][nkept_e]
+ *                            (nbls_set_estimators).
+ * nbls_timings is unchanged: the kernel's time falls inside the solve interval. */
+int nbls_set_closure(nbls_handle* h, int32_t on);
+int nbls_fetch_closure(nbls_handle* h, double* consistency, double* closure_max, double* element_consistency);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 
@@ -486,6 +522,7 @@ int nbls_est_fetch(nbls_handle* h, int32_t e, double* vel, double* baz, double* 
                    int32_t* lag, double* cmax, uint8_t* weights, double* z);
 int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t e, double* vel_uncert, double* baz_uncert);
 int nbls_est_fetch_beam(nbls_handle* h, int32_t e, double* beam_power, double* fstat);
+int nbls_est_fetch_closure(nbls_handle* h, int32_t e, double* consistency, double* closure_max, double* element_consistency);
 int nbls_est_wait_result_batch(nbls_handle* h, int32_t e, int32_t k, int64_t* out4, const void** host_block);
 
 /* ---- multi-GPU: ONE grouped RCCL operation collects every GPU's result block ----------------------

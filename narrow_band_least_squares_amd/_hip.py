@@ -29,6 +29,7 @@ EXPORTS = [
     'nbls_set_lag_limits', 'nbls_lag_limit_form', 'nbls_set_lag_seed', 'nbls_lag_seed_form',
     'nbls_set_beam_grid', 'nbls_fetch_beam_grid', 'nbls_fetch_beam_grid_map', 'nbls_fetch_beam_grid_delays',
     'nbls_beam_grid_lds_bytes',
+    'nbls_set_closure', 'nbls_fetch_closure', 'nbls_est_fetch_closure',
 ]
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
@@ -150,6 +151,9 @@ def load_library(path=None):
     lib.nbls_set_beam.argtypes = [vp, C.c_int32]
     lib.nbls_fetch_beam.argtypes = [vp, dp, dp]
     lib.nbls_est_fetch_beam.argtypes = [vp, C.c_int32, dp, dp]
+    lib.nbls_set_closure.argtypes = [vp, C.c_int32]
+    lib.nbls_fetch_closure.argtypes = [vp, dp, dp, dp]
+    lib.nbls_est_fetch_closure.argtypes = [vp, C.c_int32, dp, dp, dp]
     lib.nbls_set_lag_refinement.argtypes = [vp, C.c_int32]
     lib.nbls_fetch_lag_fraction.argtypes = [vp, dp]
     lib.nbls_refine_lds_bytes.argtypes = [C.c_int32, C.c_int32]
@@ -513,6 +517,27 @@ class Handle:
         else:
             self._chk(self.lib.nbls_est_fetch_beam(self._h, int(e), _dptr(out[0]), _dptr(out[1])))
         return out[0], out[1]
+
+    def set_closure(self, on=True):
+        """The next plans also compute, behind every unit's solve, the closure of the picked lags per window and per
+        element (``nbls_set_closure``); False switches that off."""
+        self._chk(self.lib.nbls_set_closure(self._h, int(bool(on))))
+
+    def _est_elements(self, e):
+        if e == 0:
+            return self.nchans // self.nseg
+        return int(round((1.0 + (1.0 + 8.0 * self.est_npairs[e - 1]) ** 0.5) / 2.0))      # P' = n (n - 1) / 2
+
+    def fetch_closure(self, e=0):
+        """-> (consistency, closure_max, element_consistency) of estimator ``e``: (rows, vector_len) twice and
+        (rows, vector_len, N), N that estimator's element count; seconds."""
+        out = np.empty((2, self.nbands, self.vector_len))
+        el = np.empty((self.nbands, self.vector_len, max(self._est_elements(e), 1)))
+        if e == 0:
+            self._chk(self.lib.nbls_fetch_closure(self._h, _dptr(out[0]), _dptr(out[1]), _dptr(el)))
+        else:
+            self._chk(self.lib.nbls_est_fetch_closure(self._h, int(e), _dptr(out[0]), _dptr(out[1]), _dptr(el)))
+        return out[0], out[1], el
 
     def set_beam_grid(self, grid=None, want_map=False):
         """The next plans also search, per window, the beam F-statistic of the full array over the slowness vectors

@@ -330,6 +330,11 @@ int size_result_buffers(nbls_handle* h, nbls_estimator& x, size_t cells, size_t 
     if ((rc = ensure(h, x.d_wts, cells * P))) return rc;
     if (x.want_unc && (rc = ensure(h, x.d_unc, 2 * cells * sizeof(double)))) return rc;
     if (h->beam && (rc = ensure(h, x.d_beam, 2 * cells * sizeof(double)))) return rc;
+    if (h->closure) {
+        const size_t N = own ? (size_t)h->nelem : x.kept.size();
+        if ((rc = ensure(h, x.d_closure, 2 * cells * sizeof(double)))) return rc;
+        if ((rc = ensure(h, x.d_closure_el, cells * (N ? N : 1) * sizeof(double)))) return rc;
+    }
     return 0;
 }
 
@@ -764,6 +769,17 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
     if (h->want_beam && h->comm)
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: beam results (nbls_set_beam) are not supported with an RCCL communicator (the gathered block does not carry them)");
+    if (h->want_closure) {           // closure of the picked lags (nbls_set_closure): every pair of the trace's array, in list order
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: closure results (nbls_set_closure) are not supported with an RCCL communicator (the gathered block does not carry them)");
+        const int En = h->nchans / NS;
+        bool full = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
+        for (int i = 0, k = 0; full && i < En; ++i)
+            for (int j = i + 1; j < En; ++j, ++k)
+                if (h->h_pair[2 * k] != i || h->h_pair[2 * k + 1] != j) { full = false; break; }
+        if (!full)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: closure results (nbls_set_closure) need the geometry of the trace's array, every pair in lexicographic order");
+    }
     std::vector<int32_t> gdel;       // the slowness grid (nbls_set_beam_grid): its delay table for this trace's array
     int ghalo = 0;
     if (!h->want_grid.empty()) {
@@ -799,6 +815,8 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->seed = h->want_seed;
     h->beam = h->want_beam;
     h->beam_valid = false;
+    h->closure = h->want_closure;
+    h->closure_valid = false;
     h->refine = h->want_refine;
     h->frac_valid = false;
     h->solve_ran = false;
@@ -1191,6 +1209,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     h->solve_done = false;
     h->last_stage_mask = stage_mask;
     if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
+    if ((stage_mask & 4) && h->closure) h->closure_valid = true;      // (likewise the closure grids)
     if (stage_mask & 4) h->solve_ran = true;
     // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
     if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
@@ -1449,6 +1468,39 @@ int nbls_est_fetch_beam(nbls_handle* h, int32_t est, double* beam_power, double*
         if (!h->beam_valid) { memset(outs[g], 0, cells * sizeof(double)); continue; }
         HIPCHK(h, copy_sync(h, outs[g], s.d_beam + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
         zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
+    }
+    return NBLS_OK;
+}
+
+int nbls_set_closure(nbls_handle* h, int32_t on) {
+    if (!h) return NBLS_ERR_ARG;
+    h->want_closure = on != 0;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    return NBLS_OK;
+}
+
+int nbls_fetch_closure(nbls_handle* h, double* consistency, double* closure_max, double* element_consistency) {
+    return nbls_est_fetch_closure(h, 0, consistency, closure_max, element_consistency);
+}
+
+int nbls_est_fetch_closure(nbls_handle* h, int32_t est, double* consistency, double* closure_max, double* element_consistency) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_closure: no plan");
+    if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_closure: no such estimator");
+    const nbls_estimator& s = h->est[est];
+    if (!h->closure || !s.d_closure || !s.d_closure_el) return fail(h, NBLS_ERR_STATE, "nbls_fetch_closure: nbls_set_closure before nbls_plan");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    const size_t N = s.kept.empty() ? (size_t)h->nelem : s.kept.size();
+    // the grids are written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass
+    // without it leaves them as they are
+    double* outs[3] = {consistency, closure_max, element_consistency};
+    const double* srcs[3] = {s.d_closure.p, s.d_closure.p + cells, s.d_closure_el.p};
+    for (int g = 0; g < 3; ++g) {
+        if (!outs[g]) continue;
+        const size_t row = (g == 2 ? N : 1) * sizeof(double);
+        if (!h->closure_valid) { memset(outs[g], 0, cells * row); continue; }
+        HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * row, hipMemcpyDeviceToHost));
+        zero_uncomputed(h, outs[g], row);                 // like the grids
     }
     return NBLS_OK;
 }

@@ -99,6 +99,8 @@ struct nbls_estimator {
     dev_buf<double> d_unc;             // [2][B][VL]: vel_uncert | baz_uncert
     dev_buf<int32_t> d_kept;           // [K] the kept elements' rows (a plan with beam results, est[1..]; est[0] takes every row)
     dev_buf<double> d_beam;            // [2][B][VL]: beam_power | fstat (a plan with beam results, nbls_set_beam)
+    dev_buf<double> d_closure;         // [2][B][VL]: consistency | closure_max (a plan with closure results, nbls_set_closure)
+    dev_buf<double> d_closure_el;      // [B][VL][N]: element_consistency, N this estimator's element count (likewise)
     // result block, ONE allocation = one D2H copy / one RCCL gather:
     //   [vel | baz | mdccm | sigma_tau] double[4][B][VL], then the LTS weight bit mask uint8[B][VL][MB],
     //   MB = ceil(P'/8), bit k & 7 of byte k >> 3 = weight of pair k (ceil(P/8) bytes per unit)
@@ -131,6 +133,9 @@ struct nbls_handle {
     bool want_beam = false;         // nbls_set_beam: read by the next nbls_plan
     bool beam = false;              // the plan computes beam power and F-statistic behind every estimator's solve (beam.hip)
     bool beam_valid = false;        // a pass of this plan has run the solve stage: est[].d_beam holds results
+    bool want_closure = false;      // nbls_set_closure: read by the next nbls_plan
+    bool closure = false;           // the plan computes the closure of the picked lags behind every estimator's solve (closure.hip)
+    bool closure_valid = false;     // a pass of this plan has run the solve stage: est[].d_closure / d_closure_el hold results
     bool want_refine = false;       // nbls_set_lag_refinement: read by the next nbls_plan
     bool refine = false;            // the plan refines the picked lags to sub-sample precision behind the verifier (refine.hip)
     bool frac_valid = false;        // a pass of this plan has run the correlation stage: d_lagfrac holds results
@@ -309,6 +314,8 @@ hipError_t nbls_launch_refine(nbls_handle* h, int64_t u0, int64_t nu, int gW, hi
 size_t nbls_refine_lds_bytes_of(int nelem, int W);
 // beam power and F-statistic of units [u0, u0 + nu) at the slowness estimator x has solved for them (beam.hip)
 hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
+// closure of the picked lags of units [u0, u0 + nu), per window and per element of estimator x (closure.hip)
+hipError_t nbls_launch_closure(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // slowness-grid search of the beam F-statistic over units [u0, u0 + nu) for the plan's full array (beam_grid.hip)
 hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 // dynamic LDS bytes of the form beam_grid_kernel takes for windows of W samples of nelem elements and a halo of `halo`
@@ -316,7 +323,7 @@ hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStre
 size_t nbls_beam_grid_lds_bytes_of(int nelem, int W, int halo);
 // the delay table d[G][nelem] of a grid and its halo (host, un-fused arithmetic); false: some |fs xij . s_g| reaches 2^30
 bool nbls_beam_grid_delays_of(const double* xij, int nelem, double fs, const double* grid, int G, int32_t* d, int* halo);
-// [gather ->] solve -> [uncertainty ->] [beam ->] [grid search ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
+// [gather ->] solve -> [uncertainty ->] [beam ->] [closure ->] [grid search ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
 hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);

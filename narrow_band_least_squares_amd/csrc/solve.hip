@@ -1435,6 +1435,7 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (h->beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
+    if (h->closure && s.d_closure && (e = nbls_launch_closure(h, s, u0, nu, st)) != hipSuccess) return e;
     // the slowness-grid search of a plan that asked for one: the full array only, behind the plan's own estimator (a plan
     // with a lag seed has run it in the correlation stage, ahead of the seeded correlator: once per pass)
     if (h->grid_n > 0 && h->seed.empty() && &s == &h->est[0] && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;

@@ -362,13 +362,17 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 
 
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
-               want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False):
+               want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
+               want_consistency=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
     lags are wanted.  ``grid_points`` > 0: ``grid_index`` / ``grid_fstat`` / ``grid_power`` of a slowness-grid search over that
-    many points, and with ``want_grid_map`` its ``grid_map`` (nbands, vector_len, grid_points)."""
+    many points, and with ``want_grid_map`` its ``grid_map`` (nbands, vector_len, grid_points).  ``want_consistency``:
+    ``consistency`` / ``closure_max`` (nbands, vector_len) and ``element_consistency`` (nbands, vector_len, nchans), the
+    closure of the picked lags."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
+    clo = np.zeros((2, nb, vector_len)) if want_consistency else (None, None)
     gfp = np.zeros((2, nb, vector_len)) if grid_points else (None, None)
     grids = np.zeros((4, nb, vector_len))
     unc = np.zeros((2, nb, vector_len)) if want_uncert else (None, None)
@@ -379,7 +383,8 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      lag_frac=np.zeros((nb, vector_len, P)) if (want_lag and want_subsample) else None,
                      cmax=np.zeros((nb, vector_len, P)) if want_cmax else None,
                      z=np.zeros((nb, vector_len, 2)) if want_z else None, vel_uncert=unc[0], baz_uncert=unc[1],
-                     beam_power=beam[0], fstat=beam[1],
+                     beam_power=beam[0], fstat=beam[1], consistency=clo[0], closure_max=clo[1],
+                     element_consistency=np.zeros((nb, vector_len, nchans)) if want_consistency else None,
                      grid_index=np.zeros((nb, vector_len), dtype=np.int32) if grid_points else None, grid_fstat=gfp[0],
                      grid_power=gfp[1],
                      grid_map=np.zeros((nb, vector_len, grid_points)) if (grid_points and want_grid_map) else None, sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
@@ -462,7 +467,7 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
                       host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None,
-                      slowness_grid=None, seed_halfwidths=None):
+                      slowness_grid=None, seed_halfwidths=None, want_consistency=False):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
@@ -471,7 +476,12 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``; nor is
     the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM, nor the bounded lag
     search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too,
-    nor the seeded lag search (``seed_halfwidths``), which rests on it."""
+    nor the seeded lag search (``seed_halfwidths``), which rests on it, nor the closure of the picked lags
+    (``want_consistency``), which reads the lag table of a whole pass in HBM."""
+    if want_consistency:
+        raise ValueError('want_consistency: a trace of %d x %d samples takes the time-segmented path (not even one filtered '
+                         'band fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which correlates the band slice by '
+                         'slice: closure results are not available there' % _shape_of(data))
     if seed_halfwidths is not None:
         raise ValueError('seed_halfwidths: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -587,7 +597,7 @@ def upload_trace(h, data, fs):
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None):
+           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -602,7 +612,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     F-statistic of the full array over these slowness vectors, ``beam_grid_map``: and keeps every F(g)
     (``Handle.set_beam_grid``; likewise).  ``lag_seed``: one half-width in samples per band of THIS plan (the bands
     ``bands`` of the Prep, in their order): the plan searches every pair's lag only that near the delay the grid maximum
-    predicts (``Handle.set_lag_seed``, ``planner.seed_halfwidths``; needs ``beam_grid``; likewise)."""
+    predicts (``Handle.set_lag_seed``, ``planner.seed_halfwidths``; needs ``beam_grid``; likewise).  ``closure``: the plan
+    also computes the closure of the picked lags behind every solve (``Handle.set_closure``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -624,6 +635,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     h.set_uncertainty(planner.uncertainty_frame(prep.xij) if uncert else None)     # (ltsva's confidence intervals, on request)
     if beam:
         h.set_beam(True)
+    if closure:
+        h.set_closure(True)
     if subsample:
         h.set_lag_refinement(True)
     if lag_limits is not None:
@@ -638,6 +651,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     finally:
         if beam:
             h.set_beam(False)            # (the handle is shared with calls that plan for themselves)
+        if closure:
+            h.set_closure(False)
         if subsample:
             h.set_lag_refinement(False)
         if lag_limits is not None:
@@ -762,6 +777,8 @@ def collect(res, h, b0, b1, streamed, note):
         res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty()
     if res.beam_power is not None:
         res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam()
+    if res.consistency is not None:
+        res.consistency[b0:b1], res.closure_max[b0:b1], res.element_consistency[b0:b1] = h.fetch_closure()
     if res.lag_frac is not None:
         res.lag_frac[b0:b1] = h.fetch_lag_fraction()
     if res.grid_index is not None:
@@ -843,7 +860,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-            want_grid_map=False, seed_halfwidths=None):
+            want_grid_map=False, seed_halfwidths=None, want_consistency=False):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -872,6 +889,11 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     correlation stage, ahead of the lag pick (``planner.seed_halfwidths``, ``nbls_set_lag_seed``, DESIGN.md section 16);
     it does not combine with ``min_velocity``.  ``ValueError`` before any GPU work for a bad table
     (``planner.check_seed_halfwidths``); ``process_segmented`` refuses it.
+    want_consistency=True: also ``res.consistency`` / ``res.closure_max`` (nbands, vector_len) and
+    ``res.element_consistency`` (nbands, vector_len, N), seconds: the rms and the largest closure ``l_ij + l_jk - l_ik`` of
+    the picked lags over the element triplets of each window, and per element the rms over the triplets that hold it,
+    computed on the GPU behind each unit's solve (``nbls_set_closure``); they follow whatever picks
+    the call makes (refined, bounded, seeded); ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -902,17 +924,17 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam, want_subsample, min_velocity, sgrid, seeds)
+                                     group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
-                         want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map)
+                         want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds)
+                                 lag_seed=seeds, closure=bool(want_consistency))
     finally:
         if up is not None:
             up.close()
@@ -1003,7 +1025,7 @@ class _EstimatorResults:
 def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_lag=False,
                   want_cmax=False, host_overlap=None, units_done=None, want_beam=False, want_subsample=False,
-                  min_velocity=None):
+                  min_velocity=None, want_consistency=False):
     """``process`` for several estimators ``(alpha, remove)`` of ONE trace in one device pass -> a list of ``BandBatch``,
     element e what ``process`` gives for ``alpha_e`` on the rows that ``remove_e`` leaves (``estimators`` as
     ``normalize_estimators`` returns them; ``rijs[e]``: the (2, kept) geometry of estimator e, ``t0s[e]`` its start date).
@@ -1018,7 +1040,9 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     units [u0, u1) (flat over all bands) of estimator e are in ``results[e]``.  ``want_beam``: every estimator's
     ``beam_power`` / ``fstat``, of ITS elements at ITS slowness (``process``).  ``want_subsample``: the pass refines the full
     array's lags once and every estimator solves on the refined delays of ITS pairs (``lag_frac`` with ``want_lag``).
-    ``min_velocity``: the full array's lags are searched within their physical range (``process``); a sub-array reads them."""
+    ``min_velocity``: the full array's lags are searched within their physical range (``process``); a sub-array reads them.
+    ``want_consistency``: every estimator's ``consistency`` / ``closure_max`` / ``element_consistency``, the closure of the
+    picked lags over the triplets of ITS elements (``process``)."""
     rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
     nchans, npts = _shape_of(rows)
     nb = len(band_edges)
@@ -1044,7 +1068,8 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     results = [None] * len(estimators)
     for i, (alpha, remove) in enumerate(estimators):
         res = new_result(nchans - len(remove), alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax,
-                         want_uncert=want_uncert, want_beam=want_beam, want_subsample=want_subsample)
+                         want_uncert=want_uncert, want_beam=want_beam, want_subsample=want_subsample,
+                         want_consistency=want_consistency)
         res.xij, res.pair_idx, _ = planner.co_array(rijs[i])
         results[i] = res
     streamed = stream_pays(min(a for a, _ in estimators), nwin, nchans * (nchans - 1) // 2)
@@ -1062,7 +1087,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
             try:
                 launch(h, rows, prep, trace_ready=joins or resident or b0 > 0, stream=streamed, uncert=want_uncert,
                        before_execute=up.landed if (joins and not up.row_pipeline) else None, estimators=extras,
-                       beam=want_beam, subsample=want_subsample, lag_limits=limits)
+                       beam=want_beam, subsample=want_subsample, lag_limits=limits, closure=bool(want_consistency))
             finally:
                 if joins:
                     up.landed()
@@ -1097,6 +1122,8 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
                     res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty(est=est)
                 if want_beam:
                     res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam(est)
+                if want_consistency:
+                    res.consistency[b0:b1], res.closure_max[b0:b1], res.element_consistency[b0:b1] = h.fetch_closure(est)
                 if res.lag_frac is not None:
                     res.lag_frac[b0:b1] = h.fetch_lag_fraction(est)
     finally:
@@ -1134,7 +1161,8 @@ def batch_rows(streams):
 
 def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
-                  want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None):
+                  want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
+                  want_consistency=False):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1160,7 +1188,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
                          'process it on its own' % (nchans, npts))
     out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
-                      grid_points=G, want_grid_map=want_grid_map)
+                      grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1175,7 +1203,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 R = (b1 - b0) * k
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
-                       beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1])
+                       beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
+                       closure=bool(want_consistency))
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
@@ -1183,6 +1212,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 m = m.reshape(b1 - b0, k, VL, MB)
                 unc = np.stack(h.fetch_uncertainty()).reshape(2, b1 - b0, k, VL) if want_uncert else None
                 beam = np.stack(h.fetch_beam()).reshape(2, b1 - b0, k, VL) if want_beam else None
+                clo = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_closure()] if want_consistency else None
                 sg = [a.reshape(b1 - b0, k, VL) for a in h.fetch_beam_grid()] if G else None
                 sgmap = h.fetch_beam_grid_map().reshape(b1 - b0, k, VL, G) if (G and want_grid_map) else None
                 for j, res in enumerate(out[s0:s0 + k]):
@@ -1192,6 +1222,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                         res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = unc[:, :, j]
                     if want_beam:
                         res.beam_power[b0:b1], res.fstat[b0:b1] = beam[:, :, j]
+                    if want_consistency:
+                        res.consistency[b0:b1], res.closure_max[b0:b1], res.element_consistency[b0:b1] = [a[:, j] for a in clo]
                     if G:
                         res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = [a[:, j] for a in sg]
                     if sgmap is not None:

@@ -28,6 +28,13 @@ def _returns_beam(res, nchans, alpha, keys=None):
     return _returns(res, nchans, alpha, keys) + (res.beam_power[0, :n].copy(), res.fstat[0, :n].copy())
 
 
+def _returns_consistency(res):
+    """The band's ``consistency``, ``closure_max`` (nwin,) and ``element_consistency`` (nwin, N) (csrc/closure.hip:
+    closure_kernel)."""
+    n = int(res.nwin[0])
+    return res.consistency[0, :n].copy(), res.closure_max[0, :n].copy(), res.element_consistency[0, :n].copy()
+
+
 def grid_slowness(grid, index):
     """The slowness vectors ``grid[index]`` of a grid search as ``ltsva`` reports a slowness -> (grid_vel, grid_baz):
     ``grid_vel = 1 / |s|`` km/s (``inf`` for s = 0), ``grid_baz = (atan2(s0, s1) * 180 / pi - 360) mod 360`` degrees, the
@@ -52,9 +59,10 @@ def _returns_grid(res, grid, want_map):
 
 
 def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
-           want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False, seed_halfwidths=None):
-    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded``, ``ltsva_grid`` and ``ltsva_seeded``: the checks, the
-    geometry, the device pass, the returns."""
+           want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False, seed_halfwidths=None,
+           want_consistency=False):
+    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded``, ``ltsva_grid``, ``ltsva_seeded`` and
+    ``ltsva_consistency``: the checks, the geometry, the device pass, the returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
     engine.check_elements(nchans, alpha)
@@ -72,9 +80,11 @@ def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_ar
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
                          prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
                          want_subsample=want_subsample, min_velocity=min_velocity, slowness_grid=slowness_grid,
-                         want_grid_map=grid_map, seed_halfwidths=seed_halfwidths)
+                         want_grid_map=grid_map, seed_halfwidths=seed_halfwidths, want_consistency=want_consistency)
     out = (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
-    return out if slowness_grid is None else out + _returns_grid(res, slowness_grid, grid_map)
+    if slowness_grid is not None:
+        out = out + _returns_grid(res, slowness_grid, grid_map)
+    return out + _returns_consistency(res) if want_consistency else out
 
 
 def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
@@ -124,6 +134,24 @@ def ltsva_subsample(st, lat_list, lon_list, window_length, window_overlap, alpha
     8-tuple.  Too few elements raise ``ValueError`` here (``ltsva`` keeps the reference's ``RuntimeError``)."""
     _check_elements_strict(len(st), alpha)
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, True)
+
+
+def ltsva_consistency(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, subsample=False):
+    """``ltsva`` followed by the closure (consistency) of the picked lags, as PMCC uses it (Cansi 1995): for three elements
+    i < j < k the lags of one coherent arrival satisfy ``l_ij + l_jk - l_ik = 0`` whatever its slowness, its wavefront's
+    curvature or the elements' clock offsets; only noise, cycle skips and several arrivals break it.  Three more returns
+    per window, in seconds: ``consistency`` (nwin,), the rms closure over all N (N-1) (N-2) / 6 triplets,
+    ``closure_max`` (nwin,), the largest ``|closure|``, and ``element_consistency`` (nwin, N), per element the rms over the
+    (N-1) (N-2) / 2 triplets that hold it (DESIGN.md section 17 has the definition).  A mistimed or misplaced element
+    leaves all three untouched while LTS drops it; a noisy element raises its own column.  ``subsample=True``: the lags are
+    refined to sub-sample precision first (``ltsva_subsample``), the closure is that of the refined delays and the first
+    eight returns are ``ltsva_subsample``'s; else they are ``ltsva``'s.  Computed on the GPU behind each window's solve,
+    from the lag table already there (csrc/closure.hip).  A ``subsample`` that is not a bool and too few elements raise
+    ``ValueError`` before any GPU work."""
+    _check_flag('subsample', subsample)
+    _check_elements_strict(len(st), alpha)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, bool(subsample),
+                  want_consistency=True)
 
 
 def ltsva_bounded(st, lat_list, lon_list, window_length, window_overlap, min_velocity, alpha=1.0, rij=None):
@@ -217,18 +245,18 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
 
 
 def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity=None,
-            slowness_grid=None):
+            slowness_grid=None, consistency=False):
     """The single call a batch of one recording / one estimator with nothing removed is: ``ltsva`` itself for the plain
     one, else the strict element check of ``ltsva_beam`` / ``ltsva_subsample`` and the shared body."""
-    if not beam and not subsample and min_velocity is None and slowness_grid is None:
+    if not beam and not subsample and min_velocity is None and slowness_grid is None and not consistency:
         return ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)
     _check_elements_strict(len(st), alpha)
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample),
-                  min_velocity, slowness_grid)
+                  min_velocity, slowness_grid, want_consistency=bool(consistency))
 
 
 def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False,
-                min_velocity=None):
+                min_velocity=None, consistency=False):
     """``ltsva`` of one (already filtered) stream for several estimators ``(alpha, remove)`` in one GPU pass -> a list of
     ``ltsva``'s 8-tuples, element e equal to ``ltsva`` with ``alpha_e`` on the stream without the traces ``remove_e``
     (0-based, ascending; a bare number means nothing removed; at most 8 estimators).  The windows of the full array are
@@ -237,16 +265,20 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     10-tuples, element e equal to ``ltsva_beam`` on the reduced stream (the beam of estimator e's elements at its
     slowness).  ``subsample=True``: the full array's lags are refined once (``ltsva_subsample``) and element e equals
     ``ltsva_subsample`` on the reduced stream.  ``min_velocity`` (km/s, default None): the full array's lags are searched
-    within their physical range once (``ltsva_bounded``) and every estimator reads the picks of its pairs."""
+    within their physical range once (``ltsva_bounded``) and every estimator reads the picks of its pairs.
+    ``consistency=True``: element e's tuple is followed by the three returns of ``ltsva_consistency`` on the reduced stream,
+    the closure of the lags over the triplets of estimator e's elements."""
     _check_flag('beam', beam)
     _check_flag('subsample', subsample)
+    _check_flag('consistency', consistency)
     if min_velocity is not None:
         planner.check_min_velocity(min_velocity)
     data, fs, _ = engine.stream_rows(st)
     nchans = len(data)
     ests = engine.normalize_estimators(estimators, nchans)
     if len(ests) == 1 and not ests[0][1]:          # one estimator with nothing removed IS the single call
-        return [_single(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij, beam, subsample, min_velocity)]
+        return [_single(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij, beam, subsample, min_velocity,
+                        consistency=consistency)]
     rijs, t0s = [], []
     for _, remove in ests:
         kept = engine.kept_elements(nchans, remove)
@@ -261,11 +293,12 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_multi(data, fs, t0s, rijs, [(None, None)], [window_length], window_overlap, ests,
                                    prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
-                                   min_velocity=min_velocity)
+                                   min_velocity=min_velocity, want_consistency=bool(consistency))
     keys = {}
     out = []
     for (alpha, _), res in zip(ests, results):
         if alpha != 1.0 and id(res.t) not in keys:
             keys[id(res.t)] = engine.time_keys(res.t, res.nwin)
-        out.append((_returns_beam if beam else _returns)(res, res.nchans, alpha, keys.get(id(res.t))))
+        out.append((_returns_beam if beam else _returns)(res, res.nchans, alpha, keys.get(id(res.t))) +
+                   (_returns_consistency(res) if consistency else ()))
     return out

@@ -92,7 +92,7 @@ def _prefix_stdict(stdict, band_number):
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
                key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-               want_grid_map=False, seed_period_fraction=None):
+               want_grid_map=False, seed_period_fraction=None, want_consistency=False):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -134,7 +134,7 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
                          min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map,
-                         seed_halfwidths=seeds)
+                         seed_halfwidths=seeds, want_consistency=want_consistency)
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -188,6 +188,37 @@ def narrow_band_least_squares_beam(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=True)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (res.beam_power, res.fstat)
+
+
+def narrow_band_least_squares_consistency(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                          FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                          subsample=False):
+    """``narrow_band_least_squares`` followed by ``consistency_array`` and ``closure_max_array``, each (NBANDS, vector_len),
+    and ``element_consistency_array`` (NBANDS, vector_len, N), zero-padded like ``vel_array``: per band and window the rms
+    and the largest closure ``l_ij + l_jk - l_ik`` of the picked lags over the element triplets, in seconds, and per
+    element the rms over the triplets that hold it (``lts_array.ltsva_consistency``), computed on the
+    GPU behind each window's solve from the lag table that is already there.  ``subsample=True``: the lags are refined to
+    sub-sample precision (``narrow_band_least_squares_subsample``) and the closure is that of the refined delays.  The first
+    nine returns are those of ``narrow_band_least_squares`` (of ``narrow_band_least_squares_subsample`` with
+    ``subsample=True``).  A ``subsample`` that is not a bool and fewer than 3 elements (4 under LTS) raise ``ValueError``
+    before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
+    if not isinstance(subsample, (bool, np.bool_)):
+        raise ValueError('subsample must be True or False, not %r' % (subsample,))
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
+        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
+                         'squares' % len(st))
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_subsample=bool(subsample),
+                                       want_consistency=True)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (res.consistency, res.closure_max, res.element_consistency)
 
 
 def narrow_band_least_squares_subsample(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
