@@ -1018,11 +1018,9 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
         }
         if (int rc = alloc_copy(h, h->d_limsq, sq.data(), sq.size())) return rc;
     }
-    int32_t max_seed = 0;
     if (!h->seed.empty()) {          // the half-width of every result row: row r is band r / nseg
         std::vector<int32_t> rows((size_t)R);
         for (int r = 0; r < R; ++r) rows[(size_t)r] = h->seed[(size_t)(r / h->nseg)];
-        max_seed = *std::max_element(h->seed.begin(), h->seed.end());
         for (size_t k = 0; k < h->h_pair.size(); ++k)
             if (h->h_pair[k] < 0 || h->h_pair[k] >= h->nelem) return fail(h, NBLS_ERR_ARG, "nbls_plan: a pair of the geometry names an element the trace does not have");
         if (int rc = alloc_copy(h, h->d_seed, rows.data(), rows.size())) return rc;
@@ -1033,7 +1031,7 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
         nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
         // a plan with a lag seed: every group takes the seeded correlator in the general correlators' slot
         if (!h->seed.empty()) {
-            g.sform = nbls_lag_seed_form_of(h->nelem, g.W, max_seed, h->grid_halo);
+            g.sform = nbls_lag_seed_form_of(h->nelem, g.W);
             h->wgroups.push_back(g);
             b = e;
             continue;
@@ -1598,7 +1596,7 @@ int nbls_set_lag_seed(nbls_handle* h, const int32_t* halfwidth, int32_t nbands) 
 
 int nbls_lag_seed_form(int32_t nelem, int32_t W, int32_t max_halfwidth, int32_t halo) {
     if (nelem < 3 || nelem > 32 || W < 2 || max_halfwidth < 0 || halo < 0) return NBLS_ERR_ARG;
-    return nbls_lag_seed_form_of(nelem, W, max_halfwidth, halo);
+    return nbls_lag_seed_form_of(nelem, W);        // (the staged form has no padding: neither enters the fit)
 }
 
 int nbls_lag_limit_form(int32_t nelem, int32_t W, int32_t min_limit) {

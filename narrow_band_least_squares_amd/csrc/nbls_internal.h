@@ -341,12 +341,64 @@ void nbls_route_compute(const nbls_route_query& q, nbls_route* r);
 nbls_route_query nbls_route_query_of(const nbls_handle* h, int W, int vrows, int impl, bool no_screen);
 hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue, int gW, int64_t* launches_io);
 hipError_t nbls_xcorr_screen_finish(nbls_handle* h, int64_t launches);
+// The tail of every launch of an FP64 correlator over the units [ub, ub + nu): the launch's error, then, in a plan with lag
+// refinement, the lags' sub-sample fractions (refine.hip) behind the lag pick.
+inline hipError_t nbls_finish_lag_pick(nbls_handle* h, int64_t ub, int64_t nu, int gW) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !h->refine) return e;
+    return nbls_launch_refine(h, ub, nu, gW, h->stream);
+}
+// Kernel arguments of the two range-restricted correlators (xcorr_bounded.hip, xcorr_seeded.hip; their kernels share the
+// parts of lag_pick.h).
+struct nbls_range_args {
+    const double* filt;       // [B][N][npts_pad]
+    int64_t npts_pad;
+    int nchans;               // array elements N
+    int npairs;
+    const int32_t* pair;      // [P][2]
+    const int32_t* Wb;        // [B]
+    const int32_t* incb;      // [B]
+    const int32_t* unit_band; // [U]
+    const int32_t* unit_win;  // [U]
+    int vector_len;
+    int32_t* lag;             // [B][VL][P]
+    double* cmax;             // [B][VL][P]
+    int u0;                   // first unit of this launch
+    int64_t nitems;           // general forms: (unit, pair) items of this launch
+    // bounded
+    const int32_t* limsq;     // [N][N] max_lag of the pair of two elements, symmetric, 0 on the diagonal (not yet clamped to W-1)
+    int S, CS, PF;            // matrix-core form: lag blocks per tile, channel stride (doubles), zero prefix — as xcorr_mfma_kernel
+    // seeded
+    const int32_t* halfw;     // [B] half-width K of every result row
+    const int32_t* delay;     // [G][N] the plan's delay table (beam_grid.hip)
+    const int32_t* gindex;    // [B][VL] the grid maximum of every unit, -1: none
+};
+// ... with the common fields filled for the units [ub, ub + nu) of handle h
+inline nbls_range_args nbls_range_args_of(const nbls_handle* h, int64_t ub, int64_t nu) {
+    nbls_range_args a{};
+    a.filt = h->d_filt;
+    a.npts_pad = h->npts_pad;
+    a.nchans = h->nelem;
+    a.npairs = h->npairs;
+    a.pair = h->d_pair;
+    a.Wb = h->d_W;
+    a.incb = h->d_inc;
+    a.unit_band = h->d_unit_band;
+    a.unit_win = h->d_unit_win;
+    a.vector_len = h->vector_len;
+    a.lag = h->d_lag;
+    a.cmax = h->d_cmax;
+    a.u0 = (int)ub;
+    a.nitems = nu * h->npairs;
+    return a;
+}
 // bounded-lag correlator (xcorr_bounded.hip): the form a window group takes (nbls_lag_limit_form is its C ABI form;
 // min_limit: the smallest limit of the table) and the launch of units [ub, ue) of a group in form 1 / 2
 int nbls_lag_limit_form_of(int nelem, int W, int min_limit);
 hipError_t nbls_launch_xcorr_bounded(nbls_handle* h, int64_t ub, int64_t ue, int gW, int form);
-// seeded correlator (xcorr_seeded.hip): the form a window group takes (nbls_lag_seed_form is its C ABI form) and the launch
-// of units [ub, ue) of a group in form 1 / 2, behind the grid search of the same units on the handle's stream
-int nbls_lag_seed_form_of(int nelem, int W, int max_halfwidth, int halo);
+// seeded correlator (xcorr_seeded.hip): the form a window group takes (nbls_lag_seed_form is its C ABI form: neither the
+// half-width nor the halo enters) and the launch of units [ub, ue) of a group in form 1 / 2, behind the grid search of the
+// same units on the handle's stream
+int nbls_lag_seed_form_of(int nelem, int W);
 hipError_t nbls_launch_xcorr_seeded(nbls_handle* h, int64_t ub, int64_t ue, int gW, int form);
 hipError_t nbls_launch_probe_mfma_i8(nbls_handle* h, const int* da, const int* db, int* dout);

@@ -14,8 +14,10 @@
 // HBM bound.
 #include "nbls_internal.h"
 #include "wave_ops.h"
+#include "lag_pick.h"
 
 namespace {
+using namespace nbls_pick;
 
 struct XArgs {
     const double* filt;       // [B][N][npts_pad]
@@ -88,19 +90,7 @@ __global__ __launch_bounds__(256) void xcorr_simple_kernel(XArgs a) {
     const double nrm_ab = ssa * ssb;                     // (square of the norm) maxima are compared by quotient, like np.argmax(cij / norm): better_q
     const int nl = 2 * W - 1;
     for (int kk = tid; kk < nl; kk += 256) {
-        const int d = kk - (W - 1);
-        const int nlo = d < 0 ? -d : 0;
-        const int nhi = d < 0 ? W : W - d;
-        double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
-        int n = nlo;
-        for (; n + 3 < nhi; n += 4) {
-            c0 = __builtin_fma(sa[n + d], sb[n], c0);
-            c1 = __builtin_fma(sa[n + d + 1], sb[n + 1], c1);
-            c2 = __builtin_fma(sa[n + d + 2], sb[n + 2], c2);
-            c3 = __builtin_fma(sa[n + d + 3], sb[n + 3], c3);
-        }
-        for (; n < nhi; ++n) c0 = __builtin_fma(sa[n + d], sb[n], c0);
-        const double c = (c0 + c1) + (c2 + c3);
+        const double c = lag_dot<false>(sa, sb, W, kk);
         if (nbls_wave::better_q(c, kk, best, bestk, nrm_ab)) { best = c; bestk = kk; }
     }
     for (int off = 32; off > 0; off >>= 1) {
@@ -118,149 +108,47 @@ __global__ __launch_bounds__(256) void xcorr_simple_kernel(XArgs a) {
             best = __builtin_nan("");
         }
         if (tid == 0) {
-            const int64_t o = ((int64_t)band * a.vector_len + w) * a.npairs + k;
-            a.lag[o] = (W - 1) - bestk;
-            a.cmax[o] = best / sqrt(ssa * ssb);
+            store_pick(a.lag, a.cmax, ((int64_t)band * a.vector_len + w) * a.npairs + k, W, best, bestk, ssa, ssb);
         }
     }
 }
 
 
 // ------------------------------------------------------------------------------------
-// v2: FP64 matrix-core kernel (v_mfma_f64_16x16x4_f64).  One workgroup per unit, one wave per
-// "sliding" channel i.  The whole N-channel window sits in LDS once (zero padded, one buffer per
-// channel).  For wave i the positive-lag correlations against ALL other channels are a
-// Toeplitz product that maps onto 16x16 MFMA tiles with no wasted lanes:
-//
-//     C[r][c] = sum_n'  A[r][n'] * B[n'][c],   A[r][n'] = x_i[n' + r + D0]
-//                                              B[n'][c] = x_j(c)[n' - 16 s(c)]
-//     => C[r][c] = sum_n x_i[n + d] x_j[n],    d = D0 + 16 s(c) + r
-//
-// rows r = 16 consecutive lags, columns c = (partner j, lag block s): (N-1)*S of the 16 columns
-// are live (14/16 for N = 8).  A tile step covers 16*S lags of every partner; its K loop runs
-// only over the n' that can overlap (W - D0), so the triangular lag/overlap structure costs
-// ~16*S/2 wasted samples per lag instead of W/2.  Negative lags of pair (i, j) are the positive
-// lags of wave j against partner i, so every ordered (i, j) is one column family and the total
-// is P * W^2 multiply-adds, as in the direct form.
-//
-// LDS reads per MFMA: two ds_read_b64 (one A, one B value per lane).  A lanes read <= 17
-// consecutive doubles (broadcast + conflict free); B lanes read one double per (column, k):
-// with the channel stride CS == 2 (mod 32) doubles and the 16-sample block shift, the 32
-// addresses of a half-wave fall on 32 distinct bank pairs.
-//
-// Per-lane running (max, first index) over its 4 accumulator rows and all tile steps, then a
-// shuffle reduce over the 4 lanes of a column, then one LDS hand-off to combine the two
-// orderings of each pair.  Ties resolve to the smaller np.correlate index, like np.argmax.
+// v2: FP64 matrix-core kernel: nbls_pick::mfma_tile_body (lag_pick.h) over every lag of every pair.
+// The full search orders its picks by nbls_wave::better_q alone, from (-inf, NO_PICK).  That is NOT the order of the
+// range-restricted correlators (better_first): better_q(0.0, k, -inf, NO_PICK, 0) is false, so on a dead channel (sum of
+// squares exactly zero) this kernel never picks a lag and stores lag = W-1 - NO_PICK, where the bounded kernel picks the
+// first lag of its range.  The two are kept apart on purpose.
 // ------------------------------------------------------------------------------------
-typedef double d4 __attribute__((ext_vector_type(4)));
+struct FullSearch {
+    __device__ static int wave_limit(const XArgs&, int, int W) { return W - 1; }
+    __device__ static int pair_limit(const XArgs&, int, int, int W) { return W - 1; }
+    __device__ static bool better(double v1, int k1, double v2, int k2, double ss) { return nbls_wave::better_q(v1, k1, v2, k2, ss); }
+    static constexpr bool WAVE_PER_PAIR = false;        // (a wave per pair: four trips at 8 elements, +0.6 % of the cfg-3 pass)
+    // NaN / Inf samples: NumPy's semantics (see wave_ops.h nonfinite_argmax), scanned by the pair's one thread
+    __device__ static int nonfinite(const double* xa, const double* xb, int W, int, int) {
+        bool has_nan = false;
+        int first_a = 0x7fffffff, last_b = -1;
+        for (int n = 0; n < W; ++n) {
+            const double va = xa[n], vb = xb[n];
+            has_nan = has_nan || (va != va) || (vb != vb);
+            if (fabs(va) == __builtin_inf() && n < first_a) first_a = n;
+            if (fabs(vb) == __builtin_inf()) last_b = n;
+        }
+        int kk = 0x7fffffff;
+        if (first_a != 0x7fffffff) kk = first_a;
+        if (last_b >= 0 && W - 1 - last_b < kk) kk = W - 1 - last_b;
+        return (has_nan || kk == 0x7fffffff) ? 0 : kk;
+    }
+};
 
 __global__ __launch_bounds__(1024) void xcorr_mfma_kernel(XArgs a) {
     extern __shared__ double sm[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = tid >> 6;                    // sliding channel of this wave
-    const int N = a.nchans;
     const int u = a.u0 + blockIdx.x;
     const int band = a.unit_band[u];
     const int w = u - a.unit_off[band] + a.win_off[band];   // window index inside the band (global)
-    const int W = a.Wb[band];
-    const int64_t t0 = (int64_t)w * a.incb[band];
-    const int S = a.S, CS = a.CS, PF = a.PF;
-    double* nrm = sm + (size_t)N * CS;          // [N] sum of squares
-    double* cbv = nrm + N;                      // [N][16] best value per (wave, column)
-    int* cbk = (int*)(cbv + N * 16);            // [N][16] its np.correlate index
-
-    {   // stage: wave wv loads channel wv (zero padded) and its sum of squares
-        double* ch = sm + (size_t)wv * CS;
-        const double* src = a.filt + ((int64_t)band * N + wv) * a.npts_pad + t0;
-        double q = 0.0;
-        for (int n = lane; n < CS; n += 64) {
-            const int idx = n - PF;
-            const double v = (idx >= 0 && idx < W) ? src[idx] : 0.0;
-            ch[n] = v;
-            q += v * v;
-        }
-        for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
-        if (lane == 0) nrm[wv] = q;
-    }
-    __syncthreads();
-
-    const int c = lane & 15, kq = lane >> 4;
-    const int ncol = (N - 1) * S;
-    const bool colvalid = c < ncol;
-    const int jj = colvalid ? c % (N - 1) : 0;
-    const int s = colvalid ? c / (N - 1) : 0;
-    const int j = jj + (jj >= wv ? 1 : 0);      // partner channel of this column
-    const double* pa = sm + (size_t)wv * CS + PF + kq + c;        // + D0 + n'   (row r = lane & 15)
-    const double* pb = sm + (size_t)j * CS + PF + kq - 16 * s;    // + n'
-    double bestv = -__builtin_inf();
-    int bestk = 0x7fffffff;
-    const double nrm_wj = wv < j ? nrm[wv] * nrm[j] : nrm[j] * nrm[wv];    // (square of the norm; product in pair order ci < cj, as in the final division)
-    const int step = 16 * S;
-    for (int D0 = 0; D0 < W; D0 += step) {
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        const int klen = W - D0;
-        const double* qa = pa + D0;
-        const double* qb = pb;
-        int n0 = 0;
-        for (; n0 + 28 < klen; n0 += 32) {
-#pragma unroll
-            for (int uu = 0; uu < 8; ++uu)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[n0 + 4 * uu], qb[n0 + 4 * uu], acc, 0, 0, 0);
-        }
-        for (; n0 < klen; n0 += 4)
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[n0], qb[n0], acc, 0, 0, 0);
-        if (colvalid) {
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int d = D0 + 16 * s + kq + 4 * reg;
-                if (d < W) {
-                    const int kk = (wv < j) ? (W - 1 + d) : (W - 1 - d);
-                    if (nbls_wave::better_q(acc[reg], kk, bestv, bestk, nrm_wj)) { bestv = acc[reg]; bestk = kk; }
-                }
-            }
-        }
-    }
-    for (int off = 16; off <= 32; off <<= 1) {
-        const double ov = __shfl_xor(bestv, off, 64);
-        const int ok = __shfl_xor(bestk, off, 64);
-        if (nbls_wave::better_q(ov, ok, bestv, bestk, nrm_wj)) { bestv = ov; bestk = ok; }
-    }
-    if (lane < 16) { cbv[wv * 16 + lane] = bestv; cbk[wv * 16 + lane] = bestk; }
-    __syncthreads();
-    if (tid < a.npairs) {
-        const int ci = a.pair[2 * tid], cj = a.pair[2 * tid + 1];     // ci < cj
-        double bv = -__builtin_inf();
-        int bk = 0x7fffffff;
-        const double nrm_p2 = nrm[ci] * nrm[cj];
-        for (int ss = 0; ss < S; ++ss) {
-            const int c1 = (cj - 1) + (N - 1) * ss;     // wave ci, partner cj
-            if (nbls_wave::better_q(cbv[ci * 16 + c1], cbk[ci * 16 + c1], bv, bk, nrm_p2)) { bv = cbv[ci * 16 + c1]; bk = cbk[ci * 16 + c1]; }
-            const int c2 = ci + (N - 1) * ss;           // wave cj, partner ci
-            if (nbls_wave::better_q(cbv[cj * 16 + c2], cbk[cj * 16 + c2], bv, bk, nrm_p2)) { bv = cbv[cj * 16 + c2]; bk = cbk[cj * 16 + c2]; }
-        }
-        if (!nbls_wave::finite_f64(nrm[ci]) || !nbls_wave::finite_f64(nrm[cj])) {
-            // NaN / Inf samples: NumPy's semantics (see wave_ops.h nonfinite_argmax), scanned by this one thread
-            const double* xa = sm + (size_t)ci * CS + PF;
-            const double* xb = sm + (size_t)cj * CS + PF;
-            bool has_nan = false;
-            int first_a = 0x7fffffff, last_b = -1;
-            for (int n = 0; n < W; ++n) {
-                const double va = xa[n], vb = xb[n];
-                has_nan = has_nan || (va != va) || (vb != vb);
-                if (fabs(va) == __builtin_inf() && n < first_a) first_a = n;
-                if (fabs(vb) == __builtin_inf()) last_b = n;
-            }
-            int kk = 0x7fffffff;
-            if (first_a != 0x7fffffff) kk = first_a;
-            if (last_b >= 0 && W - 1 - last_b < kk) kk = W - 1 - last_b;
-            bk = (has_nan || kk == 0x7fffffff) ? 0 : kk;
-            bv = __builtin_nan("");
-        }
-        const int64_t o = ((int64_t)band * a.vector_len + w) * a.npairs + tid;
-        a.lag[o] = (W - 1) - bk;
-        a.cmax[o] = bv / sqrt(nrm_p2);
-    }
+    mfma_tile_body<FullSearch>(a, band, w, a.Wb[band], sm);
 }
 
 __global__ void probe_mfma_f64_kernel(const double* a, const double* b, double* out) {
@@ -308,8 +196,7 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
         if (e != hipSuccess) return e;
         *used = 2;
         hipLaunchKernelGGL(xcorr_mfma_kernel, dim3((unsigned)nu), dim3(64 * h->nelem), shm, h->stream, a);
-        if ((e = hipGetLastError()) != hipSuccess || !h->refine) return e;
-        return nbls_launch_refine(h, ub, nu, gW, h->stream);
+        return nbls_finish_lag_pick(h, ub, nu, gW);
     }
     const int64_t nblocks = nu * h->npairs;
     a.from_global = r.correlator == NBLS_ROUTE_VALU_GLOBAL ? 1 : 0;
@@ -319,9 +206,7 @@ static hipError_t launch_general_range(nbls_handle* h, int64_t ub, int64_t ue, i
     }
     *used = 1;
     hipLaunchKernelGGL(xcorr_simple_kernel, dim3((unsigned)nblocks), dim3(256), shm, h->stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !h->refine) return e;
-    return nbls_launch_refine(h, ub, nu, gW, h->stream);        // the lags' sub-sample fractions (refine.hip), behind the lag pick
+    return nbls_finish_lag_pick(h, ub, nu, gW);
 }
 
 // The correlation stage of a pass.  The plan's bands come in window groups (h->wgroups: consecutive bands of one
