@@ -428,6 +428,67 @@ int nbls_lag_seed_form(int32_t nelem, int32_t W, int32_t max_halfwidth, int32_t 
 int nbls_set_closure(nbls_handle* h, int32_t on);
 int nbls_fetch_closure(nbls_handle* h, double* consistency, double* closure_max, double* element_consistency);
 
+/* Capon (MVDR) and Bartlett slowness spectra of the narrow band's cross-spectral matrix: per window,
+ * the adaptive beamformer that separates two arrivals closer than the array's beam width, where the delay-and-sum search of
+ * nbls_set_beam_grid merges them.  grid[G][2] is in s/km, the convention of nbls_set_beam_grid, 1 <= G <= 65536
+ * (NBLS_CAPON_GRID_MAX); per band b a frequency f_b > 0 (Hz), a snapshot length Ls_b >= 1 and a hop Hs_b >= 1 (samples); one
+ * diagonal loading delta >= 0.  N = nelem (3..32, NBLS_CAPON_MAX_ELEMENTS), W_b the band's window length, xij the geometry's
+ * first N-1 pairs (0, i).
+ *   tables   once per plan, host, un-fused IEEE double:
+ *            c_b[n]    = (0.5 - 0.5 cos((2 pi (n + 0.5)) / Ls_b)) (cos p, sin p),  p = -(((2 pi f_b) n) / fs),  n < Ls_b
+ *            a_b[g][0] = 1,  a_b[g][i] = (cos q, sin q),  q = -((2 pi f_b) tau_i(g)),
+ *            tau_i(g)  = xij[i-1][0] s_g0 + xij[i-1][1] s_g1   (seconds: what the delay table of nbls_set_beam_grid rounds
+ *                        after multiplying by fs)
+ *            K_b       = 1 + (W_b - Ls_b) div Hs_b   snapshots
+ *   matrix   for the unit of result row r (band b), window w (start s0 = w * wininc):
+ *            X_i[k] = sum_{n < Ls} c[n] filt[row of element i][s0 + k Hs + n];  R = (1 / K) sum_k X[k] X[k]^H  (N x N)
+ *            every index lies inside the window: no halo, no read outside the trace
+ *   loading  t = sum_i Re R_ii;  R' = R + delta (t / N) I
+ *   values   P_B(g) = Re(a^H R a) / N^2  on the unloaded R;  R' = L L^H (Cholesky), L y = a, P_C(g) = 1 / |y|^2.  For one
+ *            wave of power sigma^2 both read about sigma^2 at its slowness.
+ *   outputs  capon_index (int32): the g with the largest P_C under the total order "P descending, g ascending"; NaN is no
+ *            candidate; -1 if there is none.  capon_power = P_C there (NaN for -1).  bartlett_index / bartlett_power: the
+ *            same for P_B.  On request both maps [G] and R [N][N] complex (re, im interleaved).
+ *   degenerate  t == 0, t NaN or a NaN entry of R: every result NaN / -1 (R itself is returned as computed).  A Cholesky
+ *            pivot that is not > 0: the Capon results NaN / -1, the Bartlett results stay.
+ * With delta > 0 the condition number of R' is at most (N + delta) / delta.  The order of every sum depends on (N, W, Ls, Hs,
+ * G) alone, the arg-max is a total order and no atomics are used: single, streamed, batched (nbls_set_segments) and
+ * window-sliced passes agree bit for bit.
+ *   nbls_set_capon(h, grid, G, freq, snap_len, snap_hop, nbands, loading, flags)   copied and read by the next nbls_plan;
+ *                            G = 0 (or grid NULL) switches it off (the default: a plan without it is launch for launch the
+ *                            plain pass).  flags: NBLS_CAPON_MAPS, NBLS_CAPON_CSDM.  NBLS_ERR_ARG, the handle unchanged, for
+ *                            G outside 1..65536, an entry of the grid that is not finite, a frequency not in (0, inf), a
+ *                            length or hop < 1, a loading < 0 or not finite, nbands < 1.  nbls_plan returns NBLS_ERR_ARG if
+ *                            nbands differs from the plan's, if some Ls_b > W_b, or if delta = 0 with some K_b < N (singular
+ *                            by construction); NBLS_ERR_STATE without the geometry of the trace's array;
+ *                            NBLS_ERR_UNSUPPORTED with an RCCL communicator, for more than 32 elements, and if the steering
+ *                            table nbands * G * N * 16 bytes exceeds 1 GiB.  The search is over the full array, behind
+ *                            estimator 0's solve; it is independent of nbls_set_beam_grid / nbls_set_lag_seed and combines
+ *                            with them, with segments, streamed results and window ranges.
+ *   nbls_fetch_capon(h, capon_index, capon_power, bartlett_index, bartlett_power)   [rows][vector_len] each (any may be NULL),
+ *                            rows as for nbls_fetch; waits for the pass like nbls_fetch_beam_grid.
+ *   nbls_fetch_capon_maps(h, capon_map, bartlett_map)   [rows][vector_len][G] each (either may be NULL).
+ *   nbls_fetch_capon_csdm(h, R)   [rows][vector_len][N][N][2].
+ *   nbls_fetch_capon_tables(h, band, coef, steer)   the plan's own tables of band `band`: coef [Ls_b][2], steer [G][N][2]
+ *                            (either may be NULL).
+ *                            Each returns NBLS_ERR_STATE where the plan did not ask for the result.  The results are
+ *                            written by the solve stage alone: zeros until a pass of the plan has run it; cells beyond
+ *                            nwin[r] (and outside a window slice) are zeros.
+ * A workgroup of NBLS_CAPON_THREADS threads takes one unit; the snapshots go through LDS NBLS_CAPON_CHUNK at a time.
+ * nbls_timings is unchanged: the kernel's time falls inside the solve interval. */
+#define NBLS_CAPON_GRID_MAX 65536
+#define NBLS_CAPON_MAX_ELEMENTS 32
+#define NBLS_CAPON_THREADS 128
+#define NBLS_CAPON_CHUNK 32
+#define NBLS_CAPON_MAPS 1
+#define NBLS_CAPON_CSDM 2
+int nbls_set_capon(nbls_handle* h, const double* grid, int32_t G, const double* freq, const int32_t* snap_len,
+                   const int32_t* snap_hop, int32_t nbands, double loading, int32_t flags);
+int nbls_fetch_capon(nbls_handle* h, int32_t* capon_index, double* capon_power, int32_t* bartlett_index, double* bartlett_power);
+int nbls_fetch_capon_maps(nbls_handle* h, double* capon_map, double* bartlett_map);
+int nbls_fetch_capon_csdm(nbls_handle* h, double* R);
+int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* steer);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

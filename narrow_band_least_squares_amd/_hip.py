@@ -30,9 +30,15 @@ EXPORTS = [
     'nbls_set_beam_grid', 'nbls_fetch_beam_grid', 'nbls_fetch_beam_grid_map', 'nbls_fetch_beam_grid_delays',
     'nbls_beam_grid_lds_bytes',
     'nbls_set_closure', 'nbls_fetch_closure', 'nbls_est_fetch_closure',
+    'nbls_set_capon', 'nbls_fetch_capon', 'nbls_fetch_capon_maps', 'nbls_fetch_capon_csdm', 'nbls_fetch_capon_tables',
 ]
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
+CAPON_GRID_MAX = 65536   # grid points of the Capon spectra (NBLS_CAPON_GRID_MAX)
+CAPON_MAX_ELEMENTS = 32  # array elements of a plan with Capon spectra (NBLS_CAPON_MAX_ELEMENTS)
+CAPON_THREADS = 128      # threads of a workgroup of the Capon kernel, one grid point each (NBLS_CAPON_THREADS)
+CAPON_CHUNK = 32         # snapshots that go through LDS together (NBLS_CAPON_CHUNK)
+CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -167,6 +173,11 @@ def load_library(path=None):
     lib.nbls_fetch_beam_grid_map.argtypes = [vp, dp]
     lib.nbls_fetch_beam_grid_delays.argtypes = [vp, ip]
     lib.nbls_beam_grid_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.nbls_set_capon.argtypes = [vp, dp, C.c_int32, dp, ip, ip, C.c_int32, C.c_double, C.c_int32]
+    lib.nbls_fetch_capon.argtypes = [vp, ip, dp, ip, dp]
+    lib.nbls_fetch_capon_maps.argtypes = [vp, dp, dp]
+    lib.nbls_fetch_capon_csdm.argtypes = [vp, dp]
+    lib.nbls_fetch_capon_tables.argtypes = [vp, C.c_int32, dp, dp]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -271,6 +282,7 @@ class Handle:
         self.nseg = 1
         self.est_npairs = []            # pair counts of the further estimators (set_estimators)
         self._want_grid_n = self.grid_n = 0   # grid points of set_beam_grid / of the plan
+        self._want_capon = self.capon = None  # (G, snapshot lengths) of set_capon / of the plan
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -394,6 +406,7 @@ class Handle:
         self.fbands = nb
         self._nsec = nsec
         self.grid_n = self._want_grid_n
+        self.capon = self._want_capon
 
     def set_option(self, key, value):
         """Per-handle implementation switch (``nbls_set_option``; identical results unless the library is the
@@ -552,6 +565,57 @@ class Handle:
             raise ValueError('the slowness grid must be (G, 2), not %r' % (g.shape,))
         self._chk(self.lib.nbls_set_beam_grid(self._h, _dptr(g), g.shape[0], int(bool(want_map))))
         self._want_grid_n = g.shape[0]
+
+    def set_capon(self, grid=None, freqs=None, snap_len=None, snap_hop=None, loading=0.01, want_maps=False, want_csdm=False):
+        """The next plans also compute, per window, the Capon and Bartlett slowness spectra of the narrow band's
+        cross-spectral matrix over the slowness vectors ``grid`` (G, 2) in s/km (``nbls_set_capon``):
+        per band a frequency (Hz), a snapshot length and a hop (samples), one diagonal ``loading``; ``want_maps`` keeps
+        both spectra, ``want_csdm`` the matrix.  ``grid=None`` switches it off again."""
+        if grid is None:
+            self._chk(self.lib.nbls_set_capon(self._h, None, 0, None, None, None, 0, 0.0, 0))
+            self._want_capon = None
+            return
+        g, f = _f64(grid), _f64(freqs)
+        ls = np.ascontiguousarray(snap_len, dtype=np.int32)
+        hs = np.ascontiguousarray(snap_hop, dtype=np.int32)
+        if g.ndim != 2 or g.shape[1] != 2 or g.shape[0] < 1:
+            raise ValueError('the slowness grid must be (G, 2) with G >= 1, not %r' % (g.shape,))
+        if f.ndim != 1 or ls.shape != f.shape or hs.shape != f.shape:
+            raise ValueError('one frequency, snapshot length and hop per band')
+        flags = (CAPON_MAPS if want_maps else 0) | (CAPON_CSDM if want_csdm else 0)
+        self._chk(self.lib.nbls_set_capon(self._h, _dptr(g), g.shape[0], _dptr(f), _iptr(ls), _iptr(hs), len(f), float(loading),
+                                          flags))
+        self._want_capon = (g.shape[0], ls.copy())
+
+    def fetch_capon(self):
+        """-> (capon_index int32, capon_power, bartlett_index int32, bartlett_power), each (rows, vector_len)."""
+        idx = np.empty((2, self.nbands, self.vector_len), dtype=np.int32)
+        out = np.empty((2, self.nbands, self.vector_len))
+        self._chk(self.lib.nbls_fetch_capon(self._h, _iptr(idx[0]), _dptr(out[0]), _iptr(idx[1]), _dptr(out[1])))
+        return idx[0], out[0], idx[1], out[1]
+
+    def fetch_capon_maps(self):
+        """-> (capon_map, bartlett_map), each (rows, vector_len, G) (a plan made with ``want_maps``)."""
+        G = self.capon[0] if self.capon else 1
+        out = np.empty((2, self.nbands, self.vector_len, G))
+        self._chk(self.lib.nbls_fetch_capon_maps(self._h, _dptr(out[0]), _dptr(out[1])))
+        return out[0], out[1]
+
+    def fetch_capon_csdm(self):
+        """-> the cross-spectral matrix of every window, complex128 (rows, vector_len, N, N) (a plan made with ``want_csdm``)."""
+        N = self.nchans // self.nseg
+        out = np.empty((self.nbands, self.vector_len, N, N), dtype=np.complex128)
+        self._chk(self.lib.nbls_fetch_capon_csdm(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def fetch_capon_tables(self, band):
+        """-> (snapshot coefficients complex128 (Ls,), steering vectors complex128 (G, N)) of band ``band`` of the plan."""
+        G, ls = self.capon if self.capon else (1, np.ones(max(1, self.fbands), dtype=np.int32))
+        coef = np.empty(int(ls[band]) if 0 <= band < len(ls) else 1, dtype=np.complex128)
+        steer = np.empty((G, self.nchans // self.nseg), dtype=np.complex128)
+        cd = C.POINTER(C.c_double)
+        self._chk(self.lib.nbls_fetch_capon_tables(self._h, int(band), coef.ctypes.data_as(cd), steer.ctypes.data_as(cd)))
+        return coef, steer
 
     def fetch_beam_grid(self):
         """-> (grid_index int32, grid_fstat, grid_power) of the plan's slowness-grid search, each (rows, vector_len)."""

@@ -793,6 +793,28 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if (!nbls_beam_grid_delays_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, gdel.data(), &ghalo))
             return fail(h, NBLS_ERR_ARG, "nbls_plan: a delay of the slowness grid (nbls_set_beam_grid) reaches 2^30 samples");
     }
+    if (!h->want_capon.grid.empty()) {   // Capon spectra (nbls_set_capon): the tables are made once the windows are known (plan_capon)
+        const nbls_handle::capon_request& c = h->want_capon;
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: Capon spectra (nbls_set_capon) are not supported with an RCCL communicator (the gathered block does not carry them)");
+        const int En = h->nchans / NS;
+        if (!h->est[0].d_xij || (int64_t)En * (En - 1) / 2 != h->npairs)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: Capon spectra (nbls_set_capon) need the geometry of the trace's array");
+        if (En > NBLS_CAPON_MAX_ELEMENTS)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: Capon spectra (nbls_set_capon) support up to " + std::to_string(NBLS_CAPON_MAX_ELEMENTS) + " elements");
+        if ((int)c.freq.size() != a.nbands)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: Capon tables (nbls_set_capon) of " + std::to_string(c.freq.size()) + " bands for a plan of " +
+                                             std::to_string(a.nbands) + " bands");
+        for (int b = 0; b < a.nbands; ++b) {
+            if (c.ls[b] > a.winlen[b])
+                return fail(h, NBLS_ERR_ARG, "nbls_plan: the Capon snapshot of band " + std::to_string(b) + " (" + std::to_string(c.ls[b]) +
+                                                 " samples) is longer than its window (" + std::to_string(a.winlen[b]) + ")");
+            if (c.loading == 0.0 && 1 + (a.winlen[b] - c.ls[b]) / c.hs[b] < En)
+                return fail(h, NBLS_ERR_ARG, "nbls_plan: band " + std::to_string(b) + " has fewer Capon snapshots than elements and no loading: its matrix is singular by construction");
+        }
+        if ((size_t)a.nbands * (c.grid.size() / 2) * (size_t)En * 16 > ((size_t)1 << 30))
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the Capon steering table (nbands * G * N * 16 bytes) exceeds 1 GiB");
+    }
     if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
         if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
@@ -826,6 +848,12 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->grid_halo = ghalo;
     h->grid_map = h->grid_n > 0 && h->want_grid_map;
     h->grid_valid = false;
+    h->capon = h->want_capon;
+    h->capon_n = (int)(h->capon.grid.size() / 2);
+    h->capon_loading = h->capon.loading;
+    h->capon_maps = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_MAPS);
+    h->capon_csdm = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_CSDM);
+    h->capon_valid = false;
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
     nbls_estimator& x0 = h->est[0];
@@ -1108,6 +1136,31 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_grid_fp, 2 * cells * sizeof(double)))) return rc;
         if (h->grid_map && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->grid_n * sizeof(double)))) return rc;
     }
+    if (h->capon_n > 0) {            // the Capon spectra: the band tables and the result buffers, likewise
+        const size_t cells = (size_t)a.R * a.vector_len;
+        const int E = a.E, G = h->capon_n, nb = a.nbands;
+        int maxls = 1;
+        h->h_capon_par.resize((size_t)nb * 3);
+        for (int b = 0; b < nb; ++b) {
+            const int ls = h->capon.ls[b], hs = h->capon.hs[b];
+            h->h_capon_par[3 * b] = ls;
+            h->h_capon_par[3 * b + 1] = hs;
+            h->h_capon_par[3 * b + 2] = 1 + (a.winlen[b] - ls) / hs;
+            if (ls > maxls) maxls = ls;
+        }
+        h->capon_maxls = maxls;
+        h->h_capon_coef.resize((size_t)nb * maxls * 2);
+        h->h_capon_steer.resize((size_t)nb * E * G * 2);
+        nbls_capon_tables_of(h->est[0].h_xij.data(), E, h->fs, h->capon.grid.data(), G, h->capon.freq.data(), h->capon.ls.data(),
+                             nb, maxls, h->h_capon_coef.data(), h->h_capon_steer.data());
+        if ((rc = alloc_copy(h, h->d_capon_par, h->h_capon_par.data(), h->h_capon_par.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_capon_coef, h->h_capon_coef.data(), h->h_capon_coef.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_capon_steer, h->h_capon_steer.data(), h->h_capon_steer.size()))) return rc;
+        if ((rc = ensure(h, h->d_capon_index, 2 * cells * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(h, h->d_capon_power, 2 * cells * sizeof(double)))) return rc;
+        if (h->capon_maps && (rc = ensure(h, h->d_capon_map, 2 * cells * (size_t)G * sizeof(double)))) return rc;
+        if (h->capon_csdm && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+    }
     return 0;
 }
 
@@ -1211,6 +1264,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (stage_mask & 4) h->solve_ran = true;
     // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
     if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
+    if ((stage_mask & 4) && h->capon_n > 0) h->capon_valid = true;    // (... and the Capon spectra)
     if (stage_mask & 2) h->frac_valid = true;            // (... one without the correlation stage the lag fractions)
     // per-batch solves: behind each unit batch of the correlation stage (streamed results: a batch's rows are complete
     // while later batches are still being correlated), on the second stream with option "overlap"
@@ -1565,6 +1619,95 @@ int nbls_fetch_beam_grid_delays(nbls_handle* h, int32_t* d) {
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: no plan");
     if (h->grid_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: nbls_set_beam_grid before nbls_plan");
     memcpy(d, h->h_grid_delay.data(), h->h_grid_delay.size() * sizeof(int32_t));   // the plan's own table (the device holds a copy)
+    return NBLS_OK;
+}
+
+int nbls_set_capon(nbls_handle* h, const double* grid, int32_t G, const double* freq, const int32_t* snap_len,
+                   const int32_t* snap_hop, int32_t nbands, double loading, int32_t flags) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!grid || G == 0) { h->want_capon = nbls_handle::capon_request(); return NBLS_OK; }      // off: the next plan computes no spectra
+    if (G < 1 || G > NBLS_CAPON_GRID_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: G must be 1.." + std::to_string(NBLS_CAPON_GRID_MAX));
+    if (nbands < 1 || !freq || !snap_len || !snap_hop) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: at least one band with its frequency, snapshot length and hop");
+    for (int64_t k = 0; k < 2 * (int64_t)G; ++k)                 // everything is checked before the handle changes
+        if (!(fabs(grid[k]) < INFINITY)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: slowness vector " + std::to_string(k / 2) + " is not finite");
+    for (int b = 0; b < nbands; ++b) {
+        if (!(freq[b] > 0.0 && freq[b] < INFINITY)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: the frequency of band " + std::to_string(b) + " is not in (0, inf)");
+        if (snap_len[b] < 1 || snap_hop[b] < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: the snapshot length and hop of band " + std::to_string(b) + " must be at least 1");
+    }
+    if (!(loading >= 0.0 && loading < INFINITY)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: the loading must be finite and not negative");
+    nbls_handle::capon_request& c = h->want_capon;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    c.grid.assign(grid, grid + 2 * (size_t)G);
+    c.freq.assign(freq, freq + nbands);
+    c.ls.assign(snap_len, snap_len + nbands);
+    c.hs.assign(snap_hop, snap_hop + nbands);
+    c.loading = loading;
+    c.flags = flags;
+    return NBLS_OK;
+}
+
+// what the Capon fetches share: the plan asked, and the pass is through
+static int capon_fetch_ready(nbls_handle* h, const char* who) {
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, std::string(who) + ": no plan");
+    if (h->capon_n < 1 || !h->d_capon_index) return fail(h, NBLS_ERR_STATE, std::string(who) + ": nbls_set_capon before nbls_plan");
+    return 0;
+}
+
+// one result plane [B][VL] rows of row_bytes: zeros until a pass has run the solve stage, and where no window was computed
+static int capon_fetch_plane(nbls_handle* h, void* out, const void* src, size_t row_bytes) {
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    if (!out) return NBLS_OK;
+    if (!h->capon_valid) { memset(out, 0, cells * row_bytes); return NBLS_OK; }
+    HIPCHK(h, copy_sync(h, out, src, cells * row_bytes, hipMemcpyDeviceToHost));
+    zero_uncomputed(h, out, row_bytes);
+    return NBLS_OK;
+}
+
+int nbls_fetch_capon(nbls_handle* h, int32_t* capon_index, double* capon_power, int32_t* bartlett_index, double* bartlett_power) {
+    if (!h) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = capon_fetch_ready(h, "nbls_fetch_capon")) || (rc = finish_pass(h))) return rc;
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    if ((rc = capon_fetch_plane(h, capon_index, h->d_capon_index.p, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, bartlett_index, h->d_capon_index.p + cells, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, capon_power, h->d_capon_power.p, sizeof(double)))) return rc;
+    return capon_fetch_plane(h, bartlett_power, h->d_capon_power.p + cells, sizeof(double));
+}
+
+int nbls_fetch_capon_maps(nbls_handle* h, double* capon_map, double* bartlett_map) {
+    if (!h) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_maps"))) return rc;
+    if (!h->capon_maps || !h->d_capon_map) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_maps: the plan did not ask for the maps (nbls_set_capon, NBLS_CAPON_MAPS)");
+    if ((rc = finish_pass(h))) return rc;
+    const size_t cells = (size_t)h->nbands * h->vector_len, row = (size_t)h->capon_n * sizeof(double);
+    if ((rc = capon_fetch_plane(h, capon_map, h->d_capon_map.p, row))) return rc;
+    return capon_fetch_plane(h, bartlett_map, h->d_capon_map.p + cells * h->capon_n, row);
+}
+
+int nbls_fetch_capon_csdm(nbls_handle* h, double* R) {
+    if (!h || !R) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_csdm"))) return rc;
+    if (!h->capon_csdm || !h->d_capon_csdm) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_csdm: the plan did not ask for the matrix (nbls_set_capon, NBLS_CAPON_CSDM)");
+    if ((rc = finish_pass(h))) return rc;
+    return capon_fetch_plane(h, R, h->d_capon_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+}
+
+int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* steer) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_tables: no plan");
+    if (h->capon_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_tables: nbls_set_capon before nbls_plan");
+    if (band < 0 || band >= h->fbands) return fail(h, NBLS_ERR_ARG, "nbls_fetch_capon_tables: no such band");
+    const int G = h->capon_n, N = h->nelem;                      // the plan's own tables (the device holds copies)
+    if (coef) memcpy(coef, h->h_capon_coef.data() + (size_t)band * h->capon_maxls * 2, (size_t)h->h_capon_par[3 * band] * 2 * sizeof(double));
+    if (steer) {
+        const double* s = h->h_capon_steer.data() + (size_t)band * N * G * 2;
+        for (int g = 0; g < G; ++g)
+            for (int i = 0; i < N; ++i) {
+                steer[((size_t)g * N + i) * 2] = s[((size_t)i * G + g) * 2];
+                steer[((size_t)g * N + i) * 2 + 1] = s[((size_t)i * G + g) * 2 + 1];
+            }
+    }
     return NBLS_OK;
 }
 

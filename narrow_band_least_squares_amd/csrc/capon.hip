@@ -1,0 +1,355 @@
+// Per-window Capon (MVDR) and Bartlett slowness spectra of the narrow band's cross-spectral matrix (nbls_set_capon;
+// DESIGN.md §18).
+//
+// The caller gives G slowness vectors grid[G][2] (s/km, the convention of nbls_set_beam_grid), per band b a frequency f_b
+// (Hz), a snapshot length Ls_b and hop Hs_b (samples), and one diagonal loading delta.  N = nelem, W the band's window.
+// Once per plan, on the host in float64 (un-fused: this translation unit is built without contraction):
+//   c_b[n]    = (0.5 - 0.5 cos((2 pi (n + 0.5)) / Ls)) * (cos p, sin p),  p = -(((2 pi f) n) / fs),  n < Ls
+//   a_b[g][0] = 1,  a_b[g][i] = (cos q, sin q),  q = -((2 pi f) tau_i(g)),  tau_i(g) = xij[i-1][0] s_g0 + xij[i-1][1] s_g1
+//   K_b       = 1 + (W - Ls) div Hs
+// Per unit (result row r, window w, start s0 = w * inc[r]):
+//   X_i[k] = sum_{n < Ls} c[n] filt[r][i][s0 + k Hs + n]        every index inside the window: no halo
+//   R      = (1 / K) sum_k X[k] X[k]^H                          N x N Hermitian
+//   t      = sum_i Re R_ii,  R' = R + delta (t / N) I
+//   P_B(g) = Re(a^H R a) / N^2                                  on the unloaded R
+//   R' = L L^H (Cholesky), L y = a (forward substitution), P_C(g) = 1 / |y|^2
+// and the unit's results are the arg-max of either spectrum under "P descending, g ascending" (a NaN is no candidate; -1
+// and NaN if there is none), on request both maps and R.  t == 0, t NaN or a NaN entry of R: every result NaN / -1.  A
+// pivot that is not > 0: the Capon results NaN / -1, the Bartlett results stay.
+//
+// Mapping: one workgroup of CAPON_THREADS threads per unit.
+//   snapshots  chunks of CAPON_CHUNK snapshots; a wave takes (snapshot, element) dots, its lanes stride n and the fixed
+//              DPP tree of wave_ops.h adds them; X of the chunk goes to LDS, so no (Ls, Hs) is refused
+//   R          thread e takes the entries e, e + CAPON_THREADS, ... of the lower triangle and adds the chunk's snapshots in
+//              k order; the upper triangle is the conjugate, bit for bit
+//   Cholesky   in LDS, thread i owns row i, one barrier per column; every thread forms the pivot itself, so the decision
+//              "not > 0" is the same in all of them
+//   grid       one lane per grid point.  N is a run-time value <= 32: a register array of y indexed by it would go to
+//              scratch, and the full unrolling that makes every index a constant is a program of 4000 FMAs that the
+//              compiler does not get through; so a (then y, in place) lives in LDS, column `lane` of Y [N][2][THREADS],
+//              consecutive lanes on consecutive banks (conflict-free ds_read_b64), in the place X had.  R and L are
+//              wave-uniform LDS reads (broadcast), the steering table is laid out [band][element][G] so that consecutive
+//              lanes read consecutive g.  y is substituted, R'^-1 is never formed: the error of P_C grows with kappa(R'),
+//              not its square.  The diagonal of L is held as its reciprocal.
+//   LDS        dynamic, sized by N: R and L (N^2 complex each), N reciprocals, and max(CHUNK, THREADS) N complex for X / Y:
+//              6.3 KiB at N = 3, 18 KiB at 8, 96 KiB at 32
+// The order of every sum depends on (N, W, Ls, Hs, G) alone, the arg-max is a total order, there are no atomics and nothing
+// depends on the launch's unit range: single, streamed, batched and window-sliced passes give the same bits.
+#include "nbls_internal.h"
+#include "wave_ops.h"
+#include <cmath>
+
+namespace {
+
+constexpr int CT = NBLS_CAPON_THREADS;
+constexpr int CW = CT / 64;                  // waves
+constexpr int CCH = NBLS_CAPON_CHUNK;        // snapshots per chunk of X in LDS
+constexpr int CMAXN = NBLS_CAPON_MAX_ELEMENTS;
+constexpr int CTRI = (CMAXN * (CMAXN + 1) / 2 + CT - 1) / CT;     // lower-triangle entries per thread
+
+struct CArgs {
+    const double* filt;       // [B][nelem][npts_pad]
+    int64_t npts_pad;
+    int N, nseg;
+    const int32_t* Wb;        // [B]
+    const int32_t* incb;      // [B]
+    const int32_t* unit_band; // [U]
+    const int32_t* unit_win;  // [U]
+    int vector_len, u0, nunits;
+    int G, maxLs;
+    const int32_t* par;       // [fbands][3]: Ls, Hs, K
+    const double* coef;       // [fbands][maxLs][2]
+    const double* steer;      // [fbands][N][G][2]
+    double loading;
+    int32_t* index;           // [2][B][VL]: capon | bartlett
+    double* power;            // [2][B][VL]
+    double* map;              // [2][B][VL][G] or NULL
+    double* csdm;             // [B][VL][N][N][2] or NULL
+    int64_t cells;
+};
+
+// "P descending, g ascending"; a NaN is no candidate, g < 0 is "none yet".
+__device__ inline bool capon_better(double p, int g, double bp, int bg) {
+    if (p != p || g < 0) return false;
+    if (bg < 0) return true;
+    return p > bp || (p == bp && g < bg);
+}
+
+// The workgroup's best of the threads' bests -> thread 0 (any tree: the order is total).
+__device__ inline void capon_best(double& p, int& g, double* sp, int* sg, int tid) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const double op = __shfl_xor(p, off, 64);
+        const int og = __shfl_xor(g, off, 64);
+        if (capon_better(op, og, p, g)) { p = op; g = og; }
+    }
+    if ((tid & 63) == 0) { sp[tid >> 6] = p; sg[tid >> 6] = g; }
+    __syncthreads();
+    if (tid == 0)
+        for (int j = 1; j < CW; ++j)
+            if (capon_better(sp[j], sg[j], p, g)) { p = sp[j]; g = sg[j]; }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
+    // dynamic LDS, sized by N (capon_lds_bytes): Rm [N][N] complex, Lm [N][N] complex, invd [N], then X [CHUNK][N] complex
+    // and, in its place once R is there, Y [N][2][THREADS]: the grid phase's vector of every lane
+    extern __shared__ __attribute__((aligned(16))) double capon_lds[];
+    __shared__ double red_p[CW];
+    __shared__ int red_g[CW];
+    const int SN = a.N;                                              // row stride of Rm, Lm and X
+    double* const Rm = capon_lds;
+    double* const Lm = Rm + SN * SN * 2;
+    double* const invd = Lm + SN * SN * 2;
+    double* const X = invd + ((SN + 1) & ~1);
+    double* const Y = X;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if ((int)blockIdx.x >= a.nunits) return;                         // (the same for every thread of the workgroup)
+    const int u = a.u0 + blockIdx.x;
+    const int row = a.unit_band[u], w = a.unit_win[u];
+    const int band = row / a.nseg;
+    const int N = a.N, G = a.G;
+    const int Ls = a.par[3 * band], Hs = a.par[3 * band + 1], K = a.par[3 * band + 2];
+    const int64_t s0 = (int64_t)w * a.incb[row];
+    const int64_t cell = (int64_t)row * a.vector_len + w;
+    const double* rowbase = a.filt + (int64_t)row * N * a.npts_pad + s0;
+    const double* coef = a.coef + (int64_t)band * a.maxLs * 2;
+
+    // this thread's entries of the lower triangle: e = i (i + 1) / 2 + j, j <= i
+    const int ntri = N * (N + 1) / 2;
+    int ei[CTRI], ej[CTRI];
+    double accr[CTRI], acci[CTRI];
+#pragma unroll
+    for (int m = 0; m < CTRI; ++m) {
+        const int e = tid + m * CT;
+        int i = 0;
+        while ((i + 1) * (i + 2) / 2 <= e) ++i;
+        ei[m] = i; ej[m] = e - i * (i + 1) / 2;
+        accr[m] = 0.0; acci[m] = 0.0;
+    }
+    for (int k0 = 0; k0 < K; k0 += CCH) {
+        const int kc = K - k0 < CCH ? K - k0 : CCH;
+        for (int item = wave; item < kc * N; item += CW) {           // (item is the same for every lane of the wave)
+            const int kl = item / N, i = item - kl * N;
+            const double* x = rowbase + (int64_t)i * a.npts_pad + (int64_t)(k0 + kl) * Hs;
+            double sr = 0.0, si = 0.0;
+            for (int n = lane; n < Ls; n += 64) {
+                const double v = x[n];
+                sr += coef[2 * n] * v;
+                si += coef[2 * n + 1] * v;
+            }
+            sr = nbls_wave::sum_f64(sr);
+            si = nbls_wave::sum_f64(si);
+            if (lane == 0) { X[(kl * SN + i) * 2] = sr; X[(kl * SN + i) * 2 + 1] = si; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < CTRI; ++m) {
+            if (tid + m * CT >= ntri) continue;
+            const int i = ei[m], j = ej[m];
+            double re = accr[m], im = acci[m];
+            for (int kl = 0; kl < kc; ++kl) {                        // X_i conj(X_j)
+                const double ar = X[(kl * SN + i) * 2], ai = X[(kl * SN + i) * 2 + 1];
+                const double br = X[(kl * SN + j) * 2], bi = X[(kl * SN + j) * 2 + 1];
+                re += ar * br;
+                re += ai * bi;
+                im += ai * br;
+                im -= ar * bi;
+            }
+            accr[m] = re; acci[m] = im;
+        }
+        __syncthreads();
+    }
+    int nan_here = 0;
+    const double kd = (double)K;
+#pragma unroll
+    for (int m = 0; m < CTRI; ++m) {
+        if (tid + m * CT >= ntri) continue;
+        const int i = ei[m], j = ej[m];
+        const double re = accr[m] / kd, im = i == j ? 0.0 : acci[m] / kd;
+        nan_here |= (re != re) || (im != im);
+        Rm[(i * SN + j) * 2] = re; Rm[(i * SN + j) * 2 + 1] = im;
+        Rm[(j * SN + i) * 2] = re; Rm[(j * SN + i) * 2 + 1] = -im;
+    }
+    const int any_nan = __syncthreads_or(nan_here);                  // (and the barrier behind the writes of Rm)
+    if (a.csdm)
+        for (int e = tid; e < N * N; e += CT) {
+            const int i = e / N, j = e - i * N;
+            a.csdm[(cell * N * N + e) * 2] = Rm[(i * SN + j) * 2];
+            a.csdm[(cell * N * N + e) * 2 + 1] = Rm[(i * SN + j) * 2 + 1];
+        }
+    double t = 0.0;
+    for (int i = 0; i < N; ++i) t += Rm[(i * SN + i) * 2];        // (every thread, the same order)
+    const double nan_ = __builtin_nan("");
+    if (any_nan || t == 0.0 || t != t) {
+        if (a.map)
+            for (int g = tid; g < G; g += CT) { a.map[cell * G + g] = nan_; a.map[(a.cells + cell) * G + g] = nan_; }
+        if (tid == 0) {
+            a.index[cell] = -1; a.index[a.cells + cell] = -1;
+            a.power[cell] = nan_; a.power[a.cells + cell] = nan_;
+        }
+        return;
+    }
+    // R' = R + delta (t / N) I, then its Cholesky factor column by column
+    const double lam = a.loading * (t / (double)N);
+    for (int e = tid; e < N * N; e += CT) {
+        const int i = e / N, j = e - i * N;
+        Lm[(i * SN + j) * 2] = Rm[(i * SN + j) * 2] + (i == j ? lam : 0.0);
+        Lm[(i * SN + j) * 2 + 1] = Rm[(i * SN + j) * 2 + 1];
+    }
+    __syncthreads();
+    bool chol_ok = true;
+    for (int j = 0; j < N; ++j) {
+        double d = Lm[(j * SN + j) * 2];
+        for (int k = 0; k < j; ++k) {
+            const double lr = Lm[(j * SN + k) * 2], li = Lm[(j * SN + k) * 2 + 1];
+            d -= lr * lr;
+            d -= li * li;
+        }
+        if (!(d > 0.0)) { chol_ok = false; break; }                  // (the same d in every thread)
+        const double ljj = sqrt(d);
+        if (tid == j) invd[j] = 1.0 / ljj;
+        if (tid > j && tid < N) {
+            double sr = Lm[(tid * SN + j) * 2], si = Lm[(tid * SN + j) * 2 + 1];
+            for (int k = 0; k < j; ++k) {                            // L_ik conj(L_jk)
+                const double ar = Lm[(tid * SN + k) * 2], ai = Lm[(tid * SN + k) * 2 + 1];
+                const double br = Lm[(j * SN + k) * 2], bi = Lm[(j * SN + k) * 2 + 1];
+                sr -= ar * br;
+                sr -= ai * bi;
+                si -= ai * br;
+                si += ar * bi;
+            }
+            Lm[(tid * SN + j) * 2] = sr / ljj;
+            Lm[(tid * SN + j) * 2 + 1] = si / ljj;
+        }
+        __syncthreads();
+    }
+    // the grid: one lane per point, its vector in LDS column tid of Y (consecutive lanes, consecutive banks)
+    const double2* steer = (const double2*)a.steer + (int64_t)band * N * G;
+    const double2* R2 = (const double2*)Rm;
+    const double2* L2 = (const double2*)Lm;
+    double* const yr = Y + tid;                                      // y_i = (yr[i * 2 CT], yr[i * 2 CT + CT])
+    const double nn = (double)N * (double)N;
+    double bc = 0.0, bb = 0.0;
+    int gc = -1, gb = -1;
+    for (int g = tid; g < G; g += CT) {
+        for (int i = 0; i < N; ++i) {
+            const double2 v = steer[(int64_t)i * G + g];
+            yr[i * 2 * CT] = v.x; yr[i * 2 * CT + CT] = v.y;
+        }
+        // Bartlett: sum_i R_ii |a_i|^2 + 2 Re(conj(a_i) sum_{j<i} R_ij a_j)
+        double pb = 0.0;
+        for (int i = 0; i < N; ++i) {
+            double ur = 0.0, ui = 0.0;
+            for (int j = 0; j < i; ++j) {
+                const double2 r = R2[i * SN + j];
+                const double vr = yr[j * 2 * CT], vi = yr[j * 2 * CT + CT];
+                ur = __builtin_fma(r.x, vr, ur);
+                ur = __builtin_fma(-r.y, vi, ur);
+                ui = __builtin_fma(r.x, vi, ui);
+                ui = __builtin_fma(r.y, vr, ui);
+            }
+            const double ar = yr[i * 2 * CT], ai = yr[i * 2 * CT + CT];
+            pb += R2[i * SN + i].x * (ar * ar + ai * ai);
+            pb += 2.0 * (ar * ur + ai * ui);
+        }
+        pb /= nn;
+        // Capon: y in place of a
+        double pc = nan_;
+        if (chol_ok) {
+            double q = 0.0;
+            for (int i = 0; i < N; ++i) {
+                double sr = yr[i * 2 * CT], si = yr[i * 2 * CT + CT];
+                for (int j = 0; j < i; ++j) {
+                    const double2 l = L2[i * SN + j];
+                    const double vr = yr[j * 2 * CT], vi = yr[j * 2 * CT + CT];
+                    sr = __builtin_fma(-l.x, vr, sr);
+                    sr = __builtin_fma(l.y, vi, sr);
+                    si = __builtin_fma(-l.x, vi, si);
+                    si = __builtin_fma(-l.y, vr, si);
+                }
+                const double id = invd[i];
+                sr *= id; si *= id;
+                yr[i * 2 * CT] = sr; yr[i * 2 * CT + CT] = si;
+                q = __builtin_fma(sr, sr, q);
+                q = __builtin_fma(si, si, q);
+            }
+            pc = 1.0 / q;
+        }
+        if (a.map) { a.map[cell * G + g] = pc; a.map[(a.cells + cell) * G + g] = pb; }
+        if (capon_better(pc, g, bc, gc)) { bc = pc; gc = g; }
+        if (capon_better(pb, g, bb, gb)) { bb = pb; gb = g; }
+    }
+    capon_best(bc, gc, red_p, red_g, tid);
+    capon_best(bb, gb, red_p, red_g, tid);
+    if (tid == 0) {
+        a.index[cell] = gc; a.index[a.cells + cell] = gb;
+        a.power[cell] = gc < 0 ? nan_ : bc;
+        a.power[a.cells + cell] = gb < 0 ? nan_ : bb;
+    }
+}
+
+}  // namespace
+
+// dynamic LDS bytes of capon_kernel for an array of nelem elements (see the kernel's head)
+size_t nbls_capon_lds_bytes_of(int nelem) {
+    const size_t n = (size_t)nelem, xy = (size_t)(CCH > CT ? CCH : CT) * n * 2;
+    return (2 * n * n * 2 + ((n + 1) & ~(size_t)1) + xy) * sizeof(double);
+}
+
+// The plan's tables on the host, float64, un-fused (see the head of this file).  coef [nbands][maxLs][2] (zeros beyond
+// Ls_b), steer [nbands][nelem][G][2].
+void nbls_capon_tables_of(const double* xij, int nelem, double fs, const double* grid, int G, const double* freq,
+                          const int32_t* snap_len, int nbands, int maxLs, double* coef, double* steer) {
+    const double two_pi = 2.0 * M_PI;
+    for (int b = 0; b < nbands; ++b) {
+        const double wf = two_pi * freq[b];
+        const int Ls = snap_len[b];
+        double* c = coef + (size_t)b * maxLs * 2;
+        for (int n = 0; n < maxLs; ++n) {
+            if (n >= Ls) { c[2 * n] = 0.0; c[2 * n + 1] = 0.0; continue; }
+            const double hann = 0.5 - 0.5 * std::cos((two_pi * ((double)n + 0.5)) / (double)Ls);
+            const double p = -((wf * (double)n) / fs);
+            c[2 * n] = hann * std::cos(p);
+            c[2 * n + 1] = hann * std::sin(p);
+        }
+        double* s = steer + (size_t)b * nelem * G * 2;
+        for (int g = 0; g < G; ++g) {
+            const double s0 = grid[2 * g], s1 = grid[2 * g + 1];
+            s[2 * g] = 1.0; s[2 * g + 1] = 0.0;
+            for (int i = 1; i < nelem; ++i) {
+                const double tau = xij[2 * (i - 1)] * s0 + xij[2 * (i - 1) + 1] * s1;
+                const double q = -(wf * tau);
+                s[((size_t)i * G + g) * 2] = std::cos(q);
+                s[((size_t)i * G + g) * 2 + 1] = std::sin(q);
+            }
+        }
+    }
+}
+
+hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
+    if (nu <= 0) return hipSuccess;
+    if (h->nelem > CMAXN || h->nelem < 1) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
+    CArgs a{};
+    a.filt = h->d_filt;
+    a.npts_pad = h->npts_pad;
+    a.N = h->nelem; a.nseg = h->nbands / h->fbands;      // result row r is band r / nseg
+    a.Wb = h->d_W; a.incb = h->d_inc;
+    a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
+    a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
+    a.G = h->capon_n; a.maxLs = h->capon_maxls;
+    a.par = h->d_capon_par; a.coef = h->d_capon_coef; a.steer = h->d_capon_steer;
+    a.loading = h->capon_loading;
+    a.cells = (int64_t)h->nbands * h->vector_len;
+    a.index = h->d_capon_index; a.power = h->d_capon_power;
+    a.map = h->capon_maps ? h->d_capon_map.p : nullptr;
+    a.csdm = h->capon_csdm ? h->d_capon_csdm.p : nullptr;
+    const size_t lds = nbls_capon_lds_bytes_of(h->nelem);
+    if (!h->capon_attr_set) {              // once per handle (a streamed pass launches per unit batch)
+        const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)nbls_capon_lds_bytes_of(CMAXN));
+        if (e != hipSuccess) return e;
+        h->capon_attr_set = true;
+    }
+    hipLaunchKernelGGL(capon_kernel, dim3((unsigned)nu), dim3(CT), lds, st, a);
+    return hipGetLastError();
+}

@@ -164,6 +164,32 @@ struct nbls_handle {
     dev_buf<int32_t> d_grid_index;  // [B][VL]
     dev_buf<double> d_grid_fp;      // [2][B][VL]: grid_fstat | grid_power
     dev_buf<double> d_grid_map;     // [B][VL][G] (a plan that asked for the map)
+    // ---- Capon / Bartlett spectra of the narrow band's cross-spectral matrix (nbls_set_capon, capon.hip) ----
+    struct capon_request {
+        std::vector<double> grid;       // [G][2] slowness vectors (empty: off)
+        std::vector<double> freq;       // [nbands] Hz
+        std::vector<int32_t> ls, hs;    // [nbands] snapshot length and hop
+        double loading = 0.0;
+        int flags = 0;
+    };
+    capon_request want_capon;       // nbls_set_capon: read by the next nbls_plan
+    capon_request capon;            // the plan's copy
+    int capon_n = 0;                // G of the plan (0: the plan computes no spectra)
+    int capon_maxls = 0;            // the longest snapshot of the plan: the row length of h_capon_coef
+    double capon_loading = 0.0;
+    bool capon_maps = false, capon_csdm = false;    // the plan keeps both maps / the matrix R
+    bool capon_attr_set = false;    // capon_kernel has been given its dynamic LDS limit on this handle's device
+    bool capon_valid = false;       // a pass of this plan has run the solve stage: the Capon results are there
+    std::vector<int32_t> h_capon_par;   // [fbands][3]: Ls, Hs, K
+    std::vector<double> h_capon_coef;   // [fbands][maxLs][2] snapshot coefficients (zeros beyond Ls_b)
+    std::vector<double> h_capon_steer;  // [fbands][nelem][G][2] steering vectors, consecutive g side by side
+    dev_buf<int32_t> d_capon_par;
+    dev_buf<double> d_capon_coef;
+    dev_buf<double> d_capon_steer;
+    dev_buf<int32_t> d_capon_index; // [2][B][VL]: capon_index | bartlett_index
+    dev_buf<double> d_capon_power;  // [2][B][VL]: capon_power | bartlett_power
+    dev_buf<double> d_capon_map;    // [2][B][VL][G] (a plan that asked for the maps)
+    dev_buf<double> d_capon_csdm;   // [B][VL][N][N][2] (a plan that asked for R)
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -323,7 +349,13 @@ hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStre
 size_t nbls_beam_grid_lds_bytes_of(int nelem, int W, int halo);
 // the delay table d[G][nelem] of a grid and its halo (host, un-fused arithmetic); false: some |fs xij . s_g| reaches 2^30
 bool nbls_beam_grid_delays_of(const double* xij, int nelem, double fs, const double* grid, int G, int32_t* d, int* halo);
-// [gather ->] solve -> [uncertainty ->] [beam ->] [closure ->] [grid search ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
+// Capon / Bartlett spectra of units [u0, u0 + nu) for the plan's full array (capon.hip)
+hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+size_t nbls_capon_lds_bytes_of(int nelem);
+// the snapshot coefficients coef [nbands][maxLs][2] and steering vectors steer [nbands][nelem][G][2] of a plan (host, un-fused)
+void nbls_capon_tables_of(const double* xij, int nelem, double fs, const double* grid, int G, const double* freq,
+                          const int32_t* snap_len, int nbands, int maxLs, double* coef, double* steer);
+// [gather ->] solve -> [uncertainty ->] [beam ->] [closure ->] [grid search ->] [Capon ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
 hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);

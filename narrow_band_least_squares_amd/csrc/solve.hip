@@ -1439,6 +1439,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
     // the slowness-grid search of a plan that asked for one: the full array only, behind the plan's own estimator (a plan
     // with a lag seed has run it in the correlation stage, ahead of the seeded correlator: once per pass)
     if (h->grid_n > 0 && h->seed.empty() && &s == &h->est[0] && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;
+    // the Capon / Bartlett spectra of a plan that asked for them (nbls_set_capon): the full array, once per pass
+    if (h->capon_n > 0 && &s == &h->est[0] && (e = nbls_launch_capon(h, u0, nu, st)) != hipSuccess) return e;
     return pack_weights_of(h, s, u0, nu, st);
 }
 

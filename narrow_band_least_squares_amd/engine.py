@@ -363,15 +363,21 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
-               want_consistency=False):
+               want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
     lags are wanted.  ``grid_points`` > 0: ``grid_index`` / ``grid_fstat`` / ``grid_power`` of a slowness-grid search over that
     many points, and with ``want_grid_map`` its ``grid_map`` (nbands, vector_len, grid_points).  ``want_consistency``:
     ``consistency`` / ``closure_max`` (nbands, vector_len) and ``element_consistency`` (nbands, vector_len, nchans), the
-    closure of the picked lags."""
+    closure of the picked lags.  ``capon_points`` > 0: ``capon_index`` / ``capon_power`` / ``bartlett_index`` /
+    ``bartlett_power`` of the Capon spectra over that many points, with ``want_capon_maps`` ``capon_map`` / ``bartlett_map``
+    (nbands, vector_len, capon_points) and with ``want_capon_csdm`` ``capon_csdm`` (nbands, vector_len, nchans, nchans)
+    complex; None otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
+    cpi = np.zeros((2, nb, vector_len), dtype=np.int32) if capon_points else (None, None)
+    cpp = np.zeros((2, nb, vector_len)) if capon_points else (None, None)
+    cpm = np.zeros((2, nb, vector_len, capon_points)) if (capon_points and want_capon_maps) else (None, None)
     clo = np.zeros((2, nb, vector_len)) if want_consistency else (None, None)
     gfp = np.zeros((2, nb, vector_len)) if grid_points else (None, None)
     grids = np.zeros((4, nb, vector_len))
@@ -388,6 +394,10 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      grid_index=np.zeros((nb, vector_len), dtype=np.int32) if grid_points else None, grid_fstat=gfp[0],
                      grid_power=gfp[1],
                      grid_map=np.zeros((nb, vector_len, grid_points)) if (grid_points and want_grid_map) else None, sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
+                     capon_index=cpi[0], bartlett_index=cpi[1], capon_power=cpp[0], bartlett_power=cpp[1],
+                     capon_map=cpm[0], bartlett_map=cpm[1],
+                     capon_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128)
+                     if (capon_points and want_capon_csdm) else None,
                      lts=alpha < 1.0, fs=fs)
 
 
@@ -597,7 +607,7 @@ def upload_trace(h, data, fs):
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False):
+           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -613,7 +623,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     (``Handle.set_beam_grid``; likewise).  ``lag_seed``: one half-width in samples per band of THIS plan (the bands
     ``bands`` of the Prep, in their order): the plan searches every pair's lag only that near the delay the grid maximum
     predicts (``Handle.set_lag_seed``, ``planner.seed_halfwidths``; needs ``beam_grid``; likewise).  ``closure``: the plan
-    also computes the closure of the picked lags behind every solve (``Handle.set_closure``; likewise)."""
+    also computes the closure of the picked lags behind every solve (``Handle.set_closure``; likewise).  ``capon``: a dict
+    of ``Handle.set_capon``'s arguments, ``freqs`` / ``snap_len`` / ``snap_hop`` one per band of the Prep: the plan also
+    computes the Capon spectra of its bands (likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -645,6 +657,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_beam_grid(beam_grid, beam_grid_map)
     if lag_seed is not None:
         h.set_lag_seed(lag_seed)
+    if capon is not None:
+        h.set_capon(**dict(capon, **{k: np.asarray(capon[k])[idx] for k in ('freqs', 'snap_len', 'snap_hop')}))
     try:
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
@@ -661,6 +675,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_beam_grid(None)
         if lag_seed is not None:
             h.set_lag_seed(None)
+        if capon is not None:
+            h.set_capon(None)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -785,6 +801,12 @@ def collect(res, h, b0, b1, streamed, note):
         res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = h.fetch_beam_grid()
     if res.grid_map is not None:
         res.grid_map[b0:b1] = h.fetch_beam_grid_map()
+    if res.capon_index is not None:
+        res.capon_index[b0:b1], res.capon_power[b0:b1], res.bartlett_index[b0:b1], res.bartlett_power[b0:b1] = h.fetch_capon()
+    if res.capon_map is not None:
+        res.capon_map[b0:b1], res.bartlett_map[b0:b1] = h.fetch_capon_maps()
+    if res.capon_csdm is not None:
+        res.capon_csdm[b0:b1] = h.fetch_capon_csdm()
     if not live:
         note.bands(b0, b1)
 
@@ -809,6 +831,7 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
     handle: each is collected before the next is planned.  -> the (handle, b0, b1) still to collect."""
     launched, prep = [], None
     seed_all = launch_kw.get('lag_seed')
+    capon_all = launch_kw.get('capon')
     nchans, npts = _shape_of(data)
     for g, (b0, b1) in enumerate(bounds):
         prep = prepare(nchans, npts, res.fs, rij, band_edges[b0:b1], winlens[b0:b1], *prep_tail, common=prep,
@@ -827,6 +850,8 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
         ordered = launched and not sequential and GROUP_ORDER
         if launch_kw.get('lag_seed') is not None:         # (one half-width per band of the call: this group's)
             launch_kw = dict(launch_kw, lag_seed=seed_all[b0:b1])
+        if capon_all is not None:                         # (likewise the Capon tables)
+            launch_kw = dict(launch_kw, capon=dict(capon_all, **{k: capon_all[k][b0:b1] for k in ('freqs', 'snap_len', 'snap_hop')}))
         try:
             launch(h, data, prep, trace_from=launched[0][0] if (launched and not sequential) else None, trace_ready=early,
                    after=launched[-1][0] if ordered else None, stream=streamed,
@@ -855,12 +880,28 @@ def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
     return seeds
 
 
+def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm, W):
+    """The Capon keywords of ``process`` / ``process_batch`` -> the ``capon`` dict of ``launch`` or None; ``ValueError`` before
+    any GPU work (``planner.check_capon``)."""
+    if capon_grid is None:
+        if capon_freqs is not None or capon_snapshots is not None or want_capon_maps or want_capon_csdm:
+            raise ValueError('capon_freqs, capon_snapshots, want_capon_maps and want_capon_csdm need capon_grid')
+        return None
+    if capon_freqs is None or capon_snapshots is None:
+        raise ValueError('capon_grid needs capon_freqs (planner.capon_frequencies) and capon_snapshots (planner.capon_snapshots)')
+    g, f, ls, hs, delta = planner.check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, W,
+                                              want_capon_maps, want_capon_csdm)
+    return dict(grid=g, freqs=f, snap_len=ls, snap_hop=hs, loading=delta, want_maps=bool(want_capon_maps),
+                want_csdm=bool(want_capon_csdm))
+
+
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-            want_grid_map=False, seed_halfwidths=None, want_consistency=False):
+            want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
+            capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -894,6 +935,13 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     the picked lags over the element triplets of each window, and per element the rms over the triplets that hold it,
     computed on the GPU behind each unit's solve (``nbls_set_closure``); they follow whatever picks
     the call makes (refined, bounded, seeded); ``process_segmented`` refuses it.
+    capon_grid (G, 2) s/km with capon_freqs (Hz per band, ``planner.capon_frequencies``) and capon_snapshots ((Ls, Hs) in
+    samples, ``planner.capon_snapshots``): also ``res.capon_index`` / ``res.bartlett_index`` (int32) and ``res.capon_power`` /
+    ``res.bartlett_power`` (nbands, vector_len), per window the maxima of the Capon (MVDR) and Bartlett slowness spectra of
+    the band's cross-spectral matrix under the diagonal loading ``capon_loading``, computed on the GPU behind each unit's
+    solve (``nbls_set_capon``); want_capon_maps=True: also ``res.capon_map`` / ``res.bartlett_map``
+    (nbands, vector_len, G); want_capon_csdm=True: also ``res.capon_csdm`` (nbands, vector_len, N, N) complex.  ``ValueError``
+    before any GPU work for whatever the library would refuse (``planner.check_capon``); ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -916,6 +964,13 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
     seeds = _check_seed(seed_halfwidths, len(band_edges), sgrid, min_velocity)
     cap = max_bands_per_pass(nchans, npts)
+    # (the Capon tables are checked against the window lengths: planned here already, before the upload starts)
+    capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
+                         None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0])
+    if cap < 1 and not prefiltered and capon is not None:
+        raise ValueError('capon_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
+                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
+                         'the Capon spectra are not available there' % (nchans, npts))
     single = prefiltered or handle is not None or not upload
     up, resident = start_upload(data, fs, device) if upload and handle is None and (cap >= 1 or prefiltered) else (None, False)
     try:
@@ -927,14 +982,15 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                                      group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
-                         want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency)
+                         want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
+                         0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency))
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon)
     finally:
         if up is not None:
             up.close()
@@ -1162,7 +1218,8 @@ def batch_rows(streams):
 def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
-                  want_consistency=False):
+                  want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
+                  want_capon_maps=False, want_capon_csdm=False):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1182,13 +1239,17 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     prep = prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type, filter_order, filter_ripple,
                    vector_len, prefiltered)
     VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
+    capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
+                         prep.W)
+    CG = 0 if capon is None else len(capon['grid'])
     limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
     per_sub = S if max_bands_per_pass(S * nchans, npts) >= 1 else max_bands_per_pass(nchans, npts)
     if per_sub < 1:
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
                          'process it on its own' % (nchans, npts))
     out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
-                      grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency)
+                      grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
+                      want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1204,7 +1265,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency))
+                       closure=bool(want_consistency), capon=capon)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
@@ -1215,6 +1276,9 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 clo = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_closure()] if want_consistency else None
                 sg = [a.reshape(b1 - b0, k, VL) for a in h.fetch_beam_grid()] if G else None
                 sgmap = h.fetch_beam_grid_map().reshape(b1 - b0, k, VL, G) if (G and want_grid_map) else None
+                cp = [a.reshape(b1 - b0, k, VL) for a in h.fetch_capon()] if CG else None
+                cpmap = [a.reshape(b1 - b0, k, VL, CG) for a in h.fetch_capon_maps()] if (CG and want_capon_maps) else None
+                cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
@@ -1228,6 +1292,13 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                         res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = [a[:, j] for a in sg]
                     if sgmap is not None:
                         res.grid_map[b0:b1] = sgmap[:, j]
+                    if CG:
+                        (res.capon_index[b0:b1], res.capon_power[b0:b1], res.bartlett_index[b0:b1],
+                         res.bartlett_power[b0:b1]) = [a[:, j] for a in cp]
+                    if cpmap is not None:
+                        res.capon_map[b0:b1], res.bartlett_map[b0:b1] = [a[:, j] for a in cpmap]
+                    if cpr is not None:
+                        res.capon_csdm[b0:b1] = cpr[:, j]
     finally:
         h.set_segments(1)
     for res, t0 in zip(out, t0s):

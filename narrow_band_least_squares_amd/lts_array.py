@@ -58,9 +58,35 @@ def _returns_grid(res, grid, want_map):
     return out + ((res.grid_map[0, :n].copy(),) if want_map else ())
 
 
+def _returns_capon(res, grid, want_maps, band=0, n=None):
+    """A band's Capon results as a dict: the four fields, the slowness (``grid_slowness``) at either index and, when asked,
+    both maps (csrc/capon.hip: capon_kernel).  ``n=None``: the band's first ``nwin`` cells, copied; else whole rows."""
+    sl = slice(None) if n is None else slice(0, n)
+    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    out = {k: pick(getattr(res, k)) for k in ('capon_index', 'capon_power', 'bartlett_index', 'bartlett_power')}
+    out['capon_vel'], out['capon_baz'] = grid_slowness(grid, out['capon_index'])
+    out['bartlett_vel'], out['bartlett_baz'] = grid_slowness(grid, out['bartlett_index'])
+    if want_maps:
+        out['capon_map'], out['bartlett_map'] = pick(res.capon_map), pick(res.bartlett_map)
+    return out
+
+
+def _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading, maps):
+    """The Capon keywords of ``engine.process`` for one filtered band of window length ``W`` samples; the snapshots default
+    to ``planner.capon_snapshots``.  ``ValueError`` before any GPU work."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    _check_flag('maps', maps)
+    if snapshots is None:
+        f = planner.check_capon(nchans, grid, [freq], (1, 1), loading, [W])[1]
+        snapshots = planner.capon_snapshots(planner.co_array(rij)[0], grid, fs, f, [W])
+    planner.check_capon(nchans, grid, [freq], snapshots, loading, [W], bool(maps))
+    return dict(capon_grid=grid, capon_freqs=[freq], capon_snapshots=snapshots, capon_loading=loading,
+                want_capon_maps=bool(maps))
+
+
 def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
            want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False, seed_halfwidths=None,
-           want_consistency=False):
+           want_consistency=False, capon=None):
     """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded``, ``ltsva_grid``, ``ltsva_seeded`` and
     ``ltsva_consistency``: the checks, the geometry, the device pass, the returns."""
     data, fs, t0 = engine.stream_rows(st)
@@ -80,10 +106,14 @@ def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_ar
     res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
                          prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
                          want_subsample=want_subsample, min_velocity=min_velocity, slowness_grid=slowness_grid,
-                         want_grid_map=grid_map, seed_halfwidths=seed_halfwidths, want_consistency=want_consistency)
+                         want_grid_map=grid_map, seed_halfwidths=seed_halfwidths, want_consistency=want_consistency,
+                         **(capon(rij, fs, len(data[0])) if capon is not None else {}))
     out = (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
     if slowness_grid is not None:
         out = out + _returns_grid(res, slowness_grid, grid_map)
+    if capon is not None:
+        out = out + (_returns_capon(res, capon(rij, fs, len(data[0]))['capon_grid'], res.capon_map is not None,
+                                    n=int(res.nwin[0])),)
     return out + _returns_consistency(res) if want_consistency else out
 
 
@@ -206,6 +236,31 @@ def ltsva_seeded(st, lat_list, lon_list, window_length, window_overlap, slowness
                   bool(grid_map), seeds)
 
 
+def ltsva_capon(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None, snapshots=None,
+                loading=0.01, maps=False):
+    """``ltsva`` followed by the Capon (MVDR) and Bartlett slowness spectra of the narrow band's cross-spectral matrix: per
+    window the snapshots (Hann-tapered DFT bins at ``freq`` Hz, ``snapshots = (Ls, Hs)`` samples long and apart; default
+    ``planner.capon_snapshots``) of the full array give the matrix R, and over the slowness vectors ``slowness_grid`` (G, 2)
+    s/km ``P_B = Re(a^H R a) / N^2`` and, with ``R' = R + loading (tr R / N) I``, ``P_C = 1 / (a^H R'^-1 a)`` — the adaptive
+    beamformer that separates two arrivals closer than the array's beam width, where every other estimate here assumes one
+    wave (DESIGN.md section 18 has the definition and the counts).  Returns ``ltsva``'s 8-tuple followed by one dict:
+    ``capon_index`` / ``bartlett_index`` (int32, -1 where there is no maximum), ``capon_power`` / ``bartlett_power``,
+    ``capon_vel`` / ``capon_baz`` / ``bartlett_vel`` / ``bartlett_baz`` (``grid_slowness`` at the indices) and, with
+    ``maps=True``, ``capon_map`` / ``bartlett_map`` (nwin, G).  Computed on the GPU behind each window's solve
+    (csrc/capon.hip).  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    _check_elements_strict(len(st), alpha)
+    nchans = len(st)
+
+    def keywords(rij_used, fs, npts):
+        W = planner.window_plan(npts, fs, window_length, window_overlap)[0]
+        return _capon_keywords(nchans, rij_used, fs, int(W), slowness_grid, freq, snapshots, loading, maps)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    data, fs, _ = engine.stream_rows(st)
+    keywords(rij, fs, len(data[0]))                       # (every ValueError before any GPU work)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, capon=keywords)
+
+
 def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False,
                 subsample=False, min_velocity=None, slowness_grid=None):
     """``ltsva`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of 8-tuples,
@@ -217,7 +272,22 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     the lags are searched within their physical range as in ``ltsva_bounded``; it combines with both flags, the fractions
     and the beam then follow the bounded picks.  ``slowness_grid`` (G, 2) s/km, default None: every tuple is followed by the
     five grid returns of ``ltsva_grid`` (no map), element i equal to ``ltsva_grid(streams[i], ...)``; it combines with the
-    others, because it reads none of their results."""
+    others, because it reads none of their results.  ``ltsva_capon_batch`` is this call with the Capon spectra."""
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
+                        slowness_grid, None)
+
+
+def ltsva_capon_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
+                      snapshots=None, loading=0.01, maps=False):
+    """``ltsva_capon`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
+    element i equal to ``ltsva_capon(streams[i], ...)``; the streams as for ``ltsva_batch``."""
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, False, False, None, None,
+                        dict(slowness_grid=slowness_grid, freq=freq, snapshots=snapshots, loading=loading, maps=maps))
+
+
+def _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
+                 slowness_grid, capon):
+    """The one body of ``ltsva_batch`` and ``ltsva_capon_batch`` (``capon``: the parameters of ``ltsva_capon`` or None)."""
     _check_flag('beam', beam)
     _check_flag('subsample', subsample)
     if min_velocity is not None:
@@ -228,10 +298,17 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     if not streams:
         return []
     recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    ckw = {}
+    if capon is not None:
+        _check_elements_strict(nchans, alpha)
+        crij = get_rij(lat_list, lon_list, nchans) if rij is None else rij
+        W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
+        ckw = _capon_keywords(nchans, crij, fs, int(W), capon['slowness_grid'], capon['freq'], capon.get('snapshots'),
+                              capon.get('loading', 0.01), capon.get('maps', False))
     if len(streams) == 1:          # a batch of one IS the single call
         return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
-                        slowness_grid)]
-    nchans = len(recs[0])
+                        slowness_grid, capon=(lambda *_: ckw) if ckw else None)]
     engine.check_elements(nchans, alpha)
     if rij is None:
         rij = get_rij(lat_list, lon_list, nchans)
@@ -239,20 +316,22 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
         print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
                                    prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
-                                   min_velocity=min_velocity, slowness_grid=slowness_grid)
+                                   min_velocity=min_velocity, slowness_grid=slowness_grid, **ckw)
     return [(_returns_beam if beam else _returns)(res, nchans, alpha) +
-            (() if slowness_grid is None else _returns_grid(res, slowness_grid, False)) for res in results]
+            (() if slowness_grid is None else _returns_grid(res, slowness_grid, False)) +
+            ((_returns_capon(res, ckw['capon_grid'], ckw['want_capon_maps'], n=int(res.nwin[0])),) if ckw else ())
+            for res in results]
 
 
 def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity=None,
-            slowness_grid=None, consistency=False):
+            slowness_grid=None, consistency=False, capon=None):
     """The single call a batch of one recording / one estimator with nothing removed is: ``ltsva`` itself for the plain
     one, else the strict element check of ``ltsva_beam`` / ``ltsva_subsample`` and the shared body."""
-    if not beam and not subsample and min_velocity is None and slowness_grid is None and not consistency:
+    if not beam and not subsample and min_velocity is None and slowness_grid is None and not consistency and capon is None:
         return ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)
     _check_elements_strict(len(st), alpha)
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample),
-                  min_velocity, slowness_grid, want_consistency=bool(consistency))
+                  min_velocity, slowness_grid, want_consistency=bool(consistency), capon=capon)
 
 
 def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False,

@@ -15,7 +15,7 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
-from .lts_array import grid_slowness
+from .lts_array import grid_slowness, _returns_capon
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -92,7 +92,7 @@ def _prefix_stdict(stdict, band_number):
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
                key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-               want_grid_map=False, seed_period_fraction=None, want_consistency=False):
+               want_grid_map=False, seed_period_fraction=None, want_consistency=False, capon=None):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -134,7 +134,8 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
                          min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map,
-                         seed_halfwidths=seeds, want_consistency=want_consistency)
+                         seed_halfwidths=seeds, want_consistency=want_consistency,
+                         **(capon(rij, fs, len(rows[0]), edges, winlens) if capon is not None else {}))
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -295,6 +296,49 @@ def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + \
         ((res.grid_map,) if grid_map else ())
+
+
+def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                    FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                    slowness_grid, capon_freqs=None, snapshots=None, loading=0.01, maps=False):
+    """``narrow_band_least_squares`` followed by the Capon (MVDR) and Bartlett slowness spectra of every band's
+    cross-spectral matrix (``lts_array.ltsva_capon``), computed on the GPU behind each window's solve
+    from the filtered band that is already there.  ``capon_freqs`` (Hz per band) defaults to
+    ``planner.capon_frequencies`` of the call's bands, ``snapshots`` ((Ls, Hs) in samples) to ``planner.capon_snapshots``.
+    Returns the nine values of ``narrow_band_least_squares`` followed by one dict: ``capon_index`` / ``bartlett_index``
+    (int32), ``capon_power`` / ``bartlett_power``, ``capon_vel`` / ``capon_baz`` / ``bartlett_vel`` / ``bartlett_baz``
+    (``lts_array.grid_slowness`` at the indices), each (NBANDS, vector_len) with zeros beyond a band's windows, and with
+    ``maps=True`` ``capon_map`` / ``bartlett_map`` (NBANDS, vector_len, G).  Whatever the library would refuse raises
+    ``ValueError`` before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a
+    pass."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    if not isinstance(maps, (bool, np.bool_)):
+        raise ValueError('maps must be True or False, not %r' % (maps,))
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+
+    def keywords(rij_used, fs, npts, edges, winlens):
+        W = engine.plan_windows(npts, fs, winlens, WINOVER, vector_len)[0]
+        f = planner.capon_frequencies(edges) if capon_freqs is None else capon_freqs
+        snaps = snapshots
+        if snaps is None:
+            f = planner.check_capon(len(st), grid, f, (1, 1), loading, W)[1]
+            snaps = planner.capon_snapshots(planner.co_array(rij_used)[0], grid, fs, f, W)
+        planner.check_capon(len(st), grid, f, snaps, loading, W, bool(maps))
+        return dict(capon_grid=grid, capon_freqs=f, capon_snapshots=snaps, capon_loading=loading, want_capon_maps=bool(maps))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
+    out = _returns_capon(res, grid, bool(maps), band=None)
+    computed = np.arange(res.capon_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    for k in ('capon_vel', 'capon_baz', 'bartlett_vel', 'bartlett_baz'):
+        out[k] = np.where(computed, out[k], 0.0)                     # (zero-padded like vel_array)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (out,)
 
 
 def narrow_band_least_squares_seeded(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,

@@ -542,3 +542,102 @@ def lag_limits(xij, fs, min_velocity):
     xij = np.asarray(xij, dtype=np.float64)
     L = np.ceil(float(fs) * np.hypot(xij[:, 0], xij[:, 1]) / v) + 1.0
     return np.minimum(L, 2.0 ** 31 - 1).astype(np.int32)
+
+
+MAX_CAPON_ELEMENTS = 32      # array elements of a plan with Capon spectra (NBLS_CAPON_MAX_ELEMENTS)
+MAX_CAPON_STEER_BYTES = 1 << 30      # the steering table nbands * G * N * 16 bytes of one plan
+
+
+def _real(v):
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def capon_frequencies(band_edges):
+    """The frequency at which the Capon spectra of every band are formed (``nbls_set_capon``) ->
+    float64 (nbands,): the geometric centre ``sqrt(f_lo * f_hi)`` of the band.  ``ValueError`` unless every edge is a finite
+    real > 0."""
+    try:
+        e = np.asarray(band_edges, dtype=np.float64)
+    except Exception:
+        raise ValueError('band_edges must be a list of (f_lo, f_hi) in Hz')
+    if e.ndim != 2 or e.shape[1] != 2 or e.shape[0] < 1:
+        raise ValueError('band_edges must be a non-empty list of (f_lo, f_hi) in Hz, not %r' % (band_edges,))
+    if not np.all(np.isfinite(e)) or np.any(e <= 0.0):
+        raise ValueError('band_edges must hold finite frequencies above 0 Hz')
+    return np.sqrt(e[:, 0] * e[:, 1])
+
+
+def capon_snapshots(xij, grid, fs, freqs, W_list):
+    """Per-band snapshot length and hop of the Capon spectra -> (Ls int32 (nbands,), Hs int32 (nbands,)):
+    ``Ls = min(W, max(ceil(2 fs / f), ceil(2 fs tau_max)))`` samples, ``tau_max`` the largest ``|xij[i-1] . s_g|`` over the
+    pairs (0, i) and the grid — the narrow-band condition: the snapshot's frequency bin (two bins of the Hann taper, 2 fs / Ls)
+    must be narrower than ``1 / tau_max``, and hold two periods — and ``Hs = max(1, Ls // 2)``, the half overlap of a Hann
+    taper.  ``xij`` is the co-array (``co_array``), whose first N-1 rows are the pairs (0, i)."""
+    g = check_slowness_grid(grid)
+    xij = np.asarray(xij, dtype=np.float64)
+    f = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    W = np.atleast_1d(np.asarray(W_list)).astype(np.int64)
+    if f.shape != W.shape:
+        raise ValueError('one window length per frequency')
+    if not _real(fs) or not np.isfinite(float(fs)) or float(fs) <= 0.0:
+        raise ValueError('fs must be a finite sampling rate in Hz above 0, not %r' % (fs,))
+    if not np.all(np.isfinite(f)) or np.any(f <= 0.0):
+        raise ValueError('freqs must hold finite frequencies above 0 Hz')
+    N = int(round((1.0 + math.sqrt(1.0 + 8.0 * len(xij))) / 2.0))
+    tau_max = float(np.abs(xij[:N - 1] @ g.T).max()) if N > 1 else 0.0
+    Ls = np.maximum(np.ceil(2.0 * float(fs) / f), math.ceil(2.0 * float(fs) * tau_max))
+    Ls = np.maximum(1, np.minimum(W, Ls)).astype(np.int32)
+    return Ls, np.maximum(1, Ls // 2).astype(np.int32)
+
+
+def check_capon(nchans, grid, freqs, snapshots, loading, W_list, maps=False, csdm=False):
+    """Everything ``nbls_set_capon`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (grid (G, 2)
+    float64, freqs float64 (nbands,), Ls int32, Hs int32, loading float).  ``snapshots``: (Ls, Hs), each one integer or one
+    per band; ``W_list``: the window length of every band in samples."""
+    g = check_slowness_grid(grid)
+    for name, v in (('maps', maps), ('csdm', csdm)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError('%s must be True or False, not %r' % (name, v))
+    W = np.atleast_1d(np.asarray(W_list)).astype(np.int64)
+    nb = len(W)
+    try:
+        f = np.atleast_1d(np.asarray(freqs))
+    except Exception:
+        raise ValueError('capon_freqs must be one frequency in Hz per band')
+    if f.dtype == object or f.dtype.kind not in 'iuf' or f.ndim != 1:
+        raise ValueError('capon_freqs must be one frequency in Hz per band, not %r' % (freqs,))
+    f = f.astype(np.float64)
+    if len(f) != nb:
+        raise ValueError('capon_freqs has %d entries for %d bands' % (len(f), nb))
+    if not np.all(np.isfinite(f)) or np.any(f <= 0.0):
+        raise ValueError('capon_freqs must hold finite frequencies above 0 Hz')
+    try:
+        ls, hs = snapshots
+        ls, hs = np.asarray(ls), np.asarray(hs)
+    except Exception:
+        raise ValueError('capon_snapshots must be (lengths, hops) in samples')
+    out = []
+    for name, v in (('length', ls), ('hop', hs)):
+        if v.dtype == object or v.dtype.kind not in 'iu' or v.ndim > 1:
+            raise ValueError('the snapshot %s must be an integer number of samples (or one per band), not %r' % (name, v))
+        v = np.atleast_1d(v).astype(np.int64)
+        if v.size == 1 and nb > 1:
+            v = np.repeat(v, nb)
+        if v.size != nb:
+            raise ValueError('the snapshot %s has %d entries for %d bands' % (name, v.size, nb))
+        if np.any(v < 1) or np.any(v > 2 ** 31 - 1):
+            raise ValueError('the snapshot %s must be at least 1 sample' % name)
+        out.append(v)
+    ls, hs = out
+    if np.any(ls > W):
+        raise ValueError('a snapshot of %d samples is longer than its window of %d' % (int(ls[np.argmax(ls > W)]), int(W[np.argmax(ls > W)])))
+    if not _real(loading) or not np.isfinite(float(loading)) or float(loading) < 0.0:
+        raise ValueError('the loading must be a finite number that is not negative, not %r' % (loading,))
+    if not (3 <= int(nchans) <= MAX_CAPON_ELEMENTS):
+        raise ValueError('%d array elements: the Capon spectra support 3 to %d' % (nchans, MAX_CAPON_ELEMENTS))
+    K = 1 + (W - ls) // hs
+    if float(loading) == 0.0 and np.any(K < nchans):
+        raise ValueError('loading 0 with %d snapshots of %d elements: the matrix is singular by construction' % (int(K.min()), nchans))
+    if nb * len(g) * int(nchans) * 16 > MAX_CAPON_STEER_BYTES:
+        raise ValueError('the steering table of %d bands x %d grid points x %d elements exceeds 1 GiB' % (nb, len(g), nchans))
+    return g, f, ls.astype(np.int32), hs.astype(np.int32), float(loading)

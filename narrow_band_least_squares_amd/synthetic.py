@@ -57,6 +57,27 @@ def plane_wave(rij, npts, fs, fmin, fmax, baz_deg=225.0, vel_kms=0.34, snr_db=6.
     return out
 
 
+def plane_waves(rij, npts, fs, fmin, fmax, sources, snr_db=6.0, seed=SEED + 1):
+    """(N, npts) traces of several plane waves at once: ``sources`` is a list of ``(baz_deg, vel_kms, amplitude)``, each an
+    independent band-limited Gaussian signal of unit variance times its amplitude, delayed across the array as
+    ``plane_wave`` delays its one; white noise of ``10 ** (-snr_db / 20)`` per element on top (the SNR of a source of
+    amplitude 1)."""
+    rng = np.random.default_rng(seed)
+    nchans = rij.shape[1]
+    freqs = np.fft.rfftfreq(npts, d=1.0 / fs)
+    out = np.zeros((nchans, npts))
+    for baz_deg, vel_kms, amp in sources:
+        baz = np.radians(baz_deg)
+        delays = (-np.array([np.sin(baz), np.cos(baz)]) @ rij) / vel_kms
+        spec = rng.standard_normal(len(freqs)) + 1j * rng.standard_normal(len(freqs))
+        spec[(freqs < fmin) | (freqs > fmax)] = 0.0
+        spec[0] = 0.0
+        spec = spec * (amp / np.fft.irfft(spec, n=npts).std())
+        for i in range(nchans):
+            out[i] += np.fft.irfft(spec * np.exp(-2j * np.pi * freqs * delays[i]), n=npts)
+    return out + 10.0 ** (-snr_db / 20.0) * rng.standard_normal((nchans, npts))
+
+
 def make_stream(data, fs, starttime=17884.0729166667, lat=None, lon=None):
     """(N, npts) array -> duck-typed Stream (start time as a matplotlib date number;
     default 2018-12-19T01:45:00 as in example.py:46)."""
