@@ -489,6 +489,51 @@ int nbls_fetch_capon_maps(nbls_handle* h, double* capon_map, double* bartlett_ma
 int nbls_fetch_capon_csdm(nbls_handle* h, double* R);
 int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* steer);
 
+/* The K strongest arrivals of either spectrum: a plan with Capon spectra may also carry a peak
+ * request, and its kernel then picks the local maxima of both maps where they are complete, instead of the caller
+ * fetching [rows][vector_len][G] doubles per map to do it on the host.
+ *   request  cell[G][2] (int32): the lattice coordinates of the G grid points, distinct, 0 <= c < 32768, G that of
+ *            nbls_set_capon when the plan is made; a count 1 <= K <= 8 (NBLS_CAPON_PEAKS_MAX); a relative floor in [0, 1].
+ *            The library builds the neighbour table once per request, [8][G] on the device: the neighbours of g are the
+ *            points at cell(g) + (di, dj) in the fixed order (-1,0), (+1,0), (0,-1), (0,+1), (-1,-1), (-1,+1), (+1,-1),
+ *            (+1,+1); an absent neighbour is -1.
+ * For one unit and one spectrum P, each of the two on its own:
+ *   order    better(p, g; q, n): P descending, g ascending (the order of capon_index).
+ *   peak     g is a peak iff P[g] is not NaN and better(P[g], g; P[n], n) holds for every neighbour n >= 0 with P[n] not
+ *            NaN.  A NaN or absent neighbour does not compete; of equal neighbours the one with the smaller index wins.
+ *            The spectrum's arg-max is always a peak.
+ *   kept     the arg-max is kept; another peak iff floor == 0 or P[g] >= floor * P[argmax] (one double multiplication).
+ *            count is the number of kept peaks; it is not capped at K.
+ *   ranks    ranks k < min(count, K) hold the kept peaks in that order: index[k], power[k] = P[index[k]].  Rank 0 equals
+ *            capon_index / capon_power (bartlett_*) bit for bit.  Further ranks: index -1, power NaN, offset NaN.
+ *   offset   offset[k][axis] in lattice steps, positive towards the +1 neighbour: with m and p the -1 and +1 neighbours of
+ *            index[k] on that axis, 0.5 (P[m] - P[p]) / ((P[m] - 2 P[g]) + P[p]); 0 unless all three values are finite,
+ *            the denominator is < 0 and the quotient is finite; clamped to +-0.5, -0.0 becomes 0.0; 0 where m or p is
+ *            absent.  It is the rule of the lag refinement (nbls_set_lag_refinement).
+ *   degenerate  every Capon and Bartlett result NaN / -1: count 0, nothing kept.  A Cholesky pivot not > 0: the Capon peaks
+ *            are empty, the Bartlett peaks stay.
+ * No atomics, every order total, nothing depends on the launch's unit range: single, streamed, batched and window-sliced
+ * passes, and both routes below, give the same bits.
+ *   nbls_set_capon_peaks(h, cell, G, K, floor)   copied and read by the next nbls_plan; cell NULL or K = 0 switches it off
+ *                            (the default: such a plan launches exactly what it launched before).  NBLS_ERR_ARG, the handle
+ *                            unchanged, for K outside 1..8, G outside 1..65536, a floor outside [0, 1] or NaN, a coordinate
+ *                            out of range, two equal cells.  nbls_plan returns NBLS_ERR_ARG for a peak request without Capon
+ *                            spectra or with another G.
+ *   nbls_fetch_capon_peaks(h, which, count, index, power, offset)   which: 0 Capon, 1 Bartlett.  count [rows][vector_len],
+ *                            index and power [rows][vector_len][K], offset [rows][vector_len][K][2]; any may be NULL.  Rows,
+ *                            waiting, NBLS_ERR_STATE and the zeros beyond nwin[r] as for nbls_fetch_capon.
+ * The unit's two maps wait for the pick either in LDS behind the kernel's own (the LDS route; [2][G] doubles must fit a
+ * workgroup's 160 KiB) or in HBM (the HBM route): in the unit's rows of the maps if the plan keeps them (NBLS_CAPON_MAPS), else
+ * in one of S slabs of a scratch buffer the handle owns, the units issued in launches of at most S.  Both routes run the same
+ * code on the same values.  nbls_set_option keys, read by the next plan:
+ *   "capon_peak_route" 0 automatic (LDS where the maps fit without lowering the workgroups per CU, else HBM), 1 LDS
+ *                      (NBLS_ERR_UNSUPPORTED from nbls_plan where it does not fit), 2 HBM;
+ *   "capon_peak_slabs" S = 1..4096; 0, the default: as many as 256 MiB hold, at least 256 (256 MiB at G = 65536), at most 4096. */
+#define NBLS_CAPON_PEAKS_MAX 8
+int nbls_set_capon_peaks(nbls_handle* h, const int32_t* cell, int32_t G, int32_t K, double floor);
+int nbls_fetch_capon_peaks(nbls_handle* h, int32_t which /* 0 Capon, 1 Bartlett */,
+                           int32_t* count, int32_t* index, double* power, double* offset);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

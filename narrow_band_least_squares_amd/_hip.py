@@ -31,6 +31,7 @@ EXPORTS = [
     'nbls_beam_grid_lds_bytes',
     'nbls_set_closure', 'nbls_fetch_closure', 'nbls_est_fetch_closure',
     'nbls_set_capon', 'nbls_fetch_capon', 'nbls_fetch_capon_maps', 'nbls_fetch_capon_csdm', 'nbls_fetch_capon_tables',
+    'nbls_set_capon_peaks', 'nbls_fetch_capon_peaks',
 ]
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
@@ -39,6 +40,7 @@ CAPON_MAX_ELEMENTS = 32  # array elements of a plan with Capon spectra (NBLS_CAP
 CAPON_THREADS = 128      # threads of a workgroup of the Capon kernel, one grid point each (NBLS_CAPON_THREADS)
 CAPON_CHUNK = 32         # snapshots that go through LDS together (NBLS_CAPON_CHUNK)
 CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
+CAPON_PEAKS_MAX = 8      # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -178,6 +180,8 @@ def load_library(path=None):
     lib.nbls_fetch_capon_maps.argtypes = [vp, dp, dp]
     lib.nbls_fetch_capon_csdm.argtypes = [vp, dp]
     lib.nbls_fetch_capon_tables.argtypes = [vp, C.c_int32, dp, dp]
+    lib.nbls_set_capon_peaks.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_double]
+    lib.nbls_fetch_capon_peaks.argtypes = [vp, C.c_int32, ip, ip, dp, dp]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -283,6 +287,7 @@ class Handle:
         self.est_npairs = []            # pair counts of the further estimators (set_estimators)
         self._want_grid_n = self.grid_n = 0   # grid points of set_beam_grid / of the plan
         self._want_capon = self.capon = None  # (G, snapshot lengths) of set_capon / of the plan
+        self._want_capon_peaks = self.capon_peaks = 0     # K of set_capon_peaks / of the plan
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -304,7 +309,9 @@ class Handle:
             if rc == NBLS_ERR_GEOMETRY:
                 raise RuntimeError(msg)
             if rc in (NBLS_ERR_ARG, NBLS_ERR_UNSUPPORTED):
-                raise ValueError(msg)
+                err = ValueError(msg)
+                err.code = rc                # (which of the two it was)
+                raise err
             raise NblsError(rc, msg)
 
     def set_trace(self, data, fs):
@@ -407,6 +414,7 @@ class Handle:
         self._nsec = nsec
         self.grid_n = self._want_grid_n
         self.capon = self._want_capon
+        self.capon_peaks = self._want_capon_peaks
 
     def set_option(self, key, value):
         """Per-handle implementation switch (``nbls_set_option``; identical results unless the library is the
@@ -593,6 +601,31 @@ class Handle:
         out = np.empty((2, self.nbands, self.vector_len))
         self._chk(self.lib.nbls_fetch_capon(self._h, _iptr(idx[0]), _dptr(out[0]), _iptr(idx[1]), _dptr(out[1])))
         return idx[0], out[0], idx[1], out[1]
+
+    def set_capon_peaks(self, cells=None, K=0, floor=0.25):
+        """The next plans (with ``set_capon``) also pick, per window and spectrum, the ``K`` strongest local maxima on the
+        lattice ``cells`` (G, 2) int32 that are no lower than ``floor`` times the maximum (``nbls_set_capon_peaks``, DESIGN.md
+        section 19).  ``cells=None`` or ``K=0`` switches it off again."""
+        if cells is None or not K:
+            self._chk(self.lib.nbls_set_capon_peaks(self._h, None, 0, 0, 0.0))
+            self._want_capon_peaks = 0
+            return
+        c = np.ascontiguousarray(cells, dtype=np.int32)
+        if c.ndim != 2 or c.shape[1] != 2 or c.shape[0] < 1:
+            raise ValueError('the cells must be (G, 2) with G >= 1, not %r' % (c.shape,))
+        self._chk(self.lib.nbls_set_capon_peaks(self._h, _iptr(c), c.shape[0], int(K), float(floor)))
+        self._want_capon_peaks = int(K)
+
+    def fetch_capon_peaks(self, which):
+        """The peaks of the Capon (``which`` 0) or Bartlett (1) spectrum -> (count int32 (rows, vector_len), index int32
+        (rows, vector_len, K), power (rows, vector_len, K), offset (rows, vector_len, K, 2))."""
+        K = max(self.capon_peaks, 1)
+        cnt = np.empty((self.nbands, self.vector_len), dtype=np.int32)
+        idx = np.empty((self.nbands, self.vector_len, K), dtype=np.int32)
+        pw = np.empty((self.nbands, self.vector_len, K))
+        off = np.empty((self.nbands, self.vector_len, K, 2))
+        self._chk(self.lib.nbls_fetch_capon_peaks(self._h, int(which), _iptr(cnt), _iptr(idx), _dptr(pw), _dptr(off)))
+        return cnt, idx, pw, off
 
     def fetch_capon_maps(self):
         """-> (capon_map, bartlett_map), each (rows, vector_len, G) (a plan made with ``want_maps``)."""

@@ -422,7 +422,7 @@ void nbls_destroy(nbls_handle* h) {
     for (hipEvent_t e : h->pev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->rev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->uev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_uprev, h->ev_xd, h->ev_plan, h->ev_up})
+    for (hipEvent_t e : {h->ev_uprev, h->ev_xd, h->ev_plan, h->ev_up, h->ev_capon_slab})
         if (e) (void)hipEventDestroy(e);
     if (h->cstream) (void)hipStreamDestroy(h->cstream);
     if (h->ustream) (void)hipStreamDestroy(h->ustream);
@@ -815,6 +815,21 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if ((size_t)a.nbands * (c.grid.size() / 2) * (size_t)En * 16 > ((size_t)1 << 30))
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the Capon steering table (nbands * G * N * 16 bytes) exceeds 1 GiB");
     }
+    int peak_route = 0;              // the peaks of the spectra (nbls_set_capon_peaks): Capon spectra of the same G, and a route
+    if (!h->want_capon_peaks.nbr.empty()) {
+        const size_t G = h->want_capon.grid.size() / 2;
+        if (!G)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: a peak request (nbls_set_capon_peaks) needs Capon spectra (nbls_set_capon)");
+        if (h->want_capon_peaks.nbr.size() != 8 * G)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: the peak request (nbls_set_capon_peaks) has " + std::to_string(h->want_capon_peaks.nbr.size() / 8) +
+                                             " cells for Capon spectra of " + std::to_string(G) + " points");
+        // the unit's two maps wait in LDS or in HBM (capon.hip: nbls_capon_peak_route_of has the automatic choice)
+        const bool fits = nbls_capon_peak_lds_bytes_of(h->nchans / NS, (int)G) != 0;
+        peak_route = h->opt.capon_peak_route ? h->opt.capon_peak_route : nbls_capon_peak_route_of(h->nchans / NS, (int)G);
+        if (peak_route == 1 && !fits)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: option capon_peak_route 1: the two maps of " + std::to_string(G) + " points do not fit the LDS of a workgroup beside the kernel's " +
+                                                     std::to_string(nbls_capon_lds_bytes_of(h->nchans / NS)) + " bytes");
+    }
     if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
         if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
@@ -854,6 +869,16 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->capon_maps = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_MAPS);
     h->capon_csdm = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_CSDM);
     h->capon_valid = false;
+    h->capon_peaks = peak_route ? h->want_capon_peaks.k : 0;
+    h->capon_peak_floor = h->want_capon_peaks.floor;
+    h->capon_peak_route = peak_route;
+    // the slabs of the HBM route: what the option says, else as many as 256 MiB hold, 256 at least (which is 256 MiB at the
+    // largest grid) and 4096 at most: a launch of 256 workgroups is one per CU
+    h->capon_peak_slabs = h->opt.capon_peak_slabs;
+    if (peak_route && h->capon_peak_slabs < 1) {
+        const size_t fit = ((size_t)256 << 20) / (2 * (h->want_capon.grid.size() / 2) * sizeof(double));
+        h->capon_peak_slabs = (int)std::min<size_t>(4096, std::max<size_t>(256, fit));
+    }
     h->nelem = h->nchans / NS;
     const int E = h->nelem;
     nbls_estimator& x0 = h->est[0];
@@ -1160,6 +1185,18 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_capon_power, 2 * cells * sizeof(double)))) return rc;
         if (h->capon_maps && (rc = ensure(h, h->d_capon_map, 2 * cells * (size_t)G * sizeof(double)))) return rc;
         if (h->capon_csdm && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        if (h->capon_peaks > 0) {    // the peak request: its neighbour table, the four results and, on the HBM route of a plan without the maps, the slabs
+            const size_t K = (size_t)h->capon_peaks;
+            if ((rc = alloc_copy(h, h->d_capon_nbr, h->want_capon_peaks.nbr.data(), h->want_capon_peaks.nbr.size()))) return rc;
+            if ((rc = ensure(h, h->d_capon_peak_count, 2 * cells * sizeof(int32_t)))) return rc;
+            if ((rc = ensure(h, h->d_capon_peak_index, 2 * cells * K * sizeof(int32_t)))) return rc;
+            if ((rc = ensure(h, h->d_capon_peak_power, 2 * cells * K * sizeof(double)))) return rc;
+            if ((rc = ensure(h, h->d_capon_peak_offset, 2 * cells * K * 2 * sizeof(double)))) return rc;
+            if (h->capon_peak_route == 2 && !h->capon_maps) {
+                const size_t slabs = std::min<size_t>((size_t)h->capon_peak_slabs, std::max<size_t>((size_t)h->nunits, 1));
+                if ((rc = ensure(h, h->d_capon_peak_slab, slabs * 2 * (size_t)G * sizeof(double)))) return rc;
+            }
+        }
     }
     return 0;
 }
@@ -1673,6 +1710,44 @@ int nbls_fetch_capon(nbls_handle* h, int32_t* capon_index, double* capon_power, 
     return capon_fetch_plane(h, bartlett_power, h->d_capon_power.p + cells, sizeof(double));
 }
 
+int nbls_set_capon_peaks(nbls_handle* h, const int32_t* cell, int32_t G, int32_t K, double floor) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!cell || K == 0) { h->want_capon_peaks = nbls_handle::capon_peak_request(); return NBLS_OK; }   // off: the next plan picks no peaks
+    if (K < 1 || K > NBLS_CAPON_PEAKS_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: K must be 1.." + std::to_string(NBLS_CAPON_PEAKS_MAX));
+    if (G < 1 || G > NBLS_CAPON_GRID_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: G must be 1.." + std::to_string(NBLS_CAPON_GRID_MAX));
+    if (!(floor >= 0.0 && floor <= 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: the floor must lie in [0, 1]");
+    std::vector<int32_t> key((size_t)G);                         // everything is checked before the handle changes
+    for (int g = 0; g < G; ++g) {
+        const int32_t i = cell[2 * g], j = cell[2 * g + 1];
+        if (i < 0 || i >= 32768 || j < 0 || j >= 32768)
+            return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: the lattice coordinates of point " + std::to_string(g) + " are not in 0..32767");
+        key[g] = i * 32768 + j;
+    }
+    std::sort(key.begin(), key.end());
+    if (std::adjacent_find(key.begin(), key.end()) != key.end())
+        return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: two points share one lattice cell");
+    nbls_handle::capon_peak_request& r = h->want_capon_peaks;    // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    r.nbr.resize((size_t)8 * G);
+    nbls_capon_neighbours_of(cell, G, r.nbr.data());
+    r.k = K;
+    r.floor = floor;
+    return NBLS_OK;
+}
+
+int nbls_fetch_capon_peaks(nbls_handle* h, int32_t which, int32_t* count, int32_t* index, double* power, double* offset) {
+    if (!h) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_peaks"))) return rc;
+    if (which < 0 || which > 1) return fail(h, NBLS_ERR_ARG, "nbls_fetch_capon_peaks: which is 0 (Capon) or 1 (Bartlett)");
+    if (h->capon_peaks < 1 || !h->d_capon_peak_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_peaks: the plan did not ask for the peaks (nbls_set_capon_peaks before nbls_plan)");
+    if ((rc = finish_pass(h))) return rc;
+    const size_t cells = (size_t)h->nbands * h->vector_len, K = (size_t)h->capon_peaks, w = (size_t)which;
+    if ((rc = capon_fetch_plane(h, count, h->d_capon_peak_count.p + w * cells, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, index, h->d_capon_peak_index.p + w * cells * K, K * sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, power, h->d_capon_peak_power.p + w * cells * K, K * sizeof(double)))) return rc;
+    return capon_fetch_plane(h, offset, h->d_capon_peak_offset.p + w * cells * K * 2, K * 2 * sizeof(double));
+}
+
 int nbls_fetch_capon_maps(nbls_handle* h, double* capon_map, double* bartlett_map) {
     if (!h) return NBLS_ERR_ARG;
     int rc;
@@ -1898,6 +1973,8 @@ int nbls_set_option(nbls_handle* h, const char* key, int64_t value) {
         {"filter_row_step", &nbls_options::filter_row_step, false},
         {"filter_nofuse", &nbls_options::filter_nofuse, false},
         {"filter_nomfma", &nbls_options::filter_nomfma, false},
+        {"capon_peak_route", &nbls_options::capon_peak_route, false},
+        {"capon_peak_slabs", &nbls_options::capon_peak_slabs, false},
         {"ablate", &nbls_options::ablate, true},
         {"screen_stamps", &nbls_options::screen_stamps, true},
         {"screen_seed", &nbls_options::screen_seed, true},
@@ -1935,6 +2012,10 @@ int nbls_set_option(nbls_handle* h, const char* key, int64_t value) {
 #ifndef NBLS_DEVELOPER
         if (k.developer) return fail(h, NBLS_ERR_UNSUPPORTED, std::string("option '") + key + "' exists only in the developer build (make dev)");
 #endif
+        if (k.field == &nbls_options::capon_peak_route && (value < 0 || value > 2))
+            return fail(h, NBLS_ERR_ARG, "option 'capon_peak_route' is 0 (automatic), 1 (LDS) or 2 (HBM)");
+        if (k.field == &nbls_options::capon_peak_slabs && (value < 0 || value > 4096))
+            return fail(h, NBLS_ERR_ARG, "option 'capon_peak_slabs' is 1..4096 (0: the default)");
         h->opt.*(k.field) = (int)value;
         h->planned = false;                 // options are read by nbls_plan and by the launchers of the next pass
         return NBLS_OK;

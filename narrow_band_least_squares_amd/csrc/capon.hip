@@ -35,9 +35,23 @@
 //              6.3 KiB at N = 3, 18 KiB at 8, 96 KiB at 32
 // The order of every sum depends on (N, W, Ls, Hs, G) alone, the arg-max is a total order, there are no atomics and nothing
 // depends on the launch's unit range: single, streamed, batched and window-sliced passes give the same bits.
+//
+// A plan with a peak request (nbls_set_capon_peaks; the definition is in include/nbls.h) runs an instance of
+// the kernel that also keeps both spectra of the unit and picks the K strongest kept peaks of either behind the arg-max
+// (capon_peaks_of); the instance without is the code as it was.  Where the two maps [2][G] wait:
+//   LDS route  behind the kernel's own dynamic LDS
+//   HBM route  in the unit's rows of the maps where the plan keeps them, else in the workgroup's slab of a scratch buffer; the
+//              units go in launches of at most as many workgroups as there are slabs; the stream's order hands them on,
+//              and an event where a pass solves on two streams
+// Both instances run the same function on the same values (the pointer's address space is the compiler's business) and
+// give the same bits; nbls_capon_peak_route_of chooses.
 #include "nbls_internal.h"
 #include "wave_ops.h"
+#include "refine_fraction.h"
+#include <algorithm>
 #include <cmath>
+#include <utility>
+#include <vector>
 
 namespace {
 
@@ -66,7 +80,22 @@ struct CArgs {
     double* map;              // [2][B][VL][G] or NULL
     double* csdm;             // [B][VL][N][N][2] or NULL
     int64_t cells;
+    // ---- the peak request (nbls_set_capon_peaks): read by the instances with peaks alone ----
+    const int32_t* nbr;       // [8][G] neighbour table, -1: absent
+    int pk;                   // K
+    double pfloor;
+    double* slab;             // HBM route without the maps: [launch's workgroups][2][G]
+    int32_t* pk_count;        // [2][B][VL]
+    int32_t* pk_index;        // [2][B][VL][K]
+    double* pk_power;         // [2][B][VL][K]
+    double* pk_offset;        // [2][B][VL][K][2]
 };
+
+// doubles of the kernel's dynamic LDS without the peak maps (nbls_capon_lds_bytes_of)
+__host__ __device__ inline size_t nbls_capon_lds_doubles(int nelem) {
+    const size_t n = (size_t)nelem, xy = (size_t)(CCH > CT ? CCH : CT) * n * 2;
+    return 2 * n * n * 2 + ((n + 1) & ~(size_t)1) + xy;
+}
 
 // "P descending, g ascending"; a NaN is no candidate, g < 0 is "none yet".
 __device__ inline bool capon_better(double p, int g, double bp, int bg) {
@@ -90,6 +119,110 @@ __device__ inline void capon_best(double& p, int& g, double* sp, int* sg, int ti
     __syncthreads();
 }
 
+// ---- the K strongest peaks of one spectrum of the unit (nbls_set_capon_peaks) ----
+constexpr int PKM = NBLS_CAPON_PEAKS_MAX;
+
+// A unit without spectra: count 0, every rank empty, both spectra.
+__device__ inline void capon_peaks_none(const CArgs& a, int64_t cell, int tid) {
+    const double nan_ = __builtin_nan("");
+    for (int which = 0; which < 2; ++which) {
+        const int64_t c = which * a.cells + cell;
+        if (tid == 0) a.pk_count[c] = 0;
+        if (tid < a.pk) {
+            const int64_t o = c * a.pk + tid;
+            a.pk_index[o] = -1; a.pk_power[o] = nan_;
+            a.pk_offset[2 * o] = nan_; a.pk_offset[2 * o + 1] = nan_;
+        }
+    }
+}
+
+// P [G]: the unit's spectrum, complete and visible to the workgroup (LDS or the unit's slab: the caller's pointer decides,
+// the code is one).  (bp, bg): the spectrum's arg-max as thread 0 holds it behind capon_best.
+//   1. every thread tests the points tid, tid + CT, ... against their neighbours and keeps its own K best kept peaks in
+//      registers: an unrolled compare-and-swap chain, every index a constant
+//   2. K rounds of capon_best over the threads' heads; the owner of a round's winner pops its head
+//   3. threads k < K write rank k with its two offsets
+__device__ inline void capon_peaks_of(const CArgs& a, const double* P, int which, int64_t cell, double bp, int bg,
+                                      double* sp, int* sg, int tid) {
+    __shared__ double win_p[PKM + 1];         // [k]: the winner of round k; [PKM]: the arg-max, for every thread
+    __shared__ int win_g[PKM + 1];
+    __shared__ int cnt_w[CW];
+    const int G = a.G, K = a.pk;
+    const double nan_ = __builtin_nan("");
+    if (tid == 0) { win_p[PKM] = bp; win_g[PKM] = bg; }
+    __syncthreads();
+    const double pmax = win_p[PKM];
+    const int gmax = win_g[PKM];
+    const double thr = a.pfloor * pmax;
+    double tp[PKM];
+    int tg[PKM];
+#pragma unroll
+    for (int k = 0; k < PKM; ++k) { tp[k] = 0.0; tg[k] = -1; }
+    int cnt = 0;
+    for (int g = tid; g < G; g += CT) {
+        const double p = P[g];
+        bool peak = p == p;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            const int n = a.nbr[(int64_t)d * G + g];
+            if (n < 0) continue;
+            const double q = P[n];
+            if (q == q && !(p > q || (p == q && g < n))) peak = false;       // capon_better(p, g; q, n) of two candidates
+        }
+        if (!peak) continue;
+        if (!(g == gmax || a.pfloor == 0.0 || p >= thr)) continue;
+        ++cnt;
+        double cp = p;
+        int cg = g;
+#pragma unroll
+        for (int k = 0; k < PKM; ++k)
+            if (k < K && capon_better(cp, cg, tp[k], tg[k])) {
+                const double op = tp[k]; const int og = tg[k];
+                tp[k] = cp; tg[k] = cg;
+                cp = op; cg = og;
+            }
+    }
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if ((tid & 63) == 0) cnt_w[tid >> 6] = cnt;
+    for (int k = 0; k < K; ++k) {                                    // (K is the same for every thread)
+        double p = tp[0];
+        int g = tg[0];
+        capon_best(p, g, sp, sg, tid);
+        if (tid == 0) { win_p[k] = p; win_g[k] = g; }
+        __syncthreads();
+        const int wg = win_g[k];
+        if (wg >= 0 && tg[0] == wg) {                                // the owner pops its head
+#pragma unroll
+            for (int j = 0; j + 1 < PKM; ++j) { tp[j] = tp[j + 1]; tg[j] = tg[j + 1]; }
+            tg[PKM - 1] = -1;
+        }
+    }
+    const int64_t c = which * a.cells + cell;
+    if (tid == 0) {
+        int total = 0;
+        for (int j = 0; j < CW; ++j) total += cnt_w[j];
+        a.pk_count[c] = total;
+    }
+    if (tid < K) {
+        const int64_t o = c * K + tid;
+        const int g = win_g[tid];
+        if (g < 0) {
+            a.pk_index[o] = -1; a.pk_power[o] = nan_;
+            a.pk_offset[2 * o] = nan_; a.pk_offset[2 * o + 1] = nan_;
+        } else {
+            const double p0 = win_p[tid];
+            a.pk_index[o] = g; a.pk_power[o] = p0;
+            for (int ax = 0; ax < 2; ++ax) {
+                const int m = a.nbr[(int64_t)(2 * ax) * G + g], q = a.nbr[(int64_t)(2 * ax + 1) * G + g];
+                a.pk_offset[2 * o + ax] = (m < 0 || q < 0) ? 0.0 : refine_fraction(P[m], p0, P[q]);
+            }
+        }
+    }
+    __syncthreads();                                                 // (win_*, cnt_w and sp / sg are free again)
+}
+
+// PK: 0 no peaks (the kernel as it was), 1 the unit's two maps in LDS behind Y, 2 in the unit's slab of HBM
+template <int PK>
 __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
     // dynamic LDS, sized by N (capon_lds_bytes): Rm [N][N] complex, Lm [N][N] complex, invd [N], then X [CHUNK][N] complex
     // and, in its place once R is there, Y [N][2][THREADS]: the grid phase's vector of every lane
@@ -187,6 +320,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
             a.index[cell] = -1; a.index[a.cells + cell] = -1;
             a.power[cell] = nan_; a.power[a.cells + cell] = nan_;
         }
+        if (PK) capon_peaks_none(a, cell, tid);
         return;
     }
     // R' = R + delta (t / N) I, then its Cholesky factor column by column
@@ -231,6 +365,16 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
     const double nn = (double)N * (double)N;
     double bc = 0.0, bb = 0.0;
     int gc = -1, gb = -1;
+    // with peaks: where the unit's two spectra stay until they are picked
+    double* mc = nullptr;
+    double* mb = nullptr;
+    if (PK == 1) {
+        mc = capon_lds + nbls_capon_lds_doubles(N);
+        mb = mc + G;
+    } else if (PK == 2) {
+        mc = a.map ? a.map + cell * G : a.slab + (int64_t)blockIdx.x * 2 * G;
+        mb = a.map ? a.map + (a.cells + cell) * G : mc + G;
+    }
     for (int g = tid; g < G; g += CT) {
         for (int i = 0; i < N; ++i) {
             const double2 v = steer[(int64_t)i * G + g];
@@ -276,6 +420,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
             pc = 1.0 / q;
         }
         if (a.map) { a.map[cell * G + g] = pc; a.map[(a.cells + cell) * G + g] = pb; }
+        if (PK == 1 || (PK == 2 && !a.map)) { mc[g] = pc; mb[g] = pb; }
         if (capon_better(pc, g, bc, gc)) { bc = pc; gc = g; }
         if (capon_better(pb, g, bb, gb)) { bb = pb; gb = g; }
     }
@@ -286,14 +431,61 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
         a.power[cell] = gc < 0 ? nan_ : bc;
         a.power[a.cells + cell] = gb < 0 ? nan_ : bb;
     }
+    if (PK) {
+        // the maps are this workgroup's own writes: a fence and a barrier make them its reads (capon_best has given the
+        // barrier already; the fence is for the slab)
+        if (PK == 2) __threadfence_block();
+        __syncthreads();
+        capon_peaks_of(a, mc, 0, cell, gc < 0 ? nan_ : bc, gc, red_p, red_g, tid);
+        capon_peaks_of(a, mb, 1, cell, gb < 0 ? nan_ : bb, gb, red_p, red_g, tid);
+    }
 }
 
 }  // namespace
 
 // dynamic LDS bytes of capon_kernel for an array of nelem elements (see the kernel's head)
 size_t nbls_capon_lds_bytes_of(int nelem) {
-    const size_t n = (size_t)nelem, xy = (size_t)(CCH > CT ? CCH : CT) * n * 2;
-    return (2 * n * n * 2 + ((n + 1) & ~(size_t)1) + xy) * sizeof(double);
+    return nbls_capon_lds_doubles(nelem) * sizeof(double);
+}
+
+// ... and of the instance that keeps the unit's two maps of G points in LDS behind it (0: more than a workgroup's 160 KiB,
+// less the kernel's static arrays)
+size_t nbls_capon_peak_lds_bytes_of(int nelem, int G) {
+    const size_t b = nbls_capon_lds_bytes_of(nelem) + (size_t)2 * (size_t)G * sizeof(double);
+    return b + 1024 <= (size_t)160 * 1024 ? b : 0;
+}
+
+// The automatic route of a plan with a peak request: 1 (LDS) or 2 (HBM).  A workgroup is two waves of 96 VGPRs, so a CU
+// holds 10 of them at most, and fewer where the dynamic LDS says so (8 at N = 8).  The maps in LDS take that down further
+// (4 at N = 8, G = 1257), and at cfg-3 that costs more than the slab's trip through the vector cache and L2: the peaks add
+// 6.5 ms to the pass on the LDS route and 3.2 ms on the HBM route.  So the LDS route is taken only
+// where the maps fit without lowering the workgroups per CU (large arrays, whose own LDS leaves one or two per CU anyway).
+int nbls_capon_peak_route_of(int nelem, int G) {
+    const size_t with = nbls_capon_peak_lds_bytes_of(nelem, G);
+    if (!with) return 2;
+    const size_t cu = (size_t)160 * 1024, fixed = 1024, most = 10;
+    const size_t before = std::min(most, cu / (nbls_capon_lds_bytes_of(nelem) + fixed));
+    const size_t after = std::min(most, cu / (with + fixed));
+    return after == before ? 1 : 2;
+}
+
+// The neighbour table [8][G] of the lattice cells cell [G][2] (distinct, 0 <= c < 32768), in the order (-1,0), (+1,0),
+// (0,-1), (0,+1), (-1,-1), (-1,+1), (+1,-1), (+1,+1); -1 where there is no such point.
+void nbls_capon_neighbours_of(const int32_t* cell, int G, int32_t* nbr) {
+    static const int di[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dj[8] = {0, 0, -1, 1, -1, 1, -1, 1};
+    std::vector<std::pair<int32_t, int32_t>> key((size_t)G);       // (i * 32768 + j, g), sorted
+    for (int g = 0; g < G; ++g) key[g] = {cell[2 * g] * 32768 + cell[2 * g + 1], g};
+    std::sort(key.begin(), key.end());
+    for (int g = 0; g < G; ++g)
+        for (int d = 0; d < 8; ++d) {
+            const int i = cell[2 * g] + di[d], j = cell[2 * g + 1] + dj[d];
+            int32_t n = -1;
+            if (i >= 0 && i < 32768 && j >= 0 && j < 32768) {
+                const auto it = std::lower_bound(key.begin(), key.end(), std::make_pair((int32_t)(i * 32768 + j), (int32_t)-1));
+                if (it != key.end() && it->first == i * 32768 + j) n = it->second;
+            }
+            nbr[(size_t)d * G + g] = n;
+        }
 }
 
 // The plan's tables on the host, float64, un-fused (see the head of this file).  coef [nbands][maxLs][2] (zeros beyond
@@ -344,12 +536,64 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
     a.map = h->capon_maps ? h->d_capon_map.p : nullptr;
     a.csdm = h->capon_csdm ? h->d_capon_csdm.p : nullptr;
     const size_t lds = nbls_capon_lds_bytes_of(h->nelem);
+    if (h->capon_peaks > 0) {              // a plan with a peak request (nbls_set_capon_peaks)
+        a.nbr = h->d_capon_nbr; a.pk = h->capon_peaks; a.pfloor = h->capon_peak_floor;
+        a.pk_count = h->d_capon_peak_count; a.pk_index = h->d_capon_peak_index;
+        a.pk_power = h->d_capon_peak_power; a.pk_offset = h->d_capon_peak_offset;
+        if (h->capon_peak_route == 1) {
+            const size_t plds = nbls_capon_peak_lds_bytes_of(h->nelem, h->capon_n);
+            if (!plds) return hipErrorInvalidValue;                      // (nbls_plan has refused such a plan)
+            if (!h->capon_peak_attr_set[0]) {
+                const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                         160 * 1024 - 1024);
+                if (e != hipSuccess) return e;
+                h->capon_peak_attr_set[0] = true;
+            }
+            hipLaunchKernelGGL(capon_kernel<1>, dim3((unsigned)nu), dim3(CT), plds, st, a);
+            return hipGetLastError();
+        }
+        if (!h->capon_peak_attr_set[1]) {
+            const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)nbls_capon_lds_bytes_of(CMAXN));
+            if (e != hipSuccess) return e;
+            h->capon_peak_attr_set[1] = true;
+        }
+        // the maps of a unit lie in its own rows of d_capon_map where the plan keeps them; else in the slab of its
+        // workgroup: at most capon_peak_slabs workgroups per launch.  On one stream its order hands the slabs on; the
+        // solves of a pass may be on two (solve_on_stream2), so a launch on the other stream than the last one waits
+        // for that one's event first
+        a.slab = a.map ? nullptr : h->d_capon_peak_slab.p;
+        if (a.slab) {
+            if (!h->ev_capon_slab) {
+                const hipError_t e = hipEventCreateWithFlags(&h->ev_capon_slab, hipEventDisableTiming);
+                if (e != hipSuccess) { h->ev_capon_slab = nullptr; return e; }
+            }
+            if (h->capon_slab_stream && h->capon_slab_stream != st) {
+                const hipError_t e = hipStreamWaitEvent(st, h->ev_capon_slab, 0);
+                if (e != hipSuccess) return e;
+            }
+        }
+        const int64_t step = a.map ? nu : h->capon_peak_slabs;
+        for (int64_t o = 0; o < nu; o += step) {
+            a.u0 = (int)(u0 + o);
+            a.nunits = (int)(nu - o < step ? nu - o : step);
+            hipLaunchKernelGGL(capon_kernel<2>, dim3((unsigned)a.nunits), dim3(CT), lds, st, a);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        if (a.slab) {
+            const hipError_t e = hipEventRecord(h->ev_capon_slab, st);
+            if (e != hipSuccess) return e;
+            h->capon_slab_stream = st;
+        }
+        return hipSuccess;
+    }
     if (!h->capon_attr_set) {              // once per handle (a streamed pass launches per unit batch)
-        const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)nbls_capon_lds_bytes_of(CMAXN));
         if (e != hipSuccess) return e;
         h->capon_attr_set = true;
     }
-    hipLaunchKernelGGL(capon_kernel, dim3((unsigned)nu), dim3(CT), lds, st, a);
+    hipLaunchKernelGGL(capon_kernel<0>, dim3((unsigned)nu), dim3(CT), lds, st, a);
     return hipGetLastError();
 }

@@ -46,6 +46,8 @@ struct nbls_options {
     int overlap = 0;           // solve of batch k on a second stream while batch k+1 is correlated: 1 on, -1 off, 0 auto (streamed passes of several small batches)
     int filter_nofuse = 0;     // 1: separate state kernel for the backward filter pass
     int filter_nomfma = 0;     // 1: VALU state kernel
+    int capon_peak_route = 0;  // where a unit's maps wait for the peak pick (nbls_set_capon_peaks): 0 auto, 1 LDS, 2 HBM
+    int capon_peak_slabs = 0;  // HBM route: workgroups per launch, 1..4096 (0: what 256 MiB hold, 256 .. 4096)
     // ---- developer build only ----
     int ablate = 0;            // skip parts of the screening / verify kernels (timing; results wrong)
     int screen_stamps = 0;     // s_memtime phase stamps of the screening kernel
@@ -190,6 +192,29 @@ struct nbls_handle {
     dev_buf<double> d_capon_power;  // [2][B][VL]: capon_power | bartlett_power
     dev_buf<double> d_capon_map;    // [2][B][VL][G] (a plan that asked for the maps)
     dev_buf<double> d_capon_csdm;   // [B][VL][N][N][2] (a plan that asked for R)
+    // ---- the K strongest peaks of either spectrum (nbls_set_capon_peaks, capon.hip) ----
+    struct capon_peak_request {
+        std::vector<int32_t> nbr;       // [8][G] neighbour table of the request's cells (empty: off)
+        int k = 0;
+        double floor = 0.0;
+    };
+    capon_peak_request want_capon_peaks;    // nbls_set_capon_peaks: read by the next nbls_plan
+    int capon_peaks = 0;            // K of the plan (0: the plan picks no peaks)
+    double capon_peak_floor = 0.0;
+    int capon_peak_route = 0;       // the plan's route: 1 the unit's maps in LDS, 2 in HBM (its rows of d_capon_map, or a slab)
+    int capon_peak_slabs = 0;       // HBM route: slabs of d_capon_peak_slab = workgroups per launch
+    bool capon_peak_attr_set[2] = {false, false};   // the two instances with peaks have their dynamic LDS limit
+    dev_buf<int32_t> d_capon_nbr;           // [8][G]
+    dev_buf<double> d_capon_peak_slab;      // [slabs][2][G] (HBM route of a plan without the maps)
+    // the slabs belong to one launch at a time.  A pass may solve on two streams (solve_on_stream2: the screened window
+    // groups on stream2, a group on a general correlator on stream), so the last launch that used them records this event,
+    // and a launch on the other stream waits for it
+    hipEvent_t ev_capon_slab = nullptr;
+    hipStream_t capon_slab_stream = nullptr;    // where ev_capon_slab was recorded last (nullptr: nowhere yet)
+    dev_buf<int32_t> d_capon_peak_count;    // [2][B][VL]: Capon | Bartlett
+    dev_buf<int32_t> d_capon_peak_index;    // [2][B][VL][K]
+    dev_buf<double> d_capon_peak_power;     // [2][B][VL][K]
+    dev_buf<double> d_capon_peak_offset;    // [2][B][VL][K][2]
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -352,6 +377,12 @@ bool nbls_beam_grid_delays_of(const double* xij, int nelem, double fs, const dou
 // Capon / Bartlett spectra of units [u0, u0 + nu) for the plan's full array (capon.hip)
 hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 size_t nbls_capon_lds_bytes_of(int nelem);
+// ... of the instance that keeps the unit's two maps of G points in LDS (the LDS route of a peak request); 0: it does not fit
+size_t nbls_capon_peak_lds_bytes_of(int nelem, int G);
+// the automatic route of a peak request: 1 LDS, 2 HBM
+int nbls_capon_peak_route_of(int nelem, int G);
+// the neighbour table nbr [8][G] of the lattice cells cell [G][2] of a peak request (host)
+void nbls_capon_neighbours_of(const int32_t* cell, int G, int32_t* nbr);
 // the snapshot coefficients coef [nbands][maxLs][2] and steering vectors steer [nbands][nelem][G][2] of a plan (host, un-fused)
 void nbls_capon_tables_of(const double* xij, int nelem, double fs, const double* grid, int G, const double* freq,
                           const int32_t* snap_len, int nbands, int maxLs, double* coef, double* steer);

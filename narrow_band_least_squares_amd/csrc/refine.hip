@@ -21,6 +21,7 @@
 // the two forms give the same bits.
 #include "nbls_internal.h"
 #include "wave_ops.h"
+#include "refine_fraction.h"
 
 namespace {
 
@@ -43,16 +44,6 @@ struct RArgs {
     const int32_t* lag;       // [B][VL][P]
     double* frac;             // [B][VL][P]
 };
-
-__device__ inline double refine_fraction(double rm, double r0, double rp) {
-    const double nn = rm - rp;
-    const double dd = (rm - 2.0 * r0) + rp;
-    double f = 0.5 * nn / dd;
-    const bool ok = nbls_wave::finite_f64(rm) && nbls_wave::finite_f64(r0) && nbls_wave::finite_f64(rp) && dd < 0.0 &&
-                    nbls_wave::finite_f64(f);
-    if (!ok || f == 0.0) return 0.0;          // (also turns -0.0 into 0.0)
-    return f < -0.5 ? -0.5 : (f > 0.5 ? 0.5 : f);
-}
 
 template <bool LDS, int NW>
 __global__ __launch_bounds__(NW * 64) void refine_lag_kernel(RArgs a) {

@@ -363,7 +363,7 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
-               want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False):
+               want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
@@ -373,8 +373,16 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     closure of the picked lags.  ``capon_points`` > 0: ``capon_index`` / ``capon_power`` / ``bartlett_index`` /
     ``bartlett_power`` of the Capon spectra over that many points, with ``want_capon_maps`` ``capon_map`` / ``bartlett_map``
     (nbands, vector_len, capon_points) and with ``want_capon_csdm`` ``capon_csdm`` (nbands, vector_len, nchans, nchans)
-    complex; None otherwise."""
+    complex; with ``capon_peaks`` = K > 0 ``capon_peak_count`` (nbands, vector_len) int32, ``capon_peak_index`` (.., K) int32,
+    ``capon_peak_power`` (.., K), ``capon_peak_offset`` (.., K, 2) and the same four with ``bartlett_``; None otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
+    K = int(capon_peaks) if capon_points else 0
+    peaks = {}
+    for which in ('capon', 'bartlett'):
+        peaks[which + '_peak_count'] = np.zeros((nb, vector_len), dtype=np.int32) if K else None
+        peaks[which + '_peak_index'] = np.zeros((nb, vector_len, K), dtype=np.int32) if K else None
+        peaks[which + '_peak_power'] = np.zeros((nb, vector_len, K)) if K else None
+        peaks[which + '_peak_offset'] = np.zeros((nb, vector_len, K, 2)) if K else None
     cpi = np.zeros((2, nb, vector_len), dtype=np.int32) if capon_points else (None, None)
     cpp = np.zeros((2, nb, vector_len)) if capon_points else (None, None)
     cpm = np.zeros((2, nb, vector_len, capon_points)) if (capon_points and want_capon_maps) else (None, None)
@@ -398,7 +406,7 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      capon_map=cpm[0], bartlett_map=cpm[1],
                      capon_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128)
                      if (capon_points and want_capon_csdm) else None,
-                     lts=alpha < 1.0, fs=fs)
+                     lts=alpha < 1.0, fs=fs, **peaks)
 
 
 def drain(h, streamed, grids, mask, b0, b1, batch_done=None):
@@ -625,7 +633,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     predicts (``Handle.set_lag_seed``, ``planner.seed_halfwidths``; needs ``beam_grid``; likewise).  ``closure``: the plan
     also computes the closure of the picked lags behind every solve (``Handle.set_closure``; likewise).  ``capon``: a dict
     of ``Handle.set_capon``'s arguments, ``freqs`` / ``snap_len`` / ``snap_hop`` one per band of the Prep: the plan also
-    computes the Capon spectra of its bands (likewise)."""
+    computes the Capon spectra of its bands (likewise); with ``peaks`` = K > 0 in it also their K strongest peaks on the
+    lattice ``peak_cells`` above ``peak_floor`` (``Handle.set_capon_peaks``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -657,9 +666,14 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_beam_grid(beam_grid, beam_grid_map)
     if lag_seed is not None:
         h.set_lag_seed(lag_seed)
-    if capon is not None:
-        h.set_capon(**dict(capon, **{k: np.asarray(capon[k])[idx] for k in ('freqs', 'snap_len', 'snap_hop')}))
+    peaks = 0
     try:
+        if capon is not None:            # (inside the try: whatever one of the two refuses, the shared handle keeps neither)
+            capon = dict(capon)
+            peaks, cells, floor = capon.pop('peaks', 0), capon.pop('peak_cells', None), capon.pop('peak_floor', 0.25)
+            h.set_capon(**dict(capon, **{k: np.asarray(capon[k])[idx] for k in ('freqs', 'snap_len', 'snap_hop')}))
+            if peaks:
+                h.set_capon_peaks(cells, peaks, floor)
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
     finally:
@@ -677,6 +691,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_lag_seed(None)
         if capon is not None:
             h.set_capon(None)
+        if peaks:
+            h.set_capon_peaks(None)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -807,6 +823,10 @@ def collect(res, h, b0, b1, streamed, note):
         res.capon_map[b0:b1], res.bartlett_map[b0:b1] = h.fetch_capon_maps()
     if res.capon_csdm is not None:
         res.capon_csdm[b0:b1] = h.fetch_capon_csdm()
+    if res.capon_peak_count is not None:
+        for which, name in enumerate(('capon', 'bartlett')):
+            for field, a in zip(PEAK_FIELDS, h.fetch_capon_peaks(which)):
+                getattr(res, name + field)[b0:b1] = a
     if not live:
         note.bands(b0, b1)
 
@@ -880,19 +900,33 @@ def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
     return seeds
 
 
-def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm, W):
+PEAK_FIELDS = ('_peak_count', '_peak_index', '_peak_power', '_peak_offset')     # what ``Handle.fetch_capon_peaks`` returns, in order
+
+
+def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm, W,
+                 capon_peaks=0, capon_peak_floor=0.25, capon_cells=None):
     """The Capon keywords of ``process`` / ``process_batch`` -> the ``capon`` dict of ``launch`` or None; ``ValueError`` before
-    any GPU work (``planner.check_capon``)."""
+    any GPU work (``planner.check_capon``, ``planner.check_capon_peaks``)."""
+    wants_peaks = not (isinstance(capon_peaks, (int, np.integer)) and not isinstance(capon_peaks, (bool, np.bool_)) and capon_peaks == 0)
     if capon_grid is None:
         if capon_freqs is not None or capon_snapshots is not None or want_capon_maps or want_capon_csdm:
             raise ValueError('capon_freqs, capon_snapshots, want_capon_maps and want_capon_csdm need capon_grid')
+        if wants_peaks or capon_cells is not None:
+            raise ValueError('capon_peaks and capon_cells need capon_grid')
         return None
     if capon_freqs is None or capon_snapshots is None:
         raise ValueError('capon_grid needs capon_freqs (planner.capon_frequencies) and capon_snapshots (planner.capon_snapshots)')
     g, f, ls, hs, delta = planner.check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, W,
                                               want_capon_maps, want_capon_csdm)
-    return dict(grid=g, freqs=f, snap_len=ls, snap_hop=hs, loading=delta, want_maps=bool(want_capon_maps),
-                want_csdm=bool(want_capon_csdm))
+    out = dict(grid=g, freqs=f, snap_len=ls, snap_hop=hs, loading=delta, want_maps=bool(want_capon_maps),
+               want_csdm=bool(want_capon_csdm))
+    if wants_peaks:
+        cells, K, floor = planner.check_capon_peaks(len(g), planner.grid_cells(g)[0] if capon_cells is None else capon_cells,
+                                                    capon_peaks, capon_peak_floor)
+        out.update(peaks=K, peak_cells=cells, peak_floor=floor)
+    elif capon_cells is not None:
+        raise ValueError('capon_cells needs capon_peaks')
+    return out
 
 
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
@@ -901,7 +935,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             upload=True, window_slice=None, host_overlap=None, group_done=None, groups=None, units_done=None,
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
-            capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False):
+            capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
+            capon_peak_floor=0.25, capon_cells=None):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -942,6 +977,13 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     solve (``nbls_set_capon``); want_capon_maps=True: also ``res.capon_map`` / ``res.bartlett_map``
     (nbands, vector_len, G); want_capon_csdm=True: also ``res.capon_csdm`` (nbands, vector_len, N, N) complex.  ``ValueError``
     before any GPU work for whatever the library would refuse (``planner.check_capon``); ``process_segmented`` refuses it.
+    capon_peaks = K in 1..8 (needs ``capon_grid``): also ``res.capon_peak_count`` (nbands, vector_len) int32,
+    ``res.capon_peak_index`` (.., K) int32, ``res.capon_peak_power`` (.., K) and ``res.capon_peak_offset`` (.., K, 2), and the
+    same four with ``bartlett_``: per window the K strongest local maxima of either spectrum that reach ``capon_peak_floor``
+    times its maximum, with a sub-grid offset in lattice steps, picked on the GPU where the map is complete
+    (``nbls_set_capon_peaks``).  ``capon_cells`` (G, 2) int: the lattice coordinates of the grid points, by
+    default ``planner.grid_cells(capon_grid)[0]``.  ``ValueError`` before any GPU work (``planner.check_capon_peaks``);
+    ``process_segmented`` refuses it with the spectra.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -966,7 +1008,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     cap = max_bands_per_pass(nchans, npts)
     # (the Capon tables are checked against the window lengths: planned here already, before the upload starts)
     capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
-                         None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0])
+                         None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0],
+                         capon_peaks, capon_peak_floor, capon_cells)
     if cap < 1 and not prefiltered and capon is not None:
         raise ValueError('capon_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -983,7 +1026,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
-                         0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm)
+                         0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
+                         0 if capon is None else capon.get('peaks', 0))
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
@@ -1219,7 +1263,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
-                  want_capon_maps=False, want_capon_csdm=False):
+                  want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1240,8 +1284,9 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                    vector_len, prefiltered)
     VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
     capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
-                         prep.W)
+                         prep.W, capon_peaks, capon_peak_floor, capon_cells)
     CG = 0 if capon is None else len(capon['grid'])
+    CK = 0 if capon is None else capon.get('peaks', 0)
     limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
     per_sub = S if max_bands_per_pass(S * nchans, npts) >= 1 else max_bands_per_pass(nchans, npts)
     if per_sub < 1:
@@ -1249,7 +1294,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                          'process it on its own' % (nchans, npts))
     out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
                       grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
-                      want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm)
+                      want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1279,6 +1324,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 cp = [a.reshape(b1 - b0, k, VL) for a in h.fetch_capon()] if CG else None
                 cpmap = [a.reshape(b1 - b0, k, VL, CG) for a in h.fetch_capon_maps()] if (CG and want_capon_maps) else None
                 cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
+                cpk = [[a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_peaks(which)] for which in (0, 1)] if CK else None
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
@@ -1299,6 +1345,10 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                         res.capon_map[b0:b1], res.bartlett_map[b0:b1] = [a[:, j] for a in cpmap]
                     if cpr is not None:
                         res.capon_csdm[b0:b1] = cpr[:, j]
+                    if cpk is not None:
+                        for which, name in enumerate(('capon', 'bartlett')):
+                            for field, a in zip(PEAK_FIELDS, cpk[which]):
+                                getattr(res, name + field)[b0:b1] = a[:, j]
     finally:
         h.set_segments(1)
     for res, t0 in zip(out, t0s):

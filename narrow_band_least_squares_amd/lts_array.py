@@ -48,6 +48,19 @@ def grid_slowness(grid, index):
     return np.where(none, np.nan, vel), np.where(none, np.nan, baz)
 
 
+def peak_slowness(grid, steps, index, offset):
+    """The refined slowness vectors of a peak request -> (slowness (..., K, 2), vel (..., K), baz (..., K)):
+    ``grid[index] + offset * steps`` s/km (``steps``: ``planner.grid_cells(grid)[1]``) and its velocity and back-azimuth by the
+    formula of ``grid_slowness``; all NaN where the index is -1."""
+    index = np.asarray(index)
+    none = index < 0
+    s = np.asarray(grid, dtype=np.float64)[np.maximum(index, 0)] + np.where(none[..., None], 0.0, offset) * np.asarray(steps)
+    with np.errstate(divide='ignore'):
+        vel = 1.0 / np.hypot(s[..., 0], s[..., 1])
+    baz = np.mod(np.arctan2(s[..., 0], s[..., 1]) * 180.0 / np.pi - 360.0, 360.0)
+    return np.where(none[..., None], np.nan, s), np.where(none, np.nan, vel), np.where(none, np.nan, baz)
+
+
 def _returns_grid(res, grid, want_map):
     """The band's slowness-grid results behind ``_returns``: ``grid_vel, grid_baz, grid_fstat, grid_power, grid_index`` and,
     when asked, the map (csrc/beam_grid.hip: beam_grid_kernel)."""
@@ -60,7 +73,8 @@ def _returns_grid(res, grid, want_map):
 
 def _returns_capon(res, grid, want_maps, band=0, n=None):
     """A band's Capon results as a dict: the four fields, the slowness (``grid_slowness``) at either index and, when asked,
-    both maps (csrc/capon.hip: capon_kernel).  ``n=None``: the band's first ``nwin`` cells, copied; else whole rows."""
+    both maps (csrc/capon.hip: capon_kernel); for a pass with a peak request also its eight fields and the refined slowness
+    of every rank (``peak_slowness``).  ``n=None``: the band's first ``nwin`` cells, copied; else whole rows."""
     sl = slice(None) if n is None else slice(0, n)
     pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
     out = {k: pick(getattr(res, k)) for k in ('capon_index', 'capon_power', 'bartlett_index', 'bartlett_power')}
@@ -68,10 +82,26 @@ def _returns_capon(res, grid, want_maps, band=0, n=None):
     out['bartlett_vel'], out['bartlett_baz'] = grid_slowness(grid, out['bartlett_index'])
     if want_maps:
         out['capon_map'], out['bartlett_map'] = pick(res.capon_map), pick(res.bartlett_map)
+    if getattr(res, 'capon_peak_count', None) is not None:
+        steps = planner.grid_cells(grid)[1]
+        for which in ('capon', 'bartlett'):
+            for field in engine.PEAK_FIELDS:
+                out[which + field] = pick(getattr(res, which + field))
+            out[which + '_peak_slowness'], out[which + '_peak_vel'], out[which + '_peak_baz'] = peak_slowness(
+                grid, steps, out[which + '_peak_index'], out[which + '_peak_offset'])
     return out
 
 
-def _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading, maps):
+def _peak_keywords(grid, peaks, peak_floor):
+    """The peak keywords of ``engine.process`` behind ``peaks`` / ``peak_floor`` of the Capon entry points ({} for ``peaks=0``);
+    the cells are the grid's own lattice (``planner.grid_cells``).  ``ValueError`` before any GPU work."""
+    if isinstance(peaks, (int, np.integer)) and not isinstance(peaks, (bool, np.bool_)) and peaks == 0:
+        return {}
+    cells, K, floor = planner.check_capon_peaks(len(grid), planner.grid_cells(grid)[0], peaks, peak_floor)
+    return dict(capon_peaks=K, capon_peak_floor=floor, capon_cells=cells)
+
+
+def _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading, maps, peaks=0, peak_floor=0.25):
     """The Capon keywords of ``engine.process`` for one filtered band of window length ``W`` samples; the snapshots default
     to ``planner.capon_snapshots``.  ``ValueError`` before any GPU work."""
     grid = planner.check_slowness_grid(slowness_grid)
@@ -81,7 +111,7 @@ def _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading,
         snapshots = planner.capon_snapshots(planner.co_array(rij)[0], grid, fs, f, [W])
     planner.check_capon(nchans, grid, [freq], snapshots, loading, [W], bool(maps))
     return dict(capon_grid=grid, capon_freqs=[freq], capon_snapshots=snapshots, capon_loading=loading,
-                want_capon_maps=bool(maps))
+                want_capon_maps=bool(maps), **_peak_keywords(grid, peaks, peak_floor))
 
 
 def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
@@ -237,7 +267,7 @@ def ltsva_seeded(st, lat_list, lon_list, window_length, window_overlap, slowness
 
 
 def ltsva_capon(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None, snapshots=None,
-                loading=0.01, maps=False):
+                loading=0.01, maps=False, peaks=0, peak_floor=0.25):
     """``ltsva`` followed by the Capon (MVDR) and Bartlett slowness spectra of the narrow band's cross-spectral matrix: per
     window the snapshots (Hann-tapered DFT bins at ``freq`` Hz, ``snapshots = (Ls, Hs)`` samples long and apart; default
     ``planner.capon_snapshots``) of the full array give the matrix R, and over the slowness vectors ``slowness_grid`` (G, 2)
@@ -246,14 +276,19 @@ def ltsva_capon(st, lat_list, lon_list, window_length, window_overlap, slowness_
     wave (DESIGN.md section 18 has the definition and the counts).  Returns ``ltsva``'s 8-tuple followed by one dict:
     ``capon_index`` / ``bartlett_index`` (int32, -1 where there is no maximum), ``capon_power`` / ``bartlett_power``,
     ``capon_vel`` / ``capon_baz`` / ``bartlett_vel`` / ``bartlett_baz`` (``grid_slowness`` at the indices) and, with
-    ``maps=True``, ``capon_map`` / ``bartlett_map`` (nwin, G).  Computed on the GPU behind each window's solve
-    (csrc/capon.hip).  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    ``maps=True``, ``capon_map`` / ``bartlett_map`` (nwin, G).  With ``peaks=K`` (1..8; the grid must be a lattice,
+    ``planner.grid_cells``) the dict also holds the K strongest local maxima of either spectrum that reach ``peak_floor``
+    times its maximum: ``capon_peak_count`` (nwin,), ``capon_peak_index`` / ``capon_peak_power`` (nwin,
+    K), ``capon_peak_offset`` (nwin, K, 2) in lattice steps, ``capon_peak_slowness`` (nwin, K, 2) = ``grid[index] + offset *
+    steps``, ``capon_peak_vel`` / ``capon_peak_baz`` (nwin, K) of that refined vector, and the same seven with ``bartlett_``;
+    ranks beyond the kept peaks are -1 / NaN.  Computed on the GPU behind each window's solve (csrc/capon.hip).  Whatever the
+    library would refuse raises ``ValueError`` before any GPU work."""
     _check_elements_strict(len(st), alpha)
     nchans = len(st)
 
     def keywords(rij_used, fs, npts):
         W = planner.window_plan(npts, fs, window_length, window_overlap)[0]
-        return _capon_keywords(nchans, rij_used, fs, int(W), slowness_grid, freq, snapshots, loading, maps)
+        return _capon_keywords(nchans, rij_used, fs, int(W), slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)
     if rij is None:
         rij = get_rij(lat_list, lon_list, nchans)
     data, fs, _ = engine.stream_rows(st)
@@ -278,11 +313,12 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
 
 
 def ltsva_capon_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
-                      snapshots=None, loading=0.01, maps=False):
+                      snapshots=None, loading=0.01, maps=False, peaks=0, peak_floor=0.25):
     """``ltsva_capon`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
     element i equal to ``ltsva_capon(streams[i], ...)``; the streams as for ``ltsva_batch``."""
     return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, False, False, None, None,
-                        dict(slowness_grid=slowness_grid, freq=freq, snapshots=snapshots, loading=loading, maps=maps))
+                        dict(slowness_grid=slowness_grid, freq=freq, snapshots=snapshots, loading=loading, maps=maps,
+                             peaks=peaks, peak_floor=peak_floor))
 
 
 def _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
@@ -305,7 +341,8 @@ def _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alp
         crij = get_rij(lat_list, lon_list, nchans) if rij is None else rij
         W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
         ckw = _capon_keywords(nchans, crij, fs, int(W), capon['slowness_grid'], capon['freq'], capon.get('snapshots'),
-                              capon.get('loading', 0.01), capon.get('maps', False))
+                              capon.get('loading', 0.01), capon.get('maps', False), capon.get('peaks', 0),
+                              capon.get('peak_floor', 0.25))
     if len(streams) == 1:          # a batch of one IS the single call
         return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
                         slowness_grid, capon=(lambda *_: ckw) if ckw else None)]

@@ -15,7 +15,7 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
-from .lts_array import grid_slowness, _returns_capon
+from .lts_array import grid_slowness, _returns_capon, _peak_keywords
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -300,7 +300,8 @@ def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
 
 def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
                                     FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
-                                    slowness_grid, capon_freqs=None, snapshots=None, loading=0.01, maps=False):
+                                    slowness_grid, capon_freqs=None, snapshots=None, loading=0.01, maps=False, peaks=0,
+                                    peak_floor=0.25):
     """``narrow_band_least_squares`` followed by the Capon (MVDR) and Bartlett slowness spectra of every band's
     cross-spectral matrix (``lts_array.ltsva_capon``), computed on the GPU behind each window's solve
     from the filtered band that is already there.  ``capon_freqs`` (Hz per band) defaults to
@@ -308,12 +309,14 @@ def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     Returns the nine values of ``narrow_band_least_squares`` followed by one dict: ``capon_index`` / ``bartlett_index``
     (int32), ``capon_power`` / ``bartlett_power``, ``capon_vel`` / ``capon_baz`` / ``bartlett_vel`` / ``bartlett_baz``
     (``lts_array.grid_slowness`` at the indices), each (NBANDS, vector_len) with zeros beyond a band's windows, and with
-    ``maps=True`` ``capon_map`` / ``bartlett_map`` (NBANDS, vector_len, G).  Whatever the library would refuse raises
+    ``maps=True`` ``capon_map`` / ``bartlett_map`` (NBANDS, vector_len, G).  With ``peaks=K`` also the peak fields of
+    ``lts_array.ltsva_capon``, (NBANDS, vector_len, ...) with zeros beyond a band's windows.  Whatever the library would refuse raises
     ``ValueError`` before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a
     pass."""
     grid = planner.check_slowness_grid(slowness_grid)
     if not isinstance(maps, (bool, np.bool_)):
         raise ValueError('maps must be True or False, not %r' % (maps,))
+    peak_kw = _peak_keywords(grid, peaks, peak_floor)
     vector_len = _vector_len(WINLEN_list, WINOVER, st)
     _check_response_rows(w, h, freq_resp_list)
     if not (0.5 <= ALPHA <= 1.0):
@@ -328,7 +331,8 @@ def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
             f = planner.check_capon(len(st), grid, f, (1, 1), loading, W)[1]
             snaps = planner.capon_snapshots(planner.co_array(rij_used)[0], grid, fs, f, W)
         planner.check_capon(len(st), grid, f, snaps, loading, W, bool(maps))
-        return dict(capon_grid=grid, capon_freqs=f, capon_snapshots=snaps, capon_loading=loading, want_capon_maps=bool(maps))
+        return dict(capon_grid=grid, capon_freqs=f, capon_snapshots=snaps, capon_loading=loading, want_capon_maps=bool(maps),
+                    **peak_kw)
     res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
                                        FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
                                        FILTER_RIPPLE, vector_len, rij=rij,
@@ -337,6 +341,11 @@ def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     computed = np.arange(res.capon_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
     for k in ('capon_vel', 'capon_baz', 'bartlett_vel', 'bartlett_baz'):
         out[k] = np.where(computed, out[k], 0.0)                     # (zero-padded like vel_array)
+    if peak_kw:
+        for which in ('capon', 'bartlett'):
+            for k in ('_peak_vel', '_peak_baz'):
+                out[which + k] = np.where(computed[..., None], out[which + k], 0.0)
+            out[which + '_peak_slowness'] = np.where(computed[..., None, None], out[which + '_peak_slowness'], 0.0)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (out,)
 

@@ -641,3 +641,63 @@ def check_capon(nchans, grid, freqs, snapshots, loading, W_list, maps=False, csd
     if nb * len(g) * int(nchans) * 16 > MAX_CAPON_STEER_BYTES:
         raise ValueError('the steering table of %d bands x %d grid points x %d elements exceeds 1 GiB' % (nb, len(g), nchans))
     return g, f, ls.astype(np.int32), hs.astype(np.int32), float(loading)
+
+
+MAX_CAPON_PEAKS = 8          # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
+MAX_CAPON_CELL = 32768       # lattice coordinates of a peak request lie below this
+
+
+def grid_cells(grid):
+    """The lattice coordinates of a slowness grid, as a peak request takes them (``nbls_set_capon_peaks``, DESIGN.md section
+    19) -> (cells int32 (G, 2), steps float64 (2,)).  Per axis the step is the smallest positive difference between distinct
+    coordinates (values within 1e-9 of the axis' span count as equal; an axis with one value has step 0 and cells 0) and
+    ``cell = rint((v - min) / step)``.  ``ValueError`` if a point lies more than 1e-6 step off its lattice point, if two points
+    share a cell, or if a coordinate reaches 32768.  ``grid_cells(slowness_grid(s, n))`` gives the meshgrid indices."""
+    g = check_slowness_grid(grid)
+    cells = np.zeros(g.shape, dtype=np.int64)
+    steps = np.zeros(2)
+    for ax in (0, 1):
+        v = g[:, ax]
+        u = np.unique(v)
+        d = np.diff(u)
+        d = d[d > 1e-9 * (u[-1] - u[0])] if len(u) > 1 else d
+        if len(d) == 0:
+            continue
+        steps[ax] = d.min()
+        q = (v - u[0]) / steps[ax]
+        c = np.rint(q)
+        if np.any(np.abs(q - c) > 1e-6):
+            raise ValueError('slowness_grid is no lattice on axis %d: point %d lies %.3g steps off its lattice point'
+                             % (ax, int(np.argmax(np.abs(q - c))), float(np.abs(q - c).max())))
+        if c.max() >= MAX_CAPON_CELL:
+            raise ValueError('slowness_grid spans %d lattice steps on axis %d: fewer than %d are supported'
+                             % (int(c.max()), ax, MAX_CAPON_CELL))
+        cells[:, ax] = c.astype(np.int64)
+    if len(np.unique(cells[:, 0] * MAX_CAPON_CELL + cells[:, 1])) != len(cells):
+        raise ValueError('two points of slowness_grid share one lattice cell')
+    return np.ascontiguousarray(cells, dtype=np.int32), steps
+
+
+def check_capon_peaks(grid_len, cells, K, floor):
+    """Everything ``nbls_set_capon_peaks`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (cells int32
+    (G, 2), K int, floor float).  ``grid_len``: the G of the Capon spectra the request goes with."""
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not (1 <= int(K) <= MAX_CAPON_PEAKS):
+        raise ValueError('the number of peaks must be an integer in 1..%d, not %r' % (MAX_CAPON_PEAKS, K))
+    if not _real(floor) or not (0.0 <= float(floor) <= 1.0):
+        raise ValueError('the peak floor must be a number in [0, 1], not %r' % (floor,))
+    try:
+        c = np.asarray(cells)
+    except Exception:
+        raise ValueError('the cells must be a (G, 2) array of lattice coordinates')
+    if c.dtype == object or c.dtype.kind not in 'iu':
+        raise ValueError('the cells must hold integers, not dtype %s' % c.dtype)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError('the cells must be (G, 2), not %r' % (c.shape,))
+    if c.shape[0] != int(grid_len):
+        raise ValueError('%d cells for Capon spectra of %d grid points' % (c.shape[0], int(grid_len)))
+    c = c.astype(np.int64)
+    if np.any(c < 0) or np.any(c >= MAX_CAPON_CELL):
+        raise ValueError('the cells must lie in 0..%d' % (MAX_CAPON_CELL - 1))
+    if len(np.unique(c[:, 0] * MAX_CAPON_CELL + c[:, 1])) != len(c):
+        raise ValueError('two points share one lattice cell')
+    return np.ascontiguousarray(c, dtype=np.int32), int(K), float(floor)
