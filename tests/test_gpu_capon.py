@@ -7,6 +7,7 @@ both.  Between the forms of a pass (streamed, batched, window slices, with or wi
 output is equal bit for bit.  All cases use prefiltered traces at fs = 20 Hz."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -21,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 FS = 20.0
 T0 = 17884.0729166667
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T, CH = _hip.CAPON_THREADS, _hip.CAPON_CHUNK
 GRID = planner.slowness_grid(3.07, 5)                       # 21 points, s = 0 among them
 FREQ = 1.3
@@ -42,15 +44,16 @@ def _process(data, rij, W, alpha, Ls, Hs, grid=GRID, delta=0.01, overlap=0.5, ma
     return res
 
 
-def _against_reference(res, filt, grid, Ls, Hs, delta, label='', well_conditioned=True):
-    N, W, inc, n = filt.shape[0], int(res.W[0]), int(res.inc[0]), int(res.nwin[0])
-    coef, steer = res.handle.fetch_capon_tables(0)
-    coef_np, steer_np = ct.tables(res.xij, grid, FS, FREQ, Ls, N)
+def _against_reference(res, filt, grid, Ls, Hs, delta, label='', well_conditioned=True, band=0, freq=FREQ):
+    """``band``: the band of the plan whose rows are compared, ``filt`` its samples and ``freq``, ``Ls``, ``Hs`` its tables."""
+    N, W, inc, n = filt.shape[0], int(res.W[band]), int(res.inc[band]), int(res.nwin[band])
+    coef, steer = res.handle.fetch_capon_tables(band)
+    coef_np, steer_np = ct.tables(res.xij, grid, FS, freq, Ls, N)
     assert np.abs(coef - coef_np).max() <= ct.TABLE_TOL and np.abs(steer - steer_np).max() <= ct.TABLE_TOL
     Rref, tolA = ct.csdm_reference(filt, coef, W, inc, n, Hs)
     worst = dict(A=0.0, B=0.0, C=0.0)
     for w in range(n):
-        R = res.capon_csdm[0, w]
+        R = res.capon_csdm[band, w]
         d = (R.astype(ct.CLD) - Rref[w])
         ok = tolA[w] > 0
         if ok.any():
@@ -63,15 +66,15 @@ def _against_reference(res, filt, grid, Ls, Hs, delta, label='', well_conditione
             if delta > 0:
                 assert ref['kappa'] <= (N + delta) / delta * (1 + 1e-6)
         worst['B'] = max(worst['B'], ct.check_spectrum('%s Bartlett w=%d' % (label, w), ref['PB'], ref['tolB'], ref['index_B'],
-                                                       int(res.bartlett_index[0, w]), float(res.bartlett_power[0, w]),
-                                                       res.bartlett_map[0, w]))
+                                                       int(res.bartlett_index[band, w]), float(res.bartlett_power[band, w]),
+                                                       res.bartlett_map[band, w]))
         worst['C'] = max(worst['C'], ct.check_spectrum('%s Capon w=%d' % (label, w), ref['PC'], ref['tolC'], ref['index_C'],
-                                                       int(res.capon_index[0, w]), float(res.capon_power[0, w]),
-                                                       res.capon_map[0, w]))
+                                                       int(res.capon_index[band, w]), float(res.capon_power[band, w]),
+                                                       res.capon_map[band, w]))
     print('%s N=%d W=%d Ls=%d Hs=%d G=%d delta=%g: %d windows, worst |d| / bound: R %.3g, Bartlett %.3g, Capon %.3g'
           % (label, N, W, Ls, Hs, len(grid), delta, n, worst['A'], worst['B'], worst['C']))
     for k in FIELDS:                                                 # cells beyond nwin are zeros
-        assert not getattr(res, k)[0, n:].any(), k
+        assert not getattr(res, k)[band, n:].any(), k
     return worst
 
 
@@ -294,6 +297,19 @@ def test_refusals_of_the_library():
         assert err.value.code == _hip.NBLS_ERR_STATE
     finally:
         fresh.close()
+
+
+def test_rccl_communicator_refuses_the_spectra_at_plan_time():
+    """A communicator lives as long as its process: a child process over the tests' loopback transport."""
+    src = os.path.join(ROOT, 'tests', 'c_caller', 'loopback_rccl.cpp')
+    lib = os.path.join(ROOT, 'tests', 'c_caller', 'libloopback_rccl.so')
+    if not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
+        subprocess.run(['/opt/rocm/bin/hipcc', '-O2', '-shared', '-fPIC', '--offload-arch=gfx950', src, '-o', lib], check=True,
+                       timeout=300)
+    env = dict(os.environ, NBLS_TEST_TRANSPORT=lib)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', '_capon_comm_worker.py')], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0 and 'CAPON_COMM_OK' in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def _count_on_patch(maps, grid, shape):

@@ -58,18 +58,18 @@ def _process(data, rij, W, alpha, Ls, Hs, grid, K, floor=None, delta=0.01, overl
     return res
 
 
-def _against_truth(res, cells, K, floor, label=''):
-    """All eight fields against the truth on the pass's own maps; rank 0 is the arg-max; cells beyond nwin are zeros."""
-    n = int(res.nwin[0])
+def _against_truth(res, cells, K, floor, label='', band=0):
+    """All eight fields of the band against the truth on the pass's own maps; rank 0 is the arg-max; cells beyond nwin are zeros."""
+    n = int(res.nwin[band])
     counts = {}
     for name in ('capon', 'bartlett'):
-        want = pt.peaks_of_maps(getattr(res, name + '_map')[0, :n], cells, K, floor)
+        want = pt.peaks_of_maps(getattr(res, name + '_map')[band, :n], cells, K, floor)
         for field, exp in zip(engine.PEAK_FIELDS, want):
             got = getattr(res, name + field)
-            assert pt.same_bits(got[0, :n], exp), '%s %s%s: got %r, the truth has %r' % (label, name, field, got[0, :n], exp)
-            assert not got[0, n:].any(), name + field
-        assert np.array_equal(getattr(res, name + '_peak_index')[0, :n, 0], getattr(res, name + '_index')[0, :n])
-        assert pt.same_bits(getattr(res, name + '_peak_power')[0, :n, 0], getattr(res, name + '_power')[0, :n])
+            assert pt.same_bits(got[band, :n], exp), '%s %s%s: got %r, the truth has %r' % (label, name, field, got[band, :n], exp)
+            assert not got[band, n:].any(), name + field
+        assert np.array_equal(getattr(res, name + '_peak_index')[band, :n, 0], getattr(res, name + '_index')[band, :n])
+        assert pt.same_bits(getattr(res, name + '_peak_power')[band, :n, 0], getattr(res, name + '_power')[band, :n])
         counts[name] = want[0]
     return counts
 

@@ -346,13 +346,13 @@ def _process(data, rij, W, alpha, overlap=0.5, K=KW, **kw):
     return res
 
 
-def _check_res(res, data, K=KW):
-    n, W, inc = int(res.nwin[0]), int(res.W[0]), int(res.inc[0])
+def _check_res(res, data, K=KW, band=0):
+    n, W, inc = int(res.nwin[band]), int(res.W[band]), int(res.inc[band])
     pairs = [tuple(p) for p in res.pair_idx]
-    c = sdt.centres(res.handle.fetch_beam_grid_delays(), res.grid_index[0, :n], pairs)
+    c = sdt.centres(res.handle.fetch_beam_grid_delays(), res.grid_index[band, :n], pairs)
     lag, cmax = sdt.pick_windows(data, W, [w * inc for w in range(n)], pairs, c, K)
-    np.testing.assert_array_equal(res.lag[0, :n], lag)
-    np.testing.assert_allclose(res.cmax[0, :n], cmax, rtol=0, atol=1e-12)
+    np.testing.assert_array_equal(res.lag[band, :n], lag)
+    np.testing.assert_allclose(res.cmax[band, :n], cmax, rtol=0, atol=1e-12)
     return lag
 
 

@@ -42,25 +42,26 @@ def _process(data, rij, W, alpha, overlap=None, subsample=True, **kw):
     return res
 
 
-def _reference(res, data):
-    n, W, inc = int(res.nwin[0]), int(res.W[0]), int(res.inc[0])
-    return rt.refine_windows(data, W, [w * inc for w in range(n)], [tuple(p) for p in res.pair_idx], res.lag[0, :n]), n
+def _reference(res, data, band=0):
+    n, W, inc = int(res.nwin[band]), int(res.W[band]), int(res.inc[band])
+    return rt.refine_windows(data, W, [w * inc for w in range(n)], [tuple(p) for p in res.pair_idx], res.lag[band, :n]), n
 
 
-def _check_fractions(res, data, label):
-    """Every pair of every window within the bound; none is skipped: first, on the reference alone, |D| >= 2^20 E."""
-    ref, n = _reference(res, data)
-    W = int(res.W[0])
-    assert n >= 3 and np.all(np.abs(res.lag[0, :n]) < W - 1), '%s: a lag at the end of the range (choose another seed)' % label
+def _check_fractions(res, data, label, band=0):
+    """Every pair of every window of the band (``data``: its samples) within the bound; none is skipped: first, on the
+    reference alone, |D| >= 2^20 E."""
+    ref, n = _reference(res, data, band)
+    W = int(res.W[band])
+    assert n >= 3 and np.all(np.abs(res.lag[band, :n]) < W - 1), '%s: a lag at the end of the range (choose another seed)' % label
     assert np.all(np.abs(ref['D']) >= 2.0 ** 20 * ref['E']), '%s: a pair without a clear maximum (choose another seed)' % label
-    got = res.lag_frac[0, :n]
+    got = res.lag_frac[band, :n]
     err = np.abs(got - ref['frac'])
     print('%s: %d windows x %d pairs, worst |d frac| / bound = %.3g, |frac| median %.3g, max %.3g, min |D| / E = %.3g'
           % (label, n, got.shape[1], np.max(err / ref['bound']), np.median(np.abs(ref['frac'])), np.max(np.abs(ref['frac'])),
              np.min(np.abs(ref['D']) / ref['E'])))
     assert np.all(err <= ref['bound']), label
     assert np.all(np.abs(got) <= 0.5) and np.count_nonzero(got) >= got.size // 2
-    assert not res.lag_frac[0, n:].any()                                          # cells beyond nwin are zeros
+    assert not res.lag_frac[band, n:].any()                                       # cells beyond nwin are zeros
     return ref, n
 
 
