@@ -534,6 +534,43 @@ int nbls_set_capon_peaks(nbls_handle* h, const int32_t* cell, int32_t G, int32_t
 int nbls_fetch_capon_peaks(nbls_handle* h, int32_t which /* 0 Capon, 1 Bartlett */,
                            int32_t* count, int32_t* index, double* power, double* offset);
 
+/* ---- Beam and Capon results on the elements LTS kept ----
+ * FAST-LTS finds the mistimed or noisy element of a window and takes the weight of its pairs; the beam of nbls_set_beam and
+ * the spectra of nbls_set_capon still sum over the whole array.  On request the plan works out, per window, which elements
+ * LTS has dropped, and those results are formed over the elements it kept.  The geometry must be the full lexicographic
+ * pair list of the trace's array (as for nbls_set_closure); k(a, b) is the index of pair (a, b), a < b, in it.  For
+ * estimator 0, the unit of result row r and window w, N elements and the weights w_k exactly as nbls_fetch returns them:
+ *   count    c_m = the number of pairs k that hold element m and have w_k == 0.
+ *   dropped  element m is dropped iff c_m >= q, q the request's min_pairs, 1 <= q <= N - 1 (N - 1: every pair of the
+ *            element has lost its weight).
+ *   outputs  dropped_mask uint32 [rows][vector_len], bit m set iff m is dropped; kept_count int32 [rows][vector_len] = M.
+ *   kept set e_0 < ... < e_{M-1}, the complement of the dropped set; if fewer than 3 elements would remain, the kept set
+ *            is the whole array (M = N) and dropped_mask still shows what the rule found.
+ *   An OLS plan has every weight 1: its mask is 0 and M = N.  Cells beyond nwin[r] and outside a window slice are zeros.
+ * NBLS_KEPT_BEAM: beam_power and fstat are nbls_set_beam's definition with N -> M, the elements e_i in ascending order,
+ *   d_0 = 0 and d_i = rint(fs * (xij[k(e_0, e_i)] . z)): the reference element is the first kept one, z the solved slowness.
+ * NBLS_KEPT_CAPON: R is formed, and with NBLS_CAPON_CSDM returned, for all N elements as before.  The spectra use
+ *   R_K = R[e_i][e_j], t = sum_i Re R_K,ii, R' = R_K + delta (t / M) I, a_K[g][i] = a[g][e_i] (the plan's steering table,
+ *   not re-referenced: both spectra are invariant to a common phase), P_B = Re(a_K^H R_K a_K) / M^2, and the M x M Cholesky
+ *   factor and substitution with every loop in ascending i, j.  The degenerate rules of nbls_set_capon apply to R_K and t.
+ *   The maps, the arg-max and the peak pick (nbls_set_capon_peaks, both routes) work on these spectra unchanged.
+ * Where no element is dropped both are the plain plan's results bit for bit.  No atomics; every order depends on (N, the
+ * kept set, W, ...) alone: single, streamed, batched and window-sliced passes give the same bits; full, bounded and seeded
+ * lag picks are all accepted.
+ *   nbls_set_kept_elements(h, min_pairs, flags)   read by the next nbls_plan; min_pairs = 0 switches it off (the default:
+ *                            such a plan launches exactly what it launched before).  flags: NBLS_KEPT_BEAM, NBLS_KEPT_CAPON.
+ *                            NBLS_ERR_ARG, the handle unchanged, for a negative min_pairs or unknown flags.  nbls_plan
+ *                            returns NBLS_ERR_ARG for min_pairs > N - 1 (or N > 32), NBLS_ERR_STATE for a flag whose feature
+ *                            the plan lacks (nbls_set_beam, nbls_set_capon) or a geometry that is not the full pair list,
+ *                            NBLS_ERR_UNSUPPORTED with nbls_set_estimators (further estimators have kept sets of their
+ *                            own: out of scope) and with an RCCL communicator.
+ *   nbls_fetch_kept_elements(h, dropped_mask, kept_count)   either may be NULL.  Rows, waiting and zeros as for
+ *                            nbls_fetch_closure; NBLS_ERR_STATE if the plan did not ask.  Written by the solve stage alone. */
+#define NBLS_KEPT_BEAM 1
+#define NBLS_KEPT_CAPON 2
+int nbls_set_kept_elements(nbls_handle* h, int32_t min_pairs, int32_t flags);
+int nbls_fetch_kept_elements(nbls_handle* h, uint32_t* dropped_mask, int32_t* kept_count);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -32,6 +32,7 @@ EXPORTS = [
     'nbls_set_closure', 'nbls_fetch_closure', 'nbls_est_fetch_closure',
     'nbls_set_capon', 'nbls_fetch_capon', 'nbls_fetch_capon_maps', 'nbls_fetch_capon_csdm', 'nbls_fetch_capon_tables',
     'nbls_set_capon_peaks', 'nbls_fetch_capon_peaks',
+    'nbls_set_kept_elements', 'nbls_fetch_kept_elements',
 ]
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
@@ -41,6 +42,7 @@ CAPON_THREADS = 128      # threads of a workgroup of the Capon kernel, one grid 
 CAPON_CHUNK = 32         # snapshots that go through LDS together (NBLS_CAPON_CHUNK)
 CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
 CAPON_PEAKS_MAX = 8      # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
+KEPT_BEAM, KEPT_CAPON = 1, 2      # flags of nbls_set_kept_elements
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -182,6 +184,8 @@ def load_library(path=None):
     lib.nbls_fetch_capon_tables.argtypes = [vp, C.c_int32, dp, dp]
     lib.nbls_set_capon_peaks.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_double]
     lib.nbls_fetch_capon_peaks.argtypes = [vp, C.c_int32, ip, ip, dp, dp]
+    lib.nbls_set_kept_elements.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.nbls_fetch_kept_elements.argtypes = [vp, C.POINTER(C.c_uint32), ip]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -559,6 +563,22 @@ class Handle:
         else:
             self._chk(self.lib.nbls_est_fetch_closure(self._h, int(e), _dptr(out[0]), _dptr(out[1]), _dptr(el)))
         return out[0], out[1], el
+
+    def set_kept_elements(self, min_pairs=0, beam=False, capon=False):
+        """The next plans also work out, behind every unit's solve, which elements LTS has dropped — those with at least
+        ``min_pairs`` pairs of weight 0 — and, with ``beam`` / ``capon``, form the plan's beam results / Capon spectra over
+        the elements it kept (``nbls_set_kept_elements``); 0 switches that off."""
+        flags = (KEPT_BEAM if beam else 0) | (KEPT_CAPON if capon else 0)
+        self._chk(self.lib.nbls_set_kept_elements(self._h, int(min_pairs), flags))
+
+    def fetch_kept_elements(self):
+        """-> (dropped_mask uint32, kept_count int32), (rows, vector_len) each: bit m of the mask is set where element m
+        is dropped; the count is that of the elements the beam and the spectra are formed over."""
+        mask = np.empty((self.nbands, self.vector_len), dtype=np.uint32)
+        count = np.empty((self.nbands, self.vector_len), dtype=np.int32)
+        self._chk(self.lib.nbls_fetch_kept_elements(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                    count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return mask, count
 
     def set_beam_grid(self, grid=None, want_map=False):
         """The next plans also search, per window, the beam F-statistic of the full array over the slowness vectors

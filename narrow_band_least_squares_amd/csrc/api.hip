@@ -830,6 +830,26 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: option capon_peak_route 1: the two maps of " + std::to_string(G) + " points do not fit the LDS of a workgroup beside the kernel's " +
                                                      std::to_string(nbls_capon_lds_bytes_of(h->nchans / NS)) + " bytes");
     }
+    if (h->want_kept_q > 0) {        // the elements LTS kept (nbls_set_kept_elements): the full pair list, estimator 0 alone
+        if (h->nest > 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the kept elements (nbls_set_kept_elements) are not supported with further estimators (nbls_set_estimators)");
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the kept elements (nbls_set_kept_elements) are not supported with an RCCL communicator (the gathered block does not carry them)");
+        const int En = h->nchans / NS;
+        bool full = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
+        for (int i = 0, k = 0; full && i < En; ++i)
+            for (int j = i + 1; j < En; ++j, ++k)
+                if (h->h_pair[2 * k] != i || h->h_pair[2 * k + 1] != j) { full = false; break; }
+        if (!full)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: the kept elements (nbls_set_kept_elements) need the geometry of the trace's array, every pair in lexicographic order");
+        if (En > 32 || h->want_kept_q > En - 1)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: min_pairs (nbls_set_kept_elements) is " + std::to_string(h->want_kept_q) + " for an array of " +
+                                             std::to_string(En) + " elements (1.." + std::to_string(En - 1) + ", at most 32 elements)");
+        if ((h->want_kept_flags & NBLS_KEPT_BEAM) && !h->want_beam)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_KEPT_BEAM (nbls_set_kept_elements) needs beam results (nbls_set_beam)");
+        if ((h->want_kept_flags & NBLS_KEPT_CAPON) && h->want_capon.grid.empty())
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_KEPT_CAPON (nbls_set_kept_elements) needs Capon spectra (nbls_set_capon)");
+    }
     if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
         if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
@@ -854,6 +874,10 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->beam_valid = false;
     h->closure = h->want_closure;
     h->closure_valid = false;
+    h->kept_q = h->want_kept_q;
+    h->kept_beam = h->kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_BEAM);
+    h->kept_capon = h->kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_CAPON);
+    h->kept_valid = false;
     h->refine = h->want_refine;
     h->frac_valid = false;
     h->solve_ran = false;
@@ -1161,6 +1185,11 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_grid_fp, 2 * cells * sizeof(double)))) return rc;
         if (h->grid_map && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->grid_n * sizeof(double)))) return rc;
     }
+    if (h->kept_q > 0) {             // the elements LTS kept: the mask and the count of every cell
+        const size_t cells = (size_t)a.R * a.vector_len;
+        if ((rc = ensure(h, h->d_kept_mask, cells * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(h, h->d_kept_count, cells * sizeof(int32_t)))) return rc;
+    }
     if (h->capon_n > 0) {            // the Capon spectra: the band tables and the result buffers, likewise
         const size_t cells = (size_t)a.R * a.vector_len;
         const int E = a.E, G = h->capon_n, nb = a.nbands;
@@ -1298,6 +1327,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     h->last_stage_mask = stage_mask;
     if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
     if ((stage_mask & 4) && h->closure) h->closure_valid = true;      // (likewise the closure grids)
+    if ((stage_mask & 4) && h->kept_q > 0) h->kept_valid = true;     // (... and the kept elements)
     if (stage_mask & 4) h->solve_ran = true;
     // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
     if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
@@ -1590,6 +1620,34 @@ int nbls_est_fetch_closure(nbls_handle* h, int32_t est, double* consistency, dou
         if (!h->closure_valid) { memset(outs[g], 0, cells * row); continue; }
         HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * row, hipMemcpyDeviceToHost));
         zero_uncomputed(h, outs[g], row);                 // like the grids
+    }
+    return NBLS_OK;
+}
+
+int nbls_set_kept_elements(nbls_handle* h, int32_t min_pairs, int32_t flags) {
+    if (!h) return NBLS_ERR_ARG;
+    if (min_pairs < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_kept_elements: min_pairs must not be negative");
+    if (flags & ~(NBLS_KEPT_BEAM | NBLS_KEPT_CAPON)) return fail(h, NBLS_ERR_ARG, "nbls_set_kept_elements: unknown flags");
+    h->want_kept_q = min_pairs;              // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want_kept_flags = min_pairs > 0 ? flags : 0;
+    return NBLS_OK;
+}
+
+int nbls_fetch_kept_elements(nbls_handle* h, uint32_t* dropped_mask, int32_t* kept_count) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_kept_elements: no plan");
+    if (h->kept_q < 1 || !h->d_kept_mask || !h->d_kept_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_kept_elements: nbls_set_kept_elements before nbls_plan");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    // written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass without it leaves them
+    // as they are
+    void* outs[2] = {dropped_mask, kept_count};
+    const void* srcs[2] = {h->d_kept_mask.p, h->d_kept_count.p};
+    for (int g = 0; g < 2; ++g) {
+        if (!outs[g]) continue;
+        if (!h->kept_valid) { memset(outs[g], 0, cells * 4); continue; }
+        HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * 4, hipMemcpyDeviceToHost));
+        zero_uncomputed(h, outs[g], 4);                   // like the grids
     }
     return NBLS_OK;
 }

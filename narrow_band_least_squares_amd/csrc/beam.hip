@@ -14,6 +14,12 @@
 // keeps its own two sums in t order, the wave adds them with the fixed DPP tree of wave_ops.h, the four waves of a long
 // unit are added in wave order through LDS.  The order of every sum depends on (N, W) alone: no atomics, and nothing
 // depends on the launch's unit range, so single, batched and streamed passes give the same bits.
+//
+// A plan that asked for the beam of the elements LTS kept (nbls_set_kept_elements with NBLS_KEPT_BEAM) runs the
+// KEPT instance: "lane i holds e_i and d_i" is filled per unit instead of per launch, from the unit's dropped mask
+// (kept.hip has written it on the same stream): e_i is the i-th set bit of the kept bits, the reference element is e_0 and
+// d_i comes from the co-array row of pair (e_0, e_i).  The element count of the unit's sums and of its F is M; beam_sums is
+// the same function.  A unit without a dropped element fills the registers as the plain instance does: the same bits.
 #include "nbls_internal.h"
 #include "wave_ops.h"
 
@@ -44,20 +50,21 @@ struct BArgs {
     int vector_len, u0, nunits;
     double* power;            // [B][VL]
     double* fstat;            // [B][VL]
+    const uint32_t* dropped;  // [B][VL] the KEPT instance: bit m set, element m is dropped (kept.hip)
 };
 
-// The sums of the samples t = tl, tl + STRIDE, ... of one unit.  d_mine / el_mine: lane i < N holds d_i and e_i.  Four
+// The sums of the samples t = tl, tl + STRIDE, ... of one unit.  d_mine / el_mine: lane i < n holds d_i and e_i.  Four
 // samples of a lane go through the element loop together (four independent loads in flight per element); their squares
 // are added in t order, so the unrolling does not show in the result.
 constexpr int BEAM_TU = 4;
 template <int STRIDE>
-__device__ inline void beam_sums(const BArgs& a, const double* rowbase, int64_t s0, int W, int d_mine, int el_mine, int tl,
+__device__ inline void beam_sums(const BArgs& a, const double* rowbase, int64_t s0, int W, int d_mine, int el_mine, int n, int tl,
                                  double& sb, double& st) {
     for (int t = tl; t < W; t += BEAM_TU * STRIDE) {
         double b[BEAM_TU], q[BEAM_TU];
 #pragma unroll
         for (int k = 0; k < BEAM_TU; ++k) { b[k] = 0.0; q[k] = 0.0; }
-        for (int i = 0; i < a.N; ++i) {
+        for (int i = 0; i < n; ++i) {
             const int d = __builtin_amdgcn_readlane(d_mine, i), el = __builtin_amdgcn_readlane(el_mine, i);
             const double* row = rowbase + (int64_t)el * a.npts_pad;
 #pragma unroll
@@ -78,8 +85,8 @@ __device__ inline void beam_sums(const BArgs& a, const double* rowbase, int64_t 
     }
 }
 
-__device__ inline void beam_store(const BArgs& a, int64_t cell, int W, bool bad, double sb, double st) {
-    const double n = (double)a.N, nan_ = __builtin_nan("");
+__device__ inline void beam_store(const BArgs& a, int64_t cell, int W, int nel, bool bad, double sb, double st) {
+    const double n = (double)nel, nan_ = __builtin_nan("");
     double p, f;
     if (bad) { p = nan_; f = nan_; }
     else if (st == 0.0) { p = 0.0; f = nan_; }
@@ -92,6 +99,7 @@ __device__ inline void beam_store(const BArgs& a, int64_t cell, int W, bool bad,
     a.fstat[cell] = f;
 }
 
+template <bool KEPT>
 __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
     __shared__ double red[2 * BEAM_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -110,7 +118,24 @@ __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
         const double z0 = a.z[2 * cell], z1 = a.z[2 * cell + 1];
         bool bad_l = !nbls_wave::finite_f64(z0) || !nbls_wave::finite_f64(z1);
         int d_mine = 0, el_mine = 0;
-        if (lane < a.N) {                                        // N <= 64 = BEAM_MAX_ELEMENTS: one element per lane
+        int n = a.N;                                             // elements of this unit's sums
+        if (KEPT) {
+            // the unit's kept elements (the full array, est[0]: a.kept is NULL and N <= 32): lane i < M takes the i-th set
+            // bit of the kept bits and the co-array row of pair (e_0, e_i) of the full lexicographic list
+            const uint32_t bits = nbls_kept_bits_of(a.dropped[cell], a.N, n);
+            const int e0 = __builtin_ctz(bits);
+            uint32_t b = bits;
+            for (int i = 0; i < n; ++i) {                        // (n and bits are the same in every lane)
+                if (i == lane) el_mine = __builtin_ctz(b);
+                b &= b - 1;
+            }
+            if (lane > 0 && lane < n) {
+                const int k = e0 * (2 * a.N - e0 - 1) / 2 + (el_mine - e0 - 1);
+                const double tau = a.fs * (a.xij[2 * k] * z0 + a.xij[2 * k + 1] * z1);
+                if (fabs(tau) < BEAM_MAX_DELAY) d_mine = (int)rint(tau);
+                else bad_l = true;                               // (NaN too)
+            }
+        } else if (lane < a.N) {                                 // N <= 64 = BEAM_MAX_ELEMENTS: one element per lane
             el_mine = a.kept ? a.kept[lane] : lane;
             if (lane > 0) {
                 const double tau = a.fs * (a.xij[2 * (lane - 1)] * z0 + a.xij[2 * (lane - 1) + 1] * z1);
@@ -121,12 +146,12 @@ __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
         const bool bad = __any(bad_l) != 0;
         const double* rowbase = a.filt + (int64_t)row * a.nelem * a.npts_pad;
         double sb = 0.0, st = 0.0;
-        if (coop) beam_sums<BEAM_WAVES * 64>(a, rowbase, s0, W, d_mine, el_mine, tid, sb, st);
-        else beam_sums<64>(a, rowbase, s0, W, d_mine, el_mine, lane, sb, st);
+        if (coop) beam_sums<BEAM_WAVES * 64>(a, rowbase, s0, W, d_mine, el_mine, n, tid, sb, st);
+        else beam_sums<64>(a, rowbase, s0, W, d_mine, el_mine, n, lane, sb, st);
         sb = nbls_wave::sum_f64(sb);
         st = nbls_wave::sum_f64(st);
         if (!coop) {
-            if (lane == 0) beam_store(a, cell, W, bad, sb, st);
+            if (lane == 0) beam_store(a, cell, W, n, bad, sb, st);
             continue;
         }
         if (lane == 0) { red[wave] = sb; red[BEAM_WAVES + wave] = st; }
@@ -134,7 +159,7 @@ __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
         if (tid == 0) {
             sb = (red[0] + red[1]) + (red[2] + red[3]);
             st = (red[BEAM_WAVES] + red[BEAM_WAVES + 1]) + (red[BEAM_WAVES + 2] + red[BEAM_WAVES + 3]);
-            beam_store(a, cell, W, bad, sb, st);
+            beam_store(a, cell, W, n, bad, sb, st);
         }
         __syncthreads();
     }
@@ -159,6 +184,13 @@ hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& s, int64_t u0,
     a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
     a.power = s.d_beam; a.fstat = s.d_beam + cells;
-    hipLaunchKernelGGL(beam_fstat_kernel, dim3((unsigned)((nu + BEAM_WAVES - 1) / BEAM_WAVES)), dim3(BEAM_WAVES * 64), 0, st, a);
+    const dim3 grid((unsigned)((nu + BEAM_WAVES - 1) / BEAM_WAVES)), block(BEAM_WAVES * 64);
+    if (h->kept_beam && &s == &h->est[0]) {                     // the beam of the elements LTS kept (nbls_set_kept_elements)
+        if (a.kept || a.N > 32 || !h->d_kept_mask) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
+        a.dropped = h->d_kept_mask;
+        hipLaunchKernelGGL(beam_fstat_kernel<true>, grid, block, 0, st, a);
+    } else {
+        hipLaunchKernelGGL(beam_fstat_kernel<false>, grid, block, 0, st, a);
+    }
     return hipGetLastError();
 }

@@ -45,6 +45,14 @@
 //              and an event where a pass solves on two streams
 // Both instances run the same function on the same values (the pointer's address space is the compiler's business) and
 // give the same bits; nbls_capon_peak_route_of chooses.
+//
+// A plan that asked for the spectra of the elements LTS kept (nbls_set_kept_elements with NBLS_KEPT_CAPON) runs
+// the KEPT instances.  R is formed and written to csdm for all N elements as above; then, where the unit's dropped mask
+// (kept.hip has written it on the same stream) names an element, the workgroup compacts R_K = R[e_i][e_j] through the place
+// of L (free until the loading) to the head of R, row stride M, and the loading, the Cholesky factor and the grid run with
+// M in the place of N (count and row stride are one value, as in the plain instance) and the steering rows e_i.  The index
+// list e[] lies in LDS and is read wave-uniformly (a broadcast), so the gather of a steering row changes nothing about where
+// y lives.  A unit without a dropped element takes none of this: the same bits as the plain instance.
 #include "nbls_internal.h"
 #include "wave_ops.h"
 #include "refine_fraction.h"
@@ -89,6 +97,8 @@ struct CArgs {
     int32_t* pk_index;        // [2][B][VL][K]
     double* pk_power;         // [2][B][VL][K]
     double* pk_offset;        // [2][B][VL][K][2]
+    // ---- the elements LTS kept (nbls_set_kept_elements): read by the KEPT instances alone ----
+    const uint32_t* dropped;  // [B][VL] bit m set: element m is dropped (kept.hip)
 };
 
 // doubles of the kernel's dynamic LDS without the peak maps (nbls_capon_lds_bytes_of)
@@ -221,15 +231,22 @@ __device__ inline void capon_peaks_of(const CArgs& a, const double* P, int which
     __syncthreads();                                                 // (win_*, cnt_w and sp / sg are free again)
 }
 
+// The KEPT instances' index list e[] (static LDS of those instances alone: its address is a constant, not a register).
+__device__ inline int* capon_kept_index() {
+    __shared__ int kidx[CMAXN];
+    return kidx;
+}
+
 // PK: 0 no peaks (the kernel as it was), 1 the unit's two maps in LDS behind Y, 2 in the unit's slab of HBM
-template <int PK>
+// KEPT: the spectra of the elements LTS kept in this unit
+template <int PK, bool KEPT>
 __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
     // dynamic LDS, sized by N (capon_lds_bytes): Rm [N][N] complex, Lm [N][N] complex, invd [N], then X [CHUNK][N] complex
     // and, in its place once R is there, Y [N][2][THREADS]: the grid phase's vector of every lane
     extern __shared__ __attribute__((aligned(16))) double capon_lds[];
     __shared__ double red_p[CW];
     __shared__ int red_g[CW];
-    const int SN = a.N;                                              // row stride of Rm, Lm and X
+    int SN = a.N;                                                    // row stride of Rm, Lm and X (KEPT: of R_K and its factor, once compacted)
     double* const Rm = capon_lds;
     double* const Lm = Rm + SN * SN * 2;
     double* const invd = Lm + SN * SN * 2;
@@ -310,10 +327,40 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
             a.csdm[(cell * N * N + e) * 2] = Rm[(i * SN + j) * 2];
             a.csdm[(cell * N * N + e) * 2 + 1] = Rm[(i * SN + j) * 2 + 1];
         }
+    int bad_r = any_nan;
+    if constexpr (KEPT) {
+        int* const kidx = capon_kept_index();                        // e_i, the kept elements in ascending order
+        int M;
+        const uint32_t bits = nbls_kept_bits_of(a.dropped[cell], N, M);     // (the same in every thread)
+        if (tid < M) {                                               // the tid-th set bit
+            uint32_t b = bits;
+            for (int i = 0; i < tid; ++i) b &= b - 1;
+            kidx[tid] = __builtin_ctz(b);
+        }
+        __syncthreads();                                             // (and every thread is through with Rm -> csdm)
+        if (M < N) {
+            for (int e = tid; e < M * M; e += CT) {                  // R_K, row stride M, through the place of L ...
+                const int i = e / M, j = e - i * M;
+                const int src = kidx[i] * N + kidx[j];
+                Lm[e * 2] = Rm[src * 2];
+                Lm[e * 2 + 1] = Rm[src * 2 + 1];
+            }
+            __syncthreads();
+            int nan_k = 0;
+            for (int e = tid; e < M * M; e += CT) {                  // ... to the head of R
+                const double re = Lm[e * 2], im = Lm[e * 2 + 1];
+                nan_k |= (re != re) || (im != im);
+                Rm[e * 2] = re;
+                Rm[e * 2 + 1] = im;
+            }
+            bad_r = __syncthreads_or(nan_k);                         // (a NaN entry of R_K; and the barrier behind the writes)
+            SN = M;                                                  // from here on: M elements, rows of M
+        }
+    }
     double t = 0.0;
-    for (int i = 0; i < N; ++i) t += Rm[(i * SN + i) * 2];        // (every thread, the same order)
+    for (int i = 0; i < SN; ++i) t += Rm[(i * SN + i) * 2];       // (every thread, the same order)
     const double nan_ = __builtin_nan("");
-    if (any_nan || t == 0.0 || t != t) {
+    if (bad_r || t == 0.0 || t != t) {
         if (a.map)
             for (int g = tid; g < G; g += CT) { a.map[cell * G + g] = nan_; a.map[(a.cells + cell) * G + g] = nan_; }
         if (tid == 0) {
@@ -324,15 +371,15 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
         return;
     }
     // R' = R + delta (t / N) I, then its Cholesky factor column by column
-    const double lam = a.loading * (t / (double)N);
-    for (int e = tid; e < N * N; e += CT) {
-        const int i = e / N, j = e - i * N;
+    const double lam = a.loading * (t / (double)SN);
+    for (int e = tid; e < SN * SN; e += CT) {
+        const int i = e / SN, j = e - i * SN;
         Lm[(i * SN + j) * 2] = Rm[(i * SN + j) * 2] + (i == j ? lam : 0.0);
         Lm[(i * SN + j) * 2 + 1] = Rm[(i * SN + j) * 2 + 1];
     }
     __syncthreads();
     bool chol_ok = true;
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < SN; ++j) {
         double d = Lm[(j * SN + j) * 2];
         for (int k = 0; k < j; ++k) {
             const double lr = Lm[(j * SN + k) * 2], li = Lm[(j * SN + k) * 2 + 1];
@@ -342,7 +389,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
         if (!(d > 0.0)) { chol_ok = false; break; }                  // (the same d in every thread)
         const double ljj = sqrt(d);
         if (tid == j) invd[j] = 1.0 / ljj;
-        if (tid > j && tid < N) {
+        if (tid > j && tid < SN) {
             double sr = Lm[(tid * SN + j) * 2], si = Lm[(tid * SN + j) * 2 + 1];
             for (int k = 0; k < j; ++k) {                            // L_ik conj(L_jk)
                 const double ar = Lm[(tid * SN + k) * 2], ai = Lm[(tid * SN + k) * 2 + 1];
@@ -362,7 +409,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
     const double2* R2 = (const double2*)Rm;
     const double2* L2 = (const double2*)Lm;
     double* const yr = Y + tid;                                      // y_i = (yr[i * 2 CT], yr[i * 2 CT + CT])
-    const double nn = (double)N * (double)N;
+    const double nn = (double)SN * (double)SN;
     double bc = 0.0, bb = 0.0;
     int gc = -1, gb = -1;
     // with peaks: where the unit's two spectra stay until they are picked
@@ -376,13 +423,15 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
         mb = a.map ? a.map + (a.cells + cell) * G : mc + G;
     }
     for (int g = tid; g < G; g += CT) {
-        for (int i = 0; i < N; ++i) {
-            const double2 v = steer[(int64_t)i * G + g];
+        for (int i = 0; i < SN; ++i) {
+            int er = i;                                              // the element's row of the steering table
+            if constexpr (KEPT) er = capon_kept_index()[i];          // (a wave-uniform LDS read)
+            const double2 v = steer[(int64_t)er * G + g];
             yr[i * 2 * CT] = v.x; yr[i * 2 * CT + CT] = v.y;
         }
         // Bartlett: sum_i R_ii |a_i|^2 + 2 Re(conj(a_i) sum_{j<i} R_ij a_j)
         double pb = 0.0;
-        for (int i = 0; i < N; ++i) {
+        for (int i = 0; i < SN; ++i) {
             double ur = 0.0, ui = 0.0;
             for (int j = 0; j < i; ++j) {
                 const double2 r = R2[i * SN + j];
@@ -401,7 +450,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
         double pc = nan_;
         if (chol_ok) {
             double q = 0.0;
-            for (int i = 0; i < N; ++i) {
+            for (int i = 0; i < SN; ++i) {
                 double sr = yr[i * 2 * CT], si = yr[i * 2 * CT + CT];
                 for (int j = 0; j < i; ++j) {
                     const double2 l = L2[i * SN + j];
@@ -536,6 +585,28 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
     a.map = h->capon_maps ? h->d_capon_map.p : nullptr;
     a.csdm = h->capon_csdm ? h->d_capon_csdm.p : nullptr;
     const size_t lds = nbls_capon_lds_bytes_of(h->nelem);
+    const bool kept = h->kept_capon;       // the spectra of the elements LTS kept (nbls_set_kept_elements): the KEPT instances
+    if (kept) {
+        if (!h->d_kept_mask) return hipErrorInvalidValue;                // (nbls_plan has refused such a plan)
+        a.dropped = h->d_kept_mask;
+    }
+    // instance PK of the plan, given its dynamic LDS limit `limit` once per handle
+    const auto instance = [&](int pk, int limit, const void** fn) -> hipError_t {
+        static const void* const table[2][3] = {
+            {(const void*)capon_kernel<0, false>, (const void*)capon_kernel<1, false>, (const void*)capon_kernel<2, false>},
+            {(const void*)capon_kernel<0, true>, (const void*)capon_kernel<1, true>, (const void*)capon_kernel<2, true>}};
+        *fn = table[kept][pk];
+        bool& set = kept ? h->capon_kept_attr_set[pk] : (pk == 0 ? h->capon_attr_set : h->capon_peak_attr_set[pk - 1]);
+        if (set) return hipSuccess;
+        const hipError_t e = hipFuncSetAttribute(*fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+        if (e == hipSuccess) set = true;
+        return e;
+    };
+    const auto run = [&](const void* fn, unsigned nblocks, size_t shm) -> hipError_t {
+        void* params[] = {(void*)&a};
+        return hipLaunchKernel(fn, dim3(nblocks), dim3(CT), params, shm, st);
+    };
+    const void* fn = nullptr;
     if (h->capon_peaks > 0) {              // a plan with a peak request (nbls_set_capon_peaks)
         a.nbr = h->d_capon_nbr; a.pk = h->capon_peaks; a.pfloor = h->capon_peak_floor;
         a.pk_count = h->d_capon_peak_count; a.pk_index = h->d_capon_peak_index;
@@ -543,20 +614,13 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
         if (h->capon_peak_route == 1) {
             const size_t plds = nbls_capon_peak_lds_bytes_of(h->nelem, h->capon_n);
             if (!plds) return hipErrorInvalidValue;                      // (nbls_plan has refused such a plan)
-            if (!h->capon_peak_attr_set[0]) {
-                const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         160 * 1024 - 1024);
-                if (e != hipSuccess) return e;
-                h->capon_peak_attr_set[0] = true;
-            }
-            hipLaunchKernelGGL(capon_kernel<1>, dim3((unsigned)nu), dim3(CT), plds, st, a);
-            return hipGetLastError();
-        }
-        if (!h->capon_peak_attr_set[1]) {
-            const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)nbls_capon_lds_bytes_of(CMAXN));
+            const hipError_t e = instance(1, 160 * 1024 - 1024, &fn);
             if (e != hipSuccess) return e;
-            h->capon_peak_attr_set[1] = true;
+            return run(fn, (unsigned)nu, plds);
+        }
+        {
+            const hipError_t e = instance(2, (int)nbls_capon_lds_bytes_of(CMAXN), &fn);
+            if (e != hipSuccess) return e;
         }
         // the maps of a unit lie in its own rows of d_capon_map where the plan keeps them; else in the slab of its
         // workgroup: at most capon_peak_slabs workgroups per launch.  On one stream its order hands the slabs on; the
@@ -577,8 +641,7 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
         for (int64_t o = 0; o < nu; o += step) {
             a.u0 = (int)(u0 + o);
             a.nunits = (int)(nu - o < step ? nu - o : step);
-            hipLaunchKernelGGL(capon_kernel<2>, dim3((unsigned)a.nunits), dim3(CT), lds, st, a);
-            const hipError_t e = hipGetLastError();
+            const hipError_t e = run(fn, (unsigned)a.nunits, lds);
             if (e != hipSuccess) return e;
         }
         if (a.slab) {
@@ -588,12 +651,7 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
         }
         return hipSuccess;
     }
-    if (!h->capon_attr_set) {              // once per handle (a streamed pass launches per unit batch)
-        const hipError_t e = hipFuncSetAttribute((const void*)capon_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)nbls_capon_lds_bytes_of(CMAXN));
-        if (e != hipSuccess) return e;
-        h->capon_attr_set = true;
-    }
-    hipLaunchKernelGGL(capon_kernel<0>, dim3((unsigned)nu), dim3(CT), lds, st, a);
-    return hipGetLastError();
+    const hipError_t e = instance(0, (int)nbls_capon_lds_bytes_of(CMAXN), &fn);      // once per handle (a streamed pass launches per unit batch)
+    if (e != hipSuccess) return e;
+    return run(fn, (unsigned)nu, lds);
 }

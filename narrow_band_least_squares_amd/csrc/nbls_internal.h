@@ -215,6 +215,14 @@ struct nbls_handle {
     dev_buf<int32_t> d_capon_peak_index;    // [2][B][VL][K]
     dev_buf<double> d_capon_peak_power;     // [2][B][VL][K]
     dev_buf<double> d_capon_peak_offset;    // [2][B][VL][K][2]
+    // ---- the elements LTS kept (nbls_set_kept_elements, kept.hip) ----
+    int want_kept_q = 0, want_kept_flags = 0;   // nbls_set_kept_elements: read by the next nbls_plan (q == 0: off)
+    int kept_q = 0;                 // min_pairs of the plan (0: the plan does not ask)
+    bool kept_beam = false, kept_capon = false;     // the plan's beam / spectra are those of the kept elements
+    bool kept_valid = false;        // a pass of this plan has run the solve stage: the mask and the count are there
+    bool capon_kept_attr_set[3] = {false, false, false};    // the KEPT instances of capon_kernel have their dynamic LDS limit
+    dev_buf<uint32_t> d_kept_mask;  // [B][VL] bit m: element m is dropped
+    dev_buf<int32_t> d_kept_count;  // [B][VL] M
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -367,6 +375,17 @@ size_t nbls_refine_lds_bytes_of(int nelem, int W);
 hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // closure of the picked lags of units [u0, u0 + nu), per window and per element of estimator x (closure.hip)
 hipError_t nbls_launch_closure(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
+// the elements LTS dropped in units [u0, u0 + nu), from estimator 0's unpacked weights (kept.hip)
+hipError_t nbls_launch_kept_elements(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// The kept set of a unit from its dropped mask (nbls_set_kept_elements): the complement among N elements, or the whole
+// array where fewer than 3 would remain.  -> the kept bits; M is their count.
+__host__ __device__ inline uint32_t nbls_kept_bits_of(uint32_t dropped, int N, int& M) {
+    const uint32_t all = N >= 32 ? 0xffffffffu : ((1u << N) - 1u);
+    uint32_t kept = ~dropped & all;
+    M = __builtin_popcount(kept);
+    if (M < 3) { kept = all; M = N; }
+    return kept;
+}
 // slowness-grid search of the beam F-statistic over units [u0, u0 + nu) for the plan's full array (beam_grid.hip)
 hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 // dynamic LDS bytes of the form beam_grid_kernel takes for windows of W samples of nelem elements and a halo of `halo`

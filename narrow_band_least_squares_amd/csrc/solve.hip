@@ -1434,6 +1434,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         hipLaunchKernelGGL(uncertainty_kernel, dim3((unsigned)((nu + 63) / 64)), dim3(64), 0, st, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    // the elements LTS dropped (nbls_set_kept_elements): from the plan's own estimator's weights, ahead of what may read them
+    if (h->kept_q > 0 && &s == &h->est[0] && (e = nbls_launch_kept_elements(h, u0, nu, st)) != hipSuccess) return e;
     if (h->beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
     if (h->closure && s.d_closure && (e = nbls_launch_closure(h, s, u0, nu, st)) != hipSuccess) return e;
     // the slowness-grid search of a plan that asked for one: the full array only, behind the plan's own estimator (a plan

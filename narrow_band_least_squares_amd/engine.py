@@ -363,7 +363,8 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
-               want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0):
+               want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
+               want_kept=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
@@ -374,7 +375,9 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     ``bartlett_power`` of the Capon spectra over that many points, with ``want_capon_maps`` ``capon_map`` / ``bartlett_map``
     (nbands, vector_len, capon_points) and with ``want_capon_csdm`` ``capon_csdm`` (nbands, vector_len, nchans, nchans)
     complex; with ``capon_peaks`` = K > 0 ``capon_peak_count`` (nbands, vector_len) int32, ``capon_peak_index`` (.., K) int32,
-    ``capon_peak_power`` (.., K), ``capon_peak_offset`` (.., K, 2) and the same four with ``bartlett_``; None otherwise."""
+    ``capon_peak_power`` (.., K), ``capon_peak_offset`` (.., K, 2) and the same four with ``bartlett_``; ``want_kept``:
+    ``dropped_mask`` (nbands, vector_len) uint32 and ``kept_count`` (nbands, vector_len) int32, the elements LTS dropped;
+    None otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
     K = int(capon_peaks) if capon_points else 0
     peaks = {}
@@ -406,6 +409,8 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      capon_map=cpm[0], bartlett_map=cpm[1],
                      capon_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128)
                      if (capon_points and want_capon_csdm) else None,
+                     dropped_mask=np.zeros((nb, vector_len), dtype=np.uint32) if want_kept else None,
+                     kept_count=np.zeros((nb, vector_len), dtype=np.int32) if want_kept else None,
                      lts=alpha < 1.0, fs=fs, **peaks)
 
 
@@ -615,7 +620,8 @@ def upload_trace(h, data, fs):
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None):
+           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
+           kept=None):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -634,7 +640,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     also computes the closure of the picked lags behind every solve (``Handle.set_closure``; likewise).  ``capon``: a dict
     of ``Handle.set_capon``'s arguments, ``freqs`` / ``snap_len`` / ``snap_hop`` one per band of the Prep: the plan also
     computes the Capon spectra of its bands (likewise); with ``peaks`` = K > 0 in it also their K strongest peaks on the
-    lattice ``peak_cells`` above ``peak_floor`` (``Handle.set_capon_peaks``; likewise)."""
+    lattice ``peak_cells`` above ``peak_floor`` (``Handle.set_capon_peaks``; likewise).  ``kept``: ``(min_pairs, beam,
+    capon)`` of ``Handle.set_kept_elements``: the plan also names the elements LTS dropped and forms its beam results / Capon
+    spectra over the kept ones (likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -668,6 +676,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_lag_seed(lag_seed)
     peaks = 0
     try:
+        if kept is not None:
+            h.set_kept_elements(*kept)
         if capon is not None:            # (inside the try: whatever one of the two refuses, the shared handle keeps neither)
             capon = dict(capon)
             peaks, cells, floor = capon.pop('peaks', 0), capon.pop('peak_cells', None), capon.pop('peak_floor', 0.25)
@@ -693,6 +703,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon(None)
         if peaks:
             h.set_capon_peaks(None)
+        if kept is not None:
+            h.set_kept_elements(0)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -827,6 +839,8 @@ def collect(res, h, b0, b1, streamed, note):
         for which, name in enumerate(('capon', 'bartlett')):
             for field, a in zip(PEAK_FIELDS, h.fetch_capon_peaks(which)):
                 getattr(res, name + field)[b0:b1] = a
+    if res.dropped_mask is not None:
+        res.dropped_mask[b0:b1], res.kept_count[b0:b1] = h.fetch_kept_elements()
     if not live:
         note.bands(b0, b1)
 
@@ -929,6 +943,23 @@ def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading
     return out
 
 
+def _check_kept(nchans, kept, want_beam, capon):
+    """``kept`` of ``process`` / ``process_batch`` — None or ``(min_pairs, beam, capon)`` — -> the ``kept`` tuple of ``launch`` or
+    None; ``ValueError`` before any GPU work (``planner.check_kept``, and a flag whose results the call does not ask for)."""
+    if kept is None:
+        return None
+    try:
+        q, kb, kc = kept
+    except (TypeError, ValueError):
+        raise ValueError('kept must be (min_pairs, beam, capon), not %r' % (kept,))
+    q, kb, kc = planner.check_kept(nchans, q, kb, kc)
+    if kb and not want_beam:
+        raise ValueError('kept: the beam of the kept elements needs want_beam')
+    if kc and capon is None:
+        raise ValueError('kept: the Capon spectra of the kept elements need capon_grid')
+    return q, kb, kc
+
+
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
@@ -936,7 +967,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None):
+            capon_peak_floor=0.25, capon_cells=None, kept=None):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -984,6 +1015,12 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     (``nbls_set_capon_peaks``).  ``capon_cells`` (G, 2) int: the lattice coordinates of the grid points, by
     default ``planner.grid_cells(capon_grid)[0]``.  ``ValueError`` before any GPU work (``planner.check_capon_peaks``);
     ``process_segmented`` refuses it with the spectra.
+    kept = (min_pairs, beam, capon): also ``res.dropped_mask`` (nbands, vector_len) uint32, bit m set where FAST-LTS has taken
+    the weight of at least ``min_pairs`` (None: all N - 1) of element m's pairs in that window, and ``res.kept_count`` int32;
+    with ``beam`` (needs ``want_beam``) ``res.beam_power`` / ``res.fstat`` and with ``capon`` (needs ``capon_grid``) the
+    spectra, their maxima, maps and peaks are those of the elements that are not dropped — the whole array where fewer
+    than 3 would remain (``nbls_set_kept_elements``).  ``ValueError`` before any GPU work
+    (``planner.check_kept``); ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -1010,6 +1047,10 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
                          None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0],
                          capon_peaks, capon_peak_floor, capon_cells)
+    kept = _check_kept(nchans, kept, want_beam, capon)
+    if cap < 1 and not prefiltered and kept is not None:
+        raise ValueError('kept: a trace of %d x %d samples takes the time-segmented path (not even one filtered band fits the '
+                         'HBM budget of a pass, NBLS_MAX_FILTERED_GB): the kept elements are not available there' % (nchans, npts))
     if cap < 1 and not prefiltered and capon is not None:
         raise ValueError('capon_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -1027,14 +1068,14 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
                          0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
-                         0 if capon is None else capon.get('peaks', 0))
+                         0 if capon is None else capon.get('peaks', 0), kept is not None)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon)
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept)
     finally:
         if up is not None:
             up.close()
@@ -1263,7 +1304,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_beam=False,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
-                  want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None):
+                  want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
+                  kept=None):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1287,6 +1329,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                          prep.W, capon_peaks, capon_peak_floor, capon_cells)
     CG = 0 if capon is None else len(capon['grid'])
     CK = 0 if capon is None else capon.get('peaks', 0)
+    kept = _check_kept(nchans, kept, want_beam, capon)
     limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
     per_sub = S if max_bands_per_pass(S * nchans, npts) >= 1 else max_bands_per_pass(nchans, npts)
     if per_sub < 1:
@@ -1294,7 +1337,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                          'process it on its own' % (nchans, npts))
     out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
                       grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
-                      want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK)
+                      want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK,
+                      want_kept=kept is not None)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1310,7 +1354,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon)
+                       closure=bool(want_consistency), capon=capon, kept=kept)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
@@ -1325,6 +1369,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 cpmap = [a.reshape(b1 - b0, k, VL, CG) for a in h.fetch_capon_maps()] if (CG and want_capon_maps) else None
                 cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
                 cpk = [[a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_peaks(which)] for which in (0, 1)] if CK else None
+                kel = [a.reshape(b1 - b0, k, VL) for a in h.fetch_kept_elements()] if kept is not None else None
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
@@ -1349,6 +1394,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                         for which, name in enumerate(('capon', 'bartlett')):
                             for field, a in zip(PEAK_FIELDS, cpk[which]):
                                 getattr(res, name + field)[b0:b1] = a[:, j]
+                    if kel is not None:
+                        res.dropped_mask[b0:b1], res.kept_count[b0:b1] = [a[:, j] for a in kel]
     finally:
         h.set_segments(1)
     for res, t0 in zip(out, t0s):

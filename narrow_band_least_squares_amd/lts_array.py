@@ -418,3 +418,95 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
         out.append((_returns_beam if beam else _returns)(res, res.nchans, alpha, keys.get(id(res.t))) +
                    (_returns_consistency(res) if consistency else ()))
     return out
+
+
+def _returns_kept(res, nchans, beam, capon_kw, band=0, n=None):
+    """A band's kept-element results as a dict: ``dropped_elements`` (bool, one column per element, from the bits of the
+    mask), ``kept_count`` and, where the pass formed them, ``beam_power`` / ``fstat`` and the fields of ``_returns_capon``
+    (csrc/kept.hip, csrc/beam.hip, csrc/capon.hip).  ``band`` / ``n`` as for ``_returns_capon``."""
+    sl = slice(None) if n is None else slice(0, n)
+    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    mask = pick(res.dropped_mask)
+    out = dict(dropped_elements=((mask[..., None] >> np.arange(nchans, dtype=np.uint32)) & 1).astype(bool),
+               kept_count=pick(res.kept_count))
+    if beam:
+        out['beam_power'], out['fstat'] = pick(res.beam_power), pick(res.fstat)
+    if capon_kw:
+        out.update(_returns_capon(res, capon_kw['capon_grid'], capon_kw['want_capon_maps'], band=band, n=n))
+    return out
+
+
+def _kept_keywords(nchans, rij, fs, W, min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor):
+    """The keywords of ``engine.process`` behind the arguments of ``ltsva_kept`` for one filtered band of window length ``W``
+    samples -> (keywords, Capon keywords or {}).  ``ValueError`` before any GPU work."""
+    if slowness_grid is None and (freq is not None or snapshots is not None or maps or peaks):
+        raise ValueError('freq, snapshots, maps and peaks need slowness_grid')
+    if slowness_grid is not None and freq is None:
+        raise ValueError('slowness_grid needs freq, the frequency in Hz at which the spectra are formed')
+    q, kb, kc = planner.check_kept(nchans, min_pairs, beam, slowness_grid is not None)
+    ckw = {} if slowness_grid is None else _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading, maps,
+                                                            peaks, peak_floor)
+    return dict(ckw, want_beam=kb, kept=(q, kb, kc)), ckw
+
+
+def ltsva_kept(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, min_pairs=None, beam=True,
+               slowness_grid=None, freq=None, snapshots=None, loading=0.01, maps=False, peaks=0, peak_floor=0.25):
+    """``ltsva`` followed by the results of the elements FAST-LTS kept: per window, an element at least ``min_pairs`` of
+    whose N - 1 pairs have lost their weight (default: all of them) counts as dropped, and the beam of ``ltsva_beam``
+    (``beam=True``) and, with ``slowness_grid`` (G, 2) s/km and ``freq`` Hz, the Capon and Bartlett spectra of ``ltsva_capon``
+    (its keywords ``snapshots``, ``loading``, ``maps``, ``peaks``, ``peak_floor``) are formed over the other elements — the
+    whole array where fewer than 3 would remain (DESIGN.md section 20 has the definition and the counts).  A mistimed element
+    costs the full-array beam its F and makes the full-array Capon beamformer null the signal itself; without the element
+    both recover.  Returns ``ltsva``'s 8-tuple followed by one dict: ``dropped_elements`` (nwin, N) bool, ``kept_count``
+    (nwin,) int32, with ``beam`` ``beam_power`` / ``fstat`` (nwin,), with the grid the fields of ``ltsva_capon``'s dict.  With
+    ``alpha == 1.0`` nothing is dropped and every field is that of ``ltsva_beam`` / ``ltsva_capon``.  All of it is computed on
+    the GPU behind each window's solve (csrc/kept.hip).  Whatever the library would refuse raises ``ValueError`` before any
+    GPU work."""
+    _check_elements_strict(len(st), alpha)
+    nchans = len(st)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    data, fs, t0 = engine.stream_rows(st)
+    W = planner.window_plan(len(data[0]), fs, window_length, window_overlap)[0]
+    kw, ckw = _kept_keywords(nchans, rij, fs, int(W), min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks,
+                             peak_floor)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, **kw)
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (
+        _returns_kept(res, nchans, kw['want_beam'], ckw, n=int(res.nwin[0])),)
+
+
+def ltsva_kept_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, min_pairs=None,
+                     beam=True, slowness_grid=None, freq=None, snapshots=None, loading=0.01, maps=False, peaks=0,
+                     peak_floor=0.25):
+    """``ltsva_kept`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
+    element i equal to ``ltsva_kept(streams[i], ...)``; the streams as for ``ltsva_batch``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
+    kw, ckw = _kept_keywords(nchans, rij, fs, int(W), min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks,
+                             peak_floor)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_kept(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, min_pairs, beam,
+                           slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)]
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, **kw)
+    return [_returns(res, nchans, alpha) + (_returns_kept(res, nchans, kw['want_beam'], ckw, n=int(res.nwin[0])),)
+            for res in results]

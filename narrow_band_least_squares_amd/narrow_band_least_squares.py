@@ -15,7 +15,7 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
-from .lts_array import grid_slowness, _returns_capon, _peak_keywords
+from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -322,30 +322,85 @@ def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     if not (0.5 <= ALPHA <= 1.0):
         raise ValueError('ALPHA must be in [0.5, 1.0].')
     bands = list(range(NBANDS))
+    keywords = _capon_band_keywords(len(st), grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER, vector_len)
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
+    out = _zero_padded_capon(_returns_capon(res, grid, bool(maps), band=None), res, bool(peak_kw))
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (out,)
 
+
+def _capon_band_keywords(nchans, grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER, vector_len):
+    """The ``capon`` callable of ``_run_bands`` behind the Capon arguments of a narrow-band call: the Capon keywords of
+    ``engine.process`` for the call's bands, their frequencies and snapshots defaulted and checked."""
     def keywords(rij_used, fs, npts, edges, winlens):
         W = engine.plan_windows(npts, fs, winlens, WINOVER, vector_len)[0]
         f = planner.capon_frequencies(edges) if capon_freqs is None else capon_freqs
         snaps = snapshots
         if snaps is None:
-            f = planner.check_capon(len(st), grid, f, (1, 1), loading, W)[1]
+            f = planner.check_capon(nchans, grid, f, (1, 1), loading, W)[1]
             snaps = planner.capon_snapshots(planner.co_array(rij_used)[0], grid, fs, f, W)
-        planner.check_capon(len(st), grid, f, snaps, loading, W, bool(maps))
+        planner.check_capon(nchans, grid, f, snaps, loading, W, bool(maps))
         return dict(capon_grid=grid, capon_freqs=f, capon_snapshots=snaps, capon_loading=loading, want_capon_maps=bool(maps),
                     **peak_kw)
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
-    out = _returns_capon(res, grid, bool(maps), band=None)
+    return keywords
+
+
+def _zero_padded_capon(out, res, with_peaks):
+    """The derived slowness fields of ``_returns_capon``'s dict, zero beyond a band's windows like ``vel_array``."""
     computed = np.arange(res.capon_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
     for k in ('capon_vel', 'capon_baz', 'bartlett_vel', 'bartlett_baz'):
-        out[k] = np.where(computed, out[k], 0.0)                     # (zero-padded like vel_array)
-    if peak_kw:
+        out[k] = np.where(computed, out[k], 0.0)
+    if with_peaks:
         for which in ('capon', 'bartlett'):
             for k in ('_peak_vel', '_peak_baz'):
                 out[which + k] = np.where(computed[..., None], out[which + k], 0.0)
             out[which + '_peak_slowness'] = np.where(computed[..., None, None], out[which + '_peak_slowness'], 0.0)
+    return out
+
+
+def narrow_band_least_squares_kept(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                   FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                   min_pairs=None, beam=True, slowness_grid=None, capon_freqs=None, snapshots=None,
+                                   loading=0.01, maps=False, peaks=0, peak_floor=0.25):
+    """``narrow_band_least_squares`` followed by the results of the elements FAST-LTS kept in every band and window
+    (``lts_array.ltsva_kept``): an element at least ``min_pairs`` of whose N - 1 pairs have lost their
+    weight (default: all of them) counts as dropped, and the beam of ``narrow_band_least_squares_beam`` (``beam=True``) and,
+    with ``slowness_grid``, the spectra of ``narrow_band_least_squares_capon`` (its keywords) are formed over the other
+    elements.  Returns the nine values of ``narrow_band_least_squares`` followed by one dict: ``dropped_elements`` (NBANDS,
+    vector_len, N) bool, ``kept_count`` (NBANDS, vector_len) int32, with ``beam`` ``beam_power`` / ``fstat``, with the grid
+    the fields of ``narrow_band_least_squares_capon``'s dict; zeros beyond a band's windows.  Whatever the library would
+    refuse raises ``ValueError`` before any GPU work, and so does a trace so long that not one filtered band fits the HBM
+    budget of a pass."""
+    grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
+    if grid is None and (capon_freqs is not None or snapshots is not None or maps or peaks):
+        raise ValueError('capon_freqs, snapshots, maps and peaks need slowness_grid')
+    if not isinstance(maps, (bool, np.bool_)):
+        raise ValueError('maps must be True or False, not %r' % (maps,))
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
+        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
+                         'squares' % len(st))
+    kept = planner.check_kept(len(st), min_pairs, beam, grid is not None)
+    peak_kw = {} if grid is None else _peak_keywords(grid, peaks, peak_floor)
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    bands = list(range(NBANDS))
+    capon_kw = None if grid is None else _capon_band_keywords(len(st), grid, capon_freqs, snapshots, loading, maps, peak_kw,
+                                                              WINOVER, vector_len)
+
+    def keywords(*args):           # (the keywords that ride beside the Capon ones into ``engine.process``)
+        return dict({} if capon_kw is None else capon_kw(*args), kept=kept)
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=kept[1], capon=keywords)
+    out = _returns_kept(res, len(st), kept[1], None, band=None)
+    if grid is not None:
+        out.update(_zero_padded_capon(_returns_capon(res, grid, bool(maps), band=None), res, bool(peak_kw)))
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (out,)
 

@@ -701,3 +701,28 @@ def check_capon_peaks(grid_len, cells, K, floor):
     if len(np.unique(c[:, 0] * MAX_CAPON_CELL + c[:, 1])) != len(c):
         raise ValueError('two points share one lattice cell')
     return np.ascontiguousarray(c, dtype=np.int32), int(K), float(floor)
+
+
+MAX_KEPT_ELEMENTS = 32    # elements of a plan that names the dropped ones: one bit each of a uint32 (csrc/kept.hip)
+
+
+def check_kept(nchans, min_pairs=None, beam=True, capon=False):
+    """Everything ``nbls_set_kept_elements`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (min_pairs
+    int, beam bool, capon bool).  ``nchans``: the elements N of the array; ``min_pairs`` q: an element counts as dropped by
+    LTS when at least q of its N - 1 pairs have lost their weight, None: N - 1, all of them.  ``beam`` /
+    ``capon``: the beam results / the Capon spectra are formed over the kept elements."""
+    if isinstance(nchans, (bool, np.bool_)) or not isinstance(nchans, (int, np.integer)):
+        raise ValueError('the element count must be an integer, not %r' % (nchans,))
+    n = int(nchans)
+    if n < 3 or n > MAX_KEPT_ELEMENTS:
+        raise ValueError('%d array elements: the kept elements are worked out for 3..%d' % (n, MAX_KEPT_ELEMENTS))
+    for name, flag in (('beam', beam), ('capon', capon)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError('%s must be True or False, not %r' % (name, flag))
+    if min_pairs is None:
+        min_pairs = n - 1
+    if isinstance(min_pairs, (bool, np.bool_)) or not isinstance(min_pairs, (int, np.integer)):
+        raise ValueError('min_pairs must be an integer in 1..%d, not %r' % (n - 1, min_pairs))
+    if not (1 <= int(min_pairs) <= n - 1):
+        raise ValueError('min_pairs must lie in 1..%d (an element of %d has %d pairs), not %r' % (n - 1, n, n - 1, min_pairs))
+    return int(min_pairs), bool(beam), bool(capon)
