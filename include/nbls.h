@@ -571,6 +571,49 @@ int nbls_fetch_capon_peaks(nbls_handle* h, int32_t which /* 0 Capon, 1 Bartlett 
 int nbls_set_kept_elements(nbls_handle* h, int32_t min_pairs, int32_t flags);
 int nbls_fetch_kept_elements(nbls_handle* h, uint32_t* dropped_mask, int32_t* kept_count);
 
+/* ---- The beam trace at the windows' solved slowness ----
+ * The pass describes every window (slowness, MdCCM, beam power, F ...); on request it also returns the waveform those
+ * numbers describe: per result row one trace [npts], the delay-and-sum beam steered window by window at the slowness the
+ * window solved, the overlapping windows stitched with a synthesis window.  For estimator 0, result row r (band b; with
+ * segments r = b * nseg + s), N elements, window length W, hop inc, nwin[r] windows, the synthesis window g_b[0..W) of the
+ * request's table, and M_w the kept count of window w (N without NBLS_BEAM_TRACE_KEPT).  For window w, s0 = w * inc, z the
+ * solved slowness of its cell:
+ *   delays   d_0 = 0, d_m = rint(fs * (xij[m-1][0] * z0 + xij[m-1][1] * z1)) for m > 0, ties to even; row m - 1 of the
+ *            geometry is pair (0, m).  The delays are ALWAYS those against element 0's position, also where the kept set
+ *            does not hold element 0: that takes the geometry alone, not element 0's samples.  NBLS_KEPT_BEAM re-references
+ *            to the first kept element e_0; the trace does not, on purpose: consecutive windows of a stitched trace must
+ *            share one time base.
+ *   usable   window w is usable iff w < nwin[r], z0 and z1 are finite, |fs * (xij[m-1] . z)| < 2^30 for every m in 1..N-1
+ *            (of the whole array) and, with the gate on, mdccm[cell] >= mdccm_min (a NaN MdCCM fails the gate).  The gate
+ *            is off iff mdccm_min is NaN.
+ *   elements all N; with NBLS_BEAM_TRACE_KEPT the kept set of nbls_set_kept_elements (bit m of dropped_mask[cell] clear,
+ *            the whole array where fewer than 3 would remain), M_w = kept_count[cell].
+ *   sum      s_w[t] = ((0.0 + x_a) + x_b) + ... over the set's elements in ascending m, x_m = filt[row of m][s0 + t + d_m],
+ *            0.0 where the index is outside [0, npts): the padding up to npts_pad is never read as data.
+ *   sample   n in [0, npts), over the usable windows with 0 <= n - s0 < W in ascending w, both sums from 0.0:
+ *            acc = sum_w g_b[n - s0] * s_w[n - s0],  den = sum_w g_b[n - s0] * M_w,
+ *            trace[r][n] = acc / den if den > 0, else 0.0.  One division per sample; a NaN sample read propagates.
+ * Built without FMA contraction, no atomics; every order depends on (N, the kept set, W, inc) alone: single, streamed,
+ * batched (nbls_set_segments) and band-round passes give the same bits, and the expression is a fixed sequence of IEEE
+ * operations that NumPy float64 restates (tests/beam_trace_truth.py).  Full, bounded, seeded, refined, grid, Capon and
+ * closure plans are accepted; the delays are the whole-sample ones of z in every case.
+ *   nbls_set_beam_trace(h, window, nwindow, mdccm_min, flags)   read by the next nbls_plan.  window: the synthesis windows
+ *                            of the plan's bands one after the other, sum_b W_b = nwindow doubles; NULL switches it off (the
+ *                            default: such a plan launches exactly what it launched before).  flags: NBLS_BEAM_TRACE_KEPT.
+ *                            NBLS_ERR_ARG, the handle unchanged, for a negative nwindow or unknown flags.  nbls_plan returns
+ *                            NBLS_ERR_ARG if nwindow != sum_b W_b, an entry is negative or not finite or a band's window
+ *                            is all zero, NBLS_ERR_STATE for NBLS_BEAM_TRACE_KEPT without nbls_set_kept_elements or a
+ *                            geometry whose rows 0..N-2 are not the pairs (0, m), NBLS_ERR_UNSUPPORTED with
+ *                            nbls_set_window_ranges, nbls_set_estimators or an RCCL communicator.
+ *   nbls_fetch_beam_trace(h, row, out)   out[npts] of result row `row`; waits for the pass as nbls_fetch_beam does.
+ *                            NBLS_ERR_STATE if the plan did not ask, NBLS_ERR_ARG for a bad row.  Zeros until a pass of
+ *                            this plan has run the solve stage; a later pass without it leaves the trace as it is.
+ * One launch per pass, behind the last solve; streamed result batches do not carry the trace. */
+#define NBLS_BEAM_TRACE_KEPT 1
+int nbls_set_beam_trace(nbls_handle* h, const double* window /* concatenated per band; NULL = off */, int64_t nwindow,
+                        double mdccm_min, int32_t flags);
+int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out /* [npts] */);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -33,6 +33,7 @@ EXPORTS = [
     'nbls_set_capon', 'nbls_fetch_capon', 'nbls_fetch_capon_maps', 'nbls_fetch_capon_csdm', 'nbls_fetch_capon_tables',
     'nbls_set_capon_peaks', 'nbls_fetch_capon_peaks',
     'nbls_set_kept_elements', 'nbls_fetch_kept_elements',
+    'nbls_set_beam_trace', 'nbls_fetch_beam_trace',
 ]
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
@@ -43,6 +44,7 @@ CAPON_CHUNK = 32         # snapshots that go through LDS together (NBLS_CAPON_CH
 CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
 CAPON_PEAKS_MAX = 8      # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
 KEPT_BEAM, KEPT_CAPON = 1, 2      # flags of nbls_set_kept_elements
+BEAM_TRACE_KEPT = 1      # flag of nbls_set_beam_trace
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -186,6 +188,8 @@ def load_library(path=None):
     lib.nbls_fetch_capon_peaks.argtypes = [vp, C.c_int32, ip, ip, dp, dp]
     lib.nbls_set_kept_elements.argtypes = [vp, C.c_int32, C.c_int32]
     lib.nbls_fetch_kept_elements.argtypes = [vp, C.POINTER(C.c_uint32), ip]
+    lib.nbls_set_beam_trace.argtypes = [vp, dp, C.c_int64, C.c_double, C.c_int32]
+    lib.nbls_fetch_beam_trace.argtypes = [vp, C.c_int32, dp]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -579,6 +583,25 @@ class Handle:
         self._chk(self.lib.nbls_fetch_kept_elements(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                     count.ctypes.data_as(C.POINTER(C.c_int32))))
         return mask, count
+
+    def set_beam_trace(self, window=None, mdccm_min=None, kept=False):
+        """The next plans also form, behind the pass's last solve, the beam trace of every result row: the delay-and-sum
+        beam at each window's solved slowness, the windows stitched with the synthesis windows ``window`` — those of the
+        plan's bands one after the other, sum of the window lengths entries (``planner.beam_trace_window`` makes one) —
+        using only the windows with MdCCM >= ``mdccm_min`` (None: all) and, with ``kept``, the elements LTS kept in each
+        (``nbls_set_beam_trace``); None switches that off."""
+        if window is None:
+            self._chk(self.lib.nbls_set_beam_trace(self._h, None, 0, float('nan'), 0))
+            return
+        w = _f64(np.asarray(window, dtype=np.float64).reshape(-1))
+        self._chk(self.lib.nbls_set_beam_trace(self._h, _dptr(w), w.size, float('nan') if mdccm_min is None else float(mdccm_min),
+                                               BEAM_TRACE_KEPT if kept else 0))
+
+    def fetch_beam_trace(self, row):
+        """-> the beam trace (npts,) of result row ``row``."""
+        out = np.empty(self.npts)
+        self._chk(self.lib.nbls_fetch_beam_trace(self._h, int(row), _dptr(out)))
+        return out
 
     def set_beam_grid(self, grid=None, want_map=False):
         """The next plans also search, per window, the beam F-statistic of the full array over the slowness vectors

@@ -850,6 +850,40 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if ((h->want_kept_flags & NBLS_KEPT_CAPON) && h->want_capon.grid.empty())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_KEPT_CAPON (nbls_set_kept_elements) needs Capon spectra (nbls_set_capon)");
     }
+    if (h->want_bt) {                // the beam trace (nbls_set_beam_trace): estimator 0, every window of every band, one synthesis window per band
+        if (!h->win_first.empty())
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the beam trace (nbls_set_beam_trace) is not supported with window ranges (nbls_set_window_ranges): a slice of the windows does not cover the trace");
+        if (h->nest > 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the beam trace (nbls_set_beam_trace) is not supported with further estimators (nbls_set_estimators)");
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the beam trace (nbls_set_beam_trace) is not supported with an RCCL communicator (the gathered block does not carry it)");
+        const int En = h->nchans / NS;
+        bool rows = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
+        for (int m = 1; rows && m < En; ++m)
+            if (h->h_pair[2 * (m - 1)] != 0 || h->h_pair[2 * (m - 1) + 1] != m) rows = false;
+        if (!rows)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: the beam trace (nbls_set_beam_trace) needs the geometry of the trace's array, its first rows the pairs (0, m)");
+        if ((h->want_bt_flags & NBLS_BEAM_TRACE_KEPT) && h->want_kept_q < 1)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_BEAM_TRACE_KEPT (nbls_set_beam_trace) needs the kept elements (nbls_set_kept_elements)");
+        int64_t sumw = 0;
+        for (int b = 0; b < a.nbands; ++b) sumw += a.winlen[b] > 0 ? a.winlen[b] : 0;
+        if ((int64_t)h->want_bt_win.size() != sumw)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: a synthesis window table (nbls_set_beam_trace) of " + std::to_string(h->want_bt_win.size()) +
+                                             " entries for bands whose window lengths add up to " + std::to_string(sumw));
+        int64_t o = 0;
+        for (int b = 0; b < a.nbands; ++b) {
+            bool any = false;
+            for (int t = 0; t < a.winlen[b]; ++t) {
+                const double g = h->want_bt_win[(size_t)(o + t)];
+                if (!(g >= 0.0) || std::isinf(g))
+                    return fail(h, NBLS_ERR_ARG, "nbls_plan: the synthesis window (nbls_set_beam_trace) of band " + std::to_string(b) + " has a negative or non-finite entry");
+                any = any || g > 0.0;
+            }
+            if (!any)
+                return fail(h, NBLS_ERR_ARG, "nbls_plan: the synthesis window (nbls_set_beam_trace) of band " + std::to_string(b) + " is all zero");
+            o += a.winlen[b] > 0 ? a.winlen[b] : 0;
+        }
+    }
     if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
         if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
@@ -878,6 +912,10 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->kept_beam = h->kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_BEAM);
     h->kept_capon = h->kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_CAPON);
     h->kept_valid = false;
+    h->bt = h->want_bt;
+    h->bt_kept = h->bt && (h->want_bt_flags & NBLS_BEAM_TRACE_KEPT);
+    h->bt_min = h->want_bt_min;
+    h->bt_valid = false;
     h->refine = h->want_refine;
     h->frac_valid = false;
     h->solve_ran = false;
@@ -1190,6 +1228,16 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_kept_mask, cells * sizeof(uint32_t)))) return rc;
         if ((rc = ensure(h, h->d_kept_count, cells * sizeof(int32_t)))) return rc;
     }
+    if (h->bt) {                     // the beam trace: the synthesis windows, where every row's starts, and the trace of every row
+        std::vector<int32_t> off((size_t)a.R);
+        for (int r = 0, o = 0, b = 0; r < a.R; ++r) {
+            if (r / a.NS != b) { o += a.winlen[b]; ++b; }
+            off[(size_t)r] = o;
+        }
+        if ((rc = alloc_copy(h, h->d_bt_win, h->want_bt_win.data(), h->want_bt_win.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_bt_off, off.data(), off.size()))) return rc;
+        if ((rc = ensure(h, h->d_bt, (size_t)a.R * (size_t)h->npts_pad * sizeof(double)))) return rc;
+    }
     if (h->capon_n > 0) {            // the Capon spectra: the band tables and the result buffers, likewise
         const size_t cells = (size_t)a.R * a.vector_len;
         const int E = a.E, G = h->capon_n, nb = a.nbands;
@@ -1328,6 +1376,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
     if ((stage_mask & 4) && h->closure) h->closure_valid = true;      // (likewise the closure grids)
     if ((stage_mask & 4) && h->kept_q > 0) h->kept_valid = true;     // (... and the kept elements)
+    if ((stage_mask & 4) && h->bt) h->bt_valid = true;               // (... and the beam trace)
     if (stage_mask & 4) h->solve_ran = true;
     // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
     if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
@@ -1357,6 +1406,9 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (h->ev_xd && (stage_mask & 2) && !h->ev_xd_by_launcher) { HIPCHK(h, hipEventRecord(h->ev_xd, h->stream)); h->ev_xd_recorded = true; }
     if (h->prof) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
     if ((stage_mask & 4) && !h->solve_done) HIPCHK(h, nbls_launch_solve(h));
+    // the beam trace of a plan that asked for one (nbls_set_beam_trace): one launch behind the pass's last solve — per-batch
+    // solves on the second stream have been joined into this one (nbls_xcorr_screen_finish) — and ahead of the closing event
+    if ((stage_mask & 4) && h->bt) HIPCHK(h, nbls_launch_beam_trace(h, h->stream));
     if (h->prof) { HIPCHK(h, hipEventRecord(h->ev[3], h->stream)); h->ev_valid = true; }
     // streamed results of a pass that was not cut into batches (general correlators, stage subsets, no units): ONE batch
     if (h->stream_results && h->rbatches.empty()) HIPCHK(h, nbls_queue_result_batch(h, 0, h->nunits, h->stream));
@@ -1649,6 +1701,31 @@ int nbls_fetch_kept_elements(nbls_handle* h, uint32_t* dropped_mask, int32_t* ke
         HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * 4, hipMemcpyDeviceToHost));
         zero_uncomputed(h, outs[g], 4);                   // like the grids
     }
+    return NBLS_OK;
+}
+
+int nbls_set_beam_trace(nbls_handle* h, const double* window, int64_t nwindow, double mdccm_min, int32_t flags) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!window) { h->want_bt = false; h->want_bt_win.clear(); h->want_bt_flags = 0; return NBLS_OK; }    // off: the next plan forms no trace
+    if (nwindow < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_trace: nwindow must not be negative");
+    if (flags & ~NBLS_BEAM_TRACE_KEPT) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_trace: unknown flags");
+    h->want_bt = true;                       // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want_bt_win.assign(window, window + nwindow);
+    h->want_bt_min = mdccm_min;
+    h->want_bt_flags = flags;
+    return NBLS_OK;
+}
+
+int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out) {
+    if (!h || !out) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_trace: no plan");
+    if (!h->bt || !h->d_bt) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_trace: nbls_set_beam_trace before nbls_plan");
+    if (row < 0 || row >= h->nbands) return fail(h, NBLS_ERR_ARG, "nbls_fetch_beam_trace: row out of range");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    // written behind the solve stage alone: zeros until a pass of this plan has run it, and a later pass without it leaves
+    // the trace as it is
+    if (!h->bt_valid) { memset(out, 0, (size_t)h->npts * sizeof(double)); return NBLS_OK; }
+    HIPCHK(h, copy_sync(h, out, h->d_bt + (size_t)row * h->npts_pad, (size_t)h->npts * sizeof(double), hipMemcpyDeviceToHost));
     return NBLS_OK;
 }
 

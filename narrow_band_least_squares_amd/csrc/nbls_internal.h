@@ -223,6 +223,18 @@ struct nbls_handle {
     bool capon_kept_attr_set[3] = {false, false, false};    // the KEPT instances of capon_kernel have their dynamic LDS limit
     dev_buf<uint32_t> d_kept_mask;  // [B][VL] bit m: element m is dropped
     dev_buf<int32_t> d_kept_count;  // [B][VL] M
+    // ---- the beam trace of every result row (nbls_set_beam_trace, beam_trace.hip) ----
+    bool want_bt = false;           // nbls_set_beam_trace: read by the next nbls_plan
+    std::vector<double> want_bt_win;    // ... its synthesis windows, band after band
+    double want_bt_min = 0.0;       // ... its MdCCM gate (NaN: off)
+    int want_bt_flags = 0;
+    bool bt = false;                // the plan forms the trace behind the pass's last solve
+    bool bt_kept = false;           // ... over the elements LTS kept in each window (NBLS_BEAM_TRACE_KEPT)
+    double bt_min = 0.0;
+    bool bt_valid = false;          // a pass of this plan has run the solve stage: d_bt holds the trace
+    dev_buf<double> d_bt;           // [B][npts_pad]
+    dev_buf<double> d_bt_win;       // the plan's synthesis windows
+    dev_buf<int32_t> d_bt_off;      // [B] where the window of result row r starts in d_bt_win
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -386,6 +398,9 @@ __host__ __device__ inline uint32_t nbls_kept_bits_of(uint32_t dropped, int N, i
     if (M < 3) { kept = all; M = N; }
     return kept;
 }
+// the beam trace of every result row at the slowness estimator 0 has solved for its windows: one launch per pass, behind
+// the last solve (beam_trace.hip)
+hipError_t nbls_launch_beam_trace(nbls_handle* h, hipStream_t st);
 // slowness-grid search of the beam F-statistic over units [u0, u0 + nu) for the plan's full array (beam_grid.hip)
 hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 // dynamic LDS bytes of the form beam_grid_kernel takes for windows of W samples of nelem elements and a halo of `halo`

@@ -364,7 +364,7 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
                want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-               want_kept=False):
+               want_kept=False, beam_trace_npts=0):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
@@ -377,7 +377,7 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     complex; with ``capon_peaks`` = K > 0 ``capon_peak_count`` (nbands, vector_len) int32, ``capon_peak_index`` (.., K) int32,
     ``capon_peak_power`` (.., K), ``capon_peak_offset`` (.., K, 2) and the same four with ``bartlett_``; ``want_kept``:
     ``dropped_mask`` (nbands, vector_len) uint32 and ``kept_count`` (nbands, vector_len) int32, the elements LTS dropped;
-    None otherwise."""
+    ``beam_trace_npts`` = npts > 0: ``beam_trace`` (nbands, npts), the beam trace of every band; None otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
     K = int(capon_peaks) if capon_points else 0
     peaks = {}
@@ -411,6 +411,7 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      if (capon_points and want_capon_csdm) else None,
                      dropped_mask=np.zeros((nb, vector_len), dtype=np.uint32) if want_kept else None,
                      kept_count=np.zeros((nb, vector_len), dtype=np.int32) if want_kept else None,
+                     beam_trace=np.zeros((nb, int(beam_trace_npts))) if beam_trace_npts else None,
                      lts=alpha < 1.0, fs=fs, **peaks)
 
 
@@ -446,11 +447,12 @@ def _filtered_budget_bytes():
     return float(os.environ.get('NBLS_MAX_FILTERED_GB', '160')) * 2.0 ** 30
 
 
-def max_bands_per_pass(nchans, npts):
+def max_bands_per_pass(nchans, npts, trace_rows=0):
     """Bands whose filtered traces fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB, default 160 of
-    the 288 GB): each band keeps an (N, npts) float64 copy resident for the correlation stage.  0: not even
+    the 288 GB): each band keeps an (N, npts) float64 copy resident for the correlation stage — and, in a pass that forms
+    the beam trace (``nbls_set_beam_trace``), ``trace_rows`` more rows, one per recording.  0: not even
     one band fits -> ``process`` switches to the time-segmented path."""
-    return int(_filtered_budget_bytes() // (8.0 * nchans * (npts + 64)))
+    return int(_filtered_budget_bytes() // (8.0 * (nchans + trace_rows) * (npts + 64)))
 
 
 def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
@@ -490,7 +492,7 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
                       host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None,
-                      slowness_grid=None, seed_halfwidths=None, want_consistency=False):
+                      slowness_grid=None, seed_halfwidths=None, want_consistency=False, want_beam_trace=None):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
@@ -500,7 +502,12 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM, nor the bounded lag
     search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too,
     nor the seeded lag search (``seed_halfwidths``), which rests on it, nor the closure of the picked lags
-    (``want_consistency``), which reads the lag table of a whole pass in HBM."""
+    (``want_consistency``), which reads the lag table of a whole pass in HBM, nor the beam trace (``want_beam_trace``), which
+    reads the filtered band in HBM as the beam results do."""
+    if want_beam_trace is not None:
+        raise ValueError('want_beam_trace: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
+                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
+                         'the beam trace is not available there' % _shape_of(data))
     if want_consistency:
         raise ValueError('want_consistency: a trace of %d x %d samples takes the time-segmented path (not even one filtered '
                          'band fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which correlates the band slice by '
@@ -621,7 +628,7 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
            subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None):
+           kept=None, beam_trace=None):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -642,7 +649,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     computes the Capon spectra of its bands (likewise); with ``peaks`` = K > 0 in it also their K strongest peaks on the
     lattice ``peak_cells`` above ``peak_floor`` (``Handle.set_capon_peaks``; likewise).  ``kept``: ``(min_pairs, beam,
     capon)`` of ``Handle.set_kept_elements``: the plan also names the elements LTS dropped and forms its beam results / Capon
-    spectra over the kept ones (likewise)."""
+    spectra over the kept ones (likewise).  ``beam_trace``: ``(windows, mdccm_min, kept)`` — one synthesis window per band
+    of the Prep, the MdCCM gate (NaN: off) and the kept flag of ``Handle.set_beam_trace``: the plan also forms the beam
+    trace of its rows behind its last solve (for this plan only)."""
     if upload:
         if trace_ready:
             pass
@@ -678,6 +687,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     try:
         if kept is not None:
             h.set_kept_elements(*kept)
+        if beam_trace is not None:
+            wins, gate, bt_kept = beam_trace
+            h.set_beam_trace(np.concatenate([wins[int(i)] for i in idx]), None if gate != gate else gate, bt_kept)
         if capon is not None:            # (inside the try: whatever one of the two refuses, the shared handle keeps neither)
             capon = dict(capon)
             peaks, cells, floor = capon.pop('peaks', 0), capon.pop('peak_cells', None), capon.pop('peak_floor', 0.25)
@@ -705,6 +717,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon_peaks(None)
         if kept is not None:
             h.set_kept_elements(0)
+        if beam_trace is not None:
+            h.set_beam_trace(None)
         if window_slice is not None:
             h.set_window_ranges(None)
     if before_execute is not None:
@@ -841,6 +855,9 @@ def collect(res, h, b0, b1, streamed, note):
                 getattr(res, name + field)[b0:b1] = a
     if res.dropped_mask is not None:
         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = h.fetch_kept_elements()
+    if res.beam_trace is not None:
+        for b in range(b0, b1):
+            res.beam_trace[b] = h.fetch_beam_trace(b - b0)
     if not live:
         note.bands(b0, b1)
 
@@ -866,6 +883,7 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
     launched, prep = [], None
     seed_all = launch_kw.get('lag_seed')
     capon_all = launch_kw.get('capon')
+    trace_all = launch_kw.get('beam_trace')
     nchans, npts = _shape_of(data)
     for g, (b0, b1) in enumerate(bounds):
         prep = prepare(nchans, npts, res.fs, rij, band_edges[b0:b1], winlens[b0:b1], *prep_tail, common=prep,
@@ -886,6 +904,8 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
             launch_kw = dict(launch_kw, lag_seed=seed_all[b0:b1])
         if capon_all is not None:                         # (likewise the Capon tables)
             launch_kw = dict(launch_kw, capon=dict(capon_all, **{k: capon_all[k][b0:b1] for k in ('freqs', 'snap_len', 'snap_hop')}))
+        if trace_all is not None:                         # (likewise the synthesis windows)
+            launch_kw = dict(launch_kw, beam_trace=(trace_all[0][b0:b1],) + tuple(trace_all[1:]))
         try:
             launch(h, data, prep, trace_from=launched[0][0] if (launched and not sequential) else None, trace_ready=early,
                    after=launched[-1][0] if ordered else None, stream=streamed,
@@ -960,6 +980,25 @@ def _check_kept(nchans, kept, want_beam, capon):
     return q, kb, kc
 
 
+def _check_beam_trace(want, W, kept, window_slice=None):
+    """``want_beam_trace`` of ``process`` / ``process_batch`` — None / False, True, a window kind or a dict of ``window``,
+    ``mdccm_min``, ``kept`` — -> the ``beam_trace`` tuple of ``launch`` (one synthesis window per band, the gate, the kept flag)
+    or None; ``ValueError`` before any GPU work (``planner.check_beam_trace``).  ``W``: the window length of every band;
+    ``kept``: the call's checked ``kept`` tuple or None."""
+    if want is None or want is False:
+        return None
+    if want is True:
+        want = {}
+    elif isinstance(want, str):
+        want = dict(window=want)
+    if not isinstance(want, dict) or set(want) - {'window', 'mdccm_min', 'kept'}:
+        raise ValueError('want_beam_trace must be True, a window kind or a dict of window, mdccm_min and kept, not %r' % (want,))
+    table, gate, bt_kept = planner.check_beam_trace(np.asarray(W, dtype=np.int64), has_kept=kept is not None,
+                                                    window_slice=window_slice, **want)
+    cuts = np.cumsum(np.asarray(W, dtype=np.int64))[:-1]
+    return list(np.split(table, cuts)), gate, bt_kept
+
+
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
@@ -967,7 +1006,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None, kept=None):
+            capon_peak_floor=0.25, capon_cells=None, kept=None, want_beam_trace=None):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -1021,6 +1060,12 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     spectra, their maxima, maps and peaks are those of the elements that are not dropped — the whole array where fewer
     than 3 would remain (``nbls_set_kept_elements``).  ``ValueError`` before any GPU work
     (``planner.check_kept``); ``process_segmented`` refuses it.
+    want_beam_trace = True, ``'hann'`` / ``'boxcar'`` or a dict of ``window``, ``mdccm_min``, ``kept``: also ``res.beam_trace``
+    (nbands, npts), per band the delay-and-sum beam at every window's solved slowness, the overlapping windows stitched
+    with the synthesis window; only windows with MdCCM >= ``mdccm_min`` enter, with ``kept`` (needs ``kept=``) each over the
+    elements LTS kept in it (``nbls_set_beam_trace``).  Formed on the GPU behind the last solve of every
+    pass, fetched per HBM round.  ``ValueError`` before any GPU work (``planner.check_beam_trace``); ``process_segmented``
+    refuses it, and so does a ``window_slice``.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -1042,12 +1087,14 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij)[0], fs, min_velocity)
     sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
     seeds = _check_seed(seed_halfwidths, len(band_edges), sgrid, min_velocity)
-    cap = max_bands_per_pass(nchans, npts)
+    cap = max_bands_per_pass(nchans, npts, 0 if want_beam_trace is None or want_beam_trace is False else 1)
     # (the Capon tables are checked against the window lengths: planned here already, before the upload starts)
     capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
                          None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0],
                          capon_peaks, capon_peak_floor, capon_cells)
     kept = _check_kept(nchans, kept, want_beam, capon)
+    trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
+        want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
     if cap < 1 and not prefiltered and kept is not None:
         raise ValueError('kept: a trace of %d x %d samples takes the time-segmented path (not even one filtered band fits the '
                          'HBM budget of a pass, NBLS_MAX_FILTERED_GB): the kept elements are not available there' % (nchans, npts))
@@ -1063,19 +1110,20 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency)
+                                     group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency,
+                                     None if trace is None else want_beam_trace)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
                          0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
-                         0 if capon is None else capon.get('peaks', 0), kept is not None)
+                         0 if capon is None else capon.get('peaks', 0), kept is not None, npts if trace is not None else 0)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept)
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace)
     finally:
         if up is not None:
             up.close()
@@ -1166,7 +1214,7 @@ class _EstimatorResults:
 def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators, filter_type=None, filter_order=None,
                   filter_ripple=None, vector_len=None, device=None, prefiltered=False, want_uncert=False, want_lag=False,
                   want_cmax=False, host_overlap=None, units_done=None, want_beam=False, want_subsample=False,
-                  min_velocity=None, want_consistency=False):
+                  min_velocity=None, want_consistency=False, want_beam_trace=None):
     """``process`` for several estimators ``(alpha, remove)`` of ONE trace in one device pass -> a list of ``BandBatch``,
     element e what ``process`` gives for ``alpha_e`` on the rows that ``remove_e`` leaves (``estimators`` as
     ``normalize_estimators`` returns them; ``rijs[e]``: the (2, kept) geometry of estimator e, ``t0s[e]`` its start date).
@@ -1183,7 +1231,11 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     array's lags once and every estimator solves on the refined delays of ITS pairs (``lag_frac`` with ``want_lag``).
     ``min_velocity``: the full array's lags are searched within their physical range (``process``); a sub-array reads them.
     ``want_consistency``: every estimator's ``consistency`` / ``closure_max`` / ``element_consistency``, the closure of the
-    picked lags over the triplets of ITS elements (``process``)."""
+    picked lags over the triplets of ITS elements (``process``).  ``want_beam_trace``: refused (``ValueError``) — the beam trace
+    is estimator 0's, further estimators are out of its scope."""
+    if want_beam_trace is not None and want_beam_trace is not False:
+        raise ValueError('want_beam_trace: the beam trace is not available with several estimators (nbls_set_beam_trace is '
+                         'refused beside nbls_set_estimators)')
     rows = list(np.ascontiguousarray(data, dtype=np.float64)) if isinstance(data, np.ndarray) else data
     nchans, npts = _shape_of(rows)
     nb = len(band_edges)
@@ -1305,7 +1357,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None):
+                  kept=None, want_beam_trace=None):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1330,15 +1382,17 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     CG = 0 if capon is None else len(capon['grid'])
     CK = 0 if capon is None else capon.get('peaks', 0)
     kept = _check_kept(nchans, kept, want_beam, capon)
+    trace = _check_beam_trace(want_beam_trace, prep.W, kept)
+    tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
     limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
-    per_sub = S if max_bands_per_pass(S * nchans, npts) >= 1 else max_bands_per_pass(nchans, npts)
+    per_sub = S if max_bands_per_pass(S * nchans, npts, S * tr) >= 1 else max_bands_per_pass(nchans, npts, tr)
     if per_sub < 1:
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
                          'process it on its own' % (nchans, npts))
     out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
                       grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
                       want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK,
-                      want_kept=kept is not None)
+                      want_kept=kept is not None, beam_trace_npts=npts if trace is not None else 0)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1346,7 +1400,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
             k = min(per_sub, S - s0)
             h.set_segments(k)
             h.set_trace_rows([r for rec in recordings[s0:s0 + k] for r in rec], fs)
-            cap = max(1, max_bands_per_pass(k * nchans, npts))
+            cap = max(1, max_bands_per_pass(k * nchans, npts, k * tr))
             streamed = stream_pays(alpha, np.tile(prep.nwin, k), P)
             for b0 in range(0, nb, cap):
                 b1 = min(nb, b0 + cap)
@@ -1354,7 +1408,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon, kept=kept)
+                       closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
@@ -1396,6 +1450,9 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                                 getattr(res, name + field)[b0:b1] = a[:, j]
                     if kel is not None:
                         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = [a[:, j] for a in kel]
+                    if trace is not None:
+                        for b in range(b0, b1):
+                            res.beam_trace[b] = h.fetch_beam_trace((b - b0) * k + j)
     finally:
         h.set_segments(1)
     for res, t0 in zip(out, t0s):

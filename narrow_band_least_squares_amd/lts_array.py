@@ -307,7 +307,8 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     the lags are searched within their physical range as in ``ltsva_bounded``; it combines with both flags, the fractions
     and the beam then follow the bounded picks.  ``slowness_grid`` (G, 2) s/km, default None: every tuple is followed by the
     five grid returns of ``ltsva_grid`` (no map), element i equal to ``ltsva_grid(streams[i], ...)``; it combines with the
-    others, because it reads none of their results.  ``ltsva_capon_batch`` is this call with the Capon spectra."""
+    others, because it reads none of their results.  ``ltsva_capon_batch`` is this call with the Capon spectra,
+    ``ltsva_beam_trace_batch`` the one with the beam trace."""
     return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
                         slowness_grid, None)
 
@@ -510,3 +511,72 @@ def ltsva_kept_batch(streams, lat_list, lon_list, window_length, window_overlap,
                                    want_uncert=True, **kw)
     return [_returns(res, nchans, alpha) + (_returns_kept(res, nchans, kw['want_beam'], ckw, n=int(res.nwin[0])),)
             for res in results]
+
+
+def ltsva_beam_trace(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, mdccm_min=None, window='hann',
+                     kept=False, min_pairs=None):
+    """``ltsva`` followed by the waveform its numbers describe: the beam trace (npts,), the delay-and-sum beam steered, window
+    by window, at the slowness the window solved — the elements shifted by whole samples against element 0, as in
+    ``ltsva_beam`` — and the overlapping windows stitched with the synthesis window ``window`` (``'hann'``: sin^2, ``'boxcar'``:
+    the plain average, or the W values themselves; ``planner.beam_trace_window``).  ``mdccm_min``: only windows whose MdCCM
+    reaches it enter the trace; samples no accepted window covers are 0.0.  ``kept=True`` (LTS, ``alpha < 1``): every window
+    is summed over the elements FAST-LTS kept in it (``ltsva_kept``; ``min_pairs`` as there) and divided by their count, the
+    time base still element 0's.  DESIGN.md section 21 has the definition.  The trace is formed on the GPU behind the last
+    solve, from the filtered samples already there (csrc/beam_trace.hip): 1/N of the data a host-side beam would have to
+    fetch.  Returns ``ltsva``'s 8-tuple followed by the trace.  Whatever the library would refuse raises ``ValueError``
+    before any GPU work."""
+    nchans = len(st)
+    data, fs, t0 = engine.stream_rows(st)
+    kept_kw, want = _beam_trace_keywords(nchans, alpha, len(data[0]), fs, window_length, window_overlap, mdccm_min, window, kept,
+                                         min_pairs)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, kept=kept_kw, want_beam_trace=want)
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (res.beam_trace[0].copy(),)
+
+
+def _beam_trace_keywords(nchans, alpha, npts, fs, window_length, window_overlap, mdccm_min, window, kept, min_pairs):
+    """The ``kept`` and ``want_beam_trace`` keywords of ``engine.process`` behind the arguments of ``ltsva_beam_trace``;
+    ``ValueError`` before any GPU work."""
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    _check_flag('kept', kept)
+    if min_pairs is not None and not kept:
+        raise ValueError('min_pairs needs kept=True')
+    kept_kw = planner.check_kept(nchans, min_pairs, False, False) if kept else None
+    W = planner.window_plan(npts, fs, window_length, window_overlap)[0]
+    want = dict(window=window, mdccm_min=mdccm_min, kept=bool(kept))
+    engine._check_beam_trace(want, [int(W)], kept_kw)
+    return kept_kw, want
+
+
+def ltsva_beam_trace_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, mdccm_min=None,
+                           window='hann', kept=False, min_pairs=None):
+    """``ltsva_beam_trace`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
+    element i equal to ``ltsva_beam_trace(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``.  (``ltsva_batch``
+    and ``ltsva_kept_batch`` keep their signatures: the batch form of the trace is this function.)"""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    kept_kw, want = _beam_trace_keywords(nchans, alpha, len(recs[0][0]), fs, window_length, window_overlap, mdccm_min, window,
+                                         kept, min_pairs)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_beam_trace(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, mdccm_min, window,
+                                 kept, min_pairs)]
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, kept=kept_kw, want_beam_trace=want)
+    return [_returns(res, nchans, alpha) + (res.beam_trace[0].copy(),) for res in results]

@@ -773,3 +773,41 @@ def narrow_band_least_squares_parallel(WINLEN_list, WINOVER, ALPHA, st, lat_list
     elif ALPHA != 1.0:
         stdict_all = _merge_dictionaries(stdict_head, stdict_parts, cache, shards, mask, prep, keys)
     return _returns(ALPHA, grids[0], grids[1], grids[2], grids[3], t_array, stdict_all, prep.nwin, w_array, h_array)
+
+
+def narrow_band_least_squares_beam_trace(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                         FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                         mdccm_min=None, window='hann', kept=False):
+    """``narrow_band_least_squares`` followed by ``beam_trace_array`` (NBANDS, npts): per band the delay-and-sum beam of the
+    filtered band, steered window by window at the slowness the window solved and stitched over the overlapping windows
+    with the synthesis window ``window`` (``'hann'`` / ``'boxcar'``; ``lts_array.ltsva_beam_trace``).
+    ``mdccm_min``: only windows whose MdCCM reaches it enter, samples no accepted window covers are 0.0.  ``kept=True``
+    (``ALPHA < 1``): every window is summed over the elements FAST-LTS kept in it (every pair of a dropped element has
+    lost its weight).  The trace is formed on the GPU behind the last solve of every pass, from the filtered bands that
+    are already there.  The first nine returns are those of ``narrow_band_least_squares``.  Whatever the library would
+    refuse raises ``ValueError`` before any GPU work, and so does a trace so long that not one filtered band fits the HBM
+    budget of a pass."""
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
+        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
+                         'squares' % len(st))
+    if not isinstance(kept, (bool, np.bool_)):
+        raise ValueError('kept must be True or False, not %r' % (kept,))
+    if not isinstance(window, str):
+        raise ValueError("window must be 'hann' or 'boxcar', not %r" % (window,))
+    kept_kw = planner.check_kept(len(st), None, False, False) if kept else None
+    planner.check_beam_trace([1], window, mdccm_min, bool(kept), kept_kw is not None)       # (the bands' own lengths: engine.process)
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    bands = list(range(NBANDS))
+    want = dict(window=window, mdccm_min=mdccm_min, kept=bool(kept))
+
+    def keywords(*args):           # (the keywords that ride into ``engine.process``)
+        return dict(kept=kept_kw, want_beam_trace=want)
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (res.beam_trace,)

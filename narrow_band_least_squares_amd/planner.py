@@ -726,3 +726,63 @@ def check_kept(nchans, min_pairs=None, beam=True, capon=False):
     if not (1 <= int(min_pairs) <= n - 1):
         raise ValueError('min_pairs must lie in 1..%d (an element of %d has %d pairs), not %r' % (n - 1, n, n - 1, min_pairs))
     return int(min_pairs), bool(beam), bool(capon)
+
+
+def beam_trace_window(W, kind='hann'):
+    """The synthesis window (W,) that stitches the windows of a beam trace (``nbls_set_beam_trace``):
+    ``'hann'``: sin^2(pi (t + 1/2) / W), strictly positive, so every sample a usable window covers has a positive
+    denominator; ``'boxcar'``: ones (the plain average of the windows that cover a sample)."""
+    if isinstance(W, (bool, np.bool_)) or not isinstance(W, (int, np.integer)) or int(W) < 1:
+        raise ValueError('the window length must be a positive integer, not %r' % (W,))
+    if kind == 'boxcar':
+        return np.ones(int(W))
+    if kind == 'hann':
+        return np.sin(np.pi * (np.arange(int(W)) + 0.5) / int(W)) ** 2
+    raise ValueError("kind must be 'hann' or 'boxcar', not %r" % (kind,))
+
+
+def check_beam_trace(W, window='hann', mdccm_min=None, kept=False, has_kept=False, window_slice=None, estimators=None,
+                     comm=False):
+    """Everything ``nbls_set_beam_trace`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (table,
+    mdccm_min, kept): the synthesis windows of the bands one after the other (float64, sum of ``W`` entries), the MdCCM gate
+    as a float (NaN: off) and the kept flag.  ``W``: the window length of every band; ``window``: ``'hann'`` / ``'boxcar'``
+    (``beam_trace_window``) or the table itself, flat or one array per band; ``mdccm_min``: None or NaN (no gate) or a number —
+    only windows with MdCCM >= it enter the trace; ``kept``: sum each window over the elements LTS kept in it, which needs a
+    plan that names them (``has_kept``: the call also passes ``kept=``, ``check_kept``).  A window slice, further estimators
+    and an RCCL communicator are refused."""
+    W = np.asarray(W)
+    if W.ndim != 1 or len(W) < 1 or W.dtype.kind not in 'iu' or (W < 1).any():
+        raise ValueError('the window lengths must be positive integers, one per band')
+    if not isinstance(kept, (bool, np.bool_)):
+        raise ValueError('kept must be True or False, not %r' % (kept,))
+    if kept and not has_kept:
+        raise ValueError('the beam trace of the kept elements needs a plan that names them (kept=, planner.check_kept)')
+    if window_slice is not None:
+        raise ValueError('the beam trace is not available for a slice of the windows (window_slice): it would not cover the trace')
+    if estimators:
+        raise ValueError('the beam trace is not available with further estimators')
+    if comm:
+        raise ValueError('the beam trace is not available with an RCCL communicator (the gathered block does not carry it)')
+    if mdccm_min is None:
+        gate = float('nan')
+    else:
+        if isinstance(mdccm_min, (bool, np.bool_)) or not isinstance(mdccm_min, (int, float, np.integer, np.floating)):
+            raise ValueError('mdccm_min must be a number or None, not %r' % (mdccm_min,))
+        gate = float(mdccm_min)                    # (NaN: the gate is off, as in the C ABI)
+    if isinstance(window, str):
+        table = np.concatenate([beam_trace_window(int(w), window) for w in W])
+    else:
+        try:                                       # the table itself: flat, or one array per band
+            table = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1) for p in window])
+        except (TypeError, ValueError):
+            raise ValueError("window must be 'hann', 'boxcar' or the synthesis windows of the bands")
+    if table.size != int(W.sum()):
+        raise ValueError('%d synthesis-window entries for bands whose window lengths add up to %d' % (table.size, int(W.sum())))
+    if not np.isfinite(table).all() or (table < 0).any():
+        raise ValueError('the synthesis window must be finite and not negative')
+    o = 0
+    for b, w in enumerate(W):
+        if not (table[o:o + int(w)] > 0).any():
+            raise ValueError('the synthesis window of band %d is all zero' % b)
+        o += int(w)
+    return np.ascontiguousarray(table, dtype=np.float64), gate, bool(kept)
