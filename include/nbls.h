@@ -614,6 +614,34 @@ int nbls_set_beam_trace(nbls_handle* h, const double* window /* concatenated per
                         double mdccm_min, int32_t flags);
 int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out /* [npts] */);
 
+/* ---- Steering at fractional-sample delays ----
+ * The beam at the solved slowness (nbls_set_beam, section 12) and the slowness-grid search (nbls_set_beam_grid, section 15)
+ * shift the elements by whole samples, d = rint(tau).  On request they read every element at the delay tau itself through a
+ * Lagrange interpolator of L = taps samples.  K = L / 2, k runs over -K+1 .. K:
+ *   tau_i    fs * (xij[row][0] * z0 + xij[row][1] * z1), un-fused, the expression and the pair row of sections 12 / 15 / 20
+ *            (the kept-elements beam re-references as it does today); the reference element has tau = 0.  |tau| >= 2^30 or
+ *            NaN: the unit's beam results are NaN, a grid plan is refused, as without interpolation.
+ *   n_i, mu  n_i = floor(tau_i), mu_i = tau_i - n_i in [0, 1) (exact below 2^30).
+ *   c_k(mu)  (((1.0 * (mu - j_1)) * (mu - j_2)) * ...) / D_k, the j ascending over -K+1 .. K without k, D_k = prod_{j != k}
+ *            (k - j) an exact integer: L - 1 subtractions, L - 1 products, one division.  mu = 0: c_0 = 1.0, every other
+ *            coefficient exactly +-0.
+ *   x_i[t]   ((0.0 + c_{-K+1} * y_{-K+1}) + ...) + c_K * y_K,  y_k = filt[e_i][s0 + t + n_i + k], 0.0 where the index is
+ *            outside [0, npts).  Every product is rounded before its addition (no contraction); a zero coefficient is still
+ *            multiplied, so a NaN sample propagates.
+ * b[t], S_b, S_t, D, F, P, the +-inf / NaN rules, the arg-max order and every reduction order are those of sections 12 and
+ * 15.  Where every tau is an integer an interpolated plan returns the whole-sample plan's bits.  A fixed sequence of IEEE
+ * operations that NumPy float64 restates (tests/steer_truth.py).  The beam trace (section 21) keeps whole-sample delays.
+ *   nbls_set_beam_interpolation(h, taps)   read by the next nbls_plan; 0 switches it off (the default: such a plan launches
+ *                            exactly what it launched before), 4, 6 or 8 taps.  NBLS_ERR_ARG, the handle unchanged, for
+ *                            anything else.  nbls_plan returns NBLS_ERR_STATE if it is on and the plan asks for neither
+ *                            nbls_set_beam nor nbls_set_beam_grid.  Every estimator's beam (nbls_est_fetch_beam), the
+ *                            kept-elements beam and the grid of a seeded plan follow it.
+ *   nbls_fetch_beam_grid_delays   of an interpolated grid plan returns n[G][N] (floor, not rint).
+ *   nbls_fetch_beam_grid_coefficients(h, c)   the plan's table c[G][N][taps], k ascending; NBLS_ERR_STATE without an
+ *                            interpolated grid plan. */
+int nbls_set_beam_interpolation(nbls_handle* h, int32_t taps);
+int nbls_fetch_beam_grid_coefficients(nbls_handle* h, double* c /* [G][N][taps] */);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -34,7 +34,9 @@ EXPORTS = [
     'nbls_set_capon_peaks', 'nbls_fetch_capon_peaks',
     'nbls_set_kept_elements', 'nbls_fetch_kept_elements',
     'nbls_set_beam_trace', 'nbls_fetch_beam_trace',
+    'nbls_set_beam_interpolation', 'nbls_fetch_beam_grid_coefficients',
 ]
+STEER_TAPS = (0, 4, 6, 8)  # taps of nbls_set_beam_interpolation (0: whole-sample delays)
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
 CAPON_GRID_MAX = 65536   # grid points of the Capon spectra (NBLS_CAPON_GRID_MAX)
@@ -179,6 +181,8 @@ def load_library(path=None):
     lib.nbls_fetch_beam_grid_map.argtypes = [vp, dp]
     lib.nbls_fetch_beam_grid_delays.argtypes = [vp, ip]
     lib.nbls_beam_grid_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.nbls_set_beam_interpolation.argtypes = [vp, C.c_int32]
+    lib.nbls_fetch_beam_grid_coefficients.argtypes = [vp, dp]
     lib.nbls_set_capon.argtypes = [vp, dp, C.c_int32, dp, ip, ip, C.c_int32, C.c_double, C.c_int32]
     lib.nbls_fetch_capon.argtypes = [vp, ip, dp, ip, dp]
     lib.nbls_fetch_capon_maps.argtypes = [vp, dp, dp]
@@ -294,6 +298,7 @@ class Handle:
         self.nseg = 1
         self.est_npairs = []            # pair counts of the further estimators (set_estimators)
         self._want_grid_n = self.grid_n = 0   # grid points of set_beam_grid / of the plan
+        self._want_taps = self.taps = 0       # taps of set_beam_interpolation / of the plan
         self._want_capon = self.capon = None  # (G, snapshot lengths) of set_capon / of the plan
         self._want_capon_peaks = self.capon_peaks = 0     # K of set_capon_peaks / of the plan
         self._keep = []
@@ -421,6 +426,7 @@ class Handle:
         self.fbands = nb
         self._nsec = nsec
         self.grid_n = self._want_grid_n
+        self.taps = self._want_taps
         self.capon = self._want_capon
         self.capon_peaks = self._want_capon_peaks
 
@@ -710,6 +716,20 @@ class Handle:
         """-> the plan's delay table, (G, nelem) int32."""
         out = np.empty((max(self.grid_n, 1), self.nchans // self.nseg), dtype=np.int32)
         self._chk(self.lib.nbls_fetch_beam_grid_delays(self._h, _iptr(out)))
+        return out
+
+    def set_beam_interpolation(self, taps=8):
+        """The next plans steer their beam (``set_beam``) and their slowness grid (``set_beam_grid``) at fractional-sample
+        delays through a Lagrange interpolator of ``taps`` samples, 4, 6 or 8 (``nbls_set_beam_interpolation``, DESIGN.md
+        section 22; ``planner.steering_error`` has its error); 0 switches that off."""
+        self._chk(self.lib.nbls_set_beam_interpolation(self._h, int(taps)))
+        self._want_taps = int(taps)
+
+    def fetch_beam_grid_coefficients(self):
+        """-> the Lagrange coefficients of an interpolated grid plan, (G, nelem, taps); ``fetch_beam_grid_delays`` then
+        returns ``floor`` of the delays."""
+        out = np.empty((max(self.grid_n, 1), self.nchans // self.nseg, max(self.taps, 1)))
+        self._chk(self.lib.nbls_fetch_beam_grid_coefficients(self._h, _dptr(out)))
         return out
 
     def set_lag_refinement(self, on=True):

@@ -781,7 +781,10 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
             return fail(h, NBLS_ERR_STATE, "nbls_plan: closure results (nbls_set_closure) need the geometry of the trace's array, every pair in lexicographic order");
     }
     std::vector<int32_t> gdel;       // the slowness grid (nbls_set_beam_grid): its delay table for this trace's array
+    std::vector<double> gcoef;       // ... and, steered at fractional delays (nbls_set_beam_interpolation), its coefficient table
     int ghalo = 0;
+    if (h->want_steer_taps && !h->want_beam && h->want_grid.empty())
+        return fail(h, NBLS_ERR_STATE, "nbls_plan: fractional-sample steering (nbls_set_beam_interpolation) needs beam results (nbls_set_beam) or a slowness grid (nbls_set_beam_grid)");
     if (!h->want_grid.empty()) {
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the slowness-grid search (nbls_set_beam_grid) is not supported with an RCCL communicator (the gathered block does not carry its grids)");
@@ -790,7 +793,15 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
             return fail(h, NBLS_ERR_STATE, "nbls_plan: the slowness-grid search (nbls_set_beam_grid) needs the geometry of the trace's array");
         const int G = (int)(h->want_grid.size() / 2);
         gdel.resize((size_t)G * En);
-        if (!nbls_beam_grid_delays_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, gdel.data(), &ghalo))
+        bool made;
+        if (h->want_steer_taps) {    // floor(tau) and the Lagrange coefficients instead of rint(tau)
+            gcoef.resize((size_t)G * En * h->want_steer_taps);
+            made = nbls_beam_grid_steer_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, h->want_steer_taps, gdel.data(),
+                                           gcoef.data(), &ghalo);
+        } else {
+            made = nbls_beam_grid_delays_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, gdel.data(), &ghalo);
+        }
+        if (!made)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: a delay of the slowness grid (nbls_set_beam_grid) reaches 2^30 samples");
     }
     if (!h->want_capon.grid.empty()) {   // Capon spectra (nbls_set_capon): the tables are made once the windows are known (plan_capon)
@@ -921,6 +932,9 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->solve_ran = false;
     h->h_grid = h->want_grid;
     h->h_grid_delay.swap(gdel);
+    h->h_grid_coef.swap(gcoef);
+    h->steer_taps = h->want_steer_taps;
+    h->grid_taps = h->want_grid.empty() ? 0 : h->want_steer_taps;
     h->grid_n = (int)(h->h_grid.size() / 2);
     h->grid_halo = ghalo;
     h->grid_map = h->grid_n > 0 && h->want_grid_map;
@@ -1219,6 +1233,7 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         const size_t cells = (size_t)a.R * a.vector_len;
         if ((rc = alloc_copy(h, h->d_grid, h->h_grid.data(), h->h_grid.size()))) return rc;
         if ((rc = alloc_copy(h, h->d_grid_delay, h->h_grid_delay.data(), h->h_grid_delay.size()))) return rc;
+        if (h->grid_taps && (rc = alloc_copy(h, h->d_grid_coef, h->h_grid_coef.data(), h->h_grid_coef.size()))) return rc;
         if ((rc = ensure(h, h->d_grid_index, cells * sizeof(int32_t)))) return rc;
         if ((rc = ensure(h, h->d_grid_fp, 2 * cells * sizeof(double)))) return rc;
         if (h->grid_map && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->grid_n * sizeof(double)))) return rc;
@@ -1918,6 +1933,23 @@ int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* 
                 steer[((size_t)g * N + i) * 2 + 1] = s[((size_t)i * G + g) * 2 + 1];
             }
     }
+    return NBLS_OK;
+}
+
+int nbls_set_beam_interpolation(nbls_handle* h, int32_t taps) {
+    if (!h) return NBLS_ERR_ARG;
+    if (taps != 0 && taps != 4 && taps != 6 && taps != 8)
+        return fail(h, NBLS_ERR_ARG, "nbls_set_beam_interpolation: taps must be 0 (off), 4, 6 or 8");
+    h->want_steer_taps = taps;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    return NBLS_OK;
+}
+
+int nbls_fetch_beam_grid_coefficients(nbls_handle* h, double* c) {
+    if (!h || !c) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_coefficients: no plan");
+    if (h->grid_n < 1 || !h->grid_taps)
+        return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_coefficients: nbls_set_beam_grid and nbls_set_beam_interpolation before nbls_plan");
+    memcpy(c, h->h_grid_coef.data(), h->h_grid_coef.size() * sizeof(double));   // the plan's own table (the device holds a copy)
     return NBLS_OK;
 }
 

@@ -20,7 +20,15 @@
 // (kept.hip has written it on the same stream): e_i is the i-th set bit of the kept bits, the reference element is e_0 and
 // d_i comes from the co-array row of pair (e_0, e_i).  The element count of the unit's sums and of its F is M; beam_sums is
 // the same function.  A unit without a dropped element fills the registers as the plain instance does: the same bits.
+//
+// A plan that asked for fractional-sample steering (nbls_set_beam_interpolation) runs the TAPS = 4, 6 or 8
+// instances (built from this file by beam_steer.hip, a translation unit of their own: this one holds the two whole-sample
+// instances and their launch, as it did): lane i holds n_i = floor(tau_i) where it held d_i, and the TAPS Lagrange
+// coefficients of mu_i = tau_i - n_i in registers of its own; the element loop reads them back with readlane (two halves
+// per double: SGPR pairs, no LDS, no private segment) and forms x_i[t] from TAPS samples.  Everything behind x_i[t] is the
+// code of the TAPS = 0 instances.
 #include "nbls_internal.h"
+#include "steer.h"
 #include "wave_ops.h"
 
 namespace {
@@ -85,6 +93,61 @@ __device__ inline void beam_sums(const BArgs& a, const double* rowbase, int64_t 
     }
 }
 
+// beam_sums with x_i[t] interpolated at tau_i = n_i + mu_i (steer.h): n_mine / c_mine[j]: lane i < n holds n_i and
+// c_{j-K+1}(mu_i).  x = ((0.0 + c y) + c y) + ..., the taps ascending, every product rounded before its addition; a tap
+// outside the trace (or a sample beyond the window) reads 0.0 and is still multiplied.  The TAPS loads of a sample and the
+// four samples of a lane are independent of each other.
+template <int STRIDE, int TAPS>
+__device__ inline void beam_sums_steer(const BArgs& a, const double* rowbase, int64_t s0, int W, int n_mine, const double* c_mine,
+                                       int el_mine, int n, int tl, double& sb, double& st) {
+    for (int t = tl; t < W; t += BEAM_TU * STRIDE) {
+        double b[BEAM_TU], q[BEAM_TU];
+#pragma unroll
+        for (int k = 0; k < BEAM_TU; ++k) { b[k] = 0.0; q[k] = 0.0; }
+        for (int i = 0; i < n; ++i) {
+            const int d = __builtin_amdgcn_readlane(n_mine, i) - (TAPS / 2 - 1), el = __builtin_amdgcn_readlane(el_mine, i);
+            double c[TAPS];
+#pragma unroll
+            for (int j = 0; j < TAPS; ++j) c[j] = nbls_wave::readlane_f64(c_mine[j], i);
+            const double* row = rowbase + (int64_t)el * a.npts_pad;
+#pragma unroll
+            for (int k = 0; k < BEAM_TU; ++k) {
+                const int tk = t + k * STRIDE;
+                const int64_t idx = s0 + tk + d;                 // the sample of tap -K+1
+                double y[TAPS];
+#pragma unroll
+                for (int j = 0; j < TAPS; ++j) {
+                    const int64_t at_j = idx + j;                // (an unconditional load of a safe index and a select:
+                    const bool in = tk < W && at_j >= 0 && at_j < a.npts;    //  4 x TAPS divergent branches would cost registers)
+                    const double yy = row[in ? at_j : 0];
+                    y[j] = in ? yy : 0.0;
+                }
+                double v = 0.0;
+#pragma unroll
+                for (int j = 0; j < TAPS; ++j) v = v + c[j] * y[j];
+                b[k] += v;
+                q[k] += v * v;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < BEAM_TU; ++k) {
+            sb += b[k] * b[k];
+            st += q[k];
+        }
+    }
+}
+
+// lane's own delay: the whole-sample instances round tau, the interpolated ones split it (c: TAPS registers, 1 if TAPS == 0)
+template <int TAPS>
+__device__ inline void beam_delay_of(double tau, int& d_mine, double* c_mine) {
+    if constexpr (TAPS == 0) d_mine = (int)rint(tau);
+    else {
+        double mu;
+        nbls_steer_split(tau, d_mine, mu);
+        nbls_steer_coefficients<TAPS>(mu, c_mine);
+    }
+}
+
 __device__ inline void beam_store(const BArgs& a, int64_t cell, int W, int nel, bool bad, double sb, double st) {
     const double n = (double)nel, nan_ = __builtin_nan("");
     double p, f;
@@ -99,7 +162,7 @@ __device__ inline void beam_store(const BArgs& a, int64_t cell, int W, int nel, 
     a.fstat[cell] = f;
 }
 
-template <bool KEPT>
+template <bool KEPT, int TAPS>
 __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
     __shared__ double red[2 * BEAM_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -118,6 +181,8 @@ __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
         const double z0 = a.z[2 * cell], z1 = a.z[2 * cell + 1];
         bool bad_l = !nbls_wave::finite_f64(z0) || !nbls_wave::finite_f64(z1);
         int d_mine = 0, el_mine = 0;
+        double c_mine[TAPS ? TAPS : 1];                          // (TAPS > 0: the element's coefficients; tau = 0 is mu = 0)
+        if constexpr (TAPS > 0) nbls_steer_coefficients<TAPS>(0.0, c_mine);
         int n = a.N;                                             // elements of this unit's sums
         if (KEPT) {
             // the unit's kept elements (the full array, est[0]: a.kept is NULL and N <= 32): lane i < M takes the i-th set
@@ -132,21 +197,24 @@ __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
             if (lane > 0 && lane < n) {
                 const int k = e0 * (2 * a.N - e0 - 1) / 2 + (el_mine - e0 - 1);
                 const double tau = a.fs * (a.xij[2 * k] * z0 + a.xij[2 * k + 1] * z1);
-                if (fabs(tau) < BEAM_MAX_DELAY) d_mine = (int)rint(tau);
+                if (fabs(tau) < BEAM_MAX_DELAY) beam_delay_of<TAPS>(tau, d_mine, c_mine);
                 else bad_l = true;                               // (NaN too)
             }
         } else if (lane < a.N) {                                 // N <= 64 = BEAM_MAX_ELEMENTS: one element per lane
             el_mine = a.kept ? a.kept[lane] : lane;
             if (lane > 0) {
                 const double tau = a.fs * (a.xij[2 * (lane - 1)] * z0 + a.xij[2 * (lane - 1) + 1] * z1);
-                if (fabs(tau) < BEAM_MAX_DELAY) d_mine = (int)rint(tau);
+                if (fabs(tau) < BEAM_MAX_DELAY) beam_delay_of<TAPS>(tau, d_mine, c_mine);
                 else bad_l = true;                               // (NaN too)
             }
         }
         const bool bad = __any(bad_l) != 0;
         const double* rowbase = a.filt + (int64_t)row * a.nelem * a.npts_pad;
         double sb = 0.0, st = 0.0;
-        if (coop) beam_sums<BEAM_WAVES * 64>(a, rowbase, s0, W, d_mine, el_mine, n, tid, sb, st);
+        if constexpr (TAPS > 0) {
+            if (coop) beam_sums_steer<BEAM_WAVES * 64, TAPS>(a, rowbase, s0, W, d_mine, c_mine, el_mine, n, tid, sb, st);
+            else beam_sums_steer<64, TAPS>(a, rowbase, s0, W, d_mine, c_mine, el_mine, n, lane, sb, st);
+        } else if (coop) beam_sums<BEAM_WAVES * 64>(a, rowbase, s0, W, d_mine, el_mine, n, tid, sb, st);
         else beam_sums<64>(a, rowbase, s0, W, d_mine, el_mine, n, lane, sb, st);
         sb = nbls_wave::sum_f64(sb);
         st = nbls_wave::sum_f64(st);
@@ -167,6 +235,26 @@ __global__ __launch_bounds__(BEAM_WAVES * 64) void beam_fstat_kernel(BArgs a) {
 
 }  // namespace
 
+#ifdef NBLS_BEAM_STEER
+// the interpolated instances (beam_steer.hip): args is the BArgs nbls_launch_beam below has filled; taps 4, 6 or 8
+namespace {
+template <bool KEPT>
+void steer_launch(int taps, dim3 grid, dim3 block, hipStream_t st, const BArgs& a) {
+    switch (taps) {
+    case 4: hipLaunchKernelGGL((beam_fstat_kernel<KEPT, 4>), grid, block, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((beam_fstat_kernel<KEPT, 6>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((beam_fstat_kernel<KEPT, 8>), grid, block, 0, st, a); break;
+    }
+}
+}  // namespace
+
+hipError_t nbls_launch_beam_steer(int taps, bool kept, dim3 grid, dim3 block, hipStream_t st, const void* args) {
+    const BArgs& a = *(const BArgs*)args;
+    if (kept) steer_launch<true>(taps, grid, block, st, a);
+    else steer_launch<false>(taps, grid, block, st, a);
+    return hipGetLastError();
+}
+#else
 hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& s, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
     const size_t cells = (size_t)h->nbands * h->vector_len;
@@ -188,9 +276,12 @@ hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& s, int64_t u0,
     if (h->kept_beam && &s == &h->est[0]) {                     // the beam of the elements LTS kept (nbls_set_kept_elements)
         if (a.kept || a.N > 32 || !h->d_kept_mask) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
         a.dropped = h->d_kept_mask;
-        hipLaunchKernelGGL(beam_fstat_kernel<true>, grid, block, 0, st, a);
+        if (h->steer_taps) return nbls_launch_beam_steer(h->steer_taps, true, grid, block, st, &a);
+        hipLaunchKernelGGL((beam_fstat_kernel<true, 0>), grid, block, 0, st, a);
     } else {
-        hipLaunchKernelGGL(beam_fstat_kernel<false>, grid, block, 0, st, a);
+        if (h->steer_taps) return nbls_launch_beam_steer(h->steer_taps, false, grid, block, st, &a);
+        hipLaunchKernelGGL((beam_fstat_kernel<false, 0>), grid, block, 0, st, a);
     }
     return hipGetLastError();
 }
+#endif

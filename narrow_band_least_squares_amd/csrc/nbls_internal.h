@@ -160,9 +160,15 @@ struct nbls_handle {
     int grid_n = 0, grid_halo = 0;  // G and H = max |delay| of the plan
     bool grid_map = false;          // the plan keeps the map
     bool grid_valid = false;        // a pass of this plan has run the solve stage: the grid results are there
-    bool grid_attr_set = false;     // the LDS form of beam_grid_kernel has been given its dynamic LDS limit
+    unsigned grid_attr_set = 0;     // the LDS forms of beam_grid_kernel that have been given their dynamic LDS limit (bit taps / 2)
     dev_buf<double> d_grid;         // [G][2]
     dev_buf<int32_t> d_grid_delay;  // [G][nelem]
+    // ---- fractional-sample steering of the beam and the grid (nbls_set_beam_interpolation, steer.h) ----
+    int want_steer_taps = 0;        // nbls_set_beam_interpolation: 0 / 4 / 6 / 8, read by the next nbls_plan
+    int steer_taps = 0;             // the plan's: its beam kernels interpolate with that many taps (0: whole samples)
+    int grid_taps = 0;              // ... and its grid search (steer_taps of a plan with a grid)
+    std::vector<double> h_grid_coef;    // [G][nelem][taps] the plan's coefficient table (h_grid_delay then holds floor(tau))
+    dev_buf<double> d_grid_coef;
     dev_buf<int32_t> d_grid_index;  // [B][VL]
     dev_buf<double> d_grid_fp;      // [2][B][VL]: grid_fstat | grid_power
     dev_buf<double> d_grid_map;     // [B][VL][G] (a plan that asked for the map)
@@ -385,6 +391,8 @@ hipError_t nbls_launch_refine(nbls_handle* h, int64_t u0, int64_t nu, int gW, hi
 size_t nbls_refine_lds_bytes_of(int nelem, int W);
 // beam power and F-statistic of units [u0, u0 + nu) at the slowness estimator x has solved for them (beam.hip)
 hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
+// ... its interpolated instances (beam_steer.hip; taps 4, 6 or 8): args is the argument block nbls_launch_beam has filled
+hipError_t nbls_launch_beam_steer(int taps, bool kept, dim3 grid, dim3 block, hipStream_t st, const void* args);
 // closure of the picked lags of units [u0, u0 + nu), per window and per element of estimator x (closure.hip)
 hipError_t nbls_launch_closure(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // the elements LTS dropped in units [u0, u0 + nu), from estimator 0's unpacked weights (kept.hip)
@@ -408,6 +416,9 @@ hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStre
 size_t nbls_beam_grid_lds_bytes_of(int nelem, int W, int halo);
 // the delay table d[G][nelem] of a grid and its halo (host, un-fused arithmetic); false: some |fs xij . s_g| reaches 2^30
 bool nbls_beam_grid_delays_of(const double* xij, int nelem, double fs, const double* grid, int G, int32_t* d, int* halo);
+// the tables of an interpolated grid plan: n[G][nelem] = floor(tau), c[G][nelem][taps] and the halo max(|n - K + 1|, |n + K|)
+bool nbls_beam_grid_steer_of(const double* xij, int nelem, double fs, const double* grid, int G, int taps, int32_t* n, double* c,
+                             int* halo);
 // Capon / Bartlett spectra of units [u0, u0 + nu) for the plan's full array (capon.hip)
 hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 size_t nbls_capon_lds_bytes_of(int nelem);

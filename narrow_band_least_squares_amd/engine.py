@@ -492,7 +492,7 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
                       host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None,
-                      slowness_grid=None, seed_halfwidths=None, want_consistency=False, want_beam_trace=None):
+                      slowness_grid=None, seed_halfwidths=None, want_consistency=False, want_beam_trace=None, beam_taps=0):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
@@ -504,6 +504,10 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     nor the seeded lag search (``seed_halfwidths``), which rests on it, nor the closure of the picked lags
     (``want_consistency``), which reads the lag table of a whole pass in HBM, nor the beam trace (``want_beam_trace``), which
     reads the filtered band in HBM as the beam results do."""
+    if beam_taps:
+        raise ValueError('beam_taps: a trace of %d x %d samples takes the time-segmented path (not even one filtered band fits '
+                         'the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: fractional-'
+                         'sample steering is not available there' % _shape_of(data))
     if want_beam_trace is not None:
         raise ValueError('want_beam_trace: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
                          'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
@@ -628,7 +632,7 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
            subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None, beam_trace=None):
+           kept=None, beam_trace=None, beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -651,7 +655,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     capon)`` of ``Handle.set_kept_elements``: the plan also names the elements LTS dropped and forms its beam results / Capon
     spectra over the kept ones (likewise).  ``beam_trace``: ``(windows, mdccm_min, kept)`` — one synthesis window per band
     of the Prep, the MdCCM gate (NaN: off) and the kept flag of ``Handle.set_beam_trace``: the plan also forms the beam
-    trace of its rows behind its last solve (for this plan only)."""
+    trace of its rows behind its last solve (for this plan only).  ``beam_taps`` 4, 6 or 8: the plan steers its beam and its
+    slowness grid at fractional-sample delays with that many Lagrange taps (``Handle.set_beam_interpolation``; likewise)
+    and needs ``beam`` or ``beam_grid``; 0: whole-sample delays."""
     if upload:
         if trace_ready:
             pass
@@ -683,6 +689,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_beam_grid(beam_grid, beam_grid_map)
     if lag_seed is not None:
         h.set_lag_seed(lag_seed)
+    if beam_taps:
+        h.set_beam_interpolation(beam_taps)
     peaks = 0
     try:
         if kept is not None:
@@ -711,6 +719,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_beam_grid(None)
         if lag_seed is not None:
             h.set_lag_seed(None)
+        if beam_taps:
+            h.set_beam_interpolation(0)
         if capon is not None:
             h.set_capon(None)
         if peaks:
@@ -1006,7 +1016,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None, kept=None, want_beam_trace=None):
+            capon_peak_floor=0.25, capon_cells=None, kept=None, want_beam_trace=None, beam_taps=0):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -1092,6 +1102,9 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
                          None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0],
                          capon_peaks, capon_peak_floor, capon_cells)
+    planner.check_steering(beam_taps)
+    if beam_taps and not want_beam and sgrid is None:
+        raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
     trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
         want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
@@ -1111,7 +1124,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
                                      group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency,
-                                     None if trace is None else want_beam_trace)
+                                     None if trace is None else want_beam_trace, beam_taps=beam_taps)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
@@ -1123,7 +1136,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace)
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace,
+                                 beam_taps=beam_taps)
     finally:
         if up is not None:
             up.close()
@@ -1357,7 +1371,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None, want_beam_trace=None):
+                  kept=None, want_beam_trace=None, beam_taps=0):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1381,6 +1395,9 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                          prep.W, capon_peaks, capon_peak_floor, capon_cells)
     CG = 0 if capon is None else len(capon['grid'])
     CK = 0 if capon is None else capon.get('peaks', 0)
+    planner.check_steering(beam_taps)
+    if beam_taps and not want_beam and sgrid is None:
+        raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
     trace = _check_beam_trace(want_beam_trace, prep.W, kept)
     tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
@@ -1408,7 +1425,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace)
+                       closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace, beam_taps=beam_taps)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)

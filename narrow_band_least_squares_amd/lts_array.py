@@ -558,6 +558,87 @@ def _beam_trace_keywords(nchans, alpha, npts, fs, window_length, window_overlap,
     return kept_kw, want
 
 
+def _steered_keywords(nchans, alpha, taps, slowness_grid, grid_map, subsample, kept, min_pairs):
+    """The keywords of ``engine.process`` behind the arguments of ``ltsva_steered`` -> (keywords, grid or None);
+    ``ValueError`` before any GPU work."""
+    taps = planner.check_steering(taps)
+    grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
+    for name, flag in (('grid_map', grid_map), ('subsample', subsample), ('kept', kept)):
+        _check_flag(name, flag)
+    if grid_map and grid is None:
+        raise ValueError('grid_map needs slowness_grid')
+    if min_pairs is not None and not kept:
+        raise ValueError('min_pairs needs kept=True')
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    kw = dict(want_beam=True, want_subsample=bool(subsample), slowness_grid=grid, want_grid_map=bool(grid_map), beam_taps=taps)
+    if kept:
+        kw['kept'] = planner.check_kept(nchans, min_pairs, True, False)
+    return kw, grid
+
+
+def _returns_steered(res, nchans, alpha, kw, grid, keys=None):
+    """The returns of ``ltsva_steered`` from a pass made with ``_steered_keywords``."""
+    if 'kept' in kw:
+        out = _returns(res, nchans, alpha, keys) + (_returns_kept(res, nchans, True, {}, n=int(res.nwin[0])),)
+    else:
+        out = _returns_beam(res, nchans, alpha, keys)
+    return out if grid is None else out + _returns_grid(res, grid, kw['want_grid_map'])
+
+
+def ltsva_steered(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, taps=8, slowness_grid=None,
+                  grid_map=False, subsample=False, kept=False, min_pairs=None):
+    """``ltsva_beam`` with the beam steered at fractional-sample delays: every element is read at the delay
+    ``fs xij . z`` itself, through a Lagrange interpolator of ``taps`` (4, 6 or 8) samples around ``floor`` of it, where
+    ``ltsva_beam`` reads the nearest whole sample (DESIGN.md section 22 has the definition).  On an array whose aperture is a
+    few samples of delay the whole-sample beam is piecewise constant in the slowness — many slowness vectors share one row
+    of delays — and its maximum a plateau; the interpolated beam is smooth.  ``planner.steering_error(taps, f / fs)`` is the
+    interpolator's worst-case error on a sinusoid at f: 8 taps stay below 2.4e-5 up to a tenth of the sampling rate, 4 taps
+    below 3.5e-3.  With ``slowness_grid`` (G, 2) s/km the grid search of ``ltsva_grid`` is steered the same way and its five
+    (with ``grid_map=True`` six) returns follow; ``subsample=True`` fits the slowness to the refined lags
+    (``ltsva_subsample``), so the beam is steered by a continuous estimate; ``kept=True`` forms the beam over the elements
+    FAST-LTS kept and returns ``ltsva_kept(beam=True)``'s 9-tuple instead of ``ltsva_beam``'s 10 (``min_pairs`` as there).
+    ``taps=0`` is the whole-sample beam.  Computed on the GPU behind each window's solve (csrc/beam.hip, csrc/beam_grid.hip).
+    Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    nchans = len(st)
+    kw, grid = _steered_keywords(nchans, alpha, taps, slowness_grid, grid_map, subsample, kept, min_pairs)
+    data, fs, t0 = engine.stream_rows(st)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, **kw)
+    return _returns_steered(res, nchans, alpha, kw, grid, getattr(res, 'keys', None))
+
+
+def ltsva_steered_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, taps=8,
+                        slowness_grid=None, grid_map=False, subsample=False, kept=False, min_pairs=None):
+    """``ltsva_steered`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its tuples,
+    element i equal to ``ltsva_steered(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    kw, grid = _steered_keywords(nchans, alpha, taps, slowness_grid, grid_map, subsample, kept, min_pairs)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_steered(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, taps, slowness_grid,
+                              grid_map, subsample, kept, min_pairs)]
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, **kw)
+    return [_returns_steered(res, nchans, alpha, kw, grid) for res in results]
+
+
 def ltsva_beam_trace_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, mdccm_min=None,
                            window='hann', kept=False, min_pairs=None):
     """``ltsva_beam_trace`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,

@@ -92,7 +92,7 @@ def _prefix_stdict(stdict, band_number):
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
                key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-               want_grid_map=False, seed_period_fraction=None, want_consistency=False, capon=None):
+               want_grid_map=False, seed_period_fraction=None, want_consistency=False, capon=None, beam_taps=0):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
@@ -134,7 +134,7 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
                          FILTER_RIPPLE, vector_len=vector_len, host_overlap=host_side, group_done=group_done,
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
                          min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map,
-                         seed_halfwidths=seeds, want_consistency=want_consistency,
+                         seed_halfwidths=seeds, want_consistency=want_consistency, beam_taps=beam_taps,
                          **(capon(rij, fs, len(rows[0]), edges, winlens) if capon is not None else {}))
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
@@ -296,6 +296,45 @@ def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + \
         ((res.grid_map,) if grid_map else ())
+
+
+def narrow_band_least_squares_steered(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                      FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                      taps=8, slowness_grid=None, grid_map=False, subsample=False):
+    """``narrow_band_least_squares_beam`` with the beam steered at fractional-sample delays (``lts_array.ltsva_steered``;
+    DESIGN.md section 22): every element is read at ``fs xij . z`` itself through a Lagrange interpolator of ``taps`` (4, 6
+    or 8) samples instead of at the nearest whole sample; ``planner.steering_error(taps, f / fs)`` is the interpolator's
+    worst-case error in a band at f.  With ``slowness_grid`` (G, 2) s/km the five (with ``grid_map=True`` six) grid returns
+    of ``narrow_band_least_squares_grid`` follow, the grid steered the same way; ``subsample=True`` fits the slowness to the
+    refined lags (``narrow_band_least_squares_subsample``), so that the beam is steered by a continuous estimate.  Returns
+    ``narrow_band_least_squares_beam``'s 11-tuple, then the grid returns.  Bad ``taps``, grid or flags raise ``ValueError``
+    before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
+    taps = planner.check_steering(taps)
+    grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
+    for name, flag in (('grid_map', grid_map), ('subsample', subsample)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError('%s must be True or False, not %r' % (name, flag))
+    if grid_map and grid is None:
+        raise ValueError('grid_map needs slowness_grid')
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=True,
+                                       want_subsample=bool(subsample), slowness_grid=grid, want_grid_map=bool(grid_map),
+                                       beam_taps=taps)
+    out = _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                   w_array, h_array) + (res.beam_power, res.fstat)
+    if grid is None:
+        return out
+    gvel, gbaz = grid_slowness(grid, res.grid_index)
+    computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)
+    return out + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + ((res.grid_map,) if grid_map else ())
 
 
 def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,

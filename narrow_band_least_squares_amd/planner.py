@@ -489,6 +489,52 @@ def check_slowness_grid(grid):
     return g
 
 
+STEER_TAPS = (4, 6, 8)    # Lagrange taps of the fractional-sample steering (nbls_set_beam_interpolation); 0 switches it off
+
+
+def check_steering(taps):
+    """``taps`` of the fractional-sample steering (``nbls_set_beam_interpolation``, DESIGN.md section 22) -> int;
+    ``ValueError`` (before any GPU work) unless it is the integer 0 (off), 4, 6 or 8."""
+    if isinstance(taps, (bool, np.bool_)) or not isinstance(taps, (int, np.integer)) or int(taps) not in (0,) + STEER_TAPS:
+        raise ValueError('taps must be 0 (whole-sample delays), 4, 6 or 8, not %r' % (taps,))
+    return int(taps)
+
+
+def steering_coefficients(taps, mu):
+    """The Lagrange coefficients ``c_k(mu)``, k = -K+1 .. K, K = taps / 2, of the fractional delay ``mu`` in [0, 1) ->
+    (..., taps) float64, in the operation order of the library (csrc/steer.h): the factors ``mu - j`` multiplied for j
+    ascending without k, one division by ``D_k = prod_{j != k} (k - j)``."""
+    taps = check_steering(taps)
+    if not taps:
+        raise ValueError('taps must be 4, 6 or 8')
+    mu = np.asarray(mu, dtype=np.float64)
+    K = taps // 2
+    out = np.empty(mu.shape + (taps,))
+    for k in range(-K + 1, K + 1):
+        p, D = np.ones_like(mu), 1
+        for j in range(-K + 1, K + 1):
+            if j != k:
+                p = p * (mu - np.float64(j))
+                D *= k - j
+        out[..., k + K - 1] = p / np.float64(D)
+    return out
+
+
+def steering_error(taps, f_over_fs):
+    """Worst-case error of the ``taps``-point Lagrange interpolator on a unit sinusoid of frequency ``f_over_fs`` cycles per
+    sample: ``max_mu |sum_k c_k(mu) exp(2 pi i f/fs (k - mu)) - 1|`` over the 101 values mu = 0, 0.01, ..., 1 (DESIGN.md
+    section 22 has the table: 8 taps stay below 2.4e-5 up to a tenth of the sampling rate)."""
+    taps = check_steering(taps)
+    if not taps:
+        raise ValueError('taps must be 4, 6 or 8')
+    K = taps // 2
+    mu = np.arange(101) / 100.0
+    c = steering_coefficients(taps, mu)
+    k = np.arange(-K + 1, K + 1)
+    h = np.sum(c * np.exp(2j * np.pi * float(f_over_fs) * (k[None, :] - mu[:, None])), axis=1)
+    return float(np.max(np.abs(h - 1.0)))
+
+
 def seed_halfwidths(fmax_list, fs, period_fraction=0.5):
     """Per-band half-widths of the seeded lag search (``nbls_set_lag_seed``) -> int32 (nbands,):
     ``K_b = max(1, int(floor(period_fraction * fs / fmax_b)))`` samples — by default half a period of the band's upper edge,
