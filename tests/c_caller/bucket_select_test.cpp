@@ -140,8 +140,33 @@ int main() {
             if (P == 120 && !run_case(keys, h, sample_centre(keys, h, 1023 - 48), 48, 0, g48, "sampled48")) return 1;
         }
     }
-    std::printf("ok %ld mean_passes %.2f max_passes %d gathers %ld | sampled guess, shift0 47: P 120 %.2f (max %d), P 496 %.2f (max %d) | shift0 48: P 120 %.2f (max %d)\n",
+    // the subset sizes of tests/lts_h_cases.py at the pair counts of the bucket kernel: every h of 36 pairs; h(0.5),
+    // h(0.5) + 1, h(0.75), the first h with ALPHA > 0.875, P - 2 and P - 1 beyond.  At h = P - 1 the sample's rank
+    // hs = ceil(h ns / P) is the sample's top rank.  Keys: residuals of a noisy fit, and of an exact fit with a few gross
+    // outliers (more than h keys at rounding level), guess from the sample
+    Stats sweep;
+    for (int P : {36, 66, 120, 253, 276, 496}) {
+        const int n2 = (P + 3) / 2;
+        std::vector<int> hs;
+        if (P == 36) for (int h = n2; h < P; ++h) hs.push_back(h);
+        else {
+            int above = n2;
+            while ((above + 0.5 - (2 * n2 - P)) / (2.0 * (P - n2)) <= 0.875) ++above;
+            hs = {n2, n2 + 1, (int)std::floor(2 * n2 - P + 2 * (P - n2) * 0.75), above, P - 2, P - 1};
+        }
+        for (int h : hs)
+            for (int rep = 0; rep < 60; ++rep) {
+                std::vector<uint64_t> keys(P);
+                const double scale = std::exp2(24.0 * ud(rng) - 20.0);
+                const int nout = rep % 3 == 0 ? 0 : 1 + (int)(rng() % (unsigned)(P - h + 2));      // (also more outliers than P - h)
+                for (int i = 0; i < P; ++i) keys[i] = key_of(nd(rng) * (nout == 0 ? scale : i % (P / nout + 1) == 0 ? 0.35 : 1e-17));
+                for (int shift0 : {47, 44})
+                    if (!run_case(keys, h, sample_centre(keys, h, 1023 - 48), shift0, 0, sweep, "h sweep")) return 1;
+            }
+    }
+    std::printf("ok %ld mean_passes %.2f max_passes %d gathers %ld | sampled guess, shift0 47: P 120 %.2f (max %d), P 496 %.2f (max %d) | shift0 48: P 120 %.2f (max %d)"
+                " | h sweep: %ld selections, max_passes %d\n",
                 all.cases, (double)all.passes / all.cases, all.maxp, all.gathers, (double)s120.passes / s120.cases, s120.maxp,
-                (double)s496.passes / s496.cases, s496.maxp, (double)g48.passes / g48.cases, g48.maxp);
+                (double)s496.passes / s496.cases, s496.maxp, (double)g48.passes / g48.cases, g48.maxp, sweep.cases, sweep.maxp);
     return 0;
 }
