@@ -642,6 +642,63 @@ int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out /* [npts] */)
 int nbls_set_beam_interpolation(nbls_handle* h, int32_t taps);
 int nbls_fetch_beam_grid_coefficients(nbls_handle* h, double* c /* [G][N][taps] */);
 
+/* ---- Each element's delay against the beam of the others ----
+ * The pass can say that an element is wrong (its pairs lose their weight, nbls_set_kept_elements names it); on request it
+ * also says by how much: per window and element the whole-sample shift, within +-K of the modelled delay, at which the
+ * element correlates best with the beam of the other elements, the correlation there and the delay in seconds with a
+ * parabola fraction.  For estimator 0, the unit of result row r (band b; with segments r = b * nseg + s) and window w,
+ * s0 = w * inc, window length W, N = nelem, z the cell's solved slowness as nbls_fetch returns it, K = max_shift[b]:
+ *   model    tau_0 = 0, tau_m = fs * (xij[m-1][0] * z0 + xij[m-1][1] * z1), un-fused; d_m = rint(tau_m), ties to even.  The
+ *            delays are always those against element 0's position, as in the beam trace: row m - 1 of the geometry is pair
+ *            (0, m).  The sign is nbls_set_beam's: element m is read at +d_m.
+ *   bad unit z0 or z1 not finite, or some |tau_m| >= 2^30 over the whole array: delay and cc are NaN and shift is 0 for
+ *            every element.
+ *   samples  y_m(k)[t] = filt[row of m][s0 + t + d_m + k] for t in [0, W), k in [-K, K]; 0.0 where the index is outside
+ *            [0, npts).  The +-K samples beside the window are real trace samples, not zero padding.
+ *   set S    all N elements; with NBLS_ELEMENT_DELAY_KEPT the kept set of nbls_set_kept_elements: the clear bits of
+ *            dropped_mask[cell], the whole array where fewer than 3 elements would remain.
+ *   beam     b[t] = ((0.0 + y_a(0)[t]) + y_b(0)[t]) + ... over S in ascending element order;
+ *            b_m[t] = b[t] - y_m(0)[t] if m is in S, b[t] otherwise: a dropped element is measured against the clean beam
+ *            of the others, and every element, dropped or not, gets results.
+ *   sums     E_b,m = sum_t b_m[t]^2,  E_m(k) = sum_t y_m(k)[t]^2,  C_m(k) = sum_t y_m(k)[t] * b_m[t],
+ *            c_m(k) = C_m(k) / sqrt(E_m(k) * E_b,m).  Plain IEEE: a dead channel or an all-zero beam gives 0/0 = NaN, a NaN
+ *            sample propagates.
+ *   pick     k* = the k with the largest c_m(k) under the total order "c descending, |k| ascending, k ascending"; NaN is
+ *            no candidate; with no candidate shift = 0, cc = NaN, delay = NaN.
+ *   fraction frac = the rule of refine_fraction.h on (c_m(k*-1), c_m(k*), c_m(k*+1)): 0.5 (rm - rp) / ((rm - 2 r0) + rp)
+ *            clamped to [-1/2, 1/2], 0 unless the three are finite and the denominator < 0; 0 where |k*| == K (so K = 0
+ *            always gives 0).
+ *   outputs  shift[m] = k*, cc[m] = c_m(k*), delay[m] = ((((double)(d_m + k*)) + frac) - tau_m) / fs in seconds: positive
+ *            when element m records the beam's waveform later than a plane wave of slowness z predicts.  Subtracting tau_m
+ *            rather than d_m takes the half-sample rounding of the steering out of the result.  Cells beyond nwin[r] and
+ *            outside a window slice are zeros.
+ * Built without FMA contraction, no atomics; the order of every sum depends on (N, S, W, K) alone and nothing on the
+ * launch's unit range: single, streamed (overlap on and off), batched, window-sliced and band-round passes give the same
+ * bits, and so do the two forms of the kernel (staged in LDS / global memory; option "element_delay_form": 0 automatic,
+ * 1 staged — NBLS_ERR_UNSUPPORTED from nbls_plan where a row's block does not fit —, 2 global).
+ *   nbls_set_element_delays(h, max_shift, nbands, flags)   copies the table; read by the next nbls_plan.  max_shift NULL
+ *                            switches it off (the default: such a plan launches exactly what it launched before).
+ *                            NBLS_ERR_ARG, the handle unchanged, for nbands < 1, an entry outside
+ *                            0..NBLS_ELEMENT_DELAY_MAX_SHIFT or unknown flags.  nbls_plan returns NBLS_ERR_ARG if nbands
+ *                            differs from the plan's or N > 32, NBLS_ERR_STATE without a geometry whose rows 0..N-2 are
+ *                            the pairs (0, m) or for NBLS_ELEMENT_DELAY_KEPT without nbls_set_kept_elements,
+ *                            NBLS_ERR_UNSUPPORTED with nbls_set_estimators or an RCCL communicator.  Segments, window
+ *                            ranges, streamed results, bounded, seeded and refined picks, beam, grid, Capon, closure and
+ *                            beam trace are accepted, and so is nbls_set_beam_interpolation: this feature keeps the
+ *                            whole-sample d_m whatever the taps are, the fraction is its own.
+ *   nbls_fetch_element_delays(h, delay, cc, shift)   [rows][vector_len][nelem] each, any may be NULL; waits for the pass as
+ *                            nbls_fetch_beam does.  NBLS_ERR_STATE if the plan did not ask; zeros until a pass of this plan
+ *                            has run the solve stage.
+ *   nbls_element_delay_lds_bytes(nelem, W, max_shift)   pure host function: (nelem * (W + 2 max_shift) + W) * 8, the
+ *                            staged form's rows and b[W], where that is at most 156 KiB; 0: the global form.
+ *                            NBLS_ERR_ARG for nelem < 1, W < 1 or max_shift outside 0..NBLS_ELEMENT_DELAY_MAX_SHIFT.
+ * The kernel runs behind every solve of estimator 0 (behind the kept elements' mask), over the solve's unit range. */
+#define NBLS_ELEMENT_DELAY_KEPT 1          /* beam over the elements LTS kept */
+#define NBLS_ELEMENT_DELAY_MAX_SHIFT 256
+int nbls_set_element_delays(nbls_handle* h, const int32_t* max_shift /* [nbands]; NULL = off */, int32_t nbands, int32_t flags);
+int nbls_fetch_element_delays(nbls_handle* h, double* delay, double* cc, int32_t* shift);   /* [rows][vector_len][nelem] each; any may be NULL */
+int nbls_element_delay_lds_bytes(int32_t nelem, int32_t W, int32_t max_shift);              /* pure host function, like nbls_beam_grid_lds_bytes */
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -35,6 +35,7 @@ EXPORTS = [
     'nbls_set_kept_elements', 'nbls_fetch_kept_elements',
     'nbls_set_beam_trace', 'nbls_fetch_beam_trace',
     'nbls_set_beam_interpolation', 'nbls_fetch_beam_grid_coefficients',
+    'nbls_set_element_delays', 'nbls_fetch_element_delays', 'nbls_element_delay_lds_bytes',
 ]
 STEER_TAPS = (0, 4, 6, 8)  # taps of nbls_set_beam_interpolation (0: whole-sample delays)
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
@@ -47,6 +48,8 @@ CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
 CAPON_PEAKS_MAX = 8      # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
 KEPT_BEAM, KEPT_CAPON = 1, 2      # flags of nbls_set_kept_elements
 BEAM_TRACE_KEPT = 1      # flag of nbls_set_beam_trace
+ELEMENT_DELAY_KEPT = 1   # flag of nbls_set_element_delays (NBLS_ELEMENT_DELAY_KEPT)
+ELEMENT_DELAY_MAX_SHIFT = 256     # largest max_shift of a band (NBLS_ELEMENT_DELAY_MAX_SHIFT)
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -194,6 +197,9 @@ def load_library(path=None):
     lib.nbls_fetch_kept_elements.argtypes = [vp, C.POINTER(C.c_uint32), ip]
     lib.nbls_set_beam_trace.argtypes = [vp, dp, C.c_int64, C.c_double, C.c_int32]
     lib.nbls_fetch_beam_trace.argtypes = [vp, C.c_int32, dp]
+    lib.nbls_set_element_delays.argtypes = [vp, ip, C.c_int32, C.c_int32]
+    lib.nbls_fetch_element_delays.argtypes = [vp, dp, dp, ip]
+    lib.nbls_element_delay_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -608,6 +614,29 @@ class Handle:
         out = np.empty(self.npts)
         self._chk(self.lib.nbls_fetch_beam_trace(self._h, int(row), _dptr(out)))
         return out
+
+    def set_element_delays(self, max_shift=None, kept=False):
+        """The next plans also measure, behind every unit's solve, each element's delay against the beam of the others:
+        the shift within +-``max_shift[b]`` samples (one entry per band of the plan, 0..256) of the delay the solved
+        slowness predicts at which the element correlates best with the sum of the other elements — with ``kept`` of
+        those LTS kept (needs ``set_kept_elements``) — (``nbls_set_element_delays``); None switches
+        that off."""
+        if max_shift is None:
+            self._chk(self.lib.nbls_set_element_delays(self._h, None, 0, 0))
+            return
+        k = np.ascontiguousarray(np.asarray(max_shift).reshape(-1), dtype=np.int32)
+        self._chk(self.lib.nbls_set_element_delays(self._h, k.ctypes.data_as(C.POINTER(C.c_int32)), k.size,
+                                                   ELEMENT_DELAY_KEPT if kept else 0))
+
+    def fetch_element_delays(self):
+        """-> (delay, cc, shift), (rows, vector_len, N) each: seconds, the normalised correlation at the picked shift, and
+        the shift (int32, samples)."""
+        n = max(self._est_elements(0), 1)
+        delay = np.empty((self.nbands, self.vector_len, n))
+        cc = np.empty((self.nbands, self.vector_len, n))
+        shift = np.empty((self.nbands, self.vector_len, n), dtype=np.int32)
+        self._chk(self.lib.nbls_fetch_element_delays(self._h, _dptr(delay), _dptr(cc), shift.ctypes.data_as(C.POINTER(C.c_int32))))
+        return delay, cc, shift
 
     def set_beam_grid(self, grid=None, want_map=False):
         """The next plans also search, per window, the beam F-statistic of the full array over the slowness vectors

@@ -895,6 +895,36 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
             o += a.winlen[b] > 0 ? a.winlen[b] : 0;
         }
     }
+    size_t ed_lds = 0;
+    if (h->want_ed) {                // the element delays (nbls_set_element_delays): estimator 0, one max_shift per band
+        if ((int)h->want_ed_K.size() != a.nbands)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_ed_K.size()) + " shift ranges (nbls_set_element_delays) for a plan of " +
+                                             std::to_string(a.nbands) + " bands");
+        const int En = h->nchans / NS;
+        if (En > 32)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: the element delays (nbls_set_element_delays) take at most 32 elements, not " + std::to_string(En));
+        if (h->nest > 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the element delays (nbls_set_element_delays) are not supported with further estimators (nbls_set_estimators)");
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the element delays (nbls_set_element_delays) are not supported with an RCCL communicator (the gathered block does not carry them)");
+        bool rows = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
+        for (int m = 1; rows && m < En; ++m)
+            if (h->h_pair[2 * (m - 1)] != 0 || h->h_pair[2 * (m - 1) + 1] != m) rows = false;
+        if (!rows)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: the element delays (nbls_set_element_delays) need the geometry of the trace's array, its first rows the pairs (0, m)");
+        if ((h->want_ed_flags & NBLS_ELEMENT_DELAY_KEPT) && h->want_kept_q < 1)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_ELEMENT_DELAY_KEPT (nbls_set_element_delays) needs the kept elements (nbls_set_kept_elements)");
+        // the form: staged where the block of every band fits the LDS of a workgroup (element_delay.hip), else global
+        bool fits = true;
+        for (int b = 0; b < a.nbands; ++b) {
+            const size_t lds = a.winlen[b] > 0 ? nbls_element_delay_lds_bytes_of(En, a.winlen[b], h->want_ed_K[(size_t)b]) : 0;
+            if (!lds) fits = false;
+            if (lds > ed_lds) ed_lds = lds;
+        }
+        if (h->opt.element_delay_form == 1 && !fits)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: option element_delay_form 1: the rows of a band's windows do not fit the LDS of a workgroup");
+        if (!fits || h->opt.element_delay_form == 2) ed_lds = 0;
+    }
     if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
         if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
@@ -927,6 +957,10 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->bt_kept = h->bt && (h->want_bt_flags & NBLS_BEAM_TRACE_KEPT);
     h->bt_min = h->want_bt_min;
     h->bt_valid = false;
+    h->ed = h->want_ed;
+    h->ed_kept = h->ed && (h->want_ed_flags & NBLS_ELEMENT_DELAY_KEPT);
+    h->ed_lds = ed_lds;
+    h->ed_valid = false;
     h->refine = h->want_refine;
     h->frac_valid = false;
     h->solve_ran = false;
@@ -1253,6 +1287,14 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = alloc_copy(h, h->d_bt_off, off.data(), off.size()))) return rc;
         if ((rc = ensure(h, h->d_bt, (size_t)a.R * (size_t)h->npts_pad * sizeof(double)))) return rc;
     }
+    if (h->ed) {                     // the element delays: every row's max_shift and the three grids
+        const size_t vals = (size_t)a.R * a.vector_len * (size_t)a.E;
+        std::vector<int32_t> kb((size_t)a.R);
+        for (int r = 0; r < a.R; ++r) kb[(size_t)r] = h->want_ed_K[(size_t)(r / a.NS)];
+        if ((rc = alloc_copy(h, h->d_ed_K, kb.data(), kb.size()))) return rc;
+        if ((rc = ensure(h, h->d_ed_fp, 2 * vals * sizeof(double)))) return rc;
+        if ((rc = ensure(h, h->d_ed_shift, vals * sizeof(int32_t)))) return rc;
+    }
     if (h->capon_n > 0) {            // the Capon spectra: the band tables and the result buffers, likewise
         const size_t cells = (size_t)a.R * a.vector_len;
         const int E = a.E, G = h->capon_n, nb = a.nbands;
@@ -1392,6 +1434,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if ((stage_mask & 4) && h->closure) h->closure_valid = true;      // (likewise the closure grids)
     if ((stage_mask & 4) && h->kept_q > 0) h->kept_valid = true;     // (... and the kept elements)
     if ((stage_mask & 4) && h->bt) h->bt_valid = true;               // (... and the beam trace)
+    if ((stage_mask & 4) && h->ed) h->ed_valid = true;               // (... and the element delays)
     if (stage_mask & 4) h->solve_ran = true;
     // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
     if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
@@ -1742,6 +1785,46 @@ int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out) {
     if (!h->bt_valid) { memset(out, 0, (size_t)h->npts * sizeof(double)); return NBLS_OK; }
     HIPCHK(h, copy_sync(h, out, h->d_bt + (size_t)row * h->npts_pad, (size_t)h->npts * sizeof(double), hipMemcpyDeviceToHost));
     return NBLS_OK;
+}
+
+int nbls_set_element_delays(nbls_handle* h, const int32_t* max_shift, int32_t nbands, int32_t flags) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!max_shift) { h->want_ed = false; h->want_ed_K.clear(); h->want_ed_flags = 0; return NBLS_OK; }   // off: the next plan measures none
+    if (nbands < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_element_delays: nbands must be at least 1");
+    if (flags & ~NBLS_ELEMENT_DELAY_KEPT) return fail(h, NBLS_ERR_ARG, "nbls_set_element_delays: unknown flags");
+    for (int b = 0; b < nbands; ++b)
+        if (max_shift[b] < 0 || max_shift[b] > NBLS_ELEMENT_DELAY_MAX_SHIFT)
+            return fail(h, NBLS_ERR_ARG, "nbls_set_element_delays: max_shift of band " + std::to_string(b) + " is " + std::to_string(max_shift[b]) +
+                                             ", not in 0.." + std::to_string(NBLS_ELEMENT_DELAY_MAX_SHIFT));
+    h->want_ed = true;                       // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want_ed_K.assign(max_shift, max_shift + nbands);
+    h->want_ed_flags = flags;
+    return NBLS_OK;
+}
+
+int nbls_fetch_element_delays(nbls_handle* h, double* delay, double* cc, int32_t* shift) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_element_delays: no plan");
+    if (!h->ed || !h->d_ed_fp || !h->d_ed_shift) return fail(h, NBLS_ERR_STATE, "nbls_fetch_element_delays: nbls_set_element_delays before nbls_plan");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len, N = (size_t)h->nelem;
+    // written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass without it leaves them
+    // as they are
+    void* outs[3] = {delay, cc, shift};
+    const void* srcs[3] = {h->d_ed_fp.p, h->d_ed_fp.p + cells * N, h->d_ed_shift.p};
+    for (int g = 0; g < 3; ++g) {
+        if (!outs[g]) continue;
+        const size_t row = N * (g == 2 ? sizeof(int32_t) : sizeof(double));
+        if (!h->ed_valid) { memset(outs[g], 0, cells * row); continue; }
+        HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * row, hipMemcpyDeviceToHost));
+        zero_uncomputed(h, outs[g], row);                 // like the grids
+    }
+    return NBLS_OK;
+}
+
+int nbls_element_delay_lds_bytes(int32_t nelem, int32_t W, int32_t max_shift) {
+    if (nelem < 1 || W < 1 || max_shift < 0 || max_shift > NBLS_ELEMENT_DELAY_MAX_SHIFT) return NBLS_ERR_ARG;
+    return (int)nbls_element_delay_lds_bytes_of(nelem, W, max_shift);
 }
 
 int nbls_set_beam_grid(nbls_handle* h, const double* grid, int32_t G, int32_t want_map) {
@@ -2142,6 +2225,8 @@ int nbls_set_option(nbls_handle* h, const char* key, int64_t value) {
         {"filter_nomfma", &nbls_options::filter_nomfma, false},
         {"capon_peak_route", &nbls_options::capon_peak_route, false},
         {"capon_peak_slabs", &nbls_options::capon_peak_slabs, false},
+        {"element_delay_form", &nbls_options::element_delay_form, false},
+        {"element_delay_chunk", &nbls_options::element_delay_chunk, false},
         {"ablate", &nbls_options::ablate, true},
         {"screen_stamps", &nbls_options::screen_stamps, true},
         {"screen_seed", &nbls_options::screen_seed, true},
@@ -2183,6 +2268,10 @@ int nbls_set_option(nbls_handle* h, const char* key, int64_t value) {
             return fail(h, NBLS_ERR_ARG, "option 'capon_peak_route' is 0 (automatic), 1 (LDS) or 2 (HBM)");
         if (k.field == &nbls_options::capon_peak_slabs && (value < 0 || value > 4096))
             return fail(h, NBLS_ERR_ARG, "option 'capon_peak_slabs' is 1..4096 (0: the default)");
+        if (k.field == &nbls_options::element_delay_form && (value < 0 || value > 2))
+            return fail(h, NBLS_ERR_ARG, "option 'element_delay_form' is 0 (automatic), 1 (staged in LDS) or 2 (global memory)");
+        if (k.field == &nbls_options::element_delay_chunk && value != 0 && value != 1 && value != 4)
+            return fail(h, NBLS_ERR_ARG, "option 'element_delay_chunk' is 0 (the default), 1 or 4 shifts per wave and item");
         h->opt.*(k.field) = (int)value;
         h->planned = false;                 // options are read by nbls_plan and by the launchers of the next pass
         return NBLS_OK;

@@ -48,6 +48,8 @@ struct nbls_options {
     int filter_nomfma = 0;     // 1: VALU state kernel
     int capon_peak_route = 0;  // where a unit's maps wait for the peak pick (nbls_set_capon_peaks): 0 auto, 1 LDS, 2 HBM
     int capon_peak_slabs = 0;  // HBM route: workgroups per launch, 1..4096 (0: what 256 MiB hold, 256 .. 4096)
+    int element_delay_chunk = 0;   // shifts of an element a wave of element_delay_kernel takes together: 0 the default (4), 1 or 4; the same bits
+    int element_delay_form = 0;    // where a unit's rows wait for the element delays (nbls_set_element_delays): 0 auto, 1 staged in LDS, 2 global
     // ---- developer build only ----
     int ablate = 0;            // skip parts of the screening / verify kernels (timing; results wrong)
     int screen_stamps = 0;     // s_memtime phase stamps of the screening kernel
@@ -241,6 +243,18 @@ struct nbls_handle {
     dev_buf<double> d_bt;           // [B][npts_pad]
     dev_buf<double> d_bt_win;       // the plan's synthesis windows
     dev_buf<int32_t> d_bt_off;      // [B] where the window of result row r starts in d_bt_win
+    // ---- each element's delay against the beam of the others (nbls_set_element_delays, element_delay.hip) ----
+    bool want_ed = false;           // nbls_set_element_delays: read by the next nbls_plan
+    std::vector<int32_t> want_ed_K; // ... its max_shift, one per band
+    int want_ed_flags = 0;
+    bool ed = false;                // the plan measures the delays behind every solve of estimator 0
+    bool ed_kept = false;           // ... against the beam of the elements LTS kept (NBLS_ELEMENT_DELAY_KEPT)
+    bool ed_valid = false;          // a pass of this plan has run the solve stage: the three grids are there
+    size_t ed_lds = 0;              // dynamic LDS of the staged form (the largest row's block); 0: the global form
+    bool ed_attr_set[4] = {false, false, false, false};   // the staged instances (plain, KEPT; x chunk) have their dynamic LDS limit
+    dev_buf<int32_t> d_ed_K;        // [B] max_shift of the row's band
+    dev_buf<double> d_ed_fp;        // [2][B][VL][N]: delay | cc
+    dev_buf<int32_t> d_ed_shift;    // [B][VL][N]
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -409,6 +423,12 @@ __host__ __device__ inline uint32_t nbls_kept_bits_of(uint32_t dropped, int N, i
 // the beam trace of every result row at the slowness estimator 0 has solved for its windows: one launch per pass, behind
 // the last solve (beam_trace.hip)
 hipError_t nbls_launch_beam_trace(nbls_handle* h, hipStream_t st);
+// each element's delay against the beam of the others in units [u0, u0 + nu), at the slowness estimator 0 has solved for
+// them; behind nbls_launch_kept_elements, whose mask the KEPT form reads (element_delay.hip)
+hipError_t nbls_launch_element_delays(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// dynamic LDS bytes of the staged form of element_delay_kernel for windows of W samples of nelem elements and shifts up to
+// max_shift; 0: the global-memory form
+size_t nbls_element_delay_lds_bytes_of(int nelem, int W, int max_shift);
 // slowness-grid search of the beam F-statistic over units [u0, u0 + nu) for the plan's full array (beam_grid.hip)
 hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 // dynamic LDS bytes of the form beam_grid_kernel takes for windows of W samples of nelem elements and a halo of `halo`

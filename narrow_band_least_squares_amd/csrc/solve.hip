@@ -1436,6 +1436,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
     }
     // the elements LTS dropped (nbls_set_kept_elements): from the plan's own estimator's weights, ahead of what may read them
     if (h->kept_q > 0 && &s == &h->est[0] && (e = nbls_launch_kept_elements(h, u0, nu, st)) != hipSuccess) return e;
+    // each element's delay against the beam of the others (nbls_set_element_delays): estimator 0, behind the mask it may read
+    if (h->ed && &s == &h->est[0] && (e = nbls_launch_element_delays(h, u0, nu, st)) != hipSuccess) return e;
     if (h->beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
     if (h->closure && s.d_closure && (e = nbls_launch_closure(h, s, u0, nu, st)) != hipSuccess) return e;
     // the slowness-grid search of a plan that asked for one: the full array only, behind the plan's own estimator (a plan

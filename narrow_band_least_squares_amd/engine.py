@@ -364,7 +364,7 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
                want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-               want_kept=False, beam_trace_npts=0):
+               want_kept=False, beam_trace_npts=0, want_element_delays=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
@@ -377,7 +377,9 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     complex; with ``capon_peaks`` = K > 0 ``capon_peak_count`` (nbands, vector_len) int32, ``capon_peak_index`` (.., K) int32,
     ``capon_peak_power`` (.., K), ``capon_peak_offset`` (.., K, 2) and the same four with ``bartlett_``; ``want_kept``:
     ``dropped_mask`` (nbands, vector_len) uint32 and ``kept_count`` (nbands, vector_len) int32, the elements LTS dropped;
-    ``beam_trace_npts`` = npts > 0: ``beam_trace`` (nbands, npts), the beam trace of every band; None otherwise."""
+    ``beam_trace_npts`` = npts > 0: ``beam_trace`` (nbands, npts), the beam trace of every band; ``want_element_delays``: ``element_delay`` /
+    ``element_cc`` (nbands, vector_len, nchans) and ``element_shift`` (likewise, int32), each element's delay against the
+    beam of the others; None otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
     K = int(capon_peaks) if capon_points else 0
     peaks = {}
@@ -412,6 +414,9 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      dropped_mask=np.zeros((nb, vector_len), dtype=np.uint32) if want_kept else None,
                      kept_count=np.zeros((nb, vector_len), dtype=np.int32) if want_kept else None,
                      beam_trace=np.zeros((nb, int(beam_trace_npts))) if beam_trace_npts else None,
+                     element_delay=np.zeros((nb, vector_len, nchans)) if want_element_delays else None,
+                     element_cc=np.zeros((nb, vector_len, nchans)) if want_element_delays else None,
+                     element_shift=np.zeros((nb, vector_len, nchans), dtype=np.int32) if want_element_delays else None,
                      lts=alpha < 1.0, fs=fs, **peaks)
 
 
@@ -492,7 +497,8 @@ def filter_band_segmented(h, rows, fs, sos_apply, zero_phase, seg_len):
 def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                       filter_ripple, vector_len, device=None, xcorr_impl=0, want_lag=False, want_cmax=False, want_z=False,
                       host_overlap=None, group_done=None, want_beam=False, want_subsample=False, min_velocity=None,
-                      slowness_grid=None, seed_halfwidths=None, want_consistency=False, want_beam_trace=None, beam_taps=0):
+                      slowness_grid=None, seed_halfwidths=None, want_consistency=False, element_max_shift=None,
+                      want_beam_trace=None, beam_taps=0):
     """The hot path when not even ONE band's filtered trace fits the HBM budget: band by band,
     (1) the band is filtered in time segments with IIR state hand-off (``filter_band_segmented``) and tapered at
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
@@ -503,7 +509,11 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too,
     nor the seeded lag search (``seed_halfwidths``), which rests on it, nor the closure of the picked lags
     (``want_consistency``), which reads the lag table of a whole pass in HBM, nor the beam trace (``want_beam_trace``), which
-    reads the filtered band in HBM as the beam results do."""
+    reads the filtered band in HBM as the beam results do, nor the element delays (``element_max_shift``), likewise."""
+    if element_max_shift is not None:
+        raise ValueError('element_max_shift: a trace of %d x %d samples takes the time-segmented path (not even one filtered '
+                         'band fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the '
+                         'host: the element delays are not available there' % _shape_of(data))
     if beam_taps:
         raise ValueError('beam_taps: a trace of %d x %d samples takes the time-segmented path (not even one filtered band fits '
                          'the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: fractional-'
@@ -632,7 +642,7 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
            subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None, beam_trace=None, beam_taps=0):
+           kept=None, element_delays=None, element_delays_kept=False, beam_trace=None, beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -657,7 +667,10 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     of the Prep, the MdCCM gate (NaN: off) and the kept flag of ``Handle.set_beam_trace``: the plan also forms the beam
     trace of its rows behind its last solve (for this plan only).  ``beam_taps`` 4, 6 or 8: the plan steers its beam and its
     slowness grid at fractional-sample delays with that many Lagrange taps (``Handle.set_beam_interpolation``; likewise)
-    and needs ``beam`` or ``beam_grid``; 0: whole-sample delays."""
+    and needs ``beam`` or ``beam_grid``; 0: whole-sample delays.  ``element_delays``: one shift range in samples per band
+    of the Prep: the plan also measures each element's delay against the beam of the others behind every solve, with
+    ``element_delays_kept`` against the beam of the elements LTS kept, which needs ``kept`` (``Handle.set_element_delays``,
+    ``planner.element_shifts``; for this plan only)."""
     if upload:
         if trace_ready:
             pass
@@ -695,6 +708,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     try:
         if kept is not None:
             h.set_kept_elements(*kept)
+        if element_delays is not None:
+            h.set_element_delays(np.asarray(element_delays)[idx], element_delays_kept)
         if beam_trace is not None:
             wins, gate, bt_kept = beam_trace
             h.set_beam_trace(np.concatenate([wins[int(i)] for i in idx]), None if gate != gate else gate, bt_kept)
@@ -727,6 +742,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon_peaks(None)
         if kept is not None:
             h.set_kept_elements(0)
+        if element_delays is not None:
+            h.set_element_delays(None)
         if beam_trace is not None:
             h.set_beam_trace(None)
         if window_slice is not None:
@@ -865,6 +882,8 @@ def collect(res, h, b0, b1, streamed, note):
                 getattr(res, name + field)[b0:b1] = a
     if res.dropped_mask is not None:
         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = h.fetch_kept_elements()
+    if res.element_delay is not None:
+        res.element_delay[b0:b1], res.element_cc[b0:b1], res.element_shift[b0:b1] = h.fetch_element_delays()
     if res.beam_trace is not None:
         for b in range(b0, b1):
             res.beam_trace[b] = h.fetch_beam_trace(b - b0)
@@ -894,6 +913,7 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
     seed_all = launch_kw.get('lag_seed')
     capon_all = launch_kw.get('capon')
     trace_all = launch_kw.get('beam_trace')
+    shift_all = launch_kw.get('element_delays')
     nchans, npts = _shape_of(data)
     for g, (b0, b1) in enumerate(bounds):
         prep = prepare(nchans, npts, res.fs, rij, band_edges[b0:b1], winlens[b0:b1], *prep_tail, common=prep,
@@ -916,6 +936,8 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
             launch_kw = dict(launch_kw, capon=dict(capon_all, **{k: capon_all[k][b0:b1] for k in ('freqs', 'snap_len', 'snap_hop')}))
         if trace_all is not None:                         # (likewise the synthesis windows)
             launch_kw = dict(launch_kw, beam_trace=(trace_all[0][b0:b1],) + tuple(trace_all[1:]))
+        if shift_all is not None:                         # (likewise the shift ranges of the element delays)
+            launch_kw = dict(launch_kw, element_delays=shift_all[b0:b1])
         try:
             launch(h, data, prep, trace_from=launched[0][0] if (launched and not sequential) else None, trace_ready=early,
                    after=launched[-1][0] if ordered else None, stream=streamed,
@@ -990,6 +1012,25 @@ def _check_kept(nchans, kept, want_beam, capon):
     return q, kb, kc
 
 
+def _check_element_delays(max_shift, delays_kept, nbands, nchans, kept):
+    """``element_max_shift`` / ``element_delays_kept`` of ``process`` / ``process_batch`` -> the int32 shift range of every
+    band, or None; ``ValueError`` before any GPU work (``planner.check_element_shifts``).  ``kept``: the call's checked
+    ``kept`` tuple or None."""
+    if not isinstance(delays_kept, (bool, np.bool_)):
+        raise ValueError('element_delays_kept must be True or False, not %r' % (delays_kept,))
+    if max_shift is None:
+        if delays_kept:
+            raise ValueError('element_delays_kept needs element_max_shift')
+        return None
+    shifts = planner.check_element_shifts(max_shift, nbands)
+    if nchans > 32:
+        raise ValueError('the element delays take at most 32 array elements, not %d' % nchans)
+    if delays_kept and kept is None:
+        raise ValueError('element_delays_kept: the beam of the kept elements needs a plan that names them (kept=, '
+                         'planner.check_kept)')
+    return shifts
+
+
 def _check_beam_trace(want, W, kept, window_slice=None):
     """``want_beam_trace`` of ``process`` / ``process_batch`` — None / False, True, a window kind or a dict of ``window``,
     ``mdccm_min``, ``kept`` — -> the ``beam_trace`` tuple of ``launch`` (one synthesis window per band, the gate, the kept flag)
@@ -1016,7 +1057,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None, kept=None, want_beam_trace=None, beam_taps=0):
+            capon_peak_floor=0.25, capon_cells=None, kept=None, element_max_shift=None, element_delays_kept=False,
+            want_beam_trace=None, beam_taps=0):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -1076,6 +1118,12 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     elements LTS kept in it (``nbls_set_beam_trace``).  Formed on the GPU behind the last solve of every
     pass, fetched per HBM round.  ``ValueError`` before any GPU work (``planner.check_beam_trace``); ``process_segmented``
     refuses it, and so does a ``window_slice``.
+    element_max_shift = K, one integer in 0..256 or one per band: also ``res.element_delay`` / ``res.element_cc`` /
+    ``res.element_shift`` (nbands, vector_len, N): per window and element the delay in seconds, the normalised correlation and
+    the whole-sample shift, within +-K samples of the delay the solved slowness predicts, at which the element correlates
+    best with the sum of the other elements; with ``element_delays_kept`` (needs ``kept=``) with the sum of those LTS kept
+    (``nbls_set_element_delays``, DESIGN.md section 23; ``planner.element_shifts`` makes K).  ``ValueError`` before any GPU work;
+    ``process_segmented`` refuses it.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -1106,6 +1154,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     if beam_taps and not want_beam and sgrid is None:
         raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
+    shifts = _check_element_delays(element_max_shift, element_delays_kept, len(band_edges), nchans, kept)
     trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
         want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
     if cap < 1 and not prefiltered and kept is not None:
@@ -1124,20 +1173,21 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                      filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
                                      group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency,
-                                     None if trace is None else want_beam_trace, beam_taps=beam_taps)
+                                     shifts, None if trace is None else want_beam_trace, beam_taps=beam_taps)
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
                          0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
-                         0 if capon is None else capon.get('peaks', 0), kept is not None, npts if trace is not None else 0)
+                         0 if capon is None else capon.get('peaks', 0), kept is not None, npts if trace is not None else 0,
+                         shifts is not None)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace,
-                                 beam_taps=beam_taps)
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, element_delays=shifts,
+                                 element_delays_kept=bool(element_delays_kept), beam_trace=trace, beam_taps=beam_taps)
     finally:
         if up is not None:
             up.close()
@@ -1371,7 +1421,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None, want_beam_trace=None, beam_taps=0):
+                  kept=None, element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1399,6 +1449,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     if beam_taps and not want_beam and sgrid is None:
         raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
+    shifts = _check_element_delays(element_max_shift, element_delays_kept, nb, nchans, kept)
     trace = _check_beam_trace(want_beam_trace, prep.W, kept)
     tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
     limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
@@ -1409,7 +1460,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
                       grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
                       want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK,
-                      want_kept=kept is not None, beam_trace_npts=npts if trace is not None else 0)
+                      want_kept=kept is not None, beam_trace_npts=npts if trace is not None else 0,
+                      want_element_delays=shifts is not None)
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1425,7 +1477,9 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon, kept=kept, beam_trace=trace, beam_taps=beam_taps)
+                       closure=bool(want_consistency), capon=capon, kept=kept,
+                       element_delays=shifts, element_delays_kept=bool(element_delays_kept),
+                       beam_trace=trace, beam_taps=beam_taps)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
@@ -1441,6 +1495,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
                 cpk = [[a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_peaks(which)] for which in (0, 1)] if CK else None
                 kel = [a.reshape(b1 - b0, k, VL) for a in h.fetch_kept_elements()] if kept is not None else None
+                eld = [a.reshape(b1 - b0, k, VL, nchans) for a in h.fetch_element_delays()] if shifts is not None else None
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
@@ -1467,6 +1522,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                                 getattr(res, name + field)[b0:b1] = a[:, j]
                     if kel is not None:
                         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = [a[:, j] for a in kel]
+                    if eld is not None:
+                        res.element_delay[b0:b1], res.element_cc[b0:b1], res.element_shift[b0:b1] = [a[:, j] for a in eld]
                     if trace is not None:
                         for b in range(b0, b1):
                             res.beam_trace[b] = h.fetch_beam_trace((b - b0) * k + j)

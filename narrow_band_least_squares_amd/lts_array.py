@@ -661,3 +661,83 @@ def ltsva_beam_trace_batch(streams, lat_list, lon_list, window_length, window_ov
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
                                    want_uncert=True, kept=kept_kw, want_beam_trace=want)
     return [_returns(res, nchans, alpha) + (res.beam_trace[0].copy(),) for res in results]
+
+
+def _element_delay_keywords(nchans, alpha, max_shift, kept, min_pairs):
+    """The keywords of ``engine.process`` behind the arguments of ``ltsva_element_delays``; ``ValueError`` before any GPU
+    work."""
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    _check_flag('kept', kept)
+    if min_pairs is not None and not kept:
+        raise ValueError('min_pairs needs kept=True')
+    if max_shift is None:
+        raise ValueError('max_shift is required: an already filtered stream names no band whose upper edge could set the '
+                         'shift range (planner.element_shifts(fmax, fs) makes one)')
+    kept_kw = planner.check_kept(nchans, min_pairs, False, False) if kept else None
+    shifts = engine._check_element_delays(max_shift, bool(kept), 1, nchans, kept_kw)
+    return dict(kept=kept_kw, element_max_shift=shifts, element_delays_kept=bool(kept))
+
+
+def _returns_element_delays(res, nchans, alpha, kept, keys=None):
+    """The returns of ``ltsva_element_delays`` from a pass made with ``_element_delay_keywords``."""
+    n = int(res.nwin[0])
+    out = _returns(res, nchans, alpha, keys) + (res.element_delay[0, :n].copy(), res.element_cc[0, :n].copy(),
+                                                res.element_shift[0, :n].copy())
+    if kept:
+        mask = res.dropped_mask[0, :n].copy()
+        out += (mask, res.kept_count[0, :n].copy())
+    return out
+
+
+def ltsva_element_delays(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, max_shift=None, kept=False,
+                         min_pairs=None):
+    """``ltsva`` followed by each element's delay against the beam of the others: per window and element the shift, within
+    ``max_shift`` samples (0..256; ``planner.element_shifts(fmax, fs)`` gives half a period of the band's upper edge) either
+    side of the delay the solved slowness predicts, at which the element correlates best with the sum of the other
+    elements steered at that slowness.  Returns ``ltsva``'s 8-tuple followed by ``element_delay`` (nwin, N) in seconds —
+    the shift plus a parabola fraction, positive where the element records the beam's waveform later than the plane wave
+    predicts: a clock step, or the station static of a healthy array —, ``element_cc`` (nwin, N), the normalised
+    correlation there, and ``element_shift`` (nwin, N) int32.  ``kept=True`` (LTS, ``alpha < 1``): the beam is summed over
+    the elements FAST-LTS kept in the window (``ltsva_kept``; ``min_pairs`` as there), so a dropped element is measured
+    against a beam it has not biased, and ``dropped_mask`` (nwin,) uint32 and ``kept_count`` (nwin,) int32 follow.  The
+    stream is already filtered and names no band, so ``max_shift`` is required.  DESIGN.md section 23 has the definition;
+    computed on the GPU behind each window's solve (csrc/element_delay.hip).  Whatever the library would refuse raises
+    ``ValueError`` before any GPU work."""
+    nchans = len(st)
+    kw = _element_delay_keywords(nchans, alpha, max_shift, kept, min_pairs)
+    data, fs, t0 = engine.stream_rows(st)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, **kw)
+    return _returns_element_delays(res, nchans, alpha, kept, getattr(res, 'keys', None))
+
+
+def ltsva_element_delays_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, max_shift=None,
+                               kept=False, min_pairs=None):
+    """``ltsva_element_delays`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its
+    tuples, element i equal to ``ltsva_element_delays(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    kw = _element_delay_keywords(nchans, alpha, max_shift, kept, min_pairs)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_element_delays(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, max_shift, kept,
+                                     min_pairs)]
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, **kw)
+    return [_returns_element_delays(res, nchans, alpha, kept) for res in results]

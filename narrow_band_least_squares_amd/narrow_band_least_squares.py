@@ -92,13 +92,16 @@ def _prefix_stdict(stdict, band_number):
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
                key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-               want_grid_map=False, seed_period_fraction=None, want_consistency=False, capon=None, beam_taps=0):
+               want_grid_map=False, seed_period_fraction=None, want_consistency=False, capon=None, beam_taps=0,
+               process_keywords=None):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
     narrow_band_least_squares.py:78-80), the BT caution (:83-87) and the text of the ``stdict`` time
     keys — runs while the pass is in flight (``host_overlap`` of ``engine.process``).  The traces are
-    uploaded row by row from the stream's own buffers."""
+    uploaded row by row from the stream's own buffers.  ``capon`` / ``process_keywords``: a function of (rij, fs, npts,
+    edges, winlens) that returns further keywords of ``engine.process`` — the Capon tables, which need the call's own band
+    edges, through the first, any other feature's through the second."""
     rows, fs, t0 = engine.stream_rows(st)
     if rij is None:
         rij = get_rij(lat_list, lon_list, len(rows))
@@ -135,7 +138,8 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
                          min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map,
                          seed_halfwidths=seeds, want_consistency=want_consistency, beam_taps=beam_taps,
-                         **(capon(rij, fs, len(rows[0]), edges, winlens) if capon is not None else {}))
+                         **(capon(rij, fs, len(rows[0]), edges, winlens) if capon is not None else {}),
+                         **(process_keywords(rij, fs, len(rows[0]), edges, winlens) if process_keywords is not None else {}))
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -850,3 +854,48 @@ def narrow_band_least_squares_beam_trace(WINLEN_list, WINOVER, ALPHA, st, lat_li
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (res.beam_trace,)
+
+
+def narrow_band_least_squares_element_delays(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                             FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                             max_shift=None, kept=False, min_pairs=None):
+    """``narrow_band_least_squares`` followed by a dict of each element's delay against the beam of the others, per band:
+    ``element_delay`` / ``element_cc`` (NBANDS, vector_len, N) and ``element_shift`` (likewise, int32) — per window and
+    element the delay in seconds, the normalised correlation and the whole-sample shift at which the element correlates
+    best with the sum of the other elements steered at the window's solved slowness, searched within ``max_shift``
+    samples either side of the modelled delay (``lts_array.ltsva_element_delays``).  ``max_shift``: one
+    integer in 0..256 or one per band; None: ``planner.element_shifts`` of every band's upper edge, half a period.
+    ``kept=True`` (``ALPHA < 1``): the beam is that of the elements FAST-LTS kept in the window (``min_pairs`` as in
+    ``lts_array.ltsva_kept``), and the dict also holds ``dropped_mask`` / ``kept_count`` (NBANDS, vector_len).  The first nine
+    returns are those of ``narrow_band_least_squares``.  Whatever the library would refuse raises ``ValueError`` before any
+    GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
+        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
+                         'squares' % len(st))
+    if not isinstance(kept, (bool, np.bool_)):
+        raise ValueError('kept must be True or False, not %r' % (kept,))
+    if min_pairs is not None and not kept:
+        raise ValueError('min_pairs needs kept=True')
+    kept_kw = planner.check_kept(len(st), min_pairs, False, False) if kept else None
+    if max_shift is not None:
+        engine._check_element_delays(max_shift, bool(kept), NBANDS, len(st), kept_kw)
+    elif len(st) > 32:
+        raise ValueError('the element delays take at most 32 array elements, not %d' % len(st))
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    bands = list(range(NBANDS))
+
+    def keywords(rij_, fs, npts, edges, winlens):           # (the keywords that ride into ``engine.process``)
+        shifts = max_shift if max_shift is not None else planner.element_shifts([e[1] for e in edges], fs)
+        return dict(kept=kept_kw, element_max_shift=shifts, element_delays_kept=bool(kept))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], process_keywords=keywords)
+    out = dict(element_delay=res.element_delay, element_cc=res.element_cc, element_shift=res.element_shift)
+    if kept:
+        out.update(dropped_mask=res.dropped_mask, kept_count=res.kept_count)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (out,)

@@ -832,3 +832,33 @@ def check_beam_trace(W, window='hann', mdccm_min=None, kept=False, has_kept=Fals
             raise ValueError('the synthesis window of band %d is all zero' % b)
         o += int(w)
     return np.ascontiguousarray(table, dtype=np.float64), gate, bool(kept)
+
+
+ELEMENT_DELAY_MAX_SHIFT = 256      # NBLS_ELEMENT_DELAY_MAX_SHIFT
+
+
+def element_shifts(fmax_list, fs, period_fraction=0.5):
+    """Per-band shift ranges of the element delays (``nbls_set_element_delays``) -> int32 (nbands,):
+    ``min(seed_halfwidths(fmax_list, fs, period_fraction), 256)`` samples — by default half a period of the band's upper
+    edge either side of the modelled delay, so that the neighbouring cycle stays outside the range."""
+    return np.minimum(seed_halfwidths(fmax_list, fs, period_fraction), ELEMENT_DELAY_MAX_SHIFT).astype(np.int32)
+
+
+def check_element_shifts(max_shift, nbands):
+    """``max_shift`` of the element delays (samples; one integer for every band, or ``nbands`` of them) -> int32
+    (nbands,); ``ValueError`` (before any GPU work) unless the entries are integers in 0 .. 256 and their number fits."""
+    if isinstance(nbands, (bool, np.bool_)) or not isinstance(nbands, (int, np.integer)) or int(nbands) < 1:
+        raise ValueError('nbands must be a positive integer, not %r' % (nbands,))
+    try:
+        k = np.asarray(max_shift)
+    except Exception:
+        raise ValueError('max_shift must be an integer or a list of integers, one per band')
+    if k.dtype == object or k.dtype.kind not in 'iu' or k.ndim > 1 or k.size < 1:
+        raise ValueError('max_shift must be an integer or a list of integers, one per band, not %r' % (max_shift,))
+    if k.ndim == 0:
+        k = np.full(int(nbands), int(k))
+    if k.size != int(nbands):
+        raise ValueError('%d shift ranges for %d bands' % (k.size, int(nbands)))
+    if (k < 0).any() or (k > ELEMENT_DELAY_MAX_SHIFT).any():
+        raise ValueError('max_shift must lie in 0..%d samples, not %r' % (ELEMENT_DELAY_MAX_SHIFT, max_shift))
+    return np.ascontiguousarray(k, dtype=np.int32)
