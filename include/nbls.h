@@ -699,6 +699,60 @@ int nbls_set_element_delays(nbls_handle* h, const int32_t* max_shift /* [nbands]
 int nbls_fetch_element_delays(nbls_handle* h, double* delay, double* cc, int32_t* shift);   /* [rows][vector_len][nelem] each; any may be NULL */
 int nbls_element_delay_lds_bytes(int32_t nelem, int32_t W, int32_t max_shift);              /* pure host function, like nbls_beam_grid_lds_bytes */
 
+/* ---- A window's arrivals and their powers by CLEAN-SC ----
+ * A Bartlett peak list is mostly sidelobes and a Capon power depends on the loading.  CLEAN-SC (Sijtsma 2007) takes the
+ * Bartlett maximum of R, removes from R everything coherent with that beam, and repeats on the residual; it needs no
+ * loading, no factor and no point-spread model, and the residual stays positive semidefinite.  A plan with nbls_set_capon
+ * may carry a CLEAN request: iterations 1 <= I <= 32 (NBLS_CAPON_CLEAN_MAX), a gain phi in (0, 1], a floor f in [0, 1),
+ * flags (NBLS_CLEAN_RESIDUAL).  It applies to estimator 0 and uses the grid, the steering table a[g], R and the units of
+ * nbls_set_capon; with NBLS_KEPT_CAPON it uses R_K and the kept rows of a exactly as the spectra do, M in the place of N.
+ * Per unit, R_0 = R:
+ *   degenerate  (t = 0, t NaN or a NaN entry, as for the spectra) count = 0, every rank -1 / NaN, total and residual NaN.
+ *   total    t_0 / N,  t_0 = sum_i Re R_0,ii in ascending i.
+ *   scan     iteration i = 0 .. I-1: P_i(g) is the Bartlett spectrum of nbls_set_capon on R_i, the same operations in the
+ *            same order as the spectra's kernel; g_i its arg-max under "P descending, g ascending" (NaN is no candidate),
+ *            p_i = P_i(g_i).
+ *   stop     count = i if there is no candidate, if p_i > 0 is not true, or if i > 0 and p_i < f * p_0 (one
+ *            multiplication).
+ *   update   with a = a[g_i], every sum from 0 in ascending index, fma(x, y, z) = x * y + z rounded once:
+ *            v_j:  vr = fma(Rr_jk, ar_k, vr); vr = fma(-Ri_jk, ai_k, vr); vi = fma(Rr_jk, ai_k, vi); vi = fma(Ri_jk, ar_k, vi)
+ *                  over k  (v = R_i a)
+ *            q:    q = fma(ar_j, vr_j, q); q = fma(ai_j, vi_j, q)  over j  (q = Re(a^H v))
+ *            count = i if q > 0 is not true or q is not finite;  s = phi / q
+ *            for j >= k:  wr = fma(vi_j, vi_k, vr_j * vr_k);  wi = fma(vi_j, vr_k, -(vr_j * vi_k))   (w = v_j conj(v_k))
+ *                  Re R_{i+1},jk = fma(-wr, s, Re R_i,jk);  Im R_{i+1},jk = fma(-wi, s, Im R_i,jk)
+ *            the imaginary part of the diagonal is 0.0 and the upper triangle the conjugate, bit for bit
+ *            index[i] = g_i, power[i] = phi * p_i
+ *   count    I where no rule fired; ranks at or beyond count are -1 / NaN.
+ *   residual sum_i Re R_count,ii / N (M with the kept elements), ascending i.
+ *   NBLS_CLEAN_RESIDUAL  R_count is kept, [N][N][2]; with the kept elements it is scattered back to the elements' own rows
+ *            and columns, zeros for the dropped ones.  A degenerate unit returns its R_0.
+ * Rank 0 is bartlett_index, and power[0] == phi * bartlett_power, bit for bit.  The results of a plan with I' < I are the
+ * first I' ranks of the plan with I, count = min(count, I').  In exact arithmetic R_i stays positive semidefinite and its
+ * trace does not grow.  No atomics, every order total, nothing depends on the launch's unit range: single, streamed,
+ * batched, window-sliced and round-split passes give the same bits.
+ *   nbls_set_capon_clean(h, iterations, gain, floor, flags)   read by the next nbls_plan; 0 iterations switches it off (the
+ *                            default: such a plan launches exactly what it launched before).  NBLS_ERR_ARG, the handle
+ *                            unchanged, for iterations outside 0..32, a gain outside (0, 1], a floor outside [0, 1), NaN, or
+ *                            unknown flags.  nbls_plan returns NBLS_ERR_STATE without nbls_set_capon; whatever nbls_set_capon
+ *                            refuses stays refused.  It combines with the maps, the peaks on either route, the kept
+ *                            elements, segments, window ranges and streamed results.
+ *   nbls_fetch_capon_clean(h, count, index, power, total, residual)   count, total, residual [rows][vector_len]; index and
+ *                            power [rows][vector_len][I]; any may be NULL.  Rows, waiting, NBLS_ERR_STATE and zeros as for
+ *                            nbls_fetch_capon.
+ *   nbls_fetch_capon_clean_csdm(h, R)   [rows][vector_len][N][N][2]; NBLS_ERR_STATE without NBLS_CLEAN_RESIDUAL.
+ *   nbls_capon_clean_lds_bytes(nelem)   pure host function: (2 N^2 + 2 N + 2 * 128 * N) * 8, the kernel's dynamic LDS (R, v
+ *                            and a column of a per lane); NBLS_ERR_ARG for nelem outside 1..32.
+ * capon_clean_kernel (csrc/capon_clean.hip) runs behind the spectra's kernel on the same stream over the same units, one
+ * workgroup of NBLS_CAPON_THREADS per unit; it reads R from the plan's matrix buffer, which such a plan holds on the device
+ * whether or not NBLS_CAPON_CSDM was asked.  nbls_timings is unchanged. */
+#define NBLS_CAPON_CLEAN_MAX 32
+#define NBLS_CLEAN_RESIDUAL 1
+int nbls_set_capon_clean(nbls_handle* h, int32_t iterations, double gain, double floor, int32_t flags);
+int nbls_fetch_capon_clean(nbls_handle* h, int32_t* count, int32_t* index, double* power, double* total, double* residual);
+int nbls_fetch_capon_clean_csdm(nbls_handle* h, double* R);
+int nbls_capon_clean_lds_bytes(int32_t nelem);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -32,6 +32,7 @@ EXPORTS = [
     'nbls_set_closure', 'nbls_fetch_closure', 'nbls_est_fetch_closure',
     'nbls_set_capon', 'nbls_fetch_capon', 'nbls_fetch_capon_maps', 'nbls_fetch_capon_csdm', 'nbls_fetch_capon_tables',
     'nbls_set_capon_peaks', 'nbls_fetch_capon_peaks',
+    'nbls_set_capon_clean', 'nbls_fetch_capon_clean', 'nbls_fetch_capon_clean_csdm', 'nbls_capon_clean_lds_bytes',
     'nbls_set_kept_elements', 'nbls_fetch_kept_elements',
     'nbls_set_beam_trace', 'nbls_fetch_beam_trace',
     'nbls_set_beam_interpolation', 'nbls_fetch_beam_grid_coefficients',
@@ -46,6 +47,8 @@ CAPON_THREADS = 128      # threads of a workgroup of the Capon kernel, one grid 
 CAPON_CHUNK = 32         # snapshots that go through LDS together (NBLS_CAPON_CHUNK)
 CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
 CAPON_PEAKS_MAX = 8      # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
+CAPON_CLEAN_MAX = 32     # iterations of a CLEAN request (NBLS_CAPON_CLEAN_MAX)
+CLEAN_RESIDUAL = 1       # flag of nbls_set_capon_clean (NBLS_CLEAN_RESIDUAL)
 KEPT_BEAM, KEPT_CAPON = 1, 2      # flags of nbls_set_kept_elements
 BEAM_TRACE_KEPT = 1      # flag of nbls_set_beam_trace
 ELEMENT_DELAY_KEPT = 1   # flag of nbls_set_element_delays (NBLS_ELEMENT_DELAY_KEPT)
@@ -193,6 +196,10 @@ def load_library(path=None):
     lib.nbls_fetch_capon_tables.argtypes = [vp, C.c_int32, dp, dp]
     lib.nbls_set_capon_peaks.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_double]
     lib.nbls_fetch_capon_peaks.argtypes = [vp, C.c_int32, ip, ip, dp, dp]
+    lib.nbls_set_capon_clean.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_int32]
+    lib.nbls_fetch_capon_clean.argtypes = [vp, ip, ip, dp, dp, dp]
+    lib.nbls_fetch_capon_clean_csdm.argtypes = [vp, dp]
+    lib.nbls_capon_clean_lds_bytes.argtypes = [C.c_int32]
     lib.nbls_set_kept_elements.argtypes = [vp, C.c_int32, C.c_int32]
     lib.nbls_fetch_kept_elements.argtypes = [vp, C.POINTER(C.c_uint32), ip]
     lib.nbls_set_beam_trace.argtypes = [vp, dp, C.c_int64, C.c_double, C.c_int32]
@@ -307,6 +314,7 @@ class Handle:
         self._want_taps = self.taps = 0       # taps of set_beam_interpolation / of the plan
         self._want_capon = self.capon = None  # (G, snapshot lengths) of set_capon / of the plan
         self._want_capon_peaks = self.capon_peaks = 0     # K of set_capon_peaks / of the plan
+        self._want_capon_clean = self.capon_clean = 0     # I of set_capon_clean / of the plan
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -435,6 +443,7 @@ class Handle:
         self.taps = self._want_taps
         self.capon = self._want_capon
         self.capon_peaks = self._want_capon_peaks
+        self.capon_clean = self._want_capon_clean if self.capon else 0
 
     def set_option(self, key, value):
         """Per-handle implementation switch (``nbls_set_option``; identical results unless the library is the
@@ -704,6 +713,37 @@ class Handle:
         off = np.empty((self.nbands, self.vector_len, K, 2))
         self._chk(self.lib.nbls_fetch_capon_peaks(self._h, int(which), _iptr(cnt), _iptr(idx), _dptr(pw), _dptr(off)))
         return cnt, idx, pw, off
+
+    def set_capon_clean(self, iterations, gain=0.5, floor=0.02, residual=False):
+        """The next plans (with ``set_capon``) also resolve every window's arrivals by CLEAN-SC: up to ``iterations`` (1..32)
+        times the Bartlett maximum of the cross-spectral matrix is taken and ``gain`` in (0, 1] of everything coherent with
+        that beam removed from the matrix, until the maximum falls below ``floor`` in [0, 1) times the first one
+        (``nbls_set_capon_clean``); ``residual``: the plan also keeps the matrix that is left.
+        ``iterations=0`` switches it off again."""
+        if not iterations:
+            self._chk(self.lib.nbls_set_capon_clean(self._h, 0, 0.0, 0.0, 0))
+            self._want_capon_clean = 0
+            return
+        self._chk(self.lib.nbls_set_capon_clean(self._h, int(iterations), float(gain), float(floor), CLEAN_RESIDUAL if residual else 0))
+        self._want_capon_clean = int(iterations)
+
+    def fetch_capon_clean(self):
+        """The CLEAN-SC components -> (count int32 (rows, vector_len), index int32 (rows, vector_len, I), power (rows,
+        vector_len, I), total (rows, vector_len), residual (rows, vector_len))."""
+        n = max(self.capon_clean, 1)
+        cnt = np.empty((self.nbands, self.vector_len), dtype=np.int32)
+        idx = np.empty((self.nbands, self.vector_len, n), dtype=np.int32)
+        pw = np.empty((self.nbands, self.vector_len, n))
+        tr = np.empty((2, self.nbands, self.vector_len))
+        self._chk(self.lib.nbls_fetch_capon_clean(self._h, _iptr(cnt), _iptr(idx), _dptr(pw), _dptr(tr[0]), _dptr(tr[1])))
+        return cnt, idx, pw, tr[0], tr[1]
+
+    def fetch_capon_clean_csdm(self):
+        """-> the matrix CLEAN-SC has left of every window, complex128 (rows, vector_len, N, N) (a plan made with ``residual``)."""
+        N = self.nchans // self.nseg
+        out = np.empty((self.nbands, self.vector_len, N, N), dtype=np.complex128)
+        self._chk(self.lib.nbls_fetch_capon_clean_csdm(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def fetch_capon_maps(self):
         """-> (capon_map, bartlett_map), each (rows, vector_len, G) (a plan made with ``want_maps``)."""

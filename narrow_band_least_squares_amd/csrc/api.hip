@@ -826,6 +826,8 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if ((size_t)a.nbands * (c.grid.size() / 2) * (size_t)En * 16 > ((size_t)1 << 30))
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the Capon steering table (nbands * G * N * 16 bytes) exceeds 1 GiB");
     }
+    if (h->want_clean.iterations > 0 && h->want_capon.grid.empty())      // the CLEAN-SC request (nbls_set_capon_clean) works on the spectra's R and tables
+        return fail(h, NBLS_ERR_STATE, "nbls_plan: a CLEAN request (nbls_set_capon_clean) needs Capon spectra (nbls_set_capon)");
     int peak_route = 0;              // the peaks of the spectra (nbls_set_capon_peaks): Capon spectra of the same G, and a route
     if (!h->want_capon_peaks.nbr.empty()) {
         const size_t G = h->want_capon.grid.size() / 2;
@@ -979,6 +981,7 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->capon_maps = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_MAPS);
     h->capon_csdm = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_CSDM);
     h->capon_valid = false;
+    h->clean = h->capon_n > 0 ? h->want_clean : nbls_handle::capon_clean_request();
     h->capon_peaks = peak_route ? h->want_capon_peaks.k : 0;
     h->capon_peak_floor = h->want_capon_peaks.floor;
     h->capon_peak_route = peak_route;
@@ -1318,7 +1321,15 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_capon_index, 2 * cells * sizeof(int32_t)))) return rc;
         if ((rc = ensure(h, h->d_capon_power, 2 * cells * sizeof(double)))) return rc;
         if (h->capon_maps && (rc = ensure(h, h->d_capon_map, 2 * cells * (size_t)G * sizeof(double)))) return rc;
-        if (h->capon_csdm && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        if ((h->capon_csdm || h->clean.iterations > 0) && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        if (h->clean.iterations > 0) {   // the CLEAN-SC request: it reads R from d_capon_csdm whether or not the plan returns it
+            const size_t I = (size_t)h->clean.iterations;
+            if ((rc = ensure(h, h->d_clean_count, cells * sizeof(int32_t)))) return rc;
+            if ((rc = ensure(h, h->d_clean_index, cells * I * sizeof(int32_t)))) return rc;
+            if ((rc = ensure(h, h->d_clean_power, cells * I * sizeof(double)))) return rc;
+            if ((rc = ensure(h, h->d_clean_tr, 2 * cells * sizeof(double)))) return rc;
+            if ((h->clean.flags & NBLS_CLEAN_RESIDUAL) && (rc = ensure(h, h->d_clean_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        }
         if (h->capon_peaks > 0) {    // the peak request: its neighbour table, the four results and, on the HBM route of a plan without the maps, the slabs
             const size_t K = (size_t)h->capon_peaks;
             if ((rc = alloc_copy(h, h->d_capon_nbr, h->want_capon_peaks.nbr.data(), h->want_capon_peaks.nbr.size()))) return rc;
@@ -1999,6 +2010,50 @@ int nbls_fetch_capon_csdm(nbls_handle* h, double* R) {
     if (!h->capon_csdm || !h->d_capon_csdm) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_csdm: the plan did not ask for the matrix (nbls_set_capon, NBLS_CAPON_CSDM)");
     if ((rc = finish_pass(h))) return rc;
     return capon_fetch_plane(h, R, h->d_capon_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+}
+
+int nbls_set_capon_clean(nbls_handle* h, int32_t iterations, double gain, double floor, int32_t flags) {
+    if (!h) return NBLS_ERR_ARG;
+    if (iterations == 0) { h->want_clean = nbls_handle::capon_clean_request(); return NBLS_OK; }   // off: the next plan launches no capon_clean_kernel
+    if (iterations < 1 || iterations > NBLS_CAPON_CLEAN_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: iterations must be 1.." + std::to_string(NBLS_CAPON_CLEAN_MAX));
+    if (!(gain > 0.0 && gain <= 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: the gain must lie in (0, 1]");
+    if (!(floor >= 0.0 && floor < 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: the floor must lie in [0, 1)");
+    if (flags & ~NBLS_CLEAN_RESIDUAL) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: unknown flags");
+    nbls_handle::capon_clean_request& r = h->want_clean;         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    r.iterations = iterations;
+    r.gain = gain;
+    r.floor = floor;
+    r.flags = flags;
+    return NBLS_OK;
+}
+
+int nbls_fetch_capon_clean(nbls_handle* h, int32_t* count, int32_t* index, double* power, double* total, double* residual) {
+    if (!h) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_clean"))) return rc;
+    if (h->clean.iterations < 1 || !h->d_clean_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_clean: the plan did not ask for the components (nbls_set_capon_clean before nbls_plan)");
+    if ((rc = finish_pass(h))) return rc;
+    const size_t cells = (size_t)h->nbands * h->vector_len, I = (size_t)h->clean.iterations;
+    if ((rc = capon_fetch_plane(h, count, h->d_clean_count.p, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, index, h->d_clean_index.p, I * sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, power, h->d_clean_power.p, I * sizeof(double)))) return rc;
+    if ((rc = capon_fetch_plane(h, total, h->d_clean_tr.p, sizeof(double)))) return rc;
+    return capon_fetch_plane(h, residual, h->d_clean_tr.p + cells, sizeof(double));
+}
+
+int nbls_fetch_capon_clean_csdm(nbls_handle* h, double* R) {
+    if (!h || !R) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_clean_csdm"))) return rc;
+    if (h->clean.iterations < 1 || !(h->clean.flags & NBLS_CLEAN_RESIDUAL) || !h->d_clean_csdm)
+        return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_clean_csdm: the plan did not ask for the residual matrix (nbls_set_capon_clean, NBLS_CLEAN_RESIDUAL)");
+    if ((rc = finish_pass(h))) return rc;
+    return capon_fetch_plane(h, R, h->d_clean_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+}
+
+int nbls_capon_clean_lds_bytes(int32_t nelem) {
+    if (nelem < 1 || nelem > NBLS_CAPON_MAX_ELEMENTS) return NBLS_ERR_ARG;
+    return (int)nbls_capon_clean_lds_bytes_of(nelem);
 }
 
 int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* steer) {

@@ -56,6 +56,7 @@
 #include "nbls_internal.h"
 #include "wave_ops.h"
 #include "refine_fraction.h"
+#include "capon_point.h"
 #include <algorithm>
 #include <cmath>
 #include <utility>
@@ -63,8 +64,7 @@
 
 namespace {
 
-constexpr int CT = NBLS_CAPON_THREADS;
-constexpr int CW = CT / 64;                  // waves
+using namespace nbls_capon;                  // CT, CW, capon_better, capon_best, capon_bartlett_point (capon_point.h)
 constexpr int CCH = NBLS_CAPON_CHUNK;        // snapshots per chunk of X in LDS
 constexpr int CMAXN = NBLS_CAPON_MAX_ELEMENTS;
 constexpr int CTRI = (CMAXN * (CMAXN + 1) / 2 + CT - 1) / CT;     // lower-triangle entries per thread
@@ -105,28 +105,6 @@ struct CArgs {
 __host__ __device__ inline size_t nbls_capon_lds_doubles(int nelem) {
     const size_t n = (size_t)nelem, xy = (size_t)(CCH > CT ? CCH : CT) * n * 2;
     return 2 * n * n * 2 + ((n + 1) & ~(size_t)1) + xy;
-}
-
-// "P descending, g ascending"; a NaN is no candidate, g < 0 is "none yet".
-__device__ inline bool capon_better(double p, int g, double bp, int bg) {
-    if (p != p || g < 0) return false;
-    if (bg < 0) return true;
-    return p > bp || (p == bp && g < bg);
-}
-
-// The workgroup's best of the threads' bests -> thread 0 (any tree: the order is total).
-__device__ inline void capon_best(double& p, int& g, double* sp, int* sg, int tid) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const double op = __shfl_xor(p, off, 64);
-        const int og = __shfl_xor(g, off, 64);
-        if (capon_better(op, og, p, g)) { p = op; g = og; }
-    }
-    if ((tid & 63) == 0) { sp[tid >> 6] = p; sg[tid >> 6] = g; }
-    __syncthreads();
-    if (tid == 0)
-        for (int j = 1; j < CW; ++j)
-            if (capon_better(sp[j], sg[j], p, g)) { p = sp[j]; g = sg[j]; }
-    __syncthreads();
 }
 
 // ---- the K strongest peaks of one spectrum of the unit (nbls_set_capon_peaks) ----
@@ -430,22 +408,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
             yr[i * 2 * CT] = v.x; yr[i * 2 * CT + CT] = v.y;
         }
         // Bartlett: sum_i R_ii |a_i|^2 + 2 Re(conj(a_i) sum_{j<i} R_ij a_j)
-        double pb = 0.0;
-        for (int i = 0; i < SN; ++i) {
-            double ur = 0.0, ui = 0.0;
-            for (int j = 0; j < i; ++j) {
-                const double2 r = R2[i * SN + j];
-                const double vr = yr[j * 2 * CT], vi = yr[j * 2 * CT + CT];
-                ur = __builtin_fma(r.x, vr, ur);
-                ur = __builtin_fma(-r.y, vi, ur);
-                ui = __builtin_fma(r.x, vi, ui);
-                ui = __builtin_fma(r.y, vr, ui);
-            }
-            const double ar = yr[i * 2 * CT], ai = yr[i * 2 * CT + CT];
-            pb += R2[i * SN + i].x * (ar * ar + ai * ai);
-            pb += 2.0 * (ar * ur + ai * ui);
-        }
-        pb /= nn;
+        const double pb = capon_bartlett_point(R2, yr, SN, nn);
         // Capon: y in place of a
         double pc = nan_;
         if (chol_ok) {
@@ -583,7 +546,7 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
     a.cells = (int64_t)h->nbands * h->vector_len;
     a.index = h->d_capon_index; a.power = h->d_capon_power;
     a.map = h->capon_maps ? h->d_capon_map.p : nullptr;
-    a.csdm = h->capon_csdm ? h->d_capon_csdm.p : nullptr;
+    a.csdm = (h->capon_csdm || h->clean.iterations > 0) ? h->d_capon_csdm.p : nullptr;     // (capon_clean_kernel reads R there)
     const size_t lds = nbls_capon_lds_bytes_of(h->nelem);
     const bool kept = h->kept_capon;       // the spectra of the elements LTS kept (nbls_set_kept_elements): the KEPT instances
     if (kept) {

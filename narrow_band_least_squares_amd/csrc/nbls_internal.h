@@ -223,6 +223,20 @@ struct nbls_handle {
     dev_buf<int32_t> d_capon_peak_index;    // [2][B][VL][K]
     dev_buf<double> d_capon_peak_power;     // [2][B][VL][K]
     dev_buf<double> d_capon_peak_offset;    // [2][B][VL][K][2]
+    // ---- the window's arrivals by CLEAN-SC (nbls_set_capon_clean, capon_clean.hip) ----
+    struct capon_clean_request {
+        int iterations = 0;             // I (0: off)
+        double gain = 0.0, floor = 0.0;
+        int flags = 0;
+    };
+    capon_clean_request want_clean; // nbls_set_capon_clean: read by the next nbls_plan
+    capon_clean_request clean;      // the plan's copy (iterations 0: the plan launches no capon_clean_kernel)
+    bool clean_attr_set[2] = {false, false};    // the plain and the KEPT instance have their dynamic LDS limit
+    dev_buf<int32_t> d_clean_count; // [B][VL]
+    dev_buf<int32_t> d_clean_index; // [B][VL][I]
+    dev_buf<double> d_clean_power;  // [B][VL][I]
+    dev_buf<double> d_clean_tr;     // [2][B][VL]: total | residual
+    dev_buf<double> d_clean_csdm;   // [B][VL][N][N][2] (NBLS_CLEAN_RESIDUAL)
     // ---- the elements LTS kept (nbls_set_kept_elements, kept.hip) ----
     int want_kept_q = 0, want_kept_flags = 0;   // nbls_set_kept_elements: read by the next nbls_plan (q == 0: off)
     int kept_q = 0;                 // min_pairs of the plan (0: the plan does not ask)
@@ -442,6 +456,10 @@ bool nbls_beam_grid_steer_of(const double* xij, int nelem, double fs, const doub
 // Capon / Bartlett spectra of units [u0, u0 + nu) for the plan's full array (capon.hip)
 hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 size_t nbls_capon_lds_bytes_of(int nelem);
+// the CLEAN-SC components of units [u0, u0 + nu), behind nbls_launch_capon on the same stream (capon_clean.hip)
+hipError_t nbls_launch_capon_clean(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// dynamic LDS bytes of capon_clean_kernel: R, v and a column of a per lane
+size_t nbls_capon_clean_lds_bytes_of(int nelem);
 // ... of the instance that keeps the unit's two maps of G points in LDS (the LDS route of a peak request); 0: it does not fit
 size_t nbls_capon_peak_lds_bytes_of(int nelem, int G);
 // the automatic route of a peak request: 1 LDS, 2 HBM

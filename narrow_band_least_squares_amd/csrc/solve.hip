@@ -1445,6 +1445,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
     if (h->grid_n > 0 && h->seed.empty() && &s == &h->est[0] && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;
     // the Capon / Bartlett spectra of a plan that asked for them (nbls_set_capon): the full array, once per pass
     if (h->capon_n > 0 && &s == &h->est[0] && (e = nbls_launch_capon(h, u0, nu, st)) != hipSuccess) return e;
+    // ... and the CLEAN-SC components of a plan that asked for them (nbls_set_capon_clean), on the matrices it has just written
+    if (h->clean.iterations > 0 && &s == &h->est[0] && (e = nbls_launch_capon_clean(h, u0, nu, st)) != hipSuccess) return e;
     return pack_weights_of(h, s, u0, nu, st);
 }
 

@@ -364,7 +364,7 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
                want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-               want_kept=False, beam_trace_npts=0, want_element_delays=False):
+               want_kept=False, beam_trace_npts=0, want_element_delays=False, clean_iterations=0, want_clean_csdm=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
@@ -379,8 +379,12 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     ``dropped_mask`` (nbands, vector_len) uint32 and ``kept_count`` (nbands, vector_len) int32, the elements LTS dropped;
     ``beam_trace_npts`` = npts > 0: ``beam_trace`` (nbands, npts), the beam trace of every band; ``want_element_delays``: ``element_delay`` /
     ``element_cc`` (nbands, vector_len, nchans) and ``element_shift`` (likewise, int32), each element's delay against the
-    beam of the others; None otherwise."""
+    beam of the others; ``clean_iterations`` = I > 0 (with ``capon_points``): ``clean_count`` (nbands, vector_len) int32,
+    ``clean_index`` (.., I) int32, ``clean_power`` (.., I), ``clean_total`` and ``clean_residual`` (nbands, vector_len), the
+    CLEAN-SC components of every window, and with ``want_clean_csdm`` ``clean_csdm`` (nbands, vector_len, nchans, nchans)
+    complex, the matrix they leave; None otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
+    CI = int(clean_iterations) if capon_points else 0
     K = int(capon_peaks) if capon_points else 0
     peaks = {}
     for which in ('capon', 'bartlett'):
@@ -417,6 +421,12 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      element_delay=np.zeros((nb, vector_len, nchans)) if want_element_delays else None,
                      element_cc=np.zeros((nb, vector_len, nchans)) if want_element_delays else None,
                      element_shift=np.zeros((nb, vector_len, nchans), dtype=np.int32) if want_element_delays else None,
+                     clean_count=np.zeros((nb, vector_len), dtype=np.int32) if CI else None,
+                     clean_index=np.zeros((nb, vector_len, CI), dtype=np.int32) if CI else None,
+                     clean_power=np.zeros((nb, vector_len, CI)) if CI else None,
+                     clean_total=np.zeros((nb, vector_len)) if CI else None,
+                     clean_residual=np.zeros((nb, vector_len)) if CI else None,
+                     clean_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128) if (CI and want_clean_csdm) else None,
                      lts=alpha < 1.0, fs=fs, **peaks)
 
 
@@ -642,7 +652,7 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
            subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None, element_delays=None, element_delays_kept=False, beam_trace=None, beam_taps=0):
+           kept=None, capon_clean=None, element_delays=None, element_delays_kept=False, beam_trace=None, beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -670,7 +680,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     and needs ``beam`` or ``beam_grid``; 0: whole-sample delays.  ``element_delays``: one shift range in samples per band
     of the Prep: the plan also measures each element's delay against the beam of the others behind every solve, with
     ``element_delays_kept`` against the beam of the elements LTS kept, which needs ``kept`` (``Handle.set_element_delays``,
-    ``planner.element_shifts``; for this plan only)."""
+    ``planner.element_shifts``; for this plan only).  ``capon_clean``: ``(iterations, gain, floor, residual)`` of
+    ``Handle.set_capon_clean``: the plan also resolves every window's arrivals by CLEAN-SC (needs ``capon``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -719,6 +730,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon(**dict(capon, **{k: np.asarray(capon[k])[idx] for k in ('freqs', 'snap_len', 'snap_hop')}))
             if peaks:
                 h.set_capon_peaks(cells, peaks, floor)
+        if capon_clean is not None:
+            h.set_capon_clean(*capon_clean)
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
     finally:
@@ -740,6 +753,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon(None)
         if peaks:
             h.set_capon_peaks(None)
+        if capon_clean is not None:
+            h.set_capon_clean(0)
         if kept is not None:
             h.set_kept_elements(0)
         if element_delays is not None:
@@ -880,6 +895,11 @@ def collect(res, h, b0, b1, streamed, note):
         for which, name in enumerate(('capon', 'bartlett')):
             for field, a in zip(PEAK_FIELDS, h.fetch_capon_peaks(which)):
                 getattr(res, name + field)[b0:b1] = a
+    if res.clean_count is not None:
+        for field, a in zip(CLEAN_FIELDS, h.fetch_capon_clean()):
+            getattr(res, field)[b0:b1] = a
+    if res.clean_csdm is not None:
+        res.clean_csdm[b0:b1] = h.fetch_capon_clean_csdm()
     if res.dropped_mask is not None:
         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = h.fetch_kept_elements()
     if res.element_delay is not None:
@@ -966,6 +986,7 @@ def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
     return seeds
 
 
+CLEAN_FIELDS = ('clean_count', 'clean_index', 'clean_power', 'clean_total', 'clean_residual')   # what ``Handle.fetch_capon_clean`` returns, in order
 PEAK_FIELDS = ('_peak_count', '_peak_index', '_peak_power', '_peak_offset')     # what ``Handle.fetch_capon_peaks`` returns, in order
 
 
@@ -993,6 +1014,17 @@ def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading
     elif capon_cells is not None:
         raise ValueError('capon_cells needs capon_peaks')
     return out
+
+
+def _check_capon_clean(capon_clean, capon):
+    """``capon_clean`` of ``process`` / ``process_batch`` — None, an iteration count or ``(iterations[, gain[, floor[, residual]]])``
+    — -> the ``capon_clean`` tuple of ``launch`` or None; ``ValueError`` before any GPU work (``planner.check_capon_clean``)."""
+    if capon_clean is None:
+        return None
+    args = tuple(capon_clean) if isinstance(capon_clean, (tuple, list)) else (capon_clean,)
+    if not 1 <= len(args) <= 4:
+        raise ValueError('capon_clean must be (iterations[, gain[, floor[, residual]]]), not %r' % (capon_clean,))
+    return planner.check_capon_clean(*args, has_capon=capon is not None)
 
 
 def _check_kept(nchans, kept, want_beam, capon):
@@ -1057,8 +1089,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None, kept=None, element_max_shift=None, element_delays_kept=False,
-            want_beam_trace=None, beam_taps=0):
+            capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, element_max_shift=None,
+            element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -1124,6 +1156,13 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     best with the sum of the other elements; with ``element_delays_kept`` (needs ``kept=``) with the sum of those LTS kept
     (``nbls_set_element_delays``, DESIGN.md section 23; ``planner.element_shifts`` makes K).  ``ValueError`` before any GPU work;
     ``process_segmented`` refuses it.
+    capon_clean = iterations or (iterations, gain, floor, residual) (needs ``capon_grid``): also ``res.clean_count`` (nbands,
+    vector_len) int32, ``res.clean_index`` (.., I) int32, ``res.clean_power`` (.., I), ``res.clean_total`` and
+    ``res.clean_residual`` (nbands, vector_len): per window the CLEAN-SC components of the band's cross-spectral matrix —
+    the Bartlett maximum, ``gain`` of everything coherent with it removed, again on what is left, until a maximum falls
+    below ``floor`` times the first — with the mean element power before and after; ``residual``: also ``res.clean_csdm``
+    (nbands, vector_len, N, N) complex (``nbls_set_capon_clean``).  ``ValueError`` before any GPU work
+    (``planner.check_capon_clean``); ``process_segmented`` refuses it with the Capon spectra.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -1154,6 +1193,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     if beam_taps and not want_beam and sgrid is None:
         raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
+    clean = _check_capon_clean(capon_clean, capon)
     shifts = _check_element_delays(element_max_shift, element_delays_kept, len(band_edges), nchans, kept)
     trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
         want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
@@ -1179,14 +1219,15 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
                          0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
                          0 if capon is None else capon.get('peaks', 0), kept is not None, npts if trace is not None else 0,
-                         shifts is not None)
+                         shifts is not None, clean_iterations=0 if clean is None else clean[0],
+                         want_clean_csdm=clean is not None and clean[3])
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, element_delays=shifts,
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, element_delays=shifts,
                                  element_delays_kept=bool(element_delays_kept), beam_trace=trace, beam_taps=beam_taps)
     finally:
         if up is not None:
@@ -1421,7 +1462,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None, element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
+                  kept=None, capon_clean=None, element_max_shift=None, element_delays_kept=False, want_beam_trace=None,
+                  beam_taps=0):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1449,6 +1491,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     if beam_taps and not want_beam and sgrid is None:
         raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
+    clean = _check_capon_clean(capon_clean, capon)
     shifts = _check_element_delays(element_max_shift, element_delays_kept, nb, nchans, kept)
     trace = _check_beam_trace(want_beam_trace, prep.W, kept)
     tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
@@ -1461,7 +1504,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                       grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
                       want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK,
                       want_kept=kept is not None, beam_trace_npts=npts if trace is not None else 0,
-                      want_element_delays=shifts is not None)
+                      want_element_delays=shifts is not None, clean_iterations=0 if clean is None else clean[0],
+                      want_clean_csdm=clean is not None and clean[3])
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1477,7 +1521,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon, kept=kept,
+                       closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean,
                        element_delays=shifts, element_delays_kept=bool(element_delays_kept),
                        beam_trace=trace, beam_taps=beam_taps)
                 g = np.zeros((4, R, VL))
@@ -1494,6 +1538,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 cpmap = [a.reshape(b1 - b0, k, VL, CG) for a in h.fetch_capon_maps()] if (CG and want_capon_maps) else None
                 cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
                 cpk = [[a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_peaks(which)] for which in (0, 1)] if CK else None
+                cln = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_clean()] if clean is not None else None
+                clr = h.fetch_capon_clean_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (clean is not None and clean[3]) else None
                 kel = [a.reshape(b1 - b0, k, VL) for a in h.fetch_kept_elements()] if kept is not None else None
                 eld = [a.reshape(b1 - b0, k, VL, nchans) for a in h.fetch_element_delays()] if shifts is not None else None
                 for j, res in enumerate(out[s0:s0 + k]):
@@ -1520,6 +1566,11 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                         for which, name in enumerate(('capon', 'bartlett')):
                             for field, a in zip(PEAK_FIELDS, cpk[which]):
                                 getattr(res, name + field)[b0:b1] = a[:, j]
+                    if cln is not None:
+                        for field, a in zip(CLEAN_FIELDS, cln):
+                            getattr(res, field)[b0:b1] = a[:, j]
+                    if clr is not None:
+                        res.clean_csdm[b0:b1] = clr[:, j]
                     if kel is not None:
                         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = [a[:, j] for a in kel]
                     if eld is not None:

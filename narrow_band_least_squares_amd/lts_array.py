@@ -741,3 +741,144 @@ def ltsva_element_delays_batch(streams, lat_list, lon_list, window_length, windo
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
                                    want_uncert=True, **kw)
     return [_returns_element_delays(res, nchans, alpha, kept) for res in results]
+
+
+def clean_map(index, power, count, G):
+    """The CLEAN-SC components of ``Handle.fetch_capon_clean`` as a map: ``index`` / ``power`` (..., I) and ``count`` (...) ->
+    float64 (..., G), every window's ranks below its ``count`` scatter-added onto the grid (components that share a grid
+    point add up); zeros elsewhere."""
+    index, power, count = np.asarray(index), np.asarray(power, dtype=np.float64), np.asarray(count)
+    out = np.zeros(count.shape + (int(G),))
+    flat, idx, pw = out.reshape(-1, int(G)), index.reshape(-1, index.shape[-1]), power.reshape(-1, index.shape[-1])
+    for w, c in enumerate(count.reshape(-1)):
+        np.add.at(flat[w], idx[w, :c], pw[w, :c])
+    return out
+
+
+def clean_sources(index, power, count, grid, radius, max_sources):
+    """The CLEAN-SC components of every window merged into sources -> (source_power (..., S), source_slowness (..., S, 2),
+    source_vel (..., S), source_baz (..., S)) with S = ``max_sources``.  Per window: the strongest component not merged yet
+    (of equal ones the lower rank) takes every unmerged component within ``radius`` s/km of its grid point; the source's power
+    is their sum, its slowness their power-weighted mean, velocity and back-azimuth by the formula of ``grid_slowness``;
+    again on what is left, up to S sources in the order they are found.  NaN beyond the sources a window has."""
+    index, power, count = np.asarray(index), np.asarray(power, dtype=np.float64), np.asarray(count)
+    grid, S = np.asarray(grid, dtype=np.float64), int(max_sources)
+    spw = np.full(count.shape + (S,), np.nan)
+    ssl = np.full(count.shape + (S, 2), np.nan)
+    fpw, fsl = spw.reshape(-1, S), ssl.reshape(-1, S, 2)
+    idx, pw = index.reshape(-1, index.shape[-1]), power.reshape(-1, index.shape[-1])
+    for w, c in enumerate(count.reshape(-1)):
+        s, p = grid[idx[w, :c]], pw[w, :c]
+        free = np.ones(int(c), dtype=bool)
+        for k in range(S):
+            if not free.any():
+                break
+            lead = int(np.flatnonzero(free)[np.argmax(p[free])])
+            take = free & (np.hypot(s[:, 0] - s[lead, 0], s[:, 1] - s[lead, 1]) <= radius)
+            fpw[w, k] = p[take].sum()
+            fsl[w, k] = (s[take] * p[take, None]).sum(axis=0) / fpw[w, k]
+            free &= ~take
+    with np.errstate(divide='ignore', invalid='ignore'):
+        vel = 1.0 / np.hypot(ssl[..., 0], ssl[..., 1])
+    baz = np.mod(np.arctan2(ssl[..., 0], ssl[..., 1]) * 180.0 / np.pi - 360.0, 360.0)
+    return spw, ssl, vel, baz
+
+
+def _clean_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, iterations, gain, floor, kept, min_pairs, merge_radius,
+                    max_sources):
+    """The keywords of ``engine.process`` behind the arguments of ``ltsva_clean`` for one filtered band of window length ``W``
+    samples -> (keywords, grid, merge radius, max_sources).  ``ValueError`` before any GPU work."""
+    _check_flag('kept', kept)
+    if min_pairs is not None and not kept:
+        raise ValueError('min_pairs needs kept=True')
+    kw = _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, 0.01, False)
+    kw['capon_clean'] = planner.check_capon_clean(iterations, gain, floor, False)
+    if kept:
+        q = planner.check_kept(nchans, min_pairs, False, True)[0]
+        kw['kept'] = (q, False, True)
+    if isinstance(max_sources, (bool, np.bool_)) or not isinstance(max_sources, (int, np.integer)) or int(max_sources) < 1:
+        raise ValueError('max_sources must be a positive integer, not %r' % (max_sources,))
+    grid = kw['capon_grid']
+    if merge_radius is None:
+        merge_radius = 1.5 * float(np.max(planner.grid_cells(grid)[1]))
+    elif not planner._real(merge_radius) or not (0.0 <= float(merge_radius) < np.inf):
+        raise ValueError('merge_radius must be a finite number >= 0 (s/km), not %r' % (merge_radius,))
+    return kw, grid, float(merge_radius), int(max_sources)
+
+
+def _returns_clean(res, grid, radius, max_sources, band=0, n=None):
+    """A band's CLEAN-SC results as a dict: the fields of ``engine.CLEAN_FIELDS``, the slowness of every component
+    (``grid_slowness``), and the merged sources of ``clean_sources`` (csrc/capon_clean.hip: capon_clean_kernel).  ``band`` / ``n``
+    as for ``_returns_capon``."""
+    sl = slice(None) if n is None else slice(0, n)
+    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    out = {k: pick(getattr(res, k)) for k in engine.CLEAN_FIELDS}
+    if getattr(res, 'clean_csdm', None) is not None:
+        out['clean_csdm'] = pick(res.clean_csdm)
+    out['clean_vel'], out['clean_baz'] = grid_slowness(grid, out['clean_index'])
+    out['source_power'], out['source_slowness'], out['source_vel'], out['source_baz'] = clean_sources(
+        out['clean_index'], out['clean_power'], out['clean_count'], grid, radius, max_sources)
+    if getattr(res, 'dropped_mask', None) is not None:
+        out['kept_count'] = pick(res.kept_count)
+    return out
+
+
+def ltsva_clean(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None, snapshots=None,
+                iterations=16, gain=0.5, floor=0.02, kept=False, min_pairs=None, merge_radius=None, max_sources=4):
+    """``ltsva`` followed by the window's arrivals and their powers by CLEAN-SC (Sijtsma 2007) on the narrow band's
+    cross-spectral matrix of ``ltsva_capon`` (``slowness_grid`` (G, 2) s/km, ``freq`` Hz, ``snapshots``): up to ``iterations``
+    (1..32) times the Bartlett maximum of the matrix is taken as a component and ``gain`` of everything coherent with that
+    beam removed — sidelobes leave with their source — until a maximum falls below ``floor`` times the first (DESIGN.md
+    section 24 has the definition and the counts).  ``kept=True``: on the elements FAST-LTS kept (``min_pairs`` as for
+    ``ltsva_kept``).  Returns ``ltsva``'s 8-tuple followed by one dict: ``clean_count`` (nwin,) int32, ``clean_index`` (nwin, I)
+    int32 and ``clean_power`` (nwin, I) (-1 / NaN beyond the count), ``clean_vel`` / ``clean_baz`` (``grid_slowness``),
+    ``clean_total`` and ``clean_residual`` (nwin,), the mean element power before and after, and the components merged into
+    sources by ``clean_sources`` within ``merge_radius`` s/km (default: 1.5 steps of the grid's lattice): ``source_power``
+    (nwin, max_sources), ``source_slowness`` (.., 2), ``source_vel``, ``source_baz``.  Computed on the GPU behind each window's
+    solve (csrc/capon_clean.hip).  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    _check_elements_strict(len(st), alpha)
+    nchans = len(st)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    data, fs, t0 = engine.stream_rows(st)
+    W = planner.window_plan(len(data[0]), fs, window_length, window_overlap)[0]
+    kw, grid, radius, S = _clean_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, iterations, gain, floor, kept,
+                                          min_pairs, merge_radius, max_sources)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, **kw)
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (_returns_clean(res, grid, radius, S, n=int(res.nwin[0])),)
+
+
+def ltsva_clean_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
+                      snapshots=None, iterations=16, gain=0.5, floor=0.02, kept=False, min_pairs=None, merge_radius=None,
+                      max_sources=4):
+    """``ltsva_clean`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
+    element i equal to ``ltsva_clean(streams[i], ...)``; the streams as for ``ltsva_batch``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
+    kw, grid, radius, S = _clean_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, iterations, gain, floor, kept,
+                                          min_pairs, merge_radius, max_sources)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_clean(streams[0], lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha, rij,
+                            snapshots, iterations, gain, floor, kept, min_pairs, merge_radius, max_sources)]
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, **kw)
+    return [_returns(res, nchans, alpha) + (_returns_clean(res, grid, radius, S, n=int(res.nwin[0])),) for res in results]

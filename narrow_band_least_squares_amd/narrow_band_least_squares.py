@@ -15,7 +15,7 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
-from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept
+from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept, _returns_clean
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -371,6 +371,42 @@ def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
                                        FILTER_RIPPLE, vector_len, rij=rij,
                                        key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
     out = _zero_padded_capon(_returns_capon(res, grid, bool(maps), band=None), res, bool(peak_kw))
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (out,)
+
+
+def narrow_band_least_squares_clean(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                    FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                    slowness_grid, capon_freqs=None, snapshots=None, iterations=16, gain=0.5, floor=0.02,
+                                    merge_radius=None, max_sources=4):
+    """``narrow_band_least_squares`` followed by every window's arrivals and their powers by CLEAN-SC on the band's
+    cross-spectral matrix (``lts_array.ltsva_clean``), computed on the GPU behind each window's solve.
+    ``capon_freqs`` and ``snapshots`` as for ``narrow_band_least_squares_capon``.  Returns the nine values of
+    ``narrow_band_least_squares`` followed by one dict with the fields of ``lts_array.ltsva_clean``'s, each (NBANDS, vector_len,
+    ...) with zeros beyond a band's windows.  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    clean = planner.check_capon_clean(iterations, gain, floor, False)
+    if isinstance(max_sources, (bool, np.bool_)) or not isinstance(max_sources, (int, np.integer)) or int(max_sources) < 1:
+        raise ValueError('max_sources must be a positive integer, not %r' % (max_sources,))
+    if merge_radius is None:
+        merge_radius = 1.5 * float(np.max(planner.grid_cells(grid)[1]))
+    elif not planner._real(merge_radius) or not (0.0 <= float(merge_radius) < np.inf):
+        raise ValueError('merge_radius must be a finite number >= 0 (s/km), not %r' % (merge_radius,))
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    keywords = _capon_band_keywords(len(st), grid, capon_freqs, snapshots, 0.01, False, dict(capon_clean=clean), WINOVER, vector_len)
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
+    out = _returns_clean(res, grid, float(merge_radius), int(max_sources), band=None)
+    computed = np.arange(res.clean_count.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    for k in ('clean_vel', 'clean_baz', 'source_power', 'source_vel', 'source_baz'):
+        out[k] = np.where(computed[..., None], out[k], 0.0)
+    out['source_slowness'] = np.where(computed[..., None, None], out['source_slowness'], 0.0)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (out,)
 

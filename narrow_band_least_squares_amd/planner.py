@@ -749,6 +749,26 @@ def check_capon_peaks(grid_len, cells, K, floor):
     return np.ascontiguousarray(c, dtype=np.int32), int(K), float(floor)
 
 
+MAX_CAPON_CLEAN = 32      # iterations of a CLEAN request (NBLS_CAPON_CLEAN_MAX)
+
+
+def check_capon_clean(iterations, gain=0.5, floor=0.02, residual=False, has_capon=True):
+    """Everything ``nbls_set_capon_clean`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (iterations
+    int, gain float, floor float, residual bool): an integer number of iterations in 1..32, a gain in (0, 1], a floor in
+    [0, 1), ``residual`` a bool; ``has_capon``: the call computes the Capon spectra the request works on."""
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not (1 <= int(iterations) <= MAX_CAPON_CLEAN):
+        raise ValueError('the CLEAN iterations must be an integer in 1..%d, not %r' % (MAX_CAPON_CLEAN, iterations))
+    if not _real(gain) or not (0.0 < float(gain) <= 1.0):
+        raise ValueError('the CLEAN gain must be a number in (0, 1], not %r' % (gain,))
+    if not _real(floor) or not (0.0 <= float(floor) < 1.0):
+        raise ValueError('the CLEAN floor must be a number in [0, 1), not %r' % (floor,))
+    if not isinstance(residual, (bool, np.bool_)):
+        raise ValueError('residual must be True or False, not %r' % (residual,))
+    if not has_capon:
+        raise ValueError('a CLEAN request needs the Capon spectra (capon_grid)')
+    return int(iterations), float(gain), float(floor), bool(residual)
+
+
 MAX_KEPT_ELEMENTS = 32    # elements of a plan that names the dropped ones: one bit each of a uint32 (csrc/kept.hip)
 
 
