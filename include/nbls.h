@@ -753,6 +753,82 @@ int nbls_fetch_capon_clean(nbls_handle* h, int32_t* count, int32_t* index, doubl
 int nbls_fetch_capon_clean_csdm(nbls_handle* h, double* R);
 int nbls_capon_clean_lds_bytes(int32_t nelem);
 
+/* ---- A window's eigenvalues and its MUSIC slowness spectrum ----
+ * The eigenvalues of R say whether a window holds one arrival or several; the MUSIC pseudo-spectrum (Schmidt 1986)
+ * separates them with one scan of the grid.  A plan with nbls_set_capon may carry a MUSIC request: sources, an eigenvalue
+ * floor rho, a peak floor, flags (NBLS_MUSIC_MAP, NBLS_MUSIC_VECTORS, NBLS_MUSIC_PEAKS).  It applies to estimator 0 and uses the grid, the
+ * steering table a[g], the units and the unloaded R of nbls_set_capon, the matrix NBLS_CAPON_CSDM returns; the loading plays
+ * no part.  N is the full array, 3 <= N <= 32.  fma(x, y, z) = x * y + z rounded once.  Per unit, A = R, E = I:
+ *   degenerate  (t = 0, t NaN or a NaN entry of R, as for the spectra) every eigenvalue NaN, sources -1, sweeps 0, index
+ *            -1, power NaN, the map and the vectors NaN.
+ *   order    cyclic Jacobi in the round-robin tournament order: with H = ceil(N / 2) and m = 2 H - 1, step k = 0 .. m - 1
+ *            rotates the disjoint pairs {m, k} and {(k + r) mod m, (k - r) mod m}, r = 1 .. H - 1, p the smaller and q
+ *            the larger index; a pair with the player N of an odd array is the other's bye.  m steps are one sweep: every
+ *            pair once, the order independent of the data.
+ *   rotation of the pair (p, q) from x = A_pq, g = sqrt(fma(Im x, Im x, Re x * Re x)):  g = 0: none.  Otherwise
+ *            tau = (A_qq - A_pp) / (2 g);  t = sign(tau) / (|tau| + sqrt(fma(tau, tau, 1)))  (sign(+-0) = +-1);
+ *            c = 1 / sqrt(fma(t, t, 1));  s = t * c;  sigma = s * (x / g)  (each part divided, then multiplied).
+ *            J is the identity but for J_pp = J_qq = c, J_pq = sigma, J_qp = -conj(sigma).
+ *   step     A <- J^H A J and E <- E J with J the product of the step's rotations, all formed from the A before the step.
+ *            A_pp <- A_pp - t g, A_qq <- A_qq + t g, A_pq = A_qp = 0, the imaginary part of the diagonal 0.0.  Of the other
+ *            entries the 2 x 2 blocks X = A[{p, q}][{p', q'}] of the pairs r < r' are computed, X J' first and J^H (X J')
+ *            second, each product a chain of fma from the product with c; the entries below are their conjugates, bit
+ *            for bit.
+ *   stop     before every sweep:  off^2 = sum_{i > j} |A_ij|^2 (fma chain, rows ascending) and n^2 = sum_ij |R_ij|^2
+ *            (likewise, storage order);  stop if 2 off^2 <= 2^-92 n^2, that is off(A) <= 2^-46 ||R||_F, or after
+ *            NBLS_MUSIC_SWEEP_CAP = 24 sweeps.  sweeps is the number of sweeps made; a diagonal R takes 0.  Fewer than
+ *            the cap means the rule fired.
+ *   eigenvalues  lambda_1 >= ... >= lambda_N: the diagonal of A under the total order "value descending, then the
+ *            column's index before sorting ascending"; e_k is the column of E that belongs to lambda_k.
+ *   sources  M = sources where 1 <= sources <= N - 1;  sources = 0:  M = clamp(#{k : lambda_k >= rho * lambda_1}, 1, N - 1),
+ *            one multiplication, decided from the returned eigenvalues: the returned M is reproducible from them bit for bit.
+ *   spectrum D(g) = (1 / N) sum_{k > M} |e_k^H a(g)|^2, k ascending and inside each k the elements ascending:
+ *            zr = fma(Re e_ik, Re a_i, zr); zr = fma(Im e_ik, Im a_i, zr); zi = fma(Re e_ik, Im a_i, zi);
+ *            zi = fma(-Im e_ik, Re a_i, zi);  then d = fma(zr, zr, d); d = fma(zi, zi, d);  P(g) = 1 / (d / N).  The noise
+ *            subspace is summed, not N minus the signal subspace: nothing cancels where D -> 0.  D = 0 gives +inf, which
+ *            is a candidate.
+ *   arg-max  music_index / music_power under "P descending, g ascending", NaN no candidate, as for the spectra.
+ *   NBLS_MUSIC_MAP      the plan keeps P, [G] per unit.
+ *   NBLS_MUSIC_VECTORS  the plan keeps E, [N][N][2] per unit, entry [i][k] element i of e_k; its phase is unspecified.
+ *   NBLS_MUSIC_PEAKS    the K strongest local maxima of P as nbls_set_capon_peaks defines them for a spectrum: K and the
+ *            neighbour table are that request's, which the plan must carry (NBLS_ERR_STATE without it); the floor is this
+ *            request's own peak_floor, since a pseudo-spectrum's heights are not powers; count, index, power and offset as
+ *            there.  +inf is a local maximum like any other value; a degenerate unit has count 0 and every rank -1 / NaN.
+ * No atomics, every order total, nothing depends on the launch's unit range: single, streamed, batched, window-sliced and
+ * round-split passes give the same bits.
+ *   nbls_set_capon_music(h, sources, eig_floor, peak_floor, flags)   read by the next nbls_plan; sources = -1 switches it
+ *                            off (the default: such a plan launches exactly what it launched before).  NBLS_ERR_ARG, the
+ *                            handle unchanged, for sources outside -1..31, with sources = 0 an eig_floor outside (0, 1), a
+ *                            peak_floor outside [0, 1), NaN, or unknown flags.  nbls_plan returns NBLS_ERR_STATE without nbls_set_capon,
+ *                            NBLS_ERR_ARG for sources > N - 1, and NBLS_ERR_UNSUPPORTED for fewer than 3 elements, with an
+ *                            RCCL communicator, with further estimators (nbls_set_estimators) and with NBLS_KEPT_CAPON.
+ *                            It combines with the maps, the peaks, CLEAN-SC, segments, window ranges and streamed results.
+ *   nbls_fetch_capon_music(h, eigenvalues, sources, sweeps, index, power)   eigenvalues [rows][vector_len][N]; the others
+ *                            [rows][vector_len]; any may be NULL.  Rows, waiting, NBLS_ERR_STATE and zeros as for
+ *                            nbls_fetch_capon.
+ *   nbls_fetch_capon_music_map(h, map)   [rows][vector_len][G]; NBLS_ERR_STATE without NBLS_MUSIC_MAP.
+ *   nbls_fetch_capon_music_vectors(h, E)   [rows][vector_len][N][N][2]; NBLS_ERR_STATE without NBLS_MUSIC_VECTORS.
+ *   nbls_fetch_capon_music_peaks(h, count, index, power, offset)   count [rows][vector_len], index and power [..][K], offset
+ *                            [..][K][2]; any may be NULL; NBLS_ERR_STATE without NBLS_MUSIC_PEAKS.  nbls_fetch_capon_peaks
+ *                            keeps its `which` of 0 and 1.
+ *   nbls_capon_music_lds_bytes(nelem)   pure host function: (4 N^2 + 2 * 128 * N + 4 N + 4) * 8, the kernel's dynamic LDS (A,
+ *                            E, a column of a per lane, the step's rotations, the eigenvalues and their order);
+ *                            NBLS_ERR_ARG for nelem outside 3..32.
+ * capon_music_kernel (csrc/capon_music.hip) runs behind the spectra's kernel on the same stream over the same units, one
+ * workgroup of NBLS_CAPON_THREADS per unit; it reads R from the plan's matrix buffer, which such a plan holds on the device
+ * whether or not NBLS_CAPON_CSDM was asked.  nbls_timings is unchanged. */
+#define NBLS_MUSIC_SWEEP_CAP 24
+#define NBLS_MUSIC_STOP_SQUARED 0x1p-92
+#define NBLS_MUSIC_MAP 1
+#define NBLS_MUSIC_VECTORS 2
+#define NBLS_MUSIC_PEAKS 4
+int nbls_set_capon_music(nbls_handle* h, int32_t sources, double eig_floor, double peak_floor, int32_t flags);
+int nbls_fetch_capon_music(nbls_handle* h, double* eigenvalues, int32_t* sources, int32_t* sweeps, int32_t* index, double* power);
+int nbls_fetch_capon_music_map(nbls_handle* h, double* map);
+int nbls_fetch_capon_music_vectors(nbls_handle* h, double* E);
+int nbls_fetch_capon_music_peaks(nbls_handle* h, int32_t* count, int32_t* index, double* power, double* offset);
+int nbls_capon_music_lds_bytes(int32_t nelem);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

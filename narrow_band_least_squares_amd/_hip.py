@@ -33,6 +33,9 @@ EXPORTS = [
     'nbls_set_capon', 'nbls_fetch_capon', 'nbls_fetch_capon_maps', 'nbls_fetch_capon_csdm', 'nbls_fetch_capon_tables',
     'nbls_set_capon_peaks', 'nbls_fetch_capon_peaks',
     'nbls_set_capon_clean', 'nbls_fetch_capon_clean', 'nbls_fetch_capon_clean_csdm', 'nbls_capon_clean_lds_bytes',
+    'nbls_set_capon_music', 'nbls_fetch_capon_music', 'nbls_fetch_capon_music_map', 'nbls_fetch_capon_music_vectors',
+    'nbls_fetch_capon_music_peaks',
+    'nbls_capon_music_lds_bytes',
     'nbls_set_kept_elements', 'nbls_fetch_kept_elements',
     'nbls_set_beam_trace', 'nbls_fetch_beam_trace',
     'nbls_set_beam_interpolation', 'nbls_fetch_beam_grid_coefficients',
@@ -49,6 +52,8 @@ CAPON_MAPS, CAPON_CSDM = 1, 2     # flags of nbls_set_capon
 CAPON_PEAKS_MAX = 8      # ranks of a peak request (NBLS_CAPON_PEAKS_MAX)
 CAPON_CLEAN_MAX = 32     # iterations of a CLEAN request (NBLS_CAPON_CLEAN_MAX)
 CLEAN_RESIDUAL = 1       # flag of nbls_set_capon_clean (NBLS_CLEAN_RESIDUAL)
+MUSIC_MAP, MUSIC_VECTORS, MUSIC_PEAKS = 1, 2, 4   # flags of nbls_set_capon_music
+MUSIC_SWEEP_CAP = 24     # Jacobi sweeps of a MUSIC request at most (NBLS_MUSIC_SWEEP_CAP)
 KEPT_BEAM, KEPT_CAPON = 1, 2      # flags of nbls_set_kept_elements
 BEAM_TRACE_KEPT = 1      # flag of nbls_set_beam_trace
 ELEMENT_DELAY_KEPT = 1   # flag of nbls_set_element_delays (NBLS_ELEMENT_DELAY_KEPT)
@@ -200,6 +205,12 @@ def load_library(path=None):
     lib.nbls_fetch_capon_clean.argtypes = [vp, ip, ip, dp, dp, dp]
     lib.nbls_fetch_capon_clean_csdm.argtypes = [vp, dp]
     lib.nbls_capon_clean_lds_bytes.argtypes = [C.c_int32]
+    lib.nbls_set_capon_music.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_int32]
+    lib.nbls_fetch_capon_music.argtypes = [vp, dp, ip, ip, ip, dp]
+    lib.nbls_fetch_capon_music_map.argtypes = [vp, dp]
+    lib.nbls_fetch_capon_music_vectors.argtypes = [vp, dp]
+    lib.nbls_fetch_capon_music_peaks.argtypes = [vp, ip, ip, dp, dp]
+    lib.nbls_capon_music_lds_bytes.argtypes = [C.c_int32]
     lib.nbls_set_kept_elements.argtypes = [vp, C.c_int32, C.c_int32]
     lib.nbls_fetch_kept_elements.argtypes = [vp, C.POINTER(C.c_uint32), ip]
     lib.nbls_set_beam_trace.argtypes = [vp, dp, C.c_int64, C.c_double, C.c_int32]
@@ -315,6 +326,7 @@ class Handle:
         self._want_capon = self.capon = None  # (G, snapshot lengths) of set_capon / of the plan
         self._want_capon_peaks = self.capon_peaks = 0     # K of set_capon_peaks / of the plan
         self._want_capon_clean = self.capon_clean = 0     # I of set_capon_clean / of the plan
+        self._want_capon_music = self.capon_music = None  # (sources, maps, vectors) of set_capon_music / of the plan
         self._keep = []
         self.profiling = False
         self.resident_key = None        # engine.resident_trace: what the trace in HBM was uploaded from (any new trace clears it)
@@ -444,6 +456,7 @@ class Handle:
         self.capon = self._want_capon
         self.capon_peaks = self._want_capon_peaks
         self.capon_clean = self._want_capon_clean if self.capon else 0
+        self.capon_music = self._want_capon_music if self.capon else None
 
     def set_option(self, key, value):
         """Per-handle implementation switch (``nbls_set_option``; identical results unless the library is the
@@ -743,6 +756,58 @@ class Handle:
         N = self.nchans // self.nseg
         out = np.empty((self.nbands, self.vector_len, N, N), dtype=np.complex128)
         self._chk(self.lib.nbls_fetch_capon_clean_csdm(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def set_capon_music(self, sources=0, eig_floor=0.05, maps=False, vectors=False, peaks=False, peak_floor=0.0):
+        """The next plans (with ``set_capon``) also decompose every window's cross-spectral matrix: its eigenvalues, and the
+        MUSIC pseudo-spectrum over the grid with ``sources`` = M in 1..N-1 signal eigenvectors, or (``sources=0``) as many
+        as there are eigenvalues of at least ``eig_floor`` in (0, 1) times the largest (``nbls_set_capon_music``, DESIGN.md
+        section 25); ``maps``: the plan keeps the spectrum of every window, ``vectors``: the eigenvectors, ``peaks``: the K
+        strongest local maxima of the spectrum, K and the cells those of ``set_capon_peaks`` (which the plan needs), kept from
+        ``peak_floor`` in [0, 1) times the maximum.  ``sources=None`` switches it off again."""
+        if sources is None:
+            self._chk(self.lib.nbls_set_capon_music(self._h, -1, 0.0, 0.0, 0))
+            self._want_capon_music = None
+            return
+        flags = (MUSIC_MAP if maps else 0) | (MUSIC_VECTORS if vectors else 0) | (MUSIC_PEAKS if peaks else 0)
+        self._chk(self.lib.nbls_set_capon_music(self._h, int(sources), float(eig_floor), float(peak_floor), flags))
+        self._want_capon_music = (int(sources), bool(maps), bool(vectors), bool(peaks))
+
+    def fetch_capon_music(self):
+        """-> (eigenvalues (rows, vector_len, N) descending, sources int32 (rows, vector_len), sweeps int32, index int32 and
+        power (rows, vector_len)) of a plan made with ``set_capon_music``."""
+        N = self.nchans // self.nseg
+        ev = np.empty((self.nbands, self.vector_len, N))
+        ints = np.empty((3, self.nbands, self.vector_len), dtype=np.int32)
+        pw = np.empty((self.nbands, self.vector_len))
+        self._chk(self.lib.nbls_fetch_capon_music(self._h, _dptr(ev), _iptr(ints[0]), _iptr(ints[1]), _iptr(ints[2]), _dptr(pw)))
+        return ev, ints[0], ints[1], ints[2], pw
+
+    def fetch_capon_music_peaks(self):
+        """The K strongest peaks of the MUSIC spectrum -> (count int32 (rows, vector_len), index int32 (rows, vector_len, K),
+        power (rows, vector_len, K), offset (rows, vector_len, K, 2)), as ``fetch_capon_peaks`` returns a spectrum's (a plan made
+        with ``peaks``)."""
+        K = max(self.capon_peaks, 1)
+        cnt = np.empty((self.nbands, self.vector_len), dtype=np.int32)
+        idx = np.empty((self.nbands, self.vector_len, K), dtype=np.int32)
+        pw = np.empty((self.nbands, self.vector_len, K))
+        off = np.empty((self.nbands, self.vector_len, K, 2))
+        self._chk(self.lib.nbls_fetch_capon_music_peaks(self._h, _iptr(cnt), _iptr(idx), _dptr(pw), _dptr(off)))
+        return cnt, idx, pw, off
+
+    def fetch_capon_music_map(self):
+        """-> the MUSIC pseudo-spectrum of every window, (rows, vector_len, G) (a plan made with ``maps``)."""
+        G = self.capon[0] if self.capon else 1
+        out = np.empty((self.nbands, self.vector_len, G))
+        self._chk(self.lib.nbls_fetch_capon_music_map(self._h, _dptr(out)))
+        return out
+
+    def fetch_capon_music_vectors(self):
+        """-> the eigenvectors of every window, complex128 (rows, vector_len, N, N), column k beside eigenvalue k (a plan made
+        with ``vectors``)."""
+        N = self.nchans // self.nseg
+        out = np.empty((self.nbands, self.vector_len, N, N), dtype=np.complex128)
+        self._chk(self.lib.nbls_fetch_capon_music_vectors(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def fetch_capon_maps(self):

@@ -422,7 +422,7 @@ void nbls_destroy(nbls_handle* h) {
     for (hipEvent_t e : h->pev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->rev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->uev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_uprev, h->ev_xd, h->ev_plan, h->ev_up, h->ev_capon_slab})
+    for (hipEvent_t e : {h->ev_uprev, h->ev_xd, h->ev_plan, h->ev_up, h->ev_capon_slab, h->ev_music_slab})
         if (e) (void)hipEventDestroy(e);
     if (h->cstream) (void)hipStreamDestroy(h->cstream);
     if (h->ustream) (void)hipStreamDestroy(h->ustream);
@@ -828,6 +828,22 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     }
     if (h->want_clean.iterations > 0 && h->want_capon.grid.empty())      // the CLEAN-SC request (nbls_set_capon_clean) works on the spectra's R and tables
         return fail(h, NBLS_ERR_STATE, "nbls_plan: a CLEAN request (nbls_set_capon_clean) needs Capon spectra (nbls_set_capon)");
+    if (h->want_music.sources >= 0) {    // the MUSIC request (nbls_set_capon_music): the spectra's R and tables, the full array, estimator 0 alone
+        if (h->want_capon.grid.empty())
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: a MUSIC request (nbls_set_capon_music) needs Capon spectra (nbls_set_capon)");
+        if (h->nest > 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: a MUSIC request (nbls_set_capon_music) is not supported with further estimators (nbls_set_estimators)");
+        if (h->want_kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_CAPON))
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: a MUSIC request (nbls_set_capon_music) is not supported with NBLS_KEPT_CAPON (nbls_set_kept_elements): it works on the full array");
+        const int En = h->nchans / NS;
+        if (En < 3)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: a MUSIC request (nbls_set_capon_music) needs at least 3 elements");
+        if (h->want_music.sources > En - 1)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_music.sources) + " sources (nbls_set_capon_music) for an array of " +
+                                             std::to_string(En) + " elements (1.." + std::to_string(En - 1) + ")");
+    }
+    if (h->want_music.sources >= 0 && (h->want_music.flags & NBLS_MUSIC_PEAKS) && h->want_capon_peaks.nbr.empty())
+        return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_MUSIC_PEAKS (nbls_set_capon_music) needs K and the cells of a peak request (nbls_set_capon_peaks)");
     int peak_route = 0;              // the peaks of the spectra (nbls_set_capon_peaks): Capon spectra of the same G, and a route
     if (!h->want_capon_peaks.nbr.empty()) {
         const size_t G = h->want_capon.grid.size() / 2;
@@ -982,6 +998,7 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     h->capon_csdm = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_CSDM);
     h->capon_valid = false;
     h->clean = h->capon_n > 0 ? h->want_clean : nbls_handle::capon_clean_request();
+    h->music = h->capon_n > 0 ? h->want_music : nbls_handle::capon_music_request();
     h->capon_peaks = peak_route ? h->want_capon_peaks.k : 0;
     h->capon_peak_floor = h->want_capon_peaks.floor;
     h->capon_peak_route = peak_route;
@@ -1321,7 +1338,25 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_capon_index, 2 * cells * sizeof(int32_t)))) return rc;
         if ((rc = ensure(h, h->d_capon_power, 2 * cells * sizeof(double)))) return rc;
         if (h->capon_maps && (rc = ensure(h, h->d_capon_map, 2 * cells * (size_t)G * sizeof(double)))) return rc;
-        if ((h->capon_csdm || h->clean.iterations > 0) && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        if ((h->capon_csdm || h->clean.iterations > 0 || h->music.sources >= 0) && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        if (h->music.sources >= 0) {     // the MUSIC request: it reads R from d_capon_csdm whether or not the plan returns it
+            if ((rc = ensure(h, h->d_music_eig, cells * (size_t)E * sizeof(double)))) return rc;
+            if ((rc = ensure(h, h->d_music_int, 3 * cells * sizeof(int32_t)))) return rc;
+            if ((rc = ensure(h, h->d_music_power, cells * sizeof(double)))) return rc;
+            if ((h->music.flags & NBLS_MUSIC_MAP) && (rc = ensure(h, h->d_music_map, cells * (size_t)G * sizeof(double)))) return rc;
+            if ((h->music.flags & NBLS_MUSIC_VECTORS) && (rc = ensure(h, h->d_music_vec, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+            if (h->music.flags & NBLS_MUSIC_PEAKS) {     // K of the plan's peak request; the slabs where the plan keeps no MUSIC map
+                const size_t K = (size_t)h->capon_peaks;
+                if ((rc = ensure(h, h->d_music_peak_count, cells * sizeof(int32_t)))) return rc;
+                if ((rc = ensure(h, h->d_music_peak_index, cells * K * sizeof(int32_t)))) return rc;
+                if ((rc = ensure(h, h->d_music_peak_power, cells * K * sizeof(double)))) return rc;
+                if ((rc = ensure(h, h->d_music_peak_offset, cells * K * 2 * sizeof(double)))) return rc;
+                if (!(h->music.flags & NBLS_MUSIC_MAP)) {
+                    const size_t slabs = std::min<size_t>((size_t)h->capon_peak_slabs, std::max<size_t>((size_t)h->nunits, 1));
+                    if ((rc = ensure(h, h->d_music_slab, slabs * (size_t)G * sizeof(double)))) return rc;
+                }
+            }
+        }
         if (h->clean.iterations > 0) {   // the CLEAN-SC request: it reads R from d_capon_csdm whether or not the plan returns it
             const size_t I = (size_t)h->clean.iterations;
             if ((rc = ensure(h, h->d_clean_count, cells * sizeof(int32_t)))) return rc;
@@ -2054,6 +2089,80 @@ int nbls_fetch_capon_clean_csdm(nbls_handle* h, double* R) {
 int nbls_capon_clean_lds_bytes(int32_t nelem) {
     if (nelem < 1 || nelem > NBLS_CAPON_MAX_ELEMENTS) return NBLS_ERR_ARG;
     return (int)nbls_capon_clean_lds_bytes_of(nelem);
+}
+
+int nbls_set_capon_music(nbls_handle* h, int32_t sources, double eig_floor, double peak_floor, int32_t flags) {
+    if (!h) return NBLS_ERR_ARG;
+    if (sources == -1) { h->want_music = nbls_handle::capon_music_request(); return NBLS_OK; }   // off: the next plan launches no capon_music_kernel
+    if (sources < 0 || sources > NBLS_CAPON_MAX_ELEMENTS - 1) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: sources must be -1 (off), 0 (by the floor) or 1.." + std::to_string(NBLS_CAPON_MAX_ELEMENTS - 1));
+    if (sources == 0 && !(eig_floor > 0.0 && eig_floor < 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: the eigenvalue floor must lie in (0, 1)");
+    if (!(peak_floor >= 0.0 && peak_floor < 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: the peak floor must lie in [0, 1)");
+    if (flags & ~(NBLS_MUSIC_MAP | NBLS_MUSIC_VECTORS | NBLS_MUSIC_PEAKS)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: unknown flags");
+    nbls_handle::capon_music_request& r = h->want_music;         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    r.sources = sources;
+    r.eig_floor = sources == 0 ? eig_floor : 0.0;
+    r.peak_floor = peak_floor;
+    r.flags = flags;
+    return NBLS_OK;
+}
+
+// what the MUSIC fetches share beyond capon_fetch_ready: the plan asked
+static int music_fetch_ready(nbls_handle* h, const char* who) {
+    int rc;
+    if ((rc = capon_fetch_ready(h, who))) return rc;
+    if (h->music.sources < 0 || !h->d_music_eig) return fail(h, NBLS_ERR_STATE, std::string(who) + ": the plan did not ask for the eigenvalues (nbls_set_capon_music before nbls_plan)");
+    return 0;
+}
+
+int nbls_fetch_capon_music(nbls_handle* h, double* eigenvalues, int32_t* sources, int32_t* sweeps, int32_t* index, double* power) {
+    if (!h) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music")) || (rc = finish_pass(h))) return rc;
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    if ((rc = capon_fetch_plane(h, eigenvalues, h->d_music_eig.p, (size_t)h->nelem * sizeof(double)))) return rc;
+    if ((rc = capon_fetch_plane(h, sources, h->d_music_int.p, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, sweeps, h->d_music_int.p + cells, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, index, h->d_music_int.p + 2 * cells, sizeof(int32_t)))) return rc;
+    return capon_fetch_plane(h, power, h->d_music_power.p, sizeof(double));
+}
+
+int nbls_fetch_capon_music_map(nbls_handle* h, double* map) {
+    if (!h || !map) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music_map"))) return rc;
+    if (!(h->music.flags & NBLS_MUSIC_MAP) || !h->d_music_map)
+        return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_music_map: the plan did not ask for the map (nbls_set_capon_music, NBLS_MUSIC_MAP)");
+    if ((rc = finish_pass(h))) return rc;
+    return capon_fetch_plane(h, map, h->d_music_map.p, (size_t)h->capon_n * sizeof(double));
+}
+
+int nbls_fetch_capon_music_vectors(nbls_handle* h, double* E) {
+    if (!h || !E) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music_vectors"))) return rc;
+    if (!(h->music.flags & NBLS_MUSIC_VECTORS) || !h->d_music_vec)
+        return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_music_vectors: the plan did not ask for the eigenvectors (nbls_set_capon_music, NBLS_MUSIC_VECTORS)");
+    if ((rc = finish_pass(h))) return rc;
+    return capon_fetch_plane(h, E, h->d_music_vec.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+}
+
+int nbls_fetch_capon_music_peaks(nbls_handle* h, int32_t* count, int32_t* index, double* power, double* offset) {
+    if (!h) return NBLS_ERR_ARG;
+    int rc;
+    if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music_peaks"))) return rc;
+    if (!(h->music.flags & NBLS_MUSIC_PEAKS) || h->capon_peaks < 1 || !h->d_music_peak_count)
+        return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_music_peaks: the plan did not ask for the peaks (nbls_set_capon_music, NBLS_MUSIC_PEAKS)");
+    if ((rc = finish_pass(h))) return rc;
+    const size_t K = (size_t)h->capon_peaks;
+    if ((rc = capon_fetch_plane(h, count, h->d_music_peak_count.p, sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, index, h->d_music_peak_index.p, K * sizeof(int32_t)))) return rc;
+    if ((rc = capon_fetch_plane(h, power, h->d_music_peak_power.p, K * sizeof(double)))) return rc;
+    return capon_fetch_plane(h, offset, h->d_music_peak_offset.p, K * 2 * sizeof(double));
+}
+
+int nbls_capon_music_lds_bytes(int32_t nelem) {
+    if (nelem < 3 || nelem > NBLS_CAPON_MAX_ELEMENTS) return NBLS_ERR_ARG;
+    return (int)nbls_capon_music_lds_bytes_of(nelem);
 }
 
 int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* steer) {

@@ -57,6 +57,7 @@
 #include "wave_ops.h"
 #include "refine_fraction.h"
 #include "capon_point.h"
+#include "capon_peaks.h"
 #include <algorithm>
 #include <cmath>
 #include <utility>
@@ -108,105 +109,10 @@ __host__ __device__ inline size_t nbls_capon_lds_doubles(int nelem) {
 }
 
 // ---- the K strongest peaks of one spectrum of the unit (nbls_set_capon_peaks) ----
-constexpr int PKM = NBLS_CAPON_PEAKS_MAX;
-
-// A unit without spectra: count 0, every rank empty, both spectra.
-__device__ inline void capon_peaks_none(const CArgs& a, int64_t cell, int tid) {
-    const double nan_ = __builtin_nan("");
-    for (int which = 0; which < 2; ++which) {
-        const int64_t c = which * a.cells + cell;
-        if (tid == 0) a.pk_count[c] = 0;
-        if (tid < a.pk) {
-            const int64_t o = c * a.pk + tid;
-            a.pk_index[o] = -1; a.pk_power[o] = nan_;
-            a.pk_offset[2 * o] = nan_; a.pk_offset[2 * o + 1] = nan_;
-        }
-    }
-}
-
-// P [G]: the unit's spectrum, complete and visible to the workgroup (LDS or the unit's slab: the caller's pointer decides,
-// the code is one).  (bp, bg): the spectrum's arg-max as thread 0 holds it behind capon_best.
-//   1. every thread tests the points tid, tid + CT, ... against their neighbours and keeps its own K best kept peaks in
-//      registers: an unrolled compare-and-swap chain, every index a constant
-//   2. K rounds of capon_best over the threads' heads; the owner of a round's winner pops its head
-//   3. threads k < K write rank k with its two offsets
-__device__ inline void capon_peaks_of(const CArgs& a, const double* P, int which, int64_t cell, double bp, int bg,
-                                      double* sp, int* sg, int tid) {
-    __shared__ double win_p[PKM + 1];         // [k]: the winner of round k; [PKM]: the arg-max, for every thread
-    __shared__ int win_g[PKM + 1];
-    __shared__ int cnt_w[CW];
-    const int G = a.G, K = a.pk;
-    const double nan_ = __builtin_nan("");
-    if (tid == 0) { win_p[PKM] = bp; win_g[PKM] = bg; }
-    __syncthreads();
-    const double pmax = win_p[PKM];
-    const int gmax = win_g[PKM];
-    const double thr = a.pfloor * pmax;
-    double tp[PKM];
-    int tg[PKM];
-#pragma unroll
-    for (int k = 0; k < PKM; ++k) { tp[k] = 0.0; tg[k] = -1; }
-    int cnt = 0;
-    for (int g = tid; g < G; g += CT) {
-        const double p = P[g];
-        bool peak = p == p;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            const int n = a.nbr[(int64_t)d * G + g];
-            if (n < 0) continue;
-            const double q = P[n];
-            if (q == q && !(p > q || (p == q && g < n))) peak = false;       // capon_better(p, g; q, n) of two candidates
-        }
-        if (!peak) continue;
-        if (!(g == gmax || a.pfloor == 0.0 || p >= thr)) continue;
-        ++cnt;
-        double cp = p;
-        int cg = g;
-#pragma unroll
-        for (int k = 0; k < PKM; ++k)
-            if (k < K && capon_better(cp, cg, tp[k], tg[k])) {
-                const double op = tp[k]; const int og = tg[k];
-                tp[k] = cp; tg[k] = cg;
-                cp = op; cg = og;
-            }
-    }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((tid & 63) == 0) cnt_w[tid >> 6] = cnt;
-    for (int k = 0; k < K; ++k) {                                    // (K is the same for every thread)
-        double p = tp[0];
-        int g = tg[0];
-        capon_best(p, g, sp, sg, tid);
-        if (tid == 0) { win_p[k] = p; win_g[k] = g; }
-        __syncthreads();
-        const int wg = win_g[k];
-        if (wg >= 0 && tg[0] == wg) {                                // the owner pops its head
-#pragma unroll
-            for (int j = 0; j + 1 < PKM; ++j) { tp[j] = tp[j + 1]; tg[j] = tg[j + 1]; }
-            tg[PKM - 1] = -1;
-        }
-    }
-    const int64_t c = which * a.cells + cell;
-    if (tid == 0) {
-        int total = 0;
-        for (int j = 0; j < CW; ++j) total += cnt_w[j];
-        a.pk_count[c] = total;
-    }
-    if (tid < K) {
-        const int64_t o = c * K + tid;
-        const int g = win_g[tid];
-        if (g < 0) {
-            a.pk_index[o] = -1; a.pk_power[o] = nan_;
-            a.pk_offset[2 * o] = nan_; a.pk_offset[2 * o + 1] = nan_;
-        } else {
-            const double p0 = win_p[tid];
-            a.pk_index[o] = g; a.pk_power[o] = p0;
-            for (int ax = 0; ax < 2; ++ax) {
-                const int m = a.nbr[(int64_t)(2 * ax) * G + g], q = a.nbr[(int64_t)(2 * ax + 1) * G + g];
-                a.pk_offset[2 * o + ax] = (m < 0 || q < 0) ? 0.0 : refine_fraction(P[m], p0, P[q]);
-            }
-        }
-    }
-    __syncthreads();                                                 // (win_*, cnt_w and sp / sg are free again)
+// the peak request's results of spectrum `which` (capon_peaks.h: the picker is shared with capon_music_kernel)
+__device__ inline PeakOut capon_peak_out(const CArgs& a, int which) {
+    return PeakOut{a.nbr, a.G, a.pk, a.pfloor, a.pk_count + which * a.cells, a.pk_index + which * a.cells * a.pk,
+                   a.pk_power + which * a.cells * a.pk, a.pk_offset + which * a.cells * a.pk * 2};
 }
 
 // The KEPT instances' index list e[] (static LDS of those instances alone: its address is a constant, not a register).
@@ -345,7 +251,7 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
             a.index[cell] = -1; a.index[a.cells + cell] = -1;
             a.power[cell] = nan_; a.power[a.cells + cell] = nan_;
         }
-        if (PK) capon_peaks_none(a, cell, tid);
+        if (PK) { capon_peaks_none(capon_peak_out(a, 0), cell, tid); capon_peaks_none(capon_peak_out(a, 1), cell, tid); }
         return;
     }
     // R' = R + delta (t / N) I, then its Cholesky factor column by column
@@ -448,8 +354,8 @@ __global__ __launch_bounds__(CT) void capon_kernel(CArgs a) {
         // barrier already; the fence is for the slab)
         if (PK == 2) __threadfence_block();
         __syncthreads();
-        capon_peaks_of(a, mc, 0, cell, gc < 0 ? nan_ : bc, gc, red_p, red_g, tid);
-        capon_peaks_of(a, mb, 1, cell, gb < 0 ? nan_ : bb, gb, red_p, red_g, tid);
+        capon_peaks_of(capon_peak_out(a, 0), mc, cell, gc < 0 ? nan_ : bc, gc, red_p, red_g, tid);
+        capon_peaks_of(capon_peak_out(a, 1), mb, cell, gb < 0 ? nan_ : bb, gb, red_p, red_g, tid);
     }
 }
 
@@ -546,7 +452,7 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
     a.cells = (int64_t)h->nbands * h->vector_len;
     a.index = h->d_capon_index; a.power = h->d_capon_power;
     a.map = h->capon_maps ? h->d_capon_map.p : nullptr;
-    a.csdm = (h->capon_csdm || h->clean.iterations > 0) ? h->d_capon_csdm.p : nullptr;     // (capon_clean_kernel reads R there)
+    a.csdm = (h->capon_csdm || h->clean.iterations > 0 || h->music.sources >= 0) ? h->d_capon_csdm.p : nullptr;     // (capon_clean_kernel and capon_music_kernel read R there)
     const size_t lds = nbls_capon_lds_bytes_of(h->nelem);
     const bool kept = h->kept_capon;       // the spectra of the elements LTS kept (nbls_set_kept_elements): the KEPT instances
     if (kept) {

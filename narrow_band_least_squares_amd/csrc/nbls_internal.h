@@ -237,6 +237,27 @@ struct nbls_handle {
     dev_buf<double> d_clean_power;  // [B][VL][I]
     dev_buf<double> d_clean_tr;     // [2][B][VL]: total | residual
     dev_buf<double> d_clean_csdm;   // [B][VL][N][N][2] (NBLS_CLEAN_RESIDUAL)
+    // ---- the window's eigenvalues and MUSIC spectrum (nbls_set_capon_music, capon_music.hip) ----
+    struct capon_music_request {
+        int sources = -1;               // M, 0: by eig_floor, -1: off
+        double eig_floor = 0.0, peak_floor = 0.0;
+        int flags = 0;
+    };
+    capon_music_request want_music; // nbls_set_capon_music: read by the next nbls_plan
+    capon_music_request music;      // the plan's copy (sources -1: the plan launches no capon_music_kernel)
+    bool music_attr_set[2] = {false, false};    // the plain and the peak instance have their dynamic LDS limit
+    dev_buf<double> d_music_eig;    // [B][VL][N]
+    dev_buf<int32_t> d_music_int;   // [3][B][VL]: sources | sweeps | index
+    dev_buf<double> d_music_power;  // [B][VL]
+    dev_buf<double> d_music_map;    // [B][VL][G] (NBLS_MUSIC_MAP)
+    dev_buf<double> d_music_vec;    // [B][VL][N][N][2] (NBLS_MUSIC_VECTORS)
+    dev_buf<int32_t> d_music_peak_count;    // [B][VL] (NBLS_MUSIC_PEAKS; K of the plan's peak request)
+    dev_buf<int32_t> d_music_peak_index;    // [B][VL][K]
+    dev_buf<double> d_music_peak_power;     // [B][VL][K]
+    dev_buf<double> d_music_peak_offset;    // [B][VL][K][2]
+    dev_buf<double> d_music_slab;           // [slabs][G] (a peak request on a plan without NBLS_MUSIC_MAP)
+    hipEvent_t ev_music_slab = nullptr;     // behind the last launch that used the slabs
+    hipStream_t music_slab_stream = nullptr;    // where ev_music_slab was recorded last (nullptr: nowhere yet)
     // ---- the elements LTS kept (nbls_set_kept_elements, kept.hip) ----
     int want_kept_q = 0, want_kept_flags = 0;   // nbls_set_kept_elements: read by the next nbls_plan (q == 0: off)
     int kept_q = 0;                 // min_pairs of the plan (0: the plan does not ask)
@@ -460,6 +481,10 @@ size_t nbls_capon_lds_bytes_of(int nelem);
 hipError_t nbls_launch_capon_clean(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 // dynamic LDS bytes of capon_clean_kernel: R, v and a column of a per lane
 size_t nbls_capon_clean_lds_bytes_of(int nelem);
+// the eigenvalues and the MUSIC spectrum of units [u0, u0 + nu), behind nbls_launch_capon on the same stream (capon_music.hip)
+hipError_t nbls_launch_capon_music(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// dynamic LDS bytes of capon_music_kernel: R, E, a column of a per lane, the step's rotations, the eigenvalues and their order
+size_t nbls_capon_music_lds_bytes_of(int nelem);
 // ... of the instance that keeps the unit's two maps of G points in LDS (the LDS route of a peak request); 0: it does not fit
 size_t nbls_capon_peak_lds_bytes_of(int nelem, int G);
 // the automatic route of a peak request: 1 LDS, 2 HBM

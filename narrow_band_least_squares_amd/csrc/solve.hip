@@ -1447,6 +1447,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
     if (h->capon_n > 0 && &s == &h->est[0] && (e = nbls_launch_capon(h, u0, nu, st)) != hipSuccess) return e;
     // ... and the CLEAN-SC components of a plan that asked for them (nbls_set_capon_clean), on the matrices it has just written
     if (h->clean.iterations > 0 && &s == &h->est[0] && (e = nbls_launch_capon_clean(h, u0, nu, st)) != hipSuccess) return e;
+    // ... and the eigenvalues and the MUSIC spectrum of a plan that asked for them (nbls_set_capon_music), on the same matrices
+    if (h->music.sources >= 0 && &s == &h->est[0] && (e = nbls_launch_capon_music(h, u0, nu, st)) != hipSuccess) return e;
     return pack_weights_of(h, s, u0, nu, st);
 }
 

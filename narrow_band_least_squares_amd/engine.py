@@ -364,7 +364,8 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
                want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-               want_kept=False, beam_trace_npts=0, want_element_delays=False, clean_iterations=0, want_clean_csdm=False):
+               want_kept=False, beam_trace_npts=0, want_element_delays=False, clean_iterations=0, want_clean_csdm=False,
+               want_music=False, want_music_maps=False, want_music_vectors=False, want_music_peaks=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
@@ -382,11 +383,22 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
     beam of the others; ``clean_iterations`` = I > 0 (with ``capon_points``): ``clean_count`` (nbands, vector_len) int32,
     ``clean_index`` (.., I) int32, ``clean_power`` (.., I), ``clean_total`` and ``clean_residual`` (nbands, vector_len), the
     CLEAN-SC components of every window, and with ``want_clean_csdm`` ``clean_csdm`` (nbands, vector_len, nchans, nchans)
-    complex, the matrix they leave; None otherwise."""
+    complex, the matrix they leave; ``want_music`` (with ``capon_points``): ``music_eigenvalues`` (nbands, vector_len, nchans),
+    ``music_sources``, ``music_sweeps`` and ``music_index`` (nbands, vector_len) int32 and ``music_power`` (nbands, vector_len),
+    with ``want_music_maps`` ``music_map`` (nbands, vector_len, G) and with ``want_music_vectors`` ``music_vectors`` (nbands,
+    vector_len, nchans, nchans) complex, with ``want_music_peaks`` (and ``capon_peaks`` = K) ``music_peak_count`` (nbands,
+    vector_len) int32, ``music_peak_index`` (.., K) int32, ``music_peak_power`` (.., K) and ``music_peak_offset`` (.., K, 2); None
+    otherwise."""
     nb, P = len(nwin), nchans * (nchans - 1) // 2
     CI = int(clean_iterations) if capon_points else 0
+    MU = bool(want_music) and bool(capon_points)
     K = int(capon_peaks) if capon_points else 0
     peaks = {}
+    MK = K if (bool(want_music) and bool(want_music_peaks)) else 0
+    peaks['music_peak_count'] = np.zeros((nb, vector_len), dtype=np.int32) if MK else None
+    peaks['music_peak_index'] = np.zeros((nb, vector_len, MK), dtype=np.int32) if MK else None
+    peaks['music_peak_power'] = np.zeros((nb, vector_len, MK)) if MK else None
+    peaks['music_peak_offset'] = np.zeros((nb, vector_len, MK, 2)) if MK else None
     for which in ('capon', 'bartlett'):
         peaks[which + '_peak_count'] = np.zeros((nb, vector_len), dtype=np.int32) if K else None
         peaks[which + '_peak_index'] = np.zeros((nb, vector_len, K), dtype=np.int32) if K else None
@@ -427,6 +439,13 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                      clean_total=np.zeros((nb, vector_len)) if CI else None,
                      clean_residual=np.zeros((nb, vector_len)) if CI else None,
                      clean_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128) if (CI and want_clean_csdm) else None,
+                     music_eigenvalues=np.zeros((nb, vector_len, nchans)) if MU else None,
+                     music_sources=np.zeros((nb, vector_len), dtype=np.int32) if MU else None,
+                     music_sweeps=np.zeros((nb, vector_len), dtype=np.int32) if MU else None,
+                     music_index=np.zeros((nb, vector_len), dtype=np.int32) if MU else None,
+                     music_power=np.zeros((nb, vector_len)) if MU else None,
+                     music_map=np.zeros((nb, vector_len, capon_points)) if (MU and want_music_maps) else None,
+                     music_vectors=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128) if (MU and want_music_vectors) else None,
                      lts=alpha < 1.0, fs=fs, **peaks)
 
 
@@ -652,7 +671,8 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
            subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None, capon_clean=None, element_delays=None, element_delays_kept=False, beam_trace=None, beam_taps=0):
+           kept=None, capon_clean=None, capon_music=None, element_delays=None, element_delays_kept=False, beam_trace=None,
+           beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -681,7 +701,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     of the Prep: the plan also measures each element's delay against the beam of the others behind every solve, with
     ``element_delays_kept`` against the beam of the elements LTS kept, which needs ``kept`` (``Handle.set_element_delays``,
     ``planner.element_shifts``; for this plan only).  ``capon_clean``: ``(iterations, gain, floor, residual)`` of
-    ``Handle.set_capon_clean``: the plan also resolves every window's arrivals by CLEAN-SC (needs ``capon``; likewise)."""
+    ``Handle.set_capon_clean``: the plan also resolves every window's arrivals by CLEAN-SC (needs ``capon``; likewise).
+    ``capon_music``: ``(sources, eig_floor, maps, vectors, peaks, peak_floor)`` of ``Handle.set_capon_music``: the plan also returns every window's
+    eigenvalues and MUSIC spectrum (needs ``capon``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -732,6 +754,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
                 h.set_capon_peaks(cells, peaks, floor)
         if capon_clean is not None:
             h.set_capon_clean(*capon_clean)
+        if capon_music is not None:
+            h.set_capon_music(*capon_music)
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
     finally:
@@ -755,6 +779,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon_peaks(None)
         if capon_clean is not None:
             h.set_capon_clean(0)
+        if capon_music is not None:
+            h.set_capon_music(None)
         if kept is not None:
             h.set_kept_elements(0)
         if element_delays is not None:
@@ -900,6 +926,16 @@ def collect(res, h, b0, b1, streamed, note):
             getattr(res, field)[b0:b1] = a
     if res.clean_csdm is not None:
         res.clean_csdm[b0:b1] = h.fetch_capon_clean_csdm()
+    if res.music_eigenvalues is not None:
+        for field, a in zip(MUSIC_FIELDS, h.fetch_capon_music()):
+            getattr(res, field)[b0:b1] = a
+    if res.music_map is not None:
+        res.music_map[b0:b1] = h.fetch_capon_music_map()
+    if res.music_vectors is not None:
+        res.music_vectors[b0:b1] = h.fetch_capon_music_vectors()
+    if res.music_peak_count is not None:
+        for field, a in zip(PEAK_FIELDS, h.fetch_capon_music_peaks()):
+            getattr(res, 'music' + field)[b0:b1] = a
     if res.dropped_mask is not None:
         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = h.fetch_kept_elements()
     if res.element_delay is not None:
@@ -987,6 +1023,7 @@ def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
 
 
 CLEAN_FIELDS = ('clean_count', 'clean_index', 'clean_power', 'clean_total', 'clean_residual')   # what ``Handle.fetch_capon_clean`` returns, in order
+MUSIC_FIELDS = ('music_eigenvalues', 'music_sources', 'music_sweeps', 'music_index', 'music_power')   # what ``Handle.fetch_capon_music`` returns, in order
 PEAK_FIELDS = ('_peak_count', '_peak_index', '_peak_power', '_peak_offset')     # what ``Handle.fetch_capon_peaks`` returns, in order
 
 
@@ -1025,6 +1062,19 @@ def _check_capon_clean(capon_clean, capon):
     if not 1 <= len(args) <= 4:
         raise ValueError('capon_clean must be (iterations[, gain[, floor[, residual]]]), not %r' % (capon_clean,))
     return planner.check_capon_clean(*args, has_capon=capon is not None)
+
+
+def _check_capon_music(nchans, capon_music, capon, kept):
+    """``capon_music`` of ``process`` / ``process_batch`` — None, a number of sources or ``(sources[, eig_floor[, maps[, vectors[, peaks[, peak_floor]]]]])``
+    — -> the ``capon_music`` tuple of ``launch`` or None; ``ValueError`` before any GPU work (``planner.check_capon_music``).
+    ``kept``: the checked ``kept`` tuple of the call."""
+    if capon_music is None:
+        return None
+    args = tuple(capon_music) if isinstance(capon_music, (tuple, list)) else (capon_music,)
+    if not 1 <= len(args) <= 6:
+        raise ValueError('capon_music must be (sources[, eig_floor[, maps[, vectors[, peaks[, peak_floor]]]]]), not %r' % (capon_music,))
+    return planner.check_capon_music(nchans, *args, has_capon=capon is not None, has_peaks=capon is not None and bool(capon.get('peaks', 0)),
+                                     kept_capon=kept is not None and bool(kept[2]))
 
 
 def _check_kept(nchans, kept, want_beam, capon):
@@ -1089,7 +1139,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, element_max_shift=None,
+            capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, capon_music=None, element_max_shift=None,
             element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
@@ -1163,6 +1213,15 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     below ``floor`` times the first — with the mean element power before and after; ``residual``: also ``res.clean_csdm``
     (nbands, vector_len, N, N) complex (``nbls_set_capon_clean``).  ``ValueError`` before any GPU work
     (``planner.check_capon_clean``); ``process_segmented`` refuses it with the Capon spectra.
+    capon_music = sources or (sources, eig_floor, maps, vectors, peaks, peak_floor) (needs ``capon_grid``): also ``res.music_eigenvalues`` (nbands,
+    vector_len, N), the eigenvalues of every window's cross-spectral matrix in descending order, ``res.music_sources`` (the
+    number M of signal eigenvectors: ``sources``, or with 0 the eigenvalues of at least ``eig_floor`` times the largest),
+    ``res.music_sweeps`` (Jacobi sweeps), ``res.music_index`` and ``res.music_power``, the maximum of the MUSIC pseudo-spectrum
+    over the grid; ``maps``: also ``res.music_map`` (nbands, vector_len, G); ``vectors``: also ``res.music_vectors`` (nbands,
+    vector_len, N, N) complex; ``peaks`` (needs ``capon_peaks``): also ``res.music_peak_count`` / ``_index`` / ``_power`` /
+    ``_offset``, the K strongest local maxima of the MUSIC spectrum as ``capon_peaks`` returns a spectrum's, kept from
+    ``peak_floor`` times its maximum (``nbls_set_capon_music``).  ``ValueError`` before any GPU work
+    (``planner.check_capon_music``); not with ``kept=(.., .., True)``; ``process_segmented`` refuses it with the Capon spectra.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -1194,6 +1253,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
     clean = _check_capon_clean(capon_clean, capon)
+    music = _check_capon_music(nchans, capon_music, capon, kept)
     shifts = _check_element_delays(element_max_shift, element_delays_kept, len(band_edges), nchans, kept)
     trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
         want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
@@ -1220,14 +1280,17 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                          0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
                          0 if capon is None else capon.get('peaks', 0), kept is not None, npts if trace is not None else 0,
                          shifts is not None, clean_iterations=0 if clean is None else clean[0],
-                         want_clean_csdm=clean is not None and clean[3])
+                         want_clean_csdm=clean is not None and clean[3], want_music=music is not None,
+                         want_music_maps=music is not None and music[2], want_music_vectors=music is not None and music[3],
+                         want_music_peaks=music is not None and music[4])
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
                                  res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, element_delays=shifts,
+                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, capon_music=music,
+                                 element_delays=shifts,
                                  element_delays_kept=bool(element_delays_kept), beam_trace=trace, beam_taps=beam_taps)
     finally:
         if up is not None:
@@ -1462,8 +1525,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None, capon_clean=None, element_max_shift=None, element_delays_kept=False, want_beam_trace=None,
-                  beam_taps=0):
+                  kept=None, capon_clean=None, capon_music=None, element_max_shift=None, element_delays_kept=False,
+                  want_beam_trace=None, beam_taps=0):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1492,6 +1555,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
         raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
     kept = _check_kept(nchans, kept, want_beam, capon)
     clean = _check_capon_clean(capon_clean, capon)
+    music = _check_capon_music(nchans, capon_music, capon, kept)
     shifts = _check_element_delays(element_max_shift, element_delays_kept, nb, nchans, kept)
     trace = _check_beam_trace(want_beam_trace, prep.W, kept)
     tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
@@ -1505,7 +1569,9 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                       want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK,
                       want_kept=kept is not None, beam_trace_npts=npts if trace is not None else 0,
                       want_element_delays=shifts is not None, clean_iterations=0 if clean is None else clean[0],
-                      want_clean_csdm=clean is not None and clean[3])
+                      want_clean_csdm=clean is not None and clean[3], want_music=music is not None,
+                      want_music_maps=music is not None and music[2], want_music_vectors=music is not None and music[3],
+                      want_music_peaks=music is not None and music[4])
            for _ in range(S)]
     h = get_handle(device, 0)
     try:
@@ -1521,7 +1587,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean,
+                       closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, capon_music=music,
                        element_delays=shifts, element_delays_kept=bool(element_delays_kept),
                        beam_trace=trace, beam_taps=beam_taps)
                 g = np.zeros((4, R, VL))
@@ -1539,6 +1605,10 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
                 cpk = [[a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_peaks(which)] for which in (0, 1)] if CK else None
                 cln = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_clean()] if clean is not None else None
+                mus = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_music()] if music is not None else None
+                mum = h.fetch_capon_music_map().reshape(b1 - b0, k, VL, CG) if (music is not None and music[2]) else None
+                muv = h.fetch_capon_music_vectors().reshape(b1 - b0, k, VL, nchans, nchans) if (music is not None and music[3]) else None
+                mup = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_music_peaks()] if (music is not None and music[4]) else None
                 clr = h.fetch_capon_clean_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (clean is not None and clean[3]) else None
                 kel = [a.reshape(b1 - b0, k, VL) for a in h.fetch_kept_elements()] if kept is not None else None
                 eld = [a.reshape(b1 - b0, k, VL, nchans) for a in h.fetch_element_delays()] if shifts is not None else None
@@ -1571,6 +1641,16 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                             getattr(res, field)[b0:b1] = a[:, j]
                     if clr is not None:
                         res.clean_csdm[b0:b1] = clr[:, j]
+                    if mus is not None:
+                        for field, a in zip(MUSIC_FIELDS, mus):
+                            getattr(res, field)[b0:b1] = a[:, j]
+                    if mum is not None:
+                        res.music_map[b0:b1] = mum[:, j]
+                    if muv is not None:
+                        res.music_vectors[b0:b1] = muv[:, j]
+                    if mup is not None:
+                        for field, a in zip(PEAK_FIELDS, mup):
+                            getattr(res, 'music' + field)[b0:b1] = a[:, j]
                     if kel is not None:
                         res.dropped_mask[b0:b1], res.kept_count[b0:b1] = [a[:, j] for a in kel]
                     if eld is not None:

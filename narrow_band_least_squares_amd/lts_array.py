@@ -882,3 +882,92 @@ def ltsva_clean_batch(streams, lat_list, lon_list, window_length, window_overlap
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
                                    want_uncert=True, **kw)
     return [_returns(res, nchans, alpha) + (_returns_clean(res, grid, radius, S, n=int(res.nwin[0])),) for res in results]
+
+
+def _music_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor):
+    """The keywords of ``engine.process`` behind the arguments of ``ltsva_music`` for one filtered band of window length ``W``
+    samples -> (keywords, grid).  ``ValueError`` before any GPU work."""
+    kw = _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, 0.01, False, peaks)
+    kw['capon_music'] = planner.check_capon_music(nchans, sources, eig_floor, maps, vectors, 'capon_peaks' in kw, peak_floor)
+    return kw, kw['capon_grid']
+
+
+def _returns_music(res, grid, band=0, n=None):
+    """A band's MUSIC results as a dict: the fields of ``engine.MUSIC_FIELDS``, the slowness of the spectrum's maximum
+    (``grid_slowness``) and, where the pass kept them, ``music_map``, ``music_vectors`` and the peaks' four fields with the refined
+    slowness of every rank (``peak_slowness``) (csrc/capon_music.hip: capon_music_kernel).  ``band`` / ``n`` as for ``_returns_capon``."""
+    sl = slice(None) if n is None else slice(0, n)
+    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    out = {k: pick(getattr(res, k)) for k in engine.MUSIC_FIELDS}
+    for k in ('music_map', 'music_vectors'):
+        if getattr(res, k, None) is not None:
+            out[k] = pick(getattr(res, k))
+    out['music_vel'], out['music_baz'] = grid_slowness(grid, out['music_index'])
+    if getattr(res, 'music_peak_count', None) is not None:
+        for field in engine.PEAK_FIELDS:
+            out['music' + field] = pick(getattr(res, 'music' + field))
+        out['music_peak_slowness'], out['music_peak_vel'], out['music_peak_baz'] = peak_slowness(
+            grid, planner.grid_cells(grid)[1], out['music_peak_index'], out['music_peak_offset'])
+    return out
+
+
+def ltsva_music(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None, snapshots=None,
+                sources=0, eig_floor=0.05, maps=False, vectors=False, peaks=0, peak_floor=0.0):
+    """``ltsva`` followed by the eigenvalues of every window's narrow-band cross-spectral matrix and its MUSIC pseudo-spectrum
+    (Schmidt 1986) over ``slowness_grid`` (G, 2) s/km at ``freq`` Hz (``snapshots`` as for ``ltsva_capon``): the matrix is
+    decomposed by a cyclic Jacobi method, the ``sources`` = M strongest eigenvectors span the signals — ``sources=0``: as many
+    as there are eigenvalues of at least ``eig_floor`` times the largest — and P(g) = N / sum_{k > M} |e_k^H a(g)|^2 peaks
+    where a steering vector is orthogonal to the others (DESIGN.md section 25 has the definition, the error bounds and the
+    counts).  Returns ``ltsva``'s 8-tuple followed by one dict: ``music_eigenvalues`` (nwin, N) descending, ``music_sources``,
+    ``music_sweeps`` and ``music_index`` (nwin,) int32, ``music_power`` (nwin,), ``music_vel`` / ``music_baz``
+    (``grid_slowness``), with ``maps`` ``music_map`` (nwin, G) and with ``vectors`` ``music_vectors`` (nwin, N, N) complex,
+    column k beside eigenvalue k; with ``peaks`` = K in 1..8 the K strongest local maxima of the pseudo-spectrum that reach
+    ``peak_floor`` times its maximum, as ``ltsva_capon`` returns a spectrum's: ``music_peak_count``, ``music_peak_index`` /
+    ``_power`` (nwin, K), ``music_peak_offset`` (nwin, K, 2) and the refined ``music_peak_slowness``, ``music_peak_vel``,
+    ``music_peak_baz`` (the Capon and Bartlett peaks of the pass are not returned).  Computed on the GPU behind each window's solve (csrc/capon_music.hip).  Whatever the
+    library would refuse raises ``ValueError`` before any GPU work."""
+    _check_elements_strict(len(st), alpha)
+    nchans = len(st)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    data, fs, t0 = engine.stream_rows(st)
+    W = planner.window_plan(len(data[0]), fs, window_length, window_overlap)[0]
+    kw, grid = _music_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks,
+                               peak_floor)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, **kw)
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (_returns_music(res, grid, n=int(res.nwin[0])),)
+
+
+def ltsva_music_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
+                      snapshots=None, sources=0, eig_floor=0.05, maps=False, vectors=False, peaks=0, peak_floor=0.0):
+    """``ltsva_music`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
+    element i equal to ``ltsva_music(streams[i], ...)``; the streams as for ``ltsva_batch``."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
+    kw, grid = _music_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks,
+                               peak_floor)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_music(streams[0], lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha, rij,
+                            snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor)]
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, **kw)
+    return [_returns(res, nchans, alpha) + (_returns_music(res, grid, n=int(res.nwin[0])),) for res in results]

@@ -15,7 +15,7 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
-from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept, _returns_clean
+from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept, _returns_clean, _returns_music
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -407,6 +407,40 @@ def narrow_band_least_squares_clean(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     for k in ('clean_vel', 'clean_baz', 'source_power', 'source_vel', 'source_baz'):
         out[k] = np.where(computed[..., None], out[k], 0.0)
     out['source_slowness'] = np.where(computed[..., None, None], out['source_slowness'], 0.0)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + (out,)
+
+
+def narrow_band_least_squares_music(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                    FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                    slowness_grid, capon_freqs=None, snapshots=None, sources=0, eig_floor=0.05, maps=False,
+                                    vectors=False, peaks=0, peak_floor=0.0):
+    """``narrow_band_least_squares`` followed by the eigenvalues of every window's cross-spectral matrix and its MUSIC
+    pseudo-spectrum (``lts_array.ltsva_music``), computed on the GPU behind each window's solve.
+    ``capon_freqs`` and ``snapshots`` as for ``narrow_band_least_squares_capon``.  Returns the nine values of
+    ``narrow_band_least_squares`` followed by one dict with the fields of ``lts_array.ltsva_music``'s, each (NBANDS, vector_len,
+    ...) with zeros beyond a band's windows.  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    peak_kw = _peak_keywords(grid, peaks, 0.25)
+    music = planner.check_capon_music(len(st), sources, eig_floor, maps, vectors, bool(peak_kw), peak_floor)
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+    bands = list(range(NBANDS))
+    keywords = _capon_band_keywords(len(st), grid, capon_freqs, snapshots, 0.01, False, dict(peak_kw, capon_music=music), WINOVER, vector_len)
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
+    out = _returns_music(res, grid, band=None)
+    computed = np.arange(res.music_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    for k in ('music_vel', 'music_baz'):
+        out[k] = np.where(computed, out[k], 0.0)
+    if 'music_peak_vel' in out:
+        for k in ('music_peak_vel', 'music_peak_baz'):
+            out[k] = np.where(computed[..., None], out[k], 0.0)
+        out['music_peak_slowness'] = np.where(computed[..., None, None], out['music_peak_slowness'], 0.0)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (out,)
 

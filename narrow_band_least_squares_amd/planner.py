@@ -769,6 +769,41 @@ def check_capon_clean(iterations, gain=0.5, floor=0.02, residual=False, has_capo
     return int(iterations), float(gain), float(floor), bool(residual)
 
 
+def check_capon_music(nchans, sources=0, eig_floor=0.05, maps=False, vectors=False, peaks=False, peak_floor=0.0, has_capon=True,
+                      has_peaks=True, kept_capon=False, estimators=False, comm=False, segmented=False):
+    """Everything ``nbls_set_capon_music`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (sources int,
+    eig_floor float, maps bool, vectors bool, peaks bool, peak_floor float): an array of 3..32 elements, an integer ``sources`` in 0..nchans-1 (0: by the
+    floor), with ``sources=0`` an ``eig_floor`` in (0, 1), ``maps``, ``vectors`` and ``peaks`` bools, a ``peak_floor`` in [0, 1);
+    ``has_capon``: the call computes the Capon spectra the request works on; ``has_peaks``: and their peaks, whose K and cells
+    ``peaks`` uses; ``kept_capon``, ``estimators``, ``comm``, ``segmented``: the call also asks for the
+    spectra of the kept elements, further estimators, an RCCL communicator or the time-segmented path, none of which a MUSIC
+    request combines with."""
+    if isinstance(nchans, (bool, np.bool_)) or not isinstance(nchans, (int, np.integer)) or not (3 <= int(nchans) <= MAX_CAPON_ELEMENTS):
+        raise ValueError('a MUSIC request needs an array of 3..%d elements, not %r' % (MAX_CAPON_ELEMENTS, nchans))
+    if isinstance(sources, (bool, np.bool_)) or not isinstance(sources, (int, np.integer)) or not (0 <= int(sources) <= int(nchans) - 1):
+        raise ValueError('the MUSIC sources must be an integer in 0..%d (0: by eig_floor), not %r' % (int(nchans) - 1, sources))
+    if not _real(eig_floor) or (int(sources) == 0 and not (0.0 < float(eig_floor) < 1.0)):
+        raise ValueError('the MUSIC eig_floor must be a number in (0, 1), not %r' % (eig_floor,))
+    for name, flag in (('maps', maps), ('vectors', vectors), ('peaks', peaks)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError('%s must be True or False, not %r' % (name, flag))
+    if not _real(peak_floor) or not (0.0 <= float(peak_floor) < 1.0):
+        raise ValueError('the MUSIC peak_floor must be a number in [0, 1), not %r' % (peak_floor,))
+    if not has_capon:
+        raise ValueError('a MUSIC request needs the Capon spectra (capon_grid)')
+    if peaks and not has_peaks:
+        raise ValueError('the peaks of a MUSIC request need K and the cells of a peak request (capon_peaks, capon_cells)')
+    if kept_capon:
+        raise ValueError('a MUSIC request works on the full array: not with the Capon spectra of the kept elements')
+    if estimators:
+        raise ValueError('a MUSIC request is not supported with further estimators')
+    if comm:
+        raise ValueError('a MUSIC request is not supported with an RCCL communicator')
+    if segmented:
+        raise ValueError('a MUSIC request is not supported on the time-segmented path')
+    return int(sources), float(eig_floor), bool(maps), bool(vectors), bool(peaks), float(peak_floor)
+
+
 MAX_KEPT_ELEMENTS = 32    # elements of a plan that names the dropped ones: one bit each of a uint32 (csrc/kept.hip)
 
 
