@@ -325,12 +325,12 @@ int size_result_buffers(nbls_handle* h, nbls_estimator& x, size_t cells, size_t 
     if ((rc = ensure(h, x.d_res, x.res_bytes > min_res ? x.res_bytes : min_res))) return rc;
     if ((rc = ensure(h, own ? h->d_lag : x.d_lag, cells * P * sizeof(int32_t)))) return rc;
     if ((rc = ensure(h, own ? h->d_cmax : x.d_cmax, cells * P * sizeof(double)))) return rc;
-    if (h->refine && (rc = ensure(h, own ? h->d_lagfrac : x.d_lagfrac, cells * P * sizeof(double)))) return rc;
+    if (h->req.refine && (rc = ensure(h, own ? h->d_lagfrac : x.d_lagfrac, cells * P * sizeof(double)))) return rc;
     if ((rc = ensure(h, x.d_z, 2 * cells * sizeof(double)))) return rc;
     if ((rc = ensure(h, x.d_wts, cells * P))) return rc;
     if (x.want_unc && (rc = ensure(h, x.d_unc, 2 * cells * sizeof(double)))) return rc;
-    if (h->beam && (rc = ensure(h, x.d_beam, 2 * cells * sizeof(double)))) return rc;
-    if (h->closure) {
+    if (h->req.beam && (rc = ensure(h, x.d_beam, 2 * cells * sizeof(double)))) return rc;
+    if (h->req.closure) {
         const size_t N = own ? (size_t)h->nelem : x.kept.size();
         if ((rc = ensure(h, x.d_closure, 2 * cells * sizeof(double)))) return rc;
         if ((rc = ensure(h, x.d_closure_el, cells * (N ? N : 1) * sizeof(double)))) return rc;
@@ -358,6 +358,18 @@ void zero_uncomputed(const nbls_handle* h, void* out, size_t row_bytes) {
         if (first > 0) memset(band, 0, (size_t)first * row_bytes);
         if (first + n < h->vector_len) memset(band + (size_t)(first + n) * row_bytes, 0, (size_t)(h->vector_len - first - n) * row_bytes);
     }
+}
+
+// One result plane of a fetch, [B][VL] rows of row_bytes, into `out` (NULL: the caller does not want it).  No pass clears
+// these buffers: zeros until `valid` (a pass of this plan has run the stage that writes the plane; a later pass without
+// that stage leaves it as it is), then the plane, with zeros where no window was computed.
+int fetch_plane(nbls_handle* h, bool valid, void* out, const void* src, size_t row_bytes) {
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    if (!out) return NBLS_OK;
+    if (!valid) { memset(out, 0, cells * row_bytes); return NBLS_OK; }
+    HIPCHK(h, copy_sync(h, out, src, cells * row_bytes, hipMemcpyDeviceToHost));
+    zero_uncomputed(h, out, row_bytes);
+    return NBLS_OK;
 }
 
 }  // namespace
@@ -767,49 +779,58 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     }
     if (h->nest > 0 && (NS > 1 || !h->win_first.empty() || h->comm))
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: further estimators (nbls_set_estimators) are not supported with several segments, window ranges or the RCCL gather");
-    if (h->want_beam && h->comm)
+    const nbls_requests& w = h->want;
+    // what several requests need of the geometry (nbls_set_geometry): that it is the one of the trace's array of En elements,
+    // and of its pair list every pair in lexicographic order, or the pairs (0, m) in its first rows
+    const int En = h->nchans / NS;
+    const bool own_geometry = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs;
+    const bool pair_list = own_geometry && h->h_pair.size() == 2 * (size_t)h->npairs;
+    const auto lexicographic = [&] {
+        for (int i = 0, k = 0; pair_list && i < En; ++i)
+            for (int j = i + 1; j < En; ++j, ++k)
+                if (h->h_pair[2 * k] != i || h->h_pair[2 * k + 1] != j) return false;
+        return pair_list;
+    };
+    const auto first_rows_from_0 = [&] {
+        for (int m = 1; pair_list && m < En; ++m)
+            if (h->h_pair[2 * (m - 1)] != 0 || h->h_pair[2 * (m - 1) + 1] != m) return false;
+        return pair_list;
+    };
+    if (w.beam && h->comm)
         return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: beam results (nbls_set_beam) are not supported with an RCCL communicator (the gathered block does not carry them)");
-    if (h->want_closure) {           // closure of the picked lags (nbls_set_closure): every pair of the trace's array, in list order
+    if (w.closure) {                 // closure of the picked lags (nbls_set_closure): every pair of the trace's array, in list order
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: closure results (nbls_set_closure) are not supported with an RCCL communicator (the gathered block does not carry them)");
-        const int En = h->nchans / NS;
-        bool full = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
-        for (int i = 0, k = 0; full && i < En; ++i)
-            for (int j = i + 1; j < En; ++j, ++k)
-                if (h->h_pair[2 * k] != i || h->h_pair[2 * k + 1] != j) { full = false; break; }
-        if (!full)
+        if (!lexicographic())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: closure results (nbls_set_closure) need the geometry of the trace's array, every pair in lexicographic order");
     }
     std::vector<int32_t> gdel;       // the slowness grid (nbls_set_beam_grid): its delay table for this trace's array
     std::vector<double> gcoef;       // ... and, steered at fractional delays (nbls_set_beam_interpolation), its coefficient table
     int ghalo = 0;
-    if (h->want_steer_taps && !h->want_beam && h->want_grid.empty())
+    if (w.steer_taps && !w.beam && w.grid.empty())
         return fail(h, NBLS_ERR_STATE, "nbls_plan: fractional-sample steering (nbls_set_beam_interpolation) needs beam results (nbls_set_beam) or a slowness grid (nbls_set_beam_grid)");
-    if (!h->want_grid.empty()) {
+    if (!w.grid.empty()) {
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the slowness-grid search (nbls_set_beam_grid) is not supported with an RCCL communicator (the gathered block does not carry its grids)");
-        const int En = h->nchans / NS;
-        if (!h->est[0].d_xij || (int64_t)En * (En - 1) / 2 != h->npairs)
+        if (!own_geometry)
             return fail(h, NBLS_ERR_STATE, "nbls_plan: the slowness-grid search (nbls_set_beam_grid) needs the geometry of the trace's array");
-        const int G = (int)(h->want_grid.size() / 2);
+        const int G = (int)(w.grid.size() / 2);
         gdel.resize((size_t)G * En);
         bool made;
-        if (h->want_steer_taps) {    // floor(tau) and the Lagrange coefficients instead of rint(tau)
-            gcoef.resize((size_t)G * En * h->want_steer_taps);
-            made = nbls_beam_grid_steer_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, h->want_steer_taps, gdel.data(),
-                                           gcoef.data(), &ghalo);
+        if (w.steer_taps) {          // floor(tau) and the Lagrange coefficients instead of rint(tau)
+            gcoef.resize((size_t)G * En * w.steer_taps);
+            made = nbls_beam_grid_steer_of(h->est[0].h_xij.data(), En, h->fs, w.grid.data(), G, w.steer_taps, gdel.data(), gcoef.data(), &ghalo);
         } else {
-            made = nbls_beam_grid_delays_of(h->est[0].h_xij.data(), En, h->fs, h->want_grid.data(), G, gdel.data(), &ghalo);
+            made = nbls_beam_grid_delays_of(h->est[0].h_xij.data(), En, h->fs, w.grid.data(), G, gdel.data(), &ghalo);
         }
         if (!made)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: a delay of the slowness grid (nbls_set_beam_grid) reaches 2^30 samples");
     }
-    if (!h->want_capon.grid.empty()) {   // Capon spectra (nbls_set_capon): the tables are made once the windows are known (plan_capon)
-        const nbls_handle::capon_request& c = h->want_capon;
+    if (!w.capon.grid.empty()) {     // Capon spectra (nbls_set_capon): the tables are made once the windows are known (plan_estimators)
+        const nbls_requests::capon_request& c = w.capon;
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: Capon spectra (nbls_set_capon) are not supported with an RCCL communicator (the gathered block does not carry them)");
-        const int En = h->nchans / NS;
-        if (!h->est[0].d_xij || (int64_t)En * (En - 1) / 2 != h->npairs)
+        if (!own_geometry)
             return fail(h, NBLS_ERR_STATE, "nbls_plan: Capon spectra (nbls_set_capon) need the geometry of the trace's array");
         if (En > NBLS_CAPON_MAX_ELEMENTS)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: Capon spectra (nbls_set_capon) support up to " + std::to_string(NBLS_CAPON_MAX_ELEMENTS) + " elements");
@@ -826,84 +847,74 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if ((size_t)a.nbands * (c.grid.size() / 2) * (size_t)En * 16 > ((size_t)1 << 30))
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the Capon steering table (nbands * G * N * 16 bytes) exceeds 1 GiB");
     }
-    if (h->want_clean.iterations > 0 && h->want_capon.grid.empty())      // the CLEAN-SC request (nbls_set_capon_clean) works on the spectra's R and tables
+    if (w.clean.iterations > 0 && w.capon.grid.empty())      // the CLEAN-SC request (nbls_set_capon_clean) works on the spectra's R and tables
         return fail(h, NBLS_ERR_STATE, "nbls_plan: a CLEAN request (nbls_set_capon_clean) needs Capon spectra (nbls_set_capon)");
-    if (h->want_music.sources >= 0) {    // the MUSIC request (nbls_set_capon_music): the spectra's R and tables, the full array, estimator 0 alone
-        if (h->want_capon.grid.empty())
+    if (w.music.sources >= 0) {      // the MUSIC request (nbls_set_capon_music): the spectra's R and tables, the full array, estimator 0 alone
+        if (w.capon.grid.empty())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: a MUSIC request (nbls_set_capon_music) needs Capon spectra (nbls_set_capon)");
         if (h->nest > 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: a MUSIC request (nbls_set_capon_music) is not supported with further estimators (nbls_set_estimators)");
-        if (h->want_kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_CAPON))
+        if (w.kept_capon())
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: a MUSIC request (nbls_set_capon_music) is not supported with NBLS_KEPT_CAPON (nbls_set_kept_elements): it works on the full array");
-        const int En = h->nchans / NS;
         if (En < 3)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: a MUSIC request (nbls_set_capon_music) needs at least 3 elements");
-        if (h->want_music.sources > En - 1)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_music.sources) + " sources (nbls_set_capon_music) for an array of " +
+        if (w.music.sources > En - 1)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(w.music.sources) + " sources (nbls_set_capon_music) for an array of " +
                                              std::to_string(En) + " elements (1.." + std::to_string(En - 1) + ")");
+        if ((w.music.flags & NBLS_MUSIC_PEAKS) && w.peaks.nbr.empty())
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_MUSIC_PEAKS (nbls_set_capon_music) needs K and the cells of a peak request (nbls_set_capon_peaks)");
     }
-    if (h->want_music.sources >= 0 && (h->want_music.flags & NBLS_MUSIC_PEAKS) && h->want_capon_peaks.nbr.empty())
-        return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_MUSIC_PEAKS (nbls_set_capon_music) needs K and the cells of a peak request (nbls_set_capon_peaks)");
     int peak_route = 0;              // the peaks of the spectra (nbls_set_capon_peaks): Capon spectra of the same G, and a route
-    if (!h->want_capon_peaks.nbr.empty()) {
-        const size_t G = h->want_capon.grid.size() / 2;
+    if (!w.peaks.nbr.empty()) {
+        const size_t G = w.capon.grid.size() / 2;
         if (!G)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: a peak request (nbls_set_capon_peaks) needs Capon spectra (nbls_set_capon)");
-        if (h->want_capon_peaks.nbr.size() != 8 * G)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: the peak request (nbls_set_capon_peaks) has " + std::to_string(h->want_capon_peaks.nbr.size() / 8) +
+        if (w.peaks.nbr.size() != 8 * G)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: the peak request (nbls_set_capon_peaks) has " + std::to_string(w.peaks.nbr.size() / 8) +
                                              " cells for Capon spectra of " + std::to_string(G) + " points");
         // the unit's two maps wait in LDS or in HBM (capon.hip: nbls_capon_peak_route_of has the automatic choice)
-        const bool fits = nbls_capon_peak_lds_bytes_of(h->nchans / NS, (int)G) != 0;
-        peak_route = h->opt.capon_peak_route ? h->opt.capon_peak_route : nbls_capon_peak_route_of(h->nchans / NS, (int)G);
+        const bool fits = nbls_capon_peak_lds_bytes_of(En, (int)G) != 0;
+        peak_route = h->opt.capon_peak_route ? h->opt.capon_peak_route : nbls_capon_peak_route_of(En, (int)G);
         if (peak_route == 1 && !fits)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: option capon_peak_route 1: the two maps of " + std::to_string(G) + " points do not fit the LDS of a workgroup beside the kernel's " +
-                                                     std::to_string(nbls_capon_lds_bytes_of(h->nchans / NS)) + " bytes");
+                                                     std::to_string(nbls_capon_lds_bytes_of(En)) + " bytes");
     }
-    if (h->want_kept_q > 0) {        // the elements LTS kept (nbls_set_kept_elements): the full pair list, estimator 0 alone
+    if (w.kept_q > 0) {              // the elements LTS kept (nbls_set_kept_elements): the full pair list, estimator 0 alone
         if (h->nest > 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the kept elements (nbls_set_kept_elements) are not supported with further estimators (nbls_set_estimators)");
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the kept elements (nbls_set_kept_elements) are not supported with an RCCL communicator (the gathered block does not carry them)");
-        const int En = h->nchans / NS;
-        bool full = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
-        for (int i = 0, k = 0; full && i < En; ++i)
-            for (int j = i + 1; j < En; ++j, ++k)
-                if (h->h_pair[2 * k] != i || h->h_pair[2 * k + 1] != j) { full = false; break; }
-        if (!full)
+        if (!lexicographic())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: the kept elements (nbls_set_kept_elements) need the geometry of the trace's array, every pair in lexicographic order");
-        if (En > 32 || h->want_kept_q > En - 1)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: min_pairs (nbls_set_kept_elements) is " + std::to_string(h->want_kept_q) + " for an array of " +
+        if (En > 32 || w.kept_q > En - 1)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: min_pairs (nbls_set_kept_elements) is " + std::to_string(w.kept_q) + " for an array of " +
                                              std::to_string(En) + " elements (1.." + std::to_string(En - 1) + ", at most 32 elements)");
-        if ((h->want_kept_flags & NBLS_KEPT_BEAM) && !h->want_beam)
+        if ((w.kept_flags & NBLS_KEPT_BEAM) && !w.beam)
             return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_KEPT_BEAM (nbls_set_kept_elements) needs beam results (nbls_set_beam)");
-        if ((h->want_kept_flags & NBLS_KEPT_CAPON) && h->want_capon.grid.empty())
+        if ((w.kept_flags & NBLS_KEPT_CAPON) && w.capon.grid.empty())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_KEPT_CAPON (nbls_set_kept_elements) needs Capon spectra (nbls_set_capon)");
     }
-    if (h->want_bt) {                // the beam trace (nbls_set_beam_trace): estimator 0, every window of every band, one synthesis window per band
+    if (w.bt) {                      // the beam trace (nbls_set_beam_trace): estimator 0, every window of every band, one synthesis window per band
         if (!h->win_first.empty())
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the beam trace (nbls_set_beam_trace) is not supported with window ranges (nbls_set_window_ranges): a slice of the windows does not cover the trace");
         if (h->nest > 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the beam trace (nbls_set_beam_trace) is not supported with further estimators (nbls_set_estimators)");
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the beam trace (nbls_set_beam_trace) is not supported with an RCCL communicator (the gathered block does not carry it)");
-        const int En = h->nchans / NS;
-        bool rows = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
-        for (int m = 1; rows && m < En; ++m)
-            if (h->h_pair[2 * (m - 1)] != 0 || h->h_pair[2 * (m - 1) + 1] != m) rows = false;
-        if (!rows)
+        if (!first_rows_from_0())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: the beam trace (nbls_set_beam_trace) needs the geometry of the trace's array, its first rows the pairs (0, m)");
-        if ((h->want_bt_flags & NBLS_BEAM_TRACE_KEPT) && h->want_kept_q < 1)
+        if ((w.bt_flags & NBLS_BEAM_TRACE_KEPT) && w.kept_q < 1)
             return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_BEAM_TRACE_KEPT (nbls_set_beam_trace) needs the kept elements (nbls_set_kept_elements)");
         int64_t sumw = 0;
         for (int b = 0; b < a.nbands; ++b) sumw += a.winlen[b] > 0 ? a.winlen[b] : 0;
-        if ((int64_t)h->want_bt_win.size() != sumw)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: a synthesis window table (nbls_set_beam_trace) of " + std::to_string(h->want_bt_win.size()) +
+        if ((int64_t)w.bt_win.size() != sumw)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: a synthesis window table (nbls_set_beam_trace) of " + std::to_string(w.bt_win.size()) +
                                              " entries for bands whose window lengths add up to " + std::to_string(sumw));
         int64_t o = 0;
         for (int b = 0; b < a.nbands; ++b) {
             bool any = false;
             for (int t = 0; t < a.winlen[b]; ++t) {
-                const double g = h->want_bt_win[(size_t)(o + t)];
+                const double g = w.bt_win[(size_t)(o + t)];
                 if (!(g >= 0.0) || std::isinf(g))
                     return fail(h, NBLS_ERR_ARG, "nbls_plan: the synthesis window (nbls_set_beam_trace) of band " + std::to_string(b) + " has a negative or non-finite entry");
                 any = any || g > 0.0;
@@ -914,28 +925,24 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         }
     }
     size_t ed_lds = 0;
-    if (h->want_ed) {                // the element delays (nbls_set_element_delays): estimator 0, one max_shift per band
-        if ((int)h->want_ed_K.size() != a.nbands)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_ed_K.size()) + " shift ranges (nbls_set_element_delays) for a plan of " +
+    if (w.ed) {                      // the element delays (nbls_set_element_delays): estimator 0, one max_shift per band
+        if ((int)w.ed_K.size() != a.nbands)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(w.ed_K.size()) + " shift ranges (nbls_set_element_delays) for a plan of " +
                                              std::to_string(a.nbands) + " bands");
-        const int En = h->nchans / NS;
         if (En > 32)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: the element delays (nbls_set_element_delays) take at most 32 elements, not " + std::to_string(En));
         if (h->nest > 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the element delays (nbls_set_element_delays) are not supported with further estimators (nbls_set_estimators)");
         if (h->comm)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the element delays (nbls_set_element_delays) are not supported with an RCCL communicator (the gathered block does not carry them)");
-        bool rows = h->est[0].d_xij && (int64_t)En * (En - 1) / 2 == h->npairs && h->h_pair.size() == 2 * (size_t)h->npairs;
-        for (int m = 1; rows && m < En; ++m)
-            if (h->h_pair[2 * (m - 1)] != 0 || h->h_pair[2 * (m - 1) + 1] != m) rows = false;
-        if (!rows)
+        if (!first_rows_from_0())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: the element delays (nbls_set_element_delays) need the geometry of the trace's array, its first rows the pairs (0, m)");
-        if ((h->want_ed_flags & NBLS_ELEMENT_DELAY_KEPT) && h->want_kept_q < 1)
+        if ((w.ed_flags & NBLS_ELEMENT_DELAY_KEPT) && w.kept_q < 1)
             return fail(h, NBLS_ERR_STATE, "nbls_plan: NBLS_ELEMENT_DELAY_KEPT (nbls_set_element_delays) needs the kept elements (nbls_set_kept_elements)");
         // the form: staged where the block of every band fits the LDS of a workgroup (element_delay.hip), else global
         bool fits = true;
         for (int b = 0; b < a.nbands; ++b) {
-            const size_t lds = a.winlen[b] > 0 ? nbls_element_delay_lds_bytes_of(En, a.winlen[b], h->want_ed_K[(size_t)b]) : 0;
+            const size_t lds = a.winlen[b] > 0 ? nbls_element_delay_lds_bytes_of(En, a.winlen[b], w.ed_K[(size_t)b]) : 0;
             if (!lds) fits = false;
             if (lds > ed_lds) ed_lds = lds;
         }
@@ -943,74 +950,25 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: option element_delay_form 1: the rows of a band's windows do not fit the LDS of a workgroup");
         if (!fits || h->opt.element_delay_form == 2) ed_lds = 0;
     }
-    if (!h->want_lim.empty()) {      // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
-        if (!h->est[0].d_xij || (int)h->want_lim.size() != h->npairs)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
+    if (!w.lim.empty()) {            // lag limits (nbls_set_lag_limits): one per pair of the geometry, the auto route only
+        if (!h->est[0].d_xij || (int)w.lim.size() != h->npairs)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(w.lim.size()) + " lag limits (nbls_set_lag_limits) for a geometry of " +
                                              std::to_string(h->est[0].d_xij ? h->npairs : 0) + " pairs");
         if (a.xcorr_impl != 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: lag limits (nbls_set_lag_limits) need xcorr_impl 0: the forced correlators search every lag");
     }
-    if (!h->want_seed.empty()) {     // the lag seed (nbls_set_lag_seed): one half-width per band, a plan with a slowness grid, the auto route only
-        if ((int)h->want_seed.size() != a.nbands)
-            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(h->want_seed.size()) + " seed half-widths (nbls_set_lag_seed) for a plan of " +
+    if (!w.seed.empty()) {           // the lag seed (nbls_set_lag_seed): one half-width per band, a plan with a slowness grid, the auto route only
+        if ((int)w.seed.size() != a.nbands)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: " + std::to_string(w.seed.size()) + " seed half-widths (nbls_set_lag_seed) for a plan of " +
                                              std::to_string(a.nbands) + " bands");
-        if (h->want_grid.empty())
+        if (w.grid.empty())
             return fail(h, NBLS_ERR_STATE, "nbls_plan: the lag seed (nbls_set_lag_seed) needs a slowness grid (nbls_set_beam_grid)");
-        if (!h->want_lim.empty())
+        if (!w.lim.empty())
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the lag seed (nbls_set_lag_seed) is not supported together with lag limits (nbls_set_lag_limits): the grid's extent bounds the slowness, one restriction at a time");
         if (a.xcorr_impl != 0)
             return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the lag seed (nbls_set_lag_seed) needs xcorr_impl 0: the forced correlators search every lag");
     }
-    h->lim = h->want_lim;
-    h->seed = h->want_seed;
-    h->beam = h->want_beam;
-    h->beam_valid = false;
-    h->closure = h->want_closure;
-    h->closure_valid = false;
-    h->kept_q = h->want_kept_q;
-    h->kept_beam = h->kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_BEAM);
-    h->kept_capon = h->kept_q > 0 && (h->want_kept_flags & NBLS_KEPT_CAPON);
-    h->kept_valid = false;
-    h->bt = h->want_bt;
-    h->bt_kept = h->bt && (h->want_bt_flags & NBLS_BEAM_TRACE_KEPT);
-    h->bt_min = h->want_bt_min;
-    h->bt_valid = false;
-    h->ed = h->want_ed;
-    h->ed_kept = h->ed && (h->want_ed_flags & NBLS_ELEMENT_DELAY_KEPT);
-    h->ed_lds = ed_lds;
-    h->ed_valid = false;
-    h->refine = h->want_refine;
-    h->frac_valid = false;
-    h->solve_ran = false;
-    h->h_grid = h->want_grid;
-    h->h_grid_delay.swap(gdel);
-    h->h_grid_coef.swap(gcoef);
-    h->steer_taps = h->want_steer_taps;
-    h->grid_taps = h->want_grid.empty() ? 0 : h->want_steer_taps;
-    h->grid_n = (int)(h->h_grid.size() / 2);
-    h->grid_halo = ghalo;
-    h->grid_map = h->grid_n > 0 && h->want_grid_map;
-    h->grid_valid = false;
-    h->capon = h->want_capon;
-    h->capon_n = (int)(h->capon.grid.size() / 2);
-    h->capon_loading = h->capon.loading;
-    h->capon_maps = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_MAPS);
-    h->capon_csdm = h->capon_n > 0 && (h->capon.flags & NBLS_CAPON_CSDM);
-    h->capon_valid = false;
-    h->clean = h->capon_n > 0 ? h->want_clean : nbls_handle::capon_clean_request();
-    h->music = h->capon_n > 0 ? h->want_music : nbls_handle::capon_music_request();
-    h->capon_peaks = peak_route ? h->want_capon_peaks.k : 0;
-    h->capon_peak_floor = h->want_capon_peaks.floor;
-    h->capon_peak_route = peak_route;
-    // the slabs of the HBM route: what the option says, else as many as 256 MiB hold, 256 at least (which is 256 MiB at the
-    // largest grid) and 4096 at most: a launch of 256 workgroups is one per CU (DESIGN.md section 19.4)
-    h->capon_peak_slabs = h->opt.capon_peak_slabs;
-    if (peak_route && h->capon_peak_slabs < 1) {
-        const size_t fit = ((size_t)256 << 20) / (2 * (h->want_capon.grid.size() / 2) * sizeof(double));
-        h->capon_peak_slabs = (int)std::min<size_t>(4096, std::max<size_t>(256, fit));
-    }
-    h->nelem = h->nchans / NS;
-    const int E = h->nelem;
+    const int E = En;
     nbls_estimator& x0 = h->est[0];
     for (int e = 1; e <= h->nest; ++e)
         if (!x0.d_xij || h->est[e].kept.empty() || h->est[e].kept.back() >= E || ((int)h->est[e].kept.size() == E) != h->est[e].kept_pair.empty())
@@ -1026,6 +984,32 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if (E < 4) return fail(h, NBLS_ERR_GEOMETRY, "LTS needs at least 4 array elements");
         const int rc = check_lts(h, a.lts, P, "nbls_plan: ");
         if (rc) return rc;
+    }
+    // nothing was refused: the handle takes the plan's requests (a refused plan has left `req` as it was) and what derives
+    // from them; no pass of this plan has run yet
+    h->req = w;
+    if (w.capon.grid.empty()) {      // the CLEAN-SC and MUSIC requests belong to the spectra: a plan without them has neither
+        h->req.clean = nbls_requests::capon_clean_request();
+        h->req.music = nbls_requests::capon_music_request();
+    }
+    nbls_plan_derived& d = h->derived;
+    d.grid_n = (int)(w.grid.size() / 2);
+    d.grid_halo = ghalo;
+    d.grid_delay.swap(gdel);
+    d.grid_coef.swap(gcoef);
+    d.capon_n = (int)(w.capon.grid.size() / 2);
+    d.peak_route = peak_route;
+    // the slabs of the HBM route: what the option says, else as many as 256 MiB hold, 256 at least (which is 256 MiB at the
+    // largest grid) and 4096 at most: a launch of 256 workgroups is one per CU (DESIGN.md section 19.4)
+    d.peak_slabs = h->opt.capon_peak_slabs;
+    if (peak_route && d.peak_slabs < 1) {
+        const size_t fit = ((size_t)256 << 20) / (2 * (size_t)d.capon_n * sizeof(double));
+        d.peak_slabs = (int)std::min<size_t>(4096, std::max<size_t>(256, fit));
+    }
+    d.ed_lds = ed_lds;
+    h->solve_ran = h->xcorr_ran = false;
+    h->nelem = E;
+    if (a.lts) {
         x0.ltsp = *a.lts;
         x0.ltsp.starts = nullptr;
         x0.ltsp.rew_table = nullptr;
@@ -1190,20 +1174,20 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
     h->wgroups.clear();
     int maxWP = 0;
     bool all_ok = true, any_ok = false;
-    const int32_t min_lim = h->lim.empty() ? 0 : *std::min_element(h->lim.begin(), h->lim.end());
-    if (!h->lim.empty()) {
+    const int32_t min_lim = h->req.lim.empty() ? 0 : *std::min_element(h->req.lim.begin(), h->req.lim.end());
+    if (!h->req.lim.empty()) {
         const int E = h->nelem;
         std::vector<int32_t> sq((size_t)E * E, 0);
         for (int k = 0; k < h->npairs; ++k) {
             const int i = h->h_pair[2 * k], j = h->h_pair[2 * k + 1];
             if (i < 0 || j < 0 || i >= E || j >= E) return fail(h, NBLS_ERR_ARG, "nbls_plan: a pair of the geometry names an element the trace does not have");
-            sq[(size_t)i * E + j] = sq[(size_t)j * E + i] = h->lim[(size_t)k];
+            sq[(size_t)i * E + j] = sq[(size_t)j * E + i] = h->req.lim[(size_t)k];
         }
         if (int rc = alloc_copy(h, h->d_limsq, sq.data(), sq.size())) return rc;
     }
-    if (!h->seed.empty()) {          // the half-width of every result row: row r is band r / nseg
+    if (!h->req.seed.empty()) {          // the half-width of every result row: row r is band r / nseg
         std::vector<int32_t> rows((size_t)R);
-        for (int r = 0; r < R; ++r) rows[(size_t)r] = h->seed[(size_t)(r / h->nseg)];
+        for (int r = 0; r < R; ++r) rows[(size_t)r] = h->req.seed[(size_t)(r / h->nseg)];
         for (size_t k = 0; k < h->h_pair.size(); ++k)
             if (h->h_pair[k] < 0 || h->h_pair[k] >= h->nelem) return fail(h, NBLS_ERR_ARG, "nbls_plan: a pair of the geometry names an element the trace does not have");
         if (int rc = alloc_copy(h, h->d_seed, rows.data(), rows.size())) return rc;
@@ -1213,7 +1197,7 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
         while (e < R && h->W[e] == h->W[b]) ++e;
         nbls_wgroup g{b, e, h->W[b], h->unit_off[b], h->unit_off[e], false};
         // a plan with a lag seed: every group takes the seeded correlator in the general correlators' slot
-        if (!h->seed.empty()) {
+        if (!h->req.seed.empty()) {
             g.sform = nbls_lag_seed_form_of(h->nelem, g.W);
             h->wgroups.push_back(g);
             b = e;
@@ -1224,7 +1208,7 @@ static int plan_window_groups(nbls_handle* h, const plan_args& a) {
         g.screen = h->est[0].d_xij && r.correlator == NBLS_ROUTE_SCREEN;
         // a plan with lag limits: a group whose windows are longer than the smallest limit takes the bounded-lag correlator
         // in the general correlators' slot; where every limit reaches W-1 the full search is the bounded one
-        if (!h->lim.empty()) g.bform = nbls_lag_limit_form_of(h->nelem, g.W, std::min(min_lim, g.W - 1));
+        if (!h->req.lim.empty()) g.bform = nbls_lag_limit_form_of(h->nelem, g.W, std::min(min_lim, g.W - 1));
         if (g.bform) { g.screen = false; h->wgroups.push_back(g); b = e; continue; }
         if (g.screen) { any_ok = true; if (r.WP > maxWP) maxWP = r.WP; }
         else if (g.u1 > g.u0) all_ok = false;
@@ -1278,102 +1262,102 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
             if ((rc = alloc_copy(h, x.d_xij, x.h_xij.data(), x.h_xij.size()))) return rc;
             if ((rc = alloc_copy(h, x.d_xpinv, x.h_xpinv.data(), x.h_xpinv.size()))) return rc;
             if (!x.kept_pair.empty() && (rc = alloc_copy(h, x.d_kept_pair, x.kept_pair.data(), x.kept_pair.size()))) return rc;
-            if (h->beam && (rc = alloc_copy(h, x.d_kept, x.kept.data(), x.kept.size()))) return rc;
+            if (h->req.beam && (rc = alloc_copy(h, x.d_kept, x.kept.data(), x.kept.size()))) return rc;
         }
         if (x.lts && (rc = upload_lts_tables(h, x))) return rc;
         if (e > 0 && (rc = size_result_buffers(h, x, (size_t)a.R * a.vector_len, 0))) return rc;
     }
-    if (h->grid_n > 0) {             // the slowness-grid search: its two tables and its result buffers, for a plan that asks only
+    if (h->derived.grid_n > 0) {             // the slowness-grid search: its two tables and its result buffers, for a plan that asks only
         const size_t cells = (size_t)a.R * a.vector_len;
-        if ((rc = alloc_copy(h, h->d_grid, h->h_grid.data(), h->h_grid.size()))) return rc;
-        if ((rc = alloc_copy(h, h->d_grid_delay, h->h_grid_delay.data(), h->h_grid_delay.size()))) return rc;
-        if (h->grid_taps && (rc = alloc_copy(h, h->d_grid_coef, h->h_grid_coef.data(), h->h_grid_coef.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_grid, h->req.grid.data(), h->req.grid.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_grid_delay, h->derived.grid_delay.data(), h->derived.grid_delay.size()))) return rc;
+        if (h->req.grid_taps() && (rc = alloc_copy(h, h->d_grid_coef, h->derived.grid_coef.data(), h->derived.grid_coef.size()))) return rc;
         if ((rc = ensure(h, h->d_grid_index, cells * sizeof(int32_t)))) return rc;
         if ((rc = ensure(h, h->d_grid_fp, 2 * cells * sizeof(double)))) return rc;
-        if (h->grid_map && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->grid_n * sizeof(double)))) return rc;
+        if (h->req.grid_map() && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->derived.grid_n * sizeof(double)))) return rc;
     }
-    if (h->kept_q > 0) {             // the elements LTS kept: the mask and the count of every cell
+    if (h->req.kept_q > 0) {             // the elements LTS kept: the mask and the count of every cell
         const size_t cells = (size_t)a.R * a.vector_len;
         if ((rc = ensure(h, h->d_kept_mask, cells * sizeof(uint32_t)))) return rc;
         if ((rc = ensure(h, h->d_kept_count, cells * sizeof(int32_t)))) return rc;
     }
-    if (h->bt) {                     // the beam trace: the synthesis windows, where every row's starts, and the trace of every row
+    if (h->req.bt) {                     // the beam trace: the synthesis windows, where every row's starts, and the trace of every row
         std::vector<int32_t> off((size_t)a.R);
         for (int r = 0, o = 0, b = 0; r < a.R; ++r) {
             if (r / a.NS != b) { o += a.winlen[b]; ++b; }
             off[(size_t)r] = o;
         }
-        if ((rc = alloc_copy(h, h->d_bt_win, h->want_bt_win.data(), h->want_bt_win.size()))) return rc;
+        if ((rc = alloc_copy(h, h->d_bt_win, h->req.bt_win.data(), h->req.bt_win.size()))) return rc;
         if ((rc = alloc_copy(h, h->d_bt_off, off.data(), off.size()))) return rc;
         if ((rc = ensure(h, h->d_bt, (size_t)a.R * (size_t)h->npts_pad * sizeof(double)))) return rc;
     }
-    if (h->ed) {                     // the element delays: every row's max_shift and the three grids
+    if (h->req.ed) {                     // the element delays: every row's max_shift and the three grids
         const size_t vals = (size_t)a.R * a.vector_len * (size_t)a.E;
         std::vector<int32_t> kb((size_t)a.R);
-        for (int r = 0; r < a.R; ++r) kb[(size_t)r] = h->want_ed_K[(size_t)(r / a.NS)];
+        for (int r = 0; r < a.R; ++r) kb[(size_t)r] = h->req.ed_K[(size_t)(r / a.NS)];
         if ((rc = alloc_copy(h, h->d_ed_K, kb.data(), kb.size()))) return rc;
         if ((rc = ensure(h, h->d_ed_fp, 2 * vals * sizeof(double)))) return rc;
         if ((rc = ensure(h, h->d_ed_shift, vals * sizeof(int32_t)))) return rc;
     }
-    if (h->capon_n > 0) {            // the Capon spectra: the band tables and the result buffers, likewise
+    if (h->derived.capon_n > 0) {            // the Capon spectra: the band tables and the result buffers, likewise
         const size_t cells = (size_t)a.R * a.vector_len;
-        const int E = a.E, G = h->capon_n, nb = a.nbands;
+        const int E = a.E, G = h->derived.capon_n, nb = a.nbands;
         int maxls = 1;
         h->h_capon_par.resize((size_t)nb * 3);
         for (int b = 0; b < nb; ++b) {
-            const int ls = h->capon.ls[b], hs = h->capon.hs[b];
+            const int ls = h->req.capon.ls[b], hs = h->req.capon.hs[b];
             h->h_capon_par[3 * b] = ls;
             h->h_capon_par[3 * b + 1] = hs;
             h->h_capon_par[3 * b + 2] = 1 + (a.winlen[b] - ls) / hs;
             if (ls > maxls) maxls = ls;
         }
-        h->capon_maxls = maxls;
+        h->derived.capon_maxls = maxls;
         h->h_capon_coef.resize((size_t)nb * maxls * 2);
         h->h_capon_steer.resize((size_t)nb * E * G * 2);
-        nbls_capon_tables_of(h->est[0].h_xij.data(), E, h->fs, h->capon.grid.data(), G, h->capon.freq.data(), h->capon.ls.data(),
+        nbls_capon_tables_of(h->est[0].h_xij.data(), E, h->fs, h->req.capon.grid.data(), G, h->req.capon.freq.data(), h->req.capon.ls.data(),
                              nb, maxls, h->h_capon_coef.data(), h->h_capon_steer.data());
         if ((rc = alloc_copy(h, h->d_capon_par, h->h_capon_par.data(), h->h_capon_par.size()))) return rc;
         if ((rc = alloc_copy(h, h->d_capon_coef, h->h_capon_coef.data(), h->h_capon_coef.size()))) return rc;
         if ((rc = alloc_copy(h, h->d_capon_steer, h->h_capon_steer.data(), h->h_capon_steer.size()))) return rc;
         if ((rc = ensure(h, h->d_capon_index, 2 * cells * sizeof(int32_t)))) return rc;
         if ((rc = ensure(h, h->d_capon_power, 2 * cells * sizeof(double)))) return rc;
-        if (h->capon_maps && (rc = ensure(h, h->d_capon_map, 2 * cells * (size_t)G * sizeof(double)))) return rc;
-        if ((h->capon_csdm || h->clean.iterations > 0 || h->music.sources >= 0) && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
-        if (h->music.sources >= 0) {     // the MUSIC request: it reads R from d_capon_csdm whether or not the plan returns it
+        if (h->req.capon_maps() && (rc = ensure(h, h->d_capon_map, 2 * cells * (size_t)G * sizeof(double)))) return rc;
+        if ((h->req.capon_csdm() || h->req.clean.iterations > 0 || h->req.music.sources >= 0) && (rc = ensure(h, h->d_capon_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+        if (h->req.music.sources >= 0) {     // the MUSIC request: it reads R from d_capon_csdm whether or not the plan returns it
             if ((rc = ensure(h, h->d_music_eig, cells * (size_t)E * sizeof(double)))) return rc;
             if ((rc = ensure(h, h->d_music_int, 3 * cells * sizeof(int32_t)))) return rc;
             if ((rc = ensure(h, h->d_music_power, cells * sizeof(double)))) return rc;
-            if ((h->music.flags & NBLS_MUSIC_MAP) && (rc = ensure(h, h->d_music_map, cells * (size_t)G * sizeof(double)))) return rc;
-            if ((h->music.flags & NBLS_MUSIC_VECTORS) && (rc = ensure(h, h->d_music_vec, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
-            if (h->music.flags & NBLS_MUSIC_PEAKS) {     // K of the plan's peak request; the slabs where the plan keeps no MUSIC map
-                const size_t K = (size_t)h->capon_peaks;
+            if ((h->req.music.flags & NBLS_MUSIC_MAP) && (rc = ensure(h, h->d_music_map, cells * (size_t)G * sizeof(double)))) return rc;
+            if ((h->req.music.flags & NBLS_MUSIC_VECTORS) && (rc = ensure(h, h->d_music_vec, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+            if (h->req.music.flags & NBLS_MUSIC_PEAKS) {     // K of the plan's peak request; the slabs where the plan keeps no MUSIC map
+                const size_t K = (size_t)h->req.peaks.k;
                 if ((rc = ensure(h, h->d_music_peak_count, cells * sizeof(int32_t)))) return rc;
                 if ((rc = ensure(h, h->d_music_peak_index, cells * K * sizeof(int32_t)))) return rc;
                 if ((rc = ensure(h, h->d_music_peak_power, cells * K * sizeof(double)))) return rc;
                 if ((rc = ensure(h, h->d_music_peak_offset, cells * K * 2 * sizeof(double)))) return rc;
-                if (!(h->music.flags & NBLS_MUSIC_MAP)) {
-                    const size_t slabs = std::min<size_t>((size_t)h->capon_peak_slabs, std::max<size_t>((size_t)h->nunits, 1));
+                if (!(h->req.music.flags & NBLS_MUSIC_MAP)) {
+                    const size_t slabs = std::min<size_t>((size_t)h->derived.peak_slabs, std::max<size_t>((size_t)h->nunits, 1));
                     if ((rc = ensure(h, h->d_music_slab, slabs * (size_t)G * sizeof(double)))) return rc;
                 }
             }
         }
-        if (h->clean.iterations > 0) {   // the CLEAN-SC request: it reads R from d_capon_csdm whether or not the plan returns it
-            const size_t I = (size_t)h->clean.iterations;
+        if (h->req.clean.iterations > 0) {   // the CLEAN-SC request: it reads R from d_capon_csdm whether or not the plan returns it
+            const size_t I = (size_t)h->req.clean.iterations;
             if ((rc = ensure(h, h->d_clean_count, cells * sizeof(int32_t)))) return rc;
             if ((rc = ensure(h, h->d_clean_index, cells * I * sizeof(int32_t)))) return rc;
             if ((rc = ensure(h, h->d_clean_power, cells * I * sizeof(double)))) return rc;
             if ((rc = ensure(h, h->d_clean_tr, 2 * cells * sizeof(double)))) return rc;
-            if ((h->clean.flags & NBLS_CLEAN_RESIDUAL) && (rc = ensure(h, h->d_clean_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
+            if ((h->req.clean.flags & NBLS_CLEAN_RESIDUAL) && (rc = ensure(h, h->d_clean_csdm, cells * (size_t)E * E * 2 * sizeof(double)))) return rc;
         }
-        if (h->capon_peaks > 0) {    // the peak request: its neighbour table, the four results and, on the HBM route of a plan without the maps, the slabs
-            const size_t K = (size_t)h->capon_peaks;
-            if ((rc = alloc_copy(h, h->d_capon_nbr, h->want_capon_peaks.nbr.data(), h->want_capon_peaks.nbr.size()))) return rc;
+        if (h->req.peaks.k > 0) {    // the peak request: its neighbour table, the four results and, on the HBM route of a plan without the maps, the slabs
+            const size_t K = (size_t)h->req.peaks.k;
+            if ((rc = alloc_copy(h, h->d_capon_nbr, h->req.peaks.nbr.data(), h->req.peaks.nbr.size()))) return rc;
             if ((rc = ensure(h, h->d_capon_peak_count, 2 * cells * sizeof(int32_t)))) return rc;
             if ((rc = ensure(h, h->d_capon_peak_index, 2 * cells * K * sizeof(int32_t)))) return rc;
             if ((rc = ensure(h, h->d_capon_peak_power, 2 * cells * K * sizeof(double)))) return rc;
             if ((rc = ensure(h, h->d_capon_peak_offset, 2 * cells * K * 2 * sizeof(double)))) return rc;
-            if (h->capon_peak_route == 2 && !h->capon_maps) {
-                const size_t slabs = std::min<size_t>((size_t)h->capon_peak_slabs, std::max<size_t>((size_t)h->nunits, 1));
+            if (h->derived.peak_route == 2 && !h->req.capon_maps()) {
+                const size_t slabs = std::min<size_t>((size_t)h->derived.peak_slabs, std::max<size_t>((size_t)h->nunits, 1));
                 if ((rc = ensure(h, h->d_capon_peak_slab, slabs * 2 * (size_t)G * sizeof(double)))) return rc;
             }
         }
@@ -1476,16 +1460,8 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if (h->prof) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     h->solve_done = false;
     h->last_stage_mask = stage_mask;
-    if (stage_mask & 4) h->beam_valid = true;            // (a pass without the solve stage leaves the beam grids as they are)
-    if ((stage_mask & 4) && h->closure) h->closure_valid = true;      // (likewise the closure grids)
-    if ((stage_mask & 4) && h->kept_q > 0) h->kept_valid = true;     // (... and the kept elements)
-    if ((stage_mask & 4) && h->bt) h->bt_valid = true;               // (... and the beam trace)
-    if ((stage_mask & 4) && h->ed) h->ed_valid = true;               // (... and the element delays)
-    if (stage_mask & 4) h->solve_ran = true;
-    // (... and the grids of the slowness-grid search; a plan with a lag seed writes them in the correlation stage)
-    if (stage_mask & (h->seed.empty() ? 4 : 2)) h->grid_valid = true;
-    if ((stage_mask & 4) && h->capon_n > 0) h->capon_valid = true;    // (... and the Capon spectra)
-    if (stage_mask & 2) h->frac_valid = true;            // (... one without the correlation stage the lag fractions)
+    if (stage_mask & 4) h->solve_ran = true;             // (a pass without a stage leaves the opt-in results it writes as they are)
+    if (stage_mask & 2) h->xcorr_ran = true;
     // per-batch solves: behind each unit batch of the correlation stage (streamed results: a batch's rows are complete
     // while later batches are still being correlated), on the second stream with option "overlap"
     h->fuse_solve = ((stage_mask & 6) == 6) && h->xcorr_impl == 3 && (h->opt.overlap > 0 || h->stream_results);
@@ -1512,7 +1488,7 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     if ((stage_mask & 4) && !h->solve_done) HIPCHK(h, nbls_launch_solve(h));
     // the beam trace of a plan that asked for one (nbls_set_beam_trace): one launch behind the pass's last solve — per-batch
     // solves on the second stream have been joined into this one (nbls_xcorr_screen_finish) — and ahead of the closing event
-    if ((stage_mask & 4) && h->bt) HIPCHK(h, nbls_launch_beam_trace(h, h->stream));
+    if ((stage_mask & 4) && h->req.bt) HIPCHK(h, nbls_launch_beam_trace(h, h->stream));
     if (h->prof) { HIPCHK(h, hipEventRecord(h->ev[3], h->stream)); h->ev_valid = true; }
     // streamed results of a pass that was not cut into batches (general correlators, stage subsets, no units): ONE batch
     if (h->stream_results && h->rbatches.empty()) HIPCHK(h, nbls_queue_result_batch(h, 0, h->nunits, h->stream));
@@ -1709,19 +1685,14 @@ int nbls_est_fetch_uncertainty(nbls_handle* h, int32_t est, double* vel_uncert, 
     if (!s.want_unc || !s.d_unc) return fail(h, NBLS_ERR_STATE, "nbls_fetch_uncertainty: nbls_set_uncertainty (or the estimator's eig6) before nbls_plan");
     { const int rc = finish_pass(h); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    double* outs[2] = {vel_uncert, baz_uncert};
-    for (int g = 0; g < 2; ++g) {
-        if (!outs[g]) continue;
-        if (!(h->last_stage_mask & 4)) { memset(outs[g], 0, cells * sizeof(double)); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], s.d_unc + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
-        zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
-    }
-    return NBLS_OK;
+    const bool ran = (h->last_stage_mask & 4) != 0;          // like the grids of nbls_fetch: those of the LAST pass, or zeros
+    if (int rc = fetch_plane(h, ran, vel_uncert, s.d_unc.p, sizeof(double))) return rc;
+    return fetch_plane(h, ran, baz_uncert, s.d_unc.p + cells, sizeof(double));
 }
 
 int nbls_set_beam(nbls_handle* h, int32_t on) {
     if (!h) return NBLS_ERR_ARG;
-    h->want_beam = on != 0;                  // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.beam = on != 0;                  // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
 }
 
@@ -1732,24 +1703,17 @@ int nbls_est_fetch_beam(nbls_handle* h, int32_t est, double* beam_power, double*
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam: no plan");
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_beam: no such estimator");
     const nbls_estimator& s = h->est[est];
-    if (!h->beam || !s.d_beam) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam: nbls_set_beam before nbls_plan");
-    { const int rc = finish_pass(h); if (rc) return rc; }
+    if (!h->req.beam || !s.d_beam) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam: nbls_set_beam before nbls_plan");
+    int rc;
+    if ((rc = finish_pass(h))) return rc;
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    double* outs[2] = {beam_power, fstat};
-    for (int g = 0; g < 2; ++g) {
-        if (!outs[g]) continue;
-        // the grids are written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass
-        // without it leaves them as they are
-        if (!h->beam_valid) { memset(outs[g], 0, cells * sizeof(double)); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], s.d_beam + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
-        zero_uncomputed(h, outs[g], sizeof(double));      // like the grids
-    }
-    return NBLS_OK;
+    if ((rc = fetch_plane(h, h->solve_ran, beam_power, s.d_beam.p, sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, fstat, s.d_beam.p + cells, sizeof(double));
 }
 
 int nbls_set_closure(nbls_handle* h, int32_t on) {
     if (!h) return NBLS_ERR_ARG;
-    h->want_closure = on != 0;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.closure = on != 0;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
 }
 
@@ -1762,110 +1726,85 @@ int nbls_est_fetch_closure(nbls_handle* h, int32_t est, double* consistency, dou
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_closure: no plan");
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_closure: no such estimator");
     const nbls_estimator& s = h->est[est];
-    if (!h->closure || !s.d_closure || !s.d_closure_el) return fail(h, NBLS_ERR_STATE, "nbls_fetch_closure: nbls_set_closure before nbls_plan");
-    { const int rc = finish_pass(h); if (rc) return rc; }
+    if (!h->req.closure || !s.d_closure || !s.d_closure_el) return fail(h, NBLS_ERR_STATE, "nbls_fetch_closure: nbls_set_closure before nbls_plan");
+    int rc;
+    if ((rc = finish_pass(h))) return rc;
     const size_t cells = (size_t)h->nbands * h->vector_len;
     const size_t N = s.kept.empty() ? (size_t)h->nelem : s.kept.size();
-    // the grids are written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass
-    // without it leaves them as they are
-    double* outs[3] = {consistency, closure_max, element_consistency};
-    const double* srcs[3] = {s.d_closure.p, s.d_closure.p + cells, s.d_closure_el.p};
-    for (int g = 0; g < 3; ++g) {
-        if (!outs[g]) continue;
-        const size_t row = (g == 2 ? N : 1) * sizeof(double);
-        if (!h->closure_valid) { memset(outs[g], 0, cells * row); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * row, hipMemcpyDeviceToHost));
-        zero_uncomputed(h, outs[g], row);                 // like the grids
-    }
-    return NBLS_OK;
+    if ((rc = fetch_plane(h, h->solve_ran, consistency, s.d_closure.p, sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, closure_max, s.d_closure.p + cells, sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, element_consistency, s.d_closure_el.p, N * sizeof(double));
 }
 
 int nbls_set_kept_elements(nbls_handle* h, int32_t min_pairs, int32_t flags) {
     if (!h) return NBLS_ERR_ARG;
     if (min_pairs < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_kept_elements: min_pairs must not be negative");
     if (flags & ~(NBLS_KEPT_BEAM | NBLS_KEPT_CAPON)) return fail(h, NBLS_ERR_ARG, "nbls_set_kept_elements: unknown flags");
-    h->want_kept_q = min_pairs;              // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
-    h->want_kept_flags = min_pairs > 0 ? flags : 0;
+    h->want.kept_q = min_pairs;              // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.kept_flags = min_pairs > 0 ? flags : 0;
     return NBLS_OK;
 }
 
 int nbls_fetch_kept_elements(nbls_handle* h, uint32_t* dropped_mask, int32_t* kept_count) {
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_kept_elements: no plan");
-    if (h->kept_q < 1 || !h->d_kept_mask || !h->d_kept_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_kept_elements: nbls_set_kept_elements before nbls_plan");
-    { const int rc = finish_pass(h); if (rc) return rc; }
-    const size_t cells = (size_t)h->nbands * h->vector_len;
-    // written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass without it leaves them
-    // as they are
-    void* outs[2] = {dropped_mask, kept_count};
-    const void* srcs[2] = {h->d_kept_mask.p, h->d_kept_count.p};
-    for (int g = 0; g < 2; ++g) {
-        if (!outs[g]) continue;
-        if (!h->kept_valid) { memset(outs[g], 0, cells * 4); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * 4, hipMemcpyDeviceToHost));
-        zero_uncomputed(h, outs[g], 4);                   // like the grids
-    }
-    return NBLS_OK;
+    if (h->req.kept_q < 1 || !h->d_kept_mask || !h->d_kept_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_kept_elements: nbls_set_kept_elements before nbls_plan");
+    int rc;
+    if ((rc = finish_pass(h))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, dropped_mask, h->d_kept_mask.p, sizeof(uint32_t)))) return rc;
+    return fetch_plane(h, h->solve_ran, kept_count, h->d_kept_count.p, sizeof(int32_t));
 }
 
 int nbls_set_beam_trace(nbls_handle* h, const double* window, int64_t nwindow, double mdccm_min, int32_t flags) {
     if (!h) return NBLS_ERR_ARG;
-    if (!window) { h->want_bt = false; h->want_bt_win.clear(); h->want_bt_flags = 0; return NBLS_OK; }    // off: the next plan forms no trace
+    if (!window) { h->want.bt = false; h->want.bt_win.clear(); h->want.bt_flags = 0; return NBLS_OK; }    // off: the next plan forms no trace
     if (nwindow < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_trace: nwindow must not be negative");
     if (flags & ~NBLS_BEAM_TRACE_KEPT) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_trace: unknown flags");
-    h->want_bt = true;                       // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
-    h->want_bt_win.assign(window, window + nwindow);
-    h->want_bt_min = mdccm_min;
-    h->want_bt_flags = flags;
+    h->want.bt = true;                       // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.bt_win.assign(window, window + nwindow);
+    h->want.bt_min = mdccm_min;
+    h->want.bt_flags = flags;
     return NBLS_OK;
 }
 
 int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out) {
     if (!h || !out) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_trace: no plan");
-    if (!h->bt || !h->d_bt) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_trace: nbls_set_beam_trace before nbls_plan");
+    if (!h->req.bt || !h->d_bt) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_trace: nbls_set_beam_trace before nbls_plan");
     if (row < 0 || row >= h->nbands) return fail(h, NBLS_ERR_ARG, "nbls_fetch_beam_trace: row out of range");
     { const int rc = finish_pass(h); if (rc) return rc; }
     // written behind the solve stage alone: zeros until a pass of this plan has run it, and a later pass without it leaves
     // the trace as it is
-    if (!h->bt_valid) { memset(out, 0, (size_t)h->npts * sizeof(double)); return NBLS_OK; }
+    if (!h->solve_ran) { memset(out, 0, (size_t)h->npts * sizeof(double)); return NBLS_OK; }
     HIPCHK(h, copy_sync(h, out, h->d_bt + (size_t)row * h->npts_pad, (size_t)h->npts * sizeof(double), hipMemcpyDeviceToHost));
     return NBLS_OK;
 }
 
 int nbls_set_element_delays(nbls_handle* h, const int32_t* max_shift, int32_t nbands, int32_t flags) {
     if (!h) return NBLS_ERR_ARG;
-    if (!max_shift) { h->want_ed = false; h->want_ed_K.clear(); h->want_ed_flags = 0; return NBLS_OK; }   // off: the next plan measures none
+    if (!max_shift) { h->want.ed = false; h->want.ed_K.clear(); h->want.ed_flags = 0; return NBLS_OK; }   // off: the next plan measures none
     if (nbands < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_element_delays: nbands must be at least 1");
     if (flags & ~NBLS_ELEMENT_DELAY_KEPT) return fail(h, NBLS_ERR_ARG, "nbls_set_element_delays: unknown flags");
     for (int b = 0; b < nbands; ++b)
         if (max_shift[b] < 0 || max_shift[b] > NBLS_ELEMENT_DELAY_MAX_SHIFT)
             return fail(h, NBLS_ERR_ARG, "nbls_set_element_delays: max_shift of band " + std::to_string(b) + " is " + std::to_string(max_shift[b]) +
                                              ", not in 0.." + std::to_string(NBLS_ELEMENT_DELAY_MAX_SHIFT));
-    h->want_ed = true;                       // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
-    h->want_ed_K.assign(max_shift, max_shift + nbands);
-    h->want_ed_flags = flags;
+    h->want.ed = true;                       // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.ed_K.assign(max_shift, max_shift + nbands);
+    h->want.ed_flags = flags;
     return NBLS_OK;
 }
 
 int nbls_fetch_element_delays(nbls_handle* h, double* delay, double* cc, int32_t* shift) {
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_element_delays: no plan");
-    if (!h->ed || !h->d_ed_fp || !h->d_ed_shift) return fail(h, NBLS_ERR_STATE, "nbls_fetch_element_delays: nbls_set_element_delays before nbls_plan");
-    { const int rc = finish_pass(h); if (rc) return rc; }
+    if (!h->req.ed || !h->d_ed_fp || !h->d_ed_shift) return fail(h, NBLS_ERR_STATE, "nbls_fetch_element_delays: nbls_set_element_delays before nbls_plan");
+    int rc;
+    if ((rc = finish_pass(h))) return rc;
     const size_t cells = (size_t)h->nbands * h->vector_len, N = (size_t)h->nelem;
-    // written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass without it leaves them
-    // as they are
-    void* outs[3] = {delay, cc, shift};
-    const void* srcs[3] = {h->d_ed_fp.p, h->d_ed_fp.p + cells * N, h->d_ed_shift.p};
-    for (int g = 0; g < 3; ++g) {
-        if (!outs[g]) continue;
-        const size_t row = N * (g == 2 ? sizeof(int32_t) : sizeof(double));
-        if (!h->ed_valid) { memset(outs[g], 0, cells * row); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], srcs[g], cells * row, hipMemcpyDeviceToHost));
-        zero_uncomputed(h, outs[g], row);                 // like the grids
-    }
-    return NBLS_OK;
+    if ((rc = fetch_plane(h, h->solve_ran, delay, h->d_ed_fp.p, N * sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, cc, h->d_ed_fp.p + cells * N, N * sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, shift, h->d_ed_shift.p, N * sizeof(int32_t));
 }
 
 int nbls_element_delay_lds_bytes(int32_t nelem, int32_t W, int32_t max_shift) {
@@ -1875,12 +1814,12 @@ int nbls_element_delay_lds_bytes(int32_t nelem, int32_t W, int32_t max_shift) {
 
 int nbls_set_beam_grid(nbls_handle* h, const double* grid, int32_t G, int32_t want_map) {
     if (!h) return NBLS_ERR_ARG;
-    if (!grid) { h->want_grid.clear(); h->want_grid_map = false; return NBLS_OK; }      // off: the next plan does not search
+    if (!grid) { h->want.grid.clear(); h->want.grid_keep_map = false; return NBLS_OK; }      // off: the next plan does not search
     if (G < 1 || G > NBLS_BEAM_GRID_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_grid: G must be 1.." + std::to_string(NBLS_BEAM_GRID_MAX));
     for (int64_t k = 0; k < 2 * (int64_t)G; ++k)                 // everything is checked before the handle changes
         if (!(fabs(grid[k]) < INFINITY)) return fail(h, NBLS_ERR_ARG, "nbls_set_beam_grid: slowness vector " + std::to_string(k / 2) + " is not finite");
-    h->want_grid.assign(grid, grid + 2 * (size_t)G);             // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
-    h->want_grid_map = want_map != 0;
+    h->want.grid.assign(grid, grid + 2 * (size_t)G);             // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.grid_keep_map = want_map != 0;
     return NBLS_OK;
 }
 
@@ -1892,8 +1831,8 @@ int nbls_beam_grid_lds_bytes(int32_t nelem, int32_t W, int32_t halo) {
 // what the three grid fetches share: the plan asked, and the pass is through
 static int grid_fetch_ready(nbls_handle* h, const char* who, bool map) {
     if (!h->planned) return fail(h, NBLS_ERR_STATE, std::string(who) + ": no plan");
-    if (h->grid_n < 1 || !h->d_grid_index) return fail(h, NBLS_ERR_STATE, std::string(who) + ": nbls_set_beam_grid before nbls_plan");
-    if (map && (!h->grid_map || !h->d_grid_map)) return fail(h, NBLS_ERR_STATE, std::string(who) + ": the plan did not ask for the map (nbls_set_beam_grid, want_map)");
+    if (h->derived.grid_n < 1 || !h->d_grid_index) return fail(h, NBLS_ERR_STATE, std::string(who) + ": nbls_set_beam_grid before nbls_plan");
+    if (map && (!h->req.grid_map() || !h->d_grid_map)) return fail(h, NBLS_ERR_STATE, std::string(who) + ": the plan did not ask for the map (nbls_set_beam_grid, want_map)");
     return finish_pass(h);
 }
 
@@ -1901,47 +1840,30 @@ int nbls_fetch_beam_grid(nbls_handle* h, int32_t* index, double* fstat, double* 
     if (!h) return NBLS_ERR_ARG;
     { const int rc = grid_fetch_ready(h, "nbls_fetch_beam_grid", false); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    // the grids are written by the solve stage alone: zeros until a pass of this plan has run it, and a later pass
-    // without it leaves them as they are
-    if (index) {
-        if (!h->grid_valid) memset(index, 0, cells * sizeof(int32_t));
-        else {
-            HIPCHK(h, copy_sync(h, index, h->d_grid_index, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-            zero_uncomputed(h, index, sizeof(int32_t));
-        }
-    }
-    double* outs[2] = {fstat, power};
-    for (int g = 0; g < 2; ++g) {
-        if (!outs[g]) continue;
-        if (!h->grid_valid) { memset(outs[g], 0, cells * sizeof(double)); continue; }
-        HIPCHK(h, copy_sync(h, outs[g], h->d_grid_fp + g * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
-        zero_uncomputed(h, outs[g], sizeof(double));
-    }
-    return NBLS_OK;
+    int rc;
+    if ((rc = fetch_plane(h, h->grid_ran(), index, h->d_grid_index.p, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->grid_ran(), fstat, h->d_grid_fp.p, sizeof(double)))) return rc;
+    return fetch_plane(h, h->grid_ran(), power, h->d_grid_fp.p + cells, sizeof(double));
 }
 
 int nbls_fetch_beam_grid_map(nbls_handle* h, double* map) {
     if (!h || !map) return NBLS_ERR_ARG;
     { const int rc = grid_fetch_ready(h, "nbls_fetch_beam_grid_map", true); if (rc) return rc; }
-    const size_t cells = (size_t)h->nbands * h->vector_len, row = (size_t)h->grid_n * sizeof(double);
-    if (!h->grid_valid) { memset(map, 0, cells * row); return NBLS_OK; }
-    HIPCHK(h, copy_sync(h, map, h->d_grid_map, cells * row, hipMemcpyDeviceToHost));
-    zero_uncomputed(h, map, row);
-    return NBLS_OK;
+    return fetch_plane(h, h->grid_ran(), map, h->d_grid_map.p, (size_t)h->derived.grid_n * sizeof(double));
 }
 
 int nbls_fetch_beam_grid_delays(nbls_handle* h, int32_t* d) {
     if (!h || !d) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: no plan");
-    if (h->grid_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: nbls_set_beam_grid before nbls_plan");
-    memcpy(d, h->h_grid_delay.data(), h->h_grid_delay.size() * sizeof(int32_t));   // the plan's own table (the device holds a copy)
+    if (h->derived.grid_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_delays: nbls_set_beam_grid before nbls_plan");
+    memcpy(d, h->derived.grid_delay.data(), h->derived.grid_delay.size() * sizeof(int32_t));   // the plan's own table (the device holds a copy)
     return NBLS_OK;
 }
 
 int nbls_set_capon(nbls_handle* h, const double* grid, int32_t G, const double* freq, const int32_t* snap_len,
                    const int32_t* snap_hop, int32_t nbands, double loading, int32_t flags) {
     if (!h) return NBLS_ERR_ARG;
-    if (!grid || G == 0) { h->want_capon = nbls_handle::capon_request(); return NBLS_OK; }      // off: the next plan computes no spectra
+    if (!grid || G == 0) { h->want.capon = nbls_requests::capon_request(); return NBLS_OK; }      // off: the next plan computes no spectra
     if (G < 1 || G > NBLS_CAPON_GRID_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: G must be 1.." + std::to_string(NBLS_CAPON_GRID_MAX));
     if (nbands < 1 || !freq || !snap_len || !snap_hop) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: at least one band with its frequency, snapshot length and hop");
     for (int64_t k = 0; k < 2 * (int64_t)G; ++k)                 // everything is checked before the handle changes
@@ -1951,7 +1873,7 @@ int nbls_set_capon(nbls_handle* h, const double* grid, int32_t G, const double* 
         if (snap_len[b] < 1 || snap_hop[b] < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: the snapshot length and hop of band " + std::to_string(b) + " must be at least 1");
     }
     if (!(loading >= 0.0 && loading < INFINITY)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon: the loading must be finite and not negative");
-    nbls_handle::capon_request& c = h->want_capon;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    nbls_requests::capon_request& c = h->want.capon;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     c.grid.assign(grid, grid + 2 * (size_t)G);
     c.freq.assign(freq, freq + nbands);
     c.ls.assign(snap_len, snap_len + nbands);
@@ -1964,18 +1886,8 @@ int nbls_set_capon(nbls_handle* h, const double* grid, int32_t G, const double* 
 // what the Capon fetches share: the plan asked, and the pass is through
 static int capon_fetch_ready(nbls_handle* h, const char* who) {
     if (!h->planned) return fail(h, NBLS_ERR_STATE, std::string(who) + ": no plan");
-    if (h->capon_n < 1 || !h->d_capon_index) return fail(h, NBLS_ERR_STATE, std::string(who) + ": nbls_set_capon before nbls_plan");
+    if (h->derived.capon_n < 1 || !h->d_capon_index) return fail(h, NBLS_ERR_STATE, std::string(who) + ": nbls_set_capon before nbls_plan");
     return 0;
-}
-
-// one result plane [B][VL] rows of row_bytes: zeros until a pass has run the solve stage, and where no window was computed
-static int capon_fetch_plane(nbls_handle* h, void* out, const void* src, size_t row_bytes) {
-    const size_t cells = (size_t)h->nbands * h->vector_len;
-    if (!out) return NBLS_OK;
-    if (!h->capon_valid) { memset(out, 0, cells * row_bytes); return NBLS_OK; }
-    HIPCHK(h, copy_sync(h, out, src, cells * row_bytes, hipMemcpyDeviceToHost));
-    zero_uncomputed(h, out, row_bytes);
-    return NBLS_OK;
 }
 
 int nbls_fetch_capon(nbls_handle* h, int32_t* capon_index, double* capon_power, int32_t* bartlett_index, double* bartlett_power) {
@@ -1983,15 +1895,15 @@ int nbls_fetch_capon(nbls_handle* h, int32_t* capon_index, double* capon_power, 
     int rc;
     if ((rc = capon_fetch_ready(h, "nbls_fetch_capon")) || (rc = finish_pass(h))) return rc;
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    if ((rc = capon_fetch_plane(h, capon_index, h->d_capon_index.p, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, bartlett_index, h->d_capon_index.p + cells, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, capon_power, h->d_capon_power.p, sizeof(double)))) return rc;
-    return capon_fetch_plane(h, bartlett_power, h->d_capon_power.p + cells, sizeof(double));
+    if ((rc = fetch_plane(h, h->solve_ran, capon_index, h->d_capon_index.p, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, bartlett_index, h->d_capon_index.p + cells, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, capon_power, h->d_capon_power.p, sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, bartlett_power, h->d_capon_power.p + cells, sizeof(double));
 }
 
 int nbls_set_capon_peaks(nbls_handle* h, const int32_t* cell, int32_t G, int32_t K, double floor) {
     if (!h) return NBLS_ERR_ARG;
-    if (!cell || K == 0) { h->want_capon_peaks = nbls_handle::capon_peak_request(); return NBLS_OK; }   // off: the next plan picks no peaks
+    if (!cell || K == 0) { h->want.peaks = nbls_requests::capon_peak_request(); return NBLS_OK; }   // off: the next plan picks no peaks
     if (K < 1 || K > NBLS_CAPON_PEAKS_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: K must be 1.." + std::to_string(NBLS_CAPON_PEAKS_MAX));
     if (G < 1 || G > NBLS_CAPON_GRID_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: G must be 1.." + std::to_string(NBLS_CAPON_GRID_MAX));
     if (!(floor >= 0.0 && floor <= 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: the floor must lie in [0, 1]");
@@ -2005,7 +1917,7 @@ int nbls_set_capon_peaks(nbls_handle* h, const int32_t* cell, int32_t G, int32_t
     std::sort(key.begin(), key.end());
     if (std::adjacent_find(key.begin(), key.end()) != key.end())
         return fail(h, NBLS_ERR_ARG, "nbls_set_capon_peaks: two points share one lattice cell");
-    nbls_handle::capon_peak_request& r = h->want_capon_peaks;    // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    nbls_requests::capon_peak_request& r = h->want.peaks;    // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     r.nbr.resize((size_t)8 * G);
     nbls_capon_neighbours_of(cell, G, r.nbr.data());
     r.k = K;
@@ -2018,43 +1930,43 @@ int nbls_fetch_capon_peaks(nbls_handle* h, int32_t which, int32_t* count, int32_
     int rc;
     if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_peaks"))) return rc;
     if (which < 0 || which > 1) return fail(h, NBLS_ERR_ARG, "nbls_fetch_capon_peaks: which is 0 (Capon) or 1 (Bartlett)");
-    if (h->capon_peaks < 1 || !h->d_capon_peak_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_peaks: the plan did not ask for the peaks (nbls_set_capon_peaks before nbls_plan)");
+    if (h->req.peaks.k < 1 || !h->d_capon_peak_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_peaks: the plan did not ask for the peaks (nbls_set_capon_peaks before nbls_plan)");
     if ((rc = finish_pass(h))) return rc;
-    const size_t cells = (size_t)h->nbands * h->vector_len, K = (size_t)h->capon_peaks, w = (size_t)which;
-    if ((rc = capon_fetch_plane(h, count, h->d_capon_peak_count.p + w * cells, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, index, h->d_capon_peak_index.p + w * cells * K, K * sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, power, h->d_capon_peak_power.p + w * cells * K, K * sizeof(double)))) return rc;
-    return capon_fetch_plane(h, offset, h->d_capon_peak_offset.p + w * cells * K * 2, K * 2 * sizeof(double));
+    const size_t cells = (size_t)h->nbands * h->vector_len, K = (size_t)h->req.peaks.k, w = (size_t)which;
+    if ((rc = fetch_plane(h, h->solve_ran, count, h->d_capon_peak_count.p + w * cells, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, index, h->d_capon_peak_index.p + w * cells * K, K * sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, power, h->d_capon_peak_power.p + w * cells * K, K * sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, offset, h->d_capon_peak_offset.p + w * cells * K * 2, K * 2 * sizeof(double));
 }
 
 int nbls_fetch_capon_maps(nbls_handle* h, double* capon_map, double* bartlett_map) {
     if (!h) return NBLS_ERR_ARG;
     int rc;
     if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_maps"))) return rc;
-    if (!h->capon_maps || !h->d_capon_map) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_maps: the plan did not ask for the maps (nbls_set_capon, NBLS_CAPON_MAPS)");
+    if (!h->req.capon_maps() || !h->d_capon_map) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_maps: the plan did not ask for the maps (nbls_set_capon, NBLS_CAPON_MAPS)");
     if ((rc = finish_pass(h))) return rc;
-    const size_t cells = (size_t)h->nbands * h->vector_len, row = (size_t)h->capon_n * sizeof(double);
-    if ((rc = capon_fetch_plane(h, capon_map, h->d_capon_map.p, row))) return rc;
-    return capon_fetch_plane(h, bartlett_map, h->d_capon_map.p + cells * h->capon_n, row);
+    const size_t cells = (size_t)h->nbands * h->vector_len, row = (size_t)h->derived.capon_n * sizeof(double);
+    if ((rc = fetch_plane(h, h->solve_ran, capon_map, h->d_capon_map.p, row))) return rc;
+    return fetch_plane(h, h->solve_ran, bartlett_map, h->d_capon_map.p + cells * h->derived.capon_n, row);
 }
 
 int nbls_fetch_capon_csdm(nbls_handle* h, double* R) {
     if (!h || !R) return NBLS_ERR_ARG;
     int rc;
     if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_csdm"))) return rc;
-    if (!h->capon_csdm || !h->d_capon_csdm) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_csdm: the plan did not ask for the matrix (nbls_set_capon, NBLS_CAPON_CSDM)");
+    if (!h->req.capon_csdm() || !h->d_capon_csdm) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_csdm: the plan did not ask for the matrix (nbls_set_capon, NBLS_CAPON_CSDM)");
     if ((rc = finish_pass(h))) return rc;
-    return capon_fetch_plane(h, R, h->d_capon_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+    return fetch_plane(h, h->solve_ran, R, h->d_capon_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
 }
 
 int nbls_set_capon_clean(nbls_handle* h, int32_t iterations, double gain, double floor, int32_t flags) {
     if (!h) return NBLS_ERR_ARG;
-    if (iterations == 0) { h->want_clean = nbls_handle::capon_clean_request(); return NBLS_OK; }   // off: the next plan launches no capon_clean_kernel
+    if (iterations == 0) { h->want.clean = nbls_requests::capon_clean_request(); return NBLS_OK; }   // off: the next plan launches no capon_clean_kernel
     if (iterations < 1 || iterations > NBLS_CAPON_CLEAN_MAX) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: iterations must be 1.." + std::to_string(NBLS_CAPON_CLEAN_MAX));
     if (!(gain > 0.0 && gain <= 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: the gain must lie in (0, 1]");
     if (!(floor >= 0.0 && floor < 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: the floor must lie in [0, 1)");
     if (flags & ~NBLS_CLEAN_RESIDUAL) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_clean: unknown flags");
-    nbls_handle::capon_clean_request& r = h->want_clean;         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    nbls_requests::capon_clean_request& r = h->want.clean;         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     r.iterations = iterations;
     r.gain = gain;
     r.floor = floor;
@@ -2066,24 +1978,24 @@ int nbls_fetch_capon_clean(nbls_handle* h, int32_t* count, int32_t* index, doubl
     if (!h) return NBLS_ERR_ARG;
     int rc;
     if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_clean"))) return rc;
-    if (h->clean.iterations < 1 || !h->d_clean_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_clean: the plan did not ask for the components (nbls_set_capon_clean before nbls_plan)");
+    if (h->req.clean.iterations < 1 || !h->d_clean_count) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_clean: the plan did not ask for the components (nbls_set_capon_clean before nbls_plan)");
     if ((rc = finish_pass(h))) return rc;
-    const size_t cells = (size_t)h->nbands * h->vector_len, I = (size_t)h->clean.iterations;
-    if ((rc = capon_fetch_plane(h, count, h->d_clean_count.p, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, index, h->d_clean_index.p, I * sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, power, h->d_clean_power.p, I * sizeof(double)))) return rc;
-    if ((rc = capon_fetch_plane(h, total, h->d_clean_tr.p, sizeof(double)))) return rc;
-    return capon_fetch_plane(h, residual, h->d_clean_tr.p + cells, sizeof(double));
+    const size_t cells = (size_t)h->nbands * h->vector_len, I = (size_t)h->req.clean.iterations;
+    if ((rc = fetch_plane(h, h->solve_ran, count, h->d_clean_count.p, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, index, h->d_clean_index.p, I * sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, power, h->d_clean_power.p, I * sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, total, h->d_clean_tr.p, sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, residual, h->d_clean_tr.p + cells, sizeof(double));
 }
 
 int nbls_fetch_capon_clean_csdm(nbls_handle* h, double* R) {
     if (!h || !R) return NBLS_ERR_ARG;
     int rc;
     if ((rc = capon_fetch_ready(h, "nbls_fetch_capon_clean_csdm"))) return rc;
-    if (h->clean.iterations < 1 || !(h->clean.flags & NBLS_CLEAN_RESIDUAL) || !h->d_clean_csdm)
+    if (h->req.clean.iterations < 1 || !(h->req.clean.flags & NBLS_CLEAN_RESIDUAL) || !h->d_clean_csdm)
         return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_clean_csdm: the plan did not ask for the residual matrix (nbls_set_capon_clean, NBLS_CLEAN_RESIDUAL)");
     if ((rc = finish_pass(h))) return rc;
-    return capon_fetch_plane(h, R, h->d_clean_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+    return fetch_plane(h, h->solve_ran, R, h->d_clean_csdm.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
 }
 
 int nbls_capon_clean_lds_bytes(int32_t nelem) {
@@ -2093,12 +2005,12 @@ int nbls_capon_clean_lds_bytes(int32_t nelem) {
 
 int nbls_set_capon_music(nbls_handle* h, int32_t sources, double eig_floor, double peak_floor, int32_t flags) {
     if (!h) return NBLS_ERR_ARG;
-    if (sources == -1) { h->want_music = nbls_handle::capon_music_request(); return NBLS_OK; }   // off: the next plan launches no capon_music_kernel
+    if (sources == -1) { h->want.music = nbls_requests::capon_music_request(); return NBLS_OK; }   // off: the next plan launches no capon_music_kernel
     if (sources < 0 || sources > NBLS_CAPON_MAX_ELEMENTS - 1) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: sources must be -1 (off), 0 (by the floor) or 1.." + std::to_string(NBLS_CAPON_MAX_ELEMENTS - 1));
     if (sources == 0 && !(eig_floor > 0.0 && eig_floor < 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: the eigenvalue floor must lie in (0, 1)");
     if (!(peak_floor >= 0.0 && peak_floor < 1.0)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: the peak floor must lie in [0, 1)");
     if (flags & ~(NBLS_MUSIC_MAP | NBLS_MUSIC_VECTORS | NBLS_MUSIC_PEAKS)) return fail(h, NBLS_ERR_ARG, "nbls_set_capon_music: unknown flags");
-    nbls_handle::capon_music_request& r = h->want_music;         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    nbls_requests::capon_music_request& r = h->want.music;         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     r.sources = sources;
     r.eig_floor = sources == 0 ? eig_floor : 0.0;
     r.peak_floor = peak_floor;
@@ -2110,7 +2022,7 @@ int nbls_set_capon_music(nbls_handle* h, int32_t sources, double eig_floor, doub
 static int music_fetch_ready(nbls_handle* h, const char* who) {
     int rc;
     if ((rc = capon_fetch_ready(h, who))) return rc;
-    if (h->music.sources < 0 || !h->d_music_eig) return fail(h, NBLS_ERR_STATE, std::string(who) + ": the plan did not ask for the eigenvalues (nbls_set_capon_music before nbls_plan)");
+    if (h->req.music.sources < 0 || !h->d_music_eig) return fail(h, NBLS_ERR_STATE, std::string(who) + ": the plan did not ask for the eigenvalues (nbls_set_capon_music before nbls_plan)");
     return 0;
 }
 
@@ -2119,45 +2031,45 @@ int nbls_fetch_capon_music(nbls_handle* h, double* eigenvalues, int32_t* sources
     int rc;
     if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music")) || (rc = finish_pass(h))) return rc;
     const size_t cells = (size_t)h->nbands * h->vector_len;
-    if ((rc = capon_fetch_plane(h, eigenvalues, h->d_music_eig.p, (size_t)h->nelem * sizeof(double)))) return rc;
-    if ((rc = capon_fetch_plane(h, sources, h->d_music_int.p, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, sweeps, h->d_music_int.p + cells, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, index, h->d_music_int.p + 2 * cells, sizeof(int32_t)))) return rc;
-    return capon_fetch_plane(h, power, h->d_music_power.p, sizeof(double));
+    if ((rc = fetch_plane(h, h->solve_ran, eigenvalues, h->d_music_eig.p, (size_t)h->nelem * sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, sources, h->d_music_int.p, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, sweeps, h->d_music_int.p + cells, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, index, h->d_music_int.p + 2 * cells, sizeof(int32_t)))) return rc;
+    return fetch_plane(h, h->solve_ran, power, h->d_music_power.p, sizeof(double));
 }
 
 int nbls_fetch_capon_music_map(nbls_handle* h, double* map) {
     if (!h || !map) return NBLS_ERR_ARG;
     int rc;
     if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music_map"))) return rc;
-    if (!(h->music.flags & NBLS_MUSIC_MAP) || !h->d_music_map)
+    if (!(h->req.music.flags & NBLS_MUSIC_MAP) || !h->d_music_map)
         return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_music_map: the plan did not ask for the map (nbls_set_capon_music, NBLS_MUSIC_MAP)");
     if ((rc = finish_pass(h))) return rc;
-    return capon_fetch_plane(h, map, h->d_music_map.p, (size_t)h->capon_n * sizeof(double));
+    return fetch_plane(h, h->solve_ran, map, h->d_music_map.p, (size_t)h->derived.capon_n * sizeof(double));
 }
 
 int nbls_fetch_capon_music_vectors(nbls_handle* h, double* E) {
     if (!h || !E) return NBLS_ERR_ARG;
     int rc;
     if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music_vectors"))) return rc;
-    if (!(h->music.flags & NBLS_MUSIC_VECTORS) || !h->d_music_vec)
+    if (!(h->req.music.flags & NBLS_MUSIC_VECTORS) || !h->d_music_vec)
         return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_music_vectors: the plan did not ask for the eigenvectors (nbls_set_capon_music, NBLS_MUSIC_VECTORS)");
     if ((rc = finish_pass(h))) return rc;
-    return capon_fetch_plane(h, E, h->d_music_vec.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
+    return fetch_plane(h, h->solve_ran, E, h->d_music_vec.p, (size_t)h->nelem * h->nelem * 2 * sizeof(double));
 }
 
 int nbls_fetch_capon_music_peaks(nbls_handle* h, int32_t* count, int32_t* index, double* power, double* offset) {
     if (!h) return NBLS_ERR_ARG;
     int rc;
     if ((rc = music_fetch_ready(h, "nbls_fetch_capon_music_peaks"))) return rc;
-    if (!(h->music.flags & NBLS_MUSIC_PEAKS) || h->capon_peaks < 1 || !h->d_music_peak_count)
+    if (!(h->req.music.flags & NBLS_MUSIC_PEAKS) || h->req.peaks.k < 1 || !h->d_music_peak_count)
         return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_music_peaks: the plan did not ask for the peaks (nbls_set_capon_music, NBLS_MUSIC_PEAKS)");
     if ((rc = finish_pass(h))) return rc;
-    const size_t K = (size_t)h->capon_peaks;
-    if ((rc = capon_fetch_plane(h, count, h->d_music_peak_count.p, sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, index, h->d_music_peak_index.p, K * sizeof(int32_t)))) return rc;
-    if ((rc = capon_fetch_plane(h, power, h->d_music_peak_power.p, K * sizeof(double)))) return rc;
-    return capon_fetch_plane(h, offset, h->d_music_peak_offset.p, K * 2 * sizeof(double));
+    const size_t K = (size_t)h->req.peaks.k;
+    if ((rc = fetch_plane(h, h->solve_ran, count, h->d_music_peak_count.p, sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, index, h->d_music_peak_index.p, K * sizeof(int32_t)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, power, h->d_music_peak_power.p, K * sizeof(double)))) return rc;
+    return fetch_plane(h, h->solve_ran, offset, h->d_music_peak_offset.p, K * 2 * sizeof(double));
 }
 
 int nbls_capon_music_lds_bytes(int32_t nelem) {
@@ -2168,10 +2080,10 @@ int nbls_capon_music_lds_bytes(int32_t nelem) {
 int nbls_fetch_capon_tables(nbls_handle* h, int32_t band, double* coef, double* steer) {
     if (!h) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_tables: no plan");
-    if (h->capon_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_tables: nbls_set_capon before nbls_plan");
+    if (h->derived.capon_n < 1) return fail(h, NBLS_ERR_STATE, "nbls_fetch_capon_tables: nbls_set_capon before nbls_plan");
     if (band < 0 || band >= h->fbands) return fail(h, NBLS_ERR_ARG, "nbls_fetch_capon_tables: no such band");
-    const int G = h->capon_n, N = h->nelem;                      // the plan's own tables (the device holds copies)
-    if (coef) memcpy(coef, h->h_capon_coef.data() + (size_t)band * h->capon_maxls * 2, (size_t)h->h_capon_par[3 * band] * 2 * sizeof(double));
+    const int G = h->derived.capon_n, N = h->nelem;                      // the plan's own tables (the device holds copies)
+    if (coef) memcpy(coef, h->h_capon_coef.data() + (size_t)band * h->derived.capon_maxls * 2, (size_t)h->h_capon_par[3 * band] * 2 * sizeof(double));
     if (steer) {
         const double* s = h->h_capon_steer.data() + (size_t)band * N * G * 2;
         for (int g = 0; g < G; ++g)
@@ -2187,42 +2099,42 @@ int nbls_set_beam_interpolation(nbls_handle* h, int32_t taps) {
     if (!h) return NBLS_ERR_ARG;
     if (taps != 0 && taps != 4 && taps != 6 && taps != 8)
         return fail(h, NBLS_ERR_ARG, "nbls_set_beam_interpolation: taps must be 0 (off), 4, 6 or 8");
-    h->want_steer_taps = taps;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.steer_taps = taps;               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
 }
 
 int nbls_fetch_beam_grid_coefficients(nbls_handle* h, double* c) {
     if (!h || !c) return NBLS_ERR_ARG;
     if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_coefficients: no plan");
-    if (h->grid_n < 1 || !h->grid_taps)
+    if (h->derived.grid_n < 1 || !h->req.grid_taps())
         return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_coefficients: nbls_set_beam_grid and nbls_set_beam_interpolation before nbls_plan");
-    memcpy(c, h->h_grid_coef.data(), h->h_grid_coef.size() * sizeof(double));   // the plan's own table (the device holds a copy)
+    memcpy(c, h->derived.grid_coef.data(), h->derived.grid_coef.size() * sizeof(double));   // the plan's own table (the device holds a copy)
     return NBLS_OK;
 }
 
 int nbls_set_lag_refinement(nbls_handle* h, int32_t on) {
     if (!h) return NBLS_ERR_ARG;
-    h->want_refine = on != 0;                // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.refine = on != 0;                // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
 }
 
 int nbls_set_lag_limits(nbls_handle* h, const int32_t* max_lag, int32_t npairs) {
     if (!h) return NBLS_ERR_ARG;
-    if (!max_lag) { h->want_lim.clear(); return NBLS_OK; }      // off: the next plan searches every lag
+    if (!max_lag) { h->want.lim.clear(); return NBLS_OK; }      // off: the next plan searches every lag
     if (npairs < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_limits: npairs must be at least 1");
     for (int32_t k = 0; k < npairs; ++k)                         // everything is checked before the handle changes
         if (max_lag[k] < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_limits: negative limit of pair " + std::to_string(k));
-    h->want_lim.assign(max_lag, max_lag + npairs);               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.lim.assign(max_lag, max_lag + npairs);               // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
 }
 
 int nbls_set_lag_seed(nbls_handle* h, const int32_t* halfwidth, int32_t nbands) {
     if (!h) return NBLS_ERR_ARG;
-    if (!halfwidth) { h->want_seed.clear(); return NBLS_OK; }   // off: the next plan does not seed its lag search
+    if (!halfwidth) { h->want.seed.clear(); return NBLS_OK; }   // off: the next plan does not seed its lag search
     if (nbands < 1) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_seed: nbands must be at least 1");
     for (int32_t b = 0; b < nbands; ++b)
         if (halfwidth[b] < 0) return fail(h, NBLS_ERR_ARG, "nbls_set_lag_seed: negative half-width of band " + std::to_string(b));
-    h->want_seed.assign(halfwidth, halfwidth + nbands);         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.seed.assign(halfwidth, halfwidth + nbands);         // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
     return NBLS_OK;
 }
 
@@ -2249,12 +2161,12 @@ int nbls_est_fetch_lag_fraction(nbls_handle* h, int32_t est, double* frac) {
     if (est < 0 || est > h->nest) return fail(h, NBLS_ERR_ARG, "nbls_est_fetch_lag_fraction: no such estimator");
     const nbls_estimator& s = h->est[est];
     const nbls_est_view v = nbls_view_of(h, s);
-    if (!h->refine || !v.frac) return fail(h, NBLS_ERR_STATE, "nbls_fetch_lag_fraction: nbls_set_lag_refinement before nbls_plan");
+    if (!h->req.refine || !v.frac) return fail(h, NBLS_ERR_STATE, "nbls_fetch_lag_fraction: nbls_set_lag_refinement before nbls_plan");
     { const int rc = finish_pass(h); if (rc) return rc; }
     const size_t cells = (size_t)h->nbands * h->vector_len, P = (size_t)s.npairs;
     // the fractions are written by the correlation stage alone (a sub-array's compact rows: gathered as part of its solve):
     // zeros until a pass of this plan has run it, and a later pass without it leaves them as they are
-    const bool have = h->frac_valid && (s.kept_pair.empty() || h->solve_ran);
+    const bool have = h->xcorr_ran && (s.kept_pair.empty() || h->solve_ran);
     if (!have) { memset(frac, 0, cells * P * sizeof(double)); return NBLS_OK; }
     HIPCHK(h, copy_sync(h, frac, v.frac, cells * P * sizeof(double), hipMemcpyDeviceToHost));
     zero_uncomputed(h, frac, P * sizeof(double));

@@ -273,13 +273,13 @@ hipError_t nbls_launch_beam(nbls_handle* h, const nbls_estimator& s, int64_t u0,
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
     a.power = s.d_beam; a.fstat = s.d_beam + cells;
     const dim3 grid((unsigned)((nu + BEAM_WAVES - 1) / BEAM_WAVES)), block(BEAM_WAVES * 64);
-    if (h->kept_beam && &s == &h->est[0]) {                     // the beam of the elements LTS kept (nbls_set_kept_elements)
+    if (h->req.kept_beam() && &s == &h->est[0]) {                     // the beam of the elements LTS kept (nbls_set_kept_elements)
         if (a.kept || a.N > 32 || !h->d_kept_mask) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
         a.dropped = h->d_kept_mask;
-        if (h->steer_taps) return nbls_launch_beam_steer(h->steer_taps, true, grid, block, st, &a);
+        if (h->req.steer_taps) return nbls_launch_beam_steer(h->req.steer_taps, true, grid, block, st, &a);
         hipLaunchKernelGGL((beam_fstat_kernel<true, 0>), grid, block, 0, st, a);
     } else {
-        if (h->steer_taps) return nbls_launch_beam_steer(h->steer_taps, false, grid, block, st, &a);
+        if (h->req.steer_taps) return nbls_launch_beam_steer(h->req.steer_taps, false, grid, block, st, &a);
         hipLaunchKernelGGL((beam_fstat_kernel<false, 0>), grid, block, 0, st, a);
     }
     return hipGetLastError();

@@ -315,25 +315,25 @@ hipError_t nbls_launch_beam_grid(nbls_handle* h, int64_t u0, int64_t nu, hipStre
     a.Wb = h->d_W; a.incb = h->d_inc;
     a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
-    a.G = h->grid_n; a.halo = h->grid_halo;
+    a.G = h->derived.grid_n; a.halo = h->derived.grid_halo;
     a.maxW = h->maxW;
     a.delay = h->d_grid_delay;
-    a.coef = h->grid_taps ? h->d_grid_coef.p : nullptr;
+    a.coef = h->req.grid_taps() ? h->d_grid_coef.p : nullptr;
     a.index = h->d_grid_index;
     a.fstat = h->d_grid_fp; a.power = h->d_grid_fp + cells;
-    a.map = h->grid_map ? h->d_grid_map.p : nullptr;
+    a.map = h->req.grid_map() ? h->d_grid_map.p : nullptr;
     // the units of a plan are windows of up to maxW samples: their block in LDS where the longest one fits
-    const size_t lds = nbls_beam_grid_lds_bytes_of(h->nelem, h->maxW, h->grid_halo);
+    const size_t lds = nbls_beam_grid_lds_bytes_of(h->nelem, h->maxW, h->derived.grid_halo);
     if (lds) {
-        const unsigned bit = 1u << (h->grid_taps / 2);
+        const unsigned bit = 1u << (h->req.grid_taps() / 2);
         if (!(h->grid_attr_set & bit)) {   // once per handle and instance (a streamed pass launches per unit batch)
-            const hipError_t e = hipFuncSetAttribute(grid_kernel_of<true>(h->grid_taps), hipFuncAttributeMaxDynamicSharedMemorySize,
+            const hipError_t e = hipFuncSetAttribute(grid_kernel_of<true>(h->req.grid_taps()), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                      (int)GRID_LDS_MAX);
             if (e != hipSuccess) return e;
             h->grid_attr_set |= bit;
         }
     }
     void* args[] = {&a};
-    return hipLaunchKernel(lds ? grid_kernel_of<true>(h->grid_taps) : grid_kernel_of<false>(h->grid_taps), dim3((unsigned)nu),
+    return hipLaunchKernel(lds ? grid_kernel_of<true>(h->req.grid_taps()) : grid_kernel_of<false>(h->req.grid_taps()), dim3((unsigned)nu),
                            dim3(GRID_WAVES * 64), args, lds, st);
 }

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_trace_kernel(TArgs a) {
 }  // namespace
 
 hipError_t nbls_launch_beam_trace(nbls_handle* h, hipStream_t st) {
-    if (!h->bt || h->nbands < 1 || h->npts < 1) return hipSuccess;
+    if (!h->req.bt || h->nbands < 1 || h->npts < 1) return hipSuccess;
     const nbls_estimator& s = h->est[0];
     TArgs a{};
     a.filt = h->d_filt;
@@ -139,8 +139,8 @@ hipError_t nbls_launch_beam_trace(nbls_handle* h, hipStream_t st) {
     a.z = s.d_z;
     a.mdccm = nbls_view_of(h, s).mdccm;
     a.fs = h->fs;
-    a.gate = h->bt_min == h->bt_min ? 1 : 0;                     // (off iff mdccm_min is NaN)
-    a.mdccm_min = h->bt_min;
+    a.gate = h->req.bt_min == h->req.bt_min ? 1 : 0;                     // (off iff mdccm_min is NaN)
+    a.mdccm_min = h->req.bt_min;
     a.Wb = h->d_W; a.incb = h->d_inc; a.nwin = h->d_nwin;
     a.win = h->d_bt_win; a.win_off = h->d_bt_off;
     a.vector_len = h->vector_len;
@@ -151,7 +151,7 @@ hipError_t nbls_launch_beam_trace(nbls_handle* h, hipStream_t st) {
     const int64_t blocks = a.ntiles * h->nbands;
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks), block(BT_THREADS);
-    if (h->bt_kept) {
+    if (h->req.bt_kept()) {
         if (a.N > 32 || !h->d_kept_mask) return hipErrorInvalidValue;
         a.dropped = h->d_kept_mask;
         hipLaunchKernelGGL(beam_trace_kernel<true>, grid, block, 0, st, a);

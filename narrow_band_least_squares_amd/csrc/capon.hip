@@ -446,15 +446,15 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
     a.Wb = h->d_W; a.incb = h->d_inc;
     a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
-    a.G = h->capon_n; a.maxLs = h->capon_maxls;
+    a.G = h->derived.capon_n; a.maxLs = h->derived.capon_maxls;
     a.par = h->d_capon_par; a.coef = h->d_capon_coef; a.steer = h->d_capon_steer;
-    a.loading = h->capon_loading;
+    a.loading = h->req.capon.loading;
     a.cells = (int64_t)h->nbands * h->vector_len;
     a.index = h->d_capon_index; a.power = h->d_capon_power;
-    a.map = h->capon_maps ? h->d_capon_map.p : nullptr;
-    a.csdm = (h->capon_csdm || h->clean.iterations > 0 || h->music.sources >= 0) ? h->d_capon_csdm.p : nullptr;     // (capon_clean_kernel and capon_music_kernel read R there)
+    a.map = h->req.capon_maps() ? h->d_capon_map.p : nullptr;
+    a.csdm = (h->req.capon_csdm() || h->req.clean.iterations > 0 || h->req.music.sources >= 0) ? h->d_capon_csdm.p : nullptr;     // (capon_clean_kernel and capon_music_kernel read R there)
     const size_t lds = nbls_capon_lds_bytes_of(h->nelem);
-    const bool kept = h->kept_capon;       // the spectra of the elements LTS kept (nbls_set_kept_elements): the KEPT instances
+    const bool kept = h->req.kept_capon();       // the spectra of the elements LTS kept (nbls_set_kept_elements): the KEPT instances
     if (kept) {
         if (!h->d_kept_mask) return hipErrorInvalidValue;                // (nbls_plan has refused such a plan)
         a.dropped = h->d_kept_mask;
@@ -476,12 +476,12 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
         return hipLaunchKernel(fn, dim3(nblocks), dim3(CT), params, shm, st);
     };
     const void* fn = nullptr;
-    if (h->capon_peaks > 0) {              // a plan with a peak request (nbls_set_capon_peaks)
-        a.nbr = h->d_capon_nbr; a.pk = h->capon_peaks; a.pfloor = h->capon_peak_floor;
+    if (h->req.peaks.k > 0) {              // a plan with a peak request (nbls_set_capon_peaks)
+        a.nbr = h->d_capon_nbr; a.pk = h->req.peaks.k; a.pfloor = h->req.peaks.floor;
         a.pk_count = h->d_capon_peak_count; a.pk_index = h->d_capon_peak_index;
         a.pk_power = h->d_capon_peak_power; a.pk_offset = h->d_capon_peak_offset;
-        if (h->capon_peak_route == 1) {
-            const size_t plds = nbls_capon_peak_lds_bytes_of(h->nelem, h->capon_n);
+        if (h->derived.peak_route == 1) {
+            const size_t plds = nbls_capon_peak_lds_bytes_of(h->nelem, h->derived.capon_n);
             if (!plds) return hipErrorInvalidValue;                      // (nbls_plan has refused such a plan)
             const hipError_t e = instance(1, 160 * 1024 - 1024, &fn);
             if (e != hipSuccess) return e;
@@ -506,7 +506,7 @@ hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t
                 if (e != hipSuccess) return e;
             }
         }
-        const int64_t step = a.map ? nu : h->capon_peak_slabs;
+        const int64_t step = a.map ? nu : h->derived.peak_slabs;
         for (int64_t o = 0; o < nu; o += step) {
             a.u0 = (int)(u0 + o);
             a.nunits = (int)(nu - o < step ? nu - o : step);

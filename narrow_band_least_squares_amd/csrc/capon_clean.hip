@@ -215,17 +215,17 @@ size_t nbls_capon_clean_lds_bytes_of(int nelem) {
 
 hipError_t nbls_launch_capon_clean(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
-    if (h->nelem > CMAXN || h->nelem < 1 || h->capon_n < 1 || !h->d_capon_csdm) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
+    if (h->nelem > CMAXN || h->nelem < 1 || h->derived.capon_n < 1 || !h->d_capon_csdm) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
     CLArgs a{};
     a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
-    a.N = h->nelem; a.nseg = h->nbands / h->fbands; a.G = h->capon_n;
+    a.N = h->nelem; a.nseg = h->nbands / h->fbands; a.G = h->derived.capon_n;
     a.steer = h->d_capon_steer; a.csdm = h->d_capon_csdm.p;
-    a.iters = h->clean.iterations; a.gain = h->clean.gain; a.floor = h->clean.floor;
+    a.iters = h->req.clean.iterations; a.gain = h->req.clean.gain; a.floor = h->req.clean.floor;
     a.count = h->d_clean_count; a.index = h->d_clean_index; a.power = h->d_clean_power;
     a.total = h->d_clean_tr.p; a.residual = h->d_clean_tr.p + (size_t)h->nbands * h->vector_len;
-    a.rcsdm = (h->clean.flags & NBLS_CLEAN_RESIDUAL) ? h->d_clean_csdm.p : nullptr;
-    const bool kept = h->kept_capon;
+    a.rcsdm = (h->req.clean.flags & NBLS_CLEAN_RESIDUAL) ? h->d_clean_csdm.p : nullptr;
+    const bool kept = h->req.kept_capon();
     if (kept) {
         if (!h->d_kept_mask) return hipErrorInvalidValue;
         a.dropped = h->d_kept_mask;

@@ -314,21 +314,21 @@ size_t nbls_capon_music_lds_bytes_of(int nelem) {
 
 hipError_t nbls_launch_capon_music(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st) {
     if (nu <= 0) return hipSuccess;
-    if (h->nelem > CMAXN || h->nelem < 3 || h->capon_n < 1 || !h->d_capon_csdm || h->music.sources < 0 || h->music.sources > h->nelem - 1)
+    if (h->nelem > CMAXN || h->nelem < 3 || h->derived.capon_n < 1 || !h->d_capon_csdm || h->req.music.sources < 0 || h->req.music.sources > h->nelem - 1)
         return hipErrorInvalidValue;                                 // (nbls_plan has refused such a plan)
     MUArgs a{};
     a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;
-    a.N = h->nelem; a.nseg = h->nbands / h->fbands; a.G = h->capon_n;
+    a.N = h->nelem; a.nseg = h->nbands / h->fbands; a.G = h->derived.capon_n;
     a.steer = h->d_capon_steer; a.csdm = h->d_capon_csdm.p;
-    a.sources = h->music.sources; a.eig_floor = h->music.eig_floor;
+    a.sources = h->req.music.sources; a.eig_floor = h->req.music.eig_floor;
     a.eigenvalues = h->d_music_eig; a.nsrc = h->d_music_int.p;
     const size_t cells = (size_t)h->nbands * h->vector_len;
     a.sweeps = h->d_music_int.p + cells; a.index = h->d_music_int.p + 2 * cells;
     a.power = h->d_music_power;
-    a.map = (h->music.flags & NBLS_MUSIC_MAP) ? h->d_music_map.p : nullptr;
-    a.vectors = (h->music.flags & NBLS_MUSIC_VECTORS) ? h->d_music_vec.p : nullptr;
-    const bool peaks = (h->music.flags & NBLS_MUSIC_PEAKS) != 0;
+    a.map = (h->req.music.flags & NBLS_MUSIC_MAP) ? h->d_music_map.p : nullptr;
+    a.vectors = (h->req.music.flags & NBLS_MUSIC_VECTORS) ? h->d_music_vec.p : nullptr;
+    const bool peaks = (h->req.music.flags & NBLS_MUSIC_PEAKS) != 0;
     const void* fn = peaks ? (const void*)capon_music_kernel<true> : (const void*)capon_music_kernel<false>;
     if (!h->music_attr_set[peaks]) {                                 // once per handle (a streamed pass launches per unit batch)
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nbls_capon_music_lds_bytes_of(CMAXN));
@@ -338,8 +338,8 @@ hipError_t nbls_launch_capon_music(nbls_handle* h, int64_t u0, int64_t nu, hipSt
     const size_t lds = nbls_capon_music_lds_bytes_of(h->nelem);
     void* params[] = {(void*)&a};
     if (!peaks) return hipLaunchKernel(fn, dim3((unsigned)nu), dim3(CT), params, lds, st);
-    if (h->capon_peaks < 1 || !h->d_capon_nbr || !h->d_music_peak_count) return hipErrorInvalidValue;      // (nbls_plan has refused such a plan)
-    a.pk = PeakOut{h->d_capon_nbr, h->capon_n, h->capon_peaks, h->music.peak_floor, h->d_music_peak_count, h->d_music_peak_index,
+    if (h->req.peaks.k < 1 || !h->d_capon_nbr || !h->d_music_peak_count) return hipErrorInvalidValue;      // (nbls_plan has refused such a plan)
+    a.pk = PeakOut{h->d_capon_nbr, h->derived.capon_n, h->req.peaks.k, h->req.music.peak_floor, h->d_music_peak_count, h->d_music_peak_index,
                    h->d_music_peak_power, h->d_music_peak_offset};
     // the map of a unit lies in its own row of d_music_map where the plan keeps it; else in the slab of its workgroup: at
     // most capon_peak_slabs workgroups per launch.  On one stream its order hands the slabs on; the solves of a pass may be
@@ -355,7 +355,7 @@ hipError_t nbls_launch_capon_music(nbls_handle* h, int64_t u0, int64_t nu, hipSt
             if (e != hipSuccess) return e;
         }
     }
-    const int64_t step = a.map ? nu : h->capon_peak_slabs;
+    const int64_t step = a.map ? nu : h->derived.peak_slabs;
     if (step < 1) return hipErrorInvalidValue;
     for (int64_t o = 0; o < nu; o += step) {
         a.u0 = (int)(u0 + o);

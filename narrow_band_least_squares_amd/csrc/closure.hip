@@ -145,9 +145,9 @@ hipError_t nbls_launch_closure(nbls_handle* h, const nbls_estimator& s, int64_t 
     a.cons = s.d_closure; a.cmax = s.d_closure + cells;
     a.el = s.d_closure_el;
     const dim3 grid((unsigned)((nu + CLOSURE_WAVES - 1) / CLOSURE_WAVES)), block(CLOSURE_WAVES * 64);
-    const size_t cell_sz = h->refine ? sizeof(double) : sizeof(int32_t);
+    const size_t cell_sz = h->req.refine ? sizeof(double) : sizeof(int32_t);
     const size_t shm = (size_t)CLOSURE_WAVES * a.N * a.N * cell_sz;      // at most 32 KB
-    if (h->refine) hipLaunchKernelGGL(closure_kernel<true>, grid, block, shm, st, a);
+    if (h->req.refine) hipLaunchKernelGGL(closure_kernel<true>, grid, block, shm, st, a);
     else hipLaunchKernelGGL(closure_kernel<false>, grid, block, shm, st, a);
     return hipGetLastError();
 }

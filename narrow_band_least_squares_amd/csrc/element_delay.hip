@@ -315,19 +315,19 @@ hipError_t nbls_launch_element_delays(nbls_handle* h, int64_t u0, int64_t nu, hi
     a.shift = h->d_ed_shift;
     // (nbls_plan has refused such a plan)
     if (a.N < 1 || a.N > ED_MAX_ELEMENTS || !a.filt || !a.xij || !a.z || !a.Kb || !a.delay || !a.shift) return hipErrorInvalidValue;
-    if (h->ed_kept) {
+    if (h->req.ed_kept()) {
         if (!h->d_kept_mask) return hipErrorInvalidValue;
         a.dropped = h->d_kept_mask;
     }
-    const size_t lds = h->ed_lds;                // the plan's form: every row's block fits (the largest one's bytes), or 0
+    const size_t lds = h->derived.ed_lds;                // the plan's form: every row's block fits (the largest one's bytes), or 0
     const int chunk = h->opt.element_delay_chunk == 1 ? 1 : ED_CHUNK;
-    const int inst = (h->ed_kept ? 1 : 0) + (chunk == 1 ? 2 : 0);
+    const int inst = (h->req.ed_kept() ? 1 : 0) + (chunk == 1 ? 2 : 0);
     if (lds && !h->ed_attr_set[inst]) {          // once per handle and instance (a streamed pass launches per unit batch)
-        const hipError_t e = hipFuncSetAttribute(ed_kernel_of<true>(h->ed_kept, chunk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ED_LDS_MAX);
+        const hipError_t e = hipFuncSetAttribute(ed_kernel_of<true>(h->req.ed_kept(), chunk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ED_LDS_MAX);
         if (e != hipSuccess) return e;
         h->ed_attr_set[inst] = true;
     }
     void* args[] = {&a};
-    return hipLaunchKernel(lds ? ed_kernel_of<true>(h->ed_kept, chunk) : ed_kernel_of<false>(h->ed_kept, chunk), dim3((unsigned)nu),
+    return hipLaunchKernel(lds ? ed_kernel_of<true>(h->req.ed_kept(), chunk) : ed_kernel_of<false>(h->req.ed_kept(), chunk), dim3((unsigned)nu),
                            dim3(ED_THREADS), args, lds, st);
 }

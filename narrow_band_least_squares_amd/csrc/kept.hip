@@ -66,7 +66,7 @@ hipError_t nbls_launch_kept_elements(nbls_handle* h, int64_t u0, int64_t nu, hip
     const nbls_estimator& s = h->est[0];
     KArgs a{};
     a.wts = s.d_wts;
-    a.N = h->nelem; a.P = s.npairs; a.q = h->kept_q;
+    a.N = h->nelem; a.P = s.npairs; a.q = h->req.kept_q;
     if (a.N < 1 || a.N > KEPT_MAX_ELEMENTS || (int64_t)a.N * (a.N - 1) / 2 != a.P) return hipErrorInvalidValue;   // (nbls_plan has refused such a plan)
     a.unit_band = h->d_unit_band; a.unit_win = h->d_unit_win;
     a.vector_len = h->vector_len; a.u0 = (int)u0; a.nunits = (int)nu;

@@ -116,6 +116,81 @@ struct nbls_estimator {
 
 #define NBLS_MAX_ESTIMATORS 8      // further estimators of one pass, beside estimator 0
 
+// The opt-in requests of a plan, as the nbls_set_* calls record them.  The handle holds two: `want`, written by the setters
+// and read by the next nbls_plan alone, and `req`, the plan's own copy (committed in one assignment once nbls_plan has
+// refused nothing), which everything behind the plan's checks reads.  A request that is off is in its default state.
+struct nbls_requests {
+    bool beam = false;              // nbls_set_beam: beam power and F-statistic behind every estimator's solve (beam.hip)
+    bool closure = false;           // nbls_set_closure: closure of the picked lags behind every estimator's solve (closure.hip)
+    bool refine = false;            // nbls_set_lag_refinement: sub-sample lags behind the verifier (refine.hip)
+    std::vector<int32_t> lim;       // nbls_set_lag_limits: [npairs] max_lag per pair (empty: every lag is searched)
+    // nbls_set_lag_seed (xcorr_seeded.hip): [nbands] half-width per band (empty: off).  A plan with a slowness grid then picks
+    // every pair's lag near the delay the unit's grid maximum predicts; the grid search belongs to the correlation stage
+    std::vector<int32_t> seed;
+    std::vector<double> grid;       // nbls_set_beam_grid (beam_grid.hip): [G][2] slowness vectors (empty: off)
+    bool grid_keep_map = false;     // ... and whether the plan keeps every F(g)
+    int steer_taps = 0;             // nbls_set_beam_interpolation (steer.h): 0 whole samples / 4 / 6 / 8 taps
+    // ---- Capon / Bartlett spectra of the narrow band's cross-spectral matrix (nbls_set_capon, capon.hip) ----
+    struct capon_request {
+        std::vector<double> grid;       // [G][2] slowness vectors (empty: off)
+        std::vector<double> freq;       // [nbands] Hz
+        std::vector<int32_t> ls, hs;    // [nbands] snapshot length and hop
+        double loading = 0.0;
+        int flags = 0;
+    } capon;
+    // ---- the K strongest peaks of either spectrum (nbls_set_capon_peaks, capon.hip; DESIGN.md section 19) ----
+    struct capon_peak_request {
+        std::vector<int32_t> nbr;       // [8][G] neighbour table of the request's cells (empty: off)
+        int k = 0;                      // K (0: off)
+        double floor = 0.0;
+    } peaks;
+    // ---- the window's arrivals by CLEAN-SC (nbls_set_capon_clean, capon_clean.hip; DESIGN.md section 24) ----
+    struct capon_clean_request {
+        int iterations = 0;             // I (0: off, no capon_clean_kernel is launched)
+        double gain = 0.0, floor = 0.0;
+        int flags = 0;
+    } clean;
+    // ---- the window's eigenvalues and MUSIC spectrum (nbls_set_capon_music, capon_music.hip; DESIGN.md section 25) ----
+    struct capon_music_request {
+        int sources = -1;               // M, 0: by eig_floor, -1: off (no capon_music_kernel is launched)
+        double eig_floor = 0.0, peak_floor = 0.0;
+        int flags = 0;
+    } music;
+    // ---- the elements LTS kept (nbls_set_kept_elements, kept.hip; DESIGN.md section 20) ----
+    int kept_q = 0, kept_flags = 0;     // min_pairs (0: off) and NBLS_KEPT_*
+    // ---- the beam trace of every result row (nbls_set_beam_trace, beam_trace.hip; DESIGN.md section 21) ----
+    bool bt = false;                // the trace is formed behind the pass's last solve
+    std::vector<double> bt_win;     // ... its synthesis windows, band after band
+    double bt_min = 0.0;            // ... its MdCCM gate (NaN: off)
+    int bt_flags = 0;
+    // ---- each element's delay against the beam of the others (nbls_set_element_delays, element_delay.hip; DESIGN.md section 23) ----
+    bool ed = false;                // the delays are measured behind every solve of estimator 0
+    std::vector<int32_t> ed_K;      // ... its max_shift, one per band
+    int ed_flags = 0;
+
+    // what the flags resolve to
+    bool kept_beam() const { return kept_q > 0 && (kept_flags & NBLS_KEPT_BEAM); }      // the beam is that of the kept elements
+    bool kept_capon() const { return kept_q > 0 && (kept_flags & NBLS_KEPT_CAPON); }    // ... and so are the spectra
+    bool bt_kept() const { return bt && (bt_flags & NBLS_BEAM_TRACE_KEPT); }            // the trace over the elements LTS kept in each window
+    bool ed_kept() const { return ed && (ed_flags & NBLS_ELEMENT_DELAY_KEPT); }         // the delays against the beam of the kept elements
+    bool capon_maps() const { return !capon.grid.empty() && (capon.flags & NBLS_CAPON_MAPS); }   // the plan keeps both maps
+    bool capon_csdm() const { return !capon.grid.empty() && (capon.flags & NBLS_CAPON_CSDM); }   // ... the matrix R
+    bool grid_map() const { return !grid.empty() && grid_keep_map; }
+    int grid_taps() const { return grid.empty() ? 0 : steer_taps; }                     // the taps of the grid search (0: none, or whole samples)
+};
+
+// What nbls_plan derives from its requests and the trace; valid with `req`.
+struct nbls_plan_derived {
+    int grid_n = 0, grid_halo = 0;          // G of the slowness grid (0: the plan does not search) and H = max |delay|
+    std::vector<int32_t> grid_delay;        // [G][nelem] the delay table (interpolated: floor(tau))
+    std::vector<double> grid_coef;          // [G][nelem][taps] the coefficient table of an interpolated grid
+    int capon_n = 0;                        // G of the spectra (0: the plan computes none)
+    int capon_maxls = 0;                    // the longest snapshot: the row length of h_capon_coef
+    int peak_route = 0;                     // a peak request's route: 1 the unit's maps in LDS, 2 in HBM (its rows of d_capon_map, or a slab)
+    int peak_slabs = 0;                     // HBM route: slabs of d_capon_peak_slab = workgroups per launch
+    size_t ed_lds = 0;                      // dynamic LDS of the staged element-delay form (the largest row's block); 0: the global form
+};
+
 struct nbls_handle {
     int device = 0;
     nbls_options opt;
@@ -134,62 +209,29 @@ struct nbls_handle {
     bool solve_on_stream2 = false;  // ... on the second stream (option "overlap"), else behind the batch on `stream`
     bool solve_done = false;
     int last_stage_mask = 7;        // stages of the last pass (nbls_fetch zeroes the outputs of stages that did not run)
-    bool want_beam = false;         // nbls_set_beam: read by the next nbls_plan
-    bool beam = false;              // the plan computes beam power and F-statistic behind every estimator's solve (beam.hip)
-    bool beam_valid = false;        // a pass of this plan has run the solve stage: est[].d_beam holds results
-    bool want_closure = false;      // nbls_set_closure: read by the next nbls_plan
-    bool closure = false;           // the plan computes the closure of the picked lags behind every estimator's solve (closure.hip)
-    bool closure_valid = false;     // a pass of this plan has run the solve stage: est[].d_closure / d_closure_el hold results
-    bool want_refine = false;       // nbls_set_lag_refinement: read by the next nbls_plan
-    bool refine = false;            // the plan refines the picked lags to sub-sample precision behind the verifier (refine.hip)
-    bool frac_valid = false;        // a pass of this plan has run the correlation stage: d_lagfrac holds results
-    bool solve_ran = false;         // a pass of this plan has run the solve stage (a sub-array's compact rows are gathered there)
-    std::vector<int32_t> want_lim;  // nbls_set_lag_limits: [npairs] max_lag per pair, read by the next nbls_plan (empty: off)
-    std::vector<int32_t> lim;       // the plan's copy (empty: the plan searches every lag)
+    nbls_requests want;             // the nbls_set_* calls write here; read by the next nbls_plan, and by nothing else
+    nbls_requests req;              // the plan's requests
+    nbls_plan_derived derived;      // ... and what the plan made of them for this trace
+    // What a pass of this plan has left in the buffers of the opt-in results, which no pass clears: the solve stage has run
+    // (the results written behind a solve, and a sub-array's compact rows, gathered there), the correlation stage has run
+    // (d_lagfrac, and the grid search of a plan with a lag seed).  A fetch returns zeros until then, and a later pass
+    // without the stage leaves the results as they are.
+    bool solve_ran = false, xcorr_ran = false;
+    bool grid_ran() const { return req.seed.empty() ? solve_ran : xcorr_ran; }     // the grid search's results are there
     dev_buf<int32_t> d_limsq;       // [nelem][nelem] the plan's limit of the pair of two elements, symmetric, 0 on the diagonal
-    // ---- seeded lag search (nbls_set_lag_seed, xcorr_seeded.hip): a plan with a slowness grid picks every pair's lag near the
-    // delay the unit's grid maximum predicts; the grid search then belongs to the correlation stage ----
-    std::vector<int32_t> want_seed; // nbls_set_lag_seed: [nbands] half-width per band, read by the next nbls_plan (empty: off)
-    std::vector<int32_t> seed;      // the plan's copy (empty: the plan does not seed)
-    dev_buf<int32_t> d_seed;        // [rows] the half-width of every result row (row r: band r / nseg)
+    dev_buf<int32_t> d_seed;        // [rows] the seed half-width of every result row (row r: band r / nseg)
     bool seed_attr_set = false;     // the staged form of the seeded correlator has been given its dynamic LDS limit
     bool refine_attr_set = false;   // the LDS form of refine_lag_kernel has been given its dynamic LDS limit on this handle's device
-    // ---- slowness-grid search of the beam F-statistic (nbls_set_beam_grid, beam_grid.hip) ----
-    std::vector<double> want_grid;  // nbls_set_beam_grid: [G][2] slowness vectors, read by the next nbls_plan (empty: off)
-    bool want_grid_map = false;     // ... and whether that plan keeps every F(g)
-    std::vector<double> h_grid;     // the plan's copy (empty: the plan does not search)
-    std::vector<int32_t> h_grid_delay;   // [G][nelem] the plan's delay table
-    int grid_n = 0, grid_halo = 0;  // G and H = max |delay| of the plan
-    bool grid_map = false;          // the plan keeps the map
-    bool grid_valid = false;        // a pass of this plan has run the solve stage: the grid results are there
+    // ---- slowness-grid search of the beam F-statistic (beam_grid.hip) ----
     unsigned grid_attr_set = 0;     // the LDS forms of beam_grid_kernel that have been given their dynamic LDS limit (bit taps / 2)
     dev_buf<double> d_grid;         // [G][2]
     dev_buf<int32_t> d_grid_delay;  // [G][nelem]
-    // ---- fractional-sample steering of the beam and the grid (nbls_set_beam_interpolation, steer.h) ----
-    int want_steer_taps = 0;        // nbls_set_beam_interpolation: 0 / 4 / 6 / 8, read by the next nbls_plan
-    int steer_taps = 0;             // the plan's: its beam kernels interpolate with that many taps (0: whole samples)
-    int grid_taps = 0;              // ... and its grid search (steer_taps of a plan with a grid)
-    std::vector<double> h_grid_coef;    // [G][nelem][taps] the plan's coefficient table (h_grid_delay then holds floor(tau))
-    dev_buf<double> d_grid_coef;
+    dev_buf<double> d_grid_coef;    // [G][nelem][taps] (an interpolated grid)
     dev_buf<int32_t> d_grid_index;  // [B][VL]
     dev_buf<double> d_grid_fp;      // [2][B][VL]: grid_fstat | grid_power
     dev_buf<double> d_grid_map;     // [B][VL][G] (a plan that asked for the map)
-    // ---- Capon / Bartlett spectra of the narrow band's cross-spectral matrix (nbls_set_capon, capon.hip) ----
-    struct capon_request {
-        std::vector<double> grid;       // [G][2] slowness vectors (empty: off)
-        std::vector<double> freq;       // [nbands] Hz
-        std::vector<int32_t> ls, hs;    // [nbands] snapshot length and hop
-        double loading = 0.0;
-        int flags = 0;
-    };
-    capon_request want_capon;       // nbls_set_capon: read by the next nbls_plan
-    capon_request capon;            // the plan's copy
-    int capon_n = 0;                // G of the plan (0: the plan computes no spectra)
-    int capon_maxls = 0;            // the longest snapshot of the plan: the row length of h_capon_coef
-    double capon_loading = 0.0;
-    bool capon_maps = false, capon_csdm = false;    // the plan keeps both maps / the matrix R
+    // ---- Capon / Bartlett spectra (capon.hip) ----
     bool capon_attr_set = false;    // capon_kernel has been given its dynamic LDS limit on this handle's device
-    bool capon_valid = false;       // a pass of this plan has run the solve stage: the Capon results are there
     std::vector<int32_t> h_capon_par;   // [fbands][3]: Ls, Hs, K
     std::vector<double> h_capon_coef;   // [fbands][maxLs][2] snapshot coefficients (zeros beyond Ls_b)
     std::vector<double> h_capon_steer;  // [fbands][nelem][G][2] steering vectors, consecutive g side by side
@@ -200,17 +242,7 @@ struct nbls_handle {
     dev_buf<double> d_capon_power;  // [2][B][VL]: capon_power | bartlett_power
     dev_buf<double> d_capon_map;    // [2][B][VL][G] (a plan that asked for the maps)
     dev_buf<double> d_capon_csdm;   // [B][VL][N][N][2] (a plan that asked for R)
-    // ---- the K strongest peaks of either spectrum (nbls_set_capon_peaks, capon.hip; DESIGN.md section 19) ----
-    struct capon_peak_request {
-        std::vector<int32_t> nbr;       // [8][G] neighbour table of the request's cells (empty: off)
-        int k = 0;
-        double floor = 0.0;
-    };
-    capon_peak_request want_capon_peaks;    // nbls_set_capon_peaks: read by the next nbls_plan
-    int capon_peaks = 0;            // K of the plan (0: the plan picks no peaks)
-    double capon_peak_floor = 0.0;
-    int capon_peak_route = 0;       // the plan's route: 1 the unit's maps in LDS, 2 in HBM (its rows of d_capon_map, or a slab)
-    int capon_peak_slabs = 0;       // HBM route: slabs of d_capon_peak_slab = workgroups per launch
+    // ---- the K strongest peaks of either spectrum (capon.hip) ----
     bool capon_peak_attr_set[2] = {false, false};   // the two instances with peaks have their dynamic LDS limit
     dev_buf<int32_t> d_capon_nbr;           // [8][G]
     dev_buf<double> d_capon_peak_slab;      // [slabs][2][G] (HBM route of a plan without the maps)
@@ -223,28 +255,14 @@ struct nbls_handle {
     dev_buf<int32_t> d_capon_peak_index;    // [2][B][VL][K]
     dev_buf<double> d_capon_peak_power;     // [2][B][VL][K]
     dev_buf<double> d_capon_peak_offset;    // [2][B][VL][K][2]
-    // ---- the window's arrivals by CLEAN-SC (nbls_set_capon_clean, capon_clean.hip; DESIGN.md section 24) ----
-    struct capon_clean_request {
-        int iterations = 0;             // I (0: off)
-        double gain = 0.0, floor = 0.0;
-        int flags = 0;
-    };
-    capon_clean_request want_clean; // nbls_set_capon_clean: read by the next nbls_plan
-    capon_clean_request clean;      // the plan's copy (iterations 0: the plan launches no capon_clean_kernel)
+    // ---- the window's arrivals by CLEAN-SC (capon_clean.hip) ----
     bool clean_attr_set[2] = {false, false};    // the plain and the KEPT instance have their dynamic LDS limit
     dev_buf<int32_t> d_clean_count; // [B][VL]
     dev_buf<int32_t> d_clean_index; // [B][VL][I]
     dev_buf<double> d_clean_power;  // [B][VL][I]
     dev_buf<double> d_clean_tr;     // [2][B][VL]: total | residual
     dev_buf<double> d_clean_csdm;   // [B][VL][N][N][2] (NBLS_CLEAN_RESIDUAL)
-    // ---- the window's eigenvalues and MUSIC spectrum (nbls_set_capon_music, capon_music.hip; DESIGN.md section 25) ----
-    struct capon_music_request {
-        int sources = -1;               // M, 0: by eig_floor, -1: off
-        double eig_floor = 0.0, peak_floor = 0.0;
-        int flags = 0;
-    };
-    capon_music_request want_music; // nbls_set_capon_music: read by the next nbls_plan
-    capon_music_request music;      // the plan's copy (sources -1: the plan launches no capon_music_kernel)
+    // ---- the window's eigenvalues and MUSIC spectrum (capon_music.hip) ----
     bool music_attr_set[2] = {false, false};    // the plain and the peak instance have their dynamic LDS limit
     dev_buf<double> d_music_eig;    // [B][VL][N]
     dev_buf<int32_t> d_music_int;   // [3][B][VL]: sources | sweeps | index
@@ -258,34 +276,15 @@ struct nbls_handle {
     dev_buf<double> d_music_slab;           // [slabs][G] (a peak request on a plan without NBLS_MUSIC_MAP)
     hipEvent_t ev_music_slab = nullptr;     // behind the last launch that used the slabs
     hipStream_t music_slab_stream = nullptr;    // where ev_music_slab was recorded last (nullptr: nowhere yet)
-    // ---- the elements LTS kept (nbls_set_kept_elements, kept.hip; DESIGN.md section 20) ----
-    int want_kept_q = 0, want_kept_flags = 0;   // nbls_set_kept_elements: read by the next nbls_plan (q == 0: off)
-    int kept_q = 0;                 // min_pairs of the plan (0: the plan does not ask)
-    bool kept_beam = false, kept_capon = false;     // the plan's beam / spectra are those of the kept elements
-    bool kept_valid = false;        // a pass of this plan has run the solve stage: the mask and the count are there
+    // ---- the elements LTS kept (kept.hip) ----
     bool capon_kept_attr_set[3] = {false, false, false};    // the KEPT instances of capon_kernel have their dynamic LDS limit
     dev_buf<uint32_t> d_kept_mask;  // [B][VL] bit m: element m is dropped
     dev_buf<int32_t> d_kept_count;  // [B][VL] M
-    // ---- the beam trace of every result row (nbls_set_beam_trace, beam_trace.hip; DESIGN.md section 21) ----
-    bool want_bt = false;           // nbls_set_beam_trace: read by the next nbls_plan
-    std::vector<double> want_bt_win;    // ... its synthesis windows, band after band
-    double want_bt_min = 0.0;       // ... its MdCCM gate (NaN: off)
-    int want_bt_flags = 0;
-    bool bt = false;                // the plan forms the trace behind the pass's last solve
-    bool bt_kept = false;           // ... over the elements LTS kept in each window (NBLS_BEAM_TRACE_KEPT)
-    double bt_min = 0.0;
-    bool bt_valid = false;          // a pass of this plan has run the solve stage: d_bt holds the trace
+    // ---- the beam trace of every result row (beam_trace.hip) ----
     dev_buf<double> d_bt;           // [B][npts_pad]
     dev_buf<double> d_bt_win;       // the plan's synthesis windows
     dev_buf<int32_t> d_bt_off;      // [B] where the window of result row r starts in d_bt_win
-    // ---- each element's delay against the beam of the others (nbls_set_element_delays, element_delay.hip; DESIGN.md section 23) ----
-    bool want_ed = false;           // nbls_set_element_delays: read by the next nbls_plan
-    std::vector<int32_t> want_ed_K; // ... its max_shift, one per band
-    int want_ed_flags = 0;
-    bool ed = false;                // the plan measures the delays behind every solve of estimator 0
-    bool ed_kept = false;           // ... against the beam of the elements LTS kept (NBLS_ELEMENT_DELAY_KEPT)
-    bool ed_valid = false;          // a pass of this plan has run the solve stage: the three grids are there
-    size_t ed_lds = 0;              // dynamic LDS of the staged form (the largest row's block); 0: the global form
+    // ---- each element's delay against the beam of the others (element_delay.hip) ----
     bool ed_attr_set[4] = {false, false, false, false};   // the staged instances (plain, KEPT; x chunk) have their dynamic LDS limit
     dev_buf<int32_t> d_ed_K;        // [B] max_shift of the row's band
     dev_buf<double> d_ed_fp;        // [2][B][VL][N]: delay | cc
@@ -432,7 +431,7 @@ inline nbls_est_view nbls_view_of(const nbls_handle* h, const nbls_estimator& x)
     const bool own = x.kept_pair.empty();
     return {g, g + cells, g + 2 * cells, g + 3 * cells, x.d_res ? x.d_res + 4 * cells * sizeof(double) : nullptr,
             own ? h->d_lag : x.d_lag, own ? h->d_cmax : x.d_cmax,
-            h->refine ? (own ? h->d_lagfrac.p : x.d_lagfrac.p) : nullptr};       // (NULL: the solve reads tau = lag / fs)
+            h->req.refine ? (own ? h->d_lagfrac.p : x.d_lagfrac.p) : nullptr};       // (NULL: the solve reads tau = lag / fs)
 }
 // sub-sample fractions of the lags of units [u0, u0 + nu), behind their verifier (refine.hip; a plan with lag refinement)
 hipError_t nbls_launch_refine(nbls_handle* h, int64_t u0, int64_t nu, int gW, hipStream_t st);
@@ -516,7 +515,7 @@ hipError_t nbls_xcorr_screen_finish(nbls_handle* h, int64_t launches);
 // refinement, the lags' sub-sample fractions (refine.hip) behind the lag pick.
 inline hipError_t nbls_finish_lag_pick(nbls_handle* h, int64_t ub, int64_t nu, int gW) {
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !h->refine) return e;
+    if (e != hipSuccess || !h->req.refine) return e;
     return nbls_launch_refine(h, ub, nu, gW, h->stream);
 }
 // Kernel arguments of the two range-restricted correlators (xcorr_bounded.hip, xcorr_seeded.hip; their kernels share the

@@ -1419,7 +1419,7 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         hipLaunchKernelGGL(gather_pairs_kernel, dim3((unsigned)grid), dim3(GATHER_WAVES * 64), shm, st, (const int32_t*)h->d_lag,
                            (const double*)h->d_cmax, v.lag, v.cmax, (const int32_t*)s.d_kept_pair, (const int32_t*)h->d_unit_band,
                            (const int32_t*)h->d_unit_win, h->vector_len, P, Pc, (int)u0, (int)nu,
-                           h->refine ? (const double*)h->d_lagfrac : nullptr, v.frac);
+                           h->req.refine ? (const double*)h->d_lagfrac : nullptr, v.frac);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if ((e = solve_range_impl(h, s, v, u0, nu, st)) != hipSuccess) return e;
@@ -1434,21 +1434,23 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
         hipLaunchKernelGGL(uncertainty_kernel, dim3((unsigned)((nu + 63) / 64)), dim3(64), 0, st, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    const nbls_requests& r = h->req;
+    const bool own = &s == &h->est[0];      // the plan's own estimator: what works on the full array runs behind it, once per pass
     // the elements LTS dropped (nbls_set_kept_elements): from the plan's own estimator's weights, ahead of what may read them
-    if (h->kept_q > 0 && &s == &h->est[0] && (e = nbls_launch_kept_elements(h, u0, nu, st)) != hipSuccess) return e;
-    // each element's delay against the beam of the others (nbls_set_element_delays): estimator 0, behind the mask it may read
-    if (h->ed && &s == &h->est[0] && (e = nbls_launch_element_delays(h, u0, nu, st)) != hipSuccess) return e;
-    if (h->beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
-    if (h->closure && s.d_closure && (e = nbls_launch_closure(h, s, u0, nu, st)) != hipSuccess) return e;
-    // the slowness-grid search of a plan that asked for one: the full array only, behind the plan's own estimator (a plan
-    // with a lag seed has run it in the correlation stage, ahead of the seeded correlator: once per pass)
-    if (h->grid_n > 0 && h->seed.empty() && &s == &h->est[0] && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;
-    // the Capon / Bartlett spectra of a plan that asked for them (nbls_set_capon): the full array, once per pass
-    if (h->capon_n > 0 && &s == &h->est[0] && (e = nbls_launch_capon(h, u0, nu, st)) != hipSuccess) return e;
+    if (own && r.kept_q > 0 && (e = nbls_launch_kept_elements(h, u0, nu, st)) != hipSuccess) return e;
+    // each element's delay against the beam of the others (nbls_set_element_delays): behind the mask it may read
+    if (own && r.ed && (e = nbls_launch_element_delays(h, u0, nu, st)) != hipSuccess) return e;
+    if (r.beam && s.d_beam && (e = nbls_launch_beam(h, s, u0, nu, st)) != hipSuccess) return e;
+    if (r.closure && s.d_closure && (e = nbls_launch_closure(h, s, u0, nu, st)) != hipSuccess) return e;
+    // the slowness-grid search of a plan that asked for one (a plan with a lag seed has run it in the correlation stage,
+    // ahead of the seeded correlator)
+    if (own && h->derived.grid_n > 0 && r.seed.empty() && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;
+    // the Capon / Bartlett spectra of a plan that asked for them (nbls_set_capon)
+    if (own && h->derived.capon_n > 0 && (e = nbls_launch_capon(h, u0, nu, st)) != hipSuccess) return e;
     // ... and the CLEAN-SC components of a plan that asked for them (nbls_set_capon_clean), on the matrices it has just written
-    if (h->clean.iterations > 0 && &s == &h->est[0] && (e = nbls_launch_capon_clean(h, u0, nu, st)) != hipSuccess) return e;
+    if (own && r.clean.iterations > 0 && (e = nbls_launch_capon_clean(h, u0, nu, st)) != hipSuccess) return e;
     // ... and the eigenvalues and the MUSIC spectrum of a plan that asked for them (nbls_set_capon_music), on the same matrices
-    if (h->music.sources >= 0 && &s == &h->est[0] && (e = nbls_launch_capon_music(h, u0, nu, st)) != hipSuccess) return e;
+    if (own && r.music.sources >= 0 && (e = nbls_launch_capon_music(h, u0, nu, st)) != hipSuccess) return e;
     return pack_weights_of(h, s, u0, nu, st);
 }
 

@@ -1634,7 +1634,7 @@ hipError_t nbls_launch_xcorr_screen_range(nbls_handle* h, int64_t ub, int64_t ue
             hipLaunchKernelGGL(verify_kernel, dim3((a.nu * h->npairs + 3) / 4), dim3(256), 0, h->stream, a);
         // a plan with lag refinement: the sub-sample fractions of the batch's lags right behind their verifier (refine.hip;
         // inside this batch's verify interval)
-        if (h->refine && (e = nbls_launch_refine(h, u0, a.nu, gW, h->stream)) != hipSuccess) return e;
+        if (h->req.refine && (e = nbls_launch_refine(h, u0, a.nu, gW, h->stream)) != hipSuccess) return e;
         if (ev) (void)hipEventRecord(ev[3], h->stream);
         if (h->fuse_solve && (u0 + a.nu - solve_from >= kMinSolveUnits || u0 + a.nu >= ue)) {
             // the solve of the correlated units right behind them: on the same stream (their rows are complete, and on
