@@ -829,6 +829,62 @@ int nbls_fetch_capon_music_vectors(nbls_handle* h, double* E);
 int nbls_fetch_capon_music_peaks(nbls_handle* h, int32_t* count, int32_t* index, double* power, double* offset);
 int nbls_capon_music_lds_bytes(int32_t nelem);
 
+/* ---- A pass's windows grouped into detections: families ----
+ * Every other result describes one (band, window) cell.  A family (after PMCC, Cansi 1995) is a set of cells of one recording
+ * that neighbour each other in band and time and agree in back-azimuth and velocity: "this source, from about this
+ * back-azimuth, between these times, in these bands".  Pure integer logic and a handful of IEEE compares.
+ *   lattice   B bands, nseg recordings, result rows r = b * nseg + s, each a grid row of vector_len cells,
+ *             cell = r * vector_len + w.  Band b has window length W_b and hop inc_b; window w starts at sample
+ *             s0 = w * inc_b; its doubled centre is c2 = 2 * s0 + W_b (int64).
+ *   request   nbls_family_params.  mdccm_min finite; vel_min <= vel_max, both finite; sigma_tau_max (NaN: that gate is off);
+ *             baz_tol in [0, 180] degrees; vel_tol >= 0 km/s; band_reach in [0, 8]; time_reach in [1, 8]; min_pixels >= 1;
+ *             flags 0.  Anything else is NBLS_ERR_ARG and leaves the handle unchanged.
+ *   eligible  a cell with w < nwin[r]; vel, baz and mdccm finite; mdccm >= mdccm_min; vel_min <= vel <= vel_max; and, with
+ *             the gate on, sigma_tau <= sigma_tau_max (a NaN fails the gate).
+ *   link      two distinct eligible cells p = (b, s, w) and p' = (b', s', w') are linked iff
+ *             1. s == s' (recordings never link);
+ *             2. |b - b'| <= band_reach (band index of the plan);
+ *             3. |c2 - c2'| <= 2 * time_reach * max(inc_b, inc_b') in integer arithmetic: within one band |w - w'| <= time_reach;
+ *             4. d = |baz - baz'|, d = 360.0 - d if d > 180.0, then d <= baz_tol;  and |vel - vel'| <= vel_tol: plain
+ *                float64 subtract, abs and compare (built without contraction).
+ *   family    a connected component of the link graph with at least min_pixels cells; families are numbered 0 .. F - 1 in
+ *             ascending order of their smallest cell.
+ *   results   family [rows][vector_len] int32: the family id, -2 for an eligible cell whose component is too small, -1 for
+ *             everything else;  nfamilies = F;  table int64 [F][8]: count | first_cell (the smallest cell) | peak_cell (the
+ *             cell of the largest MdCCM, ties to the smallest cell; -0.0 == +0.0) | band_lo | band_hi | segment |
+ *             sample_first (min s0) | sample_end (max s0 + W_b).
+ * Everything is a function of the inputs alone: launch shape, batch seams and arrival order never change a bit.
+ *   nbls_set_families(h, params)   read by the next nbls_plan; NULL switches it off (the default: such a plan launches exactly
+ *                            what it launched before).  One launch sequence per pass, behind the last solve, on estimator 0's
+ *                            result grids.  nbls_plan returns NBLS_ERR_UNSUPPORTED with window ranges (nbls_set_window_ranges),
+ *                            with further estimators (nbls_set_estimators) and with an RCCL communicator; segments are
+ *                            supported; streamed result batches do not carry families.
+ *   nbls_fetch_families(h, family, nfamilies, table, capacity)   any pointer may be NULL; min(F, capacity) table rows are
+ *                            filled.  Waits for the pass as nbls_fetch_beam does; NBLS_ERR_STATE without the request; -1
+ *                            everywhere and F = 0 until a pass of the plan has run the solve stage.
+ *   nbls_label_families(h, params, nbands, nseg, vector_len, winlen, wininc, nwin, vel, baz, mdccm, sigma_tau, family,
+ *                            nfamilies, table, capacity)   the same kernels on grids the caller supplies (host pointers):
+ *                            winlen and wininc [nbands], nwin [nbands * nseg], the grids [nbands * nseg][vector_len],
+ *                            sigma_tau NULL iff the gate is off.  Uploads, labels and downloads synchronously on the handle's
+ *                            device; needs no plan and changes none.  NBLS_ERR_ARG for rows * vector_len >= 2^31, a
+ *                            non-positive winlen or wininc, nwin outside [0, vector_len], a sigma_tau that does not match
+ *                            the gate.
+ * families.hip: one thread per cell; a lock-free union-find (path halving, one compare-and-swap that hooks the larger root
+ * under the smaller) whose every access to the parent array is an agent-scope relaxed atomic; integer add / min / max on the
+ * root for the table; a three-kernel device-wide scan for the ids.  No wave waits for another.  nbls_timings is unchanged. */
+typedef struct {
+    double mdccm_min, vel_min, vel_max, sigma_tau_max, baz_tol, vel_tol;
+    int32_t band_reach, time_reach, min_pixels, flags;
+} nbls_family_params;
+#define NBLS_FAMILY_COLUMNS 8
+#define NBLS_FAMILY_MAX_REACH 8
+int nbls_set_families(nbls_handle* h, const nbls_family_params* params /* NULL = off */);
+int nbls_fetch_families(nbls_handle* h, int32_t* family, int32_t* nfamilies, int64_t* table, int64_t capacity);
+int nbls_label_families(nbls_handle* h, const nbls_family_params* params, int32_t nbands, int32_t nseg, int32_t vector_len,
+                        const int32_t* winlen, const int32_t* wininc, const int32_t* nwin, const double* vel, const double* baz,
+                        const double* mdccm, const double* sigma_tau /* NULL iff the gate is off */, int32_t* family,
+                        int32_t* nfamilies, int64_t* table, int64_t capacity);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

@@ -40,6 +40,7 @@ EXPORTS = [
     'nbls_set_beam_trace', 'nbls_fetch_beam_trace',
     'nbls_set_beam_interpolation', 'nbls_fetch_beam_grid_coefficients',
     'nbls_set_element_delays', 'nbls_fetch_element_delays', 'nbls_element_delay_lds_bytes',
+    'nbls_set_families', 'nbls_fetch_families', 'nbls_label_families',
 ]
 STEER_TAPS = (0, 4, 6, 8)  # taps of nbls_set_beam_interpolation (0: whole-sample delays)
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
@@ -58,6 +59,10 @@ KEPT_BEAM, KEPT_CAPON = 1, 2      # flags of nbls_set_kept_elements
 BEAM_TRACE_KEPT = 1      # flag of nbls_set_beam_trace
 ELEMENT_DELAY_KEPT = 1   # flag of nbls_set_element_delays (NBLS_ELEMENT_DELAY_KEPT)
 ELEMENT_DELAY_MAX_SHIFT = 256     # largest max_shift of a band (NBLS_ELEMENT_DELAY_MAX_SHIFT)
+FAMILY_COLUMNS = 8       # columns of a family table row (NBLS_FAMILY_COLUMNS)
+FAMILY_MAX_REACH = 8     # largest band_reach / time_reach of a family request (NBLS_FAMILY_MAX_REACH)
+# the columns of a family table row, in order
+FAMILY_FIELDS = ('count', 'first_cell', 'peak_cell', 'band_lo', 'band_hi', 'segment', 'sample_first', 'sample_end')
 MAX_ESTIMATORS = 8       # further estimators of one pass beside estimator 0 (NBLS_MAX_ESTIMATORS)
 
 NBLS_ERR_ARG, NBLS_ERR_STATE, NBLS_ERR_GEOMETRY = -1, -2, -3
@@ -83,6 +88,18 @@ class EstimatorDesc(C.Structure):
     _fields_ = [('lts', C.POINTER(LtsParams)), ('nkept', C.c_int32), ('kept', C.POINTER(C.c_int32)),
                 ('xij', C.POINTER(C.c_double)), ('pair_idx', C.POINTER(C.c_int32)), ('xpinv', C.POINTER(C.c_double)),
                 ('eig6', C.POINTER(C.c_double))]
+
+
+class FamilyParams(C.Structure):
+    _fields_ = [('mdccm_min', C.c_double), ('vel_min', C.c_double), ('vel_max', C.c_double), ('sigma_tau_max', C.c_double),
+                ('baz_tol', C.c_double), ('vel_tol', C.c_double), ('band_reach', C.c_int32), ('time_reach', C.c_int32),
+                ('min_pixels', C.c_int32), ('flags', C.c_int32)]
+
+
+def family_params(mdccm_min, vel_min, vel_max, sigma_tau_max, baz_tol, vel_tol, band_reach, time_reach, min_pixels):
+    """The request of ``nbls_set_families`` / ``nbls_label_families`` (``sigma_tau_max`` None: that gate is off)."""
+    return FamilyParams(float(mdccm_min), float(vel_min), float(vel_max), float('nan') if sigma_tau_max is None else float(sigma_tau_max),
+                        float(baz_tol), float(vel_tol), int(band_reach), int(time_reach), int(min_pixels), 0)
 
 
 class Timings(C.Structure):
@@ -218,6 +235,11 @@ def load_library(path=None):
     lib.nbls_set_element_delays.argtypes = [vp, ip, C.c_int32, C.c_int32]
     lib.nbls_fetch_element_delays.argtypes = [vp, dp, dp, ip]
     lib.nbls_element_delay_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    i64p = C.POINTER(C.c_int64)
+    lib.nbls_set_families.argtypes = [vp, C.POINTER(FamilyParams)]
+    lib.nbls_fetch_families.argtypes = [vp, ip, ip, i64p, C.c_int64]
+    lib.nbls_label_families.argtypes = [vp, C.POINTER(FamilyParams), C.c_int32, C.c_int32, C.c_int32, ip, ip, ip, dp, dp, dp, dp, ip, ip,
+                                        i64p, C.c_int64]
     lib.nbls_fetch_filtered.argtypes = [vp, C.c_int32, dp]
     lib.nbls_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.nbls_set_profiling.argtypes = [vp, C.c_int32]
@@ -636,6 +658,55 @@ class Handle:
         out = np.empty(self.npts)
         self._chk(self.lib.nbls_fetch_beam_trace(self._h, int(row), _dptr(out)))
         return out
+
+    def set_families(self, params=None):
+        """The next plans also group, behind the pass's last solve, the cells of estimator 0's result grids into families:
+        connected components of the eligible cells under the link of ``params`` (a ``FamilyParams``, see ``family_params``;
+        ``nbls_set_families``); None switches that off."""
+        self._chk(self.lib.nbls_set_families(self._h, None if params is None else C.byref(params)))
+
+    def _family_results(self, call, cells_shape, capacity):
+        family = np.empty(cells_shape, dtype=np.int32)
+        nfam = C.c_int32(0)
+        cap = family.size if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError('capacity must not be negative')
+        table = np.zeros((cap, FAMILY_COLUMNS), dtype=np.int64)
+        self._chk(call(_iptr(family), C.byref(nfam), table.ctypes.data_as(C.POINTER(C.c_int64)), cap))
+        return family, int(nfam.value), table[:min(int(nfam.value), cap)]
+
+    def fetch_families(self, capacity=None):
+        """-> (family int32 (rows, vector_len), nfamilies, table int64 (min(nfamilies, capacity), 8)); the columns of the
+        table are ``FAMILY_FIELDS``.  ``capacity`` None: every family."""
+        if capacity is None:                   # (one round trip for the count, then a table of that size)
+            nfam = C.c_int32(0)
+            self._chk(self.lib.nbls_fetch_families(self._h, None, C.byref(nfam), None, 0))
+            capacity = int(nfam.value)
+        return self._family_results(lambda f, n, t, c: self.lib.nbls_fetch_families(self._h, f, n, t, c),
+                                    (self.nbands, self.vector_len), capacity)
+
+    def label_families(self, params, nseg, winlen, wininc, nwin, vel, baz, mdccm, sigma_tau=None, capacity=None):
+        """The families of grids the caller has (``nbls_label_families``): ``winlen`` / ``wininc`` (nbands,), ``nwin``
+        (nbands * nseg,), the grids (nbands * nseg, vector_len), ``sigma_tau`` None exactly when ``params`` has no gate.
+        The same kernels as a plan with ``set_families``; needs no plan and changes none.  -> as ``fetch_families``
+        (``capacity`` None: room for every family the lattice can hold)."""
+        winlen = np.ascontiguousarray(winlen, dtype=np.int32).reshape(-1)
+        wininc = np.ascontiguousarray(wininc, dtype=np.int32).reshape(-1)
+        nwin = np.ascontiguousarray(nwin, dtype=np.int32).reshape(-1)
+        vel, baz, mdccm = _f64(vel), _f64(baz), _f64(mdccm)
+        sig = None if sigma_tau is None else _f64(sigma_tau)
+        rows = winlen.size * int(nseg)
+        if vel.ndim != 2 or vel.shape[0] != rows or wininc.size != winlen.size or nwin.size != rows:
+            raise ValueError('label_families: the grids must be (nbands * nseg, vector_len), nwin one entry per row')
+        for g in (baz, mdccm, sig):
+            if g is not None and g.shape != vel.shape:
+                raise ValueError('label_families: the grids must have one shape')
+        if capacity is None:
+            capacity = vel.size // max(int(params.min_pixels), 1)
+        return self._family_results(
+            lambda f, n, t, c: self.lib.nbls_label_families(self._h, C.byref(params), winlen.size, int(nseg), vel.shape[1], _iptr(winlen),
+                                                            _iptr(wininc), _iptr(nwin), _dptr(vel), _dptr(baz), _dptr(mdccm), _dptr(sig),
+                                                            f, n, t, c), vel.shape, capacity)
 
     def set_element_delays(self, max_shift=None, kept=False):
         """The next plans also measure, behind every unit's solve, each element's delay against the beam of the others:

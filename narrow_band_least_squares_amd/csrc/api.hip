@@ -924,6 +924,16 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
             o += a.winlen[b] > 0 ? a.winlen[b] : 0;
         }
     }
+    if (w.fam) {                     // the families (nbls_set_families): estimator 0's rows, every window of every band
+        if (!h->win_first.empty())
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the families (nbls_set_families) are not supported with window ranges (nbls_set_window_ranges): a slice of the windows does not cover the lattice");
+        if (h->nest > 0)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the families (nbls_set_families) are not supported with further estimators (nbls_set_estimators)");
+        if (h->comm)
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the families (nbls_set_families) are not supported with an RCCL communicator (the gathered block does not carry them)");
+        if ((int64_t)a.nbands * NS * (int64_t)a.vector_len >= ((int64_t)1 << 31))
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: the families (nbls_set_families) take fewer than 2^31 cells");
+    }
     size_t ed_lds = 0;
     if (w.ed) {                      // the element delays (nbls_set_element_delays): estimator 0, one max_shift per band
         if ((int)w.ed_K.size() != a.nbands)
@@ -1291,6 +1301,10 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = alloc_copy(h, h->d_bt_off, off.data(), off.size()))) return rc;
         if ((rc = ensure(h, h->d_bt, (size_t)a.R * (size_t)h->npts_pad * sizeof(double)))) return rc;
     }
+    if (h->req.fam) {                    // the families: the union-find's arrays and the three results
+        const hipError_t e = h->fam.grow((int64_t)a.R * a.vector_len, h->req.fam_par.min_pixels);
+        if (e != hipSuccess) return fail(h, NBLS_ERR_NOMEM, std::string("hipMalloc (nbls_set_families): ") + hipGetErrorString(e));
+    }
     if (h->req.ed) {                     // the element delays: every row's max_shift and the three grids
         const size_t vals = (size_t)a.R * a.vector_len * (size_t)a.E;
         std::vector<int32_t> kb((size_t)a.R);
@@ -1489,6 +1503,12 @@ int nbls_execute_stages(nbls_handle* h, int32_t stage_mask) {
     // the beam trace of a plan that asked for one (nbls_set_beam_trace): one launch behind the pass's last solve — per-batch
     // solves on the second stream have been joined into this one (nbls_xcorr_screen_finish) — and ahead of the closing event
     if ((stage_mask & 4) && h->req.bt) HIPCHK(h, nbls_launch_beam_trace(h, h->stream));
+    // the families of a plan that asked for them (nbls_set_families): likewise one launch sequence behind the last solve
+    if ((stage_mask & 4) && h->req.fam) {
+        const nbls_est_view v = nbls_view_of(h, h->est[0]);
+        HIPCHK(h, nbls_launch_families(h->req.fam_par, h->fam, h->nbands, h->nseg, h->vector_len, h->d_W, h->d_inc, h->d_nwin, v.vel, v.baz,
+                                       v.mdccm, v.sig, h->stream));
+    }
     if (h->prof) { HIPCHK(h, hipEventRecord(h->ev[3], h->stream)); h->ev_valid = true; }
     // streamed results of a pass that was not cut into batches (general correlators, stage subsets, no units): ONE batch
     if (h->stream_results && h->rbatches.empty()) HIPCHK(h, nbls_queue_result_batch(h, 0, h->nunits, h->stream));
@@ -1778,6 +1798,105 @@ int nbls_fetch_beam_trace(nbls_handle* h, int32_t row, double* out) {
     if (!h->solve_ran) { memset(out, 0, (size_t)h->npts * sizeof(double)); return NBLS_OK; }
     HIPCHK(h, copy_sync(h, out, h->d_bt + (size_t)row * h->npts_pad, (size_t)h->npts * sizeof(double), hipMemcpyDeviceToHost));
     return NBLS_OK;
+}
+
+// What is wrong with a family request (nbls_set_families, nbls_label_families); empty: nothing.
+static std::string family_params_error(const nbls_family_params& p) {
+    if (!std::isfinite(p.mdccm_min)) return "mdccm_min must be finite";
+    if (!std::isfinite(p.vel_min) || !std::isfinite(p.vel_max) || !(p.vel_min <= p.vel_max)) return "vel_min <= vel_max, both finite";
+    if (std::isinf(p.sigma_tau_max)) return "sigma_tau_max must be finite, or NaN for no gate";
+    if (!(p.baz_tol >= 0.0 && p.baz_tol <= 180.0)) return "baz_tol must lie in [0, 180]";
+    if (!(p.vel_tol >= 0.0) || std::isinf(p.vel_tol)) return "vel_tol must be finite and not negative";
+    if (p.band_reach < 0 || p.band_reach > NBLS_FAMILY_MAX_REACH) return "band_reach must lie in 0.." + std::to_string(NBLS_FAMILY_MAX_REACH);
+    if (p.time_reach < 1 || p.time_reach > NBLS_FAMILY_MAX_REACH) return "time_reach must lie in 1.." + std::to_string(NBLS_FAMILY_MAX_REACH);
+    if (p.min_pixels < 1) return "min_pixels must be at least 1";
+    if (p.flags != 0) return "unknown flags";
+    return std::string();
+}
+
+int nbls_set_families(nbls_handle* h, const nbls_family_params* params) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!params) { h->want.fam = false; h->want.fam_par = nbls_family_params{}; return NBLS_OK; }    // off: the next plan labels nothing
+    const std::string bad = family_params_error(*params);
+    if (!bad.empty()) return fail(h, NBLS_ERR_ARG, "nbls_set_families: " + bad);
+    h->want.fam = true;                      // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    h->want.fam_par = *params;
+    return NBLS_OK;
+}
+
+// The three results of a labelling of `cells` cells to the host; valid false: nothing has been labelled yet.
+static int fetch_family_results(nbls_handle* h, const nbls_family_work& wk, size_t cells, int min_pixels, bool valid, int32_t* family,
+                                int32_t* nfamilies, int64_t* table, int64_t capacity) {
+    if (!valid) {
+        if (family) for (size_t i = 0; i < cells; ++i) family[i] = -1;
+        if (nfamilies) *nfamilies = 0;
+        return NBLS_OK;
+    }
+    int32_t F = 0;
+    HIPCHK(h, copy_sync(h, &F, wk.nfam.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nfamilies) *nfamilies = F;
+    if (family) HIPCHK(h, copy_sync(h, family, wk.family.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t n = F < capacity ? F : capacity;
+    const int64_t have = (int64_t)nbls_family_table_rows_of((int64_t)cells, min_pixels);
+    if (n > have) n = have;
+    if (table && n > 0) HIPCHK(h, copy_sync(h, table, wk.table.p, (size_t)n * NBLS_FAMILY_COLUMNS * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return NBLS_OK;
+}
+
+int nbls_fetch_families(nbls_handle* h, int32_t* family, int32_t* nfamilies, int64_t* table, int64_t capacity) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_families: no plan");
+    if (!h->req.fam || !h->fam.family) return fail(h, NBLS_ERR_STATE, "nbls_fetch_families: nbls_set_families before nbls_plan");
+    if (table && capacity < 0) return fail(h, NBLS_ERR_ARG, "nbls_fetch_families: capacity must not be negative");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    // written behind the solve stage alone: nothing labelled until a pass of this plan has run it
+    return fetch_family_results(h, h->fam, (size_t)h->nbands * h->vector_len, h->req.fam_par.min_pixels, h->solve_ran, family, nfamilies,
+                                table, capacity);
+}
+
+int nbls_label_families(nbls_handle* h, const nbls_family_params* params, int32_t nbands, int32_t nseg, int32_t vector_len,
+                        const int32_t* winlen, const int32_t* wininc, const int32_t* nwin, const double* vel, const double* baz,
+                        const double* mdccm, const double* sigma_tau, int32_t* family, int32_t* nfamilies, int64_t* table,
+                        int64_t capacity) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!params || nbands < 1 || nseg < 1 || vector_len < 1 || !winlen || !wininc || !nwin || !vel || !baz || !mdccm)
+        return fail(h, NBLS_ERR_ARG, "nbls_label_families: bad argument");
+    const std::string bad = family_params_error(*params);
+    if (!bad.empty()) return fail(h, NBLS_ERR_ARG, "nbls_label_families: " + bad);
+    const bool gate = params->sigma_tau_max == params->sigma_tau_max;
+    if (gate != (sigma_tau != nullptr))
+        return fail(h, NBLS_ERR_ARG, "nbls_label_families: sigma_tau is given exactly when sigma_tau_max is not NaN");
+    if (table && capacity < 0) return fail(h, NBLS_ERR_ARG, "nbls_label_families: capacity must not be negative");
+    const int64_t rows = (int64_t)nbands * nseg, ncells = rows * vector_len;
+    if (ncells >= ((int64_t)1 << 31)) return fail(h, NBLS_ERR_ARG, "nbls_label_families: fewer than 2^31 cells are taken");
+    std::vector<int32_t> tabs((size_t)(3 * rows));
+    for (int64_t r = 0; r < rows; ++r) {
+        const int b = (int)(r / nseg);
+        if (winlen[b] < 1 || wininc[b] < 1)
+            return fail(h, NBLS_ERR_ARG, "nbls_label_families: window length and hop of band " + std::to_string(b) + " must be positive");
+        if (nwin[r] < 0 || nwin[r] > vector_len)
+            return fail(h, NBLS_ERR_ARG, "nbls_label_families: nwin of row " + std::to_string(r) + " is " + std::to_string(nwin[r]) +
+                                             ", not in 0.." + std::to_string(vector_len));
+        tabs[(size_t)r] = winlen[b];
+        tabs[(size_t)(rows + r)] = wininc[b];
+        tabs[(size_t)(2 * rows + r)] = nwin[r];
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    nbls_family_work& wk = h->fam_label;
+    const size_t cells = (size_t)ncells, ngrids = gate ? 4 : 3;
+    {
+        hipError_t e = wk.grow(ncells, params->min_pixels);
+        if (e == hipSuccess) e = wk.grids.grow(ngrids * cells * sizeof(double));
+        if (e == hipSuccess) e = wk.tabs.grow(tabs.size() * sizeof(int32_t));
+        if (e != hipSuccess) return fail(h, NBLS_ERR_NOMEM, std::string("hipMalloc (nbls_label_families): ") + hipGetErrorString(e));
+    }
+    const double* src[4] = {vel, baz, mdccm, sigma_tau};
+    for (size_t g = 0; g < ngrids; ++g)
+        HIPCHK(h, hipMemcpyAsync(wk.grids.p + g * cells, src[g], cells * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, copy_sync(h, wk.tabs.p, tabs.data(), tabs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(h, nbls_launch_families(*params, wk, (int)rows, nseg, vector_len, wk.tabs.p, wk.tabs.p + rows, wk.tabs.p + 2 * rows, wk.grids.p,
+                                   wk.grids.p + cells, wk.grids.p + 2 * cells, gate ? wk.grids.p + 3 * cells : nullptr, h->stream));
+    return fetch_family_results(h, wk, cells, params->min_pixels, true, family, nfamilies, table, capacity);
 }
 
 int nbls_set_element_delays(nbls_handle* h, const int32_t* max_shift, int32_t nbands, int32_t flags) {

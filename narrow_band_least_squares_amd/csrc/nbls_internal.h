@@ -167,6 +167,9 @@ struct nbls_requests {
     bool ed = false;                // the delays are measured behind every solve of estimator 0
     std::vector<int32_t> ed_K;      // ... its max_shift, one per band
     int ed_flags = 0;
+    // ---- the pass's windows grouped into families (nbls_set_families, families.hip) ----
+    bool fam = false;               // the cells are labelled behind the pass's last solve
+    nbls_family_params fam_par{};   // ... under this request
 
     // what the flags resolve to
     bool kept_beam() const { return kept_q > 0 && (kept_flags & NBLS_KEPT_BEAM); }      // the beam is that of the kept elements
@@ -189,6 +192,22 @@ struct nbls_plan_derived {
     int peak_route = 0;                     // a peak request's route: 1 the unit's maps in LDS, 2 in HBM (its rows of d_capon_map, or a slab)
     int peak_slabs = 0;                     // HBM route: slabs of d_capon_peak_slab = workgroups per launch
     size_t ed_lds = 0;                      // dynamic LDS of the staged element-delay form (the largest row's block); 0: the global form
+};
+
+// Device side of one labelling of a lattice into families (families.hip): the union-find's parent array, the records the
+// roots accumulate, the scan's block sums and the three results.  The handle holds two: the plan's and that of
+// nbls_label_families, which also keeps the caller's grids and window tables here.
+struct nbls_family_work {
+    struct ptrs { int32_t *parent, *count, *band_hi, *peak, *fid; unsigned long long *smin, *smax, *key; int32_t* sums; };
+    dev_buf<int32_t> parent, count, band_hi, peak, fid;    // [cells]: root or -1 | members | highest band | peak cell | family id (at the root)
+    dev_buf<unsigned long long> smin, smax, key;           // [cells]: min s0 | max s0 + W | image of the largest MdCCM (at the root)
+    dev_buf<int32_t> sums;                                 // [ceil(cells / 256)]
+    dev_buf<int32_t> family;                               // [cells]
+    dev_buf<int64_t> table;                                // [cells / min_pixels][8]
+    dev_buf<int32_t> nfam;                                 // [1]
+    dev_buf<double> grids;                                 // nbls_label_families: [4][cells] vel | baz | mdccm | sigma_tau
+    dev_buf<int32_t> tabs;                                 // ... [3][rows] W | inc | nwin
+    hipError_t grow(int64_t ncells, int min_pixels);       // everything but grids and tabs; contents are not kept
 };
 
 struct nbls_handle {
@@ -289,6 +308,9 @@ struct nbls_handle {
     dev_buf<int32_t> d_ed_K;        // [B] max_shift of the row's band
     dev_buf<double> d_ed_fp;        // [2][B][VL][N]: delay | cc
     dev_buf<int32_t> d_ed_shift;    // [B][VL][N]
+    // ---- the pass's windows grouped into families (families.hip) ----
+    nbls_family_work fam;           // the plan's labelling
+    nbls_family_work fam_label;     // nbls_label_families' own: it changes nothing of a plan
 
     // ---- streamed results (nbls_stream_results): a pinned host mirror of the result block, filled batch by batch ----
     bool stream_results = false;
@@ -457,6 +479,14 @@ __host__ __device__ inline uint32_t nbls_kept_bits_of(uint32_t dropped, int N, i
 // the beam trace of every result row at the slowness estimator 0 has solved for its windows: one launch per pass, behind
 // the last solve (beam_trace.hip)
 hipError_t nbls_launch_beam_trace(nbls_handle* h, hipStream_t st);
+// the families of a lattice of rows x vector_len cells (row r: band r / nseg of recording r % nseg; d_W, d_inc, d_nwin per
+// row) from its four grids, into wk.family / wk.nfam / wk.table: eight launches on st (families.hip).  In a pass: once,
+// behind the last solve, on estimator 0's result grids
+hipError_t nbls_launch_families(const nbls_family_params& p, nbls_family_work& wk, int rows, int nseg, int vector_len,
+                                const int32_t* d_W, const int32_t* d_inc, const int32_t* d_nwin, const double* vel, const double* baz,
+                                const double* mdccm, const double* sig, hipStream_t st);
+// rows of the device table of a labelling: no lattice of ncells cells has more families of min_pixels cells
+size_t nbls_family_table_rows_of(int64_t ncells, int min_pixels);
 // each element's delay against the beam of the others in units [u0, u0 + nu), at the slowness estimator 0 has solved for
 // them; behind nbls_launch_kept_elements, whose mask the KEPT form reads (element_delay.hip)
 hipError_t nbls_launch_element_delays(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);

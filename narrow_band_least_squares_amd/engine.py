@@ -10,7 +10,7 @@ import threading
 
 import numpy as np
 
-from . import planner
+from . import _hip, planner
 from ._hip import Handle
 from .stream import start_datenum
 
@@ -671,8 +671,8 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
            subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None, capon_clean=None, capon_music=None, element_delays=None, element_delays_kept=False, beam_trace=None,
-           beam_taps=0):
+           kept=None, capon_clean=None, capon_music=None, families=None, element_delays=None, element_delays_kept=False,
+           beam_trace=None, beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
@@ -703,7 +703,9 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
     ``planner.element_shifts``; for this plan only).  ``capon_clean``: ``(iterations, gain, floor, residual)`` of
     ``Handle.set_capon_clean``: the plan also resolves every window's arrivals by CLEAN-SC (needs ``capon``; likewise).
     ``capon_music``: ``(sources, eig_floor, maps, vectors, peaks, peak_floor)`` of ``Handle.set_capon_music``: the plan also returns every window's
-    eigenvalues and MUSIC spectrum (needs ``capon``; likewise)."""
+    eigenvalues and MUSIC spectrum (needs ``capon``; likewise).  ``families``: the request dict of
+    ``planner.check_families``: the plan also groups the cells of its rows into families behind its last solve
+    (``Handle.set_families``; likewise)."""
     if upload:
         if trace_ready:
             pass
@@ -756,6 +758,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon_clean(*capon_clean)
         if capon_music is not None:
             h.set_capon_music(*capon_music)
+        if families is not None:
+            h.set_families(_hip.family_params(**families))
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
     finally:
@@ -781,6 +785,8 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
             h.set_capon_clean(0)
         if capon_music is not None:
             h.set_capon_music(None)
+        if families is not None:
+            h.set_families(None)
         if kept is not None:
             h.set_kept_elements(0)
         if element_delays is not None:
@@ -943,6 +949,8 @@ def collect(res, h, b0, b1, streamed, note):
     if res.beam_trace is not None:
         for b in range(b0, b1):
             res.beam_trace[b] = h.fetch_beam_trace(b - b0)
+    if getattr(res, 'families_in_pass', False):          # (set where ONE pass covers every band of the call)
+        res.family, _, res.family_table = h.fetch_families()
     if not live:
         note.bands(b0, b1)
 
@@ -1132,6 +1140,46 @@ def _check_beam_trace(want, W, kept, window_slice=None):
     return list(np.split(table, cuts)), gate, bt_kept
 
 
+def _check_families(families, window_slice=None):
+    """``families`` of ``process`` / ``process_batch`` — None or a dict of ``planner.check_families``' arguments — -> the
+    checked request or None; ``ValueError`` before any GPU work."""
+    if families is None:
+        return None
+    if not isinstance(families, dict):
+        raise ValueError('families must be a dict of mdccm_min, baz_tol, vel_tol, vel_min, vel_max [, sigma_tau_max, band_reach, '
+                         'time_reach, min_pixels], not %r' % (families,))
+    try:
+        return planner.check_families(window_slice=window_slice, **families)
+    except TypeError as e:
+        raise ValueError('families: %s' % e)
+
+
+def label_result(h, res, par):
+    """``res.family`` / ``res.family_table`` of a ``BandBatch`` whose bands did not run in one pass: the kernels of the in-pass
+    request on the assembled grids (``Handle.label_families``)."""
+    gate = par['sigma_tau_max'] is not None
+    res.family, _, res.family_table = h.label_families(_hip.family_params(**par), 1, res.W, res.inc, res.nwin, res.vel, res.baz,
+                                                       res.mdccm, res.sigma_tau if gate else None)
+
+
+def split_families(family, table, nb, k, vector_len):
+    """The labelling of a pass over k recordings (rows b * k + s) -> per recording (family (nb, vector_len), table) as a
+    pass over that recording alone gives them: its families renumbered in their order, cells counted in its own lattice."""
+    family = family.reshape(nb, k, vector_len)
+    out = []
+    for j in range(k):
+        mine = np.flatnonzero(table[:, 5] == j)
+        new_id = np.full(len(table) + 2, -1, dtype=np.int32)        # [-2] and [-1] keep their meaning
+        new_id[-2] = -2
+        new_id[mine] = np.arange(len(mine), dtype=np.int32)
+        t = table[mine].copy()
+        for col in (1, 2):
+            t[:, col] = (t[:, col] // vector_len // k) * vector_len + t[:, col] % vector_len
+        t[:, 5] = 0
+        out.append((np.ascontiguousarray(new_id[family[:, j]]), t))
+    return out
+
+
 def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type=None,
             filter_order=None, filter_ripple=None, vector_len=None, device=None, xcorr_impl=0,
             want_lag=False, want_cmax=False, want_z=False, prefiltered=False, handle=None,
@@ -1139,8 +1187,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_uncert=False, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-            capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, capon_music=None, element_max_shift=None,
-            element_delays_kept=False, want_beam_trace=None, beam_taps=0):
+            capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, capon_music=None, families=None,
+            element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -1222,6 +1270,11 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     ``_offset``, the K strongest local maxima of the MUSIC spectrum as ``capon_peaks`` returns a spectrum's, kept from
     ``peak_floor`` times its maximum (``nbls_set_capon_music``).  ``ValueError`` before any GPU work
     (``planner.check_capon_music``); not with ``kept=(.., .., True)``; ``process_segmented`` refuses it with the Capon spectra.
+    families = a dict of ``planner.check_families``' arguments: also ``res.family`` (nbands, vector_len) int32 and
+    ``res.family_table`` (F, 8) int64, the cells grouped into families (``nbls_set_families``): labelled on
+    the GPU behind the last solve where one pass covers every band, else (band groups, HBM rounds, the time-segmented path) by
+    the same kernels on the assembled grids (``label_result``) — the same arrays either way.  ``ValueError`` before any GPU
+    work.
 
     In this order:
     1. the trace starts going up on a helper thread (``start_upload``; not for a ``handle`` of the caller's, ``upload=False``
@@ -1254,6 +1307,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     kept = _check_kept(nchans, kept, want_beam, capon)
     clean = _check_capon_clean(capon_clean, capon)
     music = _check_capon_music(nchans, capon_music, capon, kept)
+    fam = _check_families(families, window_slice)
     shifts = _check_element_delays(element_max_shift, element_delays_kept, len(band_edges), nchans, kept)
     trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
         want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
@@ -1270,10 +1324,13 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         W, inc, nwin, vector_len = plan_windows(npts, fs, winlens, winover, vector_len)
         check_elements(nchans, alpha)
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
-            return process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
-                                     filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                     group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency,
-                                     shifts, None if trace is None else want_beam_trace, beam_taps=beam_taps)
+            res = process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
+                                    filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
+                                    group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency,
+                                    shifts, None if trace is None else want_beam_trace, beam_taps=beam_taps)
+            if fam is not None:
+                label_result(res.handle if getattr(res, 'handle', None) is not None else get_handle(device, 0), res, fam)
+            return res
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
         res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
                          want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
@@ -1283,6 +1340,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                          want_clean_csdm=clean is not None and clean[3], want_music=music is not None,
                          want_music_maps=music is not None and music[2], want_music_vectors=music is not None and music[3],
                          want_music_peaks=music is not None and music[4])
+        res.families_in_pass = fam is not None and len(bounds) == 1      # (one pass covers every band: the in-pass request)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
@@ -1290,7 +1348,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
                                  window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
                                  subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
                                  lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, capon_music=music,
-                                 element_delays=shifts,
+                                 families=fam if res.families_in_pass else None, element_delays=shifts,
                                  element_delays_kept=bool(element_delays_kept), beam_trace=trace, beam_taps=beam_taps)
     finally:
         if up is not None:
@@ -1303,6 +1361,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     note.replay()
     for h, b0, b1 in launched:
         collect(res, h, b0, b1, streamed, note)
+    if fam is not None and not res.families_in_pass:
+        label_result(res.handle, res, fam)
     return res
 
 
@@ -1525,8 +1585,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None, capon_clean=None, capon_music=None, element_max_shift=None, element_delays_kept=False,
-                  want_beam_trace=None, beam_taps=0):
+                  kept=None, capon_clean=None, capon_music=None, families=None, element_max_shift=None,
+                  element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for
     recording s alone (bit for bit: the kernels see the same per-row work).
@@ -1556,6 +1616,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     kept = _check_kept(nchans, kept, want_beam, capon)
     clean = _check_capon_clean(capon_clean, capon)
     music = _check_capon_music(nchans, capon_music, capon, kept)
+    fam = _check_families(families)
     shifts = _check_element_delays(element_max_shift, element_delays_kept, nb, nchans, kept)
     trace = _check_beam_trace(want_beam_trace, prep.W, kept)
     tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
@@ -1581,6 +1642,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
             h.set_trace_rows([r for rec in recordings[s0:s0 + k] for r in rec], fs)
             cap = max(1, max_bands_per_pass(k * nchans, npts, k * tr))
             streamed = stream_pays(alpha, np.tile(prep.nwin, k), P)
+            fam_in_pass = fam is not None and cap >= nb       # (one pass covers every band of these recordings)
             for b0 in range(0, nb, cap):
                 b1 = min(nb, b0 + cap)
                 R = (b1 - b0) * k
@@ -1588,7 +1650,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                        beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
                        beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
                        closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, capon_music=music,
-                       element_delays=shifts, element_delays_kept=bool(element_delays_kept),
+                       families=fam if fam_in_pass else None, element_delays=shifts, element_delays_kept=bool(element_delays_kept),
                        beam_trace=trace, beam_taps=beam_taps)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
@@ -1612,6 +1674,10 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                 clr = h.fetch_capon_clean_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (clean is not None and clean[3]) else None
                 kel = [a.reshape(b1 - b0, k, VL) for a in h.fetch_kept_elements()] if kept is not None else None
                 eld = [a.reshape(b1 - b0, k, VL, nchans) for a in h.fetch_element_delays()] if shifts is not None else None
+                if fam_in_pass:
+                    family, _, table = h.fetch_families()
+                    for res, (f, t) in zip(out[s0:s0 + k], split_families(family, table, nb, k, VL)):
+                        res.family, res.family_table = f, t
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
@@ -1663,6 +1729,8 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     for res, t0 in zip(out, t0s):
         res.t = time_grid(t0, fs, prep.W, prep.inc, prep.nwin, VL)
         res.sos, res.pair_idx, res.xij, res.handle = list(prep.sos_ret), prep.pair_idx, prep.xij, h
+        if fam is not None and getattr(res, 'family', None) is None:     # (several rounds: the kernels on the assembled grids)
+            label_result(h, res, fam)
     return out
 
 

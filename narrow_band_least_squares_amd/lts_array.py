@@ -971,3 +971,67 @@ def ltsva_music_batch(streams, lat_list, lon_list, window_length, window_overlap
     results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
                                    want_uncert=True, **kw)
     return [_returns(res, nchans, alpha) + (_returns_music(res, grid, n=int(res.nwin[0])),) for res in results]
+
+
+def _families_keywords(nchans, alpha, params):
+    """The ``families`` keyword of ``engine.process`` behind the arguments of ``ltsva_families``; ``ValueError`` before any GPU
+    work."""
+    _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    return planner.check_families(**params)
+
+
+def _returns_families(res, fs, t0):
+    n = int(res.nwin[0])
+    return res.family[0, :n].copy(), planner.family_table(res.family, res.family_table, res.vel, res.baz, res.mdccm, res.sigma_tau,
+                                                          [(np.nan, np.nan)], res.W, res.inc, fs, t0)
+
+
+def ltsva_families(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, *, mdccm_min, baz_tol, vel_tol,
+                   vel_min, vel_max, sigma_tau_max=None, band_reach=1, time_reach=1, min_pixels=4):
+    """``ltsva`` followed by ``family_array`` (nwin,) int32 and ``families``: the windows grouped into detections — runs of
+    windows at most ``time_reach`` apart that pass the gates (``mdccm_min``, ``vel_min`` .. ``vel_max``, ``sigma_tau_max``) and
+    agree with their neighbours within ``baz_tol`` degrees and ``vel_tol`` km/s, at least ``min_pixels`` windows long;
+    ``narrow_band_least_squares_families`` has the details (one band here: ``band_reach`` plays no part; ``f_lo`` / ``f_hi``
+    are NaN), DESIGN.md section 26 the definition.  ``ValueError`` before any GPU work for what the library refuses."""
+    data, fs, t0 = engine.stream_rows(st)
+    nchans = len(data)
+    par = _families_keywords(nchans, alpha, dict(mdccm_min=mdccm_min, baz_tol=baz_tol, vel_tol=vel_tol, vel_min=vel_min, vel_max=vel_max,
+                                                 sigma_tau_max=sigma_tau_max, band_reach=band_reach, time_reach=time_reach,
+                                                 min_pixels=min_pixels))
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+
+    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
+        if alpha < 1.0:
+            res.keys = engine.time_keys(res.t, res.nwin)
+
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, families=par)
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + _returns_families(res, fs, t0)
+
+
+def ltsva_families_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, *, mdccm_min, baz_tol,
+                         vel_tol, vel_min, vel_max, sigma_tau_max=None, band_reach=1, time_reach=1, min_pixels=4):
+    """``ltsva_families`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 10-tuples,
+    element i equal to ``ltsva_families(streams[i], ...)``; the streams as for ``ltsva_batch``."""
+    params = dict(mdccm_min=mdccm_min, baz_tol=baz_tol, vel_tol=vel_tol, vel_min=vel_min, vel_max=vel_max, sigma_tau_max=sigma_tau_max,
+                  band_reach=band_reach, time_reach=time_reach, min_pixels=min_pixels)
+    streams = list(streams)
+    if not streams:
+        planner.check_families(**params)
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    nchans = len(recs[0])
+    par = _families_keywords(nchans, alpha, params)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [ltsva_families(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, **params)]
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    if alpha == 1.0:
+        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, families=par)
+    return [_returns(res, nchans, alpha) + _returns_families(res, fs, t0) for res, t0 in zip(results, t0s)]

@@ -969,3 +969,99 @@ def narrow_band_least_squares_element_delays(WINLEN_list, WINOVER, ALPHA, st, la
         out.update(dropped_mask=res.dropped_mask, kept_count=res.kept_count)
     return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
                     w_array, h_array) + (out,)
+
+
+def _families_of(res, edges, fs, t0):
+    """(family_array, families) of a ``BandBatch`` with ``family`` / ``family_table``: the int32 grid and the per-family
+    summary of ``planner.family_table`` (the table's own columns among it)."""
+    return res.family, planner.family_table(res.family, res.family_table, res.vel, res.baz, res.mdccm, res.sigma_tau, edges, res.W,
+                                            res.inc, fs, t0)
+
+
+def narrow_band_least_squares_families(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                       mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max=None, band_reach=1,
+                                       time_reach=1, min_pixels=4):
+    """``narrow_band_least_squares`` followed by ``family_array`` (NBANDS, vector_len) int32 and ``families``: the (band,
+    window) cells grouped into detections, as PMCC groups its pixels into families (the definition is
+    in include/nbls.h).  A cell is eligible with ``mdccm >= mdccm_min``, ``vel_min <= vel <= vel_max`` and, where
+    ``sigma_tau_max`` is given, ``sigma_tau <= sigma_tau_max``; two eligible cells are linked when their bands are at most
+    ``band_reach`` apart, their window centres at most ``time_reach`` hops of the coarser band apart, their back-azimuths
+    within ``baz_tol`` degrees (across 0 / 360) and their velocities within ``vel_tol`` km/s; a family is a connected component
+    of at least ``min_pixels`` cells.  ``family_array`` holds the family id, -2 for an eligible cell of a smaller component
+    and -1 elsewhere; ``families`` is the dict of ``planner.family_table`` (one entry per family: count, start and end,
+    frequency range, circular mean and spread of the back-azimuth, velocity, MdCCM, the peak cell) with the raw table columns
+    (``planner.FAMILY_FIELDS``).  Single linkage: a family can drift along a chain of cells that each agree with the next.
+    Labelled on the GPU behind the pass's last solve; a call whose bands run in several passes is labelled by the same
+    kernels on the assembled grids, with the same result.  ``ValueError`` before any GPU work for what the library refuses."""
+    par = planner.check_families(mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max, band_reach, time_reach, min_pixels)
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands],
+                                       process_keywords=lambda *a: dict(families=par))
+    _, fs, t0 = engine.stream_rows(st)
+    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                    w_array, h_array) + _families_of(res, _band_edges(freqlist, FREQ_BAND_TYPE, bands), fs, t0)
+
+
+def narrow_band_least_squares_families_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                             FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                             mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max=None, band_reach=1,
+                                             time_reach=1, min_pixels=4):
+    """``narrow_band_least_squares_families`` over several recordings of ONE array in one GPU pass -> a list of its 11-tuples,
+    element i equal to the single call on ``streams[i]``; the streams as for ``narrow_band_least_squares_batch``.  Recordings
+    never link: every recording has its own families, numbered from 0."""
+    par = planner.check_families(mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max, band_reach, time_reach, min_pixels)
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [narrow_band_least_squares_families(WINLEN_list, WINOVER, ALPHA, streams[0], lat_list, lon_list, NBANDS, w, h,
+                                                   freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                                   FILTER_RIPPLE, rij=rij, **par)]
+    vector_len = _vector_len(WINLEN_list, WINOVER, streams[0])
+    _check_response_rows(w, h, freq_resp_list)
+    nchans = len(recs[0])
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    bands = list(range(NBANDS))
+    edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
+    winlens = [WINLEN_list[ii] for ii in bands]
+    results = engine.process_batch(recs, fs, t0s, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
+                                   FILTER_RIPPLE, vector_len=vector_len, families=par)
+    w_rows, h_rows = filter_responses(results[0].sos, freq_resp_list, fs)
+    _bt_cautions(winlens, edges)
+    prefixes = [_band_prefix(ii + 1) for ii in bands]
+    out = []
+    for res, t0 in zip(results, t0s):
+        stdict_all = None
+        if ALPHA != 1.0:
+            keys = engine.time_key_text(res.t, res.nwin, prefixes)
+            stdict_all = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, res.nchans, keys)
+        out.append(_returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, stdict_all, res.nwin,
+                            w_rows.copy(), h_rows.copy()) + _families_of(res, edges, fs, t0))
+    return out
+
+
+def label_families(vel, baz, mdccm, sigma_tau, nwin, winlens, incs, *, nseg=1, device=None, **params):
+    """The families of result grids the caller already has (``nbls_label_families``): ``vel``, ``baz``, ``mdccm`` and
+    ``sigma_tau`` (None exactly when ``sigma_tau_max`` is not given) of shape (nbands * nseg, vector_len), row b * nseg + s band
+    b of recording s; ``nwin`` one entry per row; ``winlens`` / ``incs`` window length and hop of every band in samples;
+    ``params`` the request of ``narrow_band_least_squares_families`` (``planner.check_families``).  The same kernels as the
+    in-pass request, on the GPU: for the gathered result of ``narrow_band_least_squares_parallel``, the rows of another
+    estimator, or another detector's grid handed in as ``mdccm``.  -> (family int32 of the grids' shape, table int64 (F, 8),
+    columns ``planner.FAMILY_FIELDS``).  ``ValueError`` before any GPU work for what the library refuses."""
+    try:
+        par = planner.check_families(**params)
+    except TypeError as e:
+        raise ValueError('label_families: %s' % e)
+    args = planner.check_family_lattice(nseg, winlens, incs, nwin, vel, baz, mdccm, sigma_tau, par['sigma_tau_max'] is not None)
+    from ._hip import family_params
+    h = engine.get_handle(device, 0)
+    family, _, table = h.label_families(family_params(**par), args[0], args[1], args[2], args[3], args[4], args[5], args[6], args[7])
+    return family, table

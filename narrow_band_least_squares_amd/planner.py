@@ -917,3 +917,148 @@ def check_element_shifts(max_shift, nbands):
     if (k < 0).any() or (k > ELEMENT_DELAY_MAX_SHIFT).any():
         raise ValueError('max_shift must lie in 0..%d samples, not %r' % (ELEMENT_DELAY_MAX_SHIFT, max_shift))
     return np.ascontiguousarray(k, dtype=np.int32)
+
+
+FAMILY_MAX_REACH = 8      # largest band_reach / time_reach of a family request (NBLS_FAMILY_MAX_REACH)
+# the columns of a family table row (include/nbls.h), in order
+FAMILY_FIELDS = ('count', 'first_cell', 'peak_cell', 'band_lo', 'band_hi', 'segment', 'sample_first', 'sample_end')
+
+
+def _family_real(name, x):
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ValueError('%s must be a number, not %r' % (name, x))
+    return float(x)
+
+
+def _family_whole(name, x):
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+        raise ValueError('%s must be an integer, not %r' % (name, x))
+    return int(x)
+
+
+def check_families(mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max=None, band_reach=1, time_reach=1, min_pixels=1,
+                   window_slice=None, estimators=None, comm=False):
+    """Everything ``nbls_set_families`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> the request as
+    a dict of ``mdccm_min``, ``vel_min``, ``vel_max``, ``sigma_tau_max`` (None: that gate is off), ``baz_tol`` (degrees),
+    ``vel_tol`` (km/s), ``band_reach``, ``time_reach`` and ``min_pixels`` (DESIGN.md section 26).  ``mdccm_min`` finite;
+    ``vel_min <= vel_max``, both finite; ``sigma_tau_max`` None, NaN (both: no gate) or finite; ``baz_tol`` in [0, 180];
+    ``vel_tol`` >= 0 and finite; ``band_reach`` in 0..8; ``time_reach`` in 1..8; ``min_pixels`` >= 1.  A window slice, further
+    estimators and an RCCL communicator are refused for the in-pass request (``label_families`` covers them)."""
+    p = dict(mdccm_min=_family_real('mdccm_min', mdccm_min), vel_min=_family_real('vel_min', vel_min), vel_max=_family_real('vel_max', vel_max),
+             sigma_tau_max=None if sigma_tau_max is None else _family_real('sigma_tau_max', sigma_tau_max),
+             baz_tol=_family_real('baz_tol', baz_tol), vel_tol=_family_real('vel_tol', vel_tol), band_reach=_family_whole('band_reach', band_reach),
+             time_reach=_family_whole('time_reach', time_reach), min_pixels=_family_whole('min_pixels', min_pixels))
+    if not np.isfinite(p['mdccm_min']):
+        raise ValueError('mdccm_min must be finite')
+    if not (np.isfinite(p['vel_min']) and np.isfinite(p['vel_max']) and p['vel_min'] <= p['vel_max']):
+        raise ValueError('vel_min <= vel_max, both finite')
+    if p['sigma_tau_max'] is not None:
+        if np.isnan(p['sigma_tau_max']):
+            p['sigma_tau_max'] = None
+        elif np.isinf(p['sigma_tau_max']):
+            raise ValueError('sigma_tau_max must be finite, or None for no gate')
+    if not (0.0 <= p['baz_tol'] <= 180.0):
+        raise ValueError('baz_tol must lie in [0, 180] degrees')
+    if not (p['vel_tol'] >= 0.0) or np.isinf(p['vel_tol']):
+        raise ValueError('vel_tol must be finite and not negative')
+    if not (0 <= p['band_reach'] <= FAMILY_MAX_REACH):
+        raise ValueError('band_reach must lie in 0..%d' % FAMILY_MAX_REACH)
+    if not (1 <= p['time_reach'] <= FAMILY_MAX_REACH):
+        raise ValueError('time_reach must lie in 1..%d' % FAMILY_MAX_REACH)
+    if p['min_pixels'] < 1 or p['min_pixels'] >= 2 ** 31:
+        raise ValueError('min_pixels must be at least 1')
+    if window_slice is not None:
+        raise ValueError('families are not available for a slice of the windows (window_slice): it would not cover the lattice')
+    if estimators:
+        raise ValueError('families are not available with further estimators')
+    if comm:
+        raise ValueError('families are not available with an RCCL communicator (the gathered block does not carry them)')
+    return p
+
+
+def check_family_lattice(nseg, winlens, incs, nwin, vel, baz, mdccm, sigma_tau, gate):
+    """The arrays of ``label_families`` as ``nbls_label_families`` takes them -> (nseg, winlens, incs, nwin, vel, baz, mdccm,
+    sigma_tau), contiguous int32 / float64; ``ValueError`` for what the library refuses: grids that are not 2-D of one shape
+    with ``len(winlens) * nseg`` rows, 2^31 cells or more, a window length or hop below 1, ``nwin`` outside [0, vector_len],
+    a ``sigma_tau`` that does not match the gate."""
+    nseg = _family_whole('nseg', nseg)
+    winlens, incs, nwin = (np.asarray(a) for a in (winlens, incs, nwin))
+    for name, a in (('winlens', winlens), ('incs', incs), ('nwin', nwin)):
+        if a.ndim != 1 or a.dtype.kind not in 'iu':
+            raise ValueError('%s must be a 1-D array of integers' % name)
+    vel, baz, mdccm = (np.ascontiguousarray(g, dtype=np.float64) for g in (vel, baz, mdccm))
+    if nseg < 1 or len(winlens) < 1 or len(incs) != len(winlens):
+        raise ValueError('one window length and one hop per band, and at least one recording')
+    rows = len(winlens) * nseg
+    if vel.ndim != 2 or vel.shape[0] != rows or vel.shape[1] < 1 or baz.shape != vel.shape or mdccm.shape != vel.shape:
+        raise ValueError('vel, baz and mdccm must be (%d, vector_len) arrays of one shape' % rows)
+    if vel.size >= 2 ** 31:
+        raise ValueError('fewer than 2^31 cells are taken')
+    if (winlens < 1).any() or (incs < 1).any() or (winlens >= 2 ** 31).any() or (incs >= 2 ** 31).any():
+        raise ValueError('window lengths and hops must be positive')
+    if len(nwin) != rows or (nwin < 0).any() or (nwin > vel.shape[1]).any():
+        raise ValueError('nwin must have one entry per row, in 0..vector_len')
+    if gate != (sigma_tau is not None):
+        raise ValueError('sigma_tau is given exactly when sigma_tau_max sets a gate')
+    if sigma_tau is not None:
+        sigma_tau = np.ascontiguousarray(sigma_tau, dtype=np.float64)
+        if sigma_tau.shape != vel.shape:
+            raise ValueError('sigma_tau must have the shape of vel')
+    return (nseg, winlens.astype(np.int32), incs.astype(np.int32), nwin.astype(np.int32), vel, baz, mdccm, sigma_tau)
+
+
+def family_table(family, table, vel, baz, mdccm, sigma_tau, band_edges, winlens, incs, fs, starttime):
+    """The per-family summary of a labelling, on the host -> dict of arrays with one entry per family.
+
+    ``family`` (rows, vector_len) and ``table`` (F, 8) as ``label_families`` / a families call return them, the four grids of
+    the same lattice (``sigma_tau`` may be None), ``band_edges`` [(fmin, fmax)] and ``winlens`` / ``incs`` (samples) per band,
+    ``fs`` in Hz, ``starttime`` the recording's start as a date number (days, as ``res.t``), one for all or one per recording.
+    Members come in ascending cell order from a stable sort and every sum is ``np.add.reduceat`` over them.  Keys: ``count``;
+    ``t_start`` / ``t_end`` (seconds from the start: ``sample_first / fs``, ``sample_end / fs``) and ``t_start_datenum`` /
+    ``t_end_datenum``; ``f_lo`` / ``f_hi`` (the lower edge of ``band_lo``, the upper of ``band_hi``); ``baz_mean`` /
+    ``baz_std`` (circular, degrees: R = |mean e^{i baz}|, std = sqrt(-2 ln R)); ``vel_mean`` / ``vel_std`` (population);
+    ``mdccm_median`` / ``mdccm_peak``; ``peak_band`` / ``peak_window`` / ``peak_baz`` / ``peak_vel``; ``sigma_tau_median``
+    (NaN without ``sigma_tau``); and the table's own columns under their names (``FAMILY_FIELDS``)."""
+    family = np.asarray(family)
+    table = np.asarray(table, dtype=np.int64).reshape(-1, len(FAMILY_FIELDS))
+    rows, vl = family.shape
+    F = len(table)
+    flat = family.reshape(-1)
+    cells = np.flatnonzero(flat >= 0)
+    mem = cells[np.argsort(flat[cells], kind='stable')]
+    count = np.bincount(flat[cells], minlength=F)[:F] if F else np.zeros(0, dtype=np.int64)
+    if F and (len(mem) != count.sum() or (count != table[:, 0]).any() or (count < 1).any()):
+        raise ValueError('family and table do not describe the same labelling')
+    start = np.r_[0, np.cumsum(count)[:-1]].astype(np.int64) if F else np.zeros(0, dtype=np.int64)
+    g = lambda a: np.asarray(a, dtype=np.float64).reshape(-1)[mem]
+    mean = lambda x: np.add.reduceat(x, start) / count if F else np.zeros(0)
+
+    def median(x):
+        out = np.full(F, np.nan)
+        for k in range(F):
+            out[k] = np.median(x[start[k]:start[k] + count[k]])
+        return out
+    rad = np.deg2rad(g(baz))
+    c, s = mean(np.cos(rad)), mean(np.sin(rad))
+    R = np.minimum(np.hypot(c, s), 1.0)
+    v = g(vel)
+    vm = mean(v)
+    with np.errstate(divide='ignore'):
+        baz_std = np.rad2deg(np.sqrt(np.abs(-2.0 * np.log(R))))
+    edges = np.asarray(band_edges, dtype=np.float64).reshape(-1, 2)
+    t0 = np.broadcast_to(np.asarray(starttime, dtype=np.float64).reshape(-1), (max(1, rows // len(edges)),))
+    seg = table[:, 5]
+    peak = table[:, 2]
+    flatten = lambda a: np.asarray(a, dtype=np.float64).reshape(-1)
+    out = dict(count=table[:, 0].copy(), t_start=table[:, 6] / float(fs), t_end=table[:, 7] / float(fs),
+               f_lo=edges[table[:, 3], 0], f_hi=edges[table[:, 4], 1], baz_mean=np.rad2deg(np.arctan2(s, c)) % 360.0, baz_std=baz_std,
+               vel_mean=vm, vel_std=np.sqrt(np.maximum(mean((v - np.repeat(vm, count)) ** 2), 0.0)),
+               mdccm_median=median(g(mdccm)), mdccm_peak=flatten(mdccm)[peak], peak_band=(peak // vl) // (rows // len(edges)),
+               peak_window=peak % vl, peak_baz=flatten(baz)[peak], peak_vel=flatten(vel)[peak],
+               sigma_tau_median=median(g(sigma_tau)) if sigma_tau is not None else np.full(F, np.nan),
+               band_lo=table[:, 3].copy(), band_hi=table[:, 4].copy(), segment=seg.copy())
+    for k, name in enumerate(FAMILY_FIELDS):               # the table's own columns beside the summary
+        out.setdefault(name, table[:, k].copy())
+    out['t_start_datenum'] = t0[seg] + out['t_start'] / 86400.0
+    out['t_end_datenum'] = t0[seg] + out['t_end'] / 86400.0
+    return out

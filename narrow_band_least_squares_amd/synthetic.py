@@ -78,6 +78,33 @@ def plane_waves(rij, npts, fs, fmin, fmax, sources, snr_db=6.0, seed=SEED + 1):
     return out + 10.0 ** (-snr_db / 20.0) * rng.standard_normal((nchans, npts))
 
 
+def transient_waves(rij, npts, fs, sources, snr_db=6.0, seed=SEED + 1, ramp_s=1.0):
+    """(N, npts) traces of plane waves that each live in a time span and a frequency span: ``sources`` is a list of
+    ``(baz_deg, vel_kms, amplitude, t0_s, t1_s, fmin, fmax)``.  Each is an independent Gaussian signal band-limited to
+    [fmin, fmax] of unit variance times its amplitude, delayed across the array as ``plane_wave`` delays its one, and
+    switched on over [t0_s, t1_s] at the array's origin by a gate with raised-cosine ramps of ``ramp_s`` seconds inside the
+    span (the gate travels with the wave).  White noise of ``10 ** (-snr_db / 20)`` per element on top; an empty list gives
+    the noise alone."""
+    rng = np.random.default_rng(seed)
+    nchans = rij.shape[1]
+    freqs = np.fft.rfftfreq(npts, d=1.0 / fs)
+    t = np.arange(npts) / fs
+    out = np.zeros((nchans, npts))
+    for baz_deg, vel_kms, amp, t0, t1, fmin, fmax in sources:
+        baz = np.radians(baz_deg)
+        delays = (-np.array([np.sin(baz), np.cos(baz)]) @ rij) / vel_kms
+        spec = rng.standard_normal(len(freqs)) + 1j * rng.standard_normal(len(freqs))
+        spec[(freqs < fmin) | (freqs > fmax)] = 0.0
+        spec[0] = 0.0
+        spec = spec * (amp / np.fft.irfft(spec, n=npts).std())
+        ramp = max(float(ramp_s), 1.0 / fs)
+        for i in range(nchans):
+            ti = t - delays[i]
+            gate = np.clip(np.minimum(ti - t0, t1 - ti) / ramp, 0.0, 1.0)
+            out[i] += 0.5 * (1.0 - np.cos(np.pi * gate)) * np.fft.irfft(spec * np.exp(-2j * np.pi * freqs * delays[i]), n=npts)
+    return out + 10.0 ** (-snr_db / 20.0) * rng.standard_normal((nchans, npts))
+
+
 def make_stream(data, fs, starttime=17884.0729166667, lat=None, lon=None):
     """(N, npts) array -> duck-typed Stream (start time as a matplotlib date number;
     default 2018-12-19T01:45:00 as in example.py:46)."""
