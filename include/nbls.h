@@ -26,6 +26,22 @@
  * keeps no host pointer after a call returns; every function returns 0 on success or a
  * negative nbls_status; nbls_last_error() gives the message.  One handle = one GPU = one
  * host thread at a time.  All floating point is IEEE double.
+ *
+ * Amplitude.  The trace may be in any unit: no result depends on an absolute amplitude.  Every threshold below is a
+ * ratio (the floors of the peak, CLEAN-SC and MUSIC requests, the diagonal loading, the tie rule of the lag pick), the
+ * int8 screening quantises each channel window by its own max |x|, and no data-domain value is held in float.  So, as
+ * long as no sample and no window's sum of squares is subnormal and every product of two such sums is finite — samples
+ * within 2^+-100 of unit scale, the range the tests run, are far inside —
+ *   - multiplying every sample by 2^k leaves every lag, cmax, MdCCM, weight, slowness, F ratio, index, count, offset,
+ *     eigenvector and pseudo-spectrum unchanged bit for bit, multiplies the filtered samples and the beam trace by 2^k
+ *     exactly, and every power, cross-spectral matrix and eigenvalue by 2^(2k) exactly;
+ *   - negating every sample leaves everything unchanged and negates the filtered samples and the beam trace;
+ *   - a positive gain 2^(k_i) of its own on every channel leaves the lags and everything computed from them alone
+ *     unchanged (cmax, MdCCM, the sub-sample fractions, the solve, the confidence intervals, the closures, the dropped
+ *     elements, the families); beams, spectra and element delays weight the elements by their amplitude and change.  The
+ *     lags of a plan with a lag seed (nbls_set_lag_seed) start from a beam maximum and may change with them.
+ * Gains that are no powers of two give the same to rounding.  One window's results depend on no other window's
+ * amplitude, and one recording's of a batch on no other's (tests/test_gpu_scale.py).
  */
 #ifndef NBLS_H
 #define NBLS_H
