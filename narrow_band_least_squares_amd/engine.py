@@ -6,12 +6,16 @@ import functools
 import itertools
 import operator
 import os
+import contextlib
 import threading
+import types
 
 import numpy as np
 
 from . import _hip, planner
 from ._hip import Handle
+from .call_requests import (CLEAN_FIELDS, EXTRA_FIELDS, MUSIC_FIELDS, PEAK_FIELDS, RESULT_GROUPS, Requests,   # noqa: F401
+                            _check_beam_trace, _check_element_delays)       # (the last five: for the public calls' modules)
 from .stream import start_datenum
 
 try:                                   # C++ helpers for the stdict keys / dictionary (csrc/host_ext.cpp)
@@ -368,85 +372,29 @@ def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want
                want_music=False, want_music_maps=False, want_music_vectors=False, want_music_peaks=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
-    ``handle`` are the driver's to set.  ``lag_frac`` (the sub-sample fractions beside ``lag``) only for a refined pass whose
-    lags are wanted.  ``grid_points`` > 0: ``grid_index`` / ``grid_fstat`` / ``grid_power`` of a slowness-grid search over that
-    many points, and with ``want_grid_map`` its ``grid_map`` (nbands, vector_len, grid_points).  ``want_consistency``:
-    ``consistency`` / ``closure_max`` (nbands, vector_len) and ``element_consistency`` (nbands, vector_len, nchans), the
-    closure of the picked lags.  ``capon_points`` > 0: ``capon_index`` / ``capon_power`` / ``bartlett_index`` /
-    ``bartlett_power`` of the Capon spectra over that many points, with ``want_capon_maps`` ``capon_map`` / ``bartlett_map``
-    (nbands, vector_len, capon_points) and with ``want_capon_csdm`` ``capon_csdm`` (nbands, vector_len, nchans, nchans)
-    complex; with ``capon_peaks`` = K > 0 ``capon_peak_count`` (nbands, vector_len) int32, ``capon_peak_index`` (.., K) int32,
-    ``capon_peak_power`` (.., K), ``capon_peak_offset`` (.., K, 2) and the same four with ``bartlett_``; ``want_kept``:
-    ``dropped_mask`` (nbands, vector_len) uint32 and ``kept_count`` (nbands, vector_len) int32, the elements LTS dropped;
-    ``beam_trace_npts`` = npts > 0: ``beam_trace`` (nbands, npts), the beam trace of every band; ``want_element_delays``: ``element_delay`` /
-    ``element_cc`` (nbands, vector_len, nchans) and ``element_shift`` (likewise, int32), each element's delay against the
-    beam of the others; ``clean_iterations`` = I > 0 (with ``capon_points``): ``clean_count`` (nbands, vector_len) int32,
-    ``clean_index`` (.., I) int32, ``clean_power`` (.., I), ``clean_total`` and ``clean_residual`` (nbands, vector_len), the
-    CLEAN-SC components of every window, and with ``want_clean_csdm`` ``clean_csdm`` (nbands, vector_len, nchans, nchans)
-    complex, the matrix they leave; ``want_music`` (with ``capon_points``): ``music_eigenvalues`` (nbands, vector_len, nchans),
-    ``music_sources``, ``music_sweeps`` and ``music_index`` (nbands, vector_len) int32 and ``music_power`` (nbands, vector_len),
-    with ``want_music_maps`` ``music_map`` (nbands, vector_len, G) and with ``want_music_vectors`` ``music_vectors`` (nbands,
-    vector_len, nchans, nchans) complex, with ``want_music_peaks`` (and ``capon_peaks`` = K) ``music_peak_count`` (nbands,
-    vector_len) int32, ``music_peak_index`` (.., K) int32, ``music_peak_power`` (.., K) and ``music_peak_offset`` (.., K, 2); None
-    otherwise."""
+    ``handle`` are the driver's to set.  The keywords are what ``Requests.result_keywords`` makes of a call's requests; the
+    fields they bring are the rows of ``call_requests.RESULT_GROUPS`` and ``EXTRA_FIELDS`` that apply, each (nbands,
+    vector_len) + its trailing shape with N = ``nchans``, P pairs, G = ``grid_points``, C = ``capon_points``, K =
+    ``capon_peaks``, I = ``clean_iterations`` and T = ``beam_trace_npts`` (``beam_trace``: (nbands, T)); None otherwise
+    (``Requests.check`` says what each is)."""
+    want = types.SimpleNamespace(**locals())
     nb, P = len(nwin), nchans * (nchans - 1) // 2
-    CI = int(clean_iterations) if capon_points else 0
-    MU = bool(want_music) and bool(capon_points)
-    K = int(capon_peaks) if capon_points else 0
-    peaks = {}
-    MK = K if (bool(want_music) and bool(want_music_peaks)) else 0
-    peaks['music_peak_count'] = np.zeros((nb, vector_len), dtype=np.int32) if MK else None
-    peaks['music_peak_index'] = np.zeros((nb, vector_len, MK), dtype=np.int32) if MK else None
-    peaks['music_peak_power'] = np.zeros((nb, vector_len, MK)) if MK else None
-    peaks['music_peak_offset'] = np.zeros((nb, vector_len, MK, 2)) if MK else None
-    for which in ('capon', 'bartlett'):
-        peaks[which + '_peak_count'] = np.zeros((nb, vector_len), dtype=np.int32) if K else None
-        peaks[which + '_peak_index'] = np.zeros((nb, vector_len, K), dtype=np.int32) if K else None
-        peaks[which + '_peak_power'] = np.zeros((nb, vector_len, K)) if K else None
-        peaks[which + '_peak_offset'] = np.zeros((nb, vector_len, K, 2)) if K else None
-    cpi = np.zeros((2, nb, vector_len), dtype=np.int32) if capon_points else (None, None)
-    cpp = np.zeros((2, nb, vector_len)) if capon_points else (None, None)
-    cpm = np.zeros((2, nb, vector_len, capon_points)) if (capon_points and want_capon_maps) else (None, None)
-    clo = np.zeros((2, nb, vector_len)) if want_consistency else (None, None)
-    gfp = np.zeros((2, nb, vector_len)) if grid_points else (None, None)
+    size = dict(N=nchans, P=P, G=grid_points, C=capon_points, K=capon_peaks, I=clean_iterations, T=beam_trace_npts)
+    fields = {}
+
+    def allocate(on, rows, group):
+        for name, trailing, dtype in group:
+            fields[name] = np.zeros(rows + tuple(int(size.get(n, n)) for n in trailing), dtype=dtype) if on else None
+
+    for name, trailing, dtype in EXTRA_FIELDS:
+        allocate(getattr(want, 'want_' + name), (nb, vector_len), [(name, trailing, dtype)])
+    for g in RESULT_GROUPS:
+        for _, group in g.calls:
+            allocate(g.applies(want), (nb,) if g.per_row else (nb, vector_len), group)
     grids = np.zeros((4, nb, vector_len))
-    unc = np.zeros((2, nb, vector_len)) if want_uncert else (None, None)
-    beam = np.zeros((2, nb, vector_len)) if want_beam else (None, None)
-    return BandBatch(grids=grids, vel=grids[0], baz=grids[1], mdccm=grids[2], sigma_tau=grids[3], nwin=nwin.astype(int), t=None,
-                     mask=np.zeros((nb, vector_len, (P + 7) // 8), dtype=np.uint8),
-                     lag=np.zeros((nb, vector_len, P), dtype=np.int32) if want_lag else None,
-                     lag_frac=np.zeros((nb, vector_len, P)) if (want_lag and want_subsample) else None,
-                     cmax=np.zeros((nb, vector_len, P)) if want_cmax else None,
-                     z=np.zeros((nb, vector_len, 2)) if want_z else None, vel_uncert=unc[0], baz_uncert=unc[1],
-                     beam_power=beam[0], fstat=beam[1], consistency=clo[0], closure_max=clo[1],
-                     element_consistency=np.zeros((nb, vector_len, nchans)) if want_consistency else None,
-                     grid_index=np.zeros((nb, vector_len), dtype=np.int32) if grid_points else None, grid_fstat=gfp[0],
-                     grid_power=gfp[1],
-                     grid_map=np.zeros((nb, vector_len, grid_points)) if (grid_points and want_grid_map) else None, sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None,
-                     capon_index=cpi[0], bartlett_index=cpi[1], capon_power=cpp[0], bartlett_power=cpp[1],
-                     capon_map=cpm[0], bartlett_map=cpm[1],
-                     capon_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128)
-                     if (capon_points and want_capon_csdm) else None,
-                     dropped_mask=np.zeros((nb, vector_len), dtype=np.uint32) if want_kept else None,
-                     kept_count=np.zeros((nb, vector_len), dtype=np.int32) if want_kept else None,
-                     beam_trace=np.zeros((nb, int(beam_trace_npts))) if beam_trace_npts else None,
-                     element_delay=np.zeros((nb, vector_len, nchans)) if want_element_delays else None,
-                     element_cc=np.zeros((nb, vector_len, nchans)) if want_element_delays else None,
-                     element_shift=np.zeros((nb, vector_len, nchans), dtype=np.int32) if want_element_delays else None,
-                     clean_count=np.zeros((nb, vector_len), dtype=np.int32) if CI else None,
-                     clean_index=np.zeros((nb, vector_len, CI), dtype=np.int32) if CI else None,
-                     clean_power=np.zeros((nb, vector_len, CI)) if CI else None,
-                     clean_total=np.zeros((nb, vector_len)) if CI else None,
-                     clean_residual=np.zeros((nb, vector_len)) if CI else None,
-                     clean_csdm=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128) if (CI and want_clean_csdm) else None,
-                     music_eigenvalues=np.zeros((nb, vector_len, nchans)) if MU else None,
-                     music_sources=np.zeros((nb, vector_len), dtype=np.int32) if MU else None,
-                     music_sweeps=np.zeros((nb, vector_len), dtype=np.int32) if MU else None,
-                     music_index=np.zeros((nb, vector_len), dtype=np.int32) if MU else None,
-                     music_power=np.zeros((nb, vector_len)) if MU else None,
-                     music_map=np.zeros((nb, vector_len, capon_points)) if (MU and want_music_maps) else None,
-                     music_vectors=np.zeros((nb, vector_len, nchans, nchans), dtype=np.complex128) if (MU and want_music_vectors) else None,
-                     lts=alpha < 1.0, fs=fs, **peaks)
+    return BandBatch(grids=grids, nwin=nwin.astype(int), t=None, mask=np.zeros((nb, vector_len, (P + 7) // 8), dtype=np.uint8),
+                     sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None, lts=alpha < 1.0,
+                     fs=fs, **dict(zip(GRID_NAMES, grids)), **fields)
 
 
 def drain(h, streamed, grids, mask, b0, b1, batch_done=None):
@@ -533,48 +481,11 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
     global positions, (2) its windows go through the correlation + solve kernels in slices of consecutive windows
     (the ``ltsva`` entry of the device pass).  Same rows as the in-core pass up to the rounding of the carried filter
     states; HBM holds one segment / one window slice at a time.  The filtered band stays on the host and the windows reach
-    the GPU slice by slice, so the beam results of ``process`` (``want_beam``) are not available here: ``ValueError``; nor is
-    the sub-sample refinement of the lags (``want_subsample``), which reads the filtered band in HBM, nor the bounded lag
-    search (``min_velocity``), nor the slowness-grid search (``slowness_grid``), which reads the filtered band in HBM too,
-    nor the seeded lag search (``seed_halfwidths``), which rests on it, nor the closure of the picked lags
-    (``want_consistency``), which reads the lag table of a whole pass in HBM, nor the beam trace (``want_beam_trace``), which
-    reads the filtered band in HBM as the beam results do, nor the element delays (``element_max_shift``), likewise."""
-    if element_max_shift is not None:
-        raise ValueError('element_max_shift: a trace of %d x %d samples takes the time-segmented path (not even one filtered '
-                         'band fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the '
-                         'host: the element delays are not available there' % _shape_of(data))
-    if beam_taps:
-        raise ValueError('beam_taps: a trace of %d x %d samples takes the time-segmented path (not even one filtered band fits '
-                         'the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: fractional-'
-                         'sample steering is not available there' % _shape_of(data))
-    if want_beam_trace is not None:
-        raise ValueError('want_beam_trace: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
-                         'the beam trace is not available there' % _shape_of(data))
-    if want_consistency:
-        raise ValueError('want_consistency: a trace of %d x %d samples takes the time-segmented path (not even one filtered '
-                         'band fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which correlates the band slice by '
-                         'slice: closure results are not available there' % _shape_of(data))
-    if seed_halfwidths is not None:
-        raise ValueError('seed_halfwidths: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
-                         'the seeded lag search is not available there' % _shape_of(data))
-    if slowness_grid is not None:
-        raise ValueError('slowness_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
-                         'the slowness-grid search is not available there' % _shape_of(data))
-    if min_velocity is not None:
-        raise ValueError('min_velocity: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which correlates the band slice by slice: '
-                         'the bounded lag search is not available there' % _shape_of(data))
-    if want_subsample:
-        raise ValueError('want_subsample: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
-                         'sub-sample lag refinement is not available there' % _shape_of(data))
-    if want_beam:
-        raise ValueError('want_beam: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
-                         'beam results are not available there' % _shape_of(data))
+    the GPU slice by slice, so what reads the filtered band or the lag table of a whole pass in HBM is not available here:
+    every opt-in keyword of this signature is refused when it is given, ``ValueError`` (``Requests.segmented_refusal``)."""
+    Requests(beam=want_beam, subsample=want_subsample, lag_limits=min_velocity, beam_grid=slowness_grid,
+             lag_seed=seed_halfwidths, closure=want_consistency, element_delays=element_max_shift, beam_trace=want_beam_trace,
+             beam_taps=beam_taps).segmented_refusal(*_shape_of(data))        # (unchecked: only what is given matters)
     rows = [np.ascontiguousarray(r, dtype=np.float64) for r in data]
     nchans, npts = len(rows), len(rows[0])
     nb = len(band_edges)
@@ -608,7 +519,7 @@ def process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, a
             assert int(part.nwin[0]) == w1 - w0
             res.grids[:, b, w0:w1] = part.grids[:, 0]
             res.mask[b, w0:w1] = part.mask[0]
-            for name in ('lag', 'cmax', 'z'):
+            for name, _, _ in EXTRA_FIELDS:
                 if getattr(res, name) is not None:
                     getattr(res, name)[b, w0:w1] = getattr(part, name)[0]
         if group_done is not None:
@@ -669,43 +580,25 @@ def upload_trace(h, data, fs):
 
 
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
-           trace_ready=False, after=None, before_execute=None, stream=False, uncert=False, estimators=None, beam=False,
-           subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False, capon=None,
-           kept=None, capon_clean=None, capon_music=None, families=None, element_delays=None, element_delays_kept=False,
-           beam_trace=None, beam_taps=0):
+           trace_ready=False, after=None, before_execute=None, stream=False, requests=None, uncert=False, estimators=None,
+           beam=False, subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False,
+           capon=None, kept=None, capon_clean=None, capon_music=None, families=None, element_delays=None,
+           element_delays_kept=False, beam_trace=None, beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
     the same GPU that already holds this trace (device-to-device copy instead of a second upload).
     ``trace_ready``: the caller has already uploaded the trace to ``h`` (``upload_trace``).  ``after``: the handle
     of the band group queued before this one (``Handle.execute``).  ``before_execute()``: called between plan and
     execute (the caller joins its upload thread there).  ``estimators``: the further estimators of the pass
-    (``Handle.set_estimators``); a handle that still carries some from an earlier call is reset.  ``beam``: the plan also
-    computes beam power and F-statistic behind every solve (``Handle.set_beam``; for this plan only).  ``subsample``: the
-    plan refines the picked lags to sub-sample precision before the solve (``Handle.set_lag_refinement``; likewise).
-    ``lag_limits``: the plan searches the lag of pair k only within ``|lag| <= lag_limits[k]`` samples
-    (``Handle.set_lag_limits``, ``planner.lag_limits``; likewise).  ``beam_grid`` (G, 2): the plan also searches the beam
-    F-statistic of the full array over these slowness vectors, ``beam_grid_map``: and keeps every F(g)
-    (``Handle.set_beam_grid``; likewise).  ``lag_seed``: one half-width in samples per band of THIS plan (the bands
-    ``bands`` of the Prep, in their order): the plan searches every pair's lag only that near the delay the grid maximum
-    predicts (``Handle.set_lag_seed``, ``planner.seed_halfwidths``; needs ``beam_grid``; likewise).  ``closure``: the plan
-    also computes the closure of the picked lags behind every solve (``Handle.set_closure``; likewise).  ``capon``: a dict
-    of ``Handle.set_capon``'s arguments, ``freqs`` / ``snap_len`` / ``snap_hop`` one per band of the Prep: the plan also
-    computes the Capon spectra of its bands (likewise); with ``peaks`` = K > 0 in it also their K strongest peaks on the
-    lattice ``peak_cells`` above ``peak_floor`` (``Handle.set_capon_peaks``; likewise).  ``kept``: ``(min_pairs, beam,
-    capon)`` of ``Handle.set_kept_elements``: the plan also names the elements LTS dropped and forms its beam results / Capon
-    spectra over the kept ones (likewise).  ``beam_trace``: ``(windows, mdccm_min, kept)`` — one synthesis window per band
-    of the Prep, the MdCCM gate (NaN: off) and the kept flag of ``Handle.set_beam_trace``: the plan also forms the beam
-    trace of its rows behind its last solve (for this plan only).  ``beam_taps`` 4, 6 or 8: the plan steers its beam and its
-    slowness grid at fractional-sample delays with that many Lagrange taps (``Handle.set_beam_interpolation``; likewise)
-    and needs ``beam`` or ``beam_grid``; 0: whole-sample delays.  ``element_delays``: one shift range in samples per band
-    of the Prep: the plan also measures each element's delay against the beam of the others behind every solve, with
-    ``element_delays_kept`` against the beam of the elements LTS kept, which needs ``kept`` (``Handle.set_element_delays``,
-    ``planner.element_shifts``; for this plan only).  ``capon_clean``: ``(iterations, gain, floor, residual)`` of
-    ``Handle.set_capon_clean``: the plan also resolves every window's arrivals by CLEAN-SC (needs ``capon``; likewise).
-    ``capon_music``: ``(sources, eig_floor, maps, vectors, peaks, peak_floor)`` of ``Handle.set_capon_music``: the plan also returns every window's
-    eigenvalues and MUSIC spectrum (needs ``capon``; likewise).  ``families``: the request dict of
-    ``planner.check_families``: the plan also groups the cells of its rows into families behind its last solve
-    (``Handle.set_families``; likewise)."""
+    (``Handle.set_estimators``); a handle that still carries some from an earlier call is reset.  ``requests``: the opt-in
+    requests of the plan, a ``Requests`` record — or, without one, its attributes as the keywords from ``uncert`` on.  Its
+    per-band tables have one entry per band of the Prep: ``bands`` cuts them (``Requests.for_bands``).  They are on the
+    handle for this plan only (``Requests.applied``), and so is the ``window_slice``."""
+    req = requests if requests is not None else Requests(
+        uncert=uncert, beam=beam, subsample=subsample, lag_limits=lag_limits, beam_grid=beam_grid, beam_grid_map=beam_grid_map,
+        lag_seed=lag_seed, closure=closure, capon=capon, kept=kept, capon_clean=capon_clean, capon_music=capon_music,
+        families=families, element_delays=element_delays, element_delays_kept=element_delays_kept, beam_trace=beam_trace,
+        beam_taps=beam_taps)
     if upload:
         if trace_ready:
             pass
@@ -718,83 +611,17 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         h.set_estimators(estimators or ())
     idx = np.arange(prep.nbands) if bands is None else np.asarray(bands, dtype=np.int64)
     sos = None if prep.sos is None else prep.sos[idx]
-    if window_slice is not None:
-        k, n = window_slice
-        nw = prep.nwin[idx]
-        first = (nw * k) // n
-        h.set_window_ranges(first, (nw * (k + 1)) // n - first)
-    h.reserve_results(reserve_bytes)
-    h.set_uncertainty(planner.uncertainty_frame(prep.xij) if uncert else None)     # (ltsva's confidence intervals, on request)
-    if beam:
-        h.set_beam(True)
-    if closure:
-        h.set_closure(True)
-    if subsample:
-        h.set_lag_refinement(True)
-    if lag_limits is not None:
-        h.set_lag_limits(lag_limits)
-    if beam_grid is not None:
-        h.set_beam_grid(beam_grid, beam_grid_map)
-    if lag_seed is not None:
-        h.set_lag_seed(lag_seed)
-    if beam_taps:
-        h.set_beam_interpolation(beam_taps)
-    peaks = 0
-    try:
-        if kept is not None:
-            h.set_kept_elements(*kept)
-        if element_delays is not None:
-            h.set_element_delays(np.asarray(element_delays)[idx], element_delays_kept)
-        if beam_trace is not None:
-            wins, gate, bt_kept = beam_trace
-            h.set_beam_trace(np.concatenate([wins[int(i)] for i in idx]), None if gate != gate else gate, bt_kept)
-        if capon is not None:            # (inside the try: whatever one of the two refuses, the shared handle keeps neither)
-            capon = dict(capon)
-            peaks, cells, floor = capon.pop('peaks', 0), capon.pop('peak_cells', None), capon.pop('peak_floor', 0.25)
-            h.set_capon(**dict(capon, **{k: np.asarray(capon[k])[idx] for k in ('freqs', 'snap_len', 'snap_hop')}))
-            if peaks:
-                h.set_capon_peaks(cells, peaks, floor)
-        if capon_clean is not None:
-            h.set_capon_clean(*capon_clean)
-        if capon_music is not None:
-            h.set_capon_music(*capon_music)
-        if families is not None:
-            h.set_families(_hip.family_params(**families))
+    with contextlib.ExitStack() as undo:          # (the handle is shared with calls that plan for themselves)
+        if window_slice is not None:
+            k, n = window_slice
+            nw = prep.nwin[idx]
+            first = (nw * k) // n
+            h.set_window_ranges(first, (nw * (k + 1)) // n - first)
+            undo.callback(h.set_window_ranges, None)
+        h.reserve_results(reserve_bytes)
+        undo.enter_context((req if bands is None else req.for_bands(idx)).applied(h, prep.xij))
         h.plan(sos, prep.zero_phase, prep.tl, prep.tr, prep.W[idx], prep.inc[idx], prep.vector_len, lts=prep.lts,
                xcorr_impl=xcorr_impl)
-    finally:
-        if beam:
-            h.set_beam(False)            # (the handle is shared with calls that plan for themselves)
-        if closure:
-            h.set_closure(False)
-        if subsample:
-            h.set_lag_refinement(False)
-        if lag_limits is not None:
-            h.set_lag_limits(None)
-        if beam_grid is not None:
-            h.set_beam_grid(None)
-        if lag_seed is not None:
-            h.set_lag_seed(None)
-        if beam_taps:
-            h.set_beam_interpolation(0)
-        if capon is not None:
-            h.set_capon(None)
-        if peaks:
-            h.set_capon_peaks(None)
-        if capon_clean is not None:
-            h.set_capon_clean(0)
-        if capon_music is not None:
-            h.set_capon_music(None)
-        if families is not None:
-            h.set_families(None)
-        if kept is not None:
-            h.set_kept_elements(0)
-        if element_delays is not None:
-            h.set_element_delays(None)
-        if beam_trace is not None:
-            h.set_beam_trace(None)
-        if window_slice is not None:
-            h.set_window_ranges(None)
     if before_execute is not None:
         before_execute()
     h.stream_results(stream)             # (``stream``: the rows come back batch by batch, see ``process``)
@@ -895,62 +722,55 @@ class _Notifier:
             self.bands(b0, b1)
 
 
-def collect(res, h, b0, b1, streamed, note):
-    """The rows of bands [b0, b1), whose pass handle ``h`` has just run, into ``res``; then (streamed and past
-    ``host_overlap``: batch by batch) ``note`` is told."""
+def fetch_groups(h, req, results, b0, b1, est=None):
+    """Everything but the result block that the pass handle ``h`` has just run has, by the requests ``req`` of its call,
+    into the rows of bands [b0, b1) of ``results``: the k ``BandBatch`` of the k recordings of the pass, whose row b * k + s
+    is band b of recording s.  Each group of ``RESULT_GROUPS`` that applies is fetched once (its method once per call it
+    lists; the beam trace once per result row) and, like the planes of ``EXTRA_FIELDS``, goes straight into the one result
+    of a pass over one recording.  ``est``: the results of that estimator of the pass — the groups that take one only, and
+    the index is passed to them.  The families of a pass that labels them (``req.families``) come as one table per pass,
+    cut per recording by ``split_families``."""
+    k, want, index = len(results), req.wants(), () if est is None else (est,)
+
+    def put(name, a):
+        if k == 1:
+            getattr(results[0], name)[b0:b1] = a
+        else:
+            a = a.reshape((b1 - b0, k) + a.shape[1:])
+            for j, res in enumerate(results):
+                getattr(res, name)[b0:b1] = a[:, j]
+
+    extras = {'want_' + name: True for name, _, _ in EXTRA_FIELDS if getattr(want, 'want_' + name)}
+    if extras:
+        ext = h.fetch(grids=False, **extras, **({} if est is None else dict(est=est)))
+        for name in extras:
+            put(name[len('want_'):], ext[name[len('want_'):]])
+    for g in RESULT_GROUPS:
+        if not g.applies(want) or (est is not None and not g.est):
+            continue
+        fetch = getattr(h, g.method)
+        for args, fields in g.calls:
+            if g.per_row:
+                for j, res in enumerate(results):
+                    for b in range(b0, b1):
+                        getattr(res, fields[0][0])[b] = fetch((b - b0) * k + j)
+                continue
+            out = fetch(*args, *(index if g.est else ()))
+            for (name, _, _), a in zip(fields, (out,) if len(fields) == 1 else out):
+                put(name, a)
+    if req.families is not None and est is None:
+        family, _, table = h.fetch_families()
+        parts = [(family, table)] if k == 1 else split_families(family, table, b1 - b0, k, family.shape[1])
+        for res, (f, t) in zip(results, parts):
+            res.family, res.family_table = f, t
+
+
+def collect(res, h, b0, b1, streamed, note, req):
+    """The rows of bands [b0, b1), whose pass handle ``h`` has just run with the requests ``req``, into ``res``; then
+    (streamed and past ``host_overlap``: batch by batch) ``note`` is told."""
     live = streamed and note.ready
     drain(h, streamed, res.grids, res.mask, b0, b1, functools.partial(note.units, b0, b1) if live else None)
-    extras = [name for name in ('lag', 'cmax', 'z') if getattr(res, name) is not None]
-    if extras:
-        ext = h.fetch(grids=False, **{'want_' + name: True for name in extras})
-        for name in extras:
-            getattr(res, name)[b0:b1] = ext[name]
-    if res.vel_uncert is not None:
-        res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty()
-    if res.beam_power is not None:
-        res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam()
-    if res.consistency is not None:
-        res.consistency[b0:b1], res.closure_max[b0:b1], res.element_consistency[b0:b1] = h.fetch_closure()
-    if res.lag_frac is not None:
-        res.lag_frac[b0:b1] = h.fetch_lag_fraction()
-    if res.grid_index is not None:
-        res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = h.fetch_beam_grid()
-    if res.grid_map is not None:
-        res.grid_map[b0:b1] = h.fetch_beam_grid_map()
-    if res.capon_index is not None:
-        res.capon_index[b0:b1], res.capon_power[b0:b1], res.bartlett_index[b0:b1], res.bartlett_power[b0:b1] = h.fetch_capon()
-    if res.capon_map is not None:
-        res.capon_map[b0:b1], res.bartlett_map[b0:b1] = h.fetch_capon_maps()
-    if res.capon_csdm is not None:
-        res.capon_csdm[b0:b1] = h.fetch_capon_csdm()
-    if res.capon_peak_count is not None:
-        for which, name in enumerate(('capon', 'bartlett')):
-            for field, a in zip(PEAK_FIELDS, h.fetch_capon_peaks(which)):
-                getattr(res, name + field)[b0:b1] = a
-    if res.clean_count is not None:
-        for field, a in zip(CLEAN_FIELDS, h.fetch_capon_clean()):
-            getattr(res, field)[b0:b1] = a
-    if res.clean_csdm is not None:
-        res.clean_csdm[b0:b1] = h.fetch_capon_clean_csdm()
-    if res.music_eigenvalues is not None:
-        for field, a in zip(MUSIC_FIELDS, h.fetch_capon_music()):
-            getattr(res, field)[b0:b1] = a
-    if res.music_map is not None:
-        res.music_map[b0:b1] = h.fetch_capon_music_map()
-    if res.music_vectors is not None:
-        res.music_vectors[b0:b1] = h.fetch_capon_music_vectors()
-    if res.music_peak_count is not None:
-        for field, a in zip(PEAK_FIELDS, h.fetch_capon_music_peaks()):
-            getattr(res, 'music' + field)[b0:b1] = a
-    if res.dropped_mask is not None:
-        res.dropped_mask[b0:b1], res.kept_count[b0:b1] = h.fetch_kept_elements()
-    if res.element_delay is not None:
-        res.element_delay[b0:b1], res.element_cc[b0:b1], res.element_shift[b0:b1] = h.fetch_element_delays()
-    if res.beam_trace is not None:
-        for b in range(b0, b1):
-            res.beam_trace[b] = h.fetch_beam_trace(b - b0)
-    if getattr(res, 'families_in_pass', False):          # (set where ONE pass covers every band of the call)
-        res.family, _, res.family_table = h.fetch_families()
+    fetch_groups(h, req, [res], b0, b1)
     if not live:
         note.bands(b0, b1)
 
@@ -969,15 +789,12 @@ def start_upload(data, fs, device):
 
 
 def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequential, streamed, up, resident, note,
-                  handle=None, device=None, **launch_kw):
+                  handle=None, device=None, requests=Requests(), **launch_kw):
     """Design, plan and queue the pass of every band group (``prepare`` of its bands — ``prep_tail``: the arguments behind
-    ``winlens`` — then ``launch``), group 0 while the trace is still going up (``up``).  Sequential rounds share one
-    handle: each is collected before the next is planned.  -> the (handle, b0, b1) still to collect."""
+    ``winlens`` — then ``launch`` with the group's share of ``requests``), group 0 while the trace is still going up (``up``).
+    Sequential rounds share one handle: each is collected before the next is planned.  -> the (handle, b0, b1) still to
+    collect."""
     launched, prep = [], None
-    seed_all = launch_kw.get('lag_seed')
-    capon_all = launch_kw.get('capon')
-    trace_all = launch_kw.get('beam_trace')
-    shift_all = launch_kw.get('element_delays')
     nchans, npts = _shape_of(data)
     for g, (b0, b1) in enumerate(bounds):
         prep = prepare(nchans, npts, res.fs, rij, band_edges[b0:b1], winlens[b0:b1], *prep_tail, common=prep,
@@ -986,7 +803,7 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
         res.pair_idx, res.xij = prep.pair_idx, prep.xij
         h = handle if handle is not None else get_handle(device, 0 if sequential else g)
         if sequential and launched:               # one handle, one plan at a time: finish the previous round first
-            collect(res, *launched.pop(), streamed, note)
+            collect(res, *launched.pop(), streamed, note, requests)
         joins = up is not None and g == 0                 # this launch rides on the upload thread's rows
         early = joins or (resident and (g == 0 or sequential))
         # the groups finish in the order they were queued (GPU-side ordering of their correlation stages): the
@@ -994,18 +811,11 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
         # itself between the passes and all of them land together at the end (stream priorities alone did the
         # job on some boxes and not on others)
         ordered = launched and not sequential and GROUP_ORDER
-        if launch_kw.get('lag_seed') is not None:         # (one half-width per band of the call: this group's)
-            launch_kw = dict(launch_kw, lag_seed=seed_all[b0:b1])
-        if capon_all is not None:                         # (likewise the Capon tables)
-            launch_kw = dict(launch_kw, capon=dict(capon_all, **{k: capon_all[k][b0:b1] for k in ('freqs', 'snap_len', 'snap_hop')}))
-        if trace_all is not None:                         # (likewise the synthesis windows)
-            launch_kw = dict(launch_kw, beam_trace=(trace_all[0][b0:b1],) + tuple(trace_all[1:]))
-        if shift_all is not None:                         # (likewise the shift ranges of the element delays)
-            launch_kw = dict(launch_kw, element_delays=shift_all[b0:b1])
         try:
             launch(h, data, prep, trace_from=launched[0][0] if (launched and not sequential) else None, trace_ready=early,
                    after=launched[-1][0] if ordered else None, stream=streamed,
-                   before_execute=up.landed if (joins and not up.row_pipeline) else None, **launch_kw)
+                   before_execute=up.landed if (joins and not up.row_pipeline) else None,
+                   requests=requests.for_bands(slice(b0, b1)), **launch_kw)
         except BaseException:
             if joins:
                 up.landed()                       # the pass could not be queued: the upload's own error is the cause, if it has one
@@ -1015,143 +825,6 @@ def launch_groups(data, rij, band_edges, winlens, prep_tail, res, bounds, sequen
         launched.append((h, b0, b1))
         res.handle = h
     return launched
-
-
-def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
-    """``seed_halfwidths`` of ``process`` / ``process_batch`` -> int32 (nbands,) or None; ``ValueError`` before any GPU work."""
-    if seed_halfwidths is None:
-        return None
-    seeds = planner.check_seed_halfwidths(seed_halfwidths, nbands)
-    if sgrid is None:
-        raise ValueError('seed_halfwidths needs slowness_grid: the lag search is seeded by the grid maximum')
-    if min_velocity is not None:
-        raise ValueError('seed_halfwidths does not combine with min_velocity: the grid\'s own extent bounds the slowness, '
-                         'one restriction of the lag search at a time')
-    return seeds
-
-
-CLEAN_FIELDS = ('clean_count', 'clean_index', 'clean_power', 'clean_total', 'clean_residual')   # what ``Handle.fetch_capon_clean`` returns, in order
-MUSIC_FIELDS = ('music_eigenvalues', 'music_sources', 'music_sweeps', 'music_index', 'music_power')   # what ``Handle.fetch_capon_music`` returns, in order
-PEAK_FIELDS = ('_peak_count', '_peak_index', '_peak_power', '_peak_offset')     # what ``Handle.fetch_capon_peaks`` returns, in order
-
-
-def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm, W,
-                 capon_peaks=0, capon_peak_floor=0.25, capon_cells=None):
-    """The Capon keywords of ``process`` / ``process_batch`` -> the ``capon`` dict of ``launch`` or None; ``ValueError`` before
-    any GPU work (``planner.check_capon``, ``planner.check_capon_peaks``)."""
-    wants_peaks = not (isinstance(capon_peaks, (int, np.integer)) and not isinstance(capon_peaks, (bool, np.bool_)) and capon_peaks == 0)
-    if capon_grid is None:
-        if capon_freqs is not None or capon_snapshots is not None or want_capon_maps or want_capon_csdm:
-            raise ValueError('capon_freqs, capon_snapshots, want_capon_maps and want_capon_csdm need capon_grid')
-        if wants_peaks or capon_cells is not None:
-            raise ValueError('capon_peaks and capon_cells need capon_grid')
-        return None
-    if capon_freqs is None or capon_snapshots is None:
-        raise ValueError('capon_grid needs capon_freqs (planner.capon_frequencies) and capon_snapshots (planner.capon_snapshots)')
-    g, f, ls, hs, delta = planner.check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, W,
-                                              want_capon_maps, want_capon_csdm)
-    out = dict(grid=g, freqs=f, snap_len=ls, snap_hop=hs, loading=delta, want_maps=bool(want_capon_maps),
-               want_csdm=bool(want_capon_csdm))
-    if wants_peaks:
-        cells, K, floor = planner.check_capon_peaks(len(g), planner.grid_cells(g)[0] if capon_cells is None else capon_cells,
-                                                    capon_peaks, capon_peak_floor)
-        out.update(peaks=K, peak_cells=cells, peak_floor=floor)
-    elif capon_cells is not None:
-        raise ValueError('capon_cells needs capon_peaks')
-    return out
-
-
-def _check_capon_clean(capon_clean, capon):
-    """``capon_clean`` of ``process`` / ``process_batch`` — None, an iteration count or ``(iterations[, gain[, floor[, residual]]])``
-    — -> the ``capon_clean`` tuple of ``launch`` or None; ``ValueError`` before any GPU work (``planner.check_capon_clean``)."""
-    if capon_clean is None:
-        return None
-    args = tuple(capon_clean) if isinstance(capon_clean, (tuple, list)) else (capon_clean,)
-    if not 1 <= len(args) <= 4:
-        raise ValueError('capon_clean must be (iterations[, gain[, floor[, residual]]]), not %r' % (capon_clean,))
-    return planner.check_capon_clean(*args, has_capon=capon is not None)
-
-
-def _check_capon_music(nchans, capon_music, capon, kept):
-    """``capon_music`` of ``process`` / ``process_batch`` — None, a number of sources or ``(sources[, eig_floor[, maps[, vectors[, peaks[, peak_floor]]]]])``
-    — -> the ``capon_music`` tuple of ``launch`` or None; ``ValueError`` before any GPU work (``planner.check_capon_music``).
-    ``kept``: the checked ``kept`` tuple of the call."""
-    if capon_music is None:
-        return None
-    args = tuple(capon_music) if isinstance(capon_music, (tuple, list)) else (capon_music,)
-    if not 1 <= len(args) <= 6:
-        raise ValueError('capon_music must be (sources[, eig_floor[, maps[, vectors[, peaks[, peak_floor]]]]]), not %r' % (capon_music,))
-    return planner.check_capon_music(nchans, *args, has_capon=capon is not None, has_peaks=capon is not None and bool(capon.get('peaks', 0)),
-                                     kept_capon=kept is not None and bool(kept[2]))
-
-
-def _check_kept(nchans, kept, want_beam, capon):
-    """``kept`` of ``process`` / ``process_batch`` — None or ``(min_pairs, beam, capon)`` — -> the ``kept`` tuple of ``launch`` or
-    None; ``ValueError`` before any GPU work (``planner.check_kept``, and a flag whose results the call does not ask for)."""
-    if kept is None:
-        return None
-    try:
-        q, kb, kc = kept
-    except (TypeError, ValueError):
-        raise ValueError('kept must be (min_pairs, beam, capon), not %r' % (kept,))
-    q, kb, kc = planner.check_kept(nchans, q, kb, kc)
-    if kb and not want_beam:
-        raise ValueError('kept: the beam of the kept elements needs want_beam')
-    if kc and capon is None:
-        raise ValueError('kept: the Capon spectra of the kept elements need capon_grid')
-    return q, kb, kc
-
-
-def _check_element_delays(max_shift, delays_kept, nbands, nchans, kept):
-    """``element_max_shift`` / ``element_delays_kept`` of ``process`` / ``process_batch`` -> the int32 shift range of every
-    band, or None; ``ValueError`` before any GPU work (``planner.check_element_shifts``).  ``kept``: the call's checked
-    ``kept`` tuple or None."""
-    if not isinstance(delays_kept, (bool, np.bool_)):
-        raise ValueError('element_delays_kept must be True or False, not %r' % (delays_kept,))
-    if max_shift is None:
-        if delays_kept:
-            raise ValueError('element_delays_kept needs element_max_shift')
-        return None
-    shifts = planner.check_element_shifts(max_shift, nbands)
-    if nchans > 32:
-        raise ValueError('the element delays take at most 32 array elements, not %d' % nchans)
-    if delays_kept and kept is None:
-        raise ValueError('element_delays_kept: the beam of the kept elements needs a plan that names them (kept=, '
-                         'planner.check_kept)')
-    return shifts
-
-
-def _check_beam_trace(want, W, kept, window_slice=None):
-    """``want_beam_trace`` of ``process`` / ``process_batch`` — None / False, True, a window kind or a dict of ``window``,
-    ``mdccm_min``, ``kept`` — -> the ``beam_trace`` tuple of ``launch`` (one synthesis window per band, the gate, the kept flag)
-    or None; ``ValueError`` before any GPU work (``planner.check_beam_trace``).  ``W``: the window length of every band;
-    ``kept``: the call's checked ``kept`` tuple or None."""
-    if want is None or want is False:
-        return None
-    if want is True:
-        want = {}
-    elif isinstance(want, str):
-        want = dict(window=want)
-    if not isinstance(want, dict) or set(want) - {'window', 'mdccm_min', 'kept'}:
-        raise ValueError('want_beam_trace must be True, a window kind or a dict of window, mdccm_min and kept, not %r' % (want,))
-    table, gate, bt_kept = planner.check_beam_trace(np.asarray(W, dtype=np.int64), has_kept=kept is not None,
-                                                    window_slice=window_slice, **want)
-    cuts = np.cumsum(np.asarray(W, dtype=np.int64))[:-1]
-    return list(np.split(table, cuts)), gate, bt_kept
-
-
-def _check_families(families, window_slice=None):
-    """``families`` of ``process`` / ``process_batch`` — None or a dict of ``planner.check_families``' arguments — -> the
-    checked request or None; ``ValueError`` before any GPU work."""
-    if families is None:
-        return None
-    if not isinstance(families, dict):
-        raise ValueError('families must be a dict of mdccm_min, baz_tol, vel_tol, vel_min, vel_max [, sigma_tau_max, band_reach, '
-                         'time_reach, min_pixels], not %r' % (families,))
-    try:
-        return planner.check_families(window_slice=window_slice, **families)
-    except TypeError as e:
-        raise ValueError('families: %s' % e)
 
 
 def label_result(h, res, par):
@@ -1196,84 +869,8 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
     prefiltered=True: ``data`` is already filtered/tapered (``ltsva`` entry), one band.
     window_slice=(k, n): process only the k-th of n contiguous window slices of every band (window
     sharding across GPUs); rows outside the slice stay zero, ``nwin``/``t`` describe the whole band.
-    want_uncert=True: also ``res.vel_uncert`` / ``res.baz_uncert`` (nbands, vector_len), the confidence intervals of
-    the slowness estimate, computed on the GPU behind each unit's solve (``nbls_set_uncertainty``).
-    want_beam=True: also ``res.beam_power`` / ``res.fstat`` (nbands, vector_len), power and Fisher F-statistic of the
-    delay-and-sum beam at the solved slowness, computed on the GPU behind each unit's solve (``nbls_set_beam``,
-    DESIGN.md section 12); ``process_segmented`` refuses it.
-    want_subsample=True: every picked lag is refined to sub-sample precision behind its verifier and the solve reads
-    ``tau = (lag + frac) / fs`` (``nbls_set_lag_refinement``); with ``want_lag`` also ``res.lag_frac``
-    (nbands, vector_len, P) beside ``res.lag``; ``process_segmented`` refuses it.
-    min_velocity (km/s): every pair's lag is searched only within the range a plane wave no slower than that can delay the
-    pair (``planner.lag_limits``, ``nbls_set_lag_limits``); ``ValueError`` before any GPU work unless
-    it is a finite real > 0; ``process_segmented`` refuses it.
-    slowness_grid (G, 2) s/km: also ``res.grid_index`` (int32) / ``res.grid_fstat`` / ``res.grid_power`` (nbands, vector_len),
-    per window the grid point at which the Fisher ratio of the full array's delay-and-sum beam is largest and the ratio
-    and beam power there, searched on the GPU behind each unit's solve (``nbls_set_beam_grid``, DESIGN.md section 15);
-    want_grid_map=True: also ``res.grid_map`` (nbands, vector_len, G), the ratio at every grid point.  ``ValueError`` before
-    any GPU work for a bad grid (``planner.check_slowness_grid``); ``process_segmented`` refuses it.
-    seed_halfwidths (samples; one integer or one per band; needs ``slowness_grid``): every pair's lag is searched only
-    within that many samples of the delay the window's grid maximum predicts for the pair, and the grid search runs in the
-    correlation stage, ahead of the lag pick (``planner.seed_halfwidths``, ``nbls_set_lag_seed``, DESIGN.md section 16);
-    it does not combine with ``min_velocity``.  ``ValueError`` before any GPU work for a bad table
-    (``planner.check_seed_halfwidths``); ``process_segmented`` refuses it.
-    want_consistency=True: also ``res.consistency`` / ``res.closure_max`` (nbands, vector_len) and
-    ``res.element_consistency`` (nbands, vector_len, N), seconds: the rms and the largest closure ``l_ij + l_jk - l_ik`` of
-    the picked lags over the element triplets of each window, and per element the rms over the triplets that hold it,
-    computed on the GPU behind each unit's solve (``nbls_set_closure``); they follow whatever picks
-    the call makes (refined, bounded, seeded); ``process_segmented`` refuses it.
-    capon_grid (G, 2) s/km with capon_freqs (Hz per band, ``planner.capon_frequencies``) and capon_snapshots ((Ls, Hs) in
-    samples, ``planner.capon_snapshots``): also ``res.capon_index`` / ``res.bartlett_index`` (int32) and ``res.capon_power`` /
-    ``res.bartlett_power`` (nbands, vector_len), per window the maxima of the Capon (MVDR) and Bartlett slowness spectra of
-    the band's cross-spectral matrix under the diagonal loading ``capon_loading``, computed on the GPU behind each unit's
-    solve (``nbls_set_capon``); want_capon_maps=True: also ``res.capon_map`` / ``res.bartlett_map``
-    (nbands, vector_len, G); want_capon_csdm=True: also ``res.capon_csdm`` (nbands, vector_len, N, N) complex.  ``ValueError``
-    before any GPU work for whatever the library would refuse (``planner.check_capon``); ``process_segmented`` refuses it.
-    capon_peaks = K in 1..8 (needs ``capon_grid``): also ``res.capon_peak_count`` (nbands, vector_len) int32,
-    ``res.capon_peak_index`` (.., K) int32, ``res.capon_peak_power`` (.., K) and ``res.capon_peak_offset`` (.., K, 2), and the
-    same four with ``bartlett_``: per window the K strongest local maxima of either spectrum that reach ``capon_peak_floor``
-    times its maximum, with a sub-grid offset in lattice steps, picked on the GPU where the map is complete
-    (``nbls_set_capon_peaks``).  ``capon_cells`` (G, 2) int: the lattice coordinates of the grid points, by
-    default ``planner.grid_cells(capon_grid)[0]``.  ``ValueError`` before any GPU work (``planner.check_capon_peaks``);
-    ``process_segmented`` refuses it with the spectra.
-    kept = (min_pairs, beam, capon): also ``res.dropped_mask`` (nbands, vector_len) uint32, bit m set where FAST-LTS has taken
-    the weight of at least ``min_pairs`` (None: all N - 1) of element m's pairs in that window, and ``res.kept_count`` int32;
-    with ``beam`` (needs ``want_beam``) ``res.beam_power`` / ``res.fstat`` and with ``capon`` (needs ``capon_grid``) the
-    spectra, their maxima, maps and peaks are those of the elements that are not dropped — the whole array where fewer
-    than 3 would remain (``nbls_set_kept_elements``).  ``ValueError`` before any GPU work
-    (``planner.check_kept``); ``process_segmented`` refuses it.
-    want_beam_trace = True, ``'hann'`` / ``'boxcar'`` or a dict of ``window``, ``mdccm_min``, ``kept``: also ``res.beam_trace``
-    (nbands, npts), per band the delay-and-sum beam at every window's solved slowness, the overlapping windows stitched
-    with the synthesis window; only windows with MdCCM >= ``mdccm_min`` enter, with ``kept`` (needs ``kept=``) each over the
-    elements LTS kept in it (``nbls_set_beam_trace``).  Formed on the GPU behind the last solve of every
-    pass, fetched per HBM round.  ``ValueError`` before any GPU work (``planner.check_beam_trace``); ``process_segmented``
-    refuses it, and so does a ``window_slice``.
-    element_max_shift = K, one integer in 0..256 or one per band: also ``res.element_delay`` / ``res.element_cc`` /
-    ``res.element_shift`` (nbands, vector_len, N): per window and element the delay in seconds, the normalised correlation and
-    the whole-sample shift, within +-K samples of the delay the solved slowness predicts, at which the element correlates
-    best with the sum of the other elements; with ``element_delays_kept`` (needs ``kept=``) with the sum of those LTS kept
-    (``nbls_set_element_delays``, DESIGN.md section 23; ``planner.element_shifts`` makes K).  ``ValueError`` before any GPU work;
-    ``process_segmented`` refuses it.
-    capon_clean = iterations or (iterations, gain, floor, residual) (needs ``capon_grid``): also ``res.clean_count`` (nbands,
-    vector_len) int32, ``res.clean_index`` (.., I) int32, ``res.clean_power`` (.., I), ``res.clean_total`` and
-    ``res.clean_residual`` (nbands, vector_len): per window the CLEAN-SC components of the band's cross-spectral matrix —
-    the Bartlett maximum, ``gain`` of everything coherent with it removed, again on what is left, until a maximum falls
-    below ``floor`` times the first — with the mean element power before and after; ``residual``: also ``res.clean_csdm``
-    (nbands, vector_len, N, N) complex (``nbls_set_capon_clean``).  ``ValueError`` before any GPU work
-    (``planner.check_capon_clean``); ``process_segmented`` refuses it with the Capon spectra.
-    capon_music = sources or (sources, eig_floor, maps, vectors, peaks, peak_floor) (needs ``capon_grid``): also ``res.music_eigenvalues`` (nbands,
-    vector_len, N), the eigenvalues of every window's cross-spectral matrix in descending order, ``res.music_sources`` (the
-    number M of signal eigenvectors: ``sources``, or with 0 the eigenvalues of at least ``eig_floor`` times the largest),
-    ``res.music_sweeps`` (Jacobi sweeps), ``res.music_index`` and ``res.music_power``, the maximum of the MUSIC pseudo-spectrum
-    over the grid; ``maps``: also ``res.music_map`` (nbands, vector_len, G); ``vectors``: also ``res.music_vectors`` (nbands,
-    vector_len, N, N) complex; ``peaks`` (needs ``capon_peaks``): also ``res.music_peak_count`` / ``_index`` / ``_power`` /
-    ``_offset``, the K strongest local maxima of the MUSIC spectrum as ``capon_peaks`` returns a spectrum's, kept from
-    ``peak_floor`` times its maximum (``nbls_set_capon_music``).  ``ValueError`` before any GPU work
-    (``planner.check_capon_music``); not with ``kept=(.., .., True)``; ``process_segmented`` refuses it with the Capon spectra.
-    families = a dict of ``planner.check_families``' arguments: also ``res.family`` (nbands, vector_len) int32 and
-    ``res.family_table`` (F, 8) int64, the cells grouped into families (``nbls_set_families``): labelled on
-    the GPU behind the last solve where one pass covers every band, else (band groups, HBM rounds, the time-segmented path) by
-    the same kernels on the assembled grids (``label_result``) — the same arrays either way.  ``ValueError`` before any GPU
+    The keywords from ``want_uncert`` on, and ``want_lag`` / ``want_cmax`` / ``want_z``, are the opt-in requests of the call:
+    ``Requests.check`` describes every one and the results it brings, and refuses a bad one (``ValueError``) before any GPU
     work.
 
     In this order:
@@ -1292,32 +889,15 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
        units [u0, u1) (flat index over all bands of the call, band-major) are in ``res`` — per batch of a streamed pass,
        while the GPU works on the next one —; without it ``group_done(res, b0, b1)`` runs for the bands a batch or a
        group completes (the caller builds its dictionary there).  Rounds collected in step 4 are reported after step 5."""
+    asked = Requests.keywords_of(locals())
     nchans, npts = _shape_of(data)
-    limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij)[0], fs, min_velocity)
-    sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
-    seeds = _check_seed(seed_halfwidths, len(band_edges), sgrid, min_velocity)
-    cap = max_bands_per_pass(nchans, npts, 0 if want_beam_trace is None or want_beam_trace is False else 1)
-    # (the Capon tables are checked against the window lengths: planned here already, before the upload starts)
-    capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
-                         None if capon_grid is None else plan_windows(npts, fs, winlens, winover, vector_len)[0],
-                         capon_peaks, capon_peak_floor, capon_cells)
-    planner.check_steering(beam_taps)
-    if beam_taps and not want_beam and sgrid is None:
-        raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
-    kept = _check_kept(nchans, kept, want_beam, capon)
-    clean = _check_capon_clean(capon_clean, capon)
-    music = _check_capon_music(nchans, capon_music, capon, kept)
-    fam = _check_families(families, window_slice)
-    shifts = _check_element_delays(element_max_shift, element_delays_kept, len(band_edges), nchans, kept)
-    trace = None if want_beam_trace is None or want_beam_trace is False else _check_beam_trace(
-        want_beam_trace, plan_windows(npts, fs, winlens, winover, vector_len)[0], kept, window_slice)
-    if cap < 1 and not prefiltered and kept is not None:
-        raise ValueError('kept: a trace of %d x %d samples takes the time-segmented path (not even one filtered band fits the '
-                         'HBM budget of a pass, NBLS_MAX_FILTERED_GB): the kept elements are not available there' % (nchans, npts))
-    if cap < 1 and not prefiltered and capon is not None:
-        raise ValueError('capon_grid: a trace of %d x %d samples takes the time-segmented path (not even one filtered band '
-                         'fits the HBM budget of a pass, NBLS_MAX_FILTERED_GB), which keeps the filtered band on the host: '
-                         'the Capon spectra are not available there' % (nchans, npts))
+    # (what is checked against the window lengths has them planned here already, before the upload starts)
+    req = Requests.check(nchans, len(band_edges), fs, lambda: plan_windows(npts, fs, winlens, winover, vector_len)[0],
+                         window_slice, rij=rij, **asked)
+    fam = req.families
+    cap = max_bands_per_pass(nchans, npts, 0 if req.beam_trace is None else 1)
+    if cap < 1 and not prefiltered:
+        req.segmented_refusal(nchans, npts, ('kept', 'capon_grid'))
     single = prefiltered or handle is not None or not upload
     up, resident = start_upload(data, fs, device) if upload and handle is None and (cap >= 1 or prefiltered) else (None, False)
     try:
@@ -1326,30 +906,22 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         if cap < 1 and not prefiltered:            # not even one band's filtered trace fits the HBM budget
             res = process_segmented(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filter_type, filter_order,
                                     filter_ripple, vector_len, device, xcorr_impl, want_lag, want_cmax, want_z, host_overlap,
-                                    group_done, want_beam, want_subsample, min_velocity, sgrid, seeds, want_consistency,
-                                    shifts, None if trace is None else want_beam_trace, beam_taps=beam_taps)
+                                    group_done, want_beam, want_subsample, min_velocity, slowness_grid, seed_halfwidths,
+                                    want_consistency, element_max_shift, None if req.beam_trace is None else want_beam_trace,
+                                    beam_taps=beam_taps)
             if fam is not None:
                 label_result(res.handle if getattr(res, 'handle', None) is not None else get_handle(device, 0), res, fam)
             return res
         streamed, bounds, sequential = choose_form(alpha, nwin, nchans, max(1, cap), groups, window_slice, single)
-        res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax, want_z, want_uncert, want_beam,
-                         want_subsample, 0 if sgrid is None else len(sgrid), want_grid_map, want_consistency,
-                         0 if capon is None else len(capon['grid']), want_capon_maps, want_capon_csdm,
-                         0 if capon is None else capon.get('peaks', 0), kept is not None, npts if trace is not None else 0,
-                         shifts is not None, clean_iterations=0 if clean is None else clean[0],
-                         want_clean_csdm=clean is not None and clean[3], want_music=music is not None,
-                         want_music_maps=music is not None and music[2], want_music_vectors=music is not None and music[3],
-                         want_music_peaks=music is not None and music[4])
+        res = new_result(nchans, alpha, fs, W, inc, nwin, vector_len, **req.result_keywords(npts))
         res.families_in_pass = fam is not None and len(bounds) == 1      # (one pass covers every band: the in-pass request)
+        if not res.families_in_pass:
+            req = req.replace(families=None)
         note = _Notifier(res, units_done, group_done)
         launched = launch_groups(data, rij, band_edges, winlens, (winover, alpha, filter_type, filter_order, filter_ripple,
                                                                   vector_len, prefiltered),
-                                 res, bounds, sequential, streamed, up, resident, note, handle, device, upload=upload,
-                                 window_slice=window_slice, uncert=want_uncert, xcorr_impl=xcorr_impl, beam=want_beam,
-                                 subsample=want_subsample, lag_limits=limits, beam_grid=sgrid, beam_grid_map=bool(want_grid_map),
-                                 lag_seed=seeds, closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, capon_music=music,
-                                 families=fam if res.families_in_pass else None, element_delays=shifts,
-                                 element_delays_kept=bool(element_delays_kept), beam_trace=trace, beam_taps=beam_taps)
+                                 res, bounds, sequential, streamed, up, resident, note, handle, device, req, upload=upload,
+                                 window_slice=window_slice, xcorr_impl=xcorr_impl)
     finally:
         if up is not None:
             up.close()
@@ -1360,7 +932,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
         host_overlap(res)
     note.replay()
     for h, b0, b1 in launched:
-        collect(res, h, b0, b1, streamed, note)
+        collect(res, h, b0, b1, streamed, note, req)
     if fam is not None and not res.families_in_pass:
         label_result(res.handle, res, fam)
     return res
@@ -1461,6 +1033,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     ``want_consistency``: every estimator's ``consistency`` / ``closure_max`` / ``element_consistency``, the closure of the
     picked lags over the triplets of ITS elements (``process``).  ``want_beam_trace``: refused (``ValueError``) — the beam trace
     is estimator 0's, further estimators are out of its scope."""
+    asked = Requests.keywords_of(locals())
     if want_beam_trace is not None and want_beam_trace is not False:
         raise ValueError('want_beam_trace: the beam trace is not available with several estimators (nbls_set_beam_trace is '
                          'refused beside nbls_set_estimators)')
@@ -1476,7 +1049,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     alpha0 = estimators[full][0] if full is not None else 1.0
     rij0 = rijs[full] if full is not None else rijs[-1]        # (no full-array estimator: ``rijs`` ends with the full geometry)
     first_est = 0 if full is not None else 1                   # device index of order[0]
-    limits = None if min_velocity is None else planner.lag_limits(planner.co_array(rij0)[0], fs, min_velocity)
+    req = Requests.check(nchans, nb, fs, None, rij=rij0, **asked)          # (of the full array; a sub-array reads its lags)
     extras = []
     for i in (order[1:] if full is not None else order):
         alpha, remove = estimators[i]
@@ -1488,9 +1061,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
     check_elements(nchans, alpha0)
     results = [None] * len(estimators)
     for i, (alpha, remove) in enumerate(estimators):
-        res = new_result(nchans - len(remove), alpha, fs, W, inc, nwin, vector_len, want_lag, want_cmax,
-                         want_uncert=want_uncert, want_beam=want_beam, want_subsample=want_subsample,
-                         want_consistency=want_consistency)
+        res = new_result(nchans - len(remove), alpha, fs, W, inc, nwin, vector_len, **req.result_keywords(npts))
         res.xij, res.pair_idx, _ = planner.co_array(rijs[i])
         results[i] = res
     streamed = stream_pays(min(a for a, _ in estimators), nwin, nchans * (nchans - 1) // 2)
@@ -1506,9 +1077,8 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
                            windows=(W[b0:b1], inc[b0:b1], nwin[b0:b1], vector_len))
             joins = up is not None and b0 == 0
             try:
-                launch(h, rows, prep, trace_ready=joins or resident or b0 > 0, stream=streamed, uncert=want_uncert,
-                       before_execute=up.landed if (joins and not up.row_pipeline) else None, estimators=extras,
-                       beam=want_beam, subsample=want_subsample, lag_limits=limits, closure=bool(want_consistency))
+                launch(h, rows, prep, trace_ready=joins or resident or b0 > 0, stream=streamed, requests=req,
+                       before_execute=up.landed if (joins and not up.row_pipeline) else None, estimators=extras)
             finally:
                 if joins:
                     up.landed()
@@ -1534,19 +1104,7 @@ def process_multi(data, fs, t0s, rijs, band_edges, winlens, winover, estimators,
                 drain(view, streamed, res.grids, res.mask, b0, b1, done)
                 if units_done is not None and not streamed:
                     units_done(i, res, int(cum[b0]), int(cum[b1]))
-                extras_wanted = [name for name in ('lag', 'cmax') if getattr(res, name) is not None]
-                if extras_wanted:
-                    ext = h.fetch(grids=False, est=est, **{'want_' + name: True for name in extras_wanted})
-                    for name in extras_wanted:
-                        getattr(res, name)[b0:b1] = ext[name]
-                if want_uncert:
-                    res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = h.fetch_uncertainty(est=est)
-                if want_beam:
-                    res.beam_power[b0:b1], res.fstat[b0:b1] = h.fetch_beam(est)
-                if want_consistency:
-                    res.consistency[b0:b1], res.closure_max[b0:b1], res.element_consistency[b0:b1] = h.fetch_closure(est)
-                if res.lag_frac is not None:
-                    res.lag_frac[b0:b1] = h.fetch_lag_fraction(est)
+                fetch_groups(h, req, [res], b0, b1, est)
     finally:
         if up is not None:
             up.close()
@@ -1596,44 +1154,22 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
     run in consecutive rounds; if not even one band of the whole batch fits, the batch is cut into sub-batches of as many
     recordings as fit.  A batch never takes the time-segmented path.  The passes are fetched in one piece, or streamed
     batch by batch where ``stream_pays`` (per-row windows) says so; either way every recording's rows are complete before
-    its dictionary is built (the caller's side: rows of one recording are spread over all bands)."""
+    its dictionary is built (the caller's side: rows of one recording are spread over all bands).  The opt-in keywords are
+    those of ``process``, checked the same way and in the same order (``Requests.check``)."""
+    asked = Requests.keywords_of(locals())
     S = len(recordings)
     nchans, npts = len(recordings[0]), len(recordings[0][0])
     nb = len(band_edges)
-    sgrid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
-    G = 0 if sgrid is None else len(sgrid)
-    seeds = _check_seed(seed_halfwidths, nb, sgrid, min_velocity)
+    req = Requests.check(nchans, nb, fs, lambda: plan_windows(npts, fs, winlens, winover, vector_len)[0], rij=rij, **asked)
     prep = prepare(nchans, npts, fs, rij, band_edges, winlens, winover, alpha, filter_type, filter_order, filter_ripple,
                    vector_len, prefiltered)
     VL, P, MB = prep.vector_len, prep.npairs, prep.mask_bytes
-    capon = _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm,
-                         prep.W, capon_peaks, capon_peak_floor, capon_cells)
-    CG = 0 if capon is None else len(capon['grid'])
-    CK = 0 if capon is None else capon.get('peaks', 0)
-    planner.check_steering(beam_taps)
-    if beam_taps and not want_beam and sgrid is None:
-        raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
-    kept = _check_kept(nchans, kept, want_beam, capon)
-    clean = _check_capon_clean(capon_clean, capon)
-    music = _check_capon_music(nchans, capon_music, capon, kept)
-    fam = _check_families(families)
-    shifts = _check_element_delays(element_max_shift, element_delays_kept, nb, nchans, kept)
-    trace = _check_beam_trace(want_beam_trace, prep.W, kept)
-    tr = 0 if trace is None else 1                  # rows of the beam trace per recording and band, beside its N filtered ones
-    limits = None if min_velocity is None else planner.lag_limits(prep.xij, fs, min_velocity)
+    fam, tr = req.families, 0 if req.beam_trace is None else 1     # (tr: rows of the beam trace per recording and band, beside its N filtered ones)
     per_sub = S if max_bands_per_pass(S * nchans, npts, S * tr) >= 1 else max_bands_per_pass(nchans, npts, tr)
     if per_sub < 1:
         raise ValueError('a recording of %d x %d samples does not fit the HBM budget of one pass (NBLS_MAX_FILTERED_GB): '
                          'process it on its own' % (nchans, npts))
-    out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, want_uncert=want_uncert, want_beam=want_beam,
-                      grid_points=G, want_grid_map=want_grid_map, want_consistency=want_consistency, capon_points=CG,
-                      want_capon_maps=want_capon_maps, want_capon_csdm=want_capon_csdm, capon_peaks=CK,
-                      want_kept=kept is not None, beam_trace_npts=npts if trace is not None else 0,
-                      want_element_delays=shifts is not None, clean_iterations=0 if clean is None else clean[0],
-                      want_clean_csdm=clean is not None and clean[3], want_music=music is not None,
-                      want_music_maps=music is not None and music[2], want_music_vectors=music is not None and music[3],
-                      want_music_peaks=music is not None and music[4])
-           for _ in range(S)]
+    out = [new_result(nchans, alpha, fs, prep.W, prep.inc, prep.nwin, VL, **req.result_keywords(npts)) for _ in range(S)]
     h = get_handle(device, 0)
     try:
         for s0 in range(0, S, per_sub):
@@ -1642,88 +1178,21 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
             h.set_trace_rows([r for rec in recordings[s0:s0 + k] for r in rec], fs)
             cap = max(1, max_bands_per_pass(k * nchans, npts, k * tr))
             streamed = stream_pays(alpha, np.tile(prep.nwin, k), P)
-            fam_in_pass = fam is not None and cap >= nb       # (one pass covers every band of these recordings)
+            # (the families are labelled in the pass where one pass covers every band of these recordings)
+            passes = req if (fam is not None and cap >= nb) else req.replace(families=None)
             for b0 in range(0, nb, cap):
                 b1 = min(nb, b0 + cap)
                 R = (b1 - b0) * k
-                launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, uncert=want_uncert,
-                       beam=want_beam, subsample=want_subsample, lag_limits=limits, beam_grid=sgrid,
-                       beam_grid_map=bool(want_grid_map), lag_seed=None if seeds is None else seeds[b0:b1],
-                       closure=bool(want_consistency), capon=capon, kept=kept, capon_clean=clean, capon_music=music,
-                       families=fam if fam_in_pass else None, element_delays=shifts, element_delays_kept=bool(element_delays_kept),
-                       beam_trace=trace, beam_taps=beam_taps)
+                launch(h, None, prep, bands=list(range(b0, b1)), trace_ready=True, stream=streamed, requests=passes)
                 g = np.zeros((4, R, VL))
                 m = np.zeros((R, VL, MB), dtype=np.uint8)
                 drain(h, streamed, g, m, 0, R)
                 g = g.reshape(4, b1 - b0, k, VL)
                 m = m.reshape(b1 - b0, k, VL, MB)
-                unc = np.stack(h.fetch_uncertainty()).reshape(2, b1 - b0, k, VL) if want_uncert else None
-                beam = np.stack(h.fetch_beam()).reshape(2, b1 - b0, k, VL) if want_beam else None
-                clo = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_closure()] if want_consistency else None
-                sg = [a.reshape(b1 - b0, k, VL) for a in h.fetch_beam_grid()] if G else None
-                sgmap = h.fetch_beam_grid_map().reshape(b1 - b0, k, VL, G) if (G and want_grid_map) else None
-                cp = [a.reshape(b1 - b0, k, VL) for a in h.fetch_capon()] if CG else None
-                cpmap = [a.reshape(b1 - b0, k, VL, CG) for a in h.fetch_capon_maps()] if (CG and want_capon_maps) else None
-                cpr = h.fetch_capon_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (CG and want_capon_csdm) else None
-                cpk = [[a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_peaks(which)] for which in (0, 1)] if CK else None
-                cln = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_clean()] if clean is not None else None
-                mus = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_music()] if music is not None else None
-                mum = h.fetch_capon_music_map().reshape(b1 - b0, k, VL, CG) if (music is not None and music[2]) else None
-                muv = h.fetch_capon_music_vectors().reshape(b1 - b0, k, VL, nchans, nchans) if (music is not None and music[3]) else None
-                mup = [a.reshape((b1 - b0, k, VL) + a.shape[2:]) for a in h.fetch_capon_music_peaks()] if (music is not None and music[4]) else None
-                clr = h.fetch_capon_clean_csdm().reshape(b1 - b0, k, VL, nchans, nchans) if (clean is not None and clean[3]) else None
-                kel = [a.reshape(b1 - b0, k, VL) for a in h.fetch_kept_elements()] if kept is not None else None
-                eld = [a.reshape(b1 - b0, k, VL, nchans) for a in h.fetch_element_delays()] if shifts is not None else None
-                if fam_in_pass:
-                    family, _, table = h.fetch_families()
-                    for res, (f, t) in zip(out[s0:s0 + k], split_families(family, table, nb, k, VL)):
-                        res.family, res.family_table = f, t
                 for j, res in enumerate(out[s0:s0 + k]):
                     res.grids[:, b0:b1] = g[:, :, j]
                     res.mask[b0:b1] = m[:, j]
-                    if want_uncert:
-                        res.vel_uncert[b0:b1], res.baz_uncert[b0:b1] = unc[:, :, j]
-                    if want_beam:
-                        res.beam_power[b0:b1], res.fstat[b0:b1] = beam[:, :, j]
-                    if want_consistency:
-                        res.consistency[b0:b1], res.closure_max[b0:b1], res.element_consistency[b0:b1] = [a[:, j] for a in clo]
-                    if G:
-                        res.grid_index[b0:b1], res.grid_fstat[b0:b1], res.grid_power[b0:b1] = [a[:, j] for a in sg]
-                    if sgmap is not None:
-                        res.grid_map[b0:b1] = sgmap[:, j]
-                    if CG:
-                        (res.capon_index[b0:b1], res.capon_power[b0:b1], res.bartlett_index[b0:b1],
-                         res.bartlett_power[b0:b1]) = [a[:, j] for a in cp]
-                    if cpmap is not None:
-                        res.capon_map[b0:b1], res.bartlett_map[b0:b1] = [a[:, j] for a in cpmap]
-                    if cpr is not None:
-                        res.capon_csdm[b0:b1] = cpr[:, j]
-                    if cpk is not None:
-                        for which, name in enumerate(('capon', 'bartlett')):
-                            for field, a in zip(PEAK_FIELDS, cpk[which]):
-                                getattr(res, name + field)[b0:b1] = a[:, j]
-                    if cln is not None:
-                        for field, a in zip(CLEAN_FIELDS, cln):
-                            getattr(res, field)[b0:b1] = a[:, j]
-                    if clr is not None:
-                        res.clean_csdm[b0:b1] = clr[:, j]
-                    if mus is not None:
-                        for field, a in zip(MUSIC_FIELDS, mus):
-                            getattr(res, field)[b0:b1] = a[:, j]
-                    if mum is not None:
-                        res.music_map[b0:b1] = mum[:, j]
-                    if muv is not None:
-                        res.music_vectors[b0:b1] = muv[:, j]
-                    if mup is not None:
-                        for field, a in zip(PEAK_FIELDS, mup):
-                            getattr(res, 'music' + field)[b0:b1] = a[:, j]
-                    if kel is not None:
-                        res.dropped_mask[b0:b1], res.kept_count[b0:b1] = [a[:, j] for a in kel]
-                    if eld is not None:
-                        res.element_delay[b0:b1], res.element_cc[b0:b1], res.element_shift[b0:b1] = [a[:, j] for a in eld]
-                    if trace is not None:
-                        for b in range(b0, b1):
-                            res.beam_trace[b] = h.fetch_beam_trace((b - b0) * k + j)
+                fetch_groups(h, passes, out[s0:s0 + k], b0, b1)
     finally:
         h.set_segments(1)
     for res, t0 in zip(out, t0s):
