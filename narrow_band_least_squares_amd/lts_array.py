@@ -3,10 +3,14 @@ narrow_band_least_squares.py:91,183 and example.py:109; the lts_array source its
 empty git submodule in the reference checkout, so the algorithm follows the published one as
 summarised in SURVEY.md §3.3).
 """
+import typing
+
 import numpy as np
 
 from . import engine, planner
 from .helpers import get_rij
+
+OLS_MESSAGE = 'ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.'
 
 
 def _returns(res, nchans, alpha, keys=None):
@@ -24,8 +28,12 @@ def _returns(res, nchans, alpha, keys=None):
 
 def _returns_beam(res, nchans, alpha, keys=None):
     """``_returns`` followed by the band's ``beam_power`` and ``fstat`` (csrc/beam.hip: beam_fstat_kernel)."""
+    return _returns(res, nchans, alpha, keys) + _beam_tail(res)
+
+
+def _beam_tail(res):
     n = int(res.nwin[0])
-    return _returns(res, nchans, alpha, keys) + (res.beam_power[0, :n].copy(), res.fstat[0, :n].copy())
+    return res.beam_power[0, :n].copy(), res.fstat[0, :n].copy()
 
 
 def _returns_consistency(res):
@@ -71,12 +79,20 @@ def _returns_grid(res, grid, want_map):
     return out + ((res.grid_map[0, :n].copy(),) if want_map else ())
 
 
+def _picker(band, n):
+    """How the ``_returns_*`` dictionaries take a field of a ``BandBatch``: a copy of row ``band``, its first ``n`` cells or
+    (``n=None``) all of them; ``band=None``: the array itself, every band's rows."""
+    if band is None:
+        return lambda a: a
+    sl = slice(None) if n is None else slice(0, n)
+    return lambda a: a[band, sl].copy()
+
+
 def _returns_capon(res, grid, want_maps, band=0, n=None):
     """A band's Capon results as a dict: the four fields, the slowness (``grid_slowness``) at either index and, when asked,
     both maps (csrc/capon.hip: capon_kernel); for a pass with a peak request also its eight fields and the refined slowness
     of every rank (``peak_slowness``).  ``n=None``: the band's first ``nwin`` cells, copied; else whole rows."""
-    sl = slice(None) if n is None else slice(0, n)
-    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    pick = _picker(band, n)
     out = {k: pick(getattr(res, k)) for k in ('capon_index', 'capon_power', 'bartlett_index', 'bartlett_power')}
     out['capon_vel'], out['capon_baz'] = grid_slowness(grid, out['capon_index'])
     out['bartlett_vel'], out['bartlett_baz'] = grid_slowness(grid, out['bartlett_index'])
@@ -114,37 +130,95 @@ def _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading,
                 want_capon_maps=bool(maps), **_peak_keywords(grid, peaks, peak_floor))
 
 
-def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, want_beam,
-           want_subsample=False, min_velocity=None, slowness_grid=None, grid_map=False, seed_halfwidths=None,
-           want_consistency=False, capon=None):
-    """The one body of ``ltsva``, ``ltsva_beam``, ``ltsva_subsample``, ``ltsva_bounded``, ``ltsva_grid``, ``ltsva_seeded`` and
-    ``ltsva_consistency``: the checks, the geometry, the device pass, the returns."""
+class _Feature(typing.NamedTuple):
+    """What an opt-in feature hands the two bodies below.  ``keywords(nchans, alpha, rij, fs, npts)``: its keywords of
+    ``engine.process`` (``ValueError`` for whatever the library would refuse); ``tail(res, kw, nchans, fs, t0)``: the tuple its
+    returns add to ``_returns(...)``, from one recording's result and those keywords; ``strict``: too few elements raise
+    ``ValueError`` ahead of everything else (False: the engine's ``RuntimeError``, as the reference's ``ltsva``)."""
+    keywords: typing.Callable
+    tail: typing.Callable
+    strict: bool = True
+
+
+def _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, feature):
+    """The one body of every single-stream entry point: the element checks, the geometry, the feature's keywords, the
+    message, the device pass — the key text of the dictionary made while it is in flight —, the returns."""
     data, fs, t0 = engine.stream_rows(st)
     nchans = len(data)
+    if feature.strict:
+        _check_elements_strict(nchans, alpha)
     engine.check_elements(nchans, alpha)
     if rij is None:
         rij = get_rij(lat_list, lon_list, nchans)
+    kw = feature.keywords(nchans, alpha, rij, fs, len(data[0]))
     if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    if plot_array_coordinates:
-        import warnings
-        warnings.warn('plot_array_coordinates is not supported on the HIP path; ignored.')
+        print(OLS_MESSAGE)
+
     def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
         if alpha < 1.0:
             res.keys = engine.time_keys(res.t, res.nwin)
 
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha,
-                         prefiltered=True, host_overlap=host_side, want_uncert=True, want_beam=want_beam,
-                         want_subsample=want_subsample, min_velocity=min_velocity, slowness_grid=slowness_grid,
-                         want_grid_map=grid_map, seed_halfwidths=seed_halfwidths, want_consistency=want_consistency,
-                         **(capon(rij, fs, len(data[0])) if capon is not None else {}))
-    out = (_returns_beam if want_beam else _returns)(res, nchans, alpha, getattr(res, 'keys', None))
-    if slowness_grid is not None:
-        out = out + _returns_grid(res, slowness_grid, grid_map)
-    if capon is not None:
-        out = out + (_returns_capon(res, capon(rij, fs, len(data[0]))['capon_grid'], res.capon_map is not None,
-                                    n=int(res.nwin[0])),)
-    return out + _returns_consistency(res) if want_consistency else out
+    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                         host_overlap=host_side, want_uncert=True, **kw)
+    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + feature.tail(res, kw, nchans, fs, t0)
+
+
+def _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, feature, one=None):
+    """The one body of every ``_batch`` entry point: ``_ltsva`` for several recordings in one pass (no host work rides
+    behind it: the key text is made in ``_returns``).  ``one``: the feature of the single call a batch of one recording is,
+    where it is not ``feature`` itself."""
+    streams = list(streams)
+    if not streams:
+        return []
+    recs, fs, t0s = engine.batch_rows(streams)
+    if len(streams) == 1:          # a batch of one IS the single call
+        return [_ltsva(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, one or feature)]
+    nchans = len(recs[0])
+    if feature.strict:
+        _check_elements_strict(nchans, alpha)
+    engine.check_elements(nchans, alpha)
+    if rij is None:
+        rij = get_rij(lat_list, lon_list, nchans)
+    kw = feature.keywords(nchans, alpha, rij, fs, len(recs[0][0]))
+    if alpha == 1.0:
+        print(OLS_MESSAGE)
+    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
+                                   want_uncert=True, **kw)
+    return [_returns(res, nchans, alpha) + feature.tail(res, kw, nchans, fs, t0) for res, t0 in zip(results, t0s)]
+
+
+def _window(npts, fs, window_length, window_overlap):
+    """The window length in samples of a filtered stream's one band."""
+    return int(planner.window_plan(npts, fs, window_length, window_overlap)[0])
+
+
+def _plain(beam=False, subsample=False, min_velocity=None, grid=None, grid_map=False, seeds=None, consistency=False, capon=None,
+           batch=False):
+    """The feature of ``ltsva`` and of what combines with it in ``ltsva_batch`` / ``ltsva_multi``: beam, refined lags, bounded
+    or seeded search, slowness grid, closure and (``capon``: a function of (nchans, rij, fs, npts) -> its keywords) the
+    Capon spectra.  ``ltsva`` itself keeps the reference's ``RuntimeError`` for too few elements, and so does a batch of several
+    recordings without the spectra; ``batch``: as ``ltsva_batch`` passes it on, without the keywords no batch form takes."""
+    own = dict(want_beam=beam, want_subsample=subsample, min_velocity=min_velocity, slowness_grid=grid)
+    if not batch:
+        own.update(want_grid_map=grid_map, seed_halfwidths=seeds, want_consistency=consistency)
+
+    def keywords(nchans, alpha, rij, fs, npts):
+        return own if capon is None else dict(own, **capon(nchans, rij, fs, npts))
+
+    def tail(res, kw, nchans, fs, t0):
+        out = _beam_tail(res) if beam else ()
+        if grid is not None:
+            out += _returns_grid(res, grid, grid_map)
+        if capon is not None:
+            out += (_returns_capon(res, kw['capon_grid'], kw['want_capon_maps'], n=int(res.nwin[0])),)
+        return out + _returns_consistency(res) if consistency else out
+    flagged = beam or subsample or min_velocity is not None or grid is not None or consistency
+    # (``ltsva_batch`` of several recordings has always left too few elements to the engine, flags or not; only its batch
+    #  of one, the single call, and the forms with the spectra are strict)
+    return _Feature(keywords, tail, capon is not None or (flagged and not batch))
+
+
+_LTSVA = _plain()          # (the plain call builds nothing per call)
 
 
 def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
@@ -157,7 +231,10 @@ def ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
     date numbers, median cross-correlation maximum, dropped-element dictionary (``{}`` for
     OLS), sigma_tau seconds, and the 90 % confidence half-widths of trace velocity (km/s) and
     back-azimuth (degrees; NaN where the direction is undetermined).  ``rij`` (2, N) km overrides the lat/lon geometry."""
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, plot_array_coordinates, rij, False)
+    if plot_array_coordinates:
+        import warnings
+        warnings.warn('plot_array_coordinates is not supported on the HIP path; ignored.')
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _LTSVA)
 
 
 def ltsva_beam(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None):
@@ -168,8 +245,7 @@ def ltsva_beam(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
     that line up exactly and NaN for an all-zero window or a slowness that is not finite.  Both are computed on the GPU
     behind each window's solve, from the filtered samples already there.  The first eight returns are ``ltsva``'s.
     Too few elements raise ``ValueError`` here (``ltsva`` keeps the reference's ``RuntimeError``)."""
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, True)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(beam=True))
 
 
 def _check_elements_strict(nchans, alpha):
@@ -192,8 +268,7 @@ def ltsva_subsample(st, lat_list, lon_list, window_length, window_overlap, alpha
     MdCCM and the key text of ``stdict`` are those of ``ltsva``; which pairs LTS drops may differ, as the residuals do.
     The fractions are computed on the GPU from the filtered samples already there (csrc/refine.hip).  Returns ``ltsva``'s
     8-tuple.  Too few elements raise ``ValueError`` here (``ltsva`` keeps the reference's ``RuntimeError``)."""
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, True)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(subsample=True))
 
 
 def ltsva_consistency(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, subsample=False):
@@ -209,9 +284,8 @@ def ltsva_consistency(st, lat_list, lon_list, window_length, window_overlap, alp
     from the lag table already there (csrc/closure.hip).  A ``subsample`` that is not a bool and too few elements raise
     ``ValueError`` before any GPU work."""
     _check_flag('subsample', subsample)
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, bool(subsample),
-                  want_consistency=True)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                  _plain(subsample=bool(subsample), consistency=True))
 
 
 def ltsva_bounded(st, lat_list, lon_list, window_length, window_overlap, min_velocity, alpha=1.0, rij=None):
@@ -224,8 +298,7 @@ def ltsva_bounded(st, lat_list, lon_list, window_length, window_overlap, min_vel
     search; the search runs on the GPU (csrc/xcorr_bounded.hip).  Returns ``ltsva``'s 8-tuple.  ``min_velocity`` must be a
     finite real > 0 and too few elements raise ``ValueError`` before any GPU work."""
     planner.check_min_velocity(min_velocity)
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, min_velocity)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(min_velocity=min_velocity))
 
 
 def ltsva_grid(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, alpha=1.0, rij=None, grid_map=False):
@@ -242,9 +315,7 @@ def ltsva_grid(st, lat_list, lon_list, window_length, window_overlap, slowness_g
     any GPU work."""
     grid = planner.check_slowness_grid(slowness_grid)
     _check_flag('grid_map', grid_map)
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, None, grid,
-                  bool(grid_map))
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(grid=grid, grid_map=bool(grid_map)))
 
 
 def ltsva_seeded(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, halfwidth, alpha=1.0, rij=None,
@@ -261,9 +332,8 @@ def ltsva_seeded(st, lat_list, lon_list, window_length, window_overlap, slowness
     grid = planner.check_slowness_grid(slowness_grid)
     seeds = planner.check_seed_halfwidths(halfwidth, 1)
     _check_flag('grid_map', grid_map)
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, False, None, grid,
-                  bool(grid_map), seeds)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                  _plain(grid=grid, grid_map=bool(grid_map), seeds=seeds))
 
 
 def ltsva_capon(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None, snapshots=None,
@@ -283,17 +353,14 @@ def ltsva_capon(st, lat_list, lon_list, window_length, window_overlap, slowness_
     steps``, ``capon_peak_vel`` / ``capon_peak_baz`` (nwin, K) of that refined vector, and the same seven with ``bartlett_``;
     ranks beyond the kept peaks are -1 / NaN.  Computed on the GPU behind each window's solve (csrc/capon.hip).  Whatever the
     library would refuse raises ``ValueError`` before any GPU work."""
-    _check_elements_strict(len(st), alpha)
-    nchans = len(st)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(capon=_capon_band(
+        window_length, window_overlap, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)))
 
-    def keywords(rij_used, fs, npts):
-        W = planner.window_plan(npts, fs, window_length, window_overlap)[0]
-        return _capon_keywords(nchans, rij_used, fs, int(W), slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    data, fs, _ = engine.stream_rows(st)
-    keywords(rij, fs, len(data[0]))                       # (every ValueError before any GPU work)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, False, capon=keywords)
+
+def _capon_band(window_length, window_overlap, *capon):
+    """``_capon_keywords`` of a filtered stream's one band, whose window length follows from the trace: the ``capon`` of
+    ``_plain``."""
+    return lambda nchans, rij, fs, npts: _capon_keywords(nchans, rij, fs, _window(npts, fs, window_length, window_overlap), *capon)
 
 
 def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, beam=False,
@@ -309,67 +376,24 @@ def ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alph
     five grid returns of ``ltsva_grid`` (no map), element i equal to ``ltsva_grid(streams[i], ...)``; it combines with the
     others, because it reads none of their results.  ``ltsva_capon_batch`` is this call with the Capon spectra,
     ``ltsva_beam_trace_batch`` the one with the beam trace."""
-    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
-                        slowness_grid, None)
-
-
-def ltsva_capon_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
-                      snapshots=None, loading=0.01, maps=False, peaks=0, peak_floor=0.25):
-    """``ltsva_capon`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
-    element i equal to ``ltsva_capon(streams[i], ...)``; the streams as for ``ltsva_batch``."""
-    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, False, False, None, None,
-                        dict(slowness_grid=slowness_grid, freq=freq, snapshots=snapshots, loading=loading, maps=maps,
-                             peaks=peaks, peak_floor=peak_floor))
-
-
-def _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
-                 slowness_grid, capon):
-    """The one body of ``ltsva_batch`` and ``ltsva_capon_batch`` (``capon``: the parameters of ``ltsva_capon`` or None)."""
     _check_flag('beam', beam)
     _check_flag('subsample', subsample)
     if min_velocity is not None:
         planner.check_min_velocity(min_velocity)
     if slowness_grid is not None:
         slowness_grid = planner.check_slowness_grid(slowness_grid)
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    ckw = {}
-    if capon is not None:
-        _check_elements_strict(nchans, alpha)
-        crij = get_rij(lat_list, lon_list, nchans) if rij is None else rij
-        W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
-        ckw = _capon_keywords(nchans, crij, fs, int(W), capon['slowness_grid'], capon['freq'], capon.get('snapshots'),
-                              capon.get('loading', 0.01), capon.get('maps', False), capon.get('peaks', 0),
-                              capon.get('peak_floor', 0.25))
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [_single(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity,
-                        slowness_grid, capon=(lambda *_: ckw) if ckw else None)]
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha,
-                                   prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
-                                   min_velocity=min_velocity, slowness_grid=slowness_grid, **ckw)
-    return [(_returns_beam if beam else _returns)(res, nchans, alpha) +
-            (() if slowness_grid is None else _returns_grid(res, slowness_grid, False)) +
-            ((_returns_capon(res, ckw['capon_grid'], ckw['want_capon_maps'], n=int(res.nwin[0])),) if ckw else ())
-            for res in results]
+    asked = (bool(beam), bool(subsample), min_velocity, slowness_grid)
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(*asked, batch=True),
+                        one=_plain(*asked))
 
 
-def _single(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, beam, subsample, min_velocity=None,
-            slowness_grid=None, consistency=False, capon=None):
-    """The single call a batch of one recording / one estimator with nothing removed is: ``ltsva`` itself for the plain
-    one, else the strict element check of ``ltsva_beam`` / ``ltsva_subsample`` and the shared body."""
-    if not beam and not subsample and min_velocity is None and slowness_grid is None and not consistency and capon is None:
-        return ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha=alpha, rij=rij)
-    _check_elements_strict(len(st), alpha)
-    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, False, rij, bool(beam), bool(subsample),
-                  min_velocity, slowness_grid, want_consistency=bool(consistency), capon=capon)
+def ltsva_capon_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
+                      snapshots=None, loading=0.01, maps=False, peaks=0, peak_floor=0.25):
+    """``ltsva_capon`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
+    element i equal to ``ltsva_capon(streams[i], ...)``; the streams as for ``ltsva_batch``."""
+    capon = _capon_band(window_length, window_overlap, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, _plain(capon=capon, batch=True),
+                        one=_plain(capon=capon))
 
 
 def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimators, rij=None, beam=False, subsample=False,
@@ -394,8 +418,8 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     nchans = len(data)
     ests = engine.normalize_estimators(estimators, nchans)
     if len(ests) == 1 and not ests[0][1]:          # one estimator with nothing removed IS the single call
-        return [_single(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij, beam, subsample, min_velocity,
-                        consistency=consistency)]
+        return [_ltsva(st, lat_list, lon_list, window_length, window_overlap, ests[0][0], rij,
+                       _plain(bool(beam), bool(subsample), min_velocity, consistency=bool(consistency)))]
     rijs, t0s = [], []
     for _, remove in ests:
         kept = engine.kept_elements(nchans, remove)
@@ -407,7 +431,7 @@ def ltsva_multi(st, lat_list, lon_list, window_length, window_overlap, estimator
     if all(rm for _, rm in ests):
         rijs.append(get_rij(lat_list, lon_list, nchans) if rij is None else rij)
     if any(a == 1.0 for a, _ in ests):
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
+        print(OLS_MESSAGE)
     results = engine.process_multi(data, fs, t0s, rijs, [(None, None)], [window_length], window_overlap, ests,
                                    prefiltered=True, want_uncert=True, want_beam=bool(beam), want_subsample=bool(subsample),
                                    min_velocity=min_velocity, want_consistency=bool(consistency))
@@ -425,8 +449,7 @@ def _returns_kept(res, nchans, beam, capon_kw, band=0, n=None):
     """A band's kept-element results as a dict: ``dropped_elements`` (bool, one column per element, from the bits of the
     mask), ``kept_count`` and, where the pass formed them, ``beam_power`` / ``fstat`` and the fields of ``_returns_capon``
     (csrc/kept.hip, csrc/beam.hip, csrc/capon.hip).  ``band`` / ``n`` as for ``_returns_capon``."""
-    sl = slice(None) if n is None else slice(0, n)
-    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    pick = _picker(band, n)
     mask = pick(res.dropped_mask)
     out = dict(dropped_elements=((mask[..., None] >> np.arange(nchans, dtype=np.uint32)) & 1).astype(bool),
                kept_count=pick(res.kept_count))
@@ -437,17 +460,30 @@ def _returns_kept(res, nchans, beam, capon_kw, band=0, n=None):
     return out
 
 
-def _kept_keywords(nchans, rij, fs, W, min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor):
-    """The keywords of ``engine.process`` behind the arguments of ``ltsva_kept`` for one filtered band of window length ``W``
-    samples -> (keywords, Capon keywords or {}).  ``ValueError`` before any GPU work."""
-    if slowness_grid is None and (freq is not None or snapshots is not None or maps or peaks):
-        raise ValueError('freq, snapshots, maps and peaks need slowness_grid')
-    if slowness_grid is not None and freq is None:
-        raise ValueError('slowness_grid needs freq, the frequency in Hz at which the spectra are formed')
-    q, kb, kc = planner.check_kept(nchans, min_pairs, beam, slowness_grid is not None)
-    ckw = {} if slowness_grid is None else _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, loading, maps,
-                                                            peaks, peak_floor)
-    return dict(ckw, want_beam=kb, kept=(q, kb, kc)), ckw
+def _kept(window_length, window_overlap, min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor):
+    """The feature behind the arguments of ``ltsva_kept``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        if slowness_grid is None and (freq is not None or snapshots is not None or maps or peaks):
+            raise ValueError('freq, snapshots, maps and peaks need slowness_grid')
+        if slowness_grid is not None and freq is None:
+            raise ValueError('slowness_grid needs freq, the frequency in Hz at which the spectra are formed')
+        q, kb, kc = planner.check_kept(nchans, min_pairs, beam, slowness_grid is not None)
+        ckw = {} if slowness_grid is None else _capon_keywords(nchans, rij, fs, _window(npts, fs, window_length, window_overlap),
+                                                                slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)
+        return dict(ckw, want_beam=kb, kept=(q, kb, kc))
+
+    def tail(res, kw, nchans, fs, t0):
+        return (_returns_kept(res, nchans, kw['want_beam'], kw if 'capon_grid' in kw else {}, n=int(res.nwin[0])),)
+    return _Feature(keywords, tail)
+
+
+def _kept_request(nchans, kept, min_pairs, beam=False, capon=False):
+    """``kept`` / ``min_pairs`` of the entry points that form their own result over the kept elements -> the ``kept`` keyword of
+    ``engine.process`` (``planner.check_kept``), None without ``kept``.  ``ValueError`` before any GPU work."""
+    _check_flag('kept', kept)
+    if min_pairs is not None and not kept:
+        raise ValueError('min_pairs needs kept=True')
+    return planner.check_kept(nchans, min_pairs, beam, capon) if kept else None
 
 
 def ltsva_kept(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, min_pairs=None, beam=True,
@@ -463,26 +499,8 @@ def ltsva_kept(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0,
     ``alpha == 1.0`` nothing is dropped and every field is that of ``ltsva_beam`` / ``ltsva_capon``.  All of it is computed on
     the GPU behind each window's solve (csrc/kept.hip).  Whatever the library would refuse raises ``ValueError`` before any
     GPU work."""
-    _check_elements_strict(len(st), alpha)
-    nchans = len(st)
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    data, fs, t0 = engine.stream_rows(st)
-    W = planner.window_plan(len(data[0]), fs, window_length, window_overlap)[0]
-    kw, ckw = _kept_keywords(nchans, rij, fs, int(W), min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks,
-                             peak_floor)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, **kw)
-    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (
-        _returns_kept(res, nchans, kw['want_beam'], ckw, n=int(res.nwin[0])),)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _kept(
+        window_length, window_overlap, min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor))
 
 
 def ltsva_kept_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, min_pairs=None,
@@ -490,27 +508,8 @@ def ltsva_kept_batch(streams, lat_list, lon_list, window_length, window_overlap,
                      peak_floor=0.25):
     """``ltsva_kept`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
     element i equal to ``ltsva_kept(streams[i], ...)``; the streams as for ``ltsva_batch``."""
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
-    kw, ckw = _kept_keywords(nchans, rij, fs, int(W), min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks,
-                             peak_floor)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_kept(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, min_pairs, beam,
-                           slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor)]
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, **kw)
-    return [_returns(res, nchans, alpha) + (_returns_kept(res, nchans, kw['want_beam'], ckw, n=int(res.nwin[0])),)
-            for res in results]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, _kept(
+        window_length, window_overlap, min_pairs, beam, slowness_grid, freq, snapshots, loading, maps, peaks, peak_floor))
 
 
 def ltsva_beam_trace(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, mdccm_min=None, window='hann',
@@ -525,65 +524,37 @@ def ltsva_beam_trace(st, lat_list, lon_list, window_length, window_overlap, alph
     solve, from the filtered samples already there (csrc/beam_trace.hip): 1/N of the data a host-side beam would have to
     fetch.  Returns ``ltsva``'s 8-tuple followed by the trace.  Whatever the library would refuse raises ``ValueError``
     before any GPU work."""
-    nchans = len(st)
-    data, fs, t0 = engine.stream_rows(st)
-    kept_kw, want = _beam_trace_keywords(nchans, alpha, len(data[0]), fs, window_length, window_overlap, mdccm_min, window, kept,
-                                         min_pairs)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, kept=kept_kw, want_beam_trace=want)
-    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (res.beam_trace[0].copy(),)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                  _beam_trace(window_length, window_overlap, mdccm_min, window, kept, min_pairs))
 
 
-def _beam_trace_keywords(nchans, alpha, npts, fs, window_length, window_overlap, mdccm_min, window, kept, min_pairs):
-    """The ``kept`` and ``want_beam_trace`` keywords of ``engine.process`` behind the arguments of ``ltsva_beam_trace``;
-    ``ValueError`` before any GPU work."""
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    _check_flag('kept', kept)
-    if min_pairs is not None and not kept:
-        raise ValueError('min_pairs needs kept=True')
-    kept_kw = planner.check_kept(nchans, min_pairs, False, False) if kept else None
-    W = planner.window_plan(npts, fs, window_length, window_overlap)[0]
-    want = dict(window=window, mdccm_min=mdccm_min, kept=bool(kept))
-    engine._check_beam_trace(want, [int(W)], kept_kw)
-    return kept_kw, want
+def _beam_trace(window_length, window_overlap, mdccm_min, window, kept, min_pairs):
+    """The feature behind the arguments of ``ltsva_beam_trace``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        kept_kw = _kept_request(nchans, kept, min_pairs)
+        want = dict(window=window, mdccm_min=mdccm_min, kept=bool(kept))
+        engine._check_beam_trace(want, [_window(npts, fs, window_length, window_overlap)], kept_kw)
+        return dict(kept=kept_kw, want_beam_trace=want)
+    return _Feature(keywords, lambda res, *_: (res.beam_trace[0].copy(),))
 
 
-def _steered_keywords(nchans, alpha, taps, slowness_grid, grid_map, subsample, kept, min_pairs):
-    """The keywords of ``engine.process`` behind the arguments of ``ltsva_steered`` -> (keywords, grid or None);
-    ``ValueError`` before any GPU work."""
-    taps = planner.check_steering(taps)
-    grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
-    for name, flag in (('grid_map', grid_map), ('subsample', subsample), ('kept', kept)):
-        _check_flag(name, flag)
-    if grid_map and grid is None:
-        raise ValueError('grid_map needs slowness_grid')
-    if min_pairs is not None and not kept:
-        raise ValueError('min_pairs needs kept=True')
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    kw = dict(want_beam=True, want_subsample=bool(subsample), slowness_grid=grid, want_grid_map=bool(grid_map), beam_taps=taps)
-    if kept:
-        kw['kept'] = planner.check_kept(nchans, min_pairs, True, False)
-    return kw, grid
+def _steered(taps, slowness_grid, grid_map, subsample, kept, min_pairs):
+    """The feature behind the arguments of ``ltsva_steered``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        checked = planner.check_steering(taps)
+        grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
+        for name, flag in (('grid_map', grid_map), ('subsample', subsample)):
+            _check_flag(name, flag)
+        if grid_map and grid is None:
+            raise ValueError('grid_map needs slowness_grid')
+        kept_kw = _kept_request(nchans, kept, min_pairs, beam=True)
+        kw = dict(want_beam=True, want_subsample=bool(subsample), slowness_grid=grid, want_grid_map=bool(grid_map), beam_taps=checked)
+        return kw if kept_kw is None else dict(kw, kept=kept_kw)
 
-
-def _returns_steered(res, nchans, alpha, kw, grid, keys=None):
-    """The returns of ``ltsva_steered`` from a pass made with ``_steered_keywords``."""
-    if 'kept' in kw:
-        out = _returns(res, nchans, alpha, keys) + (_returns_kept(res, nchans, True, {}, n=int(res.nwin[0])),)
-    else:
-        out = _returns_beam(res, nchans, alpha, keys)
-    return out if grid is None else out + _returns_grid(res, grid, kw['want_grid_map'])
+    def tail(res, kw, nchans, fs, t0):
+        out = (_returns_kept(res, nchans, True, {}, n=int(res.nwin[0])),) if 'kept' in kw else _beam_tail(res)
+        return out if kw['slowness_grid'] is None else out + _returns_grid(res, kw['slowness_grid'], kw['want_grid_map'])
+    return _Feature(keywords, tail)
 
 
 def ltsva_steered(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, taps=8, slowness_grid=None,
@@ -600,43 +571,16 @@ def ltsva_steered(st, lat_list, lon_list, window_length, window_overlap, alpha=1
     FAST-LTS kept and returns ``ltsva_kept(beam=True)``'s 9-tuple instead of ``ltsva_beam``'s 10 (``min_pairs`` as there).
     ``taps=0`` is the whole-sample beam.  Computed on the GPU behind each window's solve (csrc/beam.hip, csrc/beam_grid.hip).
     Whatever the library would refuse raises ``ValueError`` before any GPU work."""
-    nchans = len(st)
-    kw, grid = _steered_keywords(nchans, alpha, taps, slowness_grid, grid_map, subsample, kept, min_pairs)
-    data, fs, t0 = engine.stream_rows(st)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, **kw)
-    return _returns_steered(res, nchans, alpha, kw, grid, getattr(res, 'keys', None))
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                  _steered(taps, slowness_grid, grid_map, subsample, kept, min_pairs))
 
 
 def ltsva_steered_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, taps=8,
                         slowness_grid=None, grid_map=False, subsample=False, kept=False, min_pairs=None):
     """``ltsva_steered`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its tuples,
     element i equal to ``ltsva_steered(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``."""
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    kw, grid = _steered_keywords(nchans, alpha, taps, slowness_grid, grid_map, subsample, kept, min_pairs)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_steered(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, taps, slowness_grid,
-                              grid_map, subsample, kept, min_pairs)]
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, **kw)
-    return [_returns_steered(res, nchans, alpha, kw, grid) for res in results]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                        _steered(taps, slowness_grid, grid_map, subsample, kept, min_pairs))
 
 
 def ltsva_beam_trace_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, mdccm_min=None,
@@ -644,50 +588,25 @@ def ltsva_beam_trace_batch(streams, lat_list, lon_list, window_length, window_ov
     """``ltsva_beam_trace`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
     element i equal to ``ltsva_beam_trace(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``.  (``ltsva_batch``
     and ``ltsva_kept_batch`` keep their signatures: the batch form of the trace is this function.)"""
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    kept_kw, want = _beam_trace_keywords(nchans, alpha, len(recs[0][0]), fs, window_length, window_overlap, mdccm_min, window,
-                                         kept, min_pairs)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_beam_trace(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, mdccm_min, window,
-                                 kept, min_pairs)]
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, kept=kept_kw, want_beam_trace=want)
-    return [_returns(res, nchans, alpha) + (res.beam_trace[0].copy(),) for res in results]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                        _beam_trace(window_length, window_overlap, mdccm_min, window, kept, min_pairs))
 
 
-def _element_delay_keywords(nchans, alpha, max_shift, kept, min_pairs):
-    """The keywords of ``engine.process`` behind the arguments of ``ltsva_element_delays``; ``ValueError`` before any GPU
-    work."""
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    _check_flag('kept', kept)
-    if min_pairs is not None and not kept:
-        raise ValueError('min_pairs needs kept=True')
-    if max_shift is None:
-        raise ValueError('max_shift is required: an already filtered stream names no band whose upper edge could set the '
-                         'shift range (planner.element_shifts(fmax, fs) makes one)')
-    kept_kw = planner.check_kept(nchans, min_pairs, False, False) if kept else None
-    shifts = engine._check_element_delays(max_shift, bool(kept), 1, nchans, kept_kw)
-    return dict(kept=kept_kw, element_max_shift=shifts, element_delays_kept=bool(kept))
+def _element_delays(max_shift, kept, min_pairs):
+    """The feature behind the arguments of ``ltsva_element_delays``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        kept_kw = _kept_request(nchans, kept, min_pairs)
+        if max_shift is None:
+            raise ValueError('max_shift is required: an already filtered stream names no band whose upper edge could set the '
+                             'shift range (planner.element_shifts(fmax, fs) makes one)')
+        shifts = engine._check_element_delays(max_shift, bool(kept), 1, nchans, kept_kw)
+        return dict(kept=kept_kw, element_max_shift=shifts, element_delays_kept=bool(kept))
 
-
-def _returns_element_delays(res, nchans, alpha, kept, keys=None):
-    """The returns of ``ltsva_element_delays`` from a pass made with ``_element_delay_keywords``."""
-    n = int(res.nwin[0])
-    out = _returns(res, nchans, alpha, keys) + (res.element_delay[0, :n].copy(), res.element_cc[0, :n].copy(),
-                                                res.element_shift[0, :n].copy())
-    if kept:
-        mask = res.dropped_mask[0, :n].copy()
-        out += (mask, res.kept_count[0, :n].copy())
-    return out
+    def tail(res, kw, nchans, fs, t0):
+        n = int(res.nwin[0])
+        fields = ('element_delay', 'element_cc', 'element_shift') + (('dropped_mask', 'kept_count') if kept else ())
+        return tuple(getattr(res, k)[0, :n].copy() for k in fields)
+    return _Feature(keywords, tail)
 
 
 def ltsva_element_delays(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, max_shift=None, kept=False,
@@ -704,43 +623,15 @@ def ltsva_element_delays(st, lat_list, lon_list, window_length, window_overlap, 
     stream is already filtered and names no band, so ``max_shift`` is required.  DESIGN.md section 23 has the definition;
     computed on the GPU behind each window's solve (csrc/element_delay.hip).  Whatever the library would refuse raises
     ``ValueError`` before any GPU work."""
-    nchans = len(st)
-    kw = _element_delay_keywords(nchans, alpha, max_shift, kept, min_pairs)
-    data, fs, t0 = engine.stream_rows(st)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, **kw)
-    return _returns_element_delays(res, nchans, alpha, kept, getattr(res, 'keys', None))
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _element_delays(max_shift, kept, min_pairs))
 
 
 def ltsva_element_delays_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, max_shift=None,
                                kept=False, min_pairs=None):
     """``ltsva_element_delays`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its
     tuples, element i equal to ``ltsva_element_delays(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``."""
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    kw = _element_delay_keywords(nchans, alpha, max_shift, kept, min_pairs)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_element_delays(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, max_shift, kept,
-                                     min_pairs)]
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, **kw)
-    return [_returns_element_delays(res, nchans, alpha, kept) for res in results]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                        _element_delays(max_shift, kept, min_pairs))
 
 
 def clean_map(index, power, count, G):
@@ -784,34 +675,42 @@ def clean_sources(index, power, count, grid, radius, max_sources):
     return spw, ssl, vel, baz
 
 
-def _clean_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, iterations, gain, floor, kept, min_pairs, merge_radius,
-                    max_sources):
-    """The keywords of ``engine.process`` behind the arguments of ``ltsva_clean`` for one filtered band of window length ``W``
-    samples -> (keywords, grid, merge radius, max_sources).  ``ValueError`` before any GPU work."""
-    _check_flag('kept', kept)
-    if min_pairs is not None and not kept:
-        raise ValueError('min_pairs needs kept=True')
-    kw = _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, 0.01, False)
-    kw['capon_clean'] = planner.check_capon_clean(iterations, gain, floor, False)
-    if kept:
-        q = planner.check_kept(nchans, min_pairs, False, True)[0]
-        kw['kept'] = (q, False, True)
+def _check_clean_sources(grid, merge_radius, max_sources):
+    """``merge_radius`` / ``max_sources`` of the CLEAN-SC entry points -> (the radius in s/km, default 1.5 steps of the lattice
+    of ``grid``, max_sources); ``ValueError`` before any GPU work."""
     if isinstance(max_sources, (bool, np.bool_)) or not isinstance(max_sources, (int, np.integer)) or int(max_sources) < 1:
         raise ValueError('max_sources must be a positive integer, not %r' % (max_sources,))
-    grid = kw['capon_grid']
     if merge_radius is None:
         merge_radius = 1.5 * float(np.max(planner.grid_cells(grid)[1]))
     elif not planner._real(merge_radius) or not (0.0 <= float(merge_radius) < np.inf):
         raise ValueError('merge_radius must be a finite number >= 0 (s/km), not %r' % (merge_radius,))
-    return kw, grid, float(merge_radius), int(max_sources)
+    return float(merge_radius), int(max_sources)
+
+
+def _clean(window_length, window_overlap, slowness_grid, freq, snapshots, iterations, gain, floor, kept, min_pairs, merge_radius,
+           max_sources):
+    """The feature behind the arguments of ``ltsva_clean``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        kept_kw = _kept_request(nchans, kept, min_pairs, capon=True)
+        kw = _capon_keywords(nchans, rij, fs, _window(npts, fs, window_length, window_overlap), slowness_grid, freq, snapshots, 0.01,
+                             False)
+        kw['capon_clean'] = planner.check_capon_clean(iterations, gain, floor, False)
+        if kept_kw is not None:
+            kw['kept'] = kept_kw
+        sources[:] = _check_clean_sources(kw['capon_grid'], merge_radius, max_sources)
+        return kw
+
+    def tail(res, kw, nchans, fs, t0):
+        return (_returns_clean(res, kw['capon_grid'], *sources, n=int(res.nwin[0])),)
+    sources = []               # (merge radius, max_sources): checked once per call, beside the keywords
+    return _Feature(keywords, tail)
 
 
 def _returns_clean(res, grid, radius, max_sources, band=0, n=None):
     """A band's CLEAN-SC results as a dict: the fields of ``engine.CLEAN_FIELDS``, the slowness of every component
     (``grid_slowness``), and the merged sources of ``clean_sources`` (csrc/capon_clean.hip: capon_clean_kernel).  ``band`` / ``n``
     as for ``_returns_capon``."""
-    sl = slice(None) if n is None else slice(0, n)
-    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    pick = _picker(band, n)
     out = {k: pick(getattr(res, k)) for k in engine.CLEAN_FIELDS}
     if getattr(res, 'clean_csdm', None) is not None:
         out['clean_csdm'] = pick(res.clean_csdm)
@@ -836,25 +735,8 @@ def ltsva_clean(st, lat_list, lon_list, window_length, window_overlap, slowness_
     sources by ``clean_sources`` within ``merge_radius`` s/km (default: 1.5 steps of the grid's lattice): ``source_power``
     (nwin, max_sources), ``source_slowness`` (.., 2), ``source_vel``, ``source_baz``.  Computed on the GPU behind each window's
     solve (csrc/capon_clean.hip).  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
-    _check_elements_strict(len(st), alpha)
-    nchans = len(st)
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    data, fs, t0 = engine.stream_rows(st)
-    W = planner.window_plan(len(data[0]), fs, window_length, window_overlap)[0]
-    kw, grid, radius, S = _clean_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, iterations, gain, floor, kept,
-                                          min_pairs, merge_radius, max_sources)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, **kw)
-    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (_returns_clean(res, grid, radius, S, n=int(res.nwin[0])),)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _clean(
+        window_length, window_overlap, slowness_grid, freq, snapshots, iterations, gain, floor, kept, min_pairs, merge_radius, max_sources))
 
 
 def ltsva_clean_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
@@ -862,42 +744,25 @@ def ltsva_clean_batch(streams, lat_list, lon_list, window_length, window_overlap
                       max_sources=4):
     """``ltsva_clean`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
     element i equal to ``ltsva_clean(streams[i], ...)``; the streams as for ``ltsva_batch``."""
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
-    kw, grid, radius, S = _clean_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, iterations, gain, floor, kept,
-                                          min_pairs, merge_radius, max_sources)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_clean(streams[0], lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha, rij,
-                            snapshots, iterations, gain, floor, kept, min_pairs, merge_radius, max_sources)]
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, **kw)
-    return [_returns(res, nchans, alpha) + (_returns_clean(res, grid, radius, S, n=int(res.nwin[0])),) for res in results]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, _clean(
+        window_length, window_overlap, slowness_grid, freq, snapshots, iterations, gain, floor, kept, min_pairs, merge_radius, max_sources))
 
 
-def _music_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor):
-    """The keywords of ``engine.process`` behind the arguments of ``ltsva_music`` for one filtered band of window length ``W``
-    samples -> (keywords, grid).  ``ValueError`` before any GPU work."""
-    kw = _capon_keywords(nchans, rij, fs, W, slowness_grid, freq, snapshots, 0.01, False, peaks)
-    kw['capon_music'] = planner.check_capon_music(nchans, sources, eig_floor, maps, vectors, 'capon_peaks' in kw, peak_floor)
-    return kw, kw['capon_grid']
+def _music(window_length, window_overlap, slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor):
+    """The feature behind the arguments of ``ltsva_music``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        kw = _capon_keywords(nchans, rij, fs, _window(npts, fs, window_length, window_overlap), slowness_grid, freq, snapshots, 0.01,
+                             False, peaks)
+        kw['capon_music'] = planner.check_capon_music(nchans, sources, eig_floor, maps, vectors, 'capon_peaks' in kw, peak_floor)
+        return kw
+    return _Feature(keywords, lambda res, kw, *_: (_returns_music(res, kw['capon_grid'], n=int(res.nwin[0])),))
 
 
 def _returns_music(res, grid, band=0, n=None):
     """A band's MUSIC results as a dict: the fields of ``engine.MUSIC_FIELDS``, the slowness of the spectrum's maximum
     (``grid_slowness``) and, where the pass kept them, ``music_map``, ``music_vectors`` and the peaks' four fields with the refined
     slowness of every rank (``peak_slowness``) (csrc/capon_music.hip: capon_music_kernel).  ``band`` / ``n`` as for ``_returns_capon``."""
-    sl = slice(None) if n is None else slice(0, n)
-    pick = (lambda a: a[band, sl].copy()) if band is not None else (lambda a: a)
+    pick = _picker(band, n)
     out = {k: pick(getattr(res, k)) for k in engine.MUSIC_FIELDS}
     for k in ('music_map', 'music_vectors'):
         if getattr(res, k, None) is not None:
@@ -926,65 +791,25 @@ def ltsva_music(st, lat_list, lon_list, window_length, window_overlap, slowness_
     ``_power`` (nwin, K), ``music_peak_offset`` (nwin, K, 2) and the refined ``music_peak_slowness``, ``music_peak_vel``,
     ``music_peak_baz`` (the Capon and Bartlett peaks of the pass are not returned).  Computed on the GPU behind each window's solve (csrc/capon_music.hip).  Whatever the
     library would refuse raises ``ValueError`` before any GPU work."""
-    _check_elements_strict(len(st), alpha)
-    nchans = len(st)
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    data, fs, t0 = engine.stream_rows(st)
-    W = planner.window_plan(len(data[0]), fs, window_length, window_overlap)[0]
-    kw, grid = _music_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks,
-                               peak_floor)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, **kw)
-    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + (_returns_music(res, grid, n=int(res.nwin[0])),)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _music(
+        window_length, window_overlap, slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor))
 
 
 def ltsva_music_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha=1.0, rij=None,
                       snapshots=None, sources=0, eig_floor=0.05, maps=False, vectors=False, peaks=0, peak_floor=0.0):
     """``ltsva_music`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its 9-tuples,
     element i equal to ``ltsva_music(streams[i], ...)``; the streams as for ``ltsva_batch``."""
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    W = planner.window_plan(len(recs[0][0]), fs, window_length, window_overlap)[0]
-    kw, grid = _music_keywords(nchans, rij, fs, int(W), slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks,
-                               peak_floor)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_music(streams[0], lat_list, lon_list, window_length, window_overlap, slowness_grid, freq, alpha, rij,
-                            snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor)]
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, **kw)
-    return [_returns(res, nchans, alpha) + (_returns_music(res, grid, n=int(res.nwin[0])),) for res in results]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, _music(
+        window_length, window_overlap, slowness_grid, freq, snapshots, sources, eig_floor, maps, vectors, peaks, peak_floor))
 
 
-def _families_keywords(nchans, alpha, params):
-    """The ``families`` keyword of ``engine.process`` behind the arguments of ``ltsva_families``; ``ValueError`` before any GPU
-    work."""
-    _check_elements_strict(nchans, alpha)
-    engine.check_elements(nchans, alpha)
-    return planner.check_families(**params)
-
-
-def _returns_families(res, fs, t0):
-    n = int(res.nwin[0])
-    return res.family[0, :n].copy(), planner.family_table(res.family, res.family_table, res.vel, res.baz, res.mdccm, res.sigma_tau,
-                                                          [(np.nan, np.nan)], res.W, res.inc, fs, t0)
+def _families(**params):
+    """The feature behind the arguments of ``ltsva_families``."""
+    def tail(res, kw, nchans, fs, t0):
+        n = int(res.nwin[0])
+        return res.family[0, :n].copy(), planner.family_table(res.family, res.family_table, res.vel, res.baz, res.mdccm,
+                                                              res.sigma_tau, [(np.nan, np.nan)], res.W, res.inc, fs, t0)
+    return _Feature(lambda *_: dict(families=planner.check_families(**params)), tail)
 
 
 def ltsva_families(st, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, *, mdccm_min, baz_tol, vel_tol,
@@ -994,23 +819,9 @@ def ltsva_families(st, lat_list, lon_list, window_length, window_overlap, alpha=
     agree with their neighbours within ``baz_tol`` degrees and ``vel_tol`` km/s, at least ``min_pixels`` windows long;
     ``narrow_band_least_squares_families`` has the details (one band here: ``band_reach`` plays no part; ``f_lo`` / ``f_hi``
     are NaN), DESIGN.md section 26 the definition.  ``ValueError`` before any GPU work for what the library refuses."""
-    data, fs, t0 = engine.stream_rows(st)
-    nchans = len(data)
-    par = _families_keywords(nchans, alpha, dict(mdccm_min=mdccm_min, baz_tol=baz_tol, vel_tol=vel_tol, vel_min=vel_min, vel_max=vel_max,
-                                                 sigma_tau_max=sigma_tau_max, band_reach=band_reach, time_reach=time_reach,
-                                                 min_pixels=min_pixels))
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-
-    def host_side(res):        # key text of the dropped-element dictionary: needs no GPU result
-        if alpha < 1.0:
-            res.keys = engine.time_keys(res.t, res.nwin)
-
-    res = engine.process(data, fs, t0, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                         host_overlap=host_side, want_uncert=True, families=par)
-    return _returns(res, nchans, alpha, getattr(res, 'keys', None)) + _returns_families(res, fs, t0)
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij, _families(
+        mdccm_min=mdccm_min, baz_tol=baz_tol, vel_tol=vel_tol, vel_min=vel_min, vel_max=vel_max, sigma_tau_max=sigma_tau_max,
+        band_reach=band_reach, time_reach=time_reach, min_pixels=min_pixels))
 
 
 def ltsva_families_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, *, mdccm_min, baz_tol,
@@ -1022,16 +833,4 @@ def ltsva_families_batch(streams, lat_list, lon_list, window_length, window_over
     streams = list(streams)
     if not streams:
         planner.check_families(**params)
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    nchans = len(recs[0])
-    par = _families_keywords(nchans, alpha, params)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [ltsva_families(streams[0], lat_list, lon_list, window_length, window_overlap, alpha, rij, **params)]
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    if alpha == 1.0:
-        print('ALPHA is 1.0. Performing an ordinary least squares fit, NOT least trimmed squares.')
-    results = engine.process_batch(recs, fs, t0s, rij, [(None, None)], [window_length], window_overlap, alpha, prefiltered=True,
-                                   want_uncert=True, families=par)
-    return [_returns(res, nchans, alpha) + _returns_families(res, fs, t0) for res, t0 in zip(results, t0s)]
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij, _families(**params))

@@ -15,7 +15,8 @@ from scipy import signal
 
 from . import dist, engine, planner
 from .helpers import get_rij
-from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept, _returns_clean, _returns_music
+from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept, _returns_clean, _returns_music, _check_flag, \
+    _check_elements_strict, _check_clean_sources, _kept_request
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -92,16 +93,15 @@ def _prefix_stdict(stdict, band_number):
 def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist, FREQ_BAND_TYPE,
                freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, vector_len, rij=None, want_keys=True,
                key_prefixes=None, want_beam=False, want_subsample=False, min_velocity=None, slowness_grid=None,
-               want_grid_map=False, seed_period_fraction=None, want_consistency=False, capon=None, beam_taps=0,
-               process_keywords=None):
+               want_grid_map=False, seed_period_fraction=None, want_consistency=False, beam_taps=0, keywords=None):
     """One device pass over the given band indices -> (BandBatch, w rows, h rows).
 
     Everything on the host that does not need a GPU result — the filter responses (``sosfreqz``,
     narrow_band_least_squares.py:78-80), the BT caution (:83-87) and the text of the ``stdict`` time
     keys — runs while the pass is in flight (``host_overlap`` of ``engine.process``).  The traces are
-    uploaded row by row from the stream's own buffers.  ``capon`` / ``process_keywords``: a function of (rij, fs, npts,
-    edges, winlens) that returns further keywords of ``engine.process`` — the Capon tables, which need the call's own band
-    edges, through the first, any other feature's through the second."""
+    uploaded row by row from the stream's own buffers.  ``keywords``: a function of (rij, fs, npts, edges, winlens,
+    vector_len) that returns further keywords of ``engine.process`` — those of a feature that needs the call's own band edges
+    or window lengths, as the Capon tables do."""
     rows, fs, t0 = engine.stream_rows(st)
     if rij is None:
         rij = get_rij(lat_list, lon_list, len(rows))
@@ -138,8 +138,7 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
                          units_done=units_done, want_beam=want_beam, want_subsample=want_subsample,
                          min_velocity=min_velocity, slowness_grid=slowness_grid, want_grid_map=want_grid_map,
                          seed_halfwidths=seeds, want_consistency=want_consistency, beam_taps=beam_taps,
-                         **(capon(rij, fs, len(rows[0]), edges, winlens) if capon is not None else {}),
-                         **(process_keywords(rij, fs, len(rows[0]), edges, winlens) if process_keywords is not None else {}))
+                         **(keywords(rij, fs, len(rows[0]), edges, winlens, vector_len) if keywords is not None else {}))
     if ALPHA < 1.0 and want_keys and 'size' not in res.stdict:
         res.stdict['size'] = res.nchans            # (no band had a window: lts_array's dictionary still names the array size)
     if ALPHA < 1.0 and want_keys:
@@ -148,6 +147,63 @@ def _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freql
         # arrival and the return of this call
         engine.release_later(res.__dict__.pop('pattern_cache', None), res.__dict__.pop('keys', None))
     return res, out_rows['w'], out_rows['h']
+
+
+def _check_alpha(ALPHA):
+    if not (0.5 <= ALPHA <= 1.0):
+        raise ValueError('ALPHA must be in [0.5, 1.0].')
+
+
+def _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+               FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=None, alpha_range=True, **requests):
+    """The one body of the all-band single-stream entry points: the row length, the response rows, the range of ALPHA
+    (``alpha_range``: the reference's own call has no such check), the pass over every band with the ``requests`` of
+    ``_run_bands``, the reference's 9-tuple and behind it ``tail(res)``."""
+    vector_len = _vector_len(WINLEN_list, WINOVER, st)
+    _check_response_rows(w, h, freq_resp_list)
+    if alpha_range:
+        _check_alpha(ALPHA)
+    bands = list(range(NBANDS))
+    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
+                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
+                                       FILTER_RIPPLE, vector_len, rij=rij,
+                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], **requests)
+    # (the dictionary was built group by group while the GPU was still working)
+    out = _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
+                   w_array, h_array)
+    return out if tail is None else out + tail(res)
+
+
+def _computed(res, rank=0):
+    """Which cells of the (NBANDS, vector_len) result rows hold a window, with ``rank`` trailing axes of length 1."""
+    computed = np.arange(res.vel.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
+    return computed.reshape(computed.shape + (1,) * rank)
+
+
+def _zero_beyond(out, res, keys, rank=0):
+    """The fields ``keys`` of the dict ``out`` — derived on the host, (NBANDS, vector_len) and ``rank`` trailing axes — zero
+    beyond a band's windows, like ``vel_array``."""
+    computed = _computed(res, rank)
+    for k in keys:
+        out[k] = np.where(computed, out[k], 0.0)
+
+
+def _zero_spectra(out, res, names):
+    """The derived slowness fields of the spectra ``names`` (``capon``, ``bartlett``, ``music``) in a dict of ``lts_array``'s:
+    the maximum's and, where the pass kept peaks, every rank's; zero beyond a band's windows."""
+    _zero_beyond(out, res, [n + k for n in names for k in ('_vel', '_baz')])
+    peaks = [n for n in names if n + '_peak_vel' in out]
+    _zero_beyond(out, res, [n + k for n in peaks for k in ('_peak_vel', '_peak_baz')], 1)
+    _zero_beyond(out, res, [n + '_peak_slowness' for n in peaks], 2)
+    return out
+
+
+def _returns_grid(res, grid, grid_map):
+    """The grid returns of ``narrow_band_least_squares_grid``: the slowness at the maximum (zero-padded like ``vel_array``),
+    the three fields of the search and, when asked, the map."""
+    computed = _computed(res)
+    gvel, gbaz = (np.where(computed, a, 0.0) for a in grid_slowness(grid, res.grid_index))
+    return (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + ((res.grid_map,) if grid_map else ())
 
 
 def narrow_band_least_squares(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -162,16 +218,8 @@ def narrow_band_least_squares(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_lis
     1.0`` fills ``sig_tau_array`` and returns ``stdict_all = None``; ``ALPHA < 1.0`` returns the
     merged dropped-element dictionary and leaves ``sig_tau_array`` zero, as the reference does.
     ``rij`` (2, N) km is an extension: it overrides the lat/lon geometry."""
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands])
-    # (the dictionary was built group by group while the GPU was still working)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, alpha_range=False)
 
 
 def narrow_band_least_squares_beam(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -182,17 +230,8 @@ def narrow_band_least_squares_beam(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
     solve from the filtered band that is already there.  The first nine returns are those of
     ``narrow_band_least_squares``.  A trace so long that not one filtered band fits the HBM budget of a pass raises
     ``ValueError`` (the time-segmented path keeps the band on the host)."""
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=True)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (res.beam_power, res.fstat)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=lambda res: (res.beam_power, res.fstat), want_beam=True)
 
 
 def narrow_band_least_squares_consistency(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -207,23 +246,13 @@ def narrow_band_least_squares_consistency(WINLEN_list, WINOVER, ALPHA, st, lat_l
     nine returns are those of ``narrow_band_least_squares`` (of ``narrow_band_least_squares_subsample`` with
     ``subsample=True``).  A ``subsample`` that is not a bool and fewer than 3 elements (4 under LTS) raise ``ValueError``
     before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
-    if not isinstance(subsample, (bool, np.bool_)):
-        raise ValueError('subsample must be True or False, not %r' % (subsample,))
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
-        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
-                         'squares' % len(st))
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_subsample=bool(subsample),
-                                       want_consistency=True)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (res.consistency, res.closure_max, res.element_consistency)
+    _check_flag('subsample', subsample)
+    _check_alpha(ALPHA)
+    _check_elements_strict(len(st), ALPHA)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, alpha_range=False,
+                      tail=lambda res: (res.consistency, res.closure_max, res.element_consistency),
+                      want_subsample=bool(subsample), want_consistency=True)
 
 
 def narrow_band_least_squares_subsample(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -234,17 +263,8 @@ def narrow_band_least_squares_subsample(WINLEN_list, WINOVER, ALPHA, st, lat_lis
     Returns ``narrow_band_least_squares``'s nine values; ``t`` and the window counts are the same.  A trace so long that
     not one filtered band fits the HBM budget of a pass raises ``ValueError`` (the time-segmented path keeps the band on
     the host)."""
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_subsample=True)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, want_subsample=True)
 
 
 def narrow_band_least_squares_bounded(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -257,17 +277,8 @@ def narrow_band_least_squares_bounded(WINLEN_list, WINOVER, ALPHA, st, lat_list,
     before any GPU work.  A trace so long that not one filtered band fits the HBM budget of a pass raises ``ValueError``
     (the time-segmented path correlates the band slice by slice)."""
     planner.check_min_velocity(min_velocity)
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], min_velocity=min_velocity)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, min_velocity=min_velocity)
 
 
 def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -282,24 +293,10 @@ def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
     ``narrow_band_least_squares``.  A bad grid raises ``ValueError`` before any GPU work, and so does a trace so long that
     not one filtered band fits the HBM budget of a pass (the time-segmented path keeps the band on the host)."""
     grid = planner.check_slowness_grid(slowness_grid)
-    if not isinstance(grid_map, (bool, np.bool_)):
-        raise ValueError('grid_map must be True or False, not %r' % (grid_map,))
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], slowness_grid=grid,
-                                       want_grid_map=bool(grid_map))
-    gvel, gbaz = grid_slowness(grid, res.grid_index)
-    computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
-    gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + \
-        ((res.grid_map,) if grid_map else ())
+    _check_flag('grid_map', grid_map)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=lambda res: _returns_grid(res, grid, grid_map), slowness_grid=grid,
+                      want_grid_map=bool(grid_map))
 
 
 def narrow_band_least_squares_steered(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -315,30 +312,16 @@ def narrow_band_least_squares_steered(WINLEN_list, WINOVER, ALPHA, st, lat_list,
     before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
     taps = planner.check_steering(taps)
     grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
-    for name, flag in (('grid_map', grid_map), ('subsample', subsample)):
-        if not isinstance(flag, (bool, np.bool_)):
-            raise ValueError('%s must be True or False, not %r' % (name, flag))
+    _check_flag('grid_map', grid_map)
+    _check_flag('subsample', subsample)
     if grid_map and grid is None:
         raise ValueError('grid_map needs slowness_grid')
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=True,
-                                       want_subsample=bool(subsample), slowness_grid=grid, want_grid_map=bool(grid_map),
-                                       beam_taps=taps)
-    out = _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                   w_array, h_array) + (res.beam_power, res.fstat)
-    if grid is None:
-        return out
-    gvel, gbaz = grid_slowness(grid, res.grid_index)
-    computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
-    gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)
-    return out + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + ((res.grid_map,) if grid_map else ())
+
+    def tail(res):
+        return (res.beam_power, res.fstat) + (() if grid is None else _returns_grid(res, grid, grid_map))
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=tail, want_beam=True, want_subsample=bool(subsample),
+                      slowness_grid=grid, want_grid_map=bool(grid_map), beam_taps=taps)
 
 
 def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -357,22 +340,12 @@ def narrow_band_least_squares_capon(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     ``ValueError`` before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a
     pass."""
     grid = planner.check_slowness_grid(slowness_grid)
-    if not isinstance(maps, (bool, np.bool_)):
-        raise ValueError('maps must be True or False, not %r' % (maps,))
+    _check_flag('maps', maps)
     peak_kw = _peak_keywords(grid, peaks, peak_floor)
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    keywords = _capon_band_keywords(len(st), grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER, vector_len)
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
-    out = _zero_padded_capon(_returns_capon(res, grid, bool(maps), band=None), res, bool(peak_kw))
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (out,)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij,
+                      tail=lambda res: (_zero_spectra(_returns_capon(res, grid, bool(maps), band=None), res, ('capon', 'bartlett')),),
+                      keywords=_capon_band_keywords(len(st), grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER))
 
 
 def narrow_band_least_squares_clean(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -386,29 +359,16 @@ def narrow_band_least_squares_clean(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     ...) with zeros beyond a band's windows.  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
     grid = planner.check_slowness_grid(slowness_grid)
     clean = planner.check_capon_clean(iterations, gain, floor, False)
-    if isinstance(max_sources, (bool, np.bool_)) or not isinstance(max_sources, (int, np.integer)) or int(max_sources) < 1:
-        raise ValueError('max_sources must be a positive integer, not %r' % (max_sources,))
-    if merge_radius is None:
-        merge_radius = 1.5 * float(np.max(planner.grid_cells(grid)[1]))
-    elif not planner._real(merge_radius) or not (0.0 <= float(merge_radius) < np.inf):
-        raise ValueError('merge_radius must be a finite number >= 0 (s/km), not %r' % (merge_radius,))
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    keywords = _capon_band_keywords(len(st), grid, capon_freqs, snapshots, 0.01, False, dict(capon_clean=clean), WINOVER, vector_len)
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
-    out = _returns_clean(res, grid, float(merge_radius), int(max_sources), band=None)
-    computed = np.arange(res.clean_count.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
-    for k in ('clean_vel', 'clean_baz', 'source_power', 'source_vel', 'source_baz'):
-        out[k] = np.where(computed[..., None], out[k], 0.0)
-    out['source_slowness'] = np.where(computed[..., None, None], out['source_slowness'], 0.0)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (out,)
+    radius, max_sources = _check_clean_sources(grid, merge_radius, max_sources)
+
+    def tail(res):
+        out = _returns_clean(res, grid, radius, max_sources, band=None)
+        _zero_beyond(out, res, ('clean_vel', 'clean_baz', 'source_power', 'source_vel', 'source_baz'), 1)
+        _zero_beyond(out, res, ('source_slowness',), 2)
+        return (out,)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=tail,
+                      keywords=_capon_band_keywords(len(st), grid, capon_freqs, snapshots, 0.01, False, dict(capon_clean=clean), WINOVER))
 
 
 def narrow_band_least_squares_music(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -423,32 +383,17 @@ def narrow_band_least_squares_music(WINLEN_list, WINOVER, ALPHA, st, lat_list, l
     grid = planner.check_slowness_grid(slowness_grid)
     peak_kw = _peak_keywords(grid, peaks, 0.25)
     music = planner.check_capon_music(len(st), sources, eig_floor, maps, vectors, bool(peak_kw), peak_floor)
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    keywords = _capon_band_keywords(len(st), grid, capon_freqs, snapshots, 0.01, False, dict(peak_kw, capon_music=music), WINOVER, vector_len)
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
-    out = _returns_music(res, grid, band=None)
-    computed = np.arange(res.music_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
-    for k in ('music_vel', 'music_baz'):
-        out[k] = np.where(computed, out[k], 0.0)
-    if 'music_peak_vel' in out:
-        for k in ('music_peak_vel', 'music_peak_baz'):
-            out[k] = np.where(computed[..., None], out[k], 0.0)
-        out['music_peak_slowness'] = np.where(computed[..., None, None], out['music_peak_slowness'], 0.0)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (out,)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij,
+                      tail=lambda res: (_zero_spectra(_returns_music(res, grid, band=None), res, ('music',)),),
+                      keywords=_capon_band_keywords(len(st), grid, capon_freqs, snapshots, 0.01, False,
+                                                    dict(peak_kw, capon_music=music), WINOVER))
 
 
-def _capon_band_keywords(nchans, grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER, vector_len):
-    """The ``capon`` callable of ``_run_bands`` behind the Capon arguments of a narrow-band call: the Capon keywords of
+def _capon_band_keywords(nchans, grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER):
+    """The ``keywords`` callable of ``_run_bands`` behind the Capon arguments of a narrow-band call: the Capon keywords of
     ``engine.process`` for the call's bands, their frequencies and snapshots defaulted and checked."""
-    def keywords(rij_used, fs, npts, edges, winlens):
+    def keywords(rij_used, fs, npts, edges, winlens, vector_len):
         W = engine.plan_windows(npts, fs, winlens, WINOVER, vector_len)[0]
         f = planner.capon_frequencies(edges) if capon_freqs is None else capon_freqs
         snaps = snapshots
@@ -459,19 +404,6 @@ def _capon_band_keywords(nchans, grid, capon_freqs, snapshots, loading, maps, pe
         return dict(capon_grid=grid, capon_freqs=f, capon_snapshots=snaps, capon_loading=loading, want_capon_maps=bool(maps),
                     **peak_kw)
     return keywords
-
-
-def _zero_padded_capon(out, res, with_peaks):
-    """The derived slowness fields of ``_returns_capon``'s dict, zero beyond a band's windows like ``vel_array``."""
-    computed = np.arange(res.capon_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
-    for k in ('capon_vel', 'capon_baz', 'bartlett_vel', 'bartlett_baz'):
-        out[k] = np.where(computed, out[k], 0.0)
-    if with_peaks:
-        for which in ('capon', 'bartlett'):
-            for k in ('_peak_vel', '_peak_baz'):
-                out[which + k] = np.where(computed[..., None], out[which + k], 0.0)
-            out[which + '_peak_slowness'] = np.where(computed[..., None, None], out[which + '_peak_slowness'], 0.0)
-    return out
 
 
 def narrow_band_least_squares_kept(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -490,32 +422,24 @@ def narrow_band_least_squares_kept(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
     grid = None if slowness_grid is None else planner.check_slowness_grid(slowness_grid)
     if grid is None and (capon_freqs is not None or snapshots is not None or maps or peaks):
         raise ValueError('capon_freqs, snapshots, maps and peaks need slowness_grid')
-    if not isinstance(maps, (bool, np.bool_)):
-        raise ValueError('maps must be True or False, not %r' % (maps,))
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
-        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
-                         'squares' % len(st))
+    _check_flag('maps', maps)
+    _check_alpha(ALPHA)
+    _check_elements_strict(len(st), ALPHA)
     kept = planner.check_kept(len(st), min_pairs, beam, grid is not None)
     peak_kw = {} if grid is None else _peak_keywords(grid, peaks, peak_floor)
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    bands = list(range(NBANDS))
-    capon_kw = None if grid is None else _capon_band_keywords(len(st), grid, capon_freqs, snapshots, loading, maps, peak_kw,
-                                                              WINOVER, vector_len)
+    capon_kw = None if grid is None else _capon_band_keywords(len(st), grid, capon_freqs, snapshots, loading, maps, peak_kw, WINOVER)
 
     def keywords(*args):           # (the keywords that ride beside the Capon ones into ``engine.process``)
         return dict({} if capon_kw is None else capon_kw(*args), kept=kept)
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], want_beam=kept[1], capon=keywords)
-    out = _returns_kept(res, len(st), kept[1], None, band=None)
-    if grid is not None:
-        out.update(_zero_padded_capon(_returns_capon(res, grid, bool(maps), band=None), res, bool(peak_kw)))
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (out,)
+
+    def tail(res):
+        out = _returns_kept(res, len(st), kept[1], None, band=None)
+        if grid is not None:
+            out.update(_zero_spectra(_returns_capon(res, grid, bool(maps), band=None), res, ('capon', 'bartlett')))
+        return (out,)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=tail, alpha_range=False, want_beam=kept[1],
+                      keywords=keywords)
 
 
 def narrow_band_least_squares_seeded(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -530,24 +454,10 @@ def narrow_band_least_squares_seeded(WINLEN_list, WINOVER, ALPHA, st, lat_list, 
     before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
     grid = planner.check_slowness_grid(slowness_grid)
     planner.seed_halfwidths([1.0], 1.0, period_fraction)         # (the check of period_fraction, before any GPU work)
-    if not isinstance(grid_map, (bool, np.bool_)):
-        raise ValueError('grid_map must be True or False, not %r' % (grid_map,))
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], slowness_grid=grid,
-                                       want_grid_map=bool(grid_map), seed_period_fraction=period_fraction)
-    gvel, gbaz = grid_slowness(grid, res.grid_index)
-    computed = np.arange(res.grid_index.shape[1])[None, :] < np.asarray(res.nwin)[:, None]
-    gvel, gbaz = np.where(computed, gvel, 0.0), np.where(computed, gbaz, 0.0)      # (zero-padded like vel_array)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (gvel, gbaz, res.grid_fstat, res.grid_power, res.grid_index) + \
-        ((res.grid_map,) if grid_map else ())
+    _check_flag('grid_map', grid_map)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=lambda res: _returns_grid(res, grid, grid_map),
+                      slowness_grid=grid, want_grid_map=bool(grid_map), seed_period_fraction=period_fraction)
 
 
 def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -560,14 +470,22 @@ def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_li
     from the streams' own buffers.  Window times come from each stream's own start time, the dictionary is per
     recording; ``w_array`` / ``h_array`` are equal for all recordings (separate copies).  The BT caution prints once
     per batch.  An empty sequence gives ``[]``."""
+    return _all_bands_batch(narrow_band_least_squares, WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
+                            FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij)
+
+
+def _all_bands_batch(single, WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE,
+                     freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, params=None, tail=None, **requests):
+    """The one body of the ``_batch`` entry points: ``single`` with its keywords ``params`` for a batch of one recording, else
+    one pass over every band of every recording with the ``requests`` of ``engine.process_batch`` and, per recording, the
+    reference's 9-tuple and behind it ``tail(res, edges, fs, t0)``."""
     streams = list(streams)
     if not streams:
         return []
     recs, fs, t0s = engine.batch_rows(streams)
     if len(streams) == 1:          # a batch of one IS the single call (which overlaps its upload with the plan)
-        return [narrow_band_least_squares(WINLEN_list, WINOVER, ALPHA, streams[0], lat_list, lon_list, NBANDS, w, h,
-                                          freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                          FILTER_RIPPLE, rij=rij)]
+        return [single(WINLEN_list, WINOVER, ALPHA, streams[0], lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE,
+                       freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=rij, **(params or {}))]
     vector_len = _vector_len(WINLEN_list, WINOVER, streams[0])
     _check_response_rows(w, h, freq_resp_list)
     nchans = len(recs[0])
@@ -577,18 +495,18 @@ def narrow_band_least_squares_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_li
     edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
     winlens = [WINLEN_list[ii] for ii in bands]
     results = engine.process_batch(recs, fs, t0s, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
-                                   FILTER_RIPPLE, vector_len=vector_len)
+                                   FILTER_RIPPLE, vector_len=vector_len, **requests)
     w_rows, h_rows = filter_responses(results[0].sos, freq_resp_list, fs)
     _bt_cautions(winlens, edges)
     prefixes = [_band_prefix(ii + 1) for ii in bands]
     out = []
-    for res in results:
+    for res, t0 in zip(results, t0s):
         stdict_all = None
         if ALPHA != 1.0:
             keys = engine.time_key_text(res.t, res.nwin, prefixes)
             stdict_all = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, res.nchans, keys)
         out.append(_returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, stdict_all, res.nwin,
-                            w_rows.copy(), h_rows.copy()))
+                            w_rows.copy(), h_rows.copy()) + (() if tail is None else tail(res, edges, fs, t0)))
     return out
 
 
@@ -900,30 +818,17 @@ def narrow_band_least_squares_beam_trace(WINLEN_list, WINOVER, ALPHA, st, lat_li
     are already there.  The first nine returns are those of ``narrow_band_least_squares``.  Whatever the library would
     refuse raises ``ValueError`` before any GPU work, and so does a trace so long that not one filtered band fits the HBM
     budget of a pass."""
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
-        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
-                         'squares' % len(st))
-    if not isinstance(kept, (bool, np.bool_)):
-        raise ValueError('kept must be True or False, not %r' % (kept,))
+    _check_alpha(ALPHA)
+    _check_elements_strict(len(st), ALPHA)
+    _check_flag('kept', kept)
     if not isinstance(window, str):
         raise ValueError("window must be 'hann' or 'boxcar', not %r" % (window,))
     kept_kw = planner.check_kept(len(st), None, False, False) if kept else None
     planner.check_beam_trace([1], window, mdccm_min, bool(kept), kept_kw is not None)       # (the bands' own lengths: engine.process)
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    bands = list(range(NBANDS))
     want = dict(window=window, mdccm_min=mdccm_min, kept=bool(kept))
-
-    def keywords(*args):           # (the keywords that ride into ``engine.process``)
-        return dict(kept=kept_kw, want_beam_trace=want)
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], capon=keywords)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (res.beam_trace,)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=lambda res: (res.beam_trace,), alpha_range=False,
+                      keywords=lambda *args: dict(kept=kept_kw, want_beam_trace=want))
 
 
 def narrow_band_least_squares_element_delays(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -939,36 +844,23 @@ def narrow_band_least_squares_element_delays(WINLEN_list, WINOVER, ALPHA, st, la
     ``lts_array.ltsva_kept``), and the dict also holds ``dropped_mask`` / ``kept_count`` (NBANDS, vector_len).  The first nine
     returns are those of ``narrow_band_least_squares``.  Whatever the library would refuse raises ``ValueError`` before any
     GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
-    if not (0.5 <= ALPHA <= 1.0):
-        raise ValueError('ALPHA must be in [0.5, 1.0].')
-    if len(st) < 3 or (ALPHA < 1.0 and len(st) < 4):
-        raise ValueError('%d array elements: at least 3 are needed for the least squares estimate, 4 for least trimmed '
-                         'squares' % len(st))
-    if not isinstance(kept, (bool, np.bool_)):
-        raise ValueError('kept must be True or False, not %r' % (kept,))
-    if min_pairs is not None and not kept:
-        raise ValueError('min_pairs needs kept=True')
-    kept_kw = planner.check_kept(len(st), min_pairs, False, False) if kept else None
+    _check_alpha(ALPHA)
+    _check_elements_strict(len(st), ALPHA)
+    kept_kw = _kept_request(len(st), kept, min_pairs)
     if max_shift is not None:
         engine._check_element_delays(max_shift, bool(kept), NBANDS, len(st), kept_kw)
     elif len(st) > 32:
         raise ValueError('the element delays take at most 32 array elements, not %d' % len(st))
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    bands = list(range(NBANDS))
 
-    def keywords(rij_, fs, npts, edges, winlens):           # (the keywords that ride into ``engine.process``)
+    def keywords(rij_, fs, npts, edges, winlens, vector_len):           # (the keywords that ride into ``engine.process``)
         shifts = max_shift if max_shift is not None else planner.element_shifts([e[1] for e in edges], fs)
         return dict(kept=kept_kw, element_max_shift=shifts, element_delays_kept=bool(kept))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands], process_keywords=keywords)
-    out = dict(element_delay=res.element_delay, element_cc=res.element_cc, element_shift=res.element_shift)
-    if kept:
-        out.update(dropped_mask=res.dropped_mask, kept_count=res.kept_count)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + (out,)
+
+    def tail(res):
+        fields = ('element_delay', 'element_cc', 'element_shift') + (('dropped_mask', 'kept_count') if kept else ())
+        return ({k: getattr(res, k) for k in fields},)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=tail, alpha_range=False, keywords=keywords)
 
 
 def _families_of(res, edges, fs, t0):
@@ -995,17 +887,12 @@ def narrow_band_least_squares_families(WINLEN_list, WINOVER, ALPHA, st, lat_list
     Labelled on the GPU behind the pass's last solve; a call whose bands run in several passes is labelled by the same
     kernels on the assembled grids, with the same result.  ``ValueError`` before any GPU work for what the library refuses."""
     par = planner.check_families(mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max, band_reach, time_reach, min_pixels)
-    vector_len = _vector_len(WINLEN_list, WINOVER, st)
-    _check_response_rows(w, h, freq_resp_list)
-    bands = list(range(NBANDS))
-    res, w_array, h_array = _run_bands(bands, WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, freqlist,
-                                       FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                       FILTER_RIPPLE, vector_len, rij=rij,
-                                       key_prefixes=[_band_prefix(ii + 1) for ii in bands],
-                                       process_keywords=lambda *a: dict(families=par))
-    _, fs, t0 = engine.stream_rows(st)
-    return _returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, getattr(res, 'stdict', None), res.nwin,
-                    w_array, h_array) + _families_of(res, _band_edges(freqlist, FREQ_BAND_TYPE, bands), fs, t0)
+
+    def tail(res):
+        _, fs, t0 = engine.stream_rows(st)
+        return _families_of(res, _band_edges(freqlist, FREQ_BAND_TYPE, range(NBANDS)), fs, t0)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=tail, alpha_range=False, keywords=lambda *a: dict(families=par))
 
 
 def narrow_band_least_squares_families_batch(WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h, freqlist,
@@ -1016,36 +903,9 @@ def narrow_band_least_squares_families_batch(WINLEN_list, WINOVER, ALPHA, stream
     element i equal to the single call on ``streams[i]``; the streams as for ``narrow_band_least_squares_batch``.  Recordings
     never link: every recording has its own families, numbered from 0."""
     par = planner.check_families(mdccm_min, baz_tol, vel_tol, vel_min, vel_max, sigma_tau_max, band_reach, time_reach, min_pixels)
-    streams = list(streams)
-    if not streams:
-        return []
-    recs, fs, t0s = engine.batch_rows(streams)
-    if len(streams) == 1:          # a batch of one IS the single call
-        return [narrow_band_least_squares_families(WINLEN_list, WINOVER, ALPHA, streams[0], lat_list, lon_list, NBANDS, w, h,
-                                                   freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER,
-                                                   FILTER_RIPPLE, rij=rij, **par)]
-    vector_len = _vector_len(WINLEN_list, WINOVER, streams[0])
-    _check_response_rows(w, h, freq_resp_list)
-    nchans = len(recs[0])
-    if rij is None:
-        rij = get_rij(lat_list, lon_list, nchans)
-    bands = list(range(NBANDS))
-    edges = _band_edges(freqlist, FREQ_BAND_TYPE, bands)
-    winlens = [WINLEN_list[ii] for ii in bands]
-    results = engine.process_batch(recs, fs, t0s, rij, edges, winlens, WINOVER, ALPHA, FILTER_TYPE, FILTER_ORDER,
-                                   FILTER_RIPPLE, vector_len=vector_len, families=par)
-    w_rows, h_rows = filter_responses(results[0].sos, freq_resp_list, fs)
-    _bt_cautions(winlens, edges)
-    prefixes = [_band_prefix(ii + 1) for ii in bands]
-    out = []
-    for res, t0 in zip(results, t0s):
-        stdict_all = None
-        if ALPHA != 1.0:
-            keys = engine.time_key_text(res.t, res.nwin, prefixes)
-            stdict_all = engine.stdict_from_mask(res.mask, res.nwin, res.pair_idx, res.nchans, keys)
-        out.append(_returns(ALPHA, res.vel, res.baz, res.mdccm, res.sigma_tau, res.t, stdict_all, res.nwin,
-                            w_rows.copy(), h_rows.copy()) + _families_of(res, edges, fs, t0))
-    return out
+    return _all_bands_batch(narrow_band_least_squares_families, WINLEN_list, WINOVER, ALPHA, streams, lat_list, lon_list, NBANDS, w, h,
+                            freqlist, FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, par, _families_of,
+                            families=par)
 
 
 def label_families(vel, baz, mdccm, sigma_tau, nwin, winlens, incs, *, nseg=1, device=None, **params):
