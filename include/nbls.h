@@ -901,6 +901,56 @@ int nbls_label_families(nbls_handle* h, const nbls_family_params* params, int32_
                         const double* mdccm, const double* sigma_tau /* NULL iff the gate is off */, int32_t* family,
                         int32_t* nfamilies, int64_t* table, int64_t capacity);
 
+/* ---- The grid maximum refined between grid points ----
+ * The slowness-grid search (section 15) returns an index; steered at fractional-sample delays (section 22) F is a continuous
+ * function of the slowness, so a coarse grid can find the lobe and a local search climb it.  The request needs a plan with a
+ * beam grid and fractional-sample steering (taps L in {4, 6, 8}) and holds `levels` R in 1..12 and `step` (h0, h1) in s/km,
+ * both finite and > 0; the usual step is the grid's lattice step.  For the unit of result row r and window w, over the full
+ * array exactly as section 15 takes it:
+ *   start    g* = grid_index.  g* = -1: slowness, fstat, power and stencil are NaN, every path entry is -1.
+ *            Otherwise c = (grid[g*][0], grid[g*][1]), Fc = grid_fstat, Pc = grid_power (the grid kernel's own bits).
+ *   level    l = 1 .. R:   e = (ldexp(h0, -l), ldexp(h1, -l))                  (exact: step * 2^-l)
+ *            candidates j = 0 .. 8:  a = j / 3 - 1,  b = j % 3 - 1  (integer division)
+ *                                    s_j = (c0 + a * e0,  c1 + b * e1)         (a * e exact, one rounded addition)
+ *            j = 4 is the centre and is not evaluated again: F_4 = Fc, P_4 = Pc.
+ *            j != 4: F_j, P_j = F and P of section 22 with z = s_j:
+ *                    tau_i = fs * (xij[i-1][0] * s_j0 + xij[i-1][1] * s_j1) un-fused, tau_0 = 0, n = floor(tau), mu = tau - n,
+ *                    the coefficients of section 22, the taps ascending, every product rounded before its addition.
+ *                    b[t], S_b, S_t, D, the +inf and NaN rules, the mapping of t to lanes, and every reduction order
+ *                    are those of the grid kernel for a grid point of that slowness.
+ *            choose  j* = the best candidate under the order "F descending (+inf first); the centre before any other
+ *                    candidate; then j ascending".  A NaN F is no candidate.  (Fc is never NaN when g* >= 0.)
+ *            record  path[l-1] = j*.  On the last level stencil[j] = F_j for j = 0 .. 8, taken before the move.
+ *            move    c = s_j*, Fc = F_j*, Pc = P_j*.  (j* = 4 leaves all three unchanged.)
+ *   outputs  grid_refined_slowness (2 doubles) = c,  grid_refined_fstat = Fc,  grid_refined_power = Pc,
+ *            grid_refined_path (R int32),  grid_refined_stencil (9 doubles).
+ *            Cells beyond nwin[r] and outside a window slice are zeros.
+ * So grid_refined_fstat >= grid_fstat, with equal bits where every path entry is 4; the slowness is what float64 gives when
+ * it replays the path from grid[g*]; |c - grid[g*]| <= step (1 - 2^-R) on each axis; the first l entries of the path of an
+ * R-level plan are the path of an l-level plan.  A candidate's F depends on (N, W, taps, s_j) alone: single, streamed, batched,
+ * window-sliced and HBM-round passes agree bit for bit.  Estimator 0 only, as for the grid.  The coarse step must not exceed
+ * the width of the main lobe: a grid that misses the lobe gives the search nothing to climb.
+ *   nbls_set_beam_grid_refinement(h, levels, step)   read by the next nbls_plan; levels = 0 or step = NULL switches it off (the
+ *                            default: such a plan launches exactly what it launched before).  NBLS_ERR_ARG, the handle
+ *                            unchanged, for levels outside 0..12 or a step that is not finite and > 0.  The plan derives one
+ *                            halo H_r = grid_halo + ceil(fs max_i(|xij[i][0]| h0 + |xij[i][1]| h1)) + 1 over the pairs (0, i)
+ *                            and uses it everywhere; nbls_plan returns NBLS_ERR_ARG if H_r reaches 2^30, NBLS_ERR_STATE if
+ *                            the refinement is on without a grid or without interpolation, NBLS_ERR_UNSUPPORTED with a lag
+ *                            seed (nbls_set_lag_seed: the seed keeps the unrefined maximum) and with an RCCL communicator.
+ *                            One launch behind the grid search of every unit batch.
+ *   nbls_fetch_beam_grid_refined(h, slowness, fstat, power, path, stencil)   [rows][vector_len][2] | [rows][vector_len] twice |
+ *                            [rows][vector_len][R] int32 | [rows][vector_len][9]; any may be NULL.  Waits for the pass like
+ *                            nbls_fetch_beam; NBLS_ERR_STATE if the plan did not ask; zeros until a pass of the plan has run
+ *                            the solve stage.
+ *   nbls_beam_grid_refine_lds_bytes(nelem, W, halo)   a pure host function, like nbls_beam_grid_lds_bytes: the dynamic LDS
+ *                            of the staged form, nelem * (W + 2 halo) * 8 bytes where that is at most 156 KiB, else 0: the
+ *                            form that reads the filtered band from global memory.  Both give the same bits.  NBLS_ERR_ARG
+ *                            for nelem < 1, W < 1 or halo < 0. */
+#define NBLS_BEAM_GRID_REFINE_MAX_LEVELS 12
+int nbls_set_beam_grid_refinement(nbls_handle* h, int32_t levels /* 0 = off */, const double* step /* [2]; NULL = off */);
+int nbls_fetch_beam_grid_refined(nbls_handle* h, double* slowness, double* fstat, double* power, int32_t* path, double* stencil);
+int nbls_beam_grid_refine_lds_bytes(int32_t nelem, int32_t W, int32_t halo);
+
 /* Copy the filtered+tapered trace of planned band `band` to host: out[nchans][npts]. */
 int nbls_fetch_filtered(nbls_handle* h, int32_t band, double* out);
 

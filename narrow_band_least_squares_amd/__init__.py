@@ -16,12 +16,12 @@ from .narrow_band_least_squares import (narrow_band_least_squares, narrow_band_l
                                         narrow_band_least_squares_element_delays, narrow_band_least_squares_clean,
                                         narrow_band_least_squares_music, narrow_band_least_squares_families,
                                         narrow_band_least_squares_families_batch, label_families,
-                                        narrow_band_least_squares_steered)
+                                        narrow_band_least_squares_steered, narrow_band_least_squares_grid_refined)
 from .lts_array import ltsva, ltsva_batch, ltsva_multi, ltsva_beam, ltsva_subsample, ltsva_bounded, ltsva_grid, \
     ltsva_seeded, ltsva_consistency, ltsva_capon, ltsva_capon_batch, ltsva_kept, ltsva_kept_batch, ltsva_beam_trace, \
     ltsva_beam_trace_batch, ltsva_steered, ltsva_steered_batch, ltsva_element_delays, ltsva_element_delays_batch, \
     ltsva_clean, ltsva_clean_batch, clean_map, clean_sources, ltsva_music, ltsva_music_batch, ltsva_families, \
-    ltsva_families_batch
+    ltsva_families_batch, ltsva_grid_refined, ltsva_grid_refined_batch
 from .helpers import (get_freqlist, get_winlenlist, filter_data, make_float, get_rij,
                       write_txtfile, read_txtfile)
 from .stream import Stream, Trace, Stats
@@ -42,7 +42,8 @@ __all__ = ['narrow_band_least_squares', 'narrow_band_loop', 'narrow_band_least_s
            'narrow_band_least_squares_clean', 'ltsva_clean', 'ltsva_clean_batch', 'clean_map', 'clean_sources',
            'narrow_band_least_squares_music', 'ltsva_music', 'ltsva_music_batch',
            'narrow_band_least_squares_families', 'narrow_band_least_squares_families_batch', 'ltsva_families',
-           'ltsva_families_batch', 'label_families']
+           'ltsva_families_batch', 'label_families',
+           'narrow_band_least_squares_grid_refined', 'ltsva_grid_refined', 'ltsva_grid_refined_batch']
 
 
 def install_as_reference_modules():

@@ -41,8 +41,10 @@ EXPORTS = [
     'nbls_set_beam_interpolation', 'nbls_fetch_beam_grid_coefficients',
     'nbls_set_element_delays', 'nbls_fetch_element_delays', 'nbls_element_delay_lds_bytes',
     'nbls_set_families', 'nbls_fetch_families', 'nbls_label_families',
+    'nbls_set_beam_grid_refinement', 'nbls_fetch_beam_grid_refined', 'nbls_beam_grid_refine_lds_bytes',
 ]
 STEER_TAPS = (0, 4, 6, 8)  # taps of nbls_set_beam_interpolation (0: whole-sample delays)
+GRID_REFINE_MAX_LEVELS = 12   # levels of nbls_set_beam_grid_refinement (NBLS_BEAM_GRID_REFINE_MAX_LEVELS)
 BEAM_GRID_MAX = 65536    # grid points of a slowness-grid search (NBLS_BEAM_GRID_MAX)
 BEAM_GRID_WAVES = 16     # waves of a workgroup of the search kernel (NBLS_BEAM_GRID_WAVES)
 CAPON_GRID_MAX = 65536   # grid points of the Capon spectra (NBLS_CAPON_GRID_MAX)
@@ -210,6 +212,9 @@ def load_library(path=None):
     lib.nbls_fetch_beam_grid_delays.argtypes = [vp, ip]
     lib.nbls_beam_grid_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.nbls_set_beam_interpolation.argtypes = [vp, C.c_int32]
+    lib.nbls_set_beam_grid_refinement.argtypes = [vp, C.c_int32, dp]
+    lib.nbls_fetch_beam_grid_refined.argtypes = [vp, dp, dp, dp, ip, dp]
+    lib.nbls_beam_grid_refine_lds_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.nbls_fetch_beam_grid_coefficients.argtypes = [vp, dp]
     lib.nbls_set_capon.argtypes = [vp, dp, C.c_int32, dp, ip, ip, C.c_int32, C.c_double, C.c_int32]
     lib.nbls_fetch_capon.argtypes = [vp, ip, dp, ip, dp]
@@ -345,6 +350,7 @@ class Handle:
         self.est_npairs = []            # pair counts of the further estimators (set_estimators)
         self._want_grid_n = self.grid_n = 0   # grid points of set_beam_grid / of the plan
         self._want_taps = self.taps = 0       # taps of set_beam_interpolation / of the plan
+        self._want_refine_levels = self.refine_levels = 0     # levels of set_beam_grid_refinement / of the plan
         self._want_capon = self.capon = None  # (G, snapshot lengths) of set_capon / of the plan
         self._want_capon_peaks = self.capon_peaks = 0     # K of set_capon_peaks / of the plan
         self._want_capon_clean = self.capon_clean = 0     # I of set_capon_clean / of the plan
@@ -475,6 +481,7 @@ class Handle:
         self._nsec = nsec
         self.grid_n = self._want_grid_n
         self.taps = self._want_taps
+        self.refine_levels = self._want_refine_levels
         self.capon = self._want_capon
         self.capon_peaks = self._want_capon_peaks
         self.capon_clean = self._want_capon_clean if self.capon else 0
@@ -929,6 +936,33 @@ class Handle:
         section 22; ``planner.steering_error`` has its error); 0 switches that off."""
         self._chk(self.lib.nbls_set_beam_interpolation(self._h, int(taps)))
         self._want_taps = int(taps)
+
+    def set_beam_grid_refinement(self, levels, step):
+        """The next plans — plans with a slowness grid (``set_beam_grid``) steered at fractional-sample delays
+        (``set_beam_interpolation``) — refine every window's grid maximum between the grid points: ``levels`` (1..12) times
+        the best of the centre and its eight neighbours at ``step`` (h0, h1) s/km halved per level
+        (``nbls_set_beam_grid_refinement``; ``planner.check_grid_refinement`` makes the step from the
+        grid).  ``levels=0`` or ``step=None`` switches that off; both arguments are required."""
+        if not levels or step is None:
+            self._chk(self.lib.nbls_set_beam_grid_refinement(self._h, 0, None))
+            self._want_refine_levels = 0
+            return
+        s = _f64(step).reshape(-1)
+        if s.shape != (2,):
+            raise ValueError('the refinement step must be two values (h0, h1), not %r' % (np.shape(step),))
+        self._chk(self.lib.nbls_set_beam_grid_refinement(self._h, int(levels), _dptr(s)))
+        self._want_refine_levels = int(levels)
+
+    def fetch_beam_grid_refined(self):
+        """-> (grid_refined_slowness (rows, vector_len, 2), grid_refined_fstat, grid_refined_power (rows, vector_len),
+        grid_refined_path (rows, vector_len, R) int32, grid_refined_stencil (rows, vector_len, 9)) of a plan that refines its
+        grid maximum."""
+        cells = (self.nbands, self.vector_len)
+        slow, fstat, power = np.empty(cells + (2,)), np.empty(cells), np.empty(cells)
+        path = np.empty(cells + (max(self.refine_levels, 1),), dtype=np.int32)
+        stencil = np.empty(cells + (9,))
+        self._chk(self.lib.nbls_fetch_beam_grid_refined(self._h, _dptr(slow), _dptr(fstat), _dptr(power), _iptr(path), _dptr(stencil)))
+        return slow, fstat, power, path, stencil
 
     def fetch_beam_grid_coefficients(self):
         """-> the Lagrange coefficients of an interpolated grid plan, (G, nelem, taps); ``fetch_beam_grid_delays`` then

@@ -21,14 +21,16 @@ F8, I4, U4, C16 = np.float64, np.int32, np.uint32, np.complex128
 # method, whether it takes an estimator index, whether it is called once per result row (rows (nbands, ...)) instead of once
 # per pass (rows (nbands, vector_len, ...)), and per call its arguments and its fields in the order the method returns them
 # (a method with one field returns the bare array).  A field is (name, trailing shape, dtype); N elements, P pairs, G grid
-# points of the beam grid, C of the Capon grid, K peaks, I CLEAN-SC iterations, T samples of the trace.
-Group = collections.namedtuple('Group', 'applies method est per_row calls')
+# points of the beam grid, R levels of its refinement, C of the Capon grid, K peaks, I CLEAN-SC iterations, T samples of the
+# trace.
+# ``sparse``: a result carries the fields only where the group applies (the others are None there).
+Group = collections.namedtuple('Group', 'applies method est per_row calls sparse', defaults=(False,))
 
 
-def _group(applies, method, *fields, est=False, per_row=False, args=((),)):
+def _group(applies, method, *fields, est=False, per_row=False, args=((),), sparse=False):
     if len(args) == 1:
         fields = (fields,)
-    return Group(applies, method, est, per_row, tuple(zip(args, fields)))
+    return Group(applies, method, est, per_row, tuple(zip(args, fields)), sparse)
 
 
 def _peaks(which):
@@ -47,6 +49,9 @@ RESULT_GROUPS = (
     _group(lambda w: w.want_lag and w.want_subsample, 'fetch_lag_fraction', ('lag_frac', ('P',), F8), est=True),
     _group(lambda w: w.grid_points, 'fetch_beam_grid', ('grid_index', (), I4), ('grid_fstat', (), F8), ('grid_power', (), F8)),
     _group(lambda w: w.grid_points and w.want_grid_map, 'fetch_beam_grid_map', ('grid_map', ('G',), F8)),
+    _group(lambda w: w.grid_points and w.grid_refine_levels, 'fetch_beam_grid_refined', ('grid_refined_slowness', (2,), F8),
+           ('grid_refined_fstat', (), F8), ('grid_refined_power', (), F8), ('grid_refined_path', ('R',), I4),
+           ('grid_refined_stencil', (9,), F8), sparse=True),
     _group(lambda w: w.capon_points, 'fetch_capon', ('capon_index', (), I4), ('capon_power', (), F8),
            ('bartlett_index', (), I4), ('bartlett_power', (), F8)),
     _group(lambda w: w.capon_points and w.want_capon_maps, 'fetch_capon_maps', ('capon_map', ('C',), F8),
@@ -93,6 +98,17 @@ def _check_seed(seed_halfwidths, nbands, sgrid, min_velocity):
         raise ValueError('seed_halfwidths does not combine with min_velocity: the grid\'s own extent bounds the slowness, '
                          'one restriction of the lag search at a time')
     return seeds
+
+
+def _check_grid_refine(grid_refine, sgrid, beam_taps, seeds):
+    """``grid_refine`` — None, a number of levels or ``(levels, step)`` — -> the ``grid_refine`` tuple of the record or None
+    (``planner.check_grid_refinement``)."""
+    if grid_refine is None:
+        return None
+    args = tuple(grid_refine) if isinstance(grid_refine, (tuple, list)) else (grid_refine,)
+    if not 1 <= len(args) <= 2:
+        raise ValueError('grid_refine must be levels or (levels, step), not %r' % (grid_refine,))
+    return planner.check_grid_refinement(args[0], args[1] if len(args) == 2 else None, sgrid, beam_taps, has_seed=seeds is not None)
 
 
 def _check_capon(nchans, capon_grid, capon_freqs, capon_snapshots, capon_loading, want_capon_maps, want_capon_csdm, W,
@@ -227,6 +243,7 @@ STEPS = (
     Step('beam_grid', 'set_beam_grid', lambda r: (r.beam_grid, r.beam_grid_map), (None,), False),
     Step('lag_seed', 'set_lag_seed', lambda r: (r.lag_seed,), (None,), False),
     Step('beam_taps', 'set_beam_interpolation', lambda r: (r.beam_taps,), (0,), False),
+    Step('grid_refine', 'set_beam_grid_refinement', lambda r: tuple(r.grid_refine), (0, None), False),
     Step('kept', 'set_kept_elements', lambda r: tuple(r.kept), (0,), True),
     Step('element_delays', 'set_element_delays', lambda r: (r.element_delays, r.element_delays_kept), (None,), True),
     Step('beam_trace', 'set_beam_trace', lambda r: (np.concatenate(r.beam_trace[0]),
@@ -291,7 +308,9 @@ class Requests:
     ``planner.element_shifts``).  ``beam_trace``: ``(windows, mdccm_min, kept)`` — one synthesis window per band, the MdCCM gate
     (NaN: off) and the kept flag of ``Handle.set_beam_trace``: the beam trace of the pass's rows behind its last solve.
     ``beam_taps`` 4, 6 or 8: beam and slowness grid are steered at fractional-sample delays with that many Lagrange taps
-    (``Handle.set_beam_interpolation``; needs ``beam`` or ``beam_grid``); 0: whole-sample delays.  ``want_lag``, ``want_cmax``,
+    (``Handle.set_beam_interpolation``; needs ``beam`` or ``beam_grid``); 0: whole-sample delays.  ``grid_refine``: ``(levels,
+    step)`` of ``Handle.set_beam_grid_refinement``: every window's grid maximum is refined between the grid points (needs
+    ``beam_grid`` and ``beam_taps``; not with ``lag_seed``).  ``want_lag``, ``want_cmax``,
     ``want_z``: nothing for the plan; the call fetches these planes (``Handle.fetch``).
 
     The per-band tables (``lag_seed``, the three of ``capon``, the windows of ``beam_trace``, ``element_delays``) have one
@@ -300,7 +319,7 @@ class Requests:
 
     DEFAULTS = dict(uncert=False, beam=False, subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False,
                     lag_seed=None, closure=False, capon=None, kept=None, capon_clean=None, capon_music=None, families=None,
-                    element_delays=None, element_delays_kept=False, beam_trace=None, beam_taps=0,
+                    element_delays=None, element_delays_kept=False, beam_trace=None, beam_taps=0, grid_refine=None,
                     want_lag=False, want_cmax=False, want_z=False)
 
     def __init__(self, **kw):
@@ -318,7 +337,7 @@ class Requests:
               want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
               capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
               capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, capon_music=None, families=None,
-              element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
+              grid_refine=None, element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
         """The opt-in keywords of ``process`` / ``process_batch`` (``KEYWORDS``) -> the record; ``ValueError`` for whatever the
         library would refuse, before any GPU work.  ``nbands`` bands of ``nchans`` elements; ``W``: the window length of every
         band, or a function that returns it (called only for a request that is checked against it); ``window_slice`` of the
@@ -395,6 +414,14 @@ class Requests:
         (``engine.label_result``) — the same arrays either way.
         beam_taps = 4, 6 or 8 (needs ``want_beam`` or ``slowness_grid``): beam and grid are steered at fractional-sample delays
         (``nbls_set_beam_interpolation``; ``planner.check_steering``).
+        grid_refine = levels or (levels, step) (needs ``slowness_grid`` and ``beam_taps``; not with ``seed_halfwidths``): also
+        ``res.grid_refined_slowness`` (.., 2) s/km, ``res.grid_refined_fstat``, ``res.grid_refined_power``,
+        ``res.grid_refined_path`` (.., levels) int32 and ``res.grid_refined_stencil`` (.., 9): per window the grid maximum
+        refined between the grid points — ``levels`` (1..12) times the best of the centre and its eight neighbours at
+        ``step`` (h0, h1) s/km (default: the grid's lattice step) halved per level —, the Fisher ratio and beam power there,
+        the candidate chosen on every level and the nine ratios of the last one; NaN and -1 where ``grid_index`` is -1
+        (``nbls_set_beam_grid_refinement``; ``planner.check_grid_refinement``).  The coarse step must not
+        exceed the width of the array's main lobe.
 
         The time-segmented path refuses every request but ``want_lag`` / ``want_cmax`` / ``want_z`` and ``families``
         (``segmented_refusal``)."""
@@ -411,6 +438,7 @@ class Requests:
         planner.check_steering(beam_taps)
         if beam_taps and not want_beam and sgrid is None:
             raise ValueError('beam_taps: fractional-sample steering needs want_beam or slowness_grid')
+        refine = _check_grid_refine(grid_refine, sgrid, beam_taps, seeds)
         kept = _check_kept(nchans, kept, want_beam, capon)
         clean = _check_capon_clean(capon_clean, capon)
         music = _check_capon_music(nchans, capon_music, capon, kept)
@@ -421,6 +449,7 @@ class Requests:
                    beam_grid=sgrid, beam_grid_map=bool(want_grid_map), lag_seed=seeds, closure=bool(want_consistency),
                    capon=capon, kept=kept, capon_clean=clean, capon_music=music, families=fam, element_delays=shifts,
                    element_delays_kept=bool(element_delays_kept), beam_trace=trace, beam_taps=beam_taps,
+                   grid_refine=refine,
                    want_lag=bool(want_lag), want_cmax=bool(want_cmax), want_z=bool(want_z))
 
     @classmethod
@@ -487,6 +516,7 @@ class Requests:
         return dict(want_lag=self.want_lag, want_cmax=self.want_cmax, want_z=self.want_z, want_uncert=self.uncert,
                     want_beam=self.beam, want_subsample=self.subsample,
                     grid_points=0 if self.beam_grid is None else len(self.beam_grid), want_grid_map=self.beam_grid_map,
+                    grid_refine_levels=0 if self.grid_refine is None else self.grid_refine[0],
                     want_consistency=self.closure, capon_points=len(capon.get('grid', ())),
                     want_capon_maps=capon.get('want_maps', False), want_capon_csdm=capon.get('want_csdm', False),
                     capon_peaks=capon.get('peaks', 0), want_kept=self.kept is not None,

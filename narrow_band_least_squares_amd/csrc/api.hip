@@ -826,6 +826,16 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
         if (!made)
             return fail(h, NBLS_ERR_ARG, "nbls_plan: a delay of the slowness grid (nbls_set_beam_grid) reaches 2^30 samples");
     }
+    int64_t rhalo = 0;               // the refinement of the grid maximum (nbls_set_beam_grid_refinement): its halo H_r
+    if (w.grid_refined()) {
+        if (w.grid.empty() || !w.steer_taps)
+            return fail(h, NBLS_ERR_STATE, "nbls_plan: the refinement of the grid maximum (nbls_set_beam_grid_refinement) needs a slowness grid (nbls_set_beam_grid) steered at fractional-sample delays (nbls_set_beam_interpolation): whole-sample F is piecewise constant");
+        if (!w.seed.empty())
+            return fail(h, NBLS_ERR_UNSUPPORTED, "nbls_plan: the refinement of the grid maximum (nbls_set_beam_grid_refinement) is not supported with a lag seed (nbls_set_lag_seed): the seed keeps the unrefined maximum");
+        rhalo = nbls_beam_grid_refine_halo_of(h->est[0].h_xij.data(), En, h->fs, ghalo, w.grid_refine.step);
+        if (rhalo < 0)
+            return fail(h, NBLS_ERR_ARG, "nbls_plan: the delay bound of the refined grid maximum (nbls_set_beam_grid_refinement) reaches 2^30 samples");
+    }
     if (!w.capon.grid.empty()) {     // Capon spectra (nbls_set_capon): the tables are made once the windows are known (plan_estimators)
         const nbls_requests::capon_request& c = w.capon;
         if (h->comm)
@@ -1007,6 +1017,7 @@ static int plan_check_args(nbls_handle* h, plan_args& a) {
     d.grid_halo = ghalo;
     d.grid_delay.swap(gdel);
     d.grid_coef.swap(gcoef);
+    d.grid_refine_halo = (int)rhalo;
     d.capon_n = (int)(w.capon.grid.size() / 2);
     d.peak_route = peak_route;
     // the slabs of the HBM route: what the option says, else as many as 256 MiB hold, 256 at least (which is 256 MiB at the
@@ -1285,6 +1296,10 @@ static int plan_estimators(nbls_handle* h, const plan_args& a) {
         if ((rc = ensure(h, h->d_grid_index, cells * sizeof(int32_t)))) return rc;
         if ((rc = ensure(h, h->d_grid_fp, 2 * cells * sizeof(double)))) return rc;
         if (h->req.grid_map() && (rc = ensure(h, h->d_grid_map, cells * (size_t)h->derived.grid_n * sizeof(double)))) return rc;
+        if (h->req.grid_refined()) {         // ... and its refinement: slowness (2), fstat, power and stencil (9) per cell, and the path
+            if ((rc = ensure(h, h->d_grid_refine_fp, 13 * cells * sizeof(double)))) return rc;
+            if ((rc = ensure(h, h->d_grid_refine_path, cells * (size_t)h->req.grid_refine.levels * sizeof(int32_t)))) return rc;
+        }
     }
     if (h->req.kept_q > 0) {             // the elements LTS kept: the mask and the count of every cell
         const size_t cells = (size_t)a.R * a.vector_len;
@@ -1963,6 +1978,42 @@ int nbls_fetch_beam_grid(nbls_handle* h, int32_t* index, double* fstat, double* 
     if ((rc = fetch_plane(h, h->grid_ran(), index, h->d_grid_index.p, sizeof(int32_t)))) return rc;
     if ((rc = fetch_plane(h, h->grid_ran(), fstat, h->d_grid_fp.p, sizeof(double)))) return rc;
     return fetch_plane(h, h->grid_ran(), power, h->d_grid_fp.p + cells, sizeof(double));
+}
+
+int nbls_set_beam_grid_refinement(nbls_handle* h, int32_t levels, const double* step) {
+    if (!h) return NBLS_ERR_ARG;
+    if (levels == 0 || !step) { h->want.grid_refine = nbls_requests::grid_refine_request(); return NBLS_OK; }   // off: the next plan does not refine
+    if (levels < 1 || levels > NBLS_BEAM_GRID_REFINE_MAX_LEVELS)
+        return fail(h, NBLS_ERR_ARG, "nbls_set_beam_grid_refinement: levels must be 0 (off) or 1.." + std::to_string(NBLS_BEAM_GRID_REFINE_MAX_LEVELS));
+    for (int k = 0; k < 2; ++k)
+        if (!(step[k] > 0.0 && step[k] < INFINITY))
+            return fail(h, NBLS_ERR_ARG, "nbls_set_beam_grid_refinement: step " + std::to_string(k) + " must be finite and > 0");
+    nbls_requests::grid_refine_request r;    // consumed by the NEXT nbls_plan; an existing plan keeps what it was made with
+    r.levels = levels;
+    r.step[0] = step[0]; r.step[1] = step[1];
+    h->want.grid_refine = r;
+    return NBLS_OK;
+}
+
+int nbls_beam_grid_refine_lds_bytes(int32_t nelem, int32_t W, int32_t halo) {
+    if (nelem < 1 || W < 1 || halo < 0) return NBLS_ERR_ARG;
+    return (int)nbls_beam_grid_refine_lds_bytes_of(nelem, W, halo);
+}
+
+int nbls_fetch_beam_grid_refined(nbls_handle* h, double* slowness, double* fstat, double* power, int32_t* path, double* stencil) {
+    if (!h) return NBLS_ERR_ARG;
+    if (!h->planned) return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_refined: no plan");
+    if (!h->req.grid_refined() || !h->d_grid_refine_fp || !h->d_grid_refine_path)
+        return fail(h, NBLS_ERR_STATE, "nbls_fetch_beam_grid_refined: nbls_set_beam_grid_refinement before nbls_plan");
+    { const int rc = finish_pass(h); if (rc) return rc; }
+    const size_t cells = (size_t)h->nbands * h->vector_len;
+    const double* fp = h->d_grid_refine_fp.p;
+    int rc;
+    if ((rc = fetch_plane(h, h->solve_ran, slowness, fp, 2 * sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, fstat, fp + 2 * cells, sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, power, fp + 3 * cells, sizeof(double)))) return rc;
+    if ((rc = fetch_plane(h, h->solve_ran, path, h->d_grid_refine_path.p, (size_t)h->req.grid_refine.levels * sizeof(int32_t)))) return rc;
+    return fetch_plane(h, h->solve_ran, stencil, fp + 4 * cells, 9 * sizeof(double));
 }
 
 int nbls_fetch_beam_grid_map(nbls_handle* h, double* map) {

@@ -130,6 +130,11 @@ struct nbls_requests {
     std::vector<double> grid;       // nbls_set_beam_grid (beam_grid.hip): [G][2] slowness vectors (empty: off)
     bool grid_keep_map = false;     // ... and whether the plan keeps every F(g)
     int steer_taps = 0;             // nbls_set_beam_interpolation (steer.h): 0 whole samples / 4 / 6 / 8 taps
+    // ---- the grid maximum refined between grid points (nbls_set_beam_grid_refinement, beam_grid_refine.hip) ----
+    struct grid_refine_request {
+        int levels = 0;                 // R (0: off, no grid_refine_kernel is launched)
+        double step[2] = {0.0, 0.0};    // (h0, h1) s/km
+    } grid_refine;
     // ---- Capon / Bartlett spectra of the narrow band's cross-spectral matrix (nbls_set_capon, capon.hip) ----
     struct capon_request {
         std::vector<double> grid;       // [G][2] slowness vectors (empty: off)
@@ -180,6 +185,7 @@ struct nbls_requests {
     bool capon_csdm() const { return !capon.grid.empty() && (capon.flags & NBLS_CAPON_CSDM); }   // ... the matrix R
     bool grid_map() const { return !grid.empty() && grid_keep_map; }
     int grid_taps() const { return grid.empty() ? 0 : steer_taps; }                     // the taps of the grid search (0: none, or whole samples)
+    bool grid_refined() const { return grid_refine.levels > 0; }                        // the grid maximum is refined behind the search
 };
 
 // What nbls_plan derives from its requests and the trace; valid with `req`.
@@ -187,6 +193,7 @@ struct nbls_plan_derived {
     int grid_n = 0, grid_halo = 0;          // G of the slowness grid (0: the plan does not search) and H = max |delay|
     std::vector<int32_t> grid_delay;        // [G][nelem] the delay table (interpolated: floor(tau))
     std::vector<double> grid_coef;          // [G][nelem][taps] the coefficient table of an interpolated grid
+    int grid_refine_halo = 0;               // H_r of a plan that refines the grid maximum: the reach of every candidate's taps
     int capon_n = 0;                        // G of the spectra (0: the plan computes none)
     int capon_maxls = 0;                    // the longest snapshot: the row length of h_capon_coef
     int peak_route = 0;                     // a peak request's route: 1 the unit's maps in LDS, 2 in HBM (its rows of d_capon_map, or a slab)
@@ -249,6 +256,10 @@ struct nbls_handle {
     dev_buf<int32_t> d_grid_index;  // [B][VL]
     dev_buf<double> d_grid_fp;      // [2][B][VL]: grid_fstat | grid_power
     dev_buf<double> d_grid_map;     // [B][VL][G] (a plan that asked for the map)
+    // ---- the grid maximum refined between grid points (beam_grid_refine.hip) ----
+    unsigned grid_refine_attr_set = 0;  // the LDS forms of grid_refine_kernel that have their dynamic LDS limit (bit taps / 2)
+    dev_buf<double> d_grid_refine_fp;   // [B][VL][2] slowness | [B][VL] fstat | [B][VL] power | [B][VL][9] stencil
+    dev_buf<int32_t> d_grid_refine_path;    // [B][VL][R]
     // ---- Capon / Bartlett spectra (capon.hip) ----
     bool capon_attr_set = false;    // capon_kernel has been given its dynamic LDS limit on this handle's device
     std::vector<int32_t> h_capon_par;   // [fbands][3]: Ls, Hs, K
@@ -503,6 +514,15 @@ bool nbls_beam_grid_delays_of(const double* xij, int nelem, double fs, const dou
 // the tables of an interpolated grid plan: n[G][nelem] = floor(tau), c[G][nelem][taps] and the halo max(|n - K + 1|, |n + K|)
 bool nbls_beam_grid_steer_of(const double* xij, int nelem, double fs, const double* grid, int G, int taps, int32_t* n, double* c,
                              int* halo);
+// the grid maximum of units [u0, u0 + nu) refined between grid points, behind nbls_launch_beam_grid on the same stream
+// (beam_grid_refine.hip)
+hipError_t nbls_launch_beam_grid_refine(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
+// dynamic LDS bytes of the form grid_refine_kernel takes for windows of W samples of nelem elements and a halo of `halo`
+// samples; 0: the global-memory form
+size_t nbls_beam_grid_refine_lds_bytes_of(int nelem, int W, int halo);
+// the halo H_r of a refining plan: grid_halo + ceil(fs max_i(|xij[i][0]| step[0] + |xij[i][1]| step[1])) + 1 over the pairs
+// (0, i); -1: it reaches 2^30
+int64_t nbls_beam_grid_refine_halo_of(const double* xij, int nelem, double fs, int grid_halo, const double* step);
 // Capon / Bartlett spectra of units [u0, u0 + nu) for the plan's full array (capon.hip)
 hipError_t nbls_launch_capon(nbls_handle* h, int64_t u0, int64_t nu, hipStream_t st);
 size_t nbls_capon_lds_bytes_of(int nelem);
@@ -523,7 +543,7 @@ void nbls_capon_neighbours_of(const int32_t* cell, int G, int32_t* nbr);
 // the snapshot coefficients coef [nbands][maxLs][2] and steering vectors steer [nbands][nelem][G][2] of a plan (host, un-fused)
 void nbls_capon_tables_of(const double* xij, int nelem, double fs, const double* grid, int G, const double* freq,
                           const int32_t* snap_len, int nbands, int maxLs, double* coef, double* steer);
-// [gather ->] solve -> [uncertainty ->] [beam ->] [closure ->] [grid search ->] [Capon ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
+// [gather ->] solve -> [uncertainty ->] [beam ->] [closure ->] [grid search [-> its refinement] ->] [Capon ->] pack of units [u0, u0 + nu) for one estimator of the handle's plan
 hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& x, int64_t u0, int64_t nu, hipStream_t st);
 // streamed results: queue the copy of the rows of units [u0, u1) into the pinned mirror behind what `producer` has queued
 hipError_t nbls_queue_result_batch(nbls_handle* h, int64_t u0, int64_t u1, hipStream_t producer);

@@ -1445,6 +1445,8 @@ hipError_t nbls_launch_solve_set(nbls_handle* h, const nbls_estimator& s, int64_
     // the slowness-grid search of a plan that asked for one (a plan with a lag seed has run it in the correlation stage,
     // ahead of the seeded correlator)
     if (own && h->derived.grid_n > 0 && r.seed.empty() && (e = nbls_launch_beam_grid(h, u0, nu, st)) != hipSuccess) return e;
+    // ... and its maximum refined between grid points, for a plan that asked (nbls_set_beam_grid_refinement; never with a seed)
+    if (own && r.grid_refined() && (e = nbls_launch_beam_grid_refine(h, u0, nu, st)) != hipSuccess) return e;
     // the Capon / Bartlett spectra of a plan that asked for them (nbls_set_capon)
     if (own && h->derived.capon_n > 0 && (e = nbls_launch_capon(h, u0, nu, st)) != hipSuccess) return e;
     // ... and the CLEAN-SC components of a plan that asked for them (nbls_set_capon_clean), on the matrices it has just written

@@ -368,29 +368,32 @@ GRID_NAMES = ('vel', 'baz', 'mdccm', 'sigma_tau')      # the four planes of ``Ba
 def new_result(nchans, alpha, fs, W, inc, nwin, vector_len, want_lag=False, want_cmax=False, want_z=False,
                want_uncert=False, want_beam=False, want_subsample=False, grid_points=0, want_grid_map=False,
                want_consistency=False, capon_points=0, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
-               want_kept=False, beam_trace_npts=0, want_element_delays=False, clean_iterations=0, want_clean_csdm=False,
-               want_music=False, want_music_maps=False, want_music_vectors=False, want_music_peaks=False):
+               want_kept=False, beam_trace_npts=0, want_element_delays=False, grid_refine_levels=0, clean_iterations=0,
+               want_clean_csdm=False, want_music=False, want_music_maps=False, want_music_vectors=False, want_music_peaks=False):
     """The zero-filled ``BandBatch`` of a call (calloc: pages a pass never writes stay untouched).  ``grids`` (4, nbands,
     vector_len) is what the drivers fill, ``vel`` ... ``sigma_tau`` are its planes; ``t``, ``sos``, ``pair_idx``, ``xij`` and
     ``handle`` are the driver's to set.  The keywords are what ``Requests.result_keywords`` makes of a call's requests; the
     fields they bring are the rows of ``call_requests.RESULT_GROUPS`` and ``EXTRA_FIELDS`` that apply, each (nbands,
-    vector_len) + its trailing shape with N = ``nchans``, P pairs, G = ``grid_points``, C = ``capon_points``, K =
-    ``capon_peaks``, I = ``clean_iterations`` and T = ``beam_trace_npts`` (``beam_trace``: (nbands, T)); None otherwise
+    vector_len) + its trailing shape with N = ``nchans``, P pairs, G = ``grid_points``, R = ``grid_refine_levels``, C =
+    ``capon_points``, K = ``capon_peaks``, I = ``clean_iterations`` and T = ``beam_trace_npts`` (``beam_trace``: (nbands, T)); None otherwise —
+    the fields of a ``sparse`` group are attributes of the result only where the group applies
     (``Requests.check`` says what each is)."""
     want = types.SimpleNamespace(**locals())
     nb, P = len(nwin), nchans * (nchans - 1) // 2
-    size = dict(N=nchans, P=P, G=grid_points, C=capon_points, K=capon_peaks, I=clean_iterations, T=beam_trace_npts)
+    size = dict(N=nchans, P=P, G=grid_points, R=grid_refine_levels, C=capon_points, K=capon_peaks, I=clean_iterations,
+                T=beam_trace_npts)
     fields = {}
 
-    def allocate(on, rows, group):
+    def allocate(on, rows, group, sparse=False):
         for name, trailing, dtype in group:
-            fields[name] = np.zeros(rows + tuple(int(size.get(n, n)) for n in trailing), dtype=dtype) if on else None
+            if on or not sparse:
+                fields[name] = np.zeros(rows + tuple(int(size.get(n, n)) for n in trailing), dtype=dtype) if on else None
 
     for name, trailing, dtype in EXTRA_FIELDS:
         allocate(getattr(want, 'want_' + name), (nb, vector_len), [(name, trailing, dtype)])
     for g in RESULT_GROUPS:
         for _, group in g.calls:
-            allocate(g.applies(want), (nb,) if g.per_row else (nb, vector_len), group)
+            allocate(g.applies(want), (nb,) if g.per_row else (nb, vector_len), group, g.sparse)
     grids = np.zeros((4, nb, vector_len))
     return BandBatch(grids=grids, nwin=nwin.astype(int), t=None, mask=np.zeros((nb, vector_len, (P + 7) // 8), dtype=np.uint8),
                      sos=[], W=W, inc=inc, pair_idx=None, xij=None, nchans=nchans, alpha=alpha, handle=None, lts=alpha < 1.0,
@@ -582,7 +585,7 @@ def upload_trace(h, data, fs):
 def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl=0, reserve_bytes=0, trace_from=None,
            trace_ready=False, after=None, before_execute=None, stream=False, requests=None, uncert=False, estimators=None,
            beam=False, subsample=False, lag_limits=None, beam_grid=None, beam_grid_map=False, lag_seed=None, closure=False,
-           capon=None, kept=None, capon_clean=None, capon_music=None, families=None, element_delays=None,
+           capon=None, kept=None, capon_clean=None, capon_music=None, families=None, grid_refine=None, element_delays=None,
            element_delays_kept=False, beam_trace=None, beam_taps=0):
     """Upload (optional), plan and start the pass for the band subset ``bands`` (indices into the Prep;
     None = all) on handle ``h``.  Returns as soon as the kernels are queued.  ``trace_from``: another handle of
@@ -598,7 +601,7 @@ def launch(h, data, prep, bands=None, upload=True, window_slice=None, xcorr_impl
         uncert=uncert, beam=beam, subsample=subsample, lag_limits=lag_limits, beam_grid=beam_grid, beam_grid_map=beam_grid_map,
         lag_seed=lag_seed, closure=closure, capon=capon, kept=kept, capon_clean=capon_clean, capon_music=capon_music,
         families=families, element_delays=element_delays, element_delays_kept=element_delays_kept, beam_trace=beam_trace,
-        beam_taps=beam_taps)
+        beam_taps=beam_taps, grid_refine=grid_refine)
     if upload:
         if trace_ready:
             pass
@@ -861,7 +864,7 @@ def process(data, fs, t0_datenum, rij, band_edges, winlens, winover, alpha, filt
             want_grid_map=False, seed_halfwidths=None, want_consistency=False, capon_grid=None, capon_freqs=None,
             capon_snapshots=None, capon_loading=0.01, want_capon_maps=False, want_capon_csdm=False, capon_peaks=0,
             capon_peak_floor=0.25, capon_cells=None, kept=None, capon_clean=None, capon_music=None, families=None,
-            element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
+            grid_refine=None, element_max_shift=None, element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """Run the hot path for a list of bands on one GPU -> ``BandBatch``.
 
     data (N, npts) raw traces — a 2-D array or a list of N rows (uploaded from where they lie);
@@ -1143,7 +1146,7 @@ def process_batch(recordings, fs, t0s, rij, band_edges, winlens, winover, alpha,
                   want_subsample=False, min_velocity=None, slowness_grid=None, want_grid_map=False, seed_halfwidths=None,
                   want_consistency=False, capon_grid=None, capon_freqs=None, capon_snapshots=None, capon_loading=0.01,
                   want_capon_maps=False, want_capon_csdm=False, capon_peaks=0, capon_peak_floor=0.25, capon_cells=None,
-                  kept=None, capon_clean=None, capon_music=None, families=None, element_max_shift=None,
+                  kept=None, capon_clean=None, capon_music=None, families=None, grid_refine=None, element_max_shift=None,
                   element_delays_kept=False, want_beam_trace=None, beam_taps=0):
     """``process`` for S recordings of ONE array (``recordings[s]``: the N rows of recording s, all of one length and
     rate, one geometry ``rij``) in one device pass -> a list of S ``BandBatch``, element s what ``process`` gives for

@@ -79,6 +79,28 @@ def _returns_grid(res, grid, want_map):
     return out + ((res.grid_map[0, :n].copy(),) if want_map else ())
 
 
+def refined_slowness(slowness, index):
+    """The refined slowness vectors ``slowness`` (..., 2) of a grid search with refinement -> (refined_vel, refined_baz) by
+    the formula of ``grid_slowness``; both NaN where the grid index is -1."""
+    s = np.asarray(slowness, dtype=np.float64)
+    none = np.asarray(index) < 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        vel = 1.0 / np.hypot(s[..., 0], s[..., 1])
+        baz = np.mod(np.arctan2(s[..., 0], s[..., 1]) * 180.0 / np.pi - 360.0, 360.0)
+    return np.where(none, np.nan, vel), np.where(none, np.nan, baz)
+
+
+REFINED_FIELDS = ('grid_refined_slowness', 'grid_refined_fstat', 'grid_refined_power', 'grid_refined_path', 'grid_refined_stencil')
+
+
+def _returns_grid_refined(res):
+    """The band's refined grid maximum behind ``_returns_grid``: ``refined_vel, refined_baz`` (``refined_slowness``) and the five
+    fields of the refinement (csrc/beam_grid_refine.hip: grid_refine_kernel)."""
+    n = int(res.nwin[0])
+    slow = res.grid_refined_slowness[0, :n].copy()
+    return refined_slowness(slow, res.grid_index[0, :n]) + (slow,) + tuple(getattr(res, k)[0, :n].copy() for k in REFINED_FIELDS[1:])
+
+
 def _picker(band, n):
     """How the ``_returns_*`` dictionaries take a field of a ``BandBatch``: a copy of row ``band``, its first ``n`` cells or
     (``n=None``) all of them; ``band=None``: the array itself, every band's rows."""
@@ -573,6 +595,45 @@ def ltsva_steered(st, lat_list, lon_list, window_length, window_overlap, alpha=1
     Whatever the library would refuse raises ``ValueError`` before any GPU work."""
     return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij,
                   _steered(taps, slowness_grid, grid_map, subsample, kept, min_pairs))
+
+
+def _grid_refined(slowness_grid, levels, step, taps, grid_map):
+    """The feature behind the arguments of ``ltsva_grid_refined``."""
+    def keywords(nchans, alpha, rij, fs, npts):
+        grid = planner.check_slowness_grid(slowness_grid)
+        _check_flag('grid_map', grid_map)
+        checked = planner.check_steering(taps)
+        refine = planner.check_grid_refinement(levels, step, grid, checked)
+        return dict(slowness_grid=grid, want_grid_map=bool(grid_map), beam_taps=checked, grid_refine=refine)
+
+    def tail(res, kw, nchans, fs, t0):
+        return _returns_grid(res, kw['slowness_grid'], kw['want_grid_map']) + _returns_grid_refined(res)
+    return _Feature(keywords, tail)
+
+
+def ltsva_grid_refined(st, lat_list, lon_list, window_length, window_overlap, slowness_grid, alpha=1.0, rij=None, levels=4,
+                       step=None, taps=8, grid_map=False):
+    """``ltsva_grid`` steered at fractional-sample delays (``ltsva_steered``: ``taps`` 4, 6 or 8) with the maximum refined
+    between the grid points: from the window's grid maximum, ``levels`` (1..12) times, the best of the centre and its eight
+    neighbours at ``step`` (h0, h1) s/km halved per level — by default the lattice step of ``slowness_grid``
+    (``planner.grid_cells``) — becomes the new centre (DESIGN.md section 28 has the definition and the counts).  A coarse
+    grid then finds the lobe and the search climbs it: a tenth to a quarter of the evaluations of a fine grid and a continuous
+    slowness.  The coarse step must not exceed the width of the array's main lobe, or the grid misses it.  Returns
+    ``ltsva_grid``'s tuple followed by ``refined_vel``, ``refined_baz`` (the formula of ``grid_slowness``),
+    ``refined_slowness`` (nwin, 2) s/km, ``refined_fstat`` (never below ``grid_fstat``), ``refined_power``, ``refined_path``
+    (nwin, levels) int32 — the candidate 0..8 chosen on every level, 4 the centre — and ``refined_stencil`` (nwin, 9), the
+    nine ratios of the last level; NaN (-1 in the path) where ``grid_index`` is -1.  Computed on the GPU behind each window's
+    grid search (csrc/beam_grid_refine.hip).  Whatever the library would refuse raises ``ValueError`` before any GPU work."""
+    return _ltsva(st, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                  _grid_refined(slowness_grid, levels, step, taps, grid_map))
+
+
+def ltsva_grid_refined_batch(streams, lat_list, lon_list, window_length, window_overlap, slowness_grid, alpha=1.0, rij=None,
+                             levels=4, step=None, taps=8, grid_map=False):
+    """``ltsva_grid_refined`` over several (already filtered) recordings of ONE array in one GPU pass -> a list of its tuples,
+    element i equal to ``ltsva_grid_refined(streams[i], ...)`` bit for bit; the streams as for ``ltsva_batch``."""
+    return _ltsva_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha, rij,
+                        _grid_refined(slowness_grid, levels, step, taps, grid_map))
 
 
 def ltsva_steered_batch(streams, lat_list, lon_list, window_length, window_overlap, alpha=1.0, rij=None, taps=8,

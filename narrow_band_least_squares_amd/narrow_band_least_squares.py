@@ -16,7 +16,7 @@ from scipy import signal
 from . import dist, engine, planner
 from .helpers import get_rij
 from .lts_array import grid_slowness, _returns_capon, _peak_keywords, _returns_kept, _returns_clean, _returns_music, _check_flag, \
-    _check_elements_strict, _check_clean_sources, _kept_request
+    _check_elements_strict, _check_clean_sources, _kept_request, refined_slowness
 
 
 def _vector_len(WINLEN_list, WINOVER, st):
@@ -297,6 +297,37 @@ def narrow_band_least_squares_grid(WINLEN_list, WINOVER, ALPHA, st, lat_list, lo
     return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
                       FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij, tail=lambda res: _returns_grid(res, grid, grid_map), slowness_grid=grid,
                       want_grid_map=bool(grid_map))
+
+
+def _returns_grid_refined(res):
+    """The refined returns of ``narrow_band_least_squares_grid_refined``: the slowness at the refined maximum as velocity and
+    back-azimuth (zero-padded like ``vel_array``) and the five fields of the refinement."""
+    computed = _computed(res)
+    rvel, rbaz = (np.where(computed, a, 0.0) for a in refined_slowness(res.grid_refined_slowness, res.grid_index))
+    return (rvel, rbaz, res.grid_refined_slowness, res.grid_refined_fstat, res.grid_refined_power, res.grid_refined_path,
+            res.grid_refined_stencil)
+
+
+def narrow_band_least_squares_grid_refined(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,
+                                           FREQ_BAND_TYPE, freq_resp_list, FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij=None, *,
+                                           slowness_grid, levels=4, step=None, taps=8, grid_map=False):
+    """``narrow_band_least_squares_grid`` steered at fractional-sample delays (``taps`` 4, 6 or 8) with every window's grid
+    maximum refined between the grid points (``lts_array.ltsva_grid_refined``): from the maximum,
+    ``levels`` (1..12) times, the best of the centre and its eight neighbours at ``step`` (h0, h1) s/km halved per level —
+    by default the lattice step of ``slowness_grid`` — becomes the new centre.  Returns
+    ``narrow_band_least_squares_grid``'s tuple followed by ``refined_vel_array`` and ``refined_baz_array`` (zero-padded like
+    ``vel_array``), ``refined_slowness_array`` (NBANDS, vector_len, 2), ``refined_fstat_array``, ``refined_power_array``,
+    ``refined_path_array`` (NBANDS, vector_len, levels) int32 and ``refined_stencil_array`` (NBANDS, vector_len, 9).  The
+    coarse step must not exceed the width of the array's main lobe.  Whatever the library would refuse raises ``ValueError``
+    before any GPU work, and so does a trace so long that not one filtered band fits the HBM budget of a pass."""
+    grid = planner.check_slowness_grid(slowness_grid)
+    _check_flag('grid_map', grid_map)
+    taps = planner.check_steering(taps)
+    refine = planner.check_grid_refinement(levels, step, grid, taps)
+    return _all_bands(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist, FREQ_BAND_TYPE, freq_resp_list,
+                      FILTER_TYPE, FILTER_ORDER, FILTER_RIPPLE, rij,
+                      tail=lambda res: _returns_grid(res, grid, grid_map) + _returns_grid_refined(res), slowness_grid=grid,
+                      want_grid_map=bool(grid_map), beam_taps=taps, keywords=lambda *_: dict(grid_refine=refine))
 
 
 def narrow_band_least_squares_steered(WINLEN_list, WINOVER, ALPHA, st, lat_list, lon_list, NBANDS, w, h, freqlist,

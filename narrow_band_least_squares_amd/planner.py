@@ -724,6 +724,40 @@ def grid_cells(grid):
     return np.ascontiguousarray(cells, dtype=np.int32), steps
 
 
+MAX_GRID_REFINE_LEVELS = 12      # NBLS_BEAM_GRID_REFINE_MAX_LEVELS
+
+
+def check_grid_refinement(levels, step, grid, taps, has_seed=False):
+    """Everything ``nbls_set_beam_grid_refinement`` and the plan behind it refuse, as ``ValueError`` before any GPU work ->
+    (levels int, step float64 (2,)).  ``levels``: an integer in 1..12; ``step``: (h0, h1) s/km, finite and > 0, or None: the
+    lattice step of ``grid`` (``grid_cells(grid)[1]``; ``ValueError`` where an axis of the grid has a single value); ``grid``:
+    the slowness grid of the call (None: there is none); ``taps``: its steering, which must be 4, 6 or 8 — the whole-sample
+    F is piecewise constant in the slowness —; ``has_seed``: the call seeds its lag search by the grid maximum, which does not
+    combine."""
+    if isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)) or not (1 <= int(levels) <= MAX_GRID_REFINE_LEVELS):
+        raise ValueError('the refinement levels must be an integer in 1..%d, not %r' % (MAX_GRID_REFINE_LEVELS, levels))
+    if grid is None:
+        raise ValueError('the refinement of the grid maximum needs slowness_grid')
+    if check_steering(taps) == 0:
+        raise ValueError('the refinement of the grid maximum needs fractional-sample steering (taps 4, 6 or 8): with whole-sample '
+                         'delays F is piecewise constant in the slowness')
+    if has_seed:
+        raise ValueError('the refinement of the grid maximum does not combine with the seeded lag search: the seed keeps the '
+                         'unrefined maximum')
+    if step is None:
+        step = grid_cells(grid)[1]
+        if not np.all(step > 0.0):
+            raise ValueError('slowness_grid has a single value on axis %d: it has no lattice step there, give step=(h0, h1)'
+                             % int(np.argmin(step)))
+    try:
+        s = np.array(step, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('the refinement step must be two numbers (h0, h1) in s/km, not %r' % (step,))
+    if s.shape != (2,) or not np.all(np.isfinite(s)) or not np.all(s > 0.0):
+        raise ValueError('the refinement step must be two finite numbers > 0 (h0, h1) in s/km, not %r' % (step,))
+    return int(levels), s
+
+
 def check_capon_peaks(grid_len, cells, K, floor):
     """Everything ``nbls_set_capon_peaks`` and the plan behind it refuse, as ``ValueError`` before any GPU work -> (cells int32
     (G, 2), K int, floor float).  ``grid_len``: the G of the Capon spectra the request goes with."""
